@@ -16,15 +16,27 @@ batches are in flight and one worker's serial rANS chains run beside another wor
 synchronize on both sides and holds exactly K steps; `config.call_latency_ms` is the wall time of one
 compress+decompress call of one worker.
 
-`value` is measured with the input batch resident in HBM (the tier's contract); `pcie_inclusive` repeats the run with
-the batch in page-locked host memory, uploaded INSIDE compress() as the reference's timed region does
-(general_codec.py:46-47 under basic_benchmark.py:199-202).  `scaling` is "weak" (--batch images per GPU at every N);
-at N > 1 the same run also times BASELINE configs[4] as written (256 images over N GPUs) and reports it as `strong`.
+`value` is measured with the input batch resident in HBM (the tier's contract).  A plain run sets up, probes the worker
+count, warms up, times the K steps, writes the last step's outputs when --dump-outputs DIR is given, and prints one JSON
+line on rank 0 (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step).
 
-One JSON line on rank 0, with
+--full adds everything else to the same line:
+  pcie_inclusive       -- the run repeated with the batch in page-locked host memory, uploaded INSIDE compress() as the
+                          reference's timed region does (general_codec.py:46-47 under basic_benchmark.py:199-202)
+  strong               -- at N > 1, BASELINE configs[4] as written (256 images over N GPUs); `scaling` is "weak" (--batch
+                          images per GPU at every N)
+  strong_per_gpu_proxy, ar_workloads -- one GPU's share of the strong leg and the AR parity configurations (child processes)
+  config.bytes_match_single_stream, config.gathered_* -- the last step against one quiet single-stream call; per-image
+                          (bytes, PSNR) gathered over the ranks
   roofline     -- MFMA transform kernels: algorithmic FLOPs / HIP-event time of the transform launches vs 157.3 TF fp32,
                   plus `end_to_end` = FLOPs of a step / wall time of a step (everything included)
   cpu_baseline -- the CPU oracle (PyTorch-CPU fp32 convs + C rANS restatement) on a bounded sample of the SAME images
+(--no-extra-legs, --no-ar-workloads, --no-dominant and --no-cpu-baseline leave parts of it out again.)  `--workload
+checkerboard|basic` is not the headline: it prints the whole line of one AR parity configuration, as --full's ar_workloads
+runs it.
+
+--dump-outputs DIR: what compress() / decompress() returned in the last timed step, as float32 .npy files (see
+dump_outputs()); the inputs depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -66,6 +78,12 @@ def parse():
     ap.add_argument("--input", default="hbm", choices=["hbm", "host"],
                     help="where the batch lives when the timed region starts: hbm = resident (the tier's contract for `value`), "
                          "host = page-locked host memory, uploaded inside compress() (profiling the pcie_inclusive leg on its own)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs, the AR workload lines, the single-stream check, the roofline passes and the CPU baseline "
+                         "(a plain run only times the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step (compressed bytes, reconstruction) as float32 .npy files "
+                         "under DIR, at most 64 MB in all (rank 0's images at N > 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the pcie_inclusive and strong-scaling legs (profiling runs)")
     ap.add_argument("--no-dominant", action="store_true", help="skip the single-launch roofline (counter passes: keeps the launch mix = timed passes)")
@@ -97,6 +115,40 @@ def image(i, size):
     import torch
     torch.manual_seed(int(i))
     return torch.rand(3, size, size)
+
+
+DUMP_BUDGET = 64 * 10 ** 6   # bytes of all files --dump-outputs writes (64 MB)
+
+
+def dump_outputs(out_dir, data, xhat, seed=0):
+    """--dump-outputs DIR: the last timed step's outputs as float32 .npy files, DUMP_BUDGET bytes at most in all.
+      compressed.npy      -- the bytes compress() returned, one value 0..255 per byte (up to a quarter of the budget)
+      reconstruction.npy  -- the images decompress() returned, [n, 3, H, W] (the rest of the budget)
+    An output larger than its share is written as a fixed sample instead: the values at positions drawn without
+    replacement by numpy's default_rng(seed), in increasing order, flattened, and the positions in <name>_index.npy
+    (float64).  Returns {file name: bytes written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    written = {}
+
+    def save(name, a):
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        written[name + ".npy"] = os.path.getsize(path)
+
+    def put(name, values, share):
+        values = np.asarray(values, dtype=np.float32)
+        if values.nbytes + 128 > share:   # 128: the .npy header
+            n = max(0, (share - 256) // 12)   # 4 bytes of value + 8 of position each
+            pos = np.sort(rng.choice(values.size, size=min(n, values.size), replace=False))
+            save(name + "_index", pos.astype(np.float64))
+            values = values.reshape(-1)[pos]
+        save(name, values)
+
+    put("compressed", np.frombuffer(bytes(data), dtype=np.uint8), DUMP_BUDGET // 4)
+    put("reconstruction", xhat.detach().float().cpu().numpy(), DUMP_BUDGET - sum(written.values()))
+    return written
 
 
 def conv_flops_per_image(codec, size):
@@ -352,6 +404,8 @@ def run_ar_workload(args):
                               bytes_match_single_stream=same)
         if data is None:
             data, xhat, dt = d_l, xh_l, dt_l
+            if args.dump_outputs:   # the line's value is this level's
+                dump_outputs(args.dump_outputs, data, xhat)
     pool.close()
     if levels[0] is not None:
         codec.set_complex_level(levels[0])
@@ -533,7 +587,7 @@ def strong_proxy_child(args):
     sb, sw, lanes = max(1, args.total // 8), max(2, args.strong_workers), 4
     steps = max(8 * args.steps, 4 * sw)
     cmd = [sys.executable, os.path.abspath(__file__), "--batch", str(sb), "--token-lanes", str(lanes), "--steps", str(steps),
-           "--warmup", str(sw), "--size", str(args.size), "--no-cpu-baseline", "--no-extra-legs", "--no-dominant"]   # (no --workers: probed, 4 / 5 / 6)
+           "--warmup", str(sw), "--size", str(args.size), "--full", "--no-cpu-baseline", "--no-extra-legs", "--no-dominant"]   # (no --workers: probed, 4 / 5 / 6)
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -557,7 +611,8 @@ def main():
             raise SystemExit("the AR workloads are single-GPU extra lines")
         return run_ar_workload(args)
     ar_lines = strong_proxy = None
-    if args.gpus == 1 and os.environ.get("WORLD_SIZE") is None and not args.no_extra_legs:   # before anything here initialises the GPU
+    extra_legs = args.full and not args.no_extra_legs
+    if args.gpus == 1 and os.environ.get("WORLD_SIZE") is None and extra_legs:   # before anything here initialises the GPU
         if not args.no_ar_workloads:
             ar_lines = ar_workload_children(args)
         if args.batch == args.total:   # the headline configuration: add its strong-scaling share
@@ -667,7 +722,7 @@ def main():
     strong_w = max(workers, args.strong_workers) if (by_steps and (world > 1 or args.strong_in_process)) else workers
     pool = StreamWorkerPool(make_codec, strong_w, dev)
     codec = pool.codecs[0]
-    cpu_state = {k: v.detach().cpu().clone() for k, v in codec.entropy_coder.state_dict().items()}
+    cpu_state = {k: v.detach().cpu().clone() for k, v in codec.entropy_coder.state_dict().items()} if args.full else None
 
     def strong_leg():
         ids = shard_indices(args.total, rank, world) if world > 1 else list(range(max(1, args.total // 8)))
@@ -713,30 +768,37 @@ def main():
         run_workers[0], run_lanes[0] = workers, token_lanes
     strong_first = args.strong_first or world > 1
     strong_first_result = None
-    if (world > 1 or args.strong_in_process) and strong_first and not args.no_extra_legs:
+    if (world > 1 or args.strong_in_process) and strong_first and extra_legs:
         strong_first_result = strong_leg()
     dt, step_bytes, last, call_s = run_leg(pool, x if args.input == "hbm" else x_host, args.steps, args.warmup)
 
-    # per-image (bytes, PSNR) of the last step, gathered over xGMI into image order: not part of the timed region
+    # PSNR of the last step's images: not part of the timed region
     xhat = torch.cat([xh for _, xh in last])
     psnr_img = -10 * torch.log10(K.mse_per_image(xhat, x).double())
-    img_bytes = []
-    for data, _ in last:
-        zb, yb = split_merged_bytes(data, num_segments=2)
-        (_, zo, _), (_, yo, _) = K.unframe_streams(zb), K.unframe_streams(yb)
-        img_bytes.append(4.0 * (np.diff(zo) + np.diff(yo)) + 8.0)
-    img_bytes = torch.from_numpy(np.concatenate(img_bytes)).to(dev)
-    table = torch.stack([img_bytes.double(), psnr_img.to(dev)], dim=1)
-    if dist is not None and world > 1:   # contiguous shards per rank -> concatenation in rank order is image order
-        bufs = [torch.empty_like(table) for _ in range(world)]
-        dist.all_gather(bufs, table)
-        table = torch.cat(bufs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, b"".join(d for d, _ in last), xhat)
+    gathered = None
+    if args.full:   # per-image (bytes, PSNR) of the last step, gathered over xGMI into image order
+        img_bytes = []
+        for data, _ in last:
+            zb, yb = split_merged_bytes(data, num_segments=2)
+            (_, zo, _), (_, yo, _) = K.unframe_streams(zb), K.unframe_streams(yb)
+            img_bytes.append(4.0 * (np.diff(zo) + np.diff(yo)) + 8.0)
+        img_bytes = torch.from_numpy(np.concatenate(img_bytes)).to(dev)
+        table = torch.stack([img_bytes.double(), psnr_img.to(dev)], dim=1)
+        if dist is not None and world > 1:   # contiguous shards per rank -> concatenation in rank order is image order
+            bufs = [torch.empty_like(table) for _ in range(world)]
+            dist.all_gather(bufs, table)
+            table = torch.cat(bufs)
+        gathered = dict(gathered_images=int(table.shape[0]),
+                        gathered_bpp=float(table[:, 0].sum()) * 8 / (table.shape[0] * args.size * args.size),
+                        gathered_psnr_db=float(table[:, 1].mean()))
     # the ONLY collective of a leg: metric sums (analogue of cbench/utils/logging_utils.py:458-465)
     red = reduce_metric_sums(dict(time_s=dt, images=float(args.batch * args.steps), bytes=float(step_bytes * args.steps),
                                   psnr_sum=float(psnr_img.sum()), psnr_n=float(args.batch)), device=dev)
 
     extra = {}
-    if not args.no_extra_legs:
+    if extra_legs:
         # (1) input in page-locked HOST memory, uploaded inside compress() (the reference's timed region)
         if not os.environ.get("BENCH_SKIP_PCIE"):
             hdt, _, _, _ = run_leg(pool, x_host, args.steps, 1)
@@ -754,7 +816,7 @@ def main():
     # ---- the timed schedule against ONE quiet call on this rank's idle GPU (no workers, no token, default rANS packing): the last
     # step's bytes and reconstruction must be identical, or the run fails -- the overlapped schedule is what was timed
     bytes_match = None
-    if by_steps and args.input == "hbm":
+    if args.full and by_steps and args.input == "hbm":
         codec.entropy_coder.fused_transform_token = 0
         codec.entropy_coder.fused_rans_waves = 0
         quiet = codec.compress(x)
@@ -768,14 +830,7 @@ def main():
     if rank == 0:
         dt_max, n_img, n_bytes = red["time_s"], red["images"], red["bytes"]
         pix = n_img * args.size * args.size
-        enc_f, dec_f = conv_flops_per_image(codec, args.size)
-        codec.entropy_coder.fused_transform_token = False
-        conv_s, launches = measure_conv_kernels(codec, x)
-        flops_pass = (enc_f + dec_f) * args.batch
-        achieved = flops_pass / conv_s / 1e12
         ms_step = dt_max / args.steps * 1e3
-        e2e = flops_pass / (ms_step / 1e3) / 1e12
-        traffic, traffic_source = traffic_from_profiles()
         out = dict(
             metric="encode+decode Mpix/s", value=pix / dt_max / 1e6, unit="Mpix/s", n_gpus=world, steps=args.steps,
             warmup=args.warmup, ms_per_step=ms_step, higher_is_better=True, scaling="weak",
@@ -791,19 +846,26 @@ def main():
                         shard_by=args.shard_by if workers > 1 else None, batches_in_flight=workers if by_steps else 1,
                         call_latency_ms=call_s * 1e3, bytes_match_single_stream=bytes_match,
                         bpp=n_bytes * 8 / pix, psnr_db=red["psnr_sum"] / red["psnr_n"],
-                        gathered_images=int(table.shape[0]),
-                        gathered_bpp=float(table[:, 0].sum()) * 8 / (table.shape[0] * args.size * args.size),
-                        gathered_psnr_db=float(table[:, 1].mean()),
-                        parallelism=f"image-sharded x{world}, RCCL all-reduce of metric sums + all-gather of per-image (bytes, PSNR)"),
-            roofline=dict(bound="mfma", achieved=achieved, peak=PEAK_FP32_MFMA_TFLOPS, unit="TFLOP/s",
-                          frac=achieved / PEAK_FP32_MFMA_TFLOPS, traffic=traffic, traffic_source=traffic_source,
-                          kernel="conv_tap_mfma_kernel<MT,CK,KH,KW,WAVES> + first/last-layer kernels (the transform launches of one encode+decode pass, alone on the GPU)",
-                          flops_per_launch=flops_pass / launches, launches_per_pass=launches,
-                          avg_launch_ms=conv_s / launches * 1e3, pass_ms=conv_s * 1e3,
-                          end_to_end=dict(achieved=e2e, frac=e2e / PEAK_FP32_MFMA_TFLOPS,
-                                          note="transform FLOPs of a step / wall time of a step (rANS chains, hyper path, copies, host included)"),
-                          dominant=None if args.no_dominant else measure_dominant_kernel(codec, x)),
+                        **(gathered or {}),
+                        parallelism=f"image-sharded x{world}, RCCL all-reduce of metric sums"
+                                    + (" + all-gather of per-image (bytes, PSNR)" if gathered is not None else "")),
         )
+        if args.full:   # the transform launches alone on the GPU: passes of their own
+            enc_f, dec_f = conv_flops_per_image(codec, args.size)
+            codec.entropy_coder.fused_transform_token = False
+            conv_s, launches = measure_conv_kernels(codec, x)
+            flops_pass = (enc_f + dec_f) * args.batch
+            achieved = flops_pass / conv_s / 1e12
+            e2e = flops_pass / (ms_step / 1e3) / 1e12
+            traffic, traffic_source = traffic_from_profiles()
+            out["roofline"] = dict(bound="mfma", achieved=achieved, peak=PEAK_FP32_MFMA_TFLOPS, unit="TFLOP/s",
+                                   frac=achieved / PEAK_FP32_MFMA_TFLOPS, traffic=traffic, traffic_source=traffic_source,
+                                   kernel="conv_tap_mfma_kernel<MT,CK,KH,KW,WAVES> + first/last-layer kernels (the transform launches of one encode+decode pass, alone on the GPU)",
+                                   flops_per_launch=flops_pass / launches, launches_per_pass=launches,
+                                   avg_launch_ms=conv_s / launches * 1e3, pass_ms=conv_s * 1e3,
+                                   end_to_end=dict(achieved=e2e, frac=e2e / PEAK_FP32_MFMA_TFLOPS,
+                                                   note="transform FLOPs of a step / wall time of a step (rANS chains, hyper path, copies, host included)"),
+                                   dominant=None if args.no_dominant else measure_dominant_kernel(codec, x))
         out.update(extra)
         out["value_per_gpu"] = out["value"] / world
         if "strong" in extra and "value" in extra["strong"]:   # BASELINE configs[4] as written, beside the weak figure
@@ -816,7 +878,7 @@ def main():
             out["strong_per_gpu_proxy"] = strong_proxy
         if ar_lines is not None:
             out["ar_workloads"] = ar_lines
-        if not args.no_cpu_baseline and world == 1:  # reported at N = 1 only; at N > 1 the other ranks would just wait for it
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N = 1 only; at N > 1 the other ranks would just wait for it
             out["cpu_baseline"] = cpu_baseline(cpu_state, args.cpu_images, args.size)
         print(json.dumps(out))
     if dist is not None:

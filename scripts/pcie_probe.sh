@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/pcie
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --memory-copy-trace --stats -d $O/trace -o t --output-format csv -- python3 $R/bench.py --input host --no-cpu-baseline --no-extra-legs --no-dominant > $O/bench.log 2>&1
+rocprofv3 --kernel-trace --memory-copy-trace --stats -d $O/trace -o t --output-format csv -- python3 $R/bench.py --input host --full --no-cpu-baseline --no-extra-legs --no-dominant > $O/bench.log 2>&1
 tail -1 $O/bench.log | cut -c1-300
 ls $O/trace/*
 python3 - <<PY

@@ -23,7 +23,7 @@ def main():
                     continue
                 acc[name][r["Counter_Name"]] += float(r["Counter_Value"])
                 launches[name][r["Counter_Name"]] += 1
-    doc = dict(command="rocprofv3 --kernel-trace --pmc <counters> (separate passes) -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-dominant",
+    doc = dict(command="rocprofv3 --kernel-trace --pmc <counters> (separate passes) -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-dominant",
                note="sums over all launches of a kernel in the run; mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (4 SIMDs x SQ_BUSY_CYCLES-or-GRBM_GUI_ACTIVE x CUs "
                     "as reported by the tool's own MfmaUtil expression when that derived metric was collected); lds_conflict = "
                     "SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE",

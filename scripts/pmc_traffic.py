@@ -41,7 +41,7 @@ def main():
     raw = sum(v["kib_total"] for v in fs.values()) + sum(v["kib_total"] for v in ws.values())
     kib = sum(v["kib_corrected"] for v in fs.values()) + sum(v["kib_total"] for v in ws.values())
     doc = dict(
-        command="rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE (separate passes) -- python3 bench.py --workers 1 --steps 2 --warmup 1 --no-cpu-baseline --no-dominant --no-extra-legs",
+        command="rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE (separate passes) -- python3 bench.py --workers 1 --steps 2 --warmup 1 --full --no-cpu-baseline --no-dominant --no-extra-legs",
         git=git,
         note="FETCH_SIZE x2 for every kernel (calibrated: profiles/r02_fetch_calibration.txt); WRITE_SIZE as reported; FETCH counts L2 -> fabric requests, Infinity-Cache hits included",
         per_kernel=dict(FETCH_SIZE=fs, WRITE_SIZE=ws), transform_launches=launches,

@@ -5,9 +5,9 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r02prof
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B1="--workers 1 --steps 2 --warmup 1 --no-cpu-baseline --no-dominant --no-extra-legs"
+B1="--workers 1 --steps 2 --warmup 1 --full --no-cpu-baseline --no-dominant --no-extra-legs"
 # 1. kernel trace + stats of the default bench (3 stream workers, whole batches in flight): per-kernel totals and the overlap timeline
-rocprofv3 --kernel-trace --stats -d $O/trace -o bench --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-extra-legs > $O/bench_trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/trace -o bench --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-extra-legs > $O/bench_trace.log 2>&1
 (cd $R && python scripts/prof_summary.py gpurun_out/r02prof/trace 24 > gpurun_out/r02prof/bench_summary.txt && python scripts/timeline.py gpurun_out/r02prof/trace 60 > gpurun_out/r02prof/bench_timeline.txt)
 cp $(find $O/trace -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv
 echo trace done

@@ -5,11 +5,11 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r04prof
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B1="--workers 1 --steps 2 --warmup 1 --no-cpu-baseline --no-dominant --no-extra-legs"
+B1="--workers 1 --steps 2 --warmup 1 --full --no-cpu-baseline --no-dominant --no-extra-legs"
 AR="--workers 1 --steps 1 --warmup 1 --levels 0 --no-kodak-leg --no-cpu-baseline"
 if [ "${STEP:-1}" = 1 ]; then
   # kernel trace + stats of the default bench (probed workers, whole batches in flight): per-kernel totals and the overlap timeline
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o bench --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-extra-legs --no-ar-workloads > $O/bench_trace.log 2>&1 || echo "bench trace failed"
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o bench --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-extra-legs --no-ar-workloads > $O/bench_trace.log 2>&1 || echo "bench trace failed"
   (cd $R && python scripts/prof_summary.py gpurun_out/r04prof/trace 24 > gpurun_out/r04prof/bench_summary.txt && python scripts/timeline.py gpurun_out/r04prof/trace 60 > gpurun_out/r04prof/bench_timeline.txt)
   cp $(find $O/trace -name "*kernel_stats.csv" | head -1) $O/r04_bench_kernel_stats.csv
   rm -rf $O/trace

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/b32host
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-A="--batch 32 --steps 40 --warmup 6 --workers 1 --no-cpu-baseline --no-extra-legs --no-ar-workloads --no-dominant"
+A="--batch 32 --steps 40 --warmup 6 --workers 1 --full --no-cpu-baseline --no-extra-legs --no-ar-workloads --no-dominant"
 timeout -k 10 200 python3 $R/bench.py $A > $O/plain.json 2> $O/plain.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o b --output-format csv -- python3 $R/bench.py $A > $O/trace.log 2>&1
 cd $R

@@ -5,7 +5,7 @@ O=$R/gpurun_out/r04b32
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for b in 32 256; do
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/t$b -o t --output-format csv -- python3 $R/bench.py --batch $b --workers 1 --steps 8 --warmup 2 --no-cpu-baseline --no-extra-legs --no-dominant > $O/t$b.log 2>&1 || { echo "trace $b failed"; tail -3 $O/t$b.log; }
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/t$b -o t --output-format csv -- python3 $R/bench.py --batch $b --workers 1 --steps 8 --warmup 2 --full --no-cpu-baseline --no-extra-legs --no-dominant > $O/t$b.log 2>&1 || { echo "trace $b failed"; tail -3 $O/t$b.log; }
   cp $(find $O/t$b -name "*kernel_stats.csv" | head -1) $O/stats_b$b.csv
   rm -rf $O/t$b
 done

@@ -10,6 +10,6 @@ tail -3 $O/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
 s=$(date +%s)
-timeout -k 10 600 python bench.py > $O/bench_line.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_line.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 echo "bench wall $(( $(date +%s) - s )) s"
 python scripts/r04_show_line.py $O/bench_line.json

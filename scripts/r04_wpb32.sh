@@ -5,7 +5,7 @@ O=$R/gpurun_out/wpb32
 mkdir -p $O
 cd $R
 for w in 8 4 2 8 4; do
-  timeout -k 10 200 python bench.py --batch 32 --steps 48 --warmup 6 --workers 6 --token-lanes 4 --rans-waves $w --no-cpu-baseline --no-extra-legs --no-ar-workloads --no-dominant > $O/w$w.json 2> $O/w$w.err || { tail -3 $O/w$w.err; continue; }
+  timeout -k 10 200 python bench.py --batch 32 --steps 48 --warmup 6 --workers 6 --token-lanes 4 --rans-waves $w --full --no-cpu-baseline --no-extra-legs --no-ar-workloads --no-dominant > $O/w$w.json 2> $O/w$w.err || { tail -3 $O/w$w.err; continue; }
   python - $w $O/w$w.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])

@@ -10,7 +10,7 @@ for cfg in $SWEEP; do
   IFS=: read w by rw hq <<< "$cfg"
   echo "== batch ${BATCH:-256} workers $w shard-by $by rans-waves $rw hw-queues ${hq:-default}" >> $out
   if [ -n "$hq" ]; then export GPU_MAX_HW_QUEUES=$hq; else unset GPU_MAX_HW_QUEUES; fi
-  timeout -k 10 200 python bench.py --batch ${BATCH:-256} --workers $w --shard-by $by --rans-waves $rw --steps ${STEPS:-12} --no-cpu-baseline --no-extra-legs --no-dominant 2>>gpurun_out/sweep.err | python -c "
+  timeout -k 10 200 python bench.py --batch ${BATCH:-256} --workers $w --shard-by $by --rans-waves $rw --steps ${STEPS:-12} --full --no-cpu-baseline --no-extra-legs --no-dominant 2>>"${out%.txt}.err" | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
