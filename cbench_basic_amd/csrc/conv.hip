@@ -1,6 +1,7 @@
 // Analysis / synthesis transforms: tap-list implicit-GEMM convolution on the fp32 matrix core
 // (v_mfma_f32_32x32x2_f32) with LDS-staged activation patches and a fused
-// bias + {ReLU, LeakyReLU, GDN, IGDN} epilogue.
+// bias + {ReLU, LeakyReLU, GDN, IGDN} epilogue.  The 128-channel launches of the synthesis transform (IGDN layers) run on
+// the bf16 matrix core instead, with fp32 operands split exactly into three bf16 pieces (conv_split_bf16_kernel).
 //
 // Replaces the ATen calls behind nn/models/google.py:25-101 (compressai conv/deconv/GDN) and
 // nn/layers/slimmable_layers.py:157-183,258-282 (weight slicing = plan of the active slice).
@@ -71,6 +72,10 @@ constexpr int kPSlotsFused = 6;         // ... and for the fused column-phase la
 constexpr int kFusedCK = 4;             // their channels per stage (15 / 10 taps: two 4-wave workgroups per CU still fit)
 constexpr int kMaxCoutPerLaunch = 192;  // 6 accumulator tiles per wave
 constexpr int kSplitBelowBlocks = 384;   // position grids smaller than this use the 32-channel-slice variant
+// Zero floats after a weight pack.  The stage DMA copies wl_pad floats per stage, whole pieces of at least the GDN gamma chunk
+// (32 x 32 x MTP floats): for a GDN launch with few taps the last stage reads up to 32 x 32 x 8 + one piece (2048) floats
+// past the pack (e.g. 1 tap x 8 channels x 4 tiles = 1024 floats per stage against 4096 copied).
+constexpr int kPackTail = 32 * 32 * 8 + 2048;
 
 struct TapLaunch {
     const float *in;
@@ -462,6 +467,299 @@ __global__ __launch_bounds__(64 * WAVES, (MT <= 4 && WAVES == 4 ? 2 : 1)) void c
                     } else {
                         o[co * plane] = apply_act(acc[m][r], g.act);
                     }
+                }
+            }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Split-bf16 path of the 128-channel synthesis layers.  gfx950 has no TF32, and its bf16 MFMA runs at 16x the
+// fp32 MFMA rate.  Every fp32 operand is split exactly into three bf16 pieces x = x0 + x1 + x2 (8 + 8 + 8 significant bits,
+// each the truncation of what is left), and the six products with i + j <= 2 are accumulated smallest first:
+//     a2b0, a1b1, a0b2, a1b0, a0b1, a0b0      (the three left out are below 2^-24 |a b|)
+// = 6 v_mfma_f32_32x32x16_bf16 (32 cycles each) per 16 K-values instead of 8 v_mfma_f32_32x32x2_f32 (64 cycles each).
+//   * A = weights, split once at plan time (basic_conv_plan_create) in A-fragment order
+//     [cin/16][tap][m-tile][piece][lane][8]: one ds_read_b128 per (m-tile, piece).  They are staged through LDS
+//     (5 taps x 16 channels = 60 KB per stage, two stages) by register staging: plain global loads, so that the
+//     compiler's counted vmcnt waits keep the activation loads below in flight.
+//   * B = activations, read straight from the fp32 NCHW input by buffer loads (8 channels per lane and tap, taps
+//     outside the image come back as zeros from an out-of-range offset) and split in registers right before their
+//     MFMAs.  Nothing else changes: the input and output stay fp32 NCHW.
+//   * One fixed K order per output element (channel block, then tap): results do not depend on tile, batch or launch.
+// Workgroup = 8 waves x 32 positions, each wave owns all 128 output channels of its positions (MT = 4), so the
+// bias / GDN / IGDN epilogue of conv_tap_mfma_kernel applies unchanged (its second GEMM stays fp32).
+// The launch is the fused column phases (KWB > 0) of a stride-2 transposed convolution, as in conv_tap_mfma_kernel.
+// Only the synthesis transform takes this path: its output is the reconstruction only.  The analysis transform's output is
+// quantised and coded, and a different rounding moves a few latents across a rounding boundary: the bitstream would no
+// longer be the fp32 path's byte for byte.
+// ---------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kSplitWaves = 8;
+constexpr int kSplitThreads = 64 * kSplitWaves;
+constexpr int kSplitCK = 16;                           // input channels per K block (the K of one bf16 MFMA)
+constexpr int kSplitStageTaps = 5;                     // taps per weight stage (15 and 10 taps per channel block)
+constexpr int kSplitBlockU4 = 4 * 3 * 64;              // 16-byte A fragments of one (channel block, tap): m-tile x piece x lane
+constexpr int kSplitStageU4 = kSplitStageTaps * kSplitBlockU4;                     // 3840 = 60 KB
+constexpr int kSplitWSlots = (kSplitStageU4 + kSplitThreads - 1) / kSplitThreads;  // 8 staged pieces per thread
+static_assert(kSplitWSlots % 2 == 0, "weight stage in two halves");
+constexpr size_t kSplitLdsBytes = 2 * kSplitStageU4 * 16 + 2 * 128 * sizeof(float);  // two stages + bias, beta
+
+// x = x0 + x1 + x2 exactly (normal range): each piece is the bf16 truncation of what the previous ones leave.
+// Returns the three pieces of 8 values as bf16x8 (element j = x[j]).
+__device__ __forceinline__ void split_bf16x3(const float (&x)[8], u32x4 &p0, u32x4 &p1, u32x4 &p2)
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const unsigned a = __float_as_uint(x[2 * i]), b = __float_as_uint(x[2 * i + 1]);
+        const unsigned a0 = a & 0xFFFF0000u, b0 = b & 0xFFFF0000u;
+        p0[i] = (a >> 16) | b0;
+        const unsigned ra = __float_as_uint(x[2 * i] - __uint_as_float(a0)), rb = __float_as_uint(x[2 * i + 1] - __uint_as_float(b0));
+        const unsigned a1 = ra & 0xFFFF0000u, b1 = rb & 0xFFFF0000u;
+        p1[i] = (ra >> 16) | b1;
+        const unsigned sa = __float_as_uint(__uint_as_float(ra) - __uint_as_float(a1)), sb = __float_as_uint(__uint_as_float(rb) - __uint_as_float(b1));
+        p2[i] = (sa >> 16) | (sb & 0xFFFF0000u);
+    }
+}
+
+__device__ __forceinline__ f32x16 mfma_bf16(const u32x4 &a, const u32x4 &b, const f32x16 &c)
+{
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+template <int KH, int KW, int KWB>
+__global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const TapLaunch g, const u32x4 *wsplit)
+{
+    constexpr int MT = 4;
+    constexpr int kTapsA = KH * KW, kTapsAll = KH * (KW + KWB);
+    constexpr int kGroups = kTapsAll / kSplitStageTaps;  // weight stages per channel block
+    static_assert(kTapsAll % kSplitStageTaps == 0, "taps per channel block must be whole stages");
+    static_assert(KWB > 0 && KWB <= KW, "fused phases: second grid inside the first");
+    extern __shared__ u32x4 lds_u4[];
+    float *chan_const = reinterpret_cast<float *>(lds_u4 + 2 * kSplitStageU4);  // [128] bias, [128] beta
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int khalf = lane >> 5, col = lane & 31;
+
+    int bid = xcd_tile(blockIdx.x, gridDim.x);
+    const int tx_i = bid % g.tiles_x; bid /= g.tiles_x;
+    const int ty_i = bid % g.tiles_y; bid /= g.tiles_y;
+    const int TB = 1 << g.tb_log, TH = 1 << g.th_log, TW = 1 << g.tw_log;
+    const int b0 = bid * TB, my0 = ty_i * TH, mx0 = tx_i * TW;
+    // this lane's position (tile image tb, m-grid row my, column mx) from thread t (t = tid): the epilogue recomputes it
+    // rather than keep three registers alive through the main loop
+    struct Pos { int tb, my, mx; };
+    auto pos_of = [&](int t) {
+        const int qq = (t >> 6) * 32 + (t & 31);
+        return Pos{qq >> (g.tw_log + g.th_log), my0 + ((qq >> g.tw_log) & (TH - 1)), mx0 + (qq & (TW - 1))};
+    };
+    const Pos lp = pos_of(tid);
+    const int tb = lp.tb, b = b0 + lp.tb;  // tb < TB: the tile holds exactly 256 positions
+
+    if (tid < 128) {
+        chan_const[tid] = g.bias ? g.bias[tid] : 0.f;
+        chan_const[128 + tid] = g.beta ? g.beta[tid] : 1.f;
+    }
+
+    // Activations of this tile's images through one buffer resource: a lane whose tap falls outside the image (or whose
+    // image does not exist) gets an offset past the end of the resource and loads zeros.
+    const int64_t plane = static_cast<int64_t>(g.in_h) * g.in_w;
+    const int nimg = (g.batch - b0 < TB) ? g.batch - b0 : TB;
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float *>(g.in + static_cast<int64_t>(b0) * g.cin * plane), 0, static_cast<int>(nimg * g.cin * plane * 4), 0x00020000);
+    const int gy_l = lp.my * g.s_in + g.dymin, gx_l = lp.mx * g.s_in + g.dxmin;  // patch origin of this lane
+    // byte offset of (image tb, channel 8 khalf, row gy_l, column gx_l): may be negative, then only valid taps add to it
+    const int lane_off = static_cast<int>((((static_cast<int64_t>(tb) * g.cin + 8 * khalf) * g.in_h + gy_l) * g.in_w + gx_l) * 4);
+    constexpr int kSpanX = KW;  // the fused second grid lies inside the first one's columns
+    static_assert(KH * kSpanX <= 32, "one validity bit per tap offset");
+    unsigned vmask = 0;         // bit dy * kSpanX + dx: tap offset (dy, dx) lies inside the image
+    if (b < g.batch) {
+#pragma unroll
+        for (int dy = 0; dy < KH; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < kSpanX; ++dx) {
+                const int yy = gy_l + dy, xx = gx_l + dx;
+                if (yy >= 0 && yy < g.in_h && xx >= 0 && xx < g.in_w) vmask |= 1u << (dy * kSpanX + dx);
+            }
+    }
+    const int plane_bytes = static_cast<int>(plane * 4);
+    auto tap_row = [](int t) { return t < kTapsA ? t / KW : (t - kTapsA) / KWB; };
+    auto tap_col = [](int t) { return t < kTapsA ? t % KW : (t - kTapsA) % KWB + (KW - KWB); };
+    // 8 input channels (cb * 16 + 8 khalf + j) of tap T for this lane
+    auto load_b = [&](int cb, int T, float (&d)[8]) __attribute__((always_inline)) {
+        const int dy = tap_row(T), dx = tap_col(T);
+        const int voff = ((vmask >> (dy * kSpanX + dx)) & 1u) ? lane_off + (dy * g.in_w + dx) * 4 : 0x7FFFFFF0;
+        const int soff = cb * kSplitCK * plane_bytes;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            d[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff + j * plane_bytes, 0));
+    };
+
+    // weight stages: register-staged one stage ahead, in two halves of 4 pieces per thread (fewer staging registers)
+    const int ncb = g.cin / kSplitCK;
+    constexpr int kHalf = kSplitWSlots / 2;
+    u32x4 wst[kHalf];
+    auto fetch_w = [&](int s, int h) __attribute__((always_inline)) {
+        const u32x4 *src = wsplit + static_cast<int64_t>(s) * kSplitStageU4 + tid;
+#pragma unroll
+        for (int sl = h * kHalf; sl < (h + 1) * kHalf; ++sl)
+            if (sl * kSplitThreads + tid < kSplitStageU4) wst[sl - h * kHalf] = src[sl * kSplitThreads];
+    };
+    auto store_w = [&](int buf, int h) __attribute__((always_inline)) {
+        u32x4 *dst = lds_u4 + buf * kSplitStageU4 + tid;
+#pragma unroll
+        for (int sl = h * kHalf; sl < (h + 1) * kHalf; ++sl)
+            if (sl * kSplitThreads + tid < kSplitStageU4) dst[sl * kSplitThreads] = wst[sl - h * kHalf];
+    };
+
+    f32x16 acc[MT], acc2[MT];  // output columns 2 mx and 2 mx + 1
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            acc[m][r] = 0.f;
+            acc2[m][r] = 0.f;
+        }
+
+    float xb[8];
+    load_b(0, 0, xb);
+    fetch_w(0, 0);
+    store_w(0, 0);
+    fetch_w(0, 1);
+    store_w(0, 1);
+    for (int cb = 0; cb < ncb; ++cb) {
+#pragma unroll
+        for (int gi = 0; gi < kGroups; ++gi) {
+            const int s = cb * kGroups + gi;
+            __syncthreads();  // stage s is in LDS; every wave is done with stage s - 1, whose buffer stage s + 1 takes
+            const bool more = s + 1 < ncb * kGroups;
+            if (more) fetch_w(s + 1, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            const u32x4 *wl = lds_u4 + (s & 1) * kSplitStageU4 + lane;
+#pragma unroll
+            for (int tl = 0; tl < kSplitStageTaps; ++tl) {
+                const int T = gi * kSplitStageTaps + tl;
+                // next tap's activations (the next channel block's first tap at the end; a harmless re-read at the very end),
+                // issued before this tap's MFMAs: a whole tap of matrix work covers their latency.  The sched_barriers keep the
+                // compiler from sinking them next to their use.
+                float xn[8];
+                if (T + 1 < kTapsAll) load_b(cb, T + 1, xn);
+                else load_b(cb + 1 < ncb ? cb + 1 : cb, 0, xn);
+                __builtin_amdgcn_sched_barrier(0);
+                u32x4 bp[3];
+                split_bf16x3(xb, bp[0], bp[1], bp[2]);
+                f32x16 (&dst)[MT] = T < kTapsA ? acc : acc2;  // (compile-time after unrolling)
+                // per M-tile its three A pieces (one ds_read_b128 each, read one tile ahead) and six MFMAs, smallest products
+                // first: (i, j) = (2,0) (1,1) (0,2) (1,0) (0,1) (0,0) -- one dependent chain per tile needs no interleaving
+                u32x4 ap[2][3];
+#pragma unroll
+                for (int pc = 0; pc < 3; ++pc) ap[0][pc] = wl[(tl * MT * 3 + pc) * 64];
+#pragma unroll
+                for (int m = 0; m < MT; ++m) {
+                    const int cur = m & 1;
+                    if (m + 1 < MT) {
+#pragma unroll
+                        for (int pc = 0; pc < 3; ++pc) ap[cur ^ 1][pc] = wl[((tl * MT + m + 1) * 3 + pc) * 64];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    dst[m] = mfma_bf16(ap[cur][2], bp[0], dst[m]);
+                    dst[m] = mfma_bf16(ap[cur][1], bp[1], dst[m]);
+                    dst[m] = mfma_bf16(ap[cur][0], bp[2], dst[m]);
+                    dst[m] = mfma_bf16(ap[cur][1], bp[0], dst[m]);
+                    dst[m] = mfma_bf16(ap[cur][0], bp[1], dst[m]);
+                    dst[m] = mfma_bf16(ap[cur][0], bp[0], dst[m]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) xb[j] = xn[j];
+                // the next stage's buffer has been free since the barrier: each half is written two taps after its loads
+                if (tl == 1 && more) {
+                    store_w((s + 1) & 1, 0);
+                    fetch_w(s + 1, 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (tl == 3 && more) store_w((s + 1) & 1, 1);
+            }
+        }
+    }
+
+    // ---- epilogue: bias, GDN / IGDN (as conv_tap_mfma_kernel; gamma^T resident in the free stage buffers)
+    float *gl = reinterpret_cast<float *>(lds_u4);
+    const bool gdn = g.act == BASIC_ACT_GDN || g.act == BASIC_ACT_IGDN;
+    auto finish = [&](f32x16 (&acc)[MT]) __attribute__((always_inline)) {
+        if (g.bias) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int rq = 0; rq < 4; ++rq) {
+                    const f32x4 b4 = *reinterpret_cast<const f32x4 *>(chan_const + 32 * m + 8 * rq + 4 * khalf);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[m][4 * rq + e] += b4[e];
+                }
+        }
+        if (gdn) {
+            f32x16 nrm[MT];
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) nrm[m][r] = 0.f;
+#pragma unroll
+            for (int st = 0; st < 64; ++st) {  // k = 32 mk + 8 (r >> 2) + (r & 3) [+4 for lanes 32..63], st = 16 mk + r
+                const int kk = 32 * (st >> 4) + 8 * ((st & 15) >> 2) + (st & 3);
+                float gk[4];
+                load_a<4>(gl + ((kk + 4 * khalf) * 32 + col) * 4, gk);
+                const float x = acc[st >> 4][st & 15];
+                const float bfrag = x * x;
+#pragma unroll
+                for (int m = 0; m < MT; ++m)
+                    nrm[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(gk[m], bfrag, nrm[m], 0, 0, 0);
+            }
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int rq = 0; rq < 4; ++rq) {
+                    const f32x4 b4 = *reinterpret_cast<const f32x4 *>(chan_const + 128 + 32 * m + 8 * rq + 4 * khalf);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int r = 4 * rq + e;
+                        const float nv = nrm[m][r] + b4[e];
+                        acc[m][r] *= (g.act == BASIC_ACT_GDN) ? __builtin_amdgcn_rsqf(nv) : __builtin_amdgcn_sqrtf(nv);
+                    }
+                }
+        }
+    };
+    if (gdn) {
+        __syncthreads();  // every wave is done with the last weight stage
+        const f32x4 *src = reinterpret_cast<const f32x4 *>(g.gammaT);
+        f32x4 *dst = reinterpret_cast<f32x4 *>(gl);
+#pragma unroll
+        for (int sl = 0; sl < 128 * 32 * 4 / 4 / kSplitThreads; ++sl) dst[sl * kSplitThreads + tid] = src[sl * kSplitThreads + tid];
+        __syncthreads();
+    }
+    finish(acc);
+    finish(acc2);
+
+    // ---- store
+    int tid_e = tid;
+    asm volatile("" : "+v"(tid_e));  // opaque: the position is recomputed here, not carried through the main loop
+    const Pos ep = pos_of(tid_e);
+    const int my = ep.my, mx = ep.mx, be = b0 + ep.tb;
+    if (my < g.mh && mx < g.mw && be < g.batch) {
+        const int oy = my * g.s_out + g.oy0, ox = mx * g.s_out + g.ox0;
+        const int64_t oplane = static_cast<int64_t>(g.out_h) * g.out_w;
+        float *o = g.out + (static_cast<int64_t>(be) * g.out_ctotal + g.co_base) * oplane + static_cast<int64_t>(oy) * g.out_w + ox;
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int co = 32 * m + 8 * (r >> 2) + 4 * khalf + (r & 3);
+                if (co < g.cout) {  // columns ox, ox + 1 (ox even, rows 8-byte aligned: host-checked)
+                    f32x2 v2;
+                    v2[0] = apply_act(acc[m][r], g.act);
+                    v2[1] = apply_act(acc2[m][r], g.act);
+                    *reinterpret_cast<f32x2 *>(o + co * oplane) = v2;
                 }
             }
     }
@@ -1104,6 +1402,7 @@ struct Phase {
     float *d_wpack = nullptr;
     float *d_wrow = nullptr;    // see TapLaunch::wrow
     int64_t split_wstride = 0;  // floats per output-channel slice of d_wpack
+    void *d_wsplit = nullptr;   // split-bf16 weights of conv_split_bf16_kernel (see pack_split), or nullptr: fp32 only
 };
 
 struct Chunk {  // <= 192 output channels handled by one launch family
@@ -1134,9 +1433,12 @@ extern "C" void basic_conv_plan_destroy(basic_conv_plan *p)
             for (auto &ph : ch.phases) {
                 if (ph.d_wpack) (void)hipFree(ph.d_wpack);
                 if (ph.d_wrow) (void)hipFree(ph.d_wrow);
+                if (ph.d_wsplit) (void)hipFree(ph.d_wsplit);
             }
-            for (auto &ph : ch.fused)
+            for (auto &ph : ch.fused) {
                 if (ph.d_wpack) (void)hipFree(ph.d_wpack);
+                if (ph.d_wsplit) (void)hipFree(ph.d_wsplit);
+            }
             if (ch.d_bias) (void)hipFree(ch.d_bias);
         }
     if (p->d_sched) (void)hipFree(p->d_sched);
@@ -1153,6 +1455,37 @@ int upload(const std::vector<float> &h, float **d)
 {
     BASIC_HIP_TRY(hipMalloc(d, h.size() * sizeof(float)));
     BASIC_HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return BASIC_OK;
+}
+
+// Split-bf16 weights of conv_split_bf16_kernel from the fp32 pack wp = [cin_pad / ck][ntaps][ck][32][4] of a 4-tile launch:
+// [cin / 16][tap][m-tile][piece][lane][8] bf16, lane = 32 khalf + col holding input channels 16 cb + 8 khalf + j of output
+// channel 32 m + col.  The pieces are the kernel's split_bf16x3 of the weight: w = w0 + w1 + w2, each a bf16 truncation.
+int pack_split(const std::vector<float> &wp, int ck, int ntaps, int cin, void **d)
+{
+    const int ncb = cin / kSplitCK;
+    std::vector<uint16_t> ws(static_cast<size_t>(ncb) * ntaps * kSplitBlockU4 * 8);
+    size_t i = 0;
+    for (int cb = 0; cb < ncb; ++cb)
+        for (int t = 0; t < ntaps; ++t)
+            for (int m = 0; m < 4; ++m)
+                for (int pc = 0; pc < 3; ++pc)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int j = 0; j < 8; ++j) {
+                            const int c = cb * kSplitCK + 8 * (lane >> 5) + j, o = 32 * m + (lane & 31);
+                            float rem = wp[((static_cast<size_t>(c / ck) * ntaps + t) * ck + c % ck) * 32 * 4 + (o % 32) * 4 + o / 32];
+                            uint32_t u = 0;
+                            for (int k = 0; k <= pc; ++k) {
+                                std::memcpy(&u, &rem, 4);
+                                const uint32_t hi = u & 0xFFFF0000u;
+                                float h;
+                                std::memcpy(&h, &hi, 4);
+                                if (k < pc) rem -= h;  // exact
+                            }
+                            ws[i++] = static_cast<uint16_t>(u >> 16);
+                        }
+    BASIC_HIP_TRY(hipMalloc(d, ws.size() * sizeof(uint16_t)));
+    BASIC_HIP_TRY(hipMemcpy(*d, ws.data(), ws.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return BASIC_OK;
 }
 
@@ -1232,7 +1565,7 @@ int build_chunks(basic_conv_plan *p, const float *weight, const float *bias, int
                                (((static_cast<size_t>(c / kCK) * ph.ntaps + t) * kCK + (c % kCK)) * 32 + ol % 32) * mtp + ol / 32] = w;
                         }
                     }
-                wp.resize(wp.size() + 2048, 0.f);  // the DMA copies whole 4 / 8 KB pieces and may read past the last stage
+                wp.resize(wp.size() + kPackTail, 0.f);  // the DMA may read past the last stage (see kPackTail)
                 int rc = upload(wp, &ph.d_wpack);
                 // the first analysis layer's row slab (conv5x5_cin4_gdn_persistent_kernel<true>): [ky * 16 + kx * 3 + c][32][4]
                 if (!rc && !transposed && ph.kh == 5 && ph.kw == 5 && ci_n <= 3 && ch.cout == 128 && ch.mt == 4 && ch.nsplit == 1) {
@@ -1289,13 +1622,20 @@ int build_chunks(basic_conv_plan *p, const float *weight, const float *bias, int
                             wp[static_cast<size_t>(o / ch.coutp) * f.split_wstride +
                                (((static_cast<size_t>(c / kFusedCK) * f.ntaps + t) * kFusedCK + (c % kFusedCK)) * 32 + ol % 32) * mtp + ol / 32] = w;
                         }
-                wp.resize(wp.size() + 2048, 0.f);
-                const int rcf = upload(wp, &f.d_wpack);
+                wp.resize(wp.size() + kPackTail, 0.f);
+                int rcf = upload(wp, &f.d_wpack);
+                // split-bf16 path: IGDN layers only, i.e. the synthesis transform, whose output is never coded
+                // (the hyper-synthesis layers, whose output sets the coding scales, stay fp32)
+                if (!rcf && !slice && p->act == BASIC_ACT_IGDN && ch.mt == 4 && ch.nsplit == 1 && ci_n % kSplitCK == 0)
+                    rcf = pack_split(wp, kFusedCK, f.ntaps, ci_n, &f.d_wsplit);
                 fused.push_back(f);
                 if (rcf) { ok = false; }
             }
             if (ok) ch.fused = fused;
-            else for (auto &f : fused) if (f.d_wpack) (void)hipFree(f.d_wpack);
+            else for (auto &f : fused) {
+                if (f.d_wpack) (void)hipFree(f.d_wpack);
+                if (f.d_wsplit) (void)hipFree(f.d_wsplit);
+            }
         }
         std::vector<float> hb(static_cast<size_t>(ch.coutp) * ch.nsplit, 0.f);
         if (bias) std::memcpy(hb.data(), bias + co0, sizeof(float) * ch.cout);
@@ -1471,7 +1811,7 @@ int pow2_ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 namespace {
 // which launch list forward() walks for this input: 32-channel slices for small position grids, fused column phases when
 // the output rows allow 8-byte pair stores
-struct LaunchChoice { bool use_split, fuse_ok; int dbg; };
+struct LaunchChoice { bool use_split, fuse_ok, bf16x3; int dbg; };
 LaunchChoice choose_launches(const basic_conv_plan *p, int batch, int oh, int ow, const void *d_out)
 {
     const int64_t pos_blocks = (static_cast<int64_t>(batch) * ((oh + p->s_out - 1) / p->s_out) * ((ow + p->s_out - 1) / p->s_out) + kTilePos - 1) / kTilePos;
@@ -1486,6 +1826,9 @@ LaunchChoice choose_launches(const basic_conv_plan *p, int batch, int oh, int ow
     c.dbg = dbg;
     c.use_split = !p->split.empty() && !(dbg & 8) && (pos_blocks < kSplitBelowBlocks || (dbg & 4));
     c.fuse_ok = ow % 2 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0 && !(dbg & 512);
+    // BASIC_CONV_F32=1: the launches that have a split-bf16 variant run the fp32 kernel instead (A/B runs, tests)
+    const char *f32_env = getenv("BASIC_CONV_F32");
+    c.bf16x3 = !(f32_env && atoi(f32_env) != 0);
     return c;
 }
 }  // namespace
@@ -1552,6 +1895,28 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
         g.act = p->act;
         const int kCK = ph.ck;
         g.debug = dbg;
+        if (choice.bf16x3 && ph.d_wsplit) {
+            // split-bf16 path: 256 positions per workgroup, weights through LDS, activations by buffer loads
+            int tw = pow2_ceil(g.mw); if (tw > 16) tw = 16;
+            int th = pow2_ceil(g.mh); if (th > kSplitWaves * 32 / tw) th = kSplitWaves * 32 / tw;
+            const int tb = kSplitWaves * 32 / (tw * th);
+            if (static_cast<int64_t>(tb) * p->cin * in_h * in_w * 4 < (1ll << 31)) {  // one buffer resource per tile's images
+                g.tw_log = ilog2(tw); g.th_log = ilog2(th); g.tb_log = ilog2(tb);
+                g.tiles_y = (g.mh + th - 1) / th;
+                g.tiles_x = (g.mw + tw - 1) / tw;
+                const int blocks = ((batch + tb - 1) / tb) * g.tiles_y * g.tiles_x;
+                hipStream_t st = as_stream(hip_stream);
+                const u32x4 *ws = static_cast<const u32x4 *>(ph.d_wsplit);
+                const void *kfn = ph.kh == 3 ? reinterpret_cast<const void *>(conv_split_bf16_kernel<3, 3, 2>)
+                                             : reinterpret_cast<const void *>(conv_split_bf16_kernel<2, 3, 2>);
+                BASIC_REQUIRE(ph.kw == 3 && ph.kwb == 2 && (ph.kh == 3 || ph.kh == 2), "conv_forward: split-bf16 plan / kernel instantiation mismatch");
+                BASIC_HIP_TRY(ensure_max_lds(kfn));
+                if (ph.kh == 3) hipLaunchKernelGGL((conv_split_bf16_kernel<3, 3, 2>), dim3(blocks), dim3(kSplitThreads), kSplitLdsBytes, st, g, ws);
+                else hipLaunchKernelGGL((conv_split_bf16_kernel<2, 3, 2>), dim3(blocks), dim3(kSplitThreads), kSplitLdsBytes, st, g, ws);
+                BASIC_HIP_TRY(hipGetLastError());
+                continue;
+            }
+        }
         // tile shape: 128 positions = TB images x TH x TW, powers of two, preferring wide rows
         int tw = pow2_ceil(g.mw); if (tw > 16) tw = 16;
         const int threads = 64 * ph.waves, tile_pos = 32 * ph.waves;  // one position per half-wave lane
