@@ -96,7 +96,6 @@ struct TapLaunch {
     int ph, pw, pwp;             // LDS patch rows / cols / padded cols
     int patch4;                  // 1: patch rows are whole 16-byte groups aligned to the image (x origin floor4(x0)): 16-byte DMA pieces
     int act;
-    int debug;  // ablation switches for profiling only (BASIC_CONV_DEBUG): 1 = skip staging, 2 = skip MFMA loop
     int tiles_y, tiles_x;
     signed char dy[kMaxTaps], dx[kMaxTaps];  // relative to (dymin, dxmin)
 };
@@ -301,75 +300,73 @@ __global__ __launch_bounds__(64 * WAVES, (MT <= 4 && WAVES == 4 ? 2 : 1)) void c
         }                                                                                                      \
     } while (0)
 
-    if (nstages > 0 && !(g.debug & 1)) BASIC_ISSUE_STAGE(0, 0);
+    if (nstages > 0) BASIC_ISSUE_STAGE(0, 0);
     for (int stg = 0; stg < nstages; ++stg) {
         // my DMAs of this stage have landed (vmcnt(0), part of the barrier's fence) + every wave is past the
         // previous stage, whose buffer the next DMA overwrites
         __syncthreads();
-        if (stg + 1 < nstages && !(g.debug & 1)) BASIC_ISSUE_STAGE(stg + 1, (stg + 1) & 1);  // in flight during the MFMAs below
+        if (stg + 1 < nstages) BASIC_ISSUE_STAGE(stg + 1, (stg + 1) & 1);  // in flight during the MFMAs below
         const float *wl = lds + (stg & 1) * stage_floats;
         const float *patch = wl + wl_pad;
         // ---- MFMA over (tap, channel pair) steps.  The fragment reads of the next step are issued
         // before the MFMAs of the current one, on two alternating register sets (no copies, so the
         // compiler's counted lgkmcnt waits keep the next step's reads in flight while the matrix
         // core works); sched_barriers pin that order against the machine scheduler.
-        if (!(g.debug & 2)) {
-            constexpr int kPairs = kCK / 2;
-            float fa[2][MTP], fb[2];
-            if constexpr (KH > 0) {
-                // Straight-line stage: every fragment address is lane base + compile-time offset (plus one
-                // wave-uniform row/channel term), so a step is one ds_read_b32 (B), one ds_read_b128 (A) and
-                // MT MFMAs.  The matrix pipe loses throughput to every other instruction the SIMD issues, so
-                // nothing else may sit between the MFMAs.
-                constexpr int kSteps = kTapsAll * kPairs;
-                const float *a_lane = wl + lane_a_base;
-                const float *b_lane = patch + lane_b_base;
-                fb[0] = b_lane[0];
-                load_a<MTP>(a_lane, fa[0]);
+        constexpr int kPairs = kCK / 2;
+        float fa[2][MTP], fb[2];
+        if constexpr (KH > 0) {
+            // Straight-line stage: every fragment address is lane base + compile-time offset (plus one
+            // wave-uniform row/channel term), so a step is one ds_read_b32 (B), one ds_read_b128 (A) and
+            // MT MFMAs.  The matrix pipe loses throughput to every other instruction the SIMD issues, so
+            // nothing else may sit between the MFMAs.
+            constexpr int kSteps = kTapsAll * kPairs;
+            const float *a_lane = wl + lane_a_base;
+            const float *b_lane = patch + lane_b_base;
+            fb[0] = b_lane[0];
+            load_a<MTP>(a_lane, fa[0]);
 #pragma unroll
-                for (int st = 0; st < kSteps; ++st) {
-                    const int cur = st & 1, nxt = cur ^ 1;
-                    const int sn = (st + 1 < kSteps) ? st + 1 : st;  // at the very end a harmless re-read
+            for (int st = 0; st < kSteps; ++st) {
+                const int cur = st & 1, nxt = cur ^ 1;
+                const int sn = (st + 1 < kSteps) ? st + 1 : st;  // at the very end a harmless re-read
+                const int tn = sn / kPairs, cpn = sn % kPairs;
+                // patch row / column of tap tn: the first KH x KW taps are column phase 0, the KH x KWB after them
+                // column phase 1, whose tap grid starts KW - KWB columns to the right
+                const int trow = tn < kTapsA ? tn / KW : (tn - kTapsA) / (KWB > 0 ? KWB : 1);
+                const int tcol = tn < kTapsA ? tn % KW : (tn - kTapsA) % (KWB > 0 ? KWB : 1) + (KW - KWB);
+                fb[nxt] = b_lane[trow * g.pwp + cpn * 2 * chan_stride + tcol];
+                load_a<MTP>(a_lane + (tn * kCK + cpn * 2) * 32 * MTP, fa[nxt]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (KWB == 0 || st / kPairs < kTapsA) {
+#pragma unroll
+                    for (int m = 0; m < MT; ++m)
+                        acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][m], fb[cur], acc[m], 0, 0, 0);
+                } else {
+#pragma unroll
+                    for (int m = 0; m < MT; ++m)
+                        acc2[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][m], fb[cur], acc2[m], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            // Runtime tap table, one step = (tap, channel pair).
+            const int nsteps = g.ntaps * kPairs;
+            fb[0] = patch[lane_b_base + tapoff[0]];
+            load_a<MTP>(wl + lane_a_base, fa[0]);
+            for (int st = 0; st < nsteps; st += 2) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {  // two steps per iteration: the register sets alternate statically
+                    const int cur = u, nxt = u ^ 1;
+                    const int sn = (st + u + 1 < nsteps) ? st + u + 1 : st + u;
                     const int tn = sn / kPairs, cpn = sn % kPairs;
-                    // patch row / column of tap tn: the first KH x KW taps are column phase 0, the KH x KWB after them
-                    // column phase 1, whose tap grid starts KW - KWB columns to the right
-                    const int trow = tn < kTapsA ? tn / KW : (tn - kTapsA) / (KWB > 0 ? KWB : 1);
-                    const int tcol = tn < kTapsA ? tn % KW : (tn - kTapsA) % (KWB > 0 ? KWB : 1) + (KW - KWB);
-                    fb[nxt] = b_lane[trow * g.pwp + cpn * 2 * chan_stride + tcol];
-                    load_a<MTP>(a_lane + (tn * kCK + cpn * 2) * 32 * MTP, fa[nxt]);
+                    fb[nxt] = patch[lane_b_base + tapoff[tn] + cpn * 2 * chan_stride];
+                    load_a<MTP>(wl + (tn * kCK + cpn * 2) * 32 * MTP + lane_a_base, fa[nxt]);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (KWB == 0 || st / kPairs < kTapsA) {
+                    if (st + u < nsteps) {
 #pragma unroll
                         for (int m = 0; m < MT; ++m)
                             acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][m], fb[cur], acc[m], 0, 0, 0);
-                    } else {
-#pragma unroll
-                        for (int m = 0; m < MT; ++m)
-                            acc2[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][m], fb[cur], acc2[m], 0, 0, 0);
                     }
                     __builtin_amdgcn_sched_barrier(0);
-                }
-            } else {
-                // Runtime tap table, one step = (tap, channel pair).
-                const int nsteps = g.ntaps * kPairs;
-                fb[0] = patch[lane_b_base + tapoff[0]];
-                load_a<MTP>(wl + lane_a_base, fa[0]);
-                for (int st = 0; st < nsteps; st += 2) {
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {  // two steps per iteration: the register sets alternate statically
-                        const int cur = u, nxt = u ^ 1;
-                        const int sn = (st + u + 1 < nsteps) ? st + u + 1 : st + u;
-                        const int tn = sn / kPairs, cpn = sn % kPairs;
-                        fb[nxt] = patch[lane_b_base + tapoff[tn] + cpn * 2 * chan_stride];
-                        load_a<MTP>(wl + (tn * kCK + cpn * 2) * 32 * MTP + lane_a_base, fa[nxt]);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (st + u < nsteps) {
-#pragma unroll
-                            for (int m = 0; m < MT; ++m)
-                                acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][m], fb[cur], acc[m], 0, 0, 0);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
                 }
             }
         }
@@ -899,7 +896,7 @@ __global__ __launch_bounds__(512, 1) void conv5x5_cin4_gdn_persistent_kernel(con
         __builtin_amdgcn_s_barrier();
         // the barrier also published next_slot[(it + 1) & 1], written by thread 0 during the previous iteration
         tile_next = sched ? __builtin_amdgcn_readfirstlane(next_slot[(it + 1) & 1]) : tile + static_cast<int>(gridDim.x);
-        if (tile_next < ntiles && !(g.debug & 1)) BASIC_FIRST_ISSUE_PATCH(tile_next, (it + 1) & 1);
+        if (tile_next < ntiles) BASIC_FIRST_ISSUE_PATCH(tile_next, (it + 1) & 1);
         int tile_after = 0;   // thread 0: the tile of iteration it + 2, requested now, published at the end of this iteration
         if (sched && tid == 0) tile_after = static_cast<int>(gridDim.x) + atomicAdd(sched, 1);
         const float *patch = pbuf + (it & 1) * patch_pad;
@@ -909,34 +906,32 @@ __global__ __launch_bounds__(512, 1) void conv5x5_cin4_gdn_persistent_kernel(con
         for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-        if (!(g.debug & 2)) {
-            float fa[2][4], fb[2];
-            const float *a_lane = wl + lane_a_base;
-            const float *b_lane = patch + lane_b_base;
-            const float *b_row[KW];   // ROWS: this lane's 16 operands of kernel row ky start at b_row[ky] (its khalf folded in)
+        float fa[2][4], fb[2];
+        const float *a_lane = wl + lane_a_base;
+        const float *b_lane = patch + lane_b_base;
+        const float *b_row[KW];   // ROWS: this lane's 16 operands of kernel row ky start at b_row[ky] (its khalf folded in)
 #pragma unroll
-            for (int ky = 0; ky < KW; ++ky) b_row[ky] = b_lane + ky * row_pitch;
-            fb[0] = b_lane[0];
-            load_a<4>(a_lane, fa[0]);
+        for (int ky = 0; ky < KW; ++ky) b_row[ky] = b_lane + ky * row_pitch;
+        fb[0] = b_lane[0];
+        load_a<4>(a_lane, fa[0]);
 #pragma unroll
-            for (int st = 0; st < kSteps; ++st) {
-                const int cur = st & 1, nxt = cur ^ 1;
-                const int sn = (st + 1 < kSteps) ? st + 1 : st;
-                if constexpr (ROWS) {   // step = (kernel row, pair of its 16 operands)
-                    fb[nxt] = b_row[sn / 8][2 * (sn % 8)];
-                    if (sn % 8 == 7 && khalf) fb[nxt] = 0.f;   // the row's 16th operand is the pad: whatever sits there (the next pixel) stays out, non-finite or not
-                    load_a<4>(a_lane + (sn / 8 * 16 + 2 * (sn % 8)) * 32 * 4, fa[nxt]);
-                } else {
-                const int tn = sn / 2, cpn = sn % 2;
-                fb[nxt] = b_lane[(tn / KW) * g.pwp + cpn * 2 * chan_stride + (tn % KW)];
-                load_a<4>(a_lane + (tn * kCK + cpn * 2) * 32 * 4, fa[nxt]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][m], fb[cur], acc[m], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
+        for (int st = 0; st < kSteps; ++st) {
+            const int cur = st & 1, nxt = cur ^ 1;
+            const int sn = (st + 1 < kSteps) ? st + 1 : st;
+            if constexpr (ROWS) {   // step = (kernel row, pair of its 16 operands)
+                fb[nxt] = b_row[sn / 8][2 * (sn % 8)];
+                if (sn % 8 == 7 && khalf) fb[nxt] = 0.f;   // the row's 16th operand is the pad: whatever sits there (the next pixel) stays out, non-finite or not
+                load_a<4>(a_lane + (sn / 8 * 16 + 2 * (sn % 8)) * 32 * 4, fa[nxt]);
+            } else {
+            const int tn = sn / 2, cpn = sn % 2;
+            fb[nxt] = b_lane[(tn / KW) * g.pwp + cpn * 2 * chan_stride + (tn % KW)];
+            load_a<4>(a_lane + (tn * kCK + cpn * 2) * 32 * 4, fa[nxt]);
             }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+                acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][m], fb[cur], acc[m], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
         }
         if (g.bias) {
 #pragma unroll
@@ -948,7 +943,7 @@ __global__ __launch_bounds__(512, 1) void conv5x5_cin4_gdn_persistent_kernel(con
                     for (int e = 0; e < 4; ++e) acc[m][4 * rq + e] += b4[e];
                 }
         }
-        if ((g.act == BASIC_ACT_GDN || g.act == BASIC_ACT_IGDN) && !(g.debug & 4)) {
+        if (g.act == BASIC_ACT_GDN || g.act == BASIC_ACT_IGDN) {
             f32x16 nrm[MT];
 #pragma unroll
             for (int m = 0; m < MT; ++m)
@@ -989,7 +984,7 @@ __global__ __launch_bounds__(512, 1) void conv5x5_cin4_gdn_persistent_kernel(con
         const int tx_i = bid % g.tiles_x; bid /= g.tiles_x;
         const int ty_i = bid % g.tiles_y; bid /= g.tiles_y;
         const int my = ty_i * TH + ty, mx = tx_i * TW + tx, b = bid * TB + tb;
-        if (lane_live && my < g.mh && mx < g.mw && b < g.batch && !(g.debug & 32)) {
+        if (lane_live && my < g.mh && mx < g.mw && b < g.batch) {
             const int oy = my * g.s_out + g.oy0, ox = mx * g.s_out + g.ox0;
             const int64_t plane = static_cast<int64_t>(g.out_h) * g.out_w;
             // channels of (m, rq, e) are 32 m + 8 rq + 4 khalf + e: one running pointer instead of 64 address products
@@ -1811,19 +1806,14 @@ int pow2_ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 namespace {
 // which launch list forward() walks for this input: 32-channel slices for small position grids, fused column phases when
 // the output rows allow 8-byte pair stores
-struct LaunchChoice { bool use_split, fuse_ok, bf16x3; int dbg; };
+struct LaunchChoice { bool use_split, fuse_ok, bf16x3; };
 LaunchChoice choose_launches(const basic_conv_plan *p, int batch, int oh, int ow, const void *d_out)
 {
     const int64_t pos_blocks = (static_cast<int64_t>(batch) * ((oh + p->s_out - 1) / p->s_out) * ((ow + p->s_out - 1) / p->s_out) + kTilePos - 1) / kTilePos;
+    // BASIC_CONV_DEBUG path bits (tests): 4 force slices, 8 forbid slices, 512 no fused column phases
     const char *dbg_env = getenv("BASIC_CONV_DEBUG");
-    // profiling ablations: 1 skip staging, 2 skip MFMA loop, 4 force slices, 8 forbid slices, 64 no persistent first layer,
-    // 128 no 16-byte patch pieces, 512 no fused column phases
-    int dbg = dbg_env ? atoi(dbg_env) : 0;
-#ifndef BASIC_DEBUG_ABLATIONS
-    dbg &= ~(1 | 2 | 32);   // the timing ablations give WRONG results: only a library built with `make ABLATIONS=1` honours them
-#endif
+    const int dbg = dbg_env ? atoi(dbg_env) : 0;
     LaunchChoice c;
-    c.dbg = dbg;
     c.use_split = !p->split.empty() && !(dbg & 8) && (pos_blocks < kSplitBelowBlocks || (dbg & 4));
     c.fuse_ok = ow % 2 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0 && !(dbg & 512);
     // BASIC_CONV_F32=1: the launches that have a split-bf16 variant run the fp32 kernel instead (A/B runs, tests)
@@ -1862,9 +1852,8 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
         g.tiles_y = (in_h + kSmTileH - 1) / kSmTileH;
         g.tiles_x = (in_w + kSmTileW - 1) / kSmTileW;
         const int blocks = batch * g.tiles_y * g.tiles_x;
-        const char *two = getenv("BASIC_CONV_LAST_2ROW");   // experiment switch: two strips per lane (identical results)
         const bool dma_ok = in_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0;
-        if (dma_ok && (two ? atoi(two) != 0 : in_h >= 64)) {
+        if (dma_ok && in_h >= 64) {   // two strips per lane
             g.tiles_y = (in_h + kSm2TileH - 1) / kSm2TileH;
             hipLaunchKernelGGL(deconv5s2_cout3_dma2_kernel, dim3(batch * g.tiles_y * g.tiles_x), dim3(256), 0, as_stream(hip_stream), g);
         } else if (dma_ok)
@@ -1877,7 +1866,6 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
     // small position grids: spread the output channels over gridDim.y instead of looping them inside a block;
     // fused column phases: even output width (both phases have the same m-grid) and 8-byte aligned rows for the pair stores
     const LaunchChoice choice = choose_launches(p, batch, oh, ow, d_out);
-    const int dbg = choice.dbg;
     const bool use_split = choice.use_split, fuse_ok = choice.fuse_ok;
     for (const Chunk &ch : (use_split ? p->split : p->chunks))
     for (const Phase &ph : ((fuse_ok && !ch.fused.empty()) ? ch.fused : ch.phases)) {
@@ -1894,7 +1882,6 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
         std::memcpy(g.dx, ph.dx, sizeof(g.dx));
         g.act = p->act;
         const int kCK = ph.ck;
-        g.debug = dbg;
         if (choice.bf16x3 && ph.d_wsplit) {
             // split-bf16 path: 256 positions per workgroup, weights through LDS, activations by buffer loads
             int tw = pow2_ceil(g.mw); if (tw > 16) tw = 16;
@@ -1923,13 +1910,13 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
         int th = pow2_ceil(g.mh); if (th > tile_pos / tw) th = tile_pos / tw;
         int tb = tile_pos / (tw * th);
         const bool first_layer_path = ch.mt == 4 && ch.nsplit == 1 && ph.waves == 8 && ph.kh == 5 && ph.kw == 5 &&
-                                      ph.cin_pad == kCK && kCK == 4 && ch.cout == 128 && p->d_gammaT && !(dbg & 64);
+                                      ph.cin_pad == kCK && kCK == 4 && ch.cout == 128 && p->d_gammaT;
         g.ph = (th - 1) * g.s_in + ph.span_y;
         g.pw = (tw - 1) * g.s_in + ph.span_x;
         // Patch rows as whole 16-byte groups aligned to the image (a group is then entirely inside or outside it):
         // 4x fewer DMA instructions per stage.  Needs 16-byte aligned rows; otherwise 4-byte pieces, odd row pitch.
         // (measured: pays for the 8-wave 25-tap convolutions, +1..1.5 %; the wider rows cost the few-tap launches more than they save)
-        g.patch4 = (ph.waves == 8 && !first_layer_path && in_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0 && !(dbg & 128)) ? 1 : 0;
+        g.patch4 = (ph.waves == 8 && !first_layer_path && in_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0) ? 1 : 0;
         g.pwp = g.patch4 ? (g.pw + 3 + 3) / 4 * 4 : (g.pw | 1);
         const int punit = g.patch4 ? 4 : 1;
         const int mtp = mtile_pitch(ch.mt);
@@ -1954,8 +1941,8 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
         hipStream_t st = as_stream(hip_stream);
         if (first_layer_path) {
             // single-stage GDN layer (the first analysis layer): persistent workgroups with resident weights and gamma;
-            // <= 3 input channels: the row-interleaved reduction (BASIC_CONV_DEBUG & 1024 keeps the padded-channel one)
-            const bool rows = ph.d_wrow != nullptr && !(dbg & 1024);
+            // <= 3 input channels: the row-interleaved reduction
+            const bool rows = ph.d_wrow != nullptr;
             const int patch_pad1 = (tb * (rows ? 3 : kCK) * g.ph * g.pwp + 511) / 512 * 512;
             const size_t lds1 = sizeof(float) * ((rows ? 10240 : 12800) + 16384 + 2 * static_cast<size_t>(patch_pad1) + 256 + 4);
             if (lds1 <= 160 * 1024 && patch_pad1 <= kFirstSlots * 512) {

@@ -27,8 +27,8 @@
 //   Masked / padded elements enter as zeros and all-masked slabs are skipped: both leave every partial and the total
 //   unchanged (x + 0 = x), so skipping is a pure optimisation and may differ between tiles and kernels.
 // The three kernels differ only in where the parallelism comes from:
-//   masked_conv_dma_kernel      GEMM-shaped launches (>= thousands of positions, 128-row output chunks): 8-wave workgroup =
-//                               128 rows x 256 positions, operands through LDS by LDS-DMA (weights: 16-byte pieces of a
+//   masked_conv_dma_kernel      GEMM-shaped launches (>= thousands of positions, 128-row output chunks): 4-wave workgroup =
+//                               128 rows x 128 positions, operands through LDS by LDS-DMA (weights: 16-byte pieces of a
 //                               pre-packed slab; activations: buffer loads with the channel offset on the scalar unit and
 //                               out-of-range = masked lanes writing zeros), two stage buffers, an unrolled MFMA stage of
 //                               LDS reads with immediate offsets -- an activation element is fetched once per workgroup;
@@ -86,7 +86,6 @@ struct MaskedLaunch {
     int units, blocks_per_slab;
     // dma kernel
     int n_pchunks, n_rchunks, x_bytes;
-    int debug;   // BASIC_MCONV_DEBUG dma kernel: timing ablations (wrong results) 1 no staging, 4 no stores
 };
 
 constexpr int kNoStep = INT32_MIN;
@@ -364,37 +363,32 @@ __global__ __launch_bounds__(256) void masked_conv_reduce_kernel(const MaskedLau
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// GEMM-shaped launches.  Workgroup = 8 waves = one 128-row chunk of an output channel group x 256 listed positions; wave w
+// GEMM-shaped launches.  Workgroup = 4 waves = one 128-row chunk of an output channel group x 128 listed positions; wave w
 // owns all 128 rows (4 accumulator tiles) of positions 32w .. 32w+31.  K is walked kDmaCK = 32 channels of one (tap, input
-// group) slab per stage through three LDS stage buffers { A [32 k][32 cols][4 tiles] | B [32 k][256 positions] } filled by
-// LDS-DMA a stage and a half ahead of the MFMAs:
-//   A  16-byte pieces of the pre-packed slab [row chunk][tap][ci][32][4] (contiguous per stage: two instructions per lane);
+// group) slab per stage through two LDS stage buffers of 32 KB { A [32 k][32 cols][4 tiles] | B [32 k][128 positions] }
+// filled by LDS-DMA a stage ahead of the MFMAs:
+//   A  16-byte pieces of the pre-packed slab [row chunk][tap][ci][32][4] (contiguous per stage: four instructions per lane);
 //   B  buffer_load_dword ... lds, one position per lane: the lane's byte offset of (image, neighbour position) in a VGPR --
 //      0x80000000 = out of range = the hardware writes ZERO for a masked / padded / unlisted element -- and the channel
 //      offset in an SGPR, so a stage's 16 gathers cost no vector ALU work at all.
 // A stage is 16 unrolled steps of { ds_read_b32 (B), ds_read_b128 (A), 4 MFMAs } with compile-time LDS offsets; two stages
 // make one canonical block, whose chain starts from zero and is added to the running total at the first step of the next
-// block (the adds sit between MFMAs of other tiles).  Slabs that are closed for all 256 positions are skipped.
+// block (the adds sit between MFMAs of other tiles).  Slabs that are closed for all 128 positions are skipped.
 // Workgroups are dealt to the XCDs so that all row chunks of one position chunk run on the SAME XCD back to back: the
-// position chunk's activations (256 x Cin x 4 bytes) come out of the fabric once and are re-read from that XCD's L2.
+// position chunk's activations (128 x Cin x 4 bytes) come out of the fabric once and are re-read from that XCD's L2.
+// TWO workgroups per compute unit: the co-resident one covers the pause at the stage barrier.
 // ---------------------------------------------------------------------------------------------------------------------
-// WAVES = 8: the shape above (three stage buffers of 48 KB, one workgroup per compute unit).  WAVES = 4: 128 positions per
-// workgroup, two stage buffers of 32 KB, TWO workgroups per compute unit -- for launches whose 8-wave grid would be only a
-// round or two of the chip (the 384-row layers: 384 workgroups on 256 compute units take two rounds for one and a half
-// rounds of work); twice as many, half as long workgroups cut that tail, at the price of staging the weights twice as often.
 constexpr int kDmaCK = 32, kDmaRows = 128;
+constexpr int kDmaWaves = 4, kDmaThreads = 64 * kDmaWaves, kDmaPos = 32 * kDmaWaves;
 constexpr int kDmaAFloats = kDmaCK * 32 * 4;
+constexpr int kDmaBufs = 2, kDmaStage = kDmaAFloats + kDmaCK * kDmaPos;   // stage buffers, floats per stage buffer
+constexpr size_t kDmaLdsBytes = (kDmaBufs * kDmaStage + 64 + kDmaRows) * sizeof(float);
 constexpr int kDmaMaxSlabs = 64;
 constexpr unsigned kOutOfRange = 0x80000000u;
-constexpr int dma_bufs(int waves) { return waves == 8 ? 3 : 2; }
-constexpr int dma_stage_floats(int waves) { return kDmaAFloats + kDmaCK * 32 * waves; }
-constexpr size_t dma_lds_bytes(int waves) { return (dma_bufs(waves) * dma_stage_floats(waves) + 64 + kDmaRows) * sizeof(float); }
 
-template <int WAVES>
-__global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 1 : 2)) void masked_conv_dma_kernel(const MaskedLaunch g)
+__global__ __launch_bounds__(kDmaThreads, 2) void masked_conv_dma_kernel(const MaskedLaunch g)
 {
-    constexpr int kDmaThreads = 64 * WAVES, kDmaPos = 32 * WAVES, kDmaStage = dma_stage_floats(WAVES), kDmaBufs = dma_bufs(WAVES);
-    constexpr int kChunks = WAVES / 2;                 // 64-position pieces of a B row (4-byte gathers: one piece per wave instruction)
+    constexpr int kChunks = kDmaWaves / 2;             // 64-position pieces of a B row (4-byte gathers: one piece per wave instruction)
     constexpr int kAPieces = kDmaAFloats / (kDmaThreads * 4);
     extern __shared__ float lds[];
     unsigned *s_open = reinterpret_cast<unsigned *>(lds + kDmaBufs * kDmaStage);   // [2] slab bitmask, [2] step-rule flag
@@ -470,10 +464,10 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 1 : 2)) void masked_conv_
     };
     unsigned voff = nstages > 0 ? slab_voffset(is_slab, is_t) : kOutOfRange;
 
-    // The DMA of one stage = 2 pieces of A (16 bytes per lane) + 16 gathers of B, then the issue state moves on.  It is issued in
-    // PIECES spread over the MFMA steps that follow the stage barrier: a wave that issues its 18 vector-memory instructions
+    // The DMA of one stage = 4 pieces of A (16 bytes per lane) + 16 gathers of B, then the issue state moves on.  It is issued in
+    // PIECES spread over the MFMA steps that follow the stage barrier: a wave that issues its 20 vector-memory instructions
     // back to back blocks in the issue stage until the texture-address unit has taken them (~33 cycles per 64-lane gather, all
-    // eight waves at once: thousands of cycles without an MFMA, measured as +20 % kernel time).
+    // waves at once: thousands of cycles without an MFMA, measured on the 8-wave shape as +20 % kernel time).
     int ci0_i = 0;
     float *dst_i = nullptr;
     const float *srca_i = nullptr;
@@ -509,26 +503,13 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 1 : 2)) void masked_conv_
         BASIC_MCONV_ISSUE_END();                                                                                                \
     } while (0)
 
-    // Pipeline, WAVES = 8: THREE stage buffers and ONE workgroup barrier per stage, placed in the MIDDLE of the stage.  At the
-    // barrier of stage n every wave has waited for its own DMAs of stage n+1 (issued a whole stage earlier) -- so after it
-    // stage n+1 is complete in LDS -- and every wave has left stage n-1, whose buffer the DMA of stage n+2 (issued in pieces
-    // over the steps after the barrier) overwrites.  The MFMA stream of a wave runs across stage boundaries without a pause:
-    // the first fragments of stage n+1 are read during the last step of stage n.
-    // WAVES = 4: TWO buffers, the barrier at the START of stage n (stage n has landed, everyone has left stage n-1), then the
-    // DMA of stage n+1 in pieces; the co-resident workgroup covers the pause at the barrier.
-    constexpr int kSteps = kDmaCK / 2, kBar = kDmaBufs == 3 ? kSteps / 2 : 0;
-    if (nstages > 0 && !(g.debug & 1)) {
-        BASIC_MCONV_ISSUE(0);
-        if (kDmaBufs == 3 && nstages > 1) BASIC_MCONV_ISSUE(1);
-    }
+    // Pipeline: the barrier at the START of stage n (stage n has landed, everyone has left stage n-1), then the DMA of stage
+    // n+1 into the other buffer, in pieces over the first half of the stage's steps.
+    constexpr int kSteps = kDmaCK / 2;
+    if (nstages > 0) BASIC_MCONV_ISSUE(0);
     const int a_lane = (khalf * 32 + col) * 4, b_lane = khalf * kDmaPos + wave * 32 + col;
     float fb[2];
     f32x4 fa[2];
-    if (kDmaBufs == 3) {
-        __syncthreads();   // stages 0 and 1 have landed
-        fb[0] = lds[kDmaAFloats + b_lane];
-        fa[0] = *reinterpret_cast<const f32x4 *>(lds + a_lane);
-    }
     int buf = 0;   // stage buffer of the current stage (stg % kDmaBufs)
     // one stage: 16 steps of { next step's LDS reads, 4 MFMAs }.  FIRST = first stage of a canonical block: the chain starts
     // from an inline-constant 0 (no register initialisation).
@@ -536,32 +517,23 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 1 : 2)) void masked_conv_
         constexpr bool kFirst = decltype(first_tag)::value;
         const int nbuf = buf == kDmaBufs - 1 ? 0 : buf + 1;
         const float *al = lds + buf * kDmaStage + a_lane, *bl = al + (kDmaAFloats + b_lane - a_lane);
-        const float *aln = lds + nbuf * kDmaStage + a_lane, *bln = aln + (kDmaAFloats + b_lane - a_lane);
-        const bool issuing = stg + (kDmaBufs - 1) < nstages && !(g.debug & 1);
+        const bool issuing = stg + 1 < nstages;
+        __syncthreads();   // vmcnt(0): my DMAs of this stage have landed; barrier: everyone's have, and the other buffer is free
+        if (issuing) BASIC_MCONV_ISSUE_BEGIN(nbuf);
+        fb[0] = bl[0];
+        fa[0] = *reinterpret_cast<const f32x4 *>(al);
 #pragma unroll
         for (int st = 0; st < kSteps; ++st) {
             const int cur = st & 1, nxt = cur ^ 1;
-            if (st == kBar) {
-                __syncthreads();   // vmcnt(0): my DMAs of the next stage to be read have landed; barrier: everyone's have, and the oldest buffer is free
-                if (issuing) BASIC_MCONV_ISSUE_BEGIN(kDmaBufs == 3 ? (buf == 0 ? 2 : buf - 1) : nbuf);
-                if (kDmaBufs == 2) {
-                    fb[0] = bl[0];
-                    fa[0] = *reinterpret_cast<const f32x4 *>(al);
-                }
-            }
-            if (st >= kBar && st < kBar + kSteps / 2 && issuing) {   // the next DMA, two or three pieces per step
-                const int q = st - kBar;
-                if (q < kAPieces) BASIC_MCONV_ISSUE_A(q);
-                BASIC_MCONV_ISSUE_B(2 * q);
-                BASIC_MCONV_ISSUE_B(2 * q + 1);
-                if (q == kSteps / 2 - 1) BASIC_MCONV_ISSUE_END();
+            if (st < kSteps / 2 && issuing) {   // the next DMA, two or three pieces per step
+                if (st < kAPieces) BASIC_MCONV_ISSUE_A(st);
+                BASIC_MCONV_ISSUE_B(2 * st);
+                BASIC_MCONV_ISSUE_B(2 * st + 1);
+                if (st == kSteps / 2 - 1) BASIC_MCONV_ISSUE_END();
             }
             if (st + 1 < kSteps) {
                 fb[nxt] = bl[(st + 1) * 2 * kDmaPos];
                 fa[nxt] = *reinterpret_cast<const f32x4 *>(al + (st + 1) * 2 * 128);
-            } else if (kDmaBufs == 3) {   // first fragments of the next stage (complete since this stage's barrier; a harmless read after the last stage)
-                fb[nxt] = bln[0];
-                fa[nxt] = *reinterpret_cast<const f32x4 *>(aln);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (kFirst && st == 0) {
@@ -591,7 +563,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 1 : 2)) void masked_conv_
 #undef BASIC_MCONV_ISSUE_B
 #undef BASIC_MCONV_ISSUE_END
 
-    if (mp.ok && !(g.debug & 4)) {
+    if (mp.ok) {
         float *yb = g.y + (static_cast<int64_t>(mp.b) * g.out_total + g.out_off + row0) * hw + out_slot(g, mp);
 #pragma unroll
         for (int m = 0; m < 4; ++m)
@@ -663,10 +635,6 @@ extern "C" int basic_mconv_plan_create(const float *weight, const float *bias, i
     if (const char *e = std::getenv("BASIC_MCONV_MAX_MT")) {  // tests: one tile per wave as the comparison point
         if (p->mt > std::atoi(e)) p->mt = 1;
     }
-    if (const char *e = std::getenv("BASIC_MCONV_FORCE_MT")) {  // tuning: another pack factor where it divides the group's tiles
-        const int f = std::atoi(e);
-        if (f >= 1 && f <= 4 && gs_out % (32 * f) == 0) p->mt = f;
-    }
     const int span = 32 * p->mt;
     std::vector<float> wp(static_cast<size_t>(ntaps) * cin * p->coutp, 0.f), hb(p->coutp, 0.f);
     std::vector<float> w1(p->mt > 1 ? wp.size() : 0, 0.f);
@@ -694,8 +662,7 @@ extern "C" int basic_mconv_plan_create(const float *weight, const float *bias, i
     if (e == hipSuccess && p->mt > 1) e = upload(&p->d_w1, w1);
     if (e == hipSuccess && dma) e = upload(&p->d_wa, wa);
     if (e == hipSuccess) e = upload(&p->d_bias, hb);
-    if (e == hipSuccess && dma) e = ensure_max_lds(reinterpret_cast<const void *>(&masked_conv_dma_kernel<8>));
-    if (e == hipSuccess && dma) e = ensure_max_lds(reinterpret_cast<const void *>(&masked_conv_dma_kernel<4>));
+    if (e == hipSuccess && dma) e = ensure_max_lds(reinterpret_cast<const void *>(&masked_conv_dma_kernel));
     if (e != hipSuccess) { basic_mconv_plan_destroy(p); return hip_fail(e, "mconv_plan_create", __FILE__, __LINE__); }
     *out = p;
     return BASIC_OK;
@@ -760,17 +727,15 @@ static int mconv_forward(const basic_mconv_plan *p, const float *d_x, const int3
     hipStream_t st = as_stream(hip_stream);
     // Which kernel: every one of them sums in the canonical order, so this is a matter of speed only and may depend on the
     // launch size.  BASIC_MCONV_KERNEL = dma | gather | block forces one where it applies (tests drive all three over the
-    // same inputs and require identical bits); BASIC_MCONV_BLOCK_BELOW / _DMA_FROM move the switch-overs (tile counts).
+    // same inputs and require identical bits).  The switch-overs are in (position tile x row tile) counts.
     const int64_t tiles = static_cast<int64_t>(ptiles) * rtiles;
-    int64_t block_below = 256, dma_from = 4096;
-    if (const char *e = std::getenv("BASIC_MCONV_BLOCK_BELOW")) block_below = std::atoll(e);
-    if (const char *e = std::getenv("BASIC_MCONV_DMA_FROM")) dma_from = std::atoll(e);
+    constexpr int64_t kBlockBelow = 256, kDmaFrom = 4096;
     const char *force = std::getenv("BASIC_MCONV_KERNEL");
     const int64_t x_bytes = static_cast<int64_t>(batch) * p->cin * h * w * 4;
     const int blocks_per_slab = (g.gs_in + kKB - 1) / kKB;
     const int64_t units = static_cast<int64_t>(g.ntaps) * g.gi * blocks_per_slab;
-    bool use_dma = p->d_wa && x_bytes < (1ll << 31) && tiles >= dma_from;
-    bool use_block = !use_dma && tiles < block_below && tiles * units <= kMaxUnits;
+    bool use_dma = p->d_wa && x_bytes < (1ll << 31) && tiles >= kDmaFrom;
+    bool use_block = !use_dma && tiles < kBlockBelow && tiles * units <= kMaxUnits;
     if (force) {
         if (!std::strcmp(force, "dma")) { use_dma = p->d_wa && x_bytes < (1ll << 31); use_block = false; }
         else if (!std::strcmp(force, "block")) { use_dma = false; use_block = tiles * units <= kMaxUnits; }
@@ -780,22 +745,13 @@ static int mconv_forward(const basic_mconv_plan *p, const float *d_x, const int3
         g.w = p->d_wa;
         g.n_rchunks = p->cout / kDmaRows;
         g.x_bytes = static_cast<int>(x_bytes);
-#ifdef BASIC_DEBUG_ABLATIONS   // timing ablations (wrong results): only in a library built with `make ABLATIONS=1`
-        { const char *e = std::getenv("BASIC_MCONV_DEBUG"); g.debug = e ? std::atoi(e) : 0; }
-#else
-        g.debug = 0;
-#endif
-        // 4 waves (128 positions per workgroup, two workgroups per compute unit) or 8 (256 positions, one workgroup);
-        // BASIC_MCONV_DMA_WAVES picks one
-        // measured (scripts/mconv_probe.py, warm clocks): the 4-wave shape is never slower -- 0.899 vs 0.905 ms on the 1536 -> 1536
-        // layer, 0.31 vs 0.40 / 0.48 vs 0.60 ms on the 384-row layers whose 8-wave grid is one and a half rounds of the chip
-        int waves = 4;
-        if (const char *e = std::getenv("BASIC_MCONV_DMA_WAVES")) waves = std::atoi(e) == 8 ? 8 : 4;
-        const int ppw = 32 * waves;
-        g.n_pchunks = static_cast<int>((n_pos + ppw - 1) / ppw);
+        // 4 waves, 128 positions per workgroup, two workgroups per compute unit.  Measured against an 8-wave shape (256
+        // positions, three stage buffers, one workgroup per unit; scripts/mconv_probe.py at commit 1c1d741, warm clocks): the
+        // 4-wave shape is never slower -- 0.899 vs 0.905 ms on the 1536 -> 1536 layer, 0.31 vs 0.40 / 0.48 vs 0.60 ms on the
+        // 384-row layers whose 8-wave grid is one and a half rounds of the chip.
+        g.n_pchunks = static_cast<int>((n_pos + kDmaPos - 1) / kDmaPos);
         const unsigned grid = static_cast<unsigned>((g.n_pchunks + 7) / 8 * 8) * g.n_rchunks;
-        if (waves == 8) hipLaunchKernelGGL(masked_conv_dma_kernel<8>, dim3(grid), dim3(512), dma_lds_bytes(8), st, g);
-        else hipLaunchKernelGGL(masked_conv_dma_kernel<4>, dim3(grid), dim3(256), dma_lds_bytes(4), st, g);
+        hipLaunchKernelGGL(masked_conv_dma_kernel, dim3(grid), dim3(kDmaThreads), kDmaLdsBytes, st, g);
     } else if (use_block) {
         {
             std::lock_guard<std::mutex> lock(p->mu);

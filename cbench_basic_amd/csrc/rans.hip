@@ -1229,8 +1229,7 @@ extern "C" int basic_rans_encode_batch_dev(const basic_rans_tables *t, const int
     BASIC_REQUIRE(d_symbols && d_indexes && d_seg && d_out_words && d_out_nwords && nstreams >= 1 && slot_words >= 2,
                   "rans_encode_batch: bad argument");
     BASIC_REQUIRE(!t->d_ar, "rans_encode_batch: AR tables are only supported by the host-buffer entry points");
-    static const bool no_fast = getenv("BASIC_RANS_NO_FAST_ENCODE") != nullptr;  // profiling ablation
-    if (t->fast_enc_ok && !no_fast) {
+    if (t->fast_enc_ok) {
         // Packed launches (several streams per workgroup) exist to share the chip with transforms on other HIP streams.
         // The encoder needs almost no LDS, so a convolution workgroup would settle on the same compute unit -- and its
         // LDS-DMA traffic then owns that unit's vector-memory queue: the encoder's table gathers wait behind it and the

@@ -72,13 +72,12 @@ struct ScanArgs {
     int tap_off[kMaxTaps], tap_dy[kMaxTaps], tap_dx[kMaxTaps];
     int bc, xs_off, ps_off, tab_off, part_off, part_floats, flag_off, bias_off;   // LDS float offsets (the whole LDS is dynamic)
     int x0_off, early_off, desc_off;   // pipelined kernel only: context window [B][K0], early sums, unit descriptors
+    int ncompute;          // workgroups [0, ncompute) compute, the rest decode (4 image streams each)
     unsigned *bar;
     int *err;
-    int debug;   // BASIC_SCAN_DEBUG timing ablations (wrong results): 2 no input staging, 4 no dot products
     long long *prof;   // BASIC_SCAN_PROFILE=1: [layer][4] 100 MHz ticks of workgroup 0 spent staging (incl. waiting) / in the block dots / finishing / in the
                        // Gaussian step, summed over the steps; [4 * kMaxLayers .. +1] = shader clocks and ticks of the whole loop
     // decoder only
-    int ncompute;          // workgroups [0, ncompute) compute, the rest decode (4 image streams each)
     uint64_t *mu;          // [B][C] means of the current step (compute -> decoder workgroups), granules
     uint64_t *idx_step;    // [B][C] table rows of the current step, granules (the row's bits in the value half)
     RansFastView tv;
@@ -398,7 +397,6 @@ __global__ __launch_bounds__(kThreads) void scanline_persistent_kernel(const Sca
             const int r_first = wg * a.rpw[l];
             for (int b0 = 0; b0 < a.B; b0 += a.bc) {
                 const int nb = (a.B - b0) < a.bc ? (a.B - b0) : a.bc;
-                bool ok = true;
                 const long long t0 = a.prof ? wall_clock64() : 0;
                 // encoder: this thread's latent of the Gaussian step, requested before the last layer's inputs are waited for
                 float y_pre = 0.f;
@@ -406,7 +404,7 @@ __global__ __launch_bounds__(kThreads) void scanline_persistent_kernel(const Sca
                     const int bi = tid / (rw >> 1), j = tid - bi * (rw >> 1);
                     y_pre = a.y[((static_cast<int64_t>(b0 + bi)) * a.C + (r_first >> 1) + j) * HW + p];
                 }
-                if (!(a.debug & 2)) ok = stage_inputs(a, l, p, py, px, b0, nb, xs);
+                const bool ok = stage_inputs(a, l, p, py, px, b0, nb, xs);
                 if (!ok) *s_flag = 1;    // (a flag in the dynamic LDS: __syncthreads_or would add static LDS on top of the 160 KB)
                 __syncthreads();
                 if (*s_flag) return;     // poisoned launch: the whole workgroup leaves
@@ -414,7 +412,7 @@ __global__ __launch_bounds__(kThreads) void scanline_persistent_kernel(const Sca
                 long long t2 = t1, t3 = t1;
                 // units = (canonical block, image, row), one FMA chain each; `part` holds one round of partials as
                 // [block][item]; the finishing threads add an item's partials in block order, then bias and activation
-                const int items = (a.debug & 4) ? 0 : nb * rw, Kp = a.kpad[l];
+                const int items = nb * rw, Kp = a.kpad[l];
                 const int kg = a.kgroup[l], bpg = a.bpg[l], nblk = (K / kg) * bpg;
                 const int per_round = items < a.part_floats / nblk ? items : a.part_floats / nblk;
                 for (int i0 = 0; i0 < items; i0 += per_round) {
@@ -1561,8 +1559,7 @@ extern "C" int basic_scanline_plan_create(const float *ctx_weight, const float *
     // three launches of concurrent stream workers then hold 195 of the 256 compute units and leave the rest to the transforms;
     // with 112 KB it was 77 and the workers' transforms queued behind the persistent launches); every layer in whole rows per workgroup, the
     // last one in whole (mean, scale) pairs
-    const char *wk = getenv("BASIC_SCAN_WEIGHT_KB");   // experiments: LDS budget of a workgroup's weight slices
-    const size_t weight_kb = wk && atoi(wk) >= 16 && atoi(wk) <= 150 ? static_cast<size_t>(atoi(wk)) : 126;
+    constexpr size_t kWeightKB = 126;
     int nwg = 1;
     for (;; ++nwg) {
         int floats = 0;
@@ -1571,7 +1568,7 @@ extern "C" int basic_scanline_plan_create(const float *ctx_weight, const float *
             if (l == p->nlayers - 1) rpw = (rpw + 1) & ~1;
             floats += rpw * p->kpad[l];
         }
-        if (floats * sizeof(float) <= weight_kb * 1024 || nwg >= 192) { p->weight_floats = floats; break; }
+        if (floats * sizeof(float) <= kWeightKB * 1024 || nwg >= 192) { p->weight_floats = floats; break; }
     }
     if (p->weight_floats * sizeof(float) > 150 * 1024) {
         delete p;
@@ -1664,9 +1661,13 @@ namespace {
 
 size_t align4(size_t n) { return (n + 3) & ~static_cast<size_t>(3); }
 
-// fills the launch arguments shared by both directions; *lds_bytes = LDS of a compute workgroup
+// which scan-line kernel a launch runs (kAuto: the one the launch fits best)
+enum class ScanKernel { kAuto, kGeneric, kPipelined, kBatched };
+
+// fills the launch arguments of the generic / pipelined kernels, shared by both directions; *lds_bytes = LDS of a compute
+// workgroup.  The pipelined kernel is taken when it fits, unless `force` names the generic one.
 int fill_args(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
-              size_t *lds_bytes, bool *pipelined, hipStream_t st)
+              ScanKernel force, size_t *lds_bytes, bool *pipelined, hipStream_t st)
 {
     const int64_t HW = static_cast<int64_t>(h) * w;
     a.B = batch; a.C = p->C; a.H = h; a.W = w; a.P = p->P;
@@ -1735,7 +1736,7 @@ int fill_args(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, cons
     for (int l = 0; l < p->nlayers; ++l) bias_floats += p->rpw[l];
     *lds_bytes = static_cast<size_t>(a.bias_off + static_cast<int>(align4(bias_floats))) * sizeof(float);
     // pipelined kernel: [weights][table][biases][context window B x K0][dense inputs B x Kd][partials][early sums][unit descriptors][flag]
-    // -- taken when all of it fits (BASIC_SCAN_KERNEL=generic|pipelined overrides; results are identical either way)
+    // -- taken when all of it fits (results are identical either way)
     {
         int kd = 0, units_total = 0, units_max = 0;
         for (int l = 0; l < p->nlayers; ++l) {
@@ -1757,9 +1758,8 @@ int fill_args(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, cons
         bool fits = flag_off + 4 <= static_cast<size_t>(total_floats) && p->vec4 && (p->ntaps - 1) * (p->C / 2) <= kWinU * kThreads &&
                     w >= p->ksize / 2 + 2;
         for (int l = 0; l < p->nlayers; ++l) fits = fits && batch * p->rpw[l] <= kThreads;   // one finishing item per thread
-        const char *e = getenv("BASIC_SCAN_KERNEL");
-        if (e && !strcmp(e, "generic")) fits = false;
-        if (e && !strcmp(e, "pipelined")) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=pipelined, but this batch does not fit the LDS");
+        if (force == ScanKernel::kGeneric) fits = false;
+        if (force == ScanKernel::kPipelined) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=pipelined, but this batch does not fit the LDS");
         *pipelined = fits;
         if (fits) {
             a.bias_off = static_cast<int>(bias_off); a.x0_off = static_cast<int>(x0_off); a.xs_off = static_cast<int>(xs_off);
@@ -1771,11 +1771,6 @@ int fill_args(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, cons
     }
     a.bar = p->d_bar;
     a.err = reinterpret_cast<int *>(p->d_bar + 1);
-#ifdef BASIC_DEBUG_ABLATIONS   // timing ablations (wrong results): only in a library built with `make ABLATIONS=1`
-    { const char *e = getenv("BASIC_SCAN_DEBUG"); a.debug = e ? atoi(e) : 0; }
-#else
-    a.debug = 0;
-#endif
     BASIC_HIP_TRY(hipMemsetAsync(p->d_bar, 0, 2 * sizeof(unsigned), st));
     return BASIC_OK;
 }
@@ -1790,19 +1785,6 @@ bool batched_fits(const basic_scanline_plan *p, int batch, int w, int ndec, int 
     if (!p->batched || batch < 1 || batch > 32 * kBatchedMaxTiles || w < p->ksize / 2 + 2) return false;
     const int tiles = (batch + 31) / 32;
     return tiles * p->b_nw + ndec <= cus;
-}
-
-// 0 = generic / pipelined kernels, 1 = batched.  BASIC_SCAN_KERNEL=batched|generic|pipelined forces one (identical results)
-int choose_batched(const basic_scanline_plan *p, int batch, int w, int ndec, int cus, bool *batched)
-{
-    const bool fits = batched_fits(p, batch, w, ndec, cus);
-    const char *e = getenv("BASIC_SCAN_KERNEL");
-    if (e && !strcmp(e, "batched")) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=batched, but this call does not fit the batched kernel");
-    if (e && (!strcmp(e, "generic") || !strcmp(e, "pipelined"))) { *batched = false; return BASIC_OK; }
-    const char *m = getenv("BASIC_SCAN_BATCHED_FROM");   // smallest batch the batched kernel takes by default
-    const int from = m && atoi(m) >= 1 ? atoi(m) : 3;
-    *batched = fits && (batch >= from || (e && !strcmp(e, "batched")));
-    return BASIC_OK;
 }
 
 int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
@@ -1859,7 +1841,6 @@ int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int
     *lds_bytes = (align4(table_len) + 4 + 96 + static_cast<size_t>(p->b_tiles) * kBTile) * sizeof(float);   // table, flags, biases, partial tiles
     a.bar = p->d_bar;
     a.err = reinterpret_cast<int *>(p->d_bar + 1);
-    a.debug = 0;
     BASIC_HIP_TRY(hipMemsetAsync(p->d_bar, 0, 2 * sizeof(unsigned), st));
     return BASIC_OK;
 }
@@ -1918,6 +1899,85 @@ int device_cus(int *cus)
     return BASIC_OK;
 }
 
+// decoder workgroups of `batch` image streams (one wavefront per stream)
+int decoder_workgroups(int batch) { return (batch + kThreads / 64 - 1) / (kThreads / 64); }
+
+// LDS of a decoder workgroup: the fast search image of the table set
+size_t decoder_lds_bytes(const RansFastView &tv)
+{
+    return (static_cast<size_t>((tv.image_words + 3) & ~3) + 4 * static_cast<size_t>(tv.rows) + 4) * sizeof(uint32_t);
+}
+
+struct ScanLaunch {
+    ScanKernel kernel;   // kGeneric, kPipelined or kBatched
+    int grid;            // compute workgroups, then the decoder workgroups
+    int ncompute;
+    int cus;
+    size_t lds_bytes;
+};
+
+// The one place that decides how a scan-line call runs: which kernel (the batched one from 3 images on where it fits, else the
+// pipelined one where it fits, else the generic one; BASIC_SCAN_KERNEL = generic | pipelined | batched forces one, with
+// identical results), its grid and its LDS.  Fills the launch arguments; `tables` != nullptr: decode.
+int prepare_launch(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
+                   const basic_rans_tables *tables, hipStream_t st, ScanLaunch *L)
+{
+    ScanKernel force = ScanKernel::kAuto;
+    if (const char *e = getenv("BASIC_SCAN_KERNEL")) {
+        if (!strcmp(e, "generic")) force = ScanKernel::kGeneric;
+        else if (!strcmp(e, "pipelined")) force = ScanKernel::kPipelined;
+        else if (!strcmp(e, "batched")) force = ScanKernel::kBatched;
+    }
+    const bool decode = tables != nullptr;
+    if (decode) {
+        const int rc = rans_fast_view(tables, &a.tv);
+        if (rc) return rc;
+    }
+    const int ndec = decode ? decoder_workgroups(batch) : 0;
+    int rc = device_cus(&L->cus);
+    if (rc) return rc;
+    const bool fits = batched_fits(p, batch, w, ndec, L->cus);
+    if (force == ScanKernel::kBatched) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=batched, but this call does not fit the batched kernel");
+    if (force == ScanKernel::kBatched || (force == ScanKernel::kAuto && fits && batch >= 3)) {
+        rc = fill_args_batched(p, a, batch, h, w, d_prior, d_table, table_len, &L->lds_bytes, st);
+        if (rc) return rc;
+        L->kernel = ScanKernel::kBatched;
+        L->ncompute = (a.nbt / 32) * p->b_nw;   // batched_fits: the grid is resident
+    } else {
+        bool pipelined = false;
+        rc = fill_args(p, a, batch, h, w, d_prior, d_table, table_len, force, &L->lds_bytes, &pipelined, st);
+        if (rc) return rc;
+        L->kernel = pipelined ? ScanKernel::kPipelined : ScanKernel::kGeneric;
+        L->ncompute = p->nwg;
+        BASIC_REQUIRE(p->nwg + ndec <= L->cus, "scanline: more workgroups than compute units (the grid must be resident)");
+    }
+    a.ncompute = L->ncompute;
+    L->grid = L->ncompute + ndec;
+    if (decode) L->lds_bytes = std::max(L->lds_bytes, decoder_lds_bytes(a.tv));
+    // more than half of a compute unit's LDS per workgroup: exactly one workgroup per unit, as the barrier protocol assumes
+    if (L->lds_bytes < 96 * 1024) L->lds_bytes = 96 * 1024;
+    BASIC_REQUIRE(L->lds_bytes <= 160 * 1024, "scanline: a workgroup's LDS (decoder: the search image) does not fit");
+    return BASIC_OK;
+}
+
+template <bool DECODE> int run_launch(basic_scanline_plan *p, ScanArgs &a, const ScanLaunch &L, hipStream_t st)
+{
+    const void *fn = L.kernel == ScanKernel::kBatched     ? reinterpret_cast<const void *>(scanline_batched_kernel<DECODE>)
+                     : L.kernel == ScanKernel::kPipelined ? reinterpret_cast<const void *>(scanline_pipelined_kernel<DECODE>)
+                                                          : reinterpret_cast<const void *>(scanline_persistent_kernel<DECODE>);
+    BASIC_HIP_TRY(ensure_max_lds(fn));
+    ScanProfile prof;
+    int rc = prof.begin(a, st);
+    if (rc) return rc;
+    rc = chained_launch(p, st, L.grid, L.cus, [&] {
+        if (L.kernel == ScanKernel::kBatched) hipLaunchKernelGGL(scanline_batched_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
+        else if (L.kernel == ScanKernel::kPipelined) hipLaunchKernelGGL(scanline_pipelined_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
+        else hipLaunchKernelGGL(scanline_persistent_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
+    });
+    prof.report(a, st, L.kernel == ScanKernel::kBatched ? (DECODE ? "decode (batched)" : "encode (batched)") : (DECODE ? "decode" : "encode"));
+    return rc;
+}
+
 }  // namespace
 
 extern "C" int basic_scanline_encode_dev(basic_scanline_plan *p, const float *d_y, const float *d_prior, int batch, int h, int w,
@@ -1929,46 +1989,11 @@ extern "C" int basic_scanline_encode_dev(basic_scanline_plan *p, const float *d_
                   "scanline_encode: bad argument");
     hipStream_t st = as_stream(hip_stream);
     ScanArgs a{};
-    size_t lds_bytes = 0;
-    bool pipelined = false, batched = false;
-    int cus = 0;
-    int rc = device_cus(&cus);
-    if (rc) return rc;
-    rc = choose_batched(p, batch, w, 0, cus, &batched);
-    if (rc) return rc;
-    if (batched) {
-        rc = fill_args_batched(p, a, batch, h, w, d_prior, d_table, table_len, &lds_bytes, st);
-        if (rc) return rc;
-        a.y = d_y; a.ybuf = d_ybuf; a.sym = d_symbols; a.idx = d_indexes;
-        const int grid = (a.nbt / 32) * p->b_nw;
-        a.ncompute = grid;
-        if (lds_bytes < 96 * 1024) lds_bytes = 96 * 1024;   // one workgroup per compute unit
-        BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(scanline_batched_kernel<false>)));
-        ScanProfile prof;
-        rc = prof.begin(a, st);
-        if (rc) return rc;
-        rc = chained_launch(p, st, grid, cus, [&] { hipLaunchKernelGGL(scanline_batched_kernel<false>, dim3(grid), dim3(kThreads), lds_bytes, st, a); });
-        prof.report(a, st, "encode (batched)");
-        return rc;
-    }
-    rc = fill_args(p, a, batch, h, w, d_prior, d_table, table_len, &lds_bytes, &pipelined, st);
+    ScanLaunch L{};
+    const int rc = prepare_launch(p, a, batch, h, w, d_prior, d_table, table_len, nullptr, st, &L);
     if (rc) return rc;
     a.y = d_y; a.ybuf = d_ybuf; a.sym = d_symbols; a.idx = d_indexes;
-    a.ncompute = p->nwg;
-    BASIC_REQUIRE(p->nwg <= cus, "scanline_encode: more workgroups than compute units (the grid must be resident)");
-    // more than half of a compute unit's LDS per workgroup: exactly one workgroup per unit, as the barrier protocol assumes
-    if (lds_bytes < 96 * 1024) lds_bytes = 96 * 1024;
-    BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(scanline_persistent_kernel<false>)));
-    BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(scanline_pipelined_kernel<false>)));
-    ScanProfile prof;
-    rc = prof.begin(a, st);
-    if (rc) return rc;
-    rc = chained_launch(p, st, p->nwg, cus, [&] {
-        if (pipelined) hipLaunchKernelGGL(scanline_pipelined_kernel<false>, dim3(p->nwg), dim3(kThreads), lds_bytes, st, a);
-        else hipLaunchKernelGGL(scanline_persistent_kernel<false>, dim3(p->nwg), dim3(kThreads), lds_bytes, st, a);
-    });
-    prof.report(a, st, "encode");
-    return rc;
+    return run_launch<false>(p, a, L, st);
 }
 
 extern "C" int basic_scanline_decode_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
@@ -1980,57 +2005,11 @@ extern "C" int basic_scanline_decode_dev(basic_scanline_plan *p, const basic_ran
                   "scanline_decode: bad argument");
     hipStream_t st = as_stream(hip_stream);
     ScanArgs a{};
-    size_t lds_bytes = 0;
-    bool pipelined = false, batched = false;
-    const int ndec = (batch + kThreads / 64 - 1) / (kThreads / 64);
-    int cus = 0;
-    int rc = device_cus(&cus);
-    if (rc) return rc;
-    rc = choose_batched(p, batch, w, ndec, cus, &batched);
-    if (rc) return rc;
-    if (batched) {
-        rc = fill_args_batched(p, a, batch, h, w, d_prior, d_table, table_len, &lds_bytes, st);
-        if (rc) return rc;
-        rc = rans_fast_view(tables, &a.tv);
-        if (rc) return rc;
-        a.ybuf = d_ybuf; a.sym = d_symbols; a.idx = d_indexes; a.words = d_words; a.word_off = d_word_off;
-        const int ncompute = (a.nbt / 32) * p->b_nw;
-        a.ncompute = ncompute;
-        const size_t dec_lds_b = (static_cast<size_t>((a.tv.image_words + 3) & ~3) + 4 * static_cast<size_t>(a.tv.rows) + 4) * sizeof(uint32_t);
-        if (dec_lds_b > lds_bytes) lds_bytes = dec_lds_b;
-        if (lds_bytes < 96 * 1024) lds_bytes = 96 * 1024;
-        BASIC_REQUIRE(lds_bytes <= 160 * 1024, "scanline_decode: the search image does not fit the LDS");
-        BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(scanline_batched_kernel<true>)));
-        ScanProfile prof;
-        rc = prof.begin(a, st);
-        if (rc) return rc;
-        rc = chained_launch(p, st, ncompute + ndec, cus,
-                            [&] { hipLaunchKernelGGL(scanline_batched_kernel<true>, dim3(ncompute + ndec), dim3(kThreads), lds_bytes, st, a); });
-        prof.report(a, st, "decode (batched)");
-        return rc;
-    }
-    rc = fill_args(p, a, batch, h, w, d_prior, d_table, table_len, &lds_bytes, &pipelined, st);
-    if (rc) return rc;
-    rc = rans_fast_view(tables, &a.tv);
+    ScanLaunch L{};
+    const int rc = prepare_launch(p, a, batch, h, w, d_prior, d_table, table_len, tables, st, &L);
     if (rc) return rc;
     a.ybuf = d_ybuf; a.sym = d_symbols; a.idx = d_indexes; a.words = d_words; a.word_off = d_word_off;
-    a.ncompute = p->nwg;
-    BASIC_REQUIRE(p->nwg + ndec <= cus, "scanline_decode: more workgroups than compute units (the grid must be resident)");
-    const size_t dec_lds = (static_cast<size_t>((a.tv.image_words + 3) & ~3) + 4 * static_cast<size_t>(a.tv.rows) + 4) * sizeof(uint32_t);
-    if (dec_lds > lds_bytes) lds_bytes = dec_lds;
-    if (lds_bytes < 96 * 1024) lds_bytes = 96 * 1024;
-    BASIC_REQUIRE(lds_bytes <= 160 * 1024, "scanline_decode: the search image does not fit the LDS");
-    BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(scanline_persistent_kernel<true>)));
-    BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(scanline_pipelined_kernel<true>)));
-    ScanProfile prof;
-    rc = prof.begin(a, st);
-    if (rc) return rc;
-    rc = chained_launch(p, st, p->nwg + ndec, cus, [&] {
-        if (pipelined) hipLaunchKernelGGL(scanline_pipelined_kernel<true>, dim3(p->nwg + ndec), dim3(kThreads), lds_bytes, st, a);
-        else hipLaunchKernelGGL(scanline_persistent_kernel<true>, dim3(p->nwg + ndec), dim3(kThreads), lds_bytes, st, a);
-    });
-    prof.report(a, st, "decode");
-    return rc;
+    return run_launch<true>(p, a, L, st);
 }
 
 // Whether basic_scanline_decode_dev can serve `batch` streams of this table set on the current device (the set has a fast
@@ -2045,9 +2024,7 @@ extern "C" int basic_scanline_can_decode(const basic_scanline_plan *p, const bas
     int cus = 0;
     int rc = device_cus(&cus);
     if (rc) return rc;
-    const int ndec = (batch + kThreads / 64 - 1) / (kThreads / 64);
-    const size_t dec_lds = (static_cast<size_t>((tv.image_words + 3) & ~3) + 4 * static_cast<size_t>(tv.rows) + 4) * sizeof(uint32_t);
-    *ok = p->nwg + ndec <= cus && dec_lds <= 160 * 1024;
+    *ok = p->nwg + decoder_workgroups(batch) <= cus && decoder_lds_bytes(tv) <= 160 * 1024;
     return BASIC_OK;
 }
 
@@ -2062,7 +2039,7 @@ extern "C" int basic_scanline_batched_max(const basic_scanline_plan *p, int w, i
     int rc = device_cus(&cus);
     if (rc) return rc;
     for (int b = 32 * kBatchedMaxTiles; b >= 1; b -= 32) {
-        const int ndec = decode ? (b + kThreads / 64 - 1) / (kThreads / 64) : 0;
+        const int ndec = decode ? decoder_workgroups(b) : 0;
         if (batched_fits(p, b, w, ndec, cus)) { *max_batch = b; break; }
     }
     return BASIC_OK;

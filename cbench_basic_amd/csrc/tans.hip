@@ -666,7 +666,7 @@ size_t tans_lds_bytes(const basic_tans_tables *t, bool decoder)
 {
     const size_t rows = static_cast<size_t>(t->rows) + (t->bypass ? 1 : 0);
     const size_t bytes = rows * (size_t{1} << t->log) * (decoder ? 4 : 2);
-    return bytes <= 144 * 1024 && !std::getenv("BASIC_TANS_NO_LDS") ? bytes : 0;
+    return bytes <= 144 * 1024 ? bytes : 0;
 }
 
 TansDev dev_view(const basic_tans_tables *t)

@@ -1,6 +1,6 @@
 """Per-layer timing of the checkerboard codec's masked-convolution launches (256 images 16 x 16, 32,768 coded positions) under
-environment variants: which kernel (BASIC_MCONV_KERNEL) and the dma kernel's timing ablations (BASIC_MCONV_DEBUG: 1 no staging,
-2 no MFMA stages, 4 no stores).  Usage: python scripts/mconv_probe.py [variant ...]   variant = name:ENV=VAL,ENV=VAL"""
+environment variants, e.g. which kernel (BASIC_MCONV_KERNEL).  Usage: python scripts/mconv_probe.py [variant ...]
+variant = name:ENV=VAL,ENV=VAL"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cbench_basic_amd.nn import kernels as K
