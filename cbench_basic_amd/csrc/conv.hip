@@ -479,9 +479,16 @@ __global__ __launch_bounds__(64 * WAVES, (MT <= 4 && WAVES == 4 ? 2 : 1)) void c
 //     [cin/16][tap][m-tile][piece][lane][8]: one ds_read_b128 per (m-tile, piece).  They are staged through LDS
 //     (5 taps x 16 channels = 60 KB per stage, two stages) by register staging: plain global loads, so that the
 //     compiler's counted vmcnt waits keep the activation loads below in flight.
-//   * B = activations, read straight from the fp32 NCHW input by buffer loads (8 channels per lane and tap, taps
-//     outside the image come back as zeros from an out-of-range offset) and split in registers right before their
-//     MFMAs.  Nothing else changes: the input and output stay fp32 NCHW.
+//   * B = activations, read from the fp32 NCHW input by buffer loads (positions outside the image come back as zeros
+//     from an out-of-range offset).  Two sources, the template parameter PATCH:
+//       PATCH: per channel block the workgroup loads its input patch (TB x (TH + KH - 1) x (TW + KW - 1) positions x 16
+//         channels), splits each value once and writes the pieces to LDS as [piece][position][16 channels]: a lane's 8
+//         channels of one tap and piece are one ds_read_b128 at an immediate offset of that tap.  The next block's patch
+//         is loaded into registers during the current block and written after the barrier that ends it.
+//       direct (tiles whose patch does not fit beside the weight stages): 8 channels per lane and tap by buffer loads,
+//         split in registers right before their MFMAs, i.e. once per tap that reads them.
+//     Both feed the MFMAs the same pieces in the same order: the results are identical bit for bit.  Nothing else
+//     changes: the input and output stay fp32 NCHW.
 //   * One fixed K order per output element (channel block, then tap): results do not depend on tile, batch or launch.
 // Workgroup = 8 waves x 32 positions, each wave owns all 128 output channels of its positions (MT = 4), so the
 // bias / GDN / IGDN epilogue of conv_tap_mfma_kernel applies unchanged (its second GEMM stays fp32).
@@ -525,7 +532,17 @@ __device__ __forceinline__ f32x16 mfma_bf16(const u32x4 &a, const u32x4 &b, cons
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-template <int KH, int KW, int KWB>
+// Split activation patch of the PATCH source, after the stages: 3 pieces x kSplitPatchPos positions x 16 channels x 2 B.
+// kSplitPatchPos takes the rest of the 160 KB: a 16 x 16 tile's patch is 18 x 18 (KH = 3) or 17 x 18 (KH = 2) positions.
+constexpr int kSplitPatchPos = 416;
+constexpr int kSplitPieceBytes = kSplitPatchPos * 32;
+constexpr size_t kSplitLdsPatchBytes = kSplitLdsBytes + 3 * kSplitPieceBytes;
+static_assert(kSplitLdsPatchBytes <= 160 * 1024, "patch beside the weight stages");
+static_assert(kSplitLdsBytes % 16 == 0, "16-byte aligned patch");
+// patch staging items = (position, 8-channel half): 8 buffer loads, one split and three ds_write_b128 each
+constexpr int kSplitPatchRounds = (2 * kSplitPatchPos + kSplitThreads - 1) / kSplitThreads;
+
+template <int KH, int KW, int KWB, bool PATCH>
 __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const TapLaunch g, const u32x4 *wsplit)
 {
     constexpr int MT = 4;
@@ -538,7 +555,8 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int khalf = lane >> 5, col = lane & 31;
+    const int khalf = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     int bid = xcd_tile(blockIdx.x, gridDim.x);
     const int tx_i = bid % g.tiles_x; bid /= g.tiles_x;
@@ -611,6 +629,54 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
             if (sl * kSplitThreads + tid < kSplitStageU4) dst[sl * kSplitThreads] = wst[sl - h * kHalf];
     };
 
+    // PATCH source.  Patch position p = (image, row, column) of the TB x PH x PW patch whose origin is the tile's first tap
+    // (s_in = 1, npos <= kSplitPatchPos: host-checked); [piece][p][16 channels] in LDS, 32 bytes per position and piece.
+    //   staging item i = r * 512 + tid: position i / 2, channel half i % 2, 16 bytes at i * 16 of each piece; pvoff: its
+    //   global byte offset (past the resource's end outside the image or the batch: loads zero);
+    //   brow: per tap row dy the LDS byte offset of this lane's tap (dy, 0).
+    char *const patch = reinterpret_cast<char *>(lds_u4) + kSplitLdsBytes;
+    const int PW = TW + KW - 1, PH = TH + KH - 1, npos = TB * PH * PW;
+    int pvoff[kSplitPatchRounds], brow[KH];
+    if constexpr (PATCH) {
+#pragma unroll
+        for (int r = 0; r < kSplitPatchRounds; ++r) {
+            const int i = r * kSplitThreads + tid, p = i >> 1, h = i & 1;
+            const int prow = p / PW, x = p - prow * PW, img = prow / PH, row = prow - img * PH;
+            const int gy = my0 + g.dymin + row, gx = mx0 + g.dxmin + x;
+            const bool inside = i < 2 * npos && img < nimg && gy >= 0 && gy < g.in_h && gx >= 0 && gx < g.in_w;
+            pvoff[r] = inside ? static_cast<int>((((static_cast<int64_t>(img) * g.cin + 8 * h) * g.in_h + gy) * g.in_w + gx) * 4)
+                              : 0x7FFFFFF0;
+        }
+#pragma unroll
+        for (int dy = 0; dy < KH; ++dy) brow[dy] = ((tb * PH + (lp.my - my0) + dy) * PW + (lp.mx - mx0)) * 32 + 16 * khalf;
+    }
+    float pf[kSplitPatchRounds][8];  // this thread's items of the next channel block
+    auto fetch_patch = [&](int cb) __attribute__((always_inline)) {
+        const int soff = cb * kSplitCK * plane_bytes;
+#pragma unroll
+        for (int r = 0; r < kSplitPatchRounds; ++r)
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                pf[r][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, pvoff[r], soff + j * plane_bytes, 0));
+    };
+    auto store_patch = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < kSplitPatchRounds; ++r)
+            if (r * kSplitThreads + tid < 2 * npos) {
+                u32x4 q[3];
+                split_bf16x3(pf[r], q[0], q[1], q[2]);
+#pragma unroll
+                for (int pc = 0; pc < 3; ++pc)
+                    *reinterpret_cast<u32x4 *>(patch + (r * kSplitThreads + tid) * 16 + pc * kSplitPieceBytes) = q[pc];
+            }
+    };
+    // the three pieces of this lane's 8 channels of tap T: one ds_read_b128 each, at immediate offsets from the tap row's base
+    auto read_b = [&](int T, u32x4 (&d)[3]) __attribute__((always_inline)) {
+        const char *src = patch + brow[tap_row(T)] + 32 * tap_col(T);
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc) d[pc] = *reinterpret_cast<const u32x4 *>(src + pc * kSplitPieceBytes);
+    };
+
     f32x16 acc[MT], acc2[MT];  // output columns 2 mx and 2 mx + 1
 #pragma unroll
     for (int m = 0; m < MT; ++m)
@@ -620,12 +686,15 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
             acc2[m][r] = 0.f;
         }
 
-    float xb[8];
-    load_b(0, 0, xb);
+    float xb[8];     // direct source: this tap's activations
+    u32x4 bq[2][3];  // PATCH source: the B pieces of this tap and (read one tap ahead) of the next
+    if constexpr (PATCH) fetch_patch(0);
+    else load_b(0, 0, xb);
     fetch_w(0, 0);
     store_w(0, 0);
     fetch_w(0, 1);
     store_w(0, 1);
+    if constexpr (PATCH) store_patch();
     for (int cb = 0; cb < ncb; ++cb) {
 #pragma unroll
         for (int gi = 0; gi < kGroups; ++gi) {
@@ -638,15 +707,20 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
 #pragma unroll
             for (int tl = 0; tl < kSplitStageTaps; ++tl) {
                 const int T = gi * kSplitStageTaps + tl;
-                // next tap's activations (the next channel block's first tap at the end; a harmless re-read at the very end),
-                // issued before this tap's MFMAs: a whole tap of matrix work covers their latency.  The sched_barriers keep the
-                // compiler from sinking them next to their use.
                 float xn[8];
-                if (T + 1 < kTapsAll) load_b(cb, T + 1, xn);
-                else load_b(cb + 1 < ncb ? cb + 1 : cb, 0, xn);
-                __builtin_amdgcn_sched_barrier(0);
-                u32x4 bp[3];
-                split_bf16x3(xb, bp[0], bp[1], bp[2]);
+                u32x4 bd[3];
+                if constexpr (PATCH) {
+                    if (T == 0) read_b(0, bq[0]);  // else read during the previous tap
+                } else {
+                    // next tap's activations (the next channel block's first tap at the end; a harmless re-read at the very
+                    // end), issued before this tap's MFMAs: a whole tap of matrix work covers their latency.  The
+                    // sched_barriers keep the compiler from sinking them next to their use.
+                    if (T + 1 < kTapsAll) load_b(cb, T + 1, xn);
+                    else load_b(cb + 1 < ncb ? cb + 1 : cb, 0, xn);
+                    __builtin_amdgcn_sched_barrier(0);
+                    split_bf16x3(xb, bd[0], bd[1], bd[2]);
+                }
+                const u32x4 (&bp)[3] = PATCH ? bq[T & 1] : bd;
                 f32x16 (&dst)[MT] = T < kTapsA ? acc : acc2;  // (compile-time after unrolling)
                 // per M-tile its three A pieces (one ds_read_b128 each, read one tile ahead) and six MFMAs, smallest products
                 // first: (i, j) = (2,0) (1,1) (0,2) (1,0) (0,1) (0,0) -- one dependent chain per tile needs no interleaving
@@ -659,6 +733,8 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
                     if (m + 1 < MT) {
 #pragma unroll
                         for (int pc = 0; pc < 3; ++pc) ap[cur ^ 1][pc] = wl[((tl * MT + m + 1) * 3 + pc) * 64];
+                    } else if constexpr (PATCH) {
+                        if (T + 1 < kTapsAll) read_b(T + 1, bq[(T + 1) & 1]);  // the next tap's B pieces
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     dst[m] = mfma_bf16(ap[cur][2], bp[0], dst[m]);
@@ -669,20 +745,40 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
                     dst[m] = mfma_bf16(ap[cur][0], bp[0], dst[m]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
+                if constexpr (!PATCH) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) xb[j] = xn[j];
+                    for (int j = 0; j < 8; ++j) xb[j] = xn[j];
+                }
                 // the next stage's buffer has been free since the barrier: each half is written two taps after its loads
                 if (tl == 1 && more) {
                     store_w((s + 1) & 1, 0);
                     fetch_w(s + 1, 1);
                     __builtin_amdgcn_sched_barrier(0);
                 }
+                if constexpr (PATCH) {
+                    // the next block's patch (a harmless re-read in the last block), issued after this stage's weight loads:
+                    // their waits leave it in flight, and the next stage's first weight wait finds it five taps old
+                    if (gi == 0 && tl == 1) {
+                        fetch_patch(cb + 1 < ncb ? cb + 1 : cb);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
                 if (tl == 3 && more) store_w((s + 1) & 1, 1);
+            }
+        }
+        if constexpr (PATCH) {
+            if (cb + 1 < ncb) {
+                __syncthreads();  // every wave is done with this block's patch
+                store_patch();    // read after the next stage's barrier
             }
         }
     }
 
     // ---- epilogue: bias, GDN / IGDN (as conv_tap_mfma_kernel; gamma^T resident in the free stage buffers)
+    // The thread's ids are recomputed here rather than kept in registers through the main loop: the wave index from its
+    // SGPR, the lane by v_mbcnt (the 10-tap PATCH instance spilled them otherwise).
+    const int tid_e = wave * 64 + static_cast<int>(__lane_id());
+    const int khalf_e = (tid_e >> 5) & 1, col_e = tid_e & 31;
     float *gl = reinterpret_cast<float *>(lds_u4);
     const bool gdn = g.act == BASIC_ACT_GDN || g.act == BASIC_ACT_IGDN;
     auto finish = [&](f32x16 (&acc)[MT]) __attribute__((always_inline)) {
@@ -691,7 +787,7 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const f32x4 b4 = *reinterpret_cast<const f32x4 *>(chan_const + 32 * m + 8 * rq + 4 * khalf);
+                    const f32x4 b4 = *reinterpret_cast<const f32x4 *>(chan_const + 32 * m + 8 * rq + 4 * khalf_e);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[m][4 * rq + e] += b4[e];
                 }
@@ -706,7 +802,7 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
             for (int st = 0; st < 64; ++st) {  // k = 32 mk + 8 (r >> 2) + (r & 3) [+4 for lanes 32..63], st = 16 mk + r
                 const int kk = 32 * (st >> 4) + 8 * ((st & 15) >> 2) + (st & 3);
                 float gk[4];
-                load_a<4>(gl + ((kk + 4 * khalf) * 32 + col) * 4, gk);
+                load_a<4>(gl + ((kk + 4 * khalf_e) * 32 + col_e) * 4, gk);
                 const float x = acc[st >> 4][st & 15];
                 const float bfrag = x * x;
 #pragma unroll
@@ -717,7 +813,7 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const f32x4 b4 = *reinterpret_cast<const f32x4 *>(chan_const + 128 + 32 * m + 8 * rq + 4 * khalf);
+                    const f32x4 b4 = *reinterpret_cast<const f32x4 *>(chan_const + 128 + 32 * m + 8 * rq + 4 * khalf_e);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int r = 4 * rq + e;
@@ -732,15 +828,13 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
         const f32x4 *src = reinterpret_cast<const f32x4 *>(g.gammaT);
         f32x4 *dst = reinterpret_cast<f32x4 *>(gl);
 #pragma unroll
-        for (int sl = 0; sl < 128 * 32 * 4 / 4 / kSplitThreads; ++sl) dst[sl * kSplitThreads + tid] = src[sl * kSplitThreads + tid];
+        for (int sl = 0; sl < 128 * 32 * 4 / 4 / kSplitThreads; ++sl) dst[sl * kSplitThreads + tid_e] = src[sl * kSplitThreads + tid_e];
         __syncthreads();
     }
     finish(acc);
     finish(acc2);
 
     // ---- store
-    int tid_e = tid;
-    asm volatile("" : "+v"(tid_e));  // opaque: the position is recomputed here, not carried through the main loop
     const Pos ep = pos_of(tid_e);
     const int my = ep.my, mx = ep.mx, be = b0 + ep.tb;
     if (my < g.mh && mx < g.mw && be < g.batch) {
@@ -751,7 +845,7 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
         for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = 32 * m + 8 * (r >> 2) + 4 * khalf + (r & 3);
+                const int co = 32 * m + 8 * (r >> 2) + 4 * khalf_e + (r & 3);
                 if (co < g.cout) {  // columns ox, ox + 1 (ox even, rows 8-byte aligned: host-checked)
                     f32x2 v2;
                     v2[0] = apply_act(acc[m][r], g.act);
@@ -760,6 +854,17 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
                 }
             }
     }
+}
+
+// One split-bf16 launch: the PATCH source takes all 160 KB of LDS, the direct source the stages and constants only.
+template <int KH, bool PATCH>
+hipError_t launch_split(const TapLaunch &g, const u32x4 *ws, int blocks, hipStream_t st)
+{
+    const hipError_t e = ensure_max_lds(reinterpret_cast<const void *>(conv_split_bf16_kernel<KH, 3, 2, PATCH>));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((conv_split_bf16_kernel<KH, 3, 2, PATCH>), dim3(blocks), dim3(kSplitThreads),
+                       PATCH ? kSplitLdsPatchBytes : kSplitLdsBytes, st, g, ws);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1806,11 +1911,12 @@ int pow2_ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 namespace {
 // which launch list forward() walks for this input: 32-channel slices for small position grids, fused column phases when
 // the output rows allow 8-byte pair stores
-struct LaunchChoice { bool use_split, fuse_ok, bf16x3; };
+struct LaunchChoice { bool use_split, fuse_ok, bf16x3, split_patch; };
 LaunchChoice choose_launches(const basic_conv_plan *p, int batch, int oh, int ow, const void *d_out)
 {
     const int64_t pos_blocks = (static_cast<int64_t>(batch) * ((oh + p->s_out - 1) / p->s_out) * ((ow + p->s_out - 1) / p->s_out) + kTilePos - 1) / kTilePos;
-    // BASIC_CONV_DEBUG path bits (tests): 4 force slices, 8 forbid slices, 512 no fused column phases
+    // BASIC_CONV_DEBUG path bits (tests): 4 force slices, 8 forbid slices, 512 no fused column phases, 1024 split-bf16
+    // activations by direct loads only (no LDS patch)
     const char *dbg_env = getenv("BASIC_CONV_DEBUG");
     const int dbg = dbg_env ? atoi(dbg_env) : 0;
     LaunchChoice c;
@@ -1819,6 +1925,7 @@ LaunchChoice choose_launches(const basic_conv_plan *p, int batch, int oh, int ow
     // BASIC_CONV_F32=1: the launches that have a split-bf16 variant run the fp32 kernel instead (A/B runs, tests)
     const char *f32_env = getenv("BASIC_CONV_F32");
     c.bf16x3 = !(f32_env && atoi(f32_env) != 0);
+    c.split_patch = !(dbg & 1024);
     return c;
 }
 }  // namespace
@@ -1894,13 +2001,12 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
                 const int blocks = ((batch + tb - 1) / tb) * g.tiles_y * g.tiles_x;
                 hipStream_t st = as_stream(hip_stream);
                 const u32x4 *ws = static_cast<const u32x4 *>(ph.d_wsplit);
-                const void *kfn = ph.kh == 3 ? reinterpret_cast<const void *>(conv_split_bf16_kernel<3, 3, 2>)
-                                             : reinterpret_cast<const void *>(conv_split_bf16_kernel<2, 3, 2>);
                 BASIC_REQUIRE(ph.kw == 3 && ph.kwb == 2 && (ph.kh == 3 || ph.kh == 2), "conv_forward: split-bf16 plan / kernel instantiation mismatch");
-                BASIC_HIP_TRY(ensure_max_lds(kfn));
-                if (ph.kh == 3) hipLaunchKernelGGL((conv_split_bf16_kernel<3, 3, 2>), dim3(blocks), dim3(kSplitThreads), kSplitLdsBytes, st, g, ws);
-                else hipLaunchKernelGGL((conv_split_bf16_kernel<2, 3, 2>), dim3(blocks), dim3(kSplitThreads), kSplitLdsBytes, st, g, ws);
-                BASIC_HIP_TRY(hipGetLastError());
+                // activations from the tile's split patch in LDS where it fits beside the weight stages, else by direct loads
+                const bool patch = choice.split_patch && g.s_in == 1 && tb * (th + ph.kh - 1) * (tw + ph.kw - 1) <= kSplitPatchPos;
+                const hipError_t e = ph.kh == 3 ? (patch ? launch_split<3, true>(g, ws, blocks, st) : launch_split<3, false>(g, ws, blocks, st))
+                                                : (patch ? launch_split<2, true>(g, ws, blocks, st) : launch_split<2, false>(g, ws, blocks, st));
+                BASIC_HIP_TRY(e);
                 continue;
             }
         }
