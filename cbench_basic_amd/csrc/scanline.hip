@@ -1,4 +1,6 @@
-// Persistent scan-line autoregressive coding loop: ONE launch walks all H*W coding steps of a batch.
+// Persistent scan-line autoregressive coding loop: ONE launch walks all coding steps of a batch -- H*W of them in raster order,
+// or, for an encode call under the wavefront schedule of the batched kernel (the rows of an image in parallel, each
+// ksize / 2 + 2 columns behind the row above), W + (ksize / 2 + 2) * (H - 1).
 //
 // Reference: TopoGroupPGMPriorCoder._encode_with_pgm / _pgm_generate (cbench/modules/prior_model/prior_coder/pgm_coder.py:
 // 912-981) with the "scanline" topo groups (one group per spatial position, raster order, :1416-1491), the masked 5x5
@@ -92,6 +94,12 @@ struct ScanArgs {
     int ctx_blocks;        // blocks of the first dense layer fed by the context layer (the rest: the prior)
     int tile_off[kMaxLayers];   // dense-role workgroups: LDS float offset of a layer's partial tiles
     float *wlate;          // [compute workgroups][256 threads][32]: a context workgroup's late blocks as A fragments (written by the launch itself)
+    // wavefront encode schedule of the batched kernel only (wf_cols == 0 otherwise): a column is (image, row), step t codes column
+    // position t - wf_s * row of every row, and the per-position arrays become per-step ones -- yT [steps][C][wf_yw], priorT [steps][P][nbt]
+    int wf_cols;           // B * H columns in use
+    int wf_s;              // steps a row starts after the row above it: ksize / 2 + 2
+    int wf_steps;          // W + wf_s * (H - 1)
+    int wf_yw;             // columns of a yT slab: per image ksize / 2 pad columns (the rows above the image: zeros), then its H rows
 };
 
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -1109,9 +1117,15 @@ __device__ __forceinline__ f4 b_leaky(f4 v)
     return v;
 }
 
-template <bool DECODE>
+// WF: the wavefront encode schedule (see ScanArgs): the same chains, block order, LDS sums and tag protocol; a column is a row of
+// an image, a step codes one position of every row that is inside its image in that step, the slabs of the coded latent and of
+// the prior are indexed by step.  Causal tap (dy, dx) of step t is column col + dy of slab t + dx + wf_s * dy (tap_off holds
+// dx + wf_s * dy); a column outside its row's [0, W) publishes zero granules with the step's tag, and the pad columns in front
+// of every image hold zeros for every step, so a tap outside the image multiplies zeros: no predicate inside a chain.
+template <bool DECODE, bool WF = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void scanline_batched_kernel(const ScanArgs a)
 {
+    static_assert(!(DECODE && WF), "the wavefront schedule is encode only: the decoder reads one serial rANS stream");
     extern __shared__ float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wg = blockIdx.x;
@@ -1119,8 +1133,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int HW = a.H * a.W, C = a.C, NBT = a.nbt, T = NBT >> 5;
     const int t = wg % T, j = wg / T;                  // column tile; role index inside the tile's set of workgroups
     const int h = lane >> 5, n = lane & 31, col = t * 32 + n;
-    const bool img = col < a.B;                        // columns beyond the batch: nothing published (they LOAD the last image's
-    const int colc = img ? col : a.B - 1;              // operands: no predicates, no zero fill in the load paths)
+    const int ncols = WF ? a.wf_cols : a.B;            // (wavefront: a column is one row of one image)
+    const bool img = col < ncols;                      // columns beyond the batch: nothing published (they LOAD the last image's
+    const int colc = img ? col : ncols - 1;            // operands: no predicates, no zero fill in the load paths)
     const bool dense = j < a.nd;
     const int r0 = dense ? j : j - a.nd;               // this workgroup's row tile (dense role: of every layer that has one)
     const int nb0 = a.ntaps * a.bpt;                   // context blocks; the last kBLate run in the late half (the left neighbour's bpt among them),
@@ -1128,6 +1143,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int frow = 8 * wave + 4 * h;                 // first of this thread's four finishing rows inside the tile
     const uint32_t voff = static_cast<uint32_t>(h * NBT + colc) * 16u;   // the lane's 16-byte piece inside a (channel quad, column tile) slab
     const int pstride = 2 * NBT * 16;                  // bytes between consecutive pieces of a lane
+    // the coded latent's slabs: the same layout; the wavefront's are wf_yw columns wide (pad columns) and have their own lane offset
+    const int wb = WF ? colc / a.H : 0, wr = WF ? colc - wb * a.H : 0;   // wavefront: this column's image and row
+    const int wpad = WF ? a.wf_s - 2 : 0;
+    const int YW = WF ? a.wf_yw : NBT, ycol = WF ? wb * (a.H + wpad) + wpad + wr : colc;
+    const uint32_t voff_y = WF ? static_cast<uint32_t>(h * YW + ycol) * 16u : voff;
+    const int ypstride = WF ? 2 * YW * 16 : pstride;
+    const int nsteps = WF ? a.wf_steps : HW;
     // granule index of this thread's first finishing row (channel r0 * 32 + frow) relative to its tile's first piece
     const uint32_t soff = static_cast<uint32_t>(((frow >> 2) * 2 * NBT + col) * 2);
 
@@ -1176,9 +1198,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     if (!dense) {
         // ================= context role: row tile r0 of the masked context convolution =================
         const char *yT8 = reinterpret_cast<const char *>(a.yT);
-        const int blk_bytes = 16 * pstride;   // a 64-channel block of a slab
+        const int blk_bytes = 16 * ypstride;   // a 64-channel block of a slab
         uint64_t *out_tile = a.act[0] + static_cast<int64_t>(r0 * 8) * 2 * NBT * 2;
-        const int64_t pos_bytes = static_cast<int64_t>(C) * NBT * 8;   // a position's slab of the coded latent
+        const int64_t pos_bytes = static_cast<int64_t>(C) * YW * 8;   // a position's (wavefront: a step's) slab of the coded latent
         f4 esum = zero4;   // position 0 has no causal neighbour: its early sum is zero
         int px = 0, py = 0;
         // this wave's late block as A fragments, lane-major (8 x 16 bytes per lane): saved once, re-fetched every step
@@ -1193,7 +1215,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
         const bool prof1 = a.prof && wg == a.nd * T && tid == 64, prof0 = a.prof && wg == a.nd * T && tid == 0;   // BASIC_SCAN_PROFILE: first context workgroup, waves 1 / 0
         const long long loop_t0 = prof0 ? wall_clock64() : 0;
-        for (int p = 0; p < HW; ++p) {
+        for (int p = 0; p < nsteps; ++p) {
             const uint32_t tag = static_cast<uint32_t>(p + 1);
             const long long tp0 = a.prof ? wall_clock64() : 0;
             long long tp1 = tp0;
@@ -1204,8 +1226,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
             {
                 const int e = early + wave, tp = e / a.bpt, cb = e - tp * a.bpt;
                 const bool left = tp == a.ntaps - 1;
+                // wavefront: the tap's slab is a step (left: p - 1 as well); before step 0 it is outside the image for every column
                 const int ny = py + a.tap_dy[tp], nx = px + a.tap_dx[tp];
-                const bool inside = ny >= 0 && nx >= 0 && nx < a.W;
+                const bool inside = WF ? p + a.tap_off[tp] >= 0 : ny >= 0 && nx >= 0 && nx < a.W;
+                const int dyb = WF ? a.tap_dy[tp] * 16 : 0;   // wavefront: the tap's row is the column dy pieces further on
                 f4 wl4[8];
                 {
                     uint32_t fo = static_cast<uint32_t>(tid) * 128u;
@@ -1216,12 +1240,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
                 f32x16 acc = b_zero16();
                 if (inside || (left && p > 0)) {
                     const int pos = left ? p - 1 : p + a.tap_off[tp];
-                    const brsrc yr = b_rsrc(yT8 + pos * pos_bytes);
+                    const brsrc yr = b_rsrc(yT8 + pos * pos_bytes + dyb);
                     const int sb = cb * blk_bytes;
-                    if (left && !b_sentinel(a, yr, sb + 15 * pstride, voff, static_cast<uint32_t>(pos + 1))) return;
+                    if (left && !b_sentinel(a, yr, sb + 15 * ypstride, voff_y, static_cast<uint32_t>(pos + 1))) return;
                     if (a.prof) tp1 = wall_clock64();
-                    b_issue(yr, sb, pstride, voff, gA);
-                    if (!b_wait(a, yr, sb, pstride, voff, static_cast<uint32_t>(pos + 1), gA)) return;
+                    b_issue(yr, sb, ypstride, voff_y, gA);
+                    if (!b_wait(a, yr, sb, ypstride, voff_y, static_cast<uint32_t>(pos + 1), gA)) return;
                     if (inside)
                         acc = b_chain_vv([&](int i) { return wl4[i >> 2][i & 3]; }, [&](int i) { return __uint_as_float(static_cast<uint32_t>(gA[i >> 1][i & 1])); });
                 }
@@ -1237,8 +1261,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
             }
             const long long tp3 = a.prof ? wall_clock64() : 0;
             if (prof1) { a.prof[0] += tp1 - tp0; a.prof[1] += tp2 - tp1; a.prof[2] += tp3 - tp2; }
-            if (++px == a.W) { px = 0; ++py; }
-            if (p + 1 == HW) break;
+            if (!WF && ++px == a.W) { px = 0; ++py; }
+            if (p + 1 == nsteps) break;
             // ---------- early half for the next position q = p + 1, in the shadow of the dense layers: partial tiles of the blocks
             // of the taps coded at least two steps ago, then their sum in block order.  Every granule read here was validated by
             // this workgroup's late waves in an earlier step (the newest, position p - 1, in this step's late half, before the
@@ -1251,16 +1275,25 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
             auto early_src = [&](int e, brsrc &r, int &sb) -> bool {
                 const int tp = e / a.bpt, cb = e - tp * a.bpt;
                 const int ny = qy + a.tap_dy[tp], nx = qx + a.tap_dx[tp];
-                const bool inside = ny >= 0 && nx >= 0 && nx < a.W;
-                r = b_rsrc(yT8 + (inside ? q + a.tap_off[tp] : q - 1) * pos_bytes);   // (outside: any coded position -- loaded into a buffer nobody reads)
+                const bool inside = WF ? q + a.tap_off[tp] >= 0 : ny >= 0 && nx >= 0 && nx < a.W;
+                r = b_rsrc(yT8 + (inside ? q + a.tap_off[tp] : q - 1) * pos_bytes + (WF ? a.tap_dy[tp] * 16 : 0));   // (outside: any coded position -- loaded into a buffer nobody reads)
                 sb = cb * blk_bytes;
                 return inside;
             };
+            // Wavefront, second column tile: a tap of a row above reads, in this tile's first lanes, columns of the OTHER tile, which
+            // this workgroup's late waves never validated (the tile sets run independently) -- those blocks wait for their tags
+            // here.  (Pad columns are written before the launch; columns of this tile: the argument above.)
+            auto early_tag = [&](int e, uint32_t &want) -> bool {
+                const int tp = e / a.bpt;
+                want = static_cast<uint32_t>(q + a.tap_off[tp] + 1);
+                return WF && t > 0 && a.tap_dy[tp] != 0;
+            };
+            bool early_ok = true;
             bool have_a = false, have_b = false;   // whether buffer A / B holds (or is receiving) a block that is used
             {
                 brsrc r; int sb;
-                if (early_valid(0) && (have_a = early_src(wave, r, sb))) b_issue(r, sb, pstride, voff, gA);
-                if (early_valid(1) && (have_b = early_src(wave + 4, r, sb))) b_issue(r, sb, pstride, voff, gB);
+                if (early_valid(0) && (have_a = early_src(wave, r, sb))) b_issue(r, sb, ypstride, voff_y, gA);
+                if (early_valid(1) && (have_b = early_src(wave + 4, r, sb))) b_issue(r, sb, ypstride, voff_y, gB);
             }
             static_for<0, kBSlots>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
@@ -1273,14 +1306,24 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
                 const bool have_next = next && early_src(wave + 4 * (k + 2), r2, sb2);
                 f32x16 acc = b_zero16();
                 if (have_cur) {
+                    if constexpr (WF) {
+                        uint32_t want;
+                        if (early_tag(wave + 4 * k, want)) {
+                            brsrc rc = b_rsrc(yT8);
+                            int sbc = 0;
+                            early_src(wave + 4 * k, rc, sbc);
+                            early_ok = b_wait(a, rc, sbc, ypstride, voff_y, want, cur) && early_ok;
+                        }
+                    }
                     if (!next) early_src(wave + 4 * k, r2, sb2);   // nothing follows: the refill re-reads this block (no second copy of the chain)
-                    acc = b_chain_gran<k, true>(cur, r2, sb2, pstride, voff);
+                    acc = b_chain_gran<k, true>(cur, r2, sb2, ypstride, voff_y);
                 } else if (have_next) {
-                    b_issue(r2, sb2, pstride, voff, cur);   // (a tap outside the image enters as zeros: no chain to hide the loads behind)
+                    b_issue(r2, sb2, ypstride, voff_y, cur);   // (a tap outside the image enters as zeros: no chain to hide the loads behind)
                 }
                 have_cur = have_next;
                 b_store_tile(part + (wave + 4 * k) * kBTile, lane, acc);
             });
+            if (WF && !early_ok) return;
             lds_barrier();
             esum = b_sum_tiles(zero4, part, early, tid);
             if (prof0) a.prof[3] += wall_clock64() - tp3;
@@ -1294,19 +1337,26 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     const bool codes = r0 < a.rt[last] && img;     // this thread finishes two (mean, scale) pairs of image `col`
     const int c0 = (r0 * 32 + frow) >> 1;          // its channels c0, c0 + 1  (rows 2c = mean, 2c + 1 = scale: "split_interleave")
     // element offsets of (image col, channel c0) in y / ybuf [B][C][HW], sym / idx [B][HW * C], the coded latent's slab, mu / idx_step [nbt][C]
-    const uint32_t yoff = static_cast<uint32_t>((col * C + c0) * HW), ooff = static_cast<uint32_t>(col * C * HW + c0);
-    const uint32_t toff = static_cast<uint32_t>(bm_gran(c0, col, NBT)), moff = static_cast<uint32_t>(col * C + c0);
+    // (wavefront: of (image wb, channel c0, first position of row wr); the row's position of the step is added per step)
+    const uint32_t yoff = static_cast<uint32_t>(WF ? (wb * C + c0) * HW + wr * a.W : (col * C + c0) * HW);
+    const uint32_t ooff = static_cast<uint32_t>(WF ? (wb * HW + wr * a.W) * C + c0 : col * C * HW + c0);
+    const uint32_t toff = static_cast<uint32_t>(bm_gran(c0, WF ? ycol : col, YW)), moff = static_cast<uint32_t>(col * C + c0);
+    const int wsr = WF ? a.wf_s * wr : 0;              // wavefront: the step in which this column's row starts
     const bool prof = a.prof && wg == 0 && tid == 0;   // BASIC_SCAN_PROFILE: first dense workgroup, wave 0
     const long long loop_c0 = prof ? clock64() : 0, loop_t0 = prof ? wall_clock64() : 0;
-    for (int p = 0; p < HW; ++p) {
+    for (int p = 0; p < nsteps; ++p) {
         const uint32_t tag = static_cast<uint32_t>(p + 1);
+        // wavefront: the column position this lane's row codes in this step; outside [0, W) the column is idle (zeros published)
+        const int wc = WF ? p - wsr : 0;
+        const bool active = !WF || static_cast<unsigned>(wc) < static_cast<unsigned>(a.W);
         // (per-thread element offsets stay 32-bit and opaque: as 64-bit addresses hoisted out of the loop they would be spilled)
         float y_pre0 = 0.f, y_pre1 = 0.f;
-        if (!DECODE && codes) {   // requested a whole step before they are needed
+        if (!DECODE && codes && active) {   // requested a whole step before they are needed
             uint32_t yo = yoff;
             asm volatile("" : "+v"(yo));
-            y_pre0 = (a.y + p)[yo];
-            y_pre1 = (a.y + p)[yo + static_cast<uint32_t>(HW)];
+            if constexpr (WF) yo += static_cast<uint32_t>(wc);
+            y_pre0 = (a.y + (WF ? 0 : p))[yo];
+            y_pre1 = (a.y + (WF ? 0 : p))[yo + static_cast<uint32_t>(HW)];
         }
         bool alive = true;
         static_for<1, 4>([&](auto lc) {
@@ -1380,16 +1430,23 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
                     }
                 } else {
                     const float q0 = rintf(y_pre0 - v[0]), q1 = rintf(y_pre1 - v[2]);          // torch.round: half to even
-                    uint64_t *ypos = a.yT + static_cast<int64_t>(p) * C * NBT;
-                    st_gran(ypos + to, q0 + v[0], tag);
-                    st_gran(ypos + (to + static_cast<uint32_t>(2 * NBT)), q1 + v[2], tag);     // channel c0 + 1: the odd-parity piece of the same quad
+                    uint64_t *ypos = a.yT + static_cast<int64_t>(p) * C * YW;
+                    if (WF && !active) {   // an idle column: the zero padding left and right of its row
+                        st_gran(ypos + to, 0.f, tag);
+                        st_gran(ypos + (to + static_cast<uint32_t>(2 * YW)), 0.f, tag);
+                    } else {
+                        st_gran(ypos + to, q0 + v[0], tag);
+                        st_gran(ypos + (to + static_cast<uint32_t>(2 * YW)), q1 + v[2], tag);     // channel c0 + 1: the odd-parity piece of the same quad
+                        const int op = WF ? 0 : p;
+                        if constexpr (WF) { oo += static_cast<uint32_t>(wc * C); yo += static_cast<uint32_t>(wc); }
 #pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        const float mu = v[2 * i], qq = i ? q1 : q0;
-                        const int row = nearest_scale(v[2 * i + 1], tab, a.table_len, tab_sorted);
-                        (a.idx + static_cast<int64_t>(p) * C)[oo + i] = row;
-                        (a.sym + static_cast<int64_t>(p) * C)[oo + i] = static_cast<int32_t>(qq);
-                        (a.ybuf + p)[yo + static_cast<uint32_t>(i * HW)] = qq + mu;
+                        for (int i = 0; i < 2; ++i) {
+                            const float mu = v[2 * i], qq = i ? q1 : q0;
+                            const int row = nearest_scale(v[2 * i + 1], tab, a.table_len, tab_sorted);
+                            (a.idx + static_cast<int64_t>(op) * C)[oo + i] = row;
+                            (a.sym + static_cast<int64_t>(op) * C)[oo + i] = static_cast<int32_t>(qq);
+                            (a.ybuf + op)[yo + static_cast<uint32_t>(i * HW)] = qq + mu;
+                        }
                     }
                 }
             }
@@ -1413,6 +1470,36 @@ __global__ void transpose_prior_batched_kernel(const float *__restrict__ in, flo
         const int c = static_cast<int>(r % P);
         const int b = static_cast<int>(r / P);
         out[static_cast<int64_t>(p) * P * nbt + bm_prior(c, b, nbt)] = in[i];
+    }
+}
+
+// wavefront schedule: prior [B][P][HW] -> priorT [steps] x slab [P][nbt] (bm_prior), column b * H + r of step t = position
+// (r, t - s * r) of image b, zero where that lies outside the row (the column is idle in that step)
+__global__ void transpose_prior_wavefront_kernel(const float *__restrict__ in, float *__restrict__ out, int P, int H, int W, int s, int steps, int nbt,
+                                                 int64_t total)
+{
+    for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int t = static_cast<int>(i % steps);   // step fastest: a row's positions, coalesced reads
+        const int64_t q = i / steps;
+        const int c = static_cast<int>(q % P);
+        const int col = static_cast<int>(q / P), b = col / H, r = col - b * H;
+        const int x = t - s * r;
+        out[static_cast<int64_t>(t) * P * nbt + bm_prior(c, col, nbt)] = (x >= 0 && x < W) ? in[(static_cast<int64_t>(b) * P + c) * H * W + r * W + x] : 0.f;
+    }
+}
+
+// wavefront schedule: the pad columns of every step's slab of the coded latent (the rows above each image): granules { 0.0f, step + 1 },
+// constants of the launch, written in stream order before it (the rest of the array is zeroed: tag 0)
+__global__ void wavefront_pads_kernel(uint64_t *__restrict__ yT, int C, int B, int H, int pad, int yw, int64_t total)
+{
+    for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int k = static_cast<int>(i % pad);
+        int64_t q = i / pad;
+        const int b = static_cast<int>(q % B);
+        q /= B;
+        const int c = static_cast<int>(q % C);
+        const int64_t t = q / C;
+        yT[t * C * yw + bm_gran(c, b * (H + pad) + k, yw)] = static_cast<uint64_t>(t + 1) << 32;
     }
 }
 
@@ -1447,6 +1534,8 @@ struct basic_scanline_plan {
     int b_nw = 0, b_nd = 0, b_bpt = 0, b_ctx_blocks = 0;
     int b_nblk[kMaxLayers] = {}, b_rt[kMaxLayers] = {}, b_tile_off[kMaxLayers] = {};
     int b_tiles = 0;             // partial tiles (4 KB each) the larger role keeps in LDS
+    int encode_schedule = BASIC_SCAN_SCHEDULE_AUTO;   // basic_scanline_set_encode_schedule
+    int last_kernel = BASIC_SCAN_KERNEL_NONE;         // basic_scanline_last_kernel
 };
 
 namespace {
@@ -1662,7 +1751,7 @@ namespace {
 size_t align4(size_t n) { return (n + 3) & ~static_cast<size_t>(3); }
 
 // which scan-line kernel a launch runs (kAuto: the one the launch fits best)
-enum class ScanKernel { kAuto, kGeneric, kPipelined, kBatched };
+enum class ScanKernel { kAuto, kGeneric, kPipelined, kBatched, kWavefront };
 
 // fills the launch arguments of the generic / pipelined kernels, shared by both directions; *lds_bytes = LDS of a compute
 // workgroup.  The pipelined kernel is taken when it fits, unless `force` names the generic one.
@@ -1787,11 +1876,40 @@ bool batched_fits(const basic_scanline_plan *p, int batch, int w, int ndec, int 
     return tiles * p->b_nw + ndec <= cus;
 }
 
-int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
-                      size_t *lds_bytes, hipStream_t st)
+// ---- wavefront encode schedule of the batched kernel: a column is one row of one image, so batch * h columns in at most
+// kBatchedMaxTiles tiles; a row starts ksize / 2 + 2 steps after the row above it, which leaves the left neighbour as the only
+// tap coded one step ago (the late half), every other one at least two (the early half).  No lower bound on the width: the
+// zero padding left and right of a row is what its idle column publishes.
+int wavefront_slope(const basic_scanline_plan *p) { return p->ksize / 2 + 2; }
+int wavefront_steps(const basic_scanline_plan *p, int h, int w) { return w + wavefront_slope(p) * (h - 1); }
+
+bool wavefront_fits(const basic_scanline_plan *p, int batch, int h, int cus)
 {
-    const int64_t HW = static_cast<int64_t>(h) * w;
-    const int tiles = (batch + 31) / 32, nbt = 32 * tiles;
+    if (!p->batched || batch < 1 || h < 1 || static_cast<int64_t>(batch) * h > 32 * kBatchedMaxTiles) return false;
+    const int tiles = (batch * h + 31) / 32;
+    return tiles * p->b_nw <= cus;
+}
+
+// The encode calls that take the wavefront schedule when nothing forces a choice: those with at most half the raster schedule's
+// steps.  Measured (profiles/scanline_wavefront_probe.txt): a wavefront step costs 17.5-20.5 us at any
+// shape that fits, a raster step 11.1-11.5 (pipelined, one image), 15.9 (two) or 16.3-17.2 (batched), so every call under this
+// rule measured at least 1.38 times faster (run-to-run spread: 1 %); between half and 0.56 of the steps the wavefront still
+// won by 11-19 %, above that the raster schedule is faster and stays.
+bool wavefront_auto(const basic_scanline_plan *p, int batch, int h, int w)
+{
+    (void)batch;
+    return 2 * static_cast<int64_t>(wavefront_steps(p, h, w)) <= static_cast<int64_t>(h) * w;
+}
+
+// wf: the wavefront schedule's arguments (scratch: yT [steps][C][yw], priorT [steps][P][nbt])
+int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
+                      size_t *lds_bytes, hipStream_t st, bool wf = false)
+{
+    const int pad = p->ksize / 2, yw = batch * (h + pad);
+    const int64_t HW = wf ? wavefront_steps(p, h, w) : static_cast<int64_t>(h) * w;   // slabs of the coded latent and of the prior
+    const int cols = wf ? batch * h : batch;
+    const int tiles = (cols + 31) / 32, nbt = 32 * tiles;
+    if (wf) { a.wf_cols = cols; a.wf_s = wavefront_slope(p); a.wf_steps = static_cast<int>(HW); a.wf_yw = yw; }
     a.B = batch; a.C = p->C; a.H = h; a.W = w; a.P = p->P;
     a.nlayers = p->nlayers; a.ntaps = p->ntaps; a.vec4 = p->vec4;
     a.table = d_table; a.table_len = table_len;
@@ -1799,7 +1917,7 @@ int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int
     // scratch: [granule regions: layer exchange arrays [rows][nbt], coded latent [HW][C][nbt], step means / rows [nbt][C]][prior [HW][P][nbt]]
     size_t floats = 0;
     for (int l = 0; l + 1 < p->nlayers; ++l) floats += align4(2 * static_cast<size_t>(nbt) * p->rows[l]);
-    const size_t yT_off = floats;     floats += align4(2 * static_cast<size_t>(nbt) * HW * p->C);
+    const size_t yT_off = floats;     floats += align4(2 * static_cast<size_t>(wf ? yw : nbt) * HW * p->C);
     const size_t mu_off = floats;     floats += align4(2 * static_cast<size_t>(nbt) * p->C);
     const size_t is_off = floats;     floats += align4(2 * static_cast<size_t>(nbt) * p->C);
     const size_t gran_floats = floats;
@@ -1828,16 +1946,27 @@ int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int
     a.mu = reinterpret_cast<uint64_t *>(p->d_scratch + mu_off);
     a.idx_step = reinterpret_cast<uint64_t *>(p->d_scratch + is_off);
     a.priorT = nullptr;
+    if (wf && pad > 0) {
+        const int64_t total = HW * p->C * batch * pad;
+        int64_t g = (total + 255) / 256;
+        hipLaunchKernelGGL(wavefront_pads_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, a.yT, p->C, batch, h, pad, yw, total);
+        BASIC_HIP_TRY(hipGetLastError());
+    }
     if (p->P > 0) {
         float *pT = p->d_scratch + pT_off;
-        const int64_t total = static_cast<int64_t>(batch) * HW * p->P;
+        const int64_t total = static_cast<int64_t>(cols) * HW * p->P;
         int64_t g = (total + 255) / 256;
-        hipLaunchKernelGGL(transpose_prior_batched_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, d_prior, pT, batch,
-                           p->P, static_cast<int>(HW), nbt, total);
+        if (wf)
+            hipLaunchKernelGGL(transpose_prior_wavefront_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, d_prior, pT, p->P, h, w,
+                               a.wf_s, a.wf_steps, nbt, total);
+        else
+            hipLaunchKernelGGL(transpose_prior_batched_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, d_prior, pT, batch,
+                               p->P, static_cast<int>(HW), nbt, total);
         BASIC_HIP_TRY(hipGetLastError());
         a.priorT = pT;
     }
-    for (int t = 0; t < p->ntaps; ++t) { a.tap_dy[t] = p->tap_dy[t]; a.tap_dx[t] = p->tap_dx[t]; a.tap_off[t] = p->tap_dy[t] * w + p->tap_dx[t]; }
+    // (wavefront: a tap's slab relative to the step's: dx steps along the row, wf_s per row)
+    for (int t = 0; t < p->ntaps; ++t) { a.tap_dy[t] = p->tap_dy[t]; a.tap_dx[t] = p->tap_dx[t]; a.tap_off[t] = p->tap_dy[t] * (wf ? a.wf_s : w) + p->tap_dx[t]; }
     *lds_bytes = (align4(table_len) + 4 + 96 + static_cast<size_t>(p->b_tiles) * kBTile) * sizeof(float);   // table, flags, biases, partial tiles
     a.bar = p->d_bar;
     a.err = reinterpret_cast<int *>(p->d_bar + 1);
@@ -1865,7 +1994,7 @@ struct ScanProfile {
         (void)hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
         (void)hipFree(d);
         d = nullptr;
-        const double steps = static_cast<double>(a.H) * a.W;
+        const double steps = a.wf_cols ? static_cast<double>(a.wf_steps) : static_cast<double>(a.H) * a.W;
         if (a.nbt) {   // batched kernel: first context workgroup (late: wave 1, early: wave 0), first dense workgroup (wave 0)
             fprintf(stderr, "scan-line %s profile, 10 ns ticks per coding step | context tile: wait for y %.1f, late block %.1f, barrier + finish %.1f, early half %.1f | ", what,
                     h[0] / steps, h[1] / steps, h[2] / steps, h[3] / steps);
@@ -1909,7 +2038,7 @@ size_t decoder_lds_bytes(const RansFastView &tv)
 }
 
 struct ScanLaunch {
-    ScanKernel kernel;   // kGeneric, kPipelined or kBatched
+    ScanKernel kernel;   // kGeneric, kPipelined, kBatched or kWavefront
     int grid;            // compute workgroups, then the decoder workgroups
     int ncompute;
     int cus;
@@ -1919,6 +2048,9 @@ struct ScanLaunch {
 // The one place that decides how a scan-line call runs: which kernel (the batched one from 3 images on where it fits, else the
 // pipelined one where it fits, else the generic one; BASIC_SCAN_KERNEL = generic | pipelined | batched forces one, with
 // identical results), its grid and its LDS.  Fills the launch arguments; `tables` != nullptr: decode.
+// Encode calls have a second schedule, the wavefront one of the batched kernel: forced by BASIC_SCAN_KERNEL=wavefront or by the
+// plan's encode schedule (the environment wins over the plan), taken in auto where wavefront_auto says so; the plan's raster
+// schedule is the choice above, whatever wavefront_auto says.  Decode calls ignore both.
 int prepare_launch(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
                    const basic_rans_tables *tables, hipStream_t st, ScanLaunch *L)
 {
@@ -1927,8 +2059,11 @@ int prepare_launch(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w,
         if (!strcmp(e, "generic")) force = ScanKernel::kGeneric;
         else if (!strcmp(e, "pipelined")) force = ScanKernel::kPipelined;
         else if (!strcmp(e, "batched")) force = ScanKernel::kBatched;
+        else if (!strcmp(e, "wavefront")) force = ScanKernel::kWavefront;
     }
     const bool decode = tables != nullptr;
+    if (force == ScanKernel::kWavefront && decode) force = ScanKernel::kAuto;
+    if (force == ScanKernel::kAuto && !decode && p->encode_schedule == BASIC_SCAN_SCHEDULE_WAVEFRONT) force = ScanKernel::kWavefront;
     if (decode) {
         const int rc = rans_fast_view(tables, &a.tv);
         if (rc) return rc;
@@ -1938,7 +2073,15 @@ int prepare_launch(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w,
     if (rc) return rc;
     const bool fits = batched_fits(p, batch, w, ndec, L->cus);
     if (force == ScanKernel::kBatched) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=batched, but this call does not fit the batched kernel");
-    if (force == ScanKernel::kBatched || (force == ScanKernel::kAuto && fits && batch >= 3)) {
+    const bool wf_fits = !decode && wavefront_fits(p, batch, h, L->cus);
+    if (force == ScanKernel::kWavefront) BASIC_REQUIRE(wf_fits, "scanline: the wavefront encode schedule was asked for, but this call does not fit it");
+    if (force == ScanKernel::kWavefront ||
+        (force == ScanKernel::kAuto && wf_fits && p->encode_schedule == BASIC_SCAN_SCHEDULE_AUTO && wavefront_auto(p, batch, h, w))) {
+        rc = fill_args_batched(p, a, batch, h, w, d_prior, d_table, table_len, &L->lds_bytes, st, true);
+        if (rc) return rc;
+        L->kernel = ScanKernel::kWavefront;
+        L->ncompute = (a.nbt / 32) * p->b_nw;   // wavefront_fits: the grid is resident
+    } else if (force == ScanKernel::kBatched || (force == ScanKernel::kAuto && fits && batch >= 3)) {
         rc = fill_args_batched(p, a, batch, h, w, d_prior, d_table, table_len, &L->lds_bytes, st);
         if (rc) return rc;
         L->kernel = ScanKernel::kBatched;
@@ -1962,19 +2105,26 @@ int prepare_launch(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w,
 
 template <bool DECODE> int run_launch(basic_scanline_plan *p, ScanArgs &a, const ScanLaunch &L, hipStream_t st)
 {
-    const void *fn = L.kernel == ScanKernel::kBatched     ? reinterpret_cast<const void *>(scanline_batched_kernel<DECODE>)
+    const void *fn = L.kernel == ScanKernel::kWavefront   ? reinterpret_cast<const void *>(scanline_batched_kernel<false, !DECODE>)
+                     : L.kernel == ScanKernel::kBatched   ? reinterpret_cast<const void *>(scanline_batched_kernel<DECODE>)
                      : L.kernel == ScanKernel::kPipelined ? reinterpret_cast<const void *>(scanline_pipelined_kernel<DECODE>)
                                                           : reinterpret_cast<const void *>(scanline_persistent_kernel<DECODE>);
     BASIC_HIP_TRY(ensure_max_lds(fn));
     ScanProfile prof;
     int rc = prof.begin(a, st);
     if (rc) return rc;
+    BASIC_REQUIRE(!(DECODE && L.kernel == ScanKernel::kWavefront), "scanline: the wavefront schedule is encode only");
+    p->last_kernel = L.kernel == ScanKernel::kWavefront  ? BASIC_SCAN_KERNEL_WAVEFRONT
+                     : L.kernel == ScanKernel::kBatched  ? BASIC_SCAN_KERNEL_BATCHED
+                     : L.kernel == ScanKernel::kPipelined ? BASIC_SCAN_KERNEL_PIPELINED
+                                                          : BASIC_SCAN_KERNEL_GENERIC;
     rc = chained_launch(p, st, L.grid, L.cus, [&] {
-        if (L.kernel == ScanKernel::kBatched) hipLaunchKernelGGL(scanline_batched_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
+        if (L.kernel == ScanKernel::kWavefront) hipLaunchKernelGGL((scanline_batched_kernel<false, !DECODE>), dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
+        else if (L.kernel == ScanKernel::kBatched) hipLaunchKernelGGL(scanline_batched_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
         else if (L.kernel == ScanKernel::kPipelined) hipLaunchKernelGGL(scanline_pipelined_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
         else hipLaunchKernelGGL(scanline_persistent_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
     });
-    prof.report(a, st, L.kernel == ScanKernel::kBatched ? (DECODE ? "decode (batched)" : "encode (batched)") : (DECODE ? "decode" : "encode"));
+    prof.report(a, st, L.kernel == ScanKernel::kWavefront ? "encode (wavefront)" : L.kernel == ScanKernel::kBatched ? (DECODE ? "decode (batched)" : "encode (batched)") : (DECODE ? "decode" : "encode"));
     return rc;
 }
 
@@ -2042,6 +2192,36 @@ extern "C" int basic_scanline_batched_max(const basic_scanline_plan *p, int w, i
         const int ndec = decode ? decoder_workgroups(b) : 0;
         if (batched_fits(p, b, w, ndec, cus)) { *max_batch = b; break; }
     }
+    return BASIC_OK;
+}
+
+// The largest batch the wavefront encode schedule serves for an h x w latent on the current device: 0 = never (the layers do
+// not have the batched kernel's shape, h alone needs more than its 64 columns, or the grid is not resident).  Any width fits.
+extern "C" int basic_scanline_wavefront_max(const basic_scanline_plan *p, int h, int w, int *max_batch)
+{
+    BASIC_REQUIRE(p && max_batch && h >= 1 && w >= 1, "scanline_wavefront_max: bad argument");
+    *max_batch = 0;
+    int cus = 0;
+    int rc = device_cus(&cus);
+    if (rc) return rc;
+    for (int b = 32 * kBatchedMaxTiles / h; b >= 1; --b)
+        if (wavefront_fits(p, b, h, cus)) { *max_batch = b; break; }
+    return BASIC_OK;
+}
+
+// Which kernel the plan's last launch (either direction) ran: BASIC_SCAN_KERNEL_*; NONE before the first launch.
+extern "C" int basic_scanline_last_kernel(const basic_scanline_plan *p, int *kernel)
+{
+    BASIC_REQUIRE(p && kernel, "scanline_last_kernel: bad argument");
+    *kernel = p->last_kernel;
+    return BASIC_OK;
+}
+
+extern "C" int basic_scanline_set_encode_schedule(basic_scanline_plan *p, int schedule)
+{
+    BASIC_REQUIRE(p && (schedule == BASIC_SCAN_SCHEDULE_AUTO || schedule == BASIC_SCAN_SCHEDULE_RASTER || schedule == BASIC_SCAN_SCHEDULE_WAVEFRONT),
+                  "scanline_set_encode_schedule: bad argument");
+    p->encode_schedule = schedule;
     return BASIC_OK;
 }
 

@@ -590,8 +590,12 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
     # BaSIC's shape -- take the batched persistent kernel (round 4: the batch as the N dimension of MFMA tiles, weights in
     # registers); what neither serves goes to the per-step path
     persistent_scanline_max_batch = 4
+    # how the persistent ENCODE launch walks the latent: "raster" (one step per position), "wavefront" (the rows of an image in
+    # parallel, each ksize // 2 + 2 columns behind the row above: W + s (H - 1) steps; batch * H <= 64; a call it does not fit
+    # raises) or "auto" (the library takes the wavefront where it fits and measured faster).  The integers are the same.
+    scanline_encode_schedule = "auto"
 
-    def _scanline_plan(self, plan, prior, batch=1, decode=False, width=None):
+    def _scanline_plan(self, plan, prior, batch=1, decode=False, width=None, height=None):
         """The ScanlinePlan serving this call, or None (then the per-step path codes the same integers): the configuration
         must be the scan-line schedule with dense merger layers that fit the chip's LDS, the batch one a persistent kernel
         serves, and the launch must fit the device (the decoder launch adds one wavefront per image stream and needs the
@@ -615,10 +619,16 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         sl = sp[0]
         if sl is None:
             return None
+        schedule = self.scanline_encode_schedule
         if batch > self.persistent_scanline_max_batch and (width is None or batch > sl.batched_max(width, decode)):
-            return None
+            # no raster kernel serves this batch; an encode call may still run as a wavefront (a narrow latent, for one)
+            if decode or schedule == "raster" or width is None or height is None or batch > sl.wavefront_max(height, width):
+                return None
+            schedule = "wavefront"
         if not (sl.can_decode(self._tables, batch) if decode else sl.can_encode(batch)):
             return None
+        if not decode:
+            sl.set_encode_schedule(schedule)
         return sl
 
     def _run_encode(self, y, prior, pgm=None):
@@ -628,7 +638,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
             outs = [self._run_encode(y[b:b + 1].contiguous(), None if prior is None else prior[b:b + 1].contiguous(), pgm[b:b + 1])
                     for b in range(y.shape[0])]
             return (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]), torch.cat([o[2].clone() for o in outs]), plan)
-        sl = self._scanline_plan(plan, prior, y.shape[0], width=y.shape[3])
+        sl = self._scanline_plan(plan, prior, y.shape[0], width=y.shape[3], height=y.shape[2])
         if sl is not None:
             sym, idx, ybuf = sl.encode(y, prior, self._scale_table_dev)
             sl.check()   # a launch whose grid never became resident gave up on its barriers: fail loudly, never code garbage

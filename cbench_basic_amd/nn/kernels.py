@@ -461,6 +461,20 @@ class HyperpriorSession:
         return out
 
 
+SCAN_KERNELS = ("generic", "pipelined", "batched", "wavefront")   # BASIC_SCAN_KERNEL_*
+SCAN_SCHEDULES = ("auto", "raster", "wavefront")                  # BASIC_SCAN_SCHEDULE_*
+
+
+def wavefront_schedule(h, w, ksize):
+    """The wavefront encode schedule of an h x w latent with a causal ksize x ksize window, as the kernel walks it
+    (csrc/scanline.hip): row r runs s = ksize // 2 + 2 columns behind row r - 1, so step t codes column t - s * r of every
+    row for which that lies in [0, w).  -> (steps, table): steps = w + s * (h - 1); table[t][r] = the column row r codes
+    in step t, or None where the row is idle (it then stands for the zero padding left and right of the image)."""
+    s = ksize // 2 + 2
+    steps = w + s * (h - 1)
+    return steps, [[t - s * r if 0 <= t - s * r < w else None for r in range(h)] for t in range(steps)]
+
+
 class ScanlinePlan:
     """basic_scanline_*: the persistent scan-line AR coding loop (one launch for all H*W coding steps)."""
 
@@ -522,6 +536,29 @@ class ScanlinePlan:
             _lib.check(_lib.lib().basic_scanline_batched_max(self._h, int(width), int(bool(decode)), ctypes.byref(m)))
             cache[key] = m.value
         return cache[key]
+
+    def wavefront_max(self, height, width):
+        """Largest batch the wavefront encode schedule serves for a `height` x `width` latent on this device (0: never)."""
+        key = (int(height), int(width), torch.cuda.current_device())
+        cache = self.__dict__.setdefault("_wavefront_max", {})
+        if key not in cache:
+            m = ctypes.c_int()
+            _lib.check(_lib.lib().basic_scanline_wavefront_max(self._h, int(height), int(width), ctypes.byref(m)))
+            cache[key] = m.value
+        return cache[key]
+
+    def last_kernel(self):
+        """The kernel the plan's last launch ran: "generic", "pipelined", "batched" or "wavefront"; None before the first."""
+        k = ctypes.c_int()
+        _lib.check(_lib.lib().basic_scanline_last_kernel(self._h, ctypes.byref(k)))
+        return SCAN_KERNELS[k.value] if 0 <= k.value < len(SCAN_KERNELS) else None
+
+    def set_encode_schedule(self, schedule):
+        """How encode calls are scheduled from now on: "auto", "raster" (never the wavefront) or "wavefront" (always: a call
+        that does not fit it raises).  The coded integers do not depend on it."""
+        if schedule not in SCAN_SCHEDULES:
+            raise ValueError(f"encode schedule must be one of {SCAN_SCHEDULES}, not {schedule!r}")
+        _lib.check(_lib.lib().basic_scanline_set_encode_schedule(self._h, SCAN_SCHEDULES.index(schedule)))
 
     def can_decode(self, tables, batch):
         ok = ctypes.c_int()

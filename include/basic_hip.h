@@ -341,6 +341,8 @@ void basic_hp_session_destroy(basic_hp_session *s);
  *    position (masked_conv.py:102-228: the causal raster neighbours), the dense 1x1 merger layers on cat(ctx, prior)
  *    (masked_conv.py:262-300 / pgm_coder.py:1606-1638), Gaussian index + quantise (pgm_coder.py:735-821,927-941).
  *    The layers' weights stay resident in the LDS of `workgroups` compute units for the whole launch.
+ *    An encode launch may instead walk the rows of an image in parallel (the wavefront schedule, see
+ *    basic_scanline_wavefront_max): W + (k / 2 + 2) * (H - 1) dependent steps, the same integers.
  * ==================================================================================== */
 typedef struct basic_scanline_plan basic_scanline_plan;
 /* ctx_weight [ctx_out][channels][k][k] (PyTorch layout; only the causal taps are used), ctx_bias [ctx_out] or NULL.
@@ -379,6 +381,30 @@ int basic_scanline_can_decode(const basic_scanline_plan *p, const basic_rans_tab
  * workgroups.  *max_batch = the largest batch it serves for a latent `w` columns wide on the current device (0 = never);
  * decode != 0 counts the decoder workgroups too.  Which kernel serves a call never changes the coded integers. */
 int basic_scanline_batched_max(const basic_scanline_plan *p, int w, int decode, int *max_batch);
+/* ENCODE calls have a second schedule of the batched kernel, the WAVEFRONT: the causal k x k window orders a position only
+ * after its left neighbour and the rows above, so row r may run s = k / 2 + 2 columns behind row r - 1.  A column of the MFMA
+ * tiles is then one row of one image (B * H <= 64), step t codes column position t - s * r of every row r, and a launch walks
+ * W + s * (H - 1) dependent steps instead of H * W (172 instead of 1,536 for a 32 x 48 latent).  The decoder cannot: it reads one
+ * serial rANS stream.  The schedule never changes the coded integers or d_ybuf.
+ * *max_batch = the largest batch the wavefront serves for an h x w latent on the current device; 0 = never (layers not of the
+ * batched kernel's shape, h > 64, or a grid that is not resident).  Any width fits. */
+int basic_scanline_wavefront_max(const basic_scanline_plan *p, int h, int w, int *max_batch);
+/* *kernel = which kernel the plan's last launch (encode or decode) ran. */
+#define BASIC_SCAN_KERNEL_NONE (-1) /* no launch yet */
+#define BASIC_SCAN_KERNEL_GENERIC 0
+#define BASIC_SCAN_KERNEL_PIPELINED 1
+#define BASIC_SCAN_KERNEL_BATCHED 2
+#define BASIC_SCAN_KERNEL_WAVEFRONT 3
+int basic_scanline_last_kernel(const basic_scanline_plan *p, int *kernel);
+/* How the plan's encode calls are scheduled from now on.  AUTO (the default): the wavefront where it fits and measured
+ * faster, else raster.  RASTER: the choice described at basic_scanline_batched_max, never the wavefront.  WAVEFRONT: always;
+ * a call that does not fit it fails with BASIC_ERR_INVALID ("does not fit").  The environment variable
+ * BASIC_SCAN_KERNEL = generic | pipelined | batched | wavefront, when set, wins over the plan's schedule; decode calls
+ * ignore "wavefront" and the schedule. */
+#define BASIC_SCAN_SCHEDULE_AUTO 0
+#define BASIC_SCAN_SCHEDULE_RASTER 1
+#define BASIC_SCAN_SCHEDULE_WAVEFRONT 2
+int basic_scanline_set_encode_schedule(basic_scanline_plan *p, int schedule);
 int basic_scanline_status(basic_scanline_plan *p, void *hip_stream, int *poisoned);
 void basic_scanline_plan_destroy(basic_scanline_plan *p);
 
