@@ -86,6 +86,7 @@ _SIGNATURES = {
     "basic_scanline_can_decode": (_I, [_P, _P, _I, _P]),
     "basic_scanline_batched_max": (_I, [_P, _I, _I, _P]),
     "basic_scanline_wavefront_max": (_I, [_P, _I, _I, _P]),
+    "basic_scanline_band_max": (_I, [_P, _I, _I, _P]),
     "basic_scanline_last_kernel": (_I, [_P, _P]),
     "basic_scanline_set_encode_schedule": (_I, [_P, _I]),
     "basic_scanline_status": (_I, [_P, _P, _P]),

@@ -1,6 +1,7 @@
 // Persistent scan-line autoregressive coding loop: ONE launch walks all coding steps of a batch -- H*W of them in raster order,
 // or, for an encode call under the wavefront schedule of the batched kernel (the rows of an image in parallel, each
-// ksize / 2 + 2 columns behind the row above), W + (ksize / 2 + 2) * (H - 1).
+// ksize / 2 + 2 columns behind the row above), W + (ksize / 2 + 2) * (H - 1); under its band schedule (the same steps, an image's
+// rows sharing W / (ksize / 2 + 2) + 1 columns of a tile) a batch of any size and height, in as many launches as it needs.
 //
 // Reference: TopoGroupPGMPriorCoder._encode_with_pgm / _pgm_generate (cbench/modules/prior_model/prior_coder/pgm_coder.py:
 // 912-981) with the "scanline" topo groups (one group per spatial position, raster order, :1416-1491), the masked 5x5
@@ -100,6 +101,11 @@ struct ScanArgs {
     int wf_s;              // steps a row starts after the row above it: ksize / 2 + 2
     int wf_steps;          // W + wf_s * (H - 1)
     int wf_yw;             // columns of a yT slab: per image ksize / 2 pad columns (the rows above the image: zeros), then its H rows
+    // band encode schedule only (band_A == 0 otherwise; the wf_* fields hold as for the wavefront, B = the images of THIS launch): a lane
+    // of a column tile is a SLOT of an image -- image (tile * band_ipt + lane / band_A), slot lane % band_A -- that walks rows slot,
+    // slot + band_A, ... of its image one after the other (see the band section in front of scanline_batched_kernel)
+    int band_A;            // slots per image: W / wf_s + 1, so a slot's period band_A * wf_s exceeds W
+    int band_ipt;          // images per column tile: 32 / band_A
 };
 
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -959,10 +965,11 @@ __device__ __forceinline__ uint32_t b_min_tag(const u64x2 (&g)[16])
 }
 
 // waits until all 32 granules carry `want` (re-issuing the block's loads while one is missing); false = poisoned launch
-__device__ __forceinline__ bool b_wait(const ScanArgs &a, brsrc r, int sbase, int stride, uint32_t voff, uint32_t want, u64x2 (&g)[16])
+// (mask: the lanes whose granules are looked at -- the band schedule's lanes without a row load granules nobody publishes)
+__device__ __forceinline__ bool b_wait(const ScanArgs &a, brsrc r, int sbase, int stride, uint32_t voff, uint32_t want, u64x2 (&g)[16], bool mask = true)
 {
     unsigned spins = 0;
-    while (__ballot(b_min_tag(g) != want) != 0ull) {
+    while (__ballot(mask && b_min_tag(g) != want) != 0ull) {
         if (++spins > kSpinLimit || (spins % 256u == 0u && __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
             __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return false;
@@ -974,14 +981,14 @@ __device__ __forceinline__ bool b_wait(const ScanArgs &a, brsrc r, int sbase, in
 
 // one piece polled alone before a block's loads are issued: a wave that waits LONG (the context role, idle through the dense
 // layers) keeps one load in flight instead of sixteen
-__device__ __forceinline__ bool b_sentinel(const ScanArgs &a, brsrc r, int soff, uint32_t voff, uint32_t want)
+__device__ __forceinline__ bool b_sentinel(const ScanArgs &a, brsrc r, int soff, uint32_t voff, uint32_t want, bool mask = true)
 {
     unsigned spins = 0;
     for (;;) {
         uint32_t vo = voff;
         asm volatile("" : "+v"(vo)::"memory");
         const u64x2 g = b_ld2(r, vo, soff);
-        if (__ballot(min(static_cast<uint32_t>(g[0] >> 32), static_cast<uint32_t>(g[1] >> 32)) != want) == 0ull) return true;
+        if (__ballot(mask && min(static_cast<uint32_t>(g[0] >> 32), static_cast<uint32_t>(g[1] >> 32)) != want) == 0ull) return true;
         if (++spins > kSpinLimit || (spins % 256u == 0u && __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
             __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return false;
@@ -1122,10 +1129,42 @@ __device__ __forceinline__ f4 b_leaky(f4 v)
 // the prior are indexed by step.  Causal tap (dy, dx) of step t is column col + dy of slab t + dx + wf_s * dy (tap_off holds
 // dx + wf_s * dy); a column outside its row's [0, W) publishes zero granules with the step's tag, and the pad columns in front
 // of every image hold zeros for every step, so a tap outside the image multiplies zeros: no predicate inside a chain.
-template <bool DECODE, bool WF = false>
+//
+// BAND (with WF): the band encode schedule -- the wavefront's steps, slabs, taps and tags, but a lane is no longer bound to one row.
+// Row r is in flight only during steps [s r, s r + W), so an image needs about W / s lanes, not H: it owns A = W / s + 1 SLOTS (lanes
+// of ONE column tile, 32 / A images per tile, so the tiles of a launch share nothing and never wait for each other); slot j codes
+// rows j, j + A, j + 2 A, ... back to back with period A s.  At step t the slot has u = t - s j, (n, c) = divmod(u, A s), row
+// r = j + n A (before its first row: n = 0, c = u < 0) and codes (r, c) iff r < H and 0 <= c < W.  The slabs of the coded latent
+// stay indexed by step and by the TRUE (image, pad + row) column, so tap (dy, dx) is still slab t + dx + s dy at column + dy,
+// wave-uniform; what changes per step is the lane's own row, hence its offsets into the slabs and into y / sym / idx / ybuf, and
+// the gather of the prior (transpose_prior_band_kernel).
+//   * A slot "has a row" while r < H.  Such a lane publishes (slab t, row r) in EVERY step: the coded value, or zero where c lies
+//     outside [0, W) -- A s > W, so every row is followed by at least one idle step of its slot.
+//   * The late half's left-neighbour block reads (slab t - 1, the row the lane had in step t - 1): what the lane itself published
+//     one step ago.  Inside a row that is the left neighbour; at c = 0 it is the zero of the idle step before (the padding left of
+//     the image); and it is a real wait in every step, for every lane with a row -- which paces the context workgroups exactly as
+//     the wavefront's columns do (overwrite argument of the header comment; the slot of the last row has a row until the last step).
+//     It also validates a row's LAST granule, in the idle step that follows the row, so the early half may read every coded granule
+//     unchecked as before: it was validated by this workgroup's late waves one step after it was coded, and a tap other than the
+//     left neighbour is at least two steps old.
+//   * Every other out-of-image tap of a coding lane lands on (slab s r' + c', row r') with c' in [-k/2, 0) or [W, W + k/2), or on a
+//     pad row above the image: never coded positions, all zeros.  Who writes each: the pad rows, wavefront_pads_kernel before the
+//     launch; c' in [W, A s), the row's own slot in the idle steps after the row; c' < 0 of a slot's FIRST row (r' < A), the slot
+//     before it starts; the rest -- c' < 0 of rows r' >= A, and c' >= A s -- band_edges_kernel before the launch.  The two sets are
+//     kept DISJOINT on purpose: a granule written before the launch would satisfy the left-neighbour wait of its slot at once, and
+//     a step in which no lane of a tile really waits lets the context workgroups run ahead and overwrite layer outputs that are
+//     still to be read (a latent narrower than s has such steps).
+//   * A slot that has just left its last row still waits for that row's last publication (the test is "had a row one step ago"),
+//     so every granule a slot publishes is validated one step later.
+//   * Lanes without a row (holes of a tile, slots beyond H, slots past their last row) load from clamped in-bounds addresses, are
+//     masked out of every tag test, and publish nothing into the coded latent; MFMA columns are independent, so what they compute
+//     reaches nobody.  They still publish their layer outputs (slot lanes) or read the tile's first lane's (holes), so the dense
+//     layers' tag tests see a published granule in every lane.
+template <bool DECODE, bool WF = false, bool BAND = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void scanline_batched_kernel(const ScanArgs a)
 {
     static_assert(!(DECODE && WF), "the wavefront schedule is encode only: the decoder reads one serial rANS stream");
+    static_assert(WF || !BAND, "the band schedule is a wavefront schedule");
     extern __shared__ float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wg = blockIdx.x;
@@ -1134,8 +1173,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int t = wg % T, j = wg / T;                  // column tile; role index inside the tile's set of workgroups
     const int h = lane >> 5, n = lane & 31, col = t * 32 + n;
     const int ncols = WF ? a.wf_cols : a.B;            // (wavefront: a column is one row of one image)
-    const bool img = col < ncols;                      // columns beyond the batch: nothing published (they LOAD the last image's
-    const int colc = img ? col : ncols - 1;            // operands: no predicates, no zero fill in the load paths)
+    // band: this lane's image inside its tile and its slot; a tile's first lane is always a slot of an image
+    const int bA = BAND ? a.band_A : 1, bAs = bA * a.wf_s;
+    const int bli = n / bA, bj = n - bli * bA;
+    const bool bslot = BAND && bli < a.band_ipt && t * a.band_ipt + bli < a.B && bj < a.H;
+    const bool img = BAND ? bslot : col < ncols;       // columns beyond the batch: nothing published (they LOAD the last image's
+    const int colc = img ? col : (BAND ? t * 32 : ncols - 1);   // operands: no predicates, no zero fill in the load paths)
     const bool dense = j < a.nd;
     const int r0 = dense ? j : j - a.nd;               // this workgroup's row tile (dense role: of every layer that has one)
     const int nb0 = a.ntaps * a.bpt;                   // context blocks; the last kBLate run in the late half (the left neighbour's bpt among them),
@@ -1144,10 +1187,17 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     const uint32_t voff = static_cast<uint32_t>(h * NBT + colc) * 16u;   // the lane's 16-byte piece inside a (channel quad, column tile) slab
     const int pstride = 2 * NBT * 16;                  // bytes between consecutive pieces of a lane
     // the coded latent's slabs: the same layout; the wavefront's are wf_yw columns wide (pad columns) and have their own lane offset
-    const int wb = WF ? colc / a.H : 0, wr = WF ? colc - wb * a.H : 0;   // wavefront: this column's image and row
+    // (band: the image, and the slot's FIRST row; lanes without a slot stand on row 0 of their tile's first image)
+    const int wb = BAND ? (bslot ? t * a.band_ipt + bli : t * a.band_ipt) : WF ? colc / a.H : 0;
+    const int wr = BAND ? (bslot ? bj : 0) : WF ? colc - wb * a.H : 0;   // wavefront: this column's image and row
     const int wpad = WF ? a.wf_s - 2 : 0;
     const int YW = WF ? a.wf_yw : NBT, ycol = WF ? wb * (a.H + wpad) + wpad + wr : colc;
     const uint32_t voff_y = WF ? static_cast<uint32_t>(h * YW + ycol) * 16u : voff;
+    // band: the lane's piece inside a slab while its slot stands on row r (past the last row: clamped, the lane is masked out)
+    const uint32_t voff_y0 = static_cast<uint32_t>(h * YW + ycol - wr) * 16u;
+    auto band_voff = [&](int r) { return voff_y0 + static_cast<uint32_t>(r < a.H ? r : a.H - 1) * 16u; };
+    // band: a slot's (column, row) one step on; it starts at (-s * slot, slot)
+    auto band_step = [&](int &c, int &r) { if (++c == bAs) { c = 0; r += bA; } };
     const int ypstride = WF ? 2 * YW * 16 : pstride;
     const int nsteps = WF ? a.wf_steps : HW;
     // granule index of this thread's first finishing row (channel r0 * 32 + frow) relative to its tile's first piece
@@ -1203,6 +1253,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
         const int64_t pos_bytes = static_cast<int64_t>(C) * YW * 8;   // a position's (wavefront: a step's) slab of the coded latent
         f4 esum = zero4;   // position 0 has no causal neighbour: its early sum is zero
         int px = 0, py = 0;
+        int b_c = -a.wf_s * wr, b_r = wr, b_rp = wr;   // band: this slot's column and row in step p, its row in step p - 1
         // this wave's late block as A fragments, lane-major (8 x 16 bytes per lane): saved once, re-fetched every step
         const char *wfrag = reinterpret_cast<const char *>(a.wlate) + static_cast<int64_t>(wg) * (kThreads * 128);
         {
@@ -1230,6 +1281,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
                 const int ny = py + a.tap_dy[tp], nx = px + a.tap_dx[tp];
                 const bool inside = WF ? p + a.tap_off[tp] >= 0 : ny >= 0 && nx >= 0 && nx < a.W;
                 const int dyb = WF ? a.tap_dy[tp] * 16 : 0;   // wavefront: the tap's row is the column dy pieces further on
+                // band: the left neighbour's block reads what this lane published one step ago, the others stand on this step's row;
+                // looked at are the lanes that had a row one step ago (left) / that code a position in this step (see the band section)
+                const bool b_has = bslot && b_r < a.H;
+                const uint32_t vyl = BAND ? band_voff(left ? b_rp : b_r) : voff_y;
+                const bool ml = !BAND || (left ? bslot && b_rp < a.H : b_has && static_cast<unsigned>(b_c) < static_cast<unsigned>(a.W));
                 f4 wl4[8];
                 {
                     uint32_t fo = static_cast<uint32_t>(tid) * 128u;
@@ -1242,10 +1298,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
                     const int pos = left ? p - 1 : p + a.tap_off[tp];
                     const brsrc yr = b_rsrc(yT8 + pos * pos_bytes + dyb);
                     const int sb = cb * blk_bytes;
-                    if (left && !b_sentinel(a, yr, sb + 15 * ypstride, voff_y, static_cast<uint32_t>(pos + 1))) return;
+                    if (left && !b_sentinel(a, yr, sb + 15 * ypstride, vyl, static_cast<uint32_t>(pos + 1), ml)) return;
                     if (a.prof) tp1 = wall_clock64();
-                    b_issue(yr, sb, ypstride, voff_y, gA);
-                    if (!b_wait(a, yr, sb, ypstride, voff_y, static_cast<uint32_t>(pos + 1), gA)) return;
+                    b_issue(yr, sb, ypstride, vyl, gA);
+                    if (!b_wait(a, yr, sb, ypstride, vyl, static_cast<uint32_t>(pos + 1), gA, ml)) return;
                     if (inside)
                         acc = b_chain_vv([&](int i) { return wl4[i >> 2][i & 3]; }, [&](int i) { return __uint_as_float(static_cast<uint32_t>(gA[i >> 1][i & 1])); });
                 }
@@ -1262,6 +1318,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
             const long long tp3 = a.prof ? wall_clock64() : 0;
             if (prof1) { a.prof[0] += tp1 - tp0; a.prof[1] += tp2 - tp1; a.prof[2] += tp3 - tp2; }
             if (!WF && ++px == a.W) { px = 0; ++py; }
+            if constexpr (BAND) { b_rp = b_r; band_step(b_c, b_r); }
             if (p + 1 == nsteps) break;
             // ---------- early half for the next position q = p + 1, in the shadow of the dense layers: partial tiles of the blocks
             // of the taps coded at least two steps ago, then their sum in block order.  Every granule read here was validated by
@@ -1270,6 +1327,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
             // re-filled piece by piece with block k + 2 (the loads sit between the MFMAs, where a lone wave's issue slots are
             // free), block k + 1 landed during the chain before
             const int q = p + 1, qy = py, qx = px;
+            const uint32_t vye = BAND ? band_voff(b_r) : voff_y;   // (band: the lane's piece on the row its slot has in step q)
             auto early_valid = [&](int kk) { return wave + 4 * kk < early; };
             // block e of this position's early window: false when its tap lies outside the image (zeros); r / sb = where its operands are
             auto early_src = [&](int e, brsrc &r, int &sb) -> bool {
@@ -1286,14 +1344,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
             auto early_tag = [&](int e, uint32_t &want) -> bool {
                 const int tp = e / a.bpt;
                 want = static_cast<uint32_t>(q + a.tap_off[tp] + 1);
-                return WF && t > 0 && a.tap_dy[tp] != 0;
+                return WF && !BAND && t > 0 && a.tap_dy[tp] != 0;   // (band: an image's slots share a tile)
             };
             bool early_ok = true;
             bool have_a = false, have_b = false;   // whether buffer A / B holds (or is receiving) a block that is used
             {
                 brsrc r; int sb;
-                if (early_valid(0) && (have_a = early_src(wave, r, sb))) b_issue(r, sb, ypstride, voff_y, gA);
-                if (early_valid(1) && (have_b = early_src(wave + 4, r, sb))) b_issue(r, sb, ypstride, voff_y, gB);
+                if (early_valid(0) && (have_a = early_src(wave, r, sb))) b_issue(r, sb, ypstride, vye, gA);
+                if (early_valid(1) && (have_b = early_src(wave + 4, r, sb))) b_issue(r, sb, ypstride, vye, gB);
             }
             static_for<0, kBSlots>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
@@ -1312,13 +1370,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
                             brsrc rc = b_rsrc(yT8);
                             int sbc = 0;
                             early_src(wave + 4 * k, rc, sbc);
-                            early_ok = b_wait(a, rc, sbc, ypstride, voff_y, want, cur) && early_ok;
+                            early_ok = b_wait(a, rc, sbc, ypstride, vye, want, cur) && early_ok;
                         }
                     }
                     if (!next) early_src(wave + 4 * k, r2, sb2);   // nothing follows: the refill re-reads this block (no second copy of the chain)
-                    acc = b_chain_gran<k, true>(cur, r2, sb2, ypstride, voff_y);
+                    acc = b_chain_gran<k, true>(cur, r2, sb2, ypstride, vye);
                 } else if (have_next) {
-                    b_issue(r2, sb2, ypstride, voff_y, cur);   // (a tap outside the image enters as zeros: no chain to hide the loads behind)
+                    b_issue(r2, sb2, ypstride, vye, cur);   // (a tap outside the image enters as zeros: no chain to hide the loads behind)
                 }
                 have_cur = have_next;
                 b_store_tile(part + (wave + 4 * k) * kBTile, lane, acc);
@@ -1338,17 +1396,22 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int c0 = (r0 * 32 + frow) >> 1;          // its channels c0, c0 + 1  (rows 2c = mean, 2c + 1 = scale: "split_interleave")
     // element offsets of (image col, channel c0) in y / ybuf [B][C][HW], sym / idx [B][HW * C], the coded latent's slab, mu / idx_step [nbt][C]
     // (wavefront: of (image wb, channel c0, first position of row wr); the row's position of the step is added per step)
-    const uint32_t yoff = static_cast<uint32_t>(WF ? (wb * C + c0) * HW + wr * a.W : (col * C + c0) * HW);
-    const uint32_t ooff = static_cast<uint32_t>(WF ? (wb * HW + wr * a.W) * C + c0 : col * C * HW + c0);
-    const uint32_t toff = static_cast<uint32_t>(bm_gran(c0, WF ? ycol : col, YW)), moff = static_cast<uint32_t>(col * C + c0);
+    // (band: of (image wb, channel c0, position 0) and of the image's row 0; the slot's row and column of the step are added per step)
+    const uint32_t yoff = static_cast<uint32_t>(BAND ? (wb * C + c0) * HW : WF ? (wb * C + c0) * HW + wr * a.W : (col * C + c0) * HW);
+    const uint32_t ooff = static_cast<uint32_t>(BAND ? wb * HW * C + c0 : WF ? (wb * HW + wr * a.W) * C + c0 : col * C * HW + c0);
+    const uint32_t toff = static_cast<uint32_t>(bm_gran(c0, BAND ? ycol - wr : WF ? ycol : col, YW)), moff = static_cast<uint32_t>(col * C + c0);
     const int wsr = WF ? a.wf_s * wr : 0;              // wavefront: the step in which this column's row starts
+    int b_c = -wsr, b_r = wr;                          // band: this slot's column and row in step p
     const bool prof = a.prof && wg == 0 && tid == 0;   // BASIC_SCAN_PROFILE: first dense workgroup, wave 0
     const long long loop_c0 = prof ? clock64() : 0, loop_t0 = prof ? wall_clock64() : 0;
     for (int p = 0; p < nsteps; ++p) {
         const uint32_t tag = static_cast<uint32_t>(p + 1);
         // wavefront: the column position this lane's row codes in this step; outside [0, W) the column is idle (zeros published)
-        const int wc = WF ? p - wsr : 0;
-        const bool active = !WF || static_cast<unsigned>(wc) < static_cast<unsigned>(a.W);
+        const int wc = BAND ? b_r * a.W + b_c : WF ? p - wsr : 0;   // (band: the position inside the image)
+        const bool b_has = !BAND || (bslot && b_r < a.H);           // band: the slot has a row in this step
+        const bool active = !WF || (b_has && static_cast<unsigned>(BAND ? b_c : wc) < static_cast<unsigned>(a.W));
+        const uint32_t b_to = BAND ? static_cast<uint32_t>(2 * (b_r < a.H ? b_r : a.H - 1)) : 0u;   // band: the row's column inside a slab
+        if constexpr (BAND) band_step(b_c, b_r);
         // (per-thread element offsets stay 32-bit and opaque: as 64-bit addresses hoisted out of the loop they would be spilled)
         float y_pre0 = 0.f, y_pre1 = 0.f;
         if (!DECODE && codes && active) {   // requested a whole step before they are needed
@@ -1431,9 +1494,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
                 } else {
                     const float q0 = rintf(y_pre0 - v[0]), q1 = rintf(y_pre1 - v[2]);          // torch.round: half to even
                     uint64_t *ypos = a.yT + static_cast<int64_t>(p) * C * YW;
-                    if (WF && !active) {   // an idle column: the zero padding left and right of its row
-                        st_gran(ypos + to, 0.f, tag);
-                        st_gran(ypos + (to + static_cast<uint32_t>(2 * YW)), 0.f, tag);
+                    if constexpr (BAND) to += b_to;
+                    if (WF && !active) {   // an idle column: the zero padding left and right of its row (band: of a slot with a row)
+                        if (b_has) {
+                            st_gran(ypos + to, 0.f, tag);
+                            st_gran(ypos + (to + static_cast<uint32_t>(2 * YW)), 0.f, tag);
+                        }
                     } else {
                         st_gran(ypos + to, q0 + v[0], tag);
                         st_gran(ypos + (to + static_cast<uint32_t>(2 * YW)), q1 + v[2], tag);     // channel c0 + 1: the odd-parity piece of the same quad
@@ -1500,6 +1566,44 @@ __global__ void wavefront_pads_kernel(uint64_t *__restrict__ yT, int C, int B, i
         const int c = static_cast<int>(q % C);
         const int64_t t = q / C;
         yT[t * C * yw + bm_gran(c, b * (H + pad) + k, yw)] = static_cast<uint64_t>(t + 1) << 32;
+    }
+}
+
+// band schedule: prior [B][P][HW] -> priorT [steps] x slab [P][nbt] (bm_prior); lane column (tile, lane) of step t = the position its
+// slot codes in that step, zero where it codes none (all nbt columns are written: a hole lane reads its tile's first column)
+__global__ void transpose_prior_band_kernel(const float *__restrict__ in, float *__restrict__ out, int P, int B, int H, int W, int s, int A, int ipt,
+                                            int steps, int nbt, int64_t total)
+{
+    for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int t = static_cast<int>(i % steps);   // step fastest: a row's positions, coalesced reads
+        const int64_t q = i / steps;
+        const int c = static_cast<int>(q % P);
+        const int col = static_cast<int>(q / P), n = col & 31, li = n / A, j = n - li * A, b = (col >> 5) * ipt + li;
+        const int u = t - s * j;
+        float v = 0.f;
+        if (li < ipt && b < B && j < H && u >= 0) {
+            const int k = u / (A * s), x = u - k * (A * s), r = j + k * A;
+            if (r < H && x < W) v = in[(static_cast<int64_t>(b) * P + c) * H * W + r * W + x];
+        }
+        out[static_cast<int64_t>(t) * P * nbt + bm_prior(c, col, nbt)] = v;
+    }
+}
+
+// band schedule: the padding left and right of every row -- granules (slab s * r + x, row r) for x in [-pad, 0) and [W, W + pad), as far
+// as the slab exists and NO slot publishes the granule during the launch (x < 0: rows r >= A; x >= W: x >= A * s; see the band
+// section): { 0.0f, slab + 1 }, never a coded position (wavefront_pads_kernel writes the rows above the image)
+__global__ void band_edges_kernel(uint64_t *__restrict__ yT, int C, int B, int H, int W, int s, int A, int pad, int steps, int yw, int64_t total)
+{
+    for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int k = static_cast<int>(i % (2 * pad));
+        int64_t q = i / (2 * pad);
+        const int r = static_cast<int>(q % H);
+        q /= H;
+        const int b = static_cast<int>(q % B);
+        const int c = static_cast<int>(q / B);
+        const int x = k < pad ? k - pad : W + k - pad;
+        const int64_t slab = static_cast<int64_t>(s) * r + x;
+        if ((x < 0 ? r >= A : x >= A * s) && slab >= 0 && slab < steps) yT[slab * C * yw + bm_gran(c, b * (H + pad) + pad + r, yw)] = static_cast<uint64_t>(slab + 1) << 32;
     }
 }
 
@@ -1751,7 +1855,7 @@ namespace {
 size_t align4(size_t n) { return (n + 3) & ~static_cast<size_t>(3); }
 
 // which scan-line kernel a launch runs (kAuto: the one the launch fits best)
-enum class ScanKernel { kAuto, kGeneric, kPipelined, kBatched, kWavefront };
+enum class ScanKernel { kAuto, kGeneric, kPipelined, kBatched, kWavefront, kBand };
 
 // fills the launch arguments of the generic / pipelined kernels, shared by both directions; *lds_bytes = LDS of a compute
 // workgroup.  The pipelined kernel is taken when it fits, unless `force` names the generic one.
@@ -1901,15 +2005,95 @@ bool wavefront_auto(const basic_scanline_plan *p, int batch, int h, int w)
     return 2 * static_cast<int64_t>(wavefront_steps(p, h, w)) <= static_cast<int64_t>(h) * w;
 }
 
-// wf: the wavefront schedule's arguments (scratch: yT [steps][C][yw], priorT [steps][P][nbt])
-int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
-                      size_t *lds_bytes, hipStream_t st, bool wf = false)
+// ---- band encode schedule of the batched kernel (see the band section in front of it): an image owns band_slots() lanes of one
+// column tile whatever its height, so a launch of T tiles codes T * (32 / slots) images in the wavefront's W + s (H - 1) steps, and
+// a larger batch is coded by successive launches over whole images.
+// kBandMaxTiles: a launch may hold cus / b_nw tiles (8 on a 256-unit chip with BaSIC's layers); every tile is one more set of b_nw
+// resident workgroups that other streams' persistent launches queue behind (ScanChain).  Tiles share nothing but the memory side:
+// measured (profiles/scanline_band_probe.txt), a step costs 18.4 us with one tile, 19.7 with two, 21.0 with four, 23.2-25.7 with
+// eight, so halving the launches always won over the dearer step -- 64 / 96 images of 16x16: 8.99 / 12.03 ms at two tiles per
+// launch, 4.78 / 6.37 at four, 3.52 / 3.90 at eight; 16x32x48: 13.1 / 7.0 / 4.3 ms.  8 = the whole chip.
+constexpr int kBandMaxTiles = 8;
+constexpr size_t kBandMaxScratch = static_cast<size_t>(1) << 30;   // bytes of scratch one band launch may ask for
+
+int band_slots(const basic_scanline_plan *p, int w) { return w / wavefront_slope(p) + 1; }
+
+// floats of scratch of a batched-kernel launch: [granules: layer exchange arrays, coded latent, step means / rows][prior][late fragments]
+size_t batched_scratch_floats(const basic_scanline_plan *p, int nbt, int64_t slabs, int yw, size_t *gran_floats)
 {
+    size_t floats = 0;
+    for (int l = 0; l + 1 < p->nlayers; ++l) floats += align4(2 * static_cast<size_t>(nbt) * p->rows[l]);
+    floats += align4(2 * static_cast<size_t>(yw) * slabs * p->C);
+    floats += 2 * align4(2 * static_cast<size_t>(nbt) * p->C);
+    if (gran_floats) *gran_floats = floats;
+    floats += align4(static_cast<size_t>(nbt) * slabs * p->P);
+    floats += static_cast<size_t>(nbt / 32) * p->b_nw * kThreads * 32;
+    return floats;
+}
+
+// The images one band launch codes of an h x w latent: 0 = never (layers not of the batched kernel's shape, an image's slots do not
+// fit one column tile, no tile's workgroups fit the chip, or one image alone is too large).  Limited by the tiles of a launch, by
+// the scratch, and by the 32-bit element offsets the kernel computes: into y / sym / idx / ybuf of the launch's images
+// (images * C * H * W), into a slab of the coded latent and into a step's slab of the prior (bytes).
+int band_images_per_launch(const basic_scanline_plan *p, int h, int w, int cus)
+{
+    if (!p->batched || h < 1 || w < 1 || p->b_nw < 1) return 0;
+    const int A = band_slots(p, w);
+    if (A > 32) return 0;
+    const int ipt = 32 / A, tiles_max = std::min(kBandMaxTiles, cus / p->b_nw);
+    const int64_t steps = static_cast<int64_t>(w) + static_cast<int64_t>(wavefront_slope(p)) * (h - 1);
+    if (steps >= (1 << 30)) return 0;
+    for (int n = tiles_max * ipt; n >= 1; --n) {
+        const int tiles = (n + ipt - 1) / ipt;
+        const int64_t yw = static_cast<int64_t>(n) * (h + p->ksize / 2);
+        if (static_cast<int64_t>(n) * p->C * h * w >= (1ll << 31)) continue;
+        if (yw * p->C * 8 >= (1ll << 31) || static_cast<int64_t>(tiles) * 32 * std::max(p->P, 1) * 4 >= (1ll << 31)) continue;
+        if (batched_scratch_floats(p, 32 * tiles, steps, static_cast<int>(yw), nullptr) * sizeof(float) > kBandMaxScratch) continue;
+        return n;
+    }
+    return 0;
+}
+
+// The encode calls that take the band when nothing forces a choice and the wavefront does not fit.  Measured
+// (profiles/scanline_band_probe.txt): a band step costs 17.9-18.4 us with one tile in the launch, 19.1-19.8
+// with two, 20.1-21.0 with four, 23.2-25.7 with eight (more granules in flight through the same memory side); a raster step
+// 11.1 us (pipelined, one image) or 16.1-17.7 (batched); run-to-run spread at most 0.7 %.
+//   * One or two images (too tall for the wavefront): one tile, the wavefront's kernel step against the pipelined kernel's -- the
+//     wavefront's measured rule, at most half the raster steps (1x135x120: 656 steps against 16,200, x15.2).
+//   * Three images and more: the band is faster for certain while launches * steps * 25.7 <= H * W * 16.1 (its dearest step
+//     against the cheapest batched raster step), i.e. launches * steps <= 0.625 H * W: alone on the chip every measured call under
+//     that rule won by at least x1.29 (64x16x16: two launches, 152 steps against 256, 4.54 -> 3.52 ms; 3 / 8 / 16 x 32x48: x7.5 /
+//     x7.2 / x5.9).  Alone is not how the coder runs, though: bench.py --workload basic (64x16x16, six stream workers) LOST with the
+//     band, 183-190 -> 155-174 Mpix/s, three alternating runs each -- its first launch holds all 256 compute units for 1.8 ms
+//     where the raster launch holds 64 for 4.5, and the other workers' launches queue behind it (ScanChain).  So the band must
+//     also hold no more compute-unit time than the raster launch it replaces: tiles * steps summed over its launches, at 25.7 us,
+//     against the raster launch's tiles * H * W at 16.1.  That leaves 64x16x16 (11 tile-launches of 76 steps against 2 x 256) and
+//     16x32x48 (8 x 172 against 1,536) to raster and sends 3x32x48 and 8x32x48 to the band; whatever runs beside such a launch
+//     then gets the chip sooner and no smaller.
+// Batches that no raster kernel serves (more than 64 images) reach the library only when the coder has already chosen the band
+// over its per-step path (pgm_coder._scanline_plan).
+bool band_auto(const basic_scanline_plan *p, int batch, int h, int w, int per_launch)
+{
+    const int64_t launches = (batch + per_launch - 1) / per_launch, steps = wavefront_steps(p, h, w), hw = static_cast<int64_t>(h) * w;
+    if (batch <= 2) return 2 * launches * steps <= hw;
+    const int ipt = 32 / band_slots(p, w), last = batch - static_cast<int>(launches - 1) * per_launch;
+    const int64_t tiles = (launches - 1) * ((per_launch + ipt - 1) / ipt) + (last + ipt - 1) / ipt;   // column tiles over all launches
+    return 8 * launches * steps <= 5 * hw && 8 * tiles * steps <= 5 * hw * ((batch + 31) / 32);
+}
+
+// mode 0: raster; 1: the wavefront schedule's arguments (scratch: yT [steps][C][yw], priorT [steps][P][nbt]); 2: the band's (batch =
+// the images of this launch; first: the first launch of the call, which also clears the error flag)
+int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
+                      size_t *lds_bytes, hipStream_t st, int mode = 0, bool first = true)
+{
+    const bool wf = mode != 0, band = mode == 2;
     const int pad = p->ksize / 2, yw = batch * (h + pad);
     const int64_t HW = wf ? wavefront_steps(p, h, w) : static_cast<int64_t>(h) * w;   // slabs of the coded latent and of the prior
-    const int cols = wf ? batch * h : batch;
+    const int bA = band ? band_slots(p, w) : 0, ipt = band ? 32 / bA : 0;
+    const int cols = band ? 32 * ((batch + ipt - 1) / ipt) : wf ? batch * h : batch;
     const int tiles = (cols + 31) / 32, nbt = 32 * tiles;
     if (wf) { a.wf_cols = cols; a.wf_s = wavefront_slope(p); a.wf_steps = static_cast<int>(HW); a.wf_yw = yw; }
+    a.band_A = bA; a.band_ipt = ipt;
     a.B = batch; a.C = p->C; a.H = h; a.W = w; a.P = p->P;
     a.nlayers = p->nlayers; a.ntaps = p->ntaps; a.vec4 = p->vec4;
     a.table = d_table; a.table_len = table_len;
@@ -1952,11 +2136,21 @@ int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int
         hipLaunchKernelGGL(wavefront_pads_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, a.yT, p->C, batch, h, pad, yw, total);
         BASIC_HIP_TRY(hipGetLastError());
     }
+    if (band && pad > 0) {
+        const int64_t total = static_cast<int64_t>(p->C) * batch * h * 2 * pad;
+        int64_t g = (total + 255) / 256;
+        hipLaunchKernelGGL(band_edges_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, a.yT, p->C, batch, h, w, a.wf_s, bA, pad,
+                           a.wf_steps, yw, total);
+        BASIC_HIP_TRY(hipGetLastError());
+    }
     if (p->P > 0) {
         float *pT = p->d_scratch + pT_off;
         const int64_t total = static_cast<int64_t>(cols) * HW * p->P;
         int64_t g = (total + 255) / 256;
-        if (wf)
+        if (band)
+            hipLaunchKernelGGL(transpose_prior_band_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, d_prior, pT, p->P, batch, h, w,
+                               a.wf_s, bA, ipt, a.wf_steps, nbt, total);
+        else if (wf)
             hipLaunchKernelGGL(transpose_prior_wavefront_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, d_prior, pT, p->P, h, w,
                                a.wf_s, a.wf_steps, nbt, total);
         else
@@ -1970,7 +2164,7 @@ int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int
     *lds_bytes = (align4(table_len) + 4 + 96 + static_cast<size_t>(p->b_tiles) * kBTile) * sizeof(float);   // table, flags, biases, partial tiles
     a.bar = p->d_bar;
     a.err = reinterpret_cast<int *>(p->d_bar + 1);
-    BASIC_HIP_TRY(hipMemsetAsync(p->d_bar, 0, 2 * sizeof(unsigned), st));
+    if (first) BASIC_HIP_TRY(hipMemsetAsync(p->d_bar, 0, 2 * sizeof(unsigned), st));   // (a later launch of the call keeps an earlier one's error flag)
     return BASIC_OK;
 }
 
@@ -2038,11 +2232,12 @@ size_t decoder_lds_bytes(const RansFastView &tv)
 }
 
 struct ScanLaunch {
-    ScanKernel kernel;   // kGeneric, kPipelined, kBatched or kWavefront
+    ScanKernel kernel;   // kGeneric, kPipelined, kBatched, kWavefront or kBand
     int grid;            // compute workgroups, then the decoder workgroups
     int ncompute;
     int cus;
     size_t lds_bytes;
+    int band_images;     // kBand: images per launch (prepare_launch leaves the arguments to band_launches, one set per launch)
 };
 
 // The one place that decides how a scan-line call runs: which kernel (the batched one from 3 images on where it fits, else the
@@ -2051,6 +2246,8 @@ struct ScanLaunch {
 // Encode calls have a second schedule, the wavefront one of the batched kernel: forced by BASIC_SCAN_KERNEL=wavefront or by the
 // plan's encode schedule (the environment wins over the plan), taken in auto where wavefront_auto says so; the plan's raster
 // schedule is the choice above, whatever wavefront_auto says.  Decode calls ignore both.
+// And a third, the band (BASIC_SCAN_KERNEL=band, BASIC_SCAN_SCHEDULE_BAND): any batch and height, in as many launches as the
+// batch needs.  In auto it is looked at only where the wavefront does not fit, and taken where band_auto says so.
 int prepare_launch(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
                    const basic_rans_tables *tables, hipStream_t st, ScanLaunch *L)
 {
@@ -2060,10 +2257,12 @@ int prepare_launch(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w,
         else if (!strcmp(e, "pipelined")) force = ScanKernel::kPipelined;
         else if (!strcmp(e, "batched")) force = ScanKernel::kBatched;
         else if (!strcmp(e, "wavefront")) force = ScanKernel::kWavefront;
+        else if (!strcmp(e, "band")) force = ScanKernel::kBand;
     }
     const bool decode = tables != nullptr;
-    if (force == ScanKernel::kWavefront && decode) force = ScanKernel::kAuto;
+    if ((force == ScanKernel::kWavefront || force == ScanKernel::kBand) && decode) force = ScanKernel::kAuto;
     if (force == ScanKernel::kAuto && !decode && p->encode_schedule == BASIC_SCAN_SCHEDULE_WAVEFRONT) force = ScanKernel::kWavefront;
+    if (force == ScanKernel::kAuto && !decode && p->encode_schedule == BASIC_SCAN_SCHEDULE_BAND) force = ScanKernel::kBand;
     if (decode) {
         const int rc = rans_fast_view(tables, &a.tv);
         if (rc) return rc;
@@ -2075,9 +2274,18 @@ int prepare_launch(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w,
     if (force == ScanKernel::kBatched) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=batched, but this call does not fit the batched kernel");
     const bool wf_fits = !decode && wavefront_fits(p, batch, h, L->cus);
     if (force == ScanKernel::kWavefront) BASIC_REQUIRE(wf_fits, "scanline: the wavefront encode schedule was asked for, but this call does not fit it");
+    const int band_n = (!decode && (force == ScanKernel::kBand || (force == ScanKernel::kAuto && !wf_fits && p->encode_schedule == BASIC_SCAN_SCHEDULE_AUTO)))
+                           ? band_images_per_launch(p, h, w, L->cus) : 0;
+    if (force == ScanKernel::kBand) BASIC_REQUIRE(band_n >= 1, "scanline: the band encode schedule was asked for, but this call does not fit it");
+    if (force == ScanKernel::kBand || (band_n >= 1 && band_auto(p, batch, h, w, band_n))) {
+        L->kernel = ScanKernel::kBand;
+        L->band_images = band_n;
+        L->lds_bytes = 96 * 1024;
+        return BASIC_OK;
+    }
     if (force == ScanKernel::kWavefront ||
         (force == ScanKernel::kAuto && wf_fits && p->encode_schedule == BASIC_SCAN_SCHEDULE_AUTO && wavefront_auto(p, batch, h, w))) {
-        rc = fill_args_batched(p, a, batch, h, w, d_prior, d_table, table_len, &L->lds_bytes, st, true);
+        rc = fill_args_batched(p, a, batch, h, w, d_prior, d_table, table_len, &L->lds_bytes, st, 1);
         if (rc) return rc;
         L->kernel = ScanKernel::kWavefront;
         L->ncompute = (a.nbt / 32) * p->b_nw;   // wavefront_fits: the grid is resident
@@ -2105,7 +2313,8 @@ int prepare_launch(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w,
 
 template <bool DECODE> int run_launch(basic_scanline_plan *p, ScanArgs &a, const ScanLaunch &L, hipStream_t st)
 {
-    const void *fn = L.kernel == ScanKernel::kWavefront   ? reinterpret_cast<const void *>(scanline_batched_kernel<false, !DECODE>)
+    const void *fn = L.kernel == ScanKernel::kBand        ? reinterpret_cast<const void *>(scanline_batched_kernel<false, !DECODE, !DECODE>)
+                     : L.kernel == ScanKernel::kWavefront ? reinterpret_cast<const void *>(scanline_batched_kernel<false, !DECODE>)
                      : L.kernel == ScanKernel::kBatched   ? reinterpret_cast<const void *>(scanline_batched_kernel<DECODE>)
                      : L.kernel == ScanKernel::kPipelined ? reinterpret_cast<const void *>(scanline_pipelined_kernel<DECODE>)
                                                           : reinterpret_cast<const void *>(scanline_persistent_kernel<DECODE>);
@@ -2113,18 +2322,20 @@ template <bool DECODE> int run_launch(basic_scanline_plan *p, ScanArgs &a, const
     ScanProfile prof;
     int rc = prof.begin(a, st);
     if (rc) return rc;
-    BASIC_REQUIRE(!(DECODE && L.kernel == ScanKernel::kWavefront), "scanline: the wavefront schedule is encode only");
-    p->last_kernel = L.kernel == ScanKernel::kWavefront  ? BASIC_SCAN_KERNEL_WAVEFRONT
+    BASIC_REQUIRE(!(DECODE && (L.kernel == ScanKernel::kWavefront || L.kernel == ScanKernel::kBand)), "scanline: the wavefront and band schedules are encode only");
+    p->last_kernel = L.kernel == ScanKernel::kBand       ? BASIC_SCAN_KERNEL_BAND
+                     : L.kernel == ScanKernel::kWavefront ? BASIC_SCAN_KERNEL_WAVEFRONT
                      : L.kernel == ScanKernel::kBatched  ? BASIC_SCAN_KERNEL_BATCHED
                      : L.kernel == ScanKernel::kPipelined ? BASIC_SCAN_KERNEL_PIPELINED
                                                           : BASIC_SCAN_KERNEL_GENERIC;
     rc = chained_launch(p, st, L.grid, L.cus, [&] {
-        if (L.kernel == ScanKernel::kWavefront) hipLaunchKernelGGL((scanline_batched_kernel<false, !DECODE>), dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
+        if (L.kernel == ScanKernel::kBand) hipLaunchKernelGGL((scanline_batched_kernel<false, !DECODE, !DECODE>), dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
+        else if (L.kernel == ScanKernel::kWavefront) hipLaunchKernelGGL((scanline_batched_kernel<false, !DECODE>), dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
         else if (L.kernel == ScanKernel::kBatched) hipLaunchKernelGGL(scanline_batched_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
         else if (L.kernel == ScanKernel::kPipelined) hipLaunchKernelGGL(scanline_pipelined_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
         else hipLaunchKernelGGL(scanline_persistent_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
     });
-    prof.report(a, st, L.kernel == ScanKernel::kWavefront ? "encode (wavefront)" : L.kernel == ScanKernel::kBatched ? (DECODE ? "decode (batched)" : "encode (batched)") : (DECODE ? "decode" : "encode"));
+    prof.report(a, st, L.kernel == ScanKernel::kBand ? "encode (band)" : L.kernel == ScanKernel::kWavefront ? "encode (wavefront)" : L.kernel == ScanKernel::kBatched ? (DECODE ? "decode (batched)" : "encode (batched)") : (DECODE ? "decode" : "encode"));
     return rc;
 }
 
@@ -2142,6 +2353,24 @@ extern "C" int basic_scanline_encode_dev(basic_scanline_plan *p, const float *d_
     ScanLaunch L{};
     const int rc = prepare_launch(p, a, batch, h, w, d_prior, d_table, table_len, nullptr, st, &L);
     if (rc) return rc;
+    if (L.kernel == ScanKernel::kBand) {
+        // successive launches over whole images: one stream, one scratch (each launch clears and fills it in stream order)
+        const int64_t img_lat = static_cast<int64_t>(p->C) * h * w, img_prior = static_cast<int64_t>(p->P) * h * w;
+        for (int b0 = 0; b0 < batch; b0 += L.band_images) {
+            const int nb = std::min(L.band_images, batch - b0);
+            ScanArgs ab{};
+            int rcb = fill_args_batched(p, ab, nb, h, w, d_prior ? d_prior + b0 * img_prior : nullptr, d_table, table_len, &L.lds_bytes, st, 2, b0 == 0);
+            if (rcb) return rcb;
+            L.ncompute = (ab.nbt / 32) * p->b_nw;   // band_images_per_launch: the grid is resident
+            L.grid = ab.ncompute = L.ncompute;
+            if (L.lds_bytes < 96 * 1024) L.lds_bytes = 96 * 1024;   // (one workgroup per compute unit, as in prepare_launch)
+            BASIC_REQUIRE(L.lds_bytes <= 160 * 1024, "scanline: a workgroup's LDS does not fit");
+            ab.y = d_y + b0 * img_lat; ab.ybuf = d_ybuf + b0 * img_lat; ab.sym = d_symbols + b0 * img_lat; ab.idx = d_indexes + b0 * img_lat;
+            rcb = run_launch<false>(p, ab, L, st);
+            if (rcb) return rcb;
+        }
+        return BASIC_OK;
+    }
     a.y = d_y; a.ybuf = d_ybuf; a.sym = d_symbols; a.idx = d_indexes;
     return run_launch<false>(p, a, L, st);
 }
@@ -2209,6 +2438,21 @@ extern "C" int basic_scanline_wavefront_max(const basic_scanline_plan *p, int h,
     return BASIC_OK;
 }
 
+// The images ONE launch of the band encode schedule codes of an h x w latent on the current device; a larger batch takes several
+// launches inside one call.  0 = never: the layers do not have the batched kernel's shape, the latent is so wide that an image's
+// slots (w / (ksize / 2 + 2) + 1) exceed one 32-column tile, or a single image is too large for the scratch limit or for the
+// kernel's 32-bit offsets.
+extern "C" int basic_scanline_band_max(const basic_scanline_plan *p, int h, int w, int *images_per_launch)
+{
+    BASIC_REQUIRE(p && images_per_launch && h >= 1 && w >= 1, "scanline_band_max: bad argument");
+    *images_per_launch = 0;
+    int cus = 0;
+    int rc = device_cus(&cus);
+    if (rc) return rc;
+    *images_per_launch = band_images_per_launch(p, h, w, cus);
+    return BASIC_OK;
+}
+
 // Which kernel the plan's last launch (either direction) ran: BASIC_SCAN_KERNEL_*; NONE before the first launch.
 extern "C" int basic_scanline_last_kernel(const basic_scanline_plan *p, int *kernel)
 {
@@ -2219,7 +2463,8 @@ extern "C" int basic_scanline_last_kernel(const basic_scanline_plan *p, int *ker
 
 extern "C" int basic_scanline_set_encode_schedule(basic_scanline_plan *p, int schedule)
 {
-    BASIC_REQUIRE(p && (schedule == BASIC_SCAN_SCHEDULE_AUTO || schedule == BASIC_SCAN_SCHEDULE_RASTER || schedule == BASIC_SCAN_SCHEDULE_WAVEFRONT),
+    BASIC_REQUIRE(p && (schedule == BASIC_SCAN_SCHEDULE_AUTO || schedule == BASIC_SCAN_SCHEDULE_RASTER || schedule == BASIC_SCAN_SCHEDULE_WAVEFRONT ||
+                       schedule == BASIC_SCAN_SCHEDULE_BAND),
                   "scanline_set_encode_schedule: bad argument");
     p->encode_schedule = schedule;
     return BASIC_OK;

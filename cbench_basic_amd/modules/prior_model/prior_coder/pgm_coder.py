@@ -592,7 +592,9 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
     persistent_scanline_max_batch = 4
     # how the persistent ENCODE launch walks the latent: "raster" (one step per position), "wavefront" (the rows of an image in
     # parallel, each ksize // 2 + 2 columns behind the row above: W + s (H - 1) steps; batch * H <= 64; a call it does not fit
-    # raises) or "auto" (the library takes the wavefront where it fits and measured faster).  The integers are the same.
+    # raises), "band" (the wavefront's steps with an image's rows sharing W // s + 1 columns: any batch and height, a latent up to
+    # 31 s columns wide, as many launches as the batch needs; a call it does not fit raises) or "auto" (the library takes the
+    # wavefront where it fits and measured faster).  The integers are the same.
     scanline_encode_schedule = "auto"
 
     def _scanline_plan(self, plan, prior, batch=1, decode=False, width=None, height=None):
@@ -620,16 +622,39 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         if sl is None:
             return None
         schedule = self.scanline_encode_schedule
-        if batch > self.persistent_scanline_max_batch and (width is None or batch > sl.batched_max(width, decode)):
-            # no raster kernel serves this batch; an encode call may still run as a wavefront (a narrow latent, for one)
-            if decode or schedule == "raster" or width is None or height is None or batch > sl.wavefront_max(height, width):
+        if schedule == "band" and not decode and width is not None and height is not None and sl.band_max(height, width) >= 1:
+            if not sl.can_encode(batch):
                 return None
-            schedule = "wavefront"
+            sl.set_encode_schedule("band")   # any batch: the call is cut into launches over whole images
+            return sl
+        if batch > self.persistent_scanline_max_batch and (width is None or batch > sl.batched_max(width, decode)):
+            # no raster kernel serves this batch; an encode call may still run as a wavefront (a narrow latent, for one), or, in
+            # auto, as a band where that beats the per-step path
+            if decode or schedule == "raster" or width is None or height is None:
+                return None
+            if batch <= sl.wavefront_max(height, width):
+                schedule = "wavefront"
+            elif schedule == "auto" and self._band_beats_per_step(sl, batch, height, width):
+                schedule = "band"
+            else:
+                return None
         if not (sl.can_decode(self._tables, batch) if decode else sl.can_encode(batch)):
             return None
         if not decode:
             sl.set_encode_schedule(schedule)
         return sl
+
+    @staticmethod
+    def _band_beats_per_step(sl, batch, height, width):
+        """Auto, a batch no raster kernel serves: the band against the per-step path.  Measured (scripts/scanline_band_probe.py,
+        profiles/scanline_band_probe.txt): a band step costs at most 25.7 us (eight tiles in the launch), a step of the per-step
+        path 110 us at 96 images (and more with the batch), so the band wins while launches * steps <= 4.3 H W; 3 leaves a
+        margin (96x16x16: two launches, 152 steps against 256, 28.1 -> 3.9 ms)."""
+        per_launch = sl.band_max(height, width)
+        if per_launch < 1:
+            return False
+        steps = width + (sl.ksize // 2 + 2) * (height - 1)
+        return -(-batch // per_launch) * steps <= 3 * height * width
 
     def _run_encode(self, y, prior, pgm=None):
         self._ready()

@@ -461,8 +461,8 @@ class HyperpriorSession:
         return out
 
 
-SCAN_KERNELS = ("generic", "pipelined", "batched", "wavefront")   # BASIC_SCAN_KERNEL_*
-SCAN_SCHEDULES = ("auto", "raster", "wavefront")                  # BASIC_SCAN_SCHEDULE_*
+SCAN_KERNELS = ("generic", "pipelined", "batched", "wavefront", "band")   # BASIC_SCAN_KERNEL_*
+SCAN_SCHEDULES = ("auto", "raster", "wavefront", "band")                  # BASIC_SCAN_SCHEDULE_*
 
 
 def wavefront_schedule(h, w, ksize):
@@ -473,6 +473,32 @@ def wavefront_schedule(h, w, ksize):
     s = ksize // 2 + 2
     steps = w + s * (h - 1)
     return steps, [[t - s * r if 0 <= t - s * r < w else None for r in range(h)] for t in range(steps)]
+
+
+def band_schedule(h, w, ksize, tight=False):
+    """The band encode schedule of an h x w latent with a causal ksize x ksize window, as the kernel walks it (csrc/scanline.hip):
+    the wavefront's steps -- row r codes column c at step t = s * r + c, s = ksize // 2 + 2 -- but an image owns only min(A, h)
+    column slots; slot j codes rows j, j + A, j + 2 A, ... back to back with period A * s >= w.  At step t slot j has
+    u = t - s * j, (n, c) = divmod(u, A * s) and row r = j + n * A; it is active iff u >= 0, r < h and c < w.
+    A = w // s + 1 (what the kernel uses: every row is followed by an idle step of its slot), or with `tight` the smallest
+    A with A * s >= w.  -> (A, steps, table): steps = w + s * (h - 1); table[t][j] = (row, col, active) for j < min(A, h), with
+    row = col = None before the slot's first row (u < 0)."""
+    s = ksize // 2 + 2
+    A = -(-w // s) if tight else w // s + 1
+    steps = w + s * (h - 1)
+    table = []
+    for t in range(steps):
+        slots = []
+        for j in range(min(A, h)):
+            u = t - s * j
+            if u < 0:
+                slots.append((None, None, False))
+                continue
+            n, c = divmod(u, A * s)
+            r = j + n * A
+            slots.append((r, c, r < h and c < w))
+        table.append(slots)
+    return A, steps, table
 
 
 class ScanlinePlan:
@@ -547,15 +573,26 @@ class ScanlinePlan:
             cache[key] = m.value
         return cache[key]
 
+    def band_max(self, height, width):
+        """Images ONE launch of the band encode schedule codes of a `height` x `width` latent on this device; a larger batch takes
+        several launches inside one call, so any batch is served when this is >= 1 (0: never)."""
+        key = (int(height), int(width), torch.cuda.current_device())
+        cache = self.__dict__.setdefault("_band_max", {})
+        if key not in cache:
+            m = ctypes.c_int()
+            _lib.check(_lib.lib().basic_scanline_band_max(self._h, int(height), int(width), ctypes.byref(m)))
+            cache[key] = m.value
+        return cache[key]
+
     def last_kernel(self):
-        """The kernel the plan's last launch ran: "generic", "pipelined", "batched" or "wavefront"; None before the first."""
+        """The kernel the plan's last launch ran: "generic", "pipelined", "batched", "wavefront" or "band"; None before the first."""
         k = ctypes.c_int()
         _lib.check(_lib.lib().basic_scanline_last_kernel(self._h, ctypes.byref(k)))
         return SCAN_KERNELS[k.value] if 0 <= k.value < len(SCAN_KERNELS) else None
 
     def set_encode_schedule(self, schedule):
-        """How encode calls are scheduled from now on: "auto", "raster" (never the wavefront) or "wavefront" (always: a call
-        that does not fit it raises).  The coded integers do not depend on it."""
+        """How encode calls are scheduled from now on: "auto", "raster" (never the wavefront or the band), "wavefront" or "band"
+        (always: a call that does not fit it raises).  The coded integers do not depend on it."""
         if schedule not in SCAN_SCHEDULES:
             raise ValueError(f"encode schedule must be one of {SCAN_SCHEDULES}, not {schedule!r}")
         _lib.check(_lib.lib().basic_scanline_set_encode_schedule(self._h, SCAN_SCHEDULES.index(schedule)))

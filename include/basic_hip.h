@@ -389,21 +389,35 @@ int basic_scanline_batched_max(const basic_scanline_plan *p, int w, int decode, 
  * *max_batch = the largest batch the wavefront serves for an h x w latent on the current device; 0 = never (layers not of the
  * batched kernel's shape, h > 64, or a grid that is not resident).  Any width fits. */
 int basic_scanline_wavefront_max(const basic_scanline_plan *p, int h, int w, int *max_batch);
+/* A third encode schedule, the BAND, lifts the wavefront's B * H <= 64.  Row r of the wavefront is in flight only during steps
+ * [s r, s r + w), so an image needs about w / s columns of the MFMA tiles, not h: it owns A = w / s + 1 column SLOTS of one
+ * 32-column tile, slot j codes rows j, j + A, j + 2 A, ... back to back, and 32 / A images share a tile.  The steps stay
+ * w + s * (h - 1) whatever the batch and the height; a launch runs up to 8 independent tiles, and a batch larger than one launch
+ * holds is coded by successive launches over whole images inside the one basic_scanline_encode_dev call.  Same integers, same
+ * d_ybuf; encode only.
+ * *images_per_launch = the images one launch codes of an h x w latent on the current device; 0 = never (layers not of the
+ * batched kernel's shape, A > 32 -- a latent wider than 31 * s columns --, or one image alone exceeds the scratch limit or the
+ * kernel's 32-bit offsets).  Any batch fits when it is >= 1. */
+int basic_scanline_band_max(const basic_scanline_plan *p, int h, int w, int *images_per_launch);
 /* *kernel = which kernel the plan's last launch (encode or decode) ran. */
 #define BASIC_SCAN_KERNEL_NONE (-1) /* no launch yet */
 #define BASIC_SCAN_KERNEL_GENERIC 0
 #define BASIC_SCAN_KERNEL_PIPELINED 1
 #define BASIC_SCAN_KERNEL_BATCHED 2
 #define BASIC_SCAN_KERNEL_WAVEFRONT 3
+#define BASIC_SCAN_KERNEL_BAND 4
 int basic_scanline_last_kernel(const basic_scanline_plan *p, int *kernel);
 /* How the plan's encode calls are scheduled from now on.  AUTO (the default): the wavefront where it fits and measured
- * faster, else raster.  RASTER: the choice described at basic_scanline_batched_max, never the wavefront.  WAVEFRONT: always;
- * a call that does not fit it fails with BASIC_ERR_INVALID ("does not fit").  The environment variable
- * BASIC_SCAN_KERNEL = generic | pipelined | batched | wavefront, when set, wins over the plan's schedule; decode calls
- * ignore "wavefront" and the schedule. */
+ * faster; where it does not fit, the band where it measured faster and holds no more compute-unit time than the raster launch
+ * (DESIGN.md section 3); else raster.  RASTER: the choice described at
+ * basic_scanline_batched_max, never the wavefront or the band.  WAVEFRONT / BAND: always; a call that does not fit it fails
+ * with BASIC_ERR_INVALID ("does not fit").  The environment variable
+ * BASIC_SCAN_KERNEL = generic | pipelined | batched | wavefront | band, when set, wins over the plan's schedule; decode calls
+ * ignore "wavefront", "band" and the schedule. */
 #define BASIC_SCAN_SCHEDULE_AUTO 0
 #define BASIC_SCAN_SCHEDULE_RASTER 1
 #define BASIC_SCAN_SCHEDULE_WAVEFRONT 2
+#define BASIC_SCAN_SCHEDULE_BAND 3
 int basic_scanline_set_encode_schedule(basic_scanline_plan *p, int schedule);
 int basic_scanline_status(basic_scanline_plan *p, void *hip_stream, int *poisoned);
 void basic_scanline_plan_destroy(basic_scanline_plan *p);

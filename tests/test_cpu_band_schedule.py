@@ -1,0 +1,111 @@
+"""The band encode schedule of the scan-line coder (kernels.band_schedule, the arithmetic csrc/scanline.hip walks): the wavefront's
+steps -- row r codes column c at step t = s * r + c, s = ksize // 2 + 2 -- with an image's rows sharing A column slots, slot j
+coding rows j, j + A, ... back to back.  Checked on the CPU, for A = w // s + 1 (the kernel's) and for the tight A = ceil(w / s):
+every position is coded exactly once and at its wavefront step, the left neighbour is one step old and every other causal tap at
+least two, a slot never holds two rows at once, and every tap outside the image lands on a granule of the static pre-zero set
+(the k // 2 positions left and right of every row at their own steps' slabs, and the pad rows above the image), which no slot
+ever codes."""
+import os
+import re
+
+import pytest
+
+SHAPES = [(16, 16, 5), (32, 48, 5), (48, 32, 5), (1, 1, 5), (5, 1, 5), (3, 2, 5), (1, 6, 5), (64, 1, 5), (135, 120, 5), (100, 7, 5), (9, 4, 5),
+          (4, 3, 3), (12, 8, 3), (7, 9, 7)]
+CASES = [(h, w, k, tight) for h, w, k in SHAPES for tight in (False, True)]
+
+
+def _schedule(h, w, k, tight):
+    from cbench_basic_amd.nn.kernels import band_schedule
+    return band_schedule(h, w, k, tight=tight)
+
+
+def _taps(k):
+    half = k // 2
+    return [(dy, dx) for dy in range(-half, 1) for dx in range(-half, half + 1) if dy < 0 or dx < 0]
+
+
+def _coded(table):
+    """{(row, col): [steps at which some slot codes it]}"""
+    seen = {}
+    for t, slots in enumerate(table):
+        for r, c, active in slots:
+            if active:
+                seen.setdefault((r, c), []).append(t)
+    return seen
+
+
+def _pre_zero(h, w, k):
+    """(slab, row) granules written before the launch, beside the pad rows above the image (row < 0, every slab)"""
+    s, half = k // 2 + 2, k // 2
+    return {(s * r + c, r) for r in range(h) for c in list(range(-half, 0)) + list(range(w, w + half))}
+
+
+@pytest.mark.parametrize("h,w,k,tight", CASES)
+def test_slots_steps_and_every_position_once(h, w, k, tight):
+    A, steps, table = _schedule(h, w, k, tight)
+    s = k // 2 + 2
+    assert A == (-(-w // s) if tight else w // s + 1) and A * s >= w
+    assert steps == w + s * (h - 1) == len(table)
+    seen = _coded(table)
+    assert len(seen) == h * w
+    for (r, c), ts in seen.items():
+        assert 0 <= r < h and 0 <= c < w and ts == [s * r + c]
+    for slots in table:
+        assert len(slots) == min(A, h)
+        assert sum(1 for _, _, active in slots if active) <= A
+
+
+@pytest.mark.parametrize("h,w,k,tight", CASES)
+def test_a_slot_holds_one_row_at_a_time(h, w, k, tight):
+    A, steps, table = _schedule(h, w, k, tight)
+    s = k // 2 + 2
+    for j in range(min(A, h)):
+        spans = {}
+        for t in range(steps):
+            r, c, active = table[t][j]
+            if r is None:
+                assert t < s * j and not active
+                continue
+            assert r % A == j and 0 <= c < A * s
+            if active:
+                lo, hi = spans.get(r, (t, t))
+                spans[r] = (min(lo, t), max(hi, t))
+        rows = sorted(spans)
+        assert rows == list(range(j, h, A))
+        for r0, r1 in zip(rows, rows[1:]):
+            assert spans[r0][1] < spans[r1][0]            # the next row starts after the last position of this one
+            if not tight:
+                assert spans[r1][0] - spans[r0][1] >= 2   # ... and an idle step lies between them
+
+
+@pytest.mark.parametrize("h,w,k,tight", CASES)
+def test_tap_ages_and_out_of_image_taps(h, w, k, tight):
+    A, steps, table = _schedule(h, w, k, tight)
+    s, half = k // 2 + 2, k // 2
+    step_of = {pos: ts[0] for pos, ts in _coded(table).items()}
+    coded_granules = {(t, r) for (r, c), t in step_of.items()}
+    pre_zero = _pre_zero(h, w, k)
+    assert not (pre_zero & coded_granules)                # static zeros: never a coded position
+    for (r, c), t in step_of.items():
+        for dy, dx in _taps(k):
+            slab = t + dx + s * dy                        # the step whose slab the kernel reads for this tap, at row r + dy
+            age = t - slab
+            assert age == 1 if (dy, dx) == (0, -1) else age >= 2
+            nr, nc = r + dy, c + dx
+            if 0 <= nr < h and 0 <= nc < w:
+                assert step_of[nr, nc] == slab            # inside: that slab holds exactly the neighbour
+            elif slab < 0:
+                pass                                      # before the first step: the kernel skips the tap for every lane
+            elif nr < 0:
+                assert -nr <= half                        # a pad row above the image (zeros in every slab)
+            else:
+                assert slab < steps and (slab, nr) in pre_zero
+
+
+def test_header_declares_the_entry():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "include", "basic_hip.h")) as f:
+        header = f.read()
+    assert re.search(r"\bint\s+basic_scanline_band_max\s*\(", header)
+    assert re.search(r"#define\s+BASIC_SCAN_SCHEDULE_BAND\s+3\b", header) and re.search(r"#define\s+BASIC_SCAN_KERNEL_BAND\s+4\b", header)
