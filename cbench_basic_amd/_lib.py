@@ -89,6 +89,7 @@ _SIGNATURES = {
     "basic_scanline_band_max": (_I, [_P, _I, _I, _P]),
     "basic_scanline_last_kernel": (_I, [_P, _P]),
     "basic_scanline_set_encode_schedule": (_I, [_P, _I]),
+    "basic_scanline_choose": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "basic_scanline_status": (_I, [_P, _P, _P]),
     "basic_scanline_plan_destroy": (None, [_P]),
     "basic_mse_per_image_dev": (_I, [_P, _P, _I, _L, _P, _P]),

@@ -1854,26 +1854,81 @@ namespace {
 
 size_t align4(size_t n) { return (n + 3) & ~static_cast<size_t>(3); }
 
-// which scan-line kernel a launch runs (kAuto: the one the launch fits best)
-enum class ScanKernel { kAuto, kGeneric, kPipelined, kBatched, kWavefront, kBand };
+// ---- The persistent kernels: the one list of them, in the order the planner considers them; a row's index is its ScanKernel.
+enum class ScanKernel { kBand, kWavefront, kBatched, kPipelined, kGeneric, kNone };
+using ScanFn = void (*)(ScanArgs);
+struct ScanKernelRow {
+    int id;              // BASIC_SCAN_KERNEL_*: what basic_scanline_last_kernel and basic_scanline_choose report
+    const char *env;     // its spelling in the BASIC_SCAN_KERNEL environment variable
+    const char *label;   // ScanProfile
+    ScanFn fn;           // nullptr: the schedule is encode only
+};
+template <bool DECODE> constexpr ScanKernelRow kScanKernels[] = {
+    {BASIC_SCAN_KERNEL_BAND, "band", "encode (band)", DECODE ? nullptr : scanline_batched_kernel<false, true, true>},
+    {BASIC_SCAN_KERNEL_WAVEFRONT, "wavefront", "encode (wavefront)", DECODE ? nullptr : scanline_batched_kernel<false, true>},
+    {BASIC_SCAN_KERNEL_BATCHED, "batched", DECODE ? "decode (batched)" : "encode (batched)", scanline_batched_kernel<DECODE>},
+    {BASIC_SCAN_KERNEL_PIPELINED, "pipelined", DECODE ? "decode" : "encode", scanline_pipelined_kernel<DECODE>},
+    {BASIC_SCAN_KERNEL_GENERIC, "generic", DECODE ? "decode" : "encode", scanline_persistent_kernel<DECODE>},
+};
+constexpr int scan_kernel_id(ScanKernel k) { return kScanKernels<false>[static_cast<int>(k)].id; }
+static_assert(sizeof(kScanKernels<false>) / sizeof(ScanKernelRow) == static_cast<int>(ScanKernel::kNone) &&
+                  scan_kernel_id(ScanKernel::kBand) == BASIC_SCAN_KERNEL_BAND && scan_kernel_id(ScanKernel::kWavefront) == BASIC_SCAN_KERNEL_WAVEFRONT &&
+                  scan_kernel_id(ScanKernel::kBatched) == BASIC_SCAN_KERNEL_BATCHED && scan_kernel_id(ScanKernel::kPipelined) == BASIC_SCAN_KERNEL_PIPELINED &&
+                  scan_kernel_id(ScanKernel::kGeneric) == BASIC_SCAN_KERNEL_GENERIC,
+              "kScanKernels: one row per ScanKernel, in its order, with the id include/basic_hip.h gives it");
+const ScanKernelRow &row_of(ScanKernel k, bool decode = false) { return (decode ? kScanKernels<true> : kScanKernels<false>)[static_cast<int>(k)]; }
 
-// fills the launch arguments of the generic / pipelined kernels, shared by both directions; *lds_bytes = LDS of a compute
-// workgroup.  The pipelined kernel is taken when it fits, unless `force` names the generic one.
-int fill_args(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
-              ScanKernel force, size_t *lds_bytes, bool *pipelined, hipStream_t st)
+// BASIC_SCAN_KERNEL = generic | pipelined | batched | wavefront | band forces a kernel (identical results); anything else: kNone
+ScanKernel forced_kernel()
 {
-    const int64_t HW = static_cast<int64_t>(h) * w;
-    a.B = batch; a.C = p->C; a.H = h; a.W = w; a.P = p->P;
-    a.nlayers = p->nlayers; a.ntaps = p->ntaps; a.vec4 = p->vec4;
-    a.table = d_table; a.table_len = table_len;
-    // scratch: [granule regions: layer exchange buffers, position-major coded latent, step means / rows][position-major prior]
+    if (const char *e = getenv("BASIC_SCAN_KERNEL"))
+        for (int k = 0; k < static_cast<int>(ScanKernel::kNone); ++k)
+            if (!strcmp(e, kScanKernels<false>[k].env)) return static_cast<ScanKernel>(k);
+    return ScanKernel::kNone;
+}
+
+constexpr size_t kMaxLds = 160 * 1024;
+// more than half of a compute unit's LDS per workgroup: exactly one workgroup per unit, as the barrier protocol assumes
+constexpr size_t kMinLds = 96 * 1024;
+
+// ---- The scratch of a launch, in floats from basic_scanline_plan::d_scratch:
+// [granule regions: layer exchange arrays, coded latent, step means / rows][position-major prior][late fragments]
+struct ScanScratch {
+    size_t act[kMaxLayers] = {};            // layer exchange arrays (the first `nact` layers)
+    size_t yT = 0, mu = 0, idx_step = 0;    // coded latent, step means, step rows
+    size_t gran_end = 0;                    // the granule regions end here: cleared before every launch (tag 0 = "not written in this launch")
+    size_t prior = 0, wlate = 0, total = 0;
+};
+
+// `cols` columns (images, or MFMA columns) of exchange / step / prior data, a coded latent of `ycols` columns, both in `slabs` steps
+ScanScratch scratch_layout(const basic_scanline_plan *p, int nact, size_t cols, size_t ycols, int64_t slabs, size_t late_floats)
+{
+    ScanScratch s;
     size_t floats = 0;
-    for (int l = 0; l < p->nlayers; ++l) floats += align4(2 * static_cast<size_t>(batch) * p->rows[l]);
-    const size_t yT_off = floats;     floats += align4(2 * static_cast<size_t>(batch) * HW * p->C);
-    const size_t mu_off = floats;     floats += align4(2 * static_cast<size_t>(batch) * p->C);
-    const size_t is_off = floats;     floats += align4(2 * static_cast<size_t>(batch) * p->C);
-    const size_t gran_floats = floats;
-    const size_t pT_off = floats;     floats += align4(static_cast<size_t>(batch) * HW * p->P);
+    for (int l = 0; l < nact; ++l) { s.act[l] = floats; floats += align4(2 * cols * p->rows[l]); }
+    s.yT = floats;       floats += align4(2 * ycols * slabs * p->C);
+    s.mu = floats;       floats += align4(2 * cols * p->C);
+    s.idx_step = floats; floats += align4(2 * cols * p->C);
+    s.gran_end = floats;
+    s.prior = floats;    floats += align4(cols * slabs * p->P);
+    s.wlate = floats;    floats += late_floats;
+    s.total = floats;
+    return s;
+}
+
+// lane kernels (generic / pipelined): every layer exchanges [batch][rows], coded latent [HW][batch][C], prior [batch][HW][P]
+ScanScratch lane_scratch(const basic_scanline_plan *p, int batch, int64_t hw) { return scratch_layout(p, p->nlayers, batch, batch, hw, 0); }
+
+// batched family: exchange arrays [rows][nbt] of all layers but the last, coded latent [slabs][C][nbt] (raster) or [slabs][C][yw]
+// (wavefront, band), step means / rows [nbt][C], prior [slabs][P][nbt], late fragments per workgroup
+ScanScratch batched_scratch(const basic_scanline_plan *p, int nbt, int64_t slabs, int yw, ScanKernel mode)
+{
+    return scratch_layout(p, p->nlayers - 1, nbt, mode == ScanKernel::kBatched ? nbt : yw, slabs, static_cast<size_t>(nbt / 32) * p->b_nw * kThreads * 32);
+}
+
+// grows the plan's scratch to `floats` and clears its granule regions
+int ensure_scratch(basic_scanline_plan *p, size_t floats, size_t gran_floats, hipStream_t st)
+{
     if (floats > p->scratch_cap) {
         if (p->d_scratch) (void)hipFree(p->d_scratch);
         p->d_scratch = nullptr; p->scratch_cap = 0;
@@ -1881,95 +1936,89 @@ int fill_args(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, cons
         p->scratch_cap = floats;
     }
     BASIC_HIP_TRY(hipMemsetAsync(p->d_scratch, 0, gran_floats * sizeof(float), st));   // tag 0 = "not written in this launch"
-    size_t ao = 0;
-    int kmax = 0;
-    for (int l = 0; l < p->nlayers; ++l) {
-        a.rows[l] = p->rows[l]; a.kdim[l] = p->kdim[l]; a.rpw[l] = p->rpw[l]; a.woff[l] = p->woff[l]; a.act_after[l] = p->act_after[l];
-        a.kgroup[l] = p->kgroup[l]; a.bpg[l] = p->bpg[l]; a.kpad[l] = p->kpad[l];
-        a.w[l] = p->d_w[l]; a.bias[l] = p->d_b[l];
-        a.act[l] = reinterpret_cast<uint64_t *>(p->d_scratch + ao);
-        ao += align4(2 * static_cast<size_t>(batch) * p->rows[l]);
-        kmax = p->kdim[l] > kmax ? p->kdim[l] : kmax;
-    }
-    a.yT = reinterpret_cast<uint64_t *>(p->d_scratch + yT_off);
-    a.mu = reinterpret_cast<uint64_t *>(p->d_scratch + mu_off);
-    a.idx_step = reinterpret_cast<uint64_t *>(p->d_scratch + is_off);
-    a.priorT = nullptr;
-    if (p->P > 0) {
-        float *pT = p->d_scratch + pT_off;
-        const int64_t total = static_cast<int64_t>(batch) * HW * p->P;
-        int64_t g = (total + 255) / 256;
-        hipLaunchKernelGGL(transpose_prior_kernel, dim3(static_cast<unsigned>(g > 4096 ? 4096 : g)), dim3(256), 0, st, d_prior, pT, p->P,
-                           static_cast<int>(HW), total);
-        BASIC_HIP_TRY(hipGetLastError());
-        a.priorT = pT;
-    }
-    for (int t = 0; t < p->ntaps; ++t) { a.tap_dy[t] = p->tap_dy[t]; a.tap_dx[t] = p->tap_dx[t]; a.tap_off[t] = p->tap_dy[t] * w + p->tap_dx[t]; }
-    // LDS: [weights][table][params of a chunk][inputs of a chunk][flag]; as many images per chunk as fit (at most 8)
-    const int total_floats = 160 * 1024 / 4 - 16;
-    a.tab_off = static_cast<int>(align4(p->weight_floats));
-    a.ps_off = a.tab_off + static_cast<int>(align4(table_len));
-    const int rpw_last = p->rpw[p->nlayers - 1];
-    int bc = 8 < batch ? 8 : batch;
-    // one round of block partials: [blocks][items]; 1024 floats hold a batch-1 layer in one round (<= 36 blocks x ~10 rows)
-    a.part_floats = 1024;
-    for (int l = 0; l < p->nlayers; ++l)
-        BASIC_REQUIRE((p->kdim[l] / p->kgroup[l]) * p->bpg[l] <= a.part_floats, "scanline: too many summation blocks in a layer");
-    int bias_need = 0;
-    for (int l = 0; l < p->nlayers; ++l) bias_need += p->rpw[l];
-    auto need = [&](int n) { return a.ps_off + static_cast<int>(align4(n * rpw_last)) + static_cast<int>(align4(n * kmax)) + a.part_floats + 4 + static_cast<int>(align4(bias_need)); };
-    while (bc > 1 && need(bc) > total_floats) --bc;
-    BASIC_REQUIRE(need(bc) <= total_floats, "scanline: layer inputs do not fit the LDS");
-    a.bc = bc;
-    a.xs_off = a.ps_off + static_cast<int>(align4(bc * rpw_last));
-    a.part_off = a.xs_off + static_cast<int>(align4(bc * kmax));
-    a.flag_off = a.part_off + a.part_floats;
-    a.bias_off = a.flag_off + 4;
-    int bias_floats = 0;
-    for (int l = 0; l < p->nlayers; ++l) bias_floats += p->rpw[l];
-    *lds_bytes = static_cast<size_t>(a.bias_off + static_cast<int>(align4(bias_floats))) * sizeof(float);
-    // pipelined kernel: [weights][table][biases][context window B x K0][dense inputs B x Kd][partials][early sums][unit descriptors][flag]
-    // -- taken when all of it fits (results are identical either way)
-    {
-        int kd = 0, units_total = 0, units_max = 0;
-        for (int l = 0; l < p->nlayers; ++l) {
-            if (l > 0) kd = p->kdim[l] > kd ? p->kdim[l] : kd;
-            const int u = batch * p->rpw[l] * (p->kdim[l] / p->kgroup[l]) * p->bpg[l];
-            units_total += u;
-            units_max = u > units_max ? u : units_max;
-        }
-        const size_t bias_off = align4(static_cast<size_t>(a.tab_off) + table_len);
-        const size_t x0_off = bias_off + align4(bias_need);
-        const size_t xs_off = x0_off + align4(static_cast<size_t>(batch) * p->kdim[0]);
-        const size_t part_off = xs_off + align4(static_cast<size_t>(batch) * kd);
-        const size_t early_off = part_off + align4(units_max);
-        const size_t desc_off = early_off + align4(static_cast<size_t>(batch) * p->rpw[0]) +
-                                align4(static_cast<size_t>(batch) * p->rpw[0] * (p->kdim[0] / p->kgroup[0]) * p->bpg[0]);   // early sums + the early blocks' partials
-        const size_t flag_off = desc_off + align4(2 * static_cast<size_t>(units_total));
-        // (the early half of a position's context window must be coded two steps before it: the tap up and to the right by
-        // ksize / 2 columns is w - ksize / 2 positions back, so the latent must be at least ksize / 2 + 2 columns wide)
-        bool fits = flag_off + 4 <= static_cast<size_t>(total_floats) && p->vec4 && (p->ntaps - 1) * (p->C / 2) <= kWinU * kThreads &&
-                    w >= p->ksize / 2 + 2;
-        for (int l = 0; l < p->nlayers; ++l) fits = fits && batch * p->rpw[l] <= kThreads;   // one finishing item per thread
-        if (force == ScanKernel::kGeneric) fits = false;
-        if (force == ScanKernel::kPipelined) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=pipelined, but this batch does not fit the LDS");
-        *pipelined = fits;
-        if (fits) {
-            a.bias_off = static_cast<int>(bias_off); a.x0_off = static_cast<int>(x0_off); a.xs_off = static_cast<int>(xs_off);
-            a.part_off = static_cast<int>(part_off); a.early_off = static_cast<int>(early_off); a.desc_off = static_cast<int>(desc_off);
-            a.flag_off = static_cast<int>(flag_off);
-            a.bc = batch;
-            *lds_bytes = (flag_off + 4) * sizeof(float);
-        }
-    }
-    a.bar = p->d_bar;
-    a.err = reinterpret_cast<int *>(p->d_bar + 1);
-    BASIC_HIP_TRY(hipMemsetAsync(p->d_bar, 0, 2 * sizeof(unsigned), st));
     return BASIC_OK;
 }
 
-// ---- batched kernel: when it serves a call, and its launch arguments
+// ---- LDS of a compute workgroup of the lane kernels, and which of the two serves the call
+struct ScanLaneLds {
+    int tab_off = 0, ps_off = 0, xs_off = 0, part_off = 0, flag_off = 0, bias_off = 0, x0_off = 0, early_off = 0, desc_off = 0;
+    int bc = 0, part_floats = 0;
+    bool pipelined = false;
+    size_t lds_bytes = 0;
+};
+
+// The pipelined kernel is taken when it fits, unless `force` names the generic one.
+int lane_lds(const basic_scanline_plan *p, int batch, int w, int table_len, ScanKernel force, ScanLaneLds *o)
+{
+    int kmax = 0;
+    for (int l = 0; l < p->nlayers; ++l) kmax = p->kdim[l] > kmax ? p->kdim[l] : kmax;
+    // LDS: [weights][table][params of a chunk][inputs of a chunk][flag]; as many images per chunk as fit (at most 8)
+    const int total_floats = kMaxLds / 4 - 16;
+    o->tab_off = static_cast<int>(align4(p->weight_floats));
+    o->ps_off = o->tab_off + static_cast<int>(align4(table_len));
+    const int rpw_last = p->rpw[p->nlayers - 1];
+    int bc = 8 < batch ? 8 : batch;
+    // one round of block partials: [blocks][items]; 1024 floats hold a batch-1 layer in one round (<= 36 blocks x ~10 rows)
+    o->part_floats = 1024;
+    for (int l = 0; l < p->nlayers; ++l)
+        BASIC_REQUIRE((p->kdim[l] / p->kgroup[l]) * p->bpg[l] <= o->part_floats, "scanline: too many summation blocks in a layer");
+    int bias_need = 0;
+    for (int l = 0; l < p->nlayers; ++l) bias_need += p->rpw[l];
+    auto need = [&](int n) { return o->ps_off + static_cast<int>(align4(n * rpw_last)) + static_cast<int>(align4(n * kmax)) + o->part_floats + 4 + static_cast<int>(align4(bias_need)); };
+    while (bc > 1 && need(bc) > total_floats) --bc;
+    BASIC_REQUIRE(need(bc) <= total_floats, "scanline: layer inputs do not fit the LDS");
+    o->bc = bc;
+    o->xs_off = o->ps_off + static_cast<int>(align4(bc * rpw_last));
+    o->part_off = o->xs_off + static_cast<int>(align4(bc * kmax));
+    o->flag_off = o->part_off + o->part_floats;
+    o->bias_off = o->flag_off + 4;
+    o->lds_bytes = static_cast<size_t>(o->bias_off + static_cast<int>(align4(bias_need))) * sizeof(float);
+    // pipelined kernel: [weights][table][biases][context window B x K0][dense inputs B x Kd][partials][early sums][unit descriptors][flag]
+    // -- taken when all of it fits (results are identical either way)
+    int kd = 0, units_total = 0, units_max = 0;
+    for (int l = 0; l < p->nlayers; ++l) {
+        if (l > 0) kd = p->kdim[l] > kd ? p->kdim[l] : kd;
+        const int u = batch * p->rpw[l] * (p->kdim[l] / p->kgroup[l]) * p->bpg[l];
+        units_total += u;
+        units_max = u > units_max ? u : units_max;
+    }
+    const size_t bias_off = align4(static_cast<size_t>(o->tab_off) + table_len);
+    const size_t x0_off = bias_off + align4(bias_need);
+    const size_t xs_off = x0_off + align4(static_cast<size_t>(batch) * p->kdim[0]);
+    const size_t part_off = xs_off + align4(static_cast<size_t>(batch) * kd);
+    const size_t early_off = part_off + align4(units_max);
+    const size_t desc_off = early_off + align4(static_cast<size_t>(batch) * p->rpw[0]) +
+                            align4(static_cast<size_t>(batch) * p->rpw[0] * (p->kdim[0] / p->kgroup[0]) * p->bpg[0]);   // early sums + the early blocks' partials
+    const size_t flag_off = desc_off + align4(2 * static_cast<size_t>(units_total));
+    // (the early half of a position's context window must be coded two steps before it: the tap up and to the right by
+    // ksize / 2 columns is w - ksize / 2 positions back, so the latent must be at least ksize / 2 + 2 columns wide)
+    bool fits = flag_off + 4 <= static_cast<size_t>(total_floats) && p->vec4 && (p->ntaps - 1) * (p->C / 2) <= kWinU * kThreads &&
+                w >= p->ksize / 2 + 2;
+    for (int l = 0; l < p->nlayers; ++l) fits = fits && batch * p->rpw[l] <= kThreads;   // one finishing item per thread
+    if (force == ScanKernel::kGeneric) fits = false;
+    if (force == ScanKernel::kPipelined) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=pipelined, but this batch does not fit the LDS");
+    o->pipelined = fits;
+    if (fits) {
+        o->bias_off = static_cast<int>(bias_off); o->x0_off = static_cast<int>(x0_off); o->xs_off = static_cast<int>(xs_off);
+        o->part_off = static_cast<int>(part_off); o->early_off = static_cast<int>(early_off); o->desc_off = static_cast<int>(desc_off);
+        o->flag_off = static_cast<int>(flag_off);
+        o->bc = batch;
+        o->lds_bytes = (flag_off + 4) * sizeof(float);
+    }
+    return BASIC_OK;
+}
+
+// ---- batched kernel: when it serves a call
 constexpr int kBatchedMaxTiles = 2;   // column tiles of 32 images per launch
+
+// decoder workgroups of `batch` image streams (one wavefront per stream)
+int decoder_workgroups(int batch) { return (batch + kThreads / 64 - 1) / (kThreads / 64); }
+
+// LDS of a decoder workgroup: the fast search image of the table set
+size_t decoder_lds_bytes(const RansFastView &tv)
+{
+    return (static_cast<size_t>((tv.image_words + 3) & ~3) + 4 * static_cast<size_t>(tv.rows) + 4) * sizeof(uint32_t);
+}
 
 // whether the batched kernel can serve `batch` images of a latent `w` columns wide (the context window's early half must be coded
 // two steps before it is used: w >= ksize / 2 + 2); grid = column tiles x workgroups per tile (+ decoder workgroups)
@@ -1980,12 +2029,20 @@ bool batched_fits(const basic_scanline_plan *p, int batch, int w, int ndec, int 
     return tiles * p->b_nw + ndec <= cus;
 }
 
+// basic_scanline_batched_max: the largest whole number of column tiles that fits, in images
+int batched_max_batch(const basic_scanline_plan *p, int w, bool decode, int cus)
+{
+    for (int b = 32 * kBatchedMaxTiles; b >= 1; b -= 32)
+        if (batched_fits(p, b, w, decode ? decoder_workgroups(b) : 0, cus)) return b;
+    return 0;
+}
+
 // ---- wavefront encode schedule of the batched kernel: a column is one row of one image, so batch * h columns in at most
 // kBatchedMaxTiles tiles; a row starts ksize / 2 + 2 steps after the row above it, which leaves the left neighbour as the only
 // tap coded one step ago (the late half), every other one at least two (the early half).  No lower bound on the width: the
 // zero padding left and right of a row is what its idle column publishes.
 int wavefront_slope(const basic_scanline_plan *p) { return p->ksize / 2 + 2; }
-int wavefront_steps(const basic_scanline_plan *p, int h, int w) { return w + wavefront_slope(p) * (h - 1); }
+int64_t wavefront_steps(const basic_scanline_plan *p, int h, int w) { return w + static_cast<int64_t>(wavefront_slope(p)) * (h - 1); }
 
 bool wavefront_fits(const basic_scanline_plan *p, int batch, int h, int cus)
 {
@@ -2002,7 +2059,7 @@ bool wavefront_fits(const basic_scanline_plan *p, int batch, int h, int cus)
 bool wavefront_auto(const basic_scanline_plan *p, int batch, int h, int w)
 {
     (void)batch;
-    return 2 * static_cast<int64_t>(wavefront_steps(p, h, w)) <= static_cast<int64_t>(h) * w;
+    return 2 * wavefront_steps(p, h, w) <= static_cast<int64_t>(h) * w;
 }
 
 // ---- band encode schedule of the batched kernel (see the band section in front of it): an image owns band_slots() lanes of one
@@ -2018,17 +2075,13 @@ constexpr size_t kBandMaxScratch = static_cast<size_t>(1) << 30;   // bytes of s
 
 int band_slots(const basic_scanline_plan *p, int w) { return w / wavefront_slope(p) + 1; }
 
-// floats of scratch of a batched-kernel launch: [granules: layer exchange arrays, coded latent, step means / rows][prior][late fragments]
-size_t batched_scratch_floats(const basic_scanline_plan *p, int nbt, int64_t slabs, int yw, size_t *gran_floats)
+// MFMA columns of a launch of the batched family that codes `images` images
+int batched_columns(const basic_scanline_plan *p, ScanKernel mode, int images, int h, int w)
 {
-    size_t floats = 0;
-    for (int l = 0; l + 1 < p->nlayers; ++l) floats += align4(2 * static_cast<size_t>(nbt) * p->rows[l]);
-    floats += align4(2 * static_cast<size_t>(yw) * slabs * p->C);
-    floats += 2 * align4(2 * static_cast<size_t>(nbt) * p->C);
-    if (gran_floats) *gran_floats = floats;
-    floats += align4(static_cast<size_t>(nbt) * slabs * p->P);
-    floats += static_cast<size_t>(nbt / 32) * p->b_nw * kThreads * 32;
-    return floats;
+    if (mode == ScanKernel::kBatched) return images;
+    if (mode == ScanKernel::kWavefront) return images * h;
+    const int ipt = 32 / band_slots(p, w);
+    return 32 * ((images + ipt - 1) / ipt);
 }
 
 // The images one band launch codes of an h x w latent: 0 = never (layers not of the batched kernel's shape, an image's slots do not
@@ -2041,14 +2094,14 @@ int band_images_per_launch(const basic_scanline_plan *p, int h, int w, int cus)
     const int A = band_slots(p, w);
     if (A > 32) return 0;
     const int ipt = 32 / A, tiles_max = std::min(kBandMaxTiles, cus / p->b_nw);
-    const int64_t steps = static_cast<int64_t>(w) + static_cast<int64_t>(wavefront_slope(p)) * (h - 1);
+    const int64_t steps = wavefront_steps(p, h, w);
     if (steps >= (1 << 30)) return 0;
     for (int n = tiles_max * ipt; n >= 1; --n) {
         const int tiles = (n + ipt - 1) / ipt;
         const int64_t yw = static_cast<int64_t>(n) * (h + p->ksize / 2);
         if (static_cast<int64_t>(n) * p->C * h * w >= (1ll << 31)) continue;
         if (yw * p->C * 8 >= (1ll << 31) || static_cast<int64_t>(tiles) * 32 * std::max(p->P, 1) * 4 >= (1ll << 31)) continue;
-        if (batched_scratch_floats(p, 32 * tiles, steps, static_cast<int>(yw), nullptr) * sizeof(float) > kBandMaxScratch) continue;
+        if (batched_scratch(p, 32 * tiles, steps, static_cast<int>(yw), ScanKernel::kBand).total * sizeof(float) > kBandMaxScratch) continue;
         return n;
     }
     return 0;
@@ -2070,8 +2123,8 @@ int band_images_per_launch(const basic_scanline_plan *p, int h, int w, int cus)
 //     against the raster launch's tiles * H * W at 16.1.  That leaves 64x16x16 (11 tile-launches of 76 steps against 2 x 256) and
 //     16x32x48 (8 x 172 against 1,536) to raster and sends 3x32x48 and 8x32x48 to the band; whatever runs beside such a launch
 //     then gets the chip sooner and no smaller.
-// Batches that no raster kernel serves (more than 64 images) reach the library only when the coder has already chosen the band
-// over its per-step path (pgm_coder._scanline_plan).
+// Batches that no raster kernel serves (more than 64 images) come here only when the coder's gate has already chosen the band over
+// its per-step path (band_beats_per_step).
 bool band_auto(const basic_scanline_plan *p, int batch, int h, int w, int per_launch)
 {
     const int64_t launches = (batch + per_launch - 1) / per_launch, steps = wavefront_steps(p, h, w), hw = static_cast<int64_t>(h) * w;
@@ -2081,70 +2134,212 @@ bool band_auto(const basic_scanline_plan *p, int batch, int h, int w, int per_la
     return 8 * launches * steps <= 5 * hw && 8 * tiles * steps <= 5 * hw * ((batch + 31) / 32);
 }
 
-// mode 0: raster; 1: the wavefront schedule's arguments (scratch: yT [steps][C][yw], priorT [steps][P][nbt]); 2: the band's (batch =
-// the images of this launch; first: the first launch of the call, which also clears the error flag)
-int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
-                      size_t *lds_bytes, hipStream_t st, int mode = 0, bool first = true)
+// Auto, a batch no raster kernel serves: the band against the coder's per-step path.  Measured (scripts/scanline_band_probe.py,
+// profiles/scanline_band_probe.txt): a band step costs at most 25.7 us (eight tiles in the launch), a step of the per-step
+// path 110 us at 96 images (and more with the batch), so the band wins while launches * steps <= 4.3 H W; 3 leaves a
+// margin (96x16x16: two launches, 152 steps against 256, 28.1 -> 3.9 ms).
+bool band_beats_per_step(const basic_scanline_plan *p, int batch, int h, int w, int per_launch)
 {
-    const bool wf = mode != 0, band = mode == 2;
+    if (per_launch < 1) return false;
+    const int64_t launches = (batch + per_launch - 1) / per_launch;
+    return launches * wavefront_steps(p, h, w) <= 3 * static_cast<int64_t>(h) * w;
+}
+
+// (kept as it is: the coder's residency gate counts the generic kernel's workgroups whichever kernel will run)
+bool lane_grid_resident(const basic_scanline_plan *p, int ndec, int cus) { return p->nwg + ndec <= cus; }
+
+// ---- The planner: the one place that decides how a scan-line call runs.  Pure: it asks nothing of the device or the environment.
+struct ScanRequest {
+    int batch = 1, h = 0, w = 0;     // h or w < 1: not known -- no kernel of the batched family is considered then
+    int table_len = 1;
+    bool decode = false;
+    bool fast_image = false;         // decode: the table set has a fast search image ...
+    size_t decoder_lds = 0;          // ... of this many LDS bytes per decoder workgroup
+    int cus = 0;                     // compute units of the device
+    int schedule = BASIC_SCAN_SCHEDULE_AUTO;     // the requested encode schedule
+    ScanKernel force = ScanKernel::kNone;        // BASIC_SCAN_KERNEL, parsed: wins over the schedule
+    // the coder's gates (pgm_coder: persistent_scanline_max_batch): batches up to this one may take the lane kernels, and a call
+    // that no persistent kernel should serve is left to the per-step path.  < 0: a library call, which is served or refused.
+    int lane_max_batch = -1;
+};
+
+struct ScanLaunch {
+    ScanKernel kernel = ScanKernel::kNone;   // kNone: leave the call to the per-step path
+    int launches = 0, images = 0;            // `launches` launches over `images` whole images each (the last one: what is left)
+    int grid = 0;                            // workgroups of a launch of `images` images: compute, then the decoder's
+    size_t lds_bytes = 0;
+    ScanLaneLds lane;                        // kGeneric, kPipelined: the LDS layout
+    int cus = 0;
+};
+
+// compute workgroups of one launch over `images` images (resident: *_fits, band_images_per_launch and the lane check say so)
+int compute_workgroups(const basic_scanline_plan *p, ScanKernel k, int images, int h, int w)
+{
+    if (k == ScanKernel::kGeneric || k == ScanKernel::kPipelined) return p->nwg;
+    return ((batched_columns(p, k, images, h, w) + 31) / 32) * p->b_nw;
+}
+
+// Which kernel (the batched one from 3 images on where it fits, else the pipelined one where it fits, else the generic one;
+// `force` names one, with identical results), in how many launches, with which grid and LDS.
+// Encode calls have a second schedule, the wavefront one of the batched kernel: forced by BASIC_SCAN_KERNEL=wavefront or by the
+// requested schedule (the environment wins), taken in auto where wavefront_auto says so; the raster schedule is the choice
+// above, whatever wavefront_auto says.  Decode calls ignore both.
+// And a third, the band (BASIC_SCAN_KERNEL=band, BASIC_SCAN_SCHEDULE_BAND): any batch and height, in as many launches as the
+// batch needs.  In auto it is looked at only where the wavefront does not fit, and taken where band_auto says so.
+// A forced kernel or schedule that the call does not fit is refused (BASIC_ERR_INVALID, "does not fit").
+int plan_scan(const basic_scanline_plan *p, const ScanRequest &q, ScanLaunch *L)
+{
+    *L = ScanLaunch{};
+    L->cus = q.cus;
+    const bool decode = q.decode;
+    const int batch = q.batch, h = q.h, w = q.w, cus = q.cus;
+    const int ndec = decode ? decoder_workgroups(batch) : 0;
+    int schedule = q.schedule;
+    ScanKernel force = q.force;
+    if (decode && force != ScanKernel::kNone && !row_of(force, true).fn) force = ScanKernel::kNone;   // encode only: a decode call ignores it
+    const bool wf_fits = !decode && wavefront_fits(p, batch, h, cus);
+    int band_n = -1;   // band_images_per_launch, when somebody asks
+    auto band_images = [&] { return band_n >= 0 ? band_n : (band_n = band_images_per_launch(p, h, w, cus)); };
+    if (q.lane_max_batch >= 0) {
+        if (decode && !q.fast_image) return BASIC_OK;
+        // a forced band serves any batch: the call is cut into launches over whole images
+        const bool band_asked = !decode && schedule == BASIC_SCAN_SCHEDULE_BAND && band_images() >= 1;
+        if (!band_asked && batch > q.lane_max_batch && batch > batched_max_batch(p, w, decode, cus)) {
+            // no raster kernel serves this batch; an encode call may still run as a wavefront (a narrow latent, for one), or, in
+            // auto, as a band where that beats the per-step path.  (kept as it is: a forced wavefront that does not fit is not
+            // refused here but left to the per-step path)
+            if (decode || schedule == BASIC_SCAN_SCHEDULE_RASTER) return BASIC_OK;
+            if (wf_fits) schedule = BASIC_SCAN_SCHEDULE_WAVEFRONT;
+            else if (schedule == BASIC_SCAN_SCHEDULE_AUTO && band_beats_per_step(p, batch, h, w, band_images())) schedule = BASIC_SCAN_SCHEDULE_BAND;
+            else return BASIC_OK;
+        }
+        if (!lane_grid_resident(p, ndec, cus) || (decode && q.decoder_lds > kMaxLds)) return BASIC_OK;
+    }
+    if (force == ScanKernel::kNone && !decode && schedule == BASIC_SCAN_SCHEDULE_WAVEFRONT) force = ScanKernel::kWavefront;
+    if (force == ScanKernel::kNone && !decode && schedule == BASIC_SCAN_SCHEDULE_BAND) force = ScanKernel::kBand;
+    const bool automatic = force == ScanKernel::kNone && schedule == BASIC_SCAN_SCHEDULE_AUTO;
+    const bool fits = batched_fits(p, batch, w, ndec, cus);
+    if (force == ScanKernel::kBatched) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=batched, but this call does not fit the batched kernel");
+    if (force == ScanKernel::kWavefront) BASIC_REQUIRE(wf_fits, "scanline: the wavefront encode schedule was asked for, but this call does not fit it");
+    const int per_launch = !decode && (force == ScanKernel::kBand || (automatic && !wf_fits)) ? band_images() : 0;
+    if (force == ScanKernel::kBand) BASIC_REQUIRE(per_launch >= 1, "scanline: the band encode schedule was asked for, but this call does not fit it");
+    L->images = batch;
+    if (force == ScanKernel::kBand || (per_launch >= 1 && band_auto(p, batch, h, w, per_launch))) {
+        L->kernel = ScanKernel::kBand;
+        L->images = std::min(per_launch, batch);
+    } else if (force == ScanKernel::kWavefront || (automatic && wf_fits && wavefront_auto(p, batch, h, w))) {
+        L->kernel = ScanKernel::kWavefront;
+    } else if (force == ScanKernel::kBatched || (force == ScanKernel::kNone && fits && batch >= 3)) {
+        L->kernel = ScanKernel::kBatched;
+    } else {
+        const int rc = lane_lds(p, batch, w, q.table_len, force, &L->lane);
+        if (rc) return rc;
+        L->kernel = L->lane.pipelined ? ScanKernel::kPipelined : ScanKernel::kGeneric;
+        L->lds_bytes = L->lane.lds_bytes;
+        BASIC_REQUIRE(p->nwg + ndec <= cus, "scanline: more workgroups than compute units (the grid must be resident)");
+    }
+    if (L->kernel != ScanKernel::kGeneric && L->kernel != ScanKernel::kPipelined)
+        L->lds_bytes = (align4(q.table_len) + 4 + 96 + static_cast<size_t>(p->b_tiles) * kBTile) * sizeof(float);   // table, flags, biases, partial tiles
+    L->launches = (batch + L->images - 1) / L->images;
+    L->grid = compute_workgroups(p, L->kernel, L->images, h, w) + ndec;
+    if (decode) L->lds_bytes = std::max(L->lds_bytes, q.decoder_lds);
+    if (L->lds_bytes < kMinLds) L->lds_bytes = kMinLds;
+    BASIC_REQUIRE(L->lds_bytes <= kMaxLds, L->kernel == ScanKernel::kBand ? "scanline: a workgroup's LDS does not fit"
+                                                                          : "scanline: a workgroup's LDS (decoder: the search image) does not fit");
+    return BASIC_OK;
+}
+
+int device_cus(int *cus)
+{
+    int dev = 0;
+    BASIC_HIP_TRY(hipGetDevice(&dev));
+    BASIC_HIP_TRY(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
+    return BASIC_OK;
+}
+
+// What the planner cannot know by itself: the device, the environment and the table set (`tables` != nullptr: decode; *tv: its fast
+// search image, when it has one)
+int make_request(const basic_rans_tables *tables, int batch, int h, int w, int table_len, int schedule, int lane_max_batch, ScanRequest *q,
+                 RansFastView *tv)
+{
+    q->batch = batch; q->h = h; q->w = w; q->table_len = table_len;
+    q->schedule = schedule; q->lane_max_batch = lane_max_batch;
+    q->force = forced_kernel();
+    q->decode = tables != nullptr;
+    q->fast_image = q->decode && rans_fast_view(tables, tv) == BASIC_OK;
+    q->decoder_lds = q->fast_image ? decoder_lds_bytes(*tv) : 0;
+    return device_cus(&q->cus);
+}
+
+// Plans a *_dev call: the plan's encode schedule, no coder gates; `tables` != nullptr: decode
+int prepare_launch(const basic_scanline_plan *p, int batch, int h, int w, int table_len, const basic_rans_tables *tables, RansFastView *tv,
+                   ScanLaunch *L)
+{
+    ScanRequest q;
+    const int rc = make_request(tables, batch, h, w, table_len, p->encode_schedule, -1, &q, tv);
+    if (rc) return rc;
+    if (tables && !q.fast_image) return rans_fast_view(tables, tv);   // no fast search image: its error
+    return plan_scan(p, q, L);
+}
+
+// ---- launch arguments of one launch over `batch` images (of the call's `L.images` per launch)
+// generic / pipelined kernels
+int fill_args_lane(basic_scanline_plan *p, ScanArgs &a, const ScanLaunch &L, ScanScratch *sc, int batch, int h, int w, const float *d_prior, hipStream_t st)
+{
+    const int64_t HW = static_cast<int64_t>(h) * w;
+    *sc = lane_scratch(p, batch, HW);
+    int rc = ensure_scratch(p, sc->total, sc->gran_end, st);
+    if (rc) return rc;
+    for (int l = 0; l < p->nlayers; ++l) {
+        a.rpw[l] = p->rpw[l]; a.woff[l] = p->woff[l];
+        a.kgroup[l] = p->kgroup[l]; a.bpg[l] = p->bpg[l]; a.kpad[l] = p->kpad[l];
+    }
+    if (p->P > 0) {
+        const int64_t total = static_cast<int64_t>(batch) * HW * p->P;
+        int64_t g = (total + 255) / 256;
+        hipLaunchKernelGGL(transpose_prior_kernel, dim3(static_cast<unsigned>(g > 4096 ? 4096 : g)), dim3(256), 0, st, d_prior, p->d_scratch + sc->prior, p->P,
+                           static_cast<int>(HW), total);
+        BASIC_HIP_TRY(hipGetLastError());
+    }
+    const ScanLaneLds &o = L.lane;
+    a.tab_off = o.tab_off; a.ps_off = o.ps_off; a.xs_off = o.xs_off; a.part_off = o.part_off; a.flag_off = o.flag_off; a.bias_off = o.bias_off;
+    a.x0_off = o.x0_off; a.early_off = o.early_off; a.desc_off = o.desc_off; a.bc = o.bc; a.part_floats = o.part_floats;
+    return BASIC_OK;
+}
+
+// batched family (L.kernel: kBatched raster; kWavefront: yT [steps][C][yw], priorT [steps][P][nbt]; kBand: the band's)
+int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, const ScanLaunch &L, ScanScratch *sc, int batch, int h, int w, const float *d_prior, hipStream_t st)
+{
+    const bool wf = L.kernel != ScanKernel::kBatched, band = L.kernel == ScanKernel::kBand;
     const int pad = p->ksize / 2, yw = batch * (h + pad);
     const int64_t HW = wf ? wavefront_steps(p, h, w) : static_cast<int64_t>(h) * w;   // slabs of the coded latent and of the prior
     const int bA = band ? band_slots(p, w) : 0, ipt = band ? 32 / bA : 0;
-    const int cols = band ? 32 * ((batch + ipt - 1) / ipt) : wf ? batch * h : batch;
+    const int cols = batched_columns(p, L.kernel, batch, h, w);
     const int tiles = (cols + 31) / 32, nbt = 32 * tiles;
     if (wf) { a.wf_cols = cols; a.wf_s = wavefront_slope(p); a.wf_steps = static_cast<int>(HW); a.wf_yw = yw; }
     a.band_A = bA; a.band_ipt = ipt;
-    a.B = batch; a.C = p->C; a.H = h; a.W = w; a.P = p->P;
-    a.nlayers = p->nlayers; a.ntaps = p->ntaps; a.vec4 = p->vec4;
-    a.table = d_table; a.table_len = table_len;
     a.nbt = nbt; a.nw = p->b_nw; a.nd = p->b_nd; a.bpt = p->b_bpt; a.ctx_blocks = p->b_ctx_blocks;
-    // scratch: [granule regions: layer exchange arrays [rows][nbt], coded latent [HW][C][nbt], step means / rows [nbt][C]][prior [HW][P][nbt]]
-    size_t floats = 0;
-    for (int l = 0; l + 1 < p->nlayers; ++l) floats += align4(2 * static_cast<size_t>(nbt) * p->rows[l]);
-    const size_t yT_off = floats;     floats += align4(2 * static_cast<size_t>(wf ? yw : nbt) * HW * p->C);
-    const size_t mu_off = floats;     floats += align4(2 * static_cast<size_t>(nbt) * p->C);
-    const size_t is_off = floats;     floats += align4(2 * static_cast<size_t>(nbt) * p->C);
-    const size_t gran_floats = floats;
-    const size_t pT_off = floats;     floats += align4(static_cast<size_t>(nbt) * HW * p->P);
-    const size_t wl_off = floats;     floats += static_cast<size_t>(tiles) * p->b_nw * kThreads * 32;
-    if (floats > p->scratch_cap) {
-        if (p->d_scratch) (void)hipFree(p->d_scratch);
-        p->d_scratch = nullptr; p->scratch_cap = 0;
-        BASIC_HIP_TRY(hipMalloc(&p->d_scratch, floats * sizeof(float)));
-        p->scratch_cap = floats;
-    }
-    BASIC_HIP_TRY(hipMemsetAsync(p->d_scratch, 0, gran_floats * sizeof(float), st));   // tag 0 = "not written in this launch"
-    a.wlate = p->d_scratch + wl_off;
-    size_t ao = 0;
-    for (int l = 0; l < p->nlayers; ++l) {
-        a.rows[l] = p->rows[l]; a.kdim[l] = p->kdim[l]; a.act_after[l] = p->act_after[l];
-        a.nblk[l] = p->b_nblk[l]; a.rt[l] = p->b_rt[l]; a.tile_off[l] = p->b_tile_off[l];
-        a.w[l] = p->d_w[l]; a.bias[l] = p->d_b[l];
-        a.act[l] = nullptr;
-        if (l + 1 < p->nlayers) {
-            a.act[l] = reinterpret_cast<uint64_t *>(p->d_scratch + ao);
-            ao += align4(2 * static_cast<size_t>(nbt) * p->rows[l]);
-        }
-    }
-    a.yT = reinterpret_cast<uint64_t *>(p->d_scratch + yT_off);
-    a.mu = reinterpret_cast<uint64_t *>(p->d_scratch + mu_off);
-    a.idx_step = reinterpret_cast<uint64_t *>(p->d_scratch + is_off);
-    a.priorT = nullptr;
+    *sc = batched_scratch(p, nbt, HW, yw, L.kernel);
+    int rc = ensure_scratch(p, sc->total, sc->gran_end, st);
+    if (rc) return rc;
+    a.wlate = p->d_scratch + sc->wlate;
+    for (int l = 0; l < p->nlayers; ++l) { a.nblk[l] = p->b_nblk[l]; a.rt[l] = p->b_rt[l]; a.tile_off[l] = p->b_tile_off[l]; }
+    uint64_t *yT = reinterpret_cast<uint64_t *>(p->d_scratch + sc->yT);
     if (wf && pad > 0) {
         const int64_t total = HW * p->C * batch * pad;
         int64_t g = (total + 255) / 256;
-        hipLaunchKernelGGL(wavefront_pads_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, a.yT, p->C, batch, h, pad, yw, total);
+        hipLaunchKernelGGL(wavefront_pads_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, yT, p->C, batch, h, pad, yw, total);
         BASIC_HIP_TRY(hipGetLastError());
     }
     if (band && pad > 0) {
         const int64_t total = static_cast<int64_t>(p->C) * batch * h * 2 * pad;
         int64_t g = (total + 255) / 256;
-        hipLaunchKernelGGL(band_edges_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, a.yT, p->C, batch, h, w, a.wf_s, bA, pad,
+        hipLaunchKernelGGL(band_edges_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, yT, p->C, batch, h, w, a.wf_s, bA, pad,
                            a.wf_steps, yw, total);
         BASIC_HIP_TRY(hipGetLastError());
     }
     if (p->P > 0) {
-        float *pT = p->d_scratch + pT_off;
+        float *pT = p->d_scratch + sc->prior;
         const int64_t total = static_cast<int64_t>(cols) * HW * p->P;
         int64_t g = (total + 255) / 256;
         if (band)
@@ -2157,14 +2352,40 @@ int fill_args_batched(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int
             hipLaunchKernelGGL(transpose_prior_batched_kernel, dim3(static_cast<unsigned>(g > 8192 ? 8192 : g)), dim3(256), 0, st, d_prior, pT, batch,
                                p->P, static_cast<int>(HW), nbt, total);
         BASIC_HIP_TRY(hipGetLastError());
-        a.priorT = pT;
     }
-    // (wavefront: a tap's slab relative to the step's: dx steps along the row, wf_s per row)
-    for (int t = 0; t < p->ntaps; ++t) { a.tap_dy[t] = p->tap_dy[t]; a.tap_dx[t] = p->tap_dx[t]; a.tap_off[t] = p->tap_dy[t] * (wf ? a.wf_s : w) + p->tap_dx[t]; }
-    *lds_bytes = (align4(table_len) + 4 + 96 + static_cast<size_t>(p->b_tiles) * kBTile) * sizeof(float);   // table, flags, biases, partial tiles
+    return BASIC_OK;
+}
+
+// The arguments of one launch of the call `L` plans, over `batch` of its images: the family's own, then what both families share.
+// `first`: the first launch of the call, which also clears the barrier counter and the error flag (a later launch of the call
+// keeps an earlier one's error flag).
+int fill_args(basic_scanline_plan *p, ScanArgs &a, const ScanLaunch &L, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
+              bool first, hipStream_t st)
+{
+    const bool lane = L.kernel == ScanKernel::kGeneric || L.kernel == ScanKernel::kPipelined;
+    ScanScratch sc;
+    const int rc = lane ? fill_args_lane(p, a, L, &sc, batch, h, w, d_prior, st) : fill_args_batched(p, a, L, &sc, batch, h, w, d_prior, st);
+    if (rc) return rc;
+    a.B = batch; a.C = p->C; a.H = h; a.W = w; a.P = p->P;
+    a.nlayers = p->nlayers; a.ntaps = p->ntaps; a.vec4 = p->vec4;
+    a.table = d_table; a.table_len = table_len;
+    const int nact = lane ? p->nlayers : p->nlayers - 1;
+    for (int l = 0; l < p->nlayers; ++l) {
+        a.rows[l] = p->rows[l]; a.kdim[l] = p->kdim[l]; a.act_after[l] = p->act_after[l];
+        a.w[l] = p->d_w[l]; a.bias[l] = p->d_b[l];
+        a.act[l] = l < nact ? reinterpret_cast<uint64_t *>(p->d_scratch + sc.act[l]) : nullptr;
+    }
+    a.yT = reinterpret_cast<uint64_t *>(p->d_scratch + sc.yT);
+    a.mu = reinterpret_cast<uint64_t *>(p->d_scratch + sc.mu);
+    a.idx_step = reinterpret_cast<uint64_t *>(p->d_scratch + sc.idx_step);
+    a.priorT = p->P > 0 ? p->d_scratch + sc.prior : nullptr;
+    // a tap's position relative to the coded one (wavefront, band: its slab relative to the step's: dx steps along the row, wf_s per row)
+    const int row_stride = !lane && L.kernel != ScanKernel::kBatched ? wavefront_slope(p) : w;
+    for (int t = 0; t < p->ntaps; ++t) { a.tap_dy[t] = p->tap_dy[t]; a.tap_dx[t] = p->tap_dx[t]; a.tap_off[t] = p->tap_dy[t] * row_stride + p->tap_dx[t]; }
+    a.ncompute = compute_workgroups(p, L.kernel, batch, h, w);
     a.bar = p->d_bar;
     a.err = reinterpret_cast<int *>(p->d_bar + 1);
-    if (first) BASIC_HIP_TRY(hipMemsetAsync(p->d_bar, 0, 2 * sizeof(unsigned), st));   // (a later launch of the call keeps an earlier one's error flag)
+    if (first) BASIC_HIP_TRY(hipMemsetAsync(p->d_bar, 0, 2 * sizeof(unsigned), st));
     return BASIC_OK;
 }
 
@@ -2194,17 +2415,11 @@ struct ScanProfile {
                     h[0] / steps, h[1] / steps, h[2] / steps, h[3] / steps);
             for (int l = 1; l < a.nlayers; ++l)
                 fprintf(stderr, "dense L%d: prior blocks + wait %.1f, loads + chains %.1f, barrier + finish %.1f | ", l, h[4 * l] / steps, h[4 * l + 1] / steps, h[4 * l + 2] / steps);
-            fprintf(stderr, "loop %.1f ticks per step, %.2f shader clocks per tick", h[4 * kMaxLayers + 1] / steps,
-                    h[4 * kMaxLayers + 1] ? static_cast<double>(h[4 * kMaxLayers]) / h[4 * kMaxLayers + 1] : 0.0);
-            if (h[4 * kMaxLayers + 3])
-                fprintf(stderr, " | decoder wave of stream 0: waiting %.1f, decoding %.1f (shader clocks per step: decode_chunk %.0f, publishing %.0f; stream words per step %.1f)", h[4 * kMaxLayers + 2] / steps,
-                        h[4 * kMaxLayers + 3] / steps, h[4 * kMaxLayers + 4] / steps, h[4 * kMaxLayers + 5] / steps, h[4 * kMaxLayers + 6] / steps);
-            fprintf(stderr, "\n");
-            return;
+        } else {
+            fprintf(stderr, "scan-line %s profile (workgroup 0; 10 ns ticks per coding step: stage+wait / dots / finish / gauss): ", what);
+            for (int l = 0; l < a.nlayers; ++l)
+                fprintf(stderr, "L%d %.1f / %.1f / %.1f / %.1f | ", l, h[4 * l] / steps, h[4 * l + 1] / steps, h[4 * l + 2] / steps, h[4 * l + 3] / steps);
         }
-        fprintf(stderr, "scan-line %s profile (workgroup 0; 10 ns ticks per coding step: stage+wait / dots / finish / gauss): ", what);
-        for (int l = 0; l < a.nlayers; ++l)
-            fprintf(stderr, "L%d %.1f / %.1f / %.1f / %.1f | ", l, h[4 * l] / steps, h[4 * l + 1] / steps, h[4 * l + 2] / steps, h[4 * l + 3] / steps);
         fprintf(stderr, "loop %.1f ticks per step, %.2f shader clocks per tick", h[4 * kMaxLayers + 1] / steps,
                 h[4 * kMaxLayers + 1] ? static_cast<double>(h[4 * kMaxLayers]) / h[4 * kMaxLayers + 1] : 0.0);
         if (h[4 * kMaxLayers + 3])
@@ -2214,129 +2429,45 @@ struct ScanProfile {
     }
 };
 
-int device_cus(int *cus)
+int run_launch(basic_scanline_plan *p, ScanArgs &a, const ScanLaunch &L, int grid, bool decode, hipStream_t st)
 {
-    int dev = 0;
-    BASIC_HIP_TRY(hipGetDevice(&dev));
-    BASIC_HIP_TRY(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
-    return BASIC_OK;
-}
-
-// decoder workgroups of `batch` image streams (one wavefront per stream)
-int decoder_workgroups(int batch) { return (batch + kThreads / 64 - 1) / (kThreads / 64); }
-
-// LDS of a decoder workgroup: the fast search image of the table set
-size_t decoder_lds_bytes(const RansFastView &tv)
-{
-    return (static_cast<size_t>((tv.image_words + 3) & ~3) + 4 * static_cast<size_t>(tv.rows) + 4) * sizeof(uint32_t);
-}
-
-struct ScanLaunch {
-    ScanKernel kernel;   // kGeneric, kPipelined, kBatched, kWavefront or kBand
-    int grid;            // compute workgroups, then the decoder workgroups
-    int ncompute;
-    int cus;
-    size_t lds_bytes;
-    int band_images;     // kBand: images per launch (prepare_launch leaves the arguments to band_launches, one set per launch)
-};
-
-// The one place that decides how a scan-line call runs: which kernel (the batched one from 3 images on where it fits, else the
-// pipelined one where it fits, else the generic one; BASIC_SCAN_KERNEL = generic | pipelined | batched forces one, with
-// identical results), its grid and its LDS.  Fills the launch arguments; `tables` != nullptr: decode.
-// Encode calls have a second schedule, the wavefront one of the batched kernel: forced by BASIC_SCAN_KERNEL=wavefront or by the
-// plan's encode schedule (the environment wins over the plan), taken in auto where wavefront_auto says so; the plan's raster
-// schedule is the choice above, whatever wavefront_auto says.  Decode calls ignore both.
-// And a third, the band (BASIC_SCAN_KERNEL=band, BASIC_SCAN_SCHEDULE_BAND): any batch and height, in as many launches as the
-// batch needs.  In auto it is looked at only where the wavefront does not fit, and taken where band_auto says so.
-int prepare_launch(basic_scanline_plan *p, ScanArgs &a, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
-                   const basic_rans_tables *tables, hipStream_t st, ScanLaunch *L)
-{
-    ScanKernel force = ScanKernel::kAuto;
-    if (const char *e = getenv("BASIC_SCAN_KERNEL")) {
-        if (!strcmp(e, "generic")) force = ScanKernel::kGeneric;
-        else if (!strcmp(e, "pipelined")) force = ScanKernel::kPipelined;
-        else if (!strcmp(e, "batched")) force = ScanKernel::kBatched;
-        else if (!strcmp(e, "wavefront")) force = ScanKernel::kWavefront;
-        else if (!strcmp(e, "band")) force = ScanKernel::kBand;
-    }
-    const bool decode = tables != nullptr;
-    if ((force == ScanKernel::kWavefront || force == ScanKernel::kBand) && decode) force = ScanKernel::kAuto;
-    if (force == ScanKernel::kAuto && !decode && p->encode_schedule == BASIC_SCAN_SCHEDULE_WAVEFRONT) force = ScanKernel::kWavefront;
-    if (force == ScanKernel::kAuto && !decode && p->encode_schedule == BASIC_SCAN_SCHEDULE_BAND) force = ScanKernel::kBand;
-    if (decode) {
-        const int rc = rans_fast_view(tables, &a.tv);
-        if (rc) return rc;
-    }
-    const int ndec = decode ? decoder_workgroups(batch) : 0;
-    int rc = device_cus(&L->cus);
-    if (rc) return rc;
-    const bool fits = batched_fits(p, batch, w, ndec, L->cus);
-    if (force == ScanKernel::kBatched) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=batched, but this call does not fit the batched kernel");
-    const bool wf_fits = !decode && wavefront_fits(p, batch, h, L->cus);
-    if (force == ScanKernel::kWavefront) BASIC_REQUIRE(wf_fits, "scanline: the wavefront encode schedule was asked for, but this call does not fit it");
-    const int band_n = (!decode && (force == ScanKernel::kBand || (force == ScanKernel::kAuto && !wf_fits && p->encode_schedule == BASIC_SCAN_SCHEDULE_AUTO)))
-                           ? band_images_per_launch(p, h, w, L->cus) : 0;
-    if (force == ScanKernel::kBand) BASIC_REQUIRE(band_n >= 1, "scanline: the band encode schedule was asked for, but this call does not fit it");
-    if (force == ScanKernel::kBand || (band_n >= 1 && band_auto(p, batch, h, w, band_n))) {
-        L->kernel = ScanKernel::kBand;
-        L->band_images = band_n;
-        L->lds_bytes = 96 * 1024;
-        return BASIC_OK;
-    }
-    if (force == ScanKernel::kWavefront ||
-        (force == ScanKernel::kAuto && wf_fits && p->encode_schedule == BASIC_SCAN_SCHEDULE_AUTO && wavefront_auto(p, batch, h, w))) {
-        rc = fill_args_batched(p, a, batch, h, w, d_prior, d_table, table_len, &L->lds_bytes, st, 1);
-        if (rc) return rc;
-        L->kernel = ScanKernel::kWavefront;
-        L->ncompute = (a.nbt / 32) * p->b_nw;   // wavefront_fits: the grid is resident
-    } else if (force == ScanKernel::kBatched || (force == ScanKernel::kAuto && fits && batch >= 3)) {
-        rc = fill_args_batched(p, a, batch, h, w, d_prior, d_table, table_len, &L->lds_bytes, st);
-        if (rc) return rc;
-        L->kernel = ScanKernel::kBatched;
-        L->ncompute = (a.nbt / 32) * p->b_nw;   // batched_fits: the grid is resident
-    } else {
-        bool pipelined = false;
-        rc = fill_args(p, a, batch, h, w, d_prior, d_table, table_len, force, &L->lds_bytes, &pipelined, st);
-        if (rc) return rc;
-        L->kernel = pipelined ? ScanKernel::kPipelined : ScanKernel::kGeneric;
-        L->ncompute = p->nwg;
-        BASIC_REQUIRE(p->nwg + ndec <= L->cus, "scanline: more workgroups than compute units (the grid must be resident)");
-    }
-    a.ncompute = L->ncompute;
-    L->grid = L->ncompute + ndec;
-    if (decode) L->lds_bytes = std::max(L->lds_bytes, decoder_lds_bytes(a.tv));
-    // more than half of a compute unit's LDS per workgroup: exactly one workgroup per unit, as the barrier protocol assumes
-    if (L->lds_bytes < 96 * 1024) L->lds_bytes = 96 * 1024;
-    BASIC_REQUIRE(L->lds_bytes <= 160 * 1024, "scanline: a workgroup's LDS (decoder: the search image) does not fit");
-    return BASIC_OK;
-}
-
-template <bool DECODE> int run_launch(basic_scanline_plan *p, ScanArgs &a, const ScanLaunch &L, hipStream_t st)
-{
-    const void *fn = L.kernel == ScanKernel::kBand        ? reinterpret_cast<const void *>(scanline_batched_kernel<false, !DECODE, !DECODE>)
-                     : L.kernel == ScanKernel::kWavefront ? reinterpret_cast<const void *>(scanline_batched_kernel<false, !DECODE>)
-                     : L.kernel == ScanKernel::kBatched   ? reinterpret_cast<const void *>(scanline_batched_kernel<DECODE>)
-                     : L.kernel == ScanKernel::kPipelined ? reinterpret_cast<const void *>(scanline_pipelined_kernel<DECODE>)
-                                                          : reinterpret_cast<const void *>(scanline_persistent_kernel<DECODE>);
-    BASIC_HIP_TRY(ensure_max_lds(fn));
+    const ScanKernelRow &k = row_of(L.kernel, decode);
+    const ScanFn fn = k.fn;
+    BASIC_REQUIRE(fn, "scanline: the wavefront and band schedules are encode only");
+    BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(fn)));
     ScanProfile prof;
     int rc = prof.begin(a, st);
     if (rc) return rc;
-    BASIC_REQUIRE(!(DECODE && (L.kernel == ScanKernel::kWavefront || L.kernel == ScanKernel::kBand)), "scanline: the wavefront and band schedules are encode only");
-    p->last_kernel = L.kernel == ScanKernel::kBand       ? BASIC_SCAN_KERNEL_BAND
-                     : L.kernel == ScanKernel::kWavefront ? BASIC_SCAN_KERNEL_WAVEFRONT
-                     : L.kernel == ScanKernel::kBatched  ? BASIC_SCAN_KERNEL_BATCHED
-                     : L.kernel == ScanKernel::kPipelined ? BASIC_SCAN_KERNEL_PIPELINED
-                                                          : BASIC_SCAN_KERNEL_GENERIC;
-    rc = chained_launch(p, st, L.grid, L.cus, [&] {
-        if (L.kernel == ScanKernel::kBand) hipLaunchKernelGGL((scanline_batched_kernel<false, !DECODE, !DECODE>), dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
-        else if (L.kernel == ScanKernel::kWavefront) hipLaunchKernelGGL((scanline_batched_kernel<false, !DECODE>), dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
-        else if (L.kernel == ScanKernel::kBatched) hipLaunchKernelGGL(scanline_batched_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
-        else if (L.kernel == ScanKernel::kPipelined) hipLaunchKernelGGL(scanline_pipelined_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
-        else hipLaunchKernelGGL(scanline_persistent_kernel<DECODE>, dim3(L.grid), dim3(kThreads), L.lds_bytes, st, a);
-    });
-    prof.report(a, st, L.kernel == ScanKernel::kBand ? "encode (band)" : L.kernel == ScanKernel::kWavefront ? "encode (wavefront)" : L.kernel == ScanKernel::kBatched ? (DECODE ? "decode (batched)" : "encode (batched)") : (DECODE ? "decode" : "encode"));
+    p->last_kernel = k.id;
+    rc = chained_launch(p, st, grid, L.cus, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), L.lds_bytes, st, a); });
+    prof.report(a, st, k.label);
     return rc;
+}
+
+// A whole *_dev call: plan it, then one launch after the other over whole images (one launch is the common case; the band takes
+// more for a large batch): one stream, one scratch -- each launch clears and fills it in stream order.  `io`: the call's buffers,
+// of which a launch gets those of its images.
+int run_call(basic_scanline_plan *p, const ScanArgs &io, int batch, int h, int w, const float *d_prior, const float *d_table, int table_len,
+             const basic_rans_tables *tables, hipStream_t st)
+{
+    ScanLaunch L;
+    RansFastView tv;
+    int rc = prepare_launch(p, batch, h, w, table_len, tables, &tv, &L);
+    if (rc) return rc;
+    const bool decode = tables != nullptr;
+    const int64_t img_lat = static_cast<int64_t>(p->C) * h * w, img_prior = static_cast<int64_t>(p->P) * h * w;
+    for (int b0 = 0; b0 < batch; b0 += L.images) {
+        const int nb = std::min(L.images, batch - b0);
+        ScanArgs a = io;
+        if (decode) a.tv = tv;
+        rc = fill_args(p, a, L, nb, h, w, d_prior ? d_prior + b0 * img_prior : nullptr, d_table, table_len, b0 == 0, st);
+        if (rc) return rc;
+        if (a.y) a.y += b0 * img_lat;
+        a.ybuf += b0 * img_lat; a.sym += b0 * img_lat; a.idx += b0 * img_lat;
+        rc = run_launch(p, a, L, nb == L.images ? L.grid : a.ncompute, decode, st);   // (a short last launch: the band's, no decoder)
+        if (rc) return rc;
+    }
+    return BASIC_OK;
 }
 
 }  // namespace
@@ -2348,31 +2479,9 @@ extern "C" int basic_scanline_encode_dev(basic_scanline_plan *p, const float *d_
     BASIC_REQUIRE(p && d_y && d_table && d_symbols && d_indexes && d_ybuf && batch >= 1 && h >= 1 && w >= 1 && table_len >= 1 &&
                       table_len <= 4096 && (d_prior || p->P == 0),
                   "scanline_encode: bad argument");
-    hipStream_t st = as_stream(hip_stream);
-    ScanArgs a{};
-    ScanLaunch L{};
-    const int rc = prepare_launch(p, a, batch, h, w, d_prior, d_table, table_len, nullptr, st, &L);
-    if (rc) return rc;
-    if (L.kernel == ScanKernel::kBand) {
-        // successive launches over whole images: one stream, one scratch (each launch clears and fills it in stream order)
-        const int64_t img_lat = static_cast<int64_t>(p->C) * h * w, img_prior = static_cast<int64_t>(p->P) * h * w;
-        for (int b0 = 0; b0 < batch; b0 += L.band_images) {
-            const int nb = std::min(L.band_images, batch - b0);
-            ScanArgs ab{};
-            int rcb = fill_args_batched(p, ab, nb, h, w, d_prior ? d_prior + b0 * img_prior : nullptr, d_table, table_len, &L.lds_bytes, st, 2, b0 == 0);
-            if (rcb) return rcb;
-            L.ncompute = (ab.nbt / 32) * p->b_nw;   // band_images_per_launch: the grid is resident
-            L.grid = ab.ncompute = L.ncompute;
-            if (L.lds_bytes < 96 * 1024) L.lds_bytes = 96 * 1024;   // (one workgroup per compute unit, as in prepare_launch)
-            BASIC_REQUIRE(L.lds_bytes <= 160 * 1024, "scanline: a workgroup's LDS does not fit");
-            ab.y = d_y + b0 * img_lat; ab.ybuf = d_ybuf + b0 * img_lat; ab.sym = d_symbols + b0 * img_lat; ab.idx = d_indexes + b0 * img_lat;
-            rcb = run_launch<false>(p, ab, L, st);
-            if (rcb) return rcb;
-        }
-        return BASIC_OK;
-    }
-    a.y = d_y; a.ybuf = d_ybuf; a.sym = d_symbols; a.idx = d_indexes;
-    return run_launch<false>(p, a, L, st);
+    ScanArgs io{};
+    io.y = d_y; io.ybuf = d_ybuf; io.sym = d_symbols; io.idx = d_indexes;
+    return run_call(p, io, batch, h, w, d_prior, d_table, table_len, nullptr, as_stream(hip_stream));
 }
 
 extern "C" int basic_scanline_decode_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
@@ -2382,13 +2491,29 @@ extern "C" int basic_scanline_decode_dev(basic_scanline_plan *p, const basic_ran
     BASIC_REQUIRE(p && tables && d_words && d_word_off && d_table && d_symbols && d_indexes && d_ybuf && batch >= 1 && h >= 1 && w >= 1 &&
                       table_len >= 1 && table_len <= 4096 && (d_prior || p->P == 0),
                   "scanline_decode: bad argument");
-    hipStream_t st = as_stream(hip_stream);
-    ScanArgs a{};
-    ScanLaunch L{};
-    const int rc = prepare_launch(p, a, batch, h, w, d_prior, d_table, table_len, tables, st, &L);
+    ScanArgs io{};
+    io.ybuf = d_ybuf; io.sym = d_symbols; io.idx = d_indexes; io.words = d_words; io.word_off = d_word_off;
+    return run_call(p, io, batch, h, w, d_prior, d_table, table_len, tables, as_stream(hip_stream));
+}
+
+// What a basic_scanline_encode_dev (tables == nullptr) or basic_scanline_decode_dev call with these arguments would run, after the
+// coder's gates (ScanRequest::lane_max_batch): *kernel = BASIC_SCAN_KERNEL_NONE leaves the call to the per-step path, which codes
+// the same integers.  Launches nothing.
+extern "C" int basic_scanline_choose(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int h, int w, int table_len,
+                                     int schedule, int lane_max_batch, int *kernel, int *launches)
+{
+    BASIC_REQUIRE(p && kernel && batch >= 1 && h >= 0 && w >= 0 && table_len >= 1 && table_len <= 4096 && lane_max_batch >= 0 &&
+                      schedule >= BASIC_SCAN_SCHEDULE_AUTO && schedule <= BASIC_SCAN_SCHEDULE_BAND,
+                  "scanline_choose: bad argument");
+    ScanRequest q;
+    RansFastView tv;
+    ScanLaunch L;
+    int rc = make_request(tables, batch, h, w, table_len, schedule, lane_max_batch, &q, &tv);
+    if (!rc) rc = plan_scan(p, q, &L);
     if (rc) return rc;
-    a.ybuf = d_ybuf; a.sym = d_symbols; a.idx = d_indexes; a.words = d_words; a.word_off = d_word_off;
-    return run_launch<true>(p, a, L, st);
+    *kernel = L.kernel == ScanKernel::kNone ? BASIC_SCAN_KERNEL_NONE : row_of(L.kernel).id;
+    if (launches) *launches = L.launches;
+    return BASIC_OK;
 }
 
 // Whether basic_scanline_decode_dev can serve `batch` streams of this table set on the current device (the set has a fast
@@ -2403,7 +2528,7 @@ extern "C" int basic_scanline_can_decode(const basic_scanline_plan *p, const bas
     int cus = 0;
     int rc = device_cus(&cus);
     if (rc) return rc;
-    *ok = p->nwg + decoder_workgroups(batch) <= cus && decoder_lds_bytes(tv) <= 160 * 1024;
+    *ok = lane_grid_resident(p, decoder_workgroups(batch), cus) && decoder_lds_bytes(tv) <= kMaxLds;
     return BASIC_OK;
 }
 
@@ -2417,10 +2542,7 @@ extern "C" int basic_scanline_batched_max(const basic_scanline_plan *p, int w, i
     int cus = 0;
     int rc = device_cus(&cus);
     if (rc) return rc;
-    for (int b = 32 * kBatchedMaxTiles; b >= 1; b -= 32) {
-        const int ndec = decode ? decoder_workgroups(b) : 0;
-        if (batched_fits(p, b, w, ndec, cus)) { *max_batch = b; break; }
-    }
+    *max_batch = batched_max_batch(p, w, decode != 0, cus);
     return BASIC_OK;
 }
 

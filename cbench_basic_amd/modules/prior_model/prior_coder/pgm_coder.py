@@ -621,40 +621,17 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         sl = sp[0]
         if sl is None:
             return None
-        schedule = self.scanline_encode_schedule
-        if schedule == "band" and not decode and width is not None and height is not None and sl.band_max(height, width) >= 1:
-            if not sl.can_encode(batch):
-                return None
-            sl.set_encode_schedule("band")   # any batch: the call is cut into launches over whole images
-            return sl
-        if batch > self.persistent_scanline_max_batch and (width is None or batch > sl.batched_max(width, decode)):
-            # no raster kernel serves this batch; an encode call may still run as a wavefront (a narrow latent, for one), or, in
-            # auto, as a band where that beats the per-step path
-            if decode or schedule == "raster" or width is None or height is None:
-                return None
-            if batch <= sl.wavefront_max(height, width):
-                schedule = "wavefront"
-            elif schedule == "auto" and self._band_beats_per_step(sl, batch, height, width):
-                schedule = "band"
-            else:
-                return None
-        if not (sl.can_decode(self._tables, batch) if decode else sl.can_encode(batch)):
+        # one planner (csrc/scanline.hip: plan_scan) holds every rule: which kernel, or None where the per-step path should code the
+        # call.  A call whose latent size is not given can only be asked about the kernels that need none.
+        known = width is not None and height is not None
+        schedule = self.scanline_encode_schedule if known else "auto"
+        kernel, _ = sl.choose(batch, height or 0, width or 0, self._scale_table_dev.numel(), schedule, self.persistent_scanline_max_batch,
+                              self._tables if decode else None)
+        if kernel is None:
             return None
-        if not decode:
-            sl.set_encode_schedule(schedule)
+        if not decode:   # (a wavefront or a band the planner took for this call is pinned: the launch plans without the coder's gates)
+            sl.set_encode_schedule(kernel if kernel in ("wavefront", "band") else self.scanline_encode_schedule)
         return sl
-
-    @staticmethod
-    def _band_beats_per_step(sl, batch, height, width):
-        """Auto, a batch no raster kernel serves: the band against the per-step path.  Measured (scripts/scanline_band_probe.py,
-        profiles/scanline_band_probe.txt): a band step costs at most 25.7 us (eight tiles in the launch), a step of the per-step
-        path 110 us at 96 images (and more with the batch), so the band wins while launches * steps <= 4.3 H W; 3 leaves a
-        margin (96x16x16: two launches, 152 steps against 256, 28.1 -> 3.9 ms)."""
-        per_launch = sl.band_max(height, width)
-        if per_launch < 1:
-            return False
-        steps = width + (sl.ksize // 2 + 2) * (height - 1)
-        return -(-batch // per_launch) * steps <= 3 * height * width
 
     def _run_encode(self, y, prior, pgm=None):
         self._ready()
@@ -856,7 +833,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         stage = self._tables._stage_in(int(woff[-1]))
         stage.numpy()[:] = np.frombuffer(body, dtype=np.int32, count=int(woff[-1]), offset=payload)
         words_np = stage.numpy()
-        sl = self._scanline_plan(plan, prior, B, decode=True, width=W)
+        sl = self._scanline_plan(plan, prior, B, decode=True, width=W, height=H)
         if sl is not None:   # persistent scan-line launch (see _run_encode); one stream per image
             d_words = stage.to(dev, non_blocking=True)
             self._tables._pin_in_event = torch.cuda.Event()

@@ -5,6 +5,7 @@ hand-written HIP kernel.  All functions require CUDA(HIP) tensors and raise othe
 there is no CPU implementation behind them.
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -596,6 +597,27 @@ class ScanlinePlan:
         if schedule not in SCAN_SCHEDULES:
             raise ValueError(f"encode schedule must be one of {SCAN_SCHEDULES}, not {schedule!r}")
         _lib.check(_lib.lib().basic_scanline_set_encode_schedule(self._h, SCAN_SCHEDULES.index(schedule)))
+
+    def choose(self, batch, height, width, table_len, schedule="auto", lane_max_batch=0, tables=None):
+        """What an encode call (tables None) or a decode call with that table set would run for `batch` images of a `height` x
+        `width` latent (0: not known), as the library's one planner decides it -- without launching: -> (kernel, launches), kernel
+        one of SCAN_KERNELS, or None where the call is left to the per-step path.  `schedule` stands for the plan's encode schedule
+        (BASIC_SCAN_KERNEL wins over it); batches above `lane_max_batch` are not given to the generic and pipelined kernels.  A
+        forced kernel or schedule the call does not fit raises, as the launch would."""
+        if schedule not in SCAN_SCHEDULES:
+            raise ValueError(f"encode schedule must be one of {SCAN_SCHEDULES}, not {schedule!r}")
+        # the answer depends on nothing but these, so a repeated call (every step of a stream worker) asks the library once: a
+        # library call releases the interpreter lock, and with several workers each release is a chance to wait for it again
+        key = (int(batch), int(height), int(width), int(table_len), schedule, int(lane_max_batch), id(tables), os.environ.get("BASIC_SCAN_KERNEL"),
+               torch.cuda.current_device())
+        cache = self.__dict__.setdefault("_chosen", {})
+        if key not in cache:
+            k, n = ctypes.c_int(), ctypes.c_int()
+            _lib.check(_lib.lib().basic_scanline_choose(self._h, tables._h if tables is not None else None, int(batch), int(height), int(width),
+                                                        int(table_len), SCAN_SCHEDULES.index(schedule), int(lane_max_batch), ctypes.byref(k),
+                                                        ctypes.byref(n)))
+            cache[key] = ((SCAN_KERNELS[k.value] if k.value >= 0 else None), n.value, tables)   # (tables: keeps its id its own)
+        return cache[key][:2]
 
     def can_decode(self, tables, batch):
         ok = ctypes.c_int()

@@ -419,6 +419,18 @@ int basic_scanline_last_kernel(const basic_scanline_plan *p, int *kernel);
 #define BASIC_SCAN_SCHEDULE_WAVEFRONT 2
 #define BASIC_SCAN_SCHEDULE_BAND 3
 int basic_scanline_set_encode_schedule(basic_scanline_plan *p, int schedule);
+/* What a call would run, without launching anything: tables == NULL asks about basic_scanline_encode_dev, otherwise about
+ * basic_scanline_decode_dev with that table set, for `batch` images of an h x w latent (0 = not known: only the kernels that
+ * need no such knowledge are considered) and a scale table of table_len entries.  One planner in csrc/scanline.hip answers this
+ * and plans the launches of both *_dev calls, so the answer is what they do.  `schedule` (BASIC_SCAN_SCHEDULE_*) stands for the
+ * plan's encode schedule, BASIC_SCAN_KERNEL still wins over it, and lane_max_batch (>= 0) is the coder's gate: a larger batch is
+ * not given to the kernels that keep one output per lane (generic, pipelined).
+ * *kernel = BASIC_SCAN_KERNEL_*; BASIC_SCAN_KERNEL_NONE = leave the call to the per-step path (no persistent kernel serves the
+ * batch, the grid would not be resident, or the table set has no fast search image).  *launches (may be NULL) = the launches of
+ * the call: 1, or what the band needs for the batch.  A forced kernel or schedule that the call does not fit fails as the
+ * launch would: BASIC_ERR_INVALID ("does not fit"). */
+int basic_scanline_choose(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int h, int w, int table_len,
+                          int schedule, int lane_max_batch, int *kernel, int *launches);
 int basic_scanline_status(basic_scanline_plan *p, void *hip_stream, int *poisoned);
 void basic_scanline_plan_destroy(basic_scanline_plan *p);
 

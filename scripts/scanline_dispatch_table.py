@@ -1,0 +1,56 @@
+#!/usr/bin/env python3
+"""Records which kernel serves a scan-line call: walks a fixed list of (coder, batch, H, W, direction, scanline_encode_schedule,
+BASIC_SCAN_KERNEL) and writes one outcome per call to tests/golden/scanline_dispatch.json, with the device's compute-unit count
+(the rules count workgroups against it):
+
+    "per-step"   the coder's _scanline_plan returns None (nothing is run: the per-step path would code the call)
+    "raises"     the call is refused ("does not fit")
+    otherwise    ScanlinePlan.last_kernel() after _run_encode, or after decoding what the coder's defaults encoded
+
+tests/test_gpu_scanline_dispatch.py replays the table: a change of the host code must not change a row.  Run it on the GPU the
+table is for, at the commit whose decisions are the reference:
+
+    python scripts/scanline_dispatch_table.py"""
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import scanline_cases as sc  # noqa: E402
+
+KERNELS = ("generic", "pipelined", "batched", "wavefront", "band")
+SCHEDULES = ("auto", "raster", "wavefront", "band")
+# 5x5 window, C = 192: Kodak-shaped latents, bench.py's 16x16 up to and past the raster kernels' 64 images, more images than the
+# wavefront's 64 columns, a full wavefront, a latent narrower than ksize / 2 + 2, one taller than 64 rows, one too wide for a band
+SHAPES = [("ctxmodel", 192, B, 32, 48) for B in (1, 2, 3, 8, 16)] + [("ctxmodel", 192, B, 16, 16) for B in (1, 4, 5, 33, 64, 96)] + \
+         [("ctxmodel", 192, 65, 1, 4), ("ctxmodel", 192, 13, 4, 4), ("ctxmodel", 192, 2, 3, 2), ("ctxmodel", 192, 1, 70, 24),
+          ("ctxmodel", 192, 1, 3, 130), ("ctxmodel-k3", 192, 1, 4, 3), ("ctxmodel-k3", 192, 3, 16, 16), ("merger", 32, 1, 5, 5)]
+
+
+def calls():
+    for shape in SHAPES:
+        for direction in ("encode", "decode"):   # (a decode call ignores the schedule: crossed with it all the same)
+            for schedule, env in [(s, None) for s in SCHEDULES] + [("auto", k) for k in KERNELS]:
+                yield dict(zip(sc.DISPATCH_FIELDS, shape + (direction, schedule, env)))
+
+
+def main():
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    rows, cache = [], {}
+    for row in calls():
+        row["outcome"] = sc.dispatch_run(sc._shared_coder(row["kind"], row["C"]), row, cache)
+        print(row, flush=True)
+        rows.append(row)
+    path = os.path.join(ROOT, "tests", "golden", "scanline_dispatch.json")
+    with open(path, "w") as f:
+        f.write('{"compute_units": %d, "fields": %s, "rows": [\n' % (cus, json.dumps(list(sc.DISPATCH_FIELDS) + ["outcome"])))
+        f.write(",\n".join(json.dumps([r[k] for k in sc.DISPATCH_FIELDS + ("outcome",)]) for r in rows))
+        f.write("\n]}\n")
+    print(f"{len(rows)} rows -> {path}")
+
+
+if __name__ == "__main__":
+    main()

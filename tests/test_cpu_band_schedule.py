@@ -108,4 +108,5 @@ def test_header_declares_the_entry():
     with open(os.path.join(root, "include", "basic_hip.h")) as f:
         header = f.read()
     assert re.search(r"\bint\s+basic_scanline_band_max\s*\(", header)
+    assert re.search(r"\bint\s+basic_scanline_choose\s*\(\s*const\s+basic_scanline_plan\s*\*\s*p\s*,\s*const\s+basic_rans_tables\s*\*\s*tables\s*,", header)
     assert re.search(r"#define\s+BASIC_SCAN_SCHEDULE_BAND\s+3\b", header) and re.search(r"#define\s+BASIC_SCAN_KERNEL_BAND\s+4\b", header)

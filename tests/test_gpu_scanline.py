@@ -8,28 +8,9 @@ import os
 import pytest
 import torch
 
+from scanline_cases import _coder
+
 pytestmark = pytest.mark.gpu
-
-
-def _coder(kind, C):
-    from cbench_basic_amd.modules.prior_model.prior_coder.pgm_coder import (GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder as Coder,
-                                                                            TopoGroupDynamicMaskConv2dContextModel as Ctx)
-    if kind.startswith("ctxmodel"):   # "ctxmodel", or "ctxmodel-k3" for a 3x3 context window (the masked-convolution plans stop at 5x5)
-        ks = int(kind.split("-k")[1]) if "-k" in kind else 5
-        c = Coder(in_channels=C, default_topo_group_method="scanline", topo_group_context_model=Ctx(in_channels=C, out_channels=2 * C, kernel_size=ks))
-    elif kind == "merger":
-        c = Coder(in_channels=C, default_topo_group_method="scanline")
-    elif kind == "merger-expand":
-        c = Coder(in_channels=C, default_topo_group_method="scanline", param_merger_expand_bottleneck=True)
-    else:
-        c = Coder(in_channels=C, use_joint_ar_model_impl=True)
-    g = torch.Generator().manual_seed(17)
-    with torch.no_grad():
-        for p in c.parameters():
-            p.copy_(torch.randn(p.shape, generator=g) * (0.05 if p.dim() > 1 else 0.02))
-    c = c.eval().cuda()
-    c.update_state()
-    return c
 
 
 @pytest.mark.parametrize("kind,C,B,H,W", [("ctxmodel", 32, 1, 6, 5), ("ctxmodel", 32, 3, 4, 7), ("ctxmodel", 192, 2, 5, 6), ("merger", 32, 2, 5, 5),
