@@ -1119,13 +1119,27 @@ __global__ __launch_bounds__(512, 1) void conv5x5_cin4_gdn_persistent_kernel(con
 // position and produces its 2x2 output pixels x Cout: per input channel 9 LDS reads (the 3x3
 // neighbourhood) feed all 25 taps x Cout FMAs, with the weights as wave-uniform scalar operands.
 // ---------------------------------------------------------------------------------------------
-constexpr int kSmTileH = 16;              // input positions per workgroup: 16 rows x 64 columns,
-constexpr int kSmTileW = 64;              // one lane = a 1 x 4 strip -> 2 x 8 output pixels x Cout
-constexpr int kSmCK = 8;                  // input channels per LDS stage
-constexpr int kSmPH = kSmTileH + 2;       // +-1 halo
-constexpr int kSmPW = kSmTileW + 2;
+constexpr int kSmTileW = 64;              // input columns per workgroup: a lane owns a 1 x 4 strip
+constexpr int kSmCK = 8;                  // plain staging: input channels per LDS stage
+constexpr int kSmPW = kSmTileW + 2;       // +-1 halo
 constexpr int kSmPitch = 68;              // row pitch in floats (16-byte multiple: aligned ds_read_b128)
+constexpr int kSmDRow = 18;               // LDS-DMA staging: 16-byte chunks per LDS row (pitch 72 floats)
 constexpr int kSmWRow = 80;               // packed weights per input channel: 25 taps x 3, padded to 5 x 16
+
+// A workgroup's tile of input positions: 16 lane rows x 64 columns, STRIPS vertically adjacent 1 x 4 strips per lane.
+// STRIPS = 2: a channel's 75 scalar weights feed 300 packed FMAs instead of 150 (the 40 KB of weights do not fit the
+// scalar cache: round 2's counters showed half of those loads missing), and the strips share two of four patch rows.
+template <int STRIPS>
+struct SmTile {
+    static_assert(4 % STRIPS == 0, "a stage holds 4 / STRIPS whole input channels");
+    static constexpr int kTileH = 16 * STRIPS;                    // input rows per workgroup
+    static constexpr int kPH = kTileH + 2;                        // +-1 halo
+    static constexpr int kDCK = 4 / STRIPS;                       // LDS-DMA staging: input channels per stage
+    static constexpr int kDChunks = kDCK * kPH * kSmDRow;         // chunks per stage
+    static constexpr int kDSlots = (kDChunks + 255) / 256;        // DMA instructions per thread and stage
+    static constexpr int kDStage = kDSlots * 256 * 4;             // floats per stage buffer (whole instructions)
+    static_assert(kDStage % 1024 == 0, "every DMA instruction of the workgroup writes 1024 floats");
+};
 
 struct SmallLaunch {
     const float *in;      // [B][cin][H][W]
@@ -1138,8 +1152,83 @@ struct SmallLaunch {
 typedef float f32x16s __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(4))) f32x16s cf32x16s;
 
-// The 75 weights of input channel C as wave-uniform scalars (5 x s_load_dwordx16) times the pair table pr[3][5]
-// of a lane's strip: 150 packed FMAs into acc[pair][py][px][co].
+// acc[strip row][pair of strip positions][py][px][co]: both LDS-DMA kernels accumulate and store through the three
+// functions below, so each output's FMA chain is the same in them (and in the plain kernel's own copy): identical results.
+template <int STRIPS>
+__device__ __forceinline__ void sm_zero(f32x2 (&acc)[STRIPS][2][2][2][3])
+{
+#pragma unroll
+    for (int sr = 0; sr < STRIPS; ++sr)
+#pragma unroll
+        for (int qp = 0; qp < 2; ++qp)
+#pragma unroll
+            for (int py = 0; py < 2; ++py)
+#pragma unroll
+                for (int px = 0; px < 2; ++px)
+#pragma unroll
+                    for (int co = 0; co < 3; ++co) acc[sr][qp][py][px][co] = f32x2{0.f, 0.f};
+}
+
+// The 75 weights of one input channel (wrow: its 80 packed floats) as wave-uniform scalars (5 x s_load_dwordx16) times the
+// pair table pr[STRIPS + 2][5] of a lane's strips: 150 packed FMAs per strip.  Strip row sr uses patch rows sr .. sr + 2.
+template <int STRIPS>
+__device__ __forceinline__ void sm_accumulate(f32x2 (&acc)[STRIPS][2][2][2][3], const float *wrow, const f32x2 (&pr)[STRIPS + 2][5])
+{
+    // constant address space: keeps these wave-uniform loads on the scalar unit (s_load_dwordx16) even
+    // after the LDS-DMA intrinsic, which the compiler treats as a store that could alias them
+    const cf32x16s *w16 = (const cf32x16s *)wrow;
+    const f32x16s w0 = w16[0], w1 = w16[1], w2 = w16[2], w3 = w16[3], w4 = w16[4];
+#pragma unroll
+    for (int ky = 0; ky < 5; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 5; ++kx) {
+            // output row 2*my + py receives input row my + dy through ky = py + 2 - 2*dy
+            const int py = ky & 1, px = kx & 1;
+            const int dy = (py + 2 - ky) / 2, dx = (px + 2 - kx) / 2;  // in {-1, 0, 1}
+#pragma unroll
+            for (int co = 0; co < 3; ++co) {
+                const int wi = (ky * 5 + kx) * 3 + co;
+                const float w = wi < 16 ? w0[wi & 15] : wi < 32 ? w1[wi & 15] : wi < 48 ? w2[wi & 15] : wi < 64 ? w3[wi & 15] : w4[wi & 15];
+                const f32x2 ww = {w, w};
+#pragma unroll
+                for (int sr = 0; sr < STRIPS; ++sr)
+#pragma unroll
+                    for (int qp = 0; qp < 2; ++qp)
+                        acc[sr][qp][py][px][co] = __builtin_elementwise_fma(pr[sr + dy + 1][2 * qp + dx + 1], ww, acc[sr][qp][py][px][co]);
+            }
+        }
+}
+
+// bias + activation, 8-byte pair stores: the lane's strips start at input position (my, mx0) of image b
+template <int STRIPS>
+__device__ __forceinline__ void sm_store(const f32x2 (&acc)[STRIPS][2][2][2][3], const SmallLaunch &g, int b, int my, int mx0)
+{
+    const int oh = 2 * g.in_h, ow = 2 * g.in_w;
+#pragma unroll
+    for (int sr = 0; sr < STRIPS; ++sr) {
+        if (my + sr >= g.in_h) break;
+#pragma unroll
+        for (int co = 0; co < 3; ++co) {
+            if (co >= g.cout) break;
+            const float bv = g.bias[co];
+            float *o = g.out + (static_cast<int64_t>(b) * g.cout + co) * oh * ow + static_cast<int64_t>(2 * (my + sr)) * ow + 2 * mx0;
+#pragma unroll
+            for (int py = 0; py < 2; ++py)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (mx0 + q >= g.in_w) break;
+                    float2 r;
+                    r.x = apply_act(acc[sr][q >> 1][py][0][co][q & 1] + bv, g.act);
+                    r.y = apply_act(acc[sr][q >> 1][py][1][co][q & 1] + bv, g.act);
+                    *reinterpret_cast<float2 *>(o + py * ow + 2 * q) = r;
+                }
+        }
+    }
+}
+
+// Plain staging (any width and alignment): one strip per lane, element-wise guarded loads into a [channel][row][68] patch.
+// The kernel keeps its own copy of the accumulate (the loop nest of sm_accumulate<1>, as a macro), zeroing and epilogue:
+// built on the shared functions it measured 0.8-1.1 % slower on the MI355X (profiles/small_deconv_refactor.txt).
 #define BASIC_SM_ACCUMULATE(C)                                                                                 \
     do {                                                                                                       \
         /* constant address space: keeps these wave-uniform loads on the scalar unit (s_load_dwordx16) even */ \
@@ -1163,6 +1252,7 @@ typedef __attribute__((address_space(4))) f32x16s cf32x16s;
 
 __global__ __launch_bounds__(256) void deconv5s2_cout3_kernel(const SmallLaunch g)
 {
+    constexpr int kSmTileH = SmTile<1>::kTileH, kSmPH = SmTile<1>::kPH;
     __shared__ __attribute__((aligned(16))) float patch[kSmCK][kSmPH][kSmPitch];
     const int tid = threadIdx.x;
     int bid = xcd_tile(blockIdx.x, gridDim.x);
@@ -1235,19 +1325,17 @@ __global__ __launch_bounds__(256) void deconv5s2_cout3_kernel(const SmallLaunch 
         }
     }
 }
+#undef BASIC_SM_ACCUMULATE
 
 // The same layer with LDS-DMA staging (needs in_w % 4 == 0): an LDS row is the 16-byte aligned global span
 // [x0 - 4, x0 + 68) of an input row -- 18 chunks that are each entirely inside or entirely outside the image --
 // so a stage is a lane-linear image of 16-byte pieces, double buffered one stage ahead of the FMAs.
-constexpr int kSmDCK = 4;                                   // input channels per stage
-constexpr int kSmDRow = 18;                                 // 16-byte chunks per LDS row (pitch 72 floats)
-constexpr int kSmDChunks = kSmDCK * kSmPH * kSmDRow;        // chunks per stage
-constexpr int kSmDSlots = (kSmDChunks + 255) / 256;         // DMA instructions per thread and stage
-constexpr int kSmDStage = kSmDSlots * 256 * 4;              // floats per stage buffer (whole instructions)
-
+// Tile = 16 STRIPS x 64 input positions per workgroup.
+template <int STRIPS>
 __global__ __launch_bounds__(256) void deconv5s2_cout3_dma_kernel(const SmallLaunch g)
 {
-    __shared__ __attribute__((aligned(16))) float buf[2 * kSmDStage];
+    using T = SmTile<STRIPS>;
+    __shared__ __attribute__((aligned(16))) float buf[2 * T::kDStage];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: LDS-DMA bases stay scalar
     int bid = xcd_tile(blockIdx.x, gridDim.x);
@@ -1255,69 +1343,64 @@ __global__ __launch_bounds__(256) void deconv5s2_cout3_dma_kernel(const SmallLau
     const int ty_i = bid % g.tiles_y; bid /= g.tiles_y;
     const int b = bid;
     const int lxq = tid & 15, ly = tid >> 4;
-    const int my = ty_i * kSmTileH + ly, mx0 = tx_i * kSmTileW + 4 * lxq;
+    const int my = ty_i * T::kTileH + STRIPS * ly, mx0 = tx_i * kSmTileW + 4 * lxq;
     const int64_t plane = static_cast<int64_t>(g.in_h) * g.in_w;
     const float *inb = g.in + static_cast<int64_t>(b) * g.cin * plane;
-    const int nstages = (g.cin + kSmDCK - 1) / kSmDCK;
+    const int nstages = (g.cin + T::kDCK - 1) / T::kDCK;
 
     // gather descriptors (see conv_tap_mfma_kernel): chunk k = tid + 256 s of every stage comes from pp[s]
-    const float *pp[kSmDSlots];
-    int pstride[kSmDSlots];
+    const float *pp[T::kDSlots];
+    int pstride[T::kDSlots];
     unsigned lastmask = 0;
 #pragma unroll
-    for (int sl = 0; sl < kSmDSlots; ++sl) {
+    for (int sl = 0; sl < T::kDSlots; ++sl) {
         const int k = tid + sl * 256;
         const float *ptr = basic_zero_page;
         int stride = 0;
-        if (k < kSmDChunks) {
+        if (k < T::kDChunks) {
             const int j = k % kSmDRow, r = k / kSmDRow;
-            const int py = r % kSmPH, ci = r / kSmPH;
-            const int gy = ty_i * kSmTileH - 1 + py, gx = tx_i * kSmTileW - 4 + 4 * j;
+            const int py = r % T::kPH, ci = r / T::kPH;
+            const int gy = ty_i * T::kTileH - 1 + py, gx = tx_i * kSmTileW - 4 + 4 * j;
             if (gy >= 0 && gy < g.in_h && gx >= 0 && gx < g.in_w && ci < g.cin) {
                 ptr = inb + ci * plane + static_cast<int64_t>(gy) * g.in_w + gx;
-                stride = static_cast<int>(kSmDCK * plane * 4);
-                if ((nstages - 1) * kSmDCK + ci >= g.cin) lastmask |= 1u << sl;
+                stride = static_cast<int>(T::kDCK * plane * 4);
+                if ((nstages - 1) * T::kDCK + ci >= g.cin) lastmask |= 1u << sl;
             }
         }
         pp[sl] = ptr;
         pstride[sl] = stride;
     }
-#define BASIC_SM_ISSUE(S)                                                                                      \
-    do {                                                                                                       \
-        if ((S) == nstages - 1 && lastmask) {                                                                  \
-            _Pragma("unroll") for (int sl = 0; sl < kSmDSlots; ++sl)                                           \
-                if ((lastmask >> sl) & 1u) pp[sl] = basic_zero_page;                                           \
-        }                                                                                                      \
-        float *dst_ = buf + ((S) & 1) * kSmDStage + wave * 256;                                                \
-        _Pragma("unroll") for (int sl = 0; sl < kSmDSlots; ++sl) {                                             \
-            __builtin_amdgcn_global_load_lds((glb_cvoid *)pp[sl], (lds_void *)(dst_ + sl * 1024), 16, 0, 0);   \
-            pp[sl] = reinterpret_cast<const float *>(reinterpret_cast<const char *>(pp[sl]) + pstride[sl]);    \
-        }                                                                                                      \
-    } while (0)
+    // stage s into buffer s & 1; the channels past cin of a ragged last stage read the zero page
+    auto issue = [&](int s) {
+        if (s == nstages - 1 && lastmask) {
+#pragma unroll
+            for (int sl = 0; sl < T::kDSlots; ++sl)
+                if ((lastmask >> sl) & 1u) pp[sl] = basic_zero_page;
+        }
+        float *dst = buf + (s & 1) * T::kDStage + wave * 256;
+#pragma unroll
+        for (int sl = 0; sl < T::kDSlots; ++sl) {
+            __builtin_amdgcn_global_load_lds((glb_cvoid *)pp[sl], (lds_void *)(dst + sl * 1024), 16, 0, 0);
+            pp[sl] = reinterpret_cast<const float *>(reinterpret_cast<const char *>(pp[sl]) + pstride[sl]);
+        }
+    };
 
-    f32x2 acc[2][2][2][3];  // [pair of strip positions][py][px][co]
-#pragma unroll
-    for (int qp = 0; qp < 2; ++qp)
-#pragma unroll
-        for (int py = 0; py < 2; ++py)
-#pragma unroll
-            for (int px = 0; px < 2; ++px)
-#pragma unroll
-                for (int co = 0; co < 3; ++co) acc[qp][py][px][co] = f32x2{0.f, 0.f};
-
-    BASIC_SM_ISSUE(0);
+    f32x2 acc[STRIPS][2][2][2][3];
+    sm_zero<STRIPS>(acc);
+    issue(0);
     for (int stg = 0; stg < nstages; ++stg) {
         __syncthreads();  // this stage has landed; every wave is done with the buffer the next DMA overwrites
-        if (stg + 1 < nstages) BASIC_SM_ISSUE(stg + 1);
-        const float *st = buf + (stg & 1) * kSmDStage;
-        const int c0 = stg * kSmDCK;
-        const int cmax = (g.cin - c0 < kSmDCK) ? g.cin - c0 : kSmDCK;
+        if (stg + 1 < nstages) issue(stg + 1);
+        const float *st = buf + (stg & 1) * T::kDStage;
+        const int c0 = stg * T::kDCK;
+        const int cmax = (g.cin - c0 < T::kDCK) ? g.cin - c0 : T::kDCK;
         for (int ci = 0; ci < cmax; ++ci) {
-            // the strip's 3 x 6 neighbourhood starts one float before chunk lxq + 1 of rows ly .. ly + 2
-            f32x2 pr[3][5];
+            // patch rows STRIPS ly .. STRIPS ly + STRIPS + 1 = image rows my - 1 .. my + STRIPS; the strips'
+            // (STRIPS + 2) x 6 neighbourhood starts one float before chunk lxq + 1 of those rows
+            f32x2 pr[STRIPS + 2][5];
 #pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float *row = st + ((ci * kSmPH + ly + a) * kSmDRow + lxq) * 4 + 3;
+            for (int a = 0; a < STRIPS + 2; ++a) {
+                const float *row = st + ((ci * T::kPH + STRIPS * ly + a) * kSmDRow + lxq) * 4 + 3;
                 const float v0 = row[0], v5 = row[5];
                 const f32x4 mid = *reinterpret_cast<const f32x4 *>(row + 1);
                 pr[a][0] = f32x2{v0, mid[0]};
@@ -1326,169 +1409,10 @@ __global__ __launch_bounds__(256) void deconv5s2_cout3_dma_kernel(const SmallLau
                 pr[a][3] = f32x2{mid[2], mid[3]};
                 pr[a][4] = f32x2{mid[3], v5};
             }
-            BASIC_SM_ACCUMULATE(c0 + ci);
+            sm_accumulate<STRIPS>(acc, g.wsm + static_cast<int64_t>(c0 + ci) * kSmWRow, pr);
         }
     }
-#undef BASIC_SM_ISSUE
-    if (my < g.in_h) {
-        const int oh = 2 * g.in_h, ow = 2 * g.in_w;
-#pragma unroll
-        for (int co = 0; co < 3; ++co) {
-            if (co >= g.cout) break;
-            const float bv = g.bias[co];
-            float *o = g.out + (static_cast<int64_t>(b) * g.cout + co) * oh * ow + static_cast<int64_t>(2 * my) * ow + 2 * mx0;
-#pragma unroll
-            for (int py = 0; py < 2; ++py)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (mx0 + q >= g.in_w) break;
-                    float2 r;
-                    r.x = apply_act(acc[q >> 1][py][0][co][q & 1] + bv, g.act);
-                    r.y = apply_act(acc[q >> 1][py][1][co][q & 1] + bv, g.act);
-                    *reinterpret_cast<float2 *>(o + py * ow + 2 * q) = r;
-                }
-        }
-    }
-}
-
-// The same layer with TWO vertically adjacent strips per lane (a 2 x 4 block of input positions -> 4 x 8 output pixels x Cout):
-// a channel's 75 wave-uniform weights now feed 300 packed FMAs per lane instead of 150 -- the scalar loads per FMA halve (the
-// 40 KB of weights do not fit the scalar cache: counters of round 2 showed half of those loads missing) -- and the two strips
-// share two of their four patch rows (24 LDS values per 8 positions instead of 36).  Same FMA order per output as the kernel
-// above: identical results.  Tile = 32 x 64 input positions per workgroup.
-constexpr int kSm2TileH = 32;
-constexpr int kSm2PH = kSm2TileH + 2;
-constexpr int kSm2CK = 2;                                    // input channels per stage
-constexpr int kSm2Chunks = kSm2CK * kSm2PH * kSmDRow;        // 16-byte chunks per stage
-constexpr int kSm2Slots = (kSm2Chunks + 255) / 256;
-constexpr int kSm2Stage = kSm2Slots * 256 * 4;
-
-__global__ __launch_bounds__(256) void deconv5s2_cout3_dma2_kernel(const SmallLaunch g)
-{
-    __shared__ __attribute__((aligned(16))) float buf[2 * kSm2Stage];
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bid = xcd_tile(blockIdx.x, gridDim.x);
-    const int tx_i = bid % g.tiles_x; bid /= g.tiles_x;
-    const int ty_i = bid % g.tiles_y; bid /= g.tiles_y;
-    const int b = bid;
-    const int lxq = tid & 15, ly = tid >> 4;
-    const int my = ty_i * kSm2TileH + 2 * ly, mx0 = tx_i * kSmTileW + 4 * lxq;
-    const int64_t plane = static_cast<int64_t>(g.in_h) * g.in_w;
-    const float *inb = g.in + static_cast<int64_t>(b) * g.cin * plane;
-    const int nstages = (g.cin + kSm2CK - 1) / kSm2CK;
-
-    const float *pp[kSm2Slots];
-    int pstride[kSm2Slots];
-    unsigned lastmask = 0;
-#pragma unroll
-    for (int sl = 0; sl < kSm2Slots; ++sl) {
-        const int k = tid + sl * 256;
-        const float *ptr = basic_zero_page;
-        int stride = 0;
-        if (k < kSm2Chunks) {
-            const int j = k % kSmDRow, r = k / kSmDRow;
-            const int py = r % kSm2PH, ci = r / kSm2PH;
-            const int gy = ty_i * kSm2TileH - 1 + py, gx = tx_i * kSmTileW - 4 + 4 * j;
-            if (gy >= 0 && gy < g.in_h && gx >= 0 && gx < g.in_w && ci < g.cin) {
-                ptr = inb + ci * plane + static_cast<int64_t>(gy) * g.in_w + gx;
-                stride = static_cast<int>(kSm2CK * plane * 4);
-                if ((nstages - 1) * kSm2CK + ci >= g.cin) lastmask |= 1u << sl;
-            }
-        }
-        pp[sl] = ptr;
-        pstride[sl] = stride;
-    }
-#define BASIC_SM2_ISSUE(S)                                                                                     \
-    do {                                                                                                       \
-        if ((S) == nstages - 1 && lastmask) {                                                                  \
-            _Pragma("unroll") for (int sl = 0; sl < kSm2Slots; ++sl)                                           \
-                if ((lastmask >> sl) & 1u) pp[sl] = basic_zero_page;                                           \
-        }                                                                                                      \
-        float *dst_ = buf + ((S) & 1) * kSm2Stage + wave * 256;                                                \
-        _Pragma("unroll") for (int sl = 0; sl < kSm2Slots; ++sl) {                                             \
-            __builtin_amdgcn_global_load_lds((glb_cvoid *)pp[sl], (lds_void *)(dst_ + sl * 1024), 16, 0, 0);   \
-            pp[sl] = reinterpret_cast<const float *>(reinterpret_cast<const char *>(pp[sl]) + pstride[sl]);    \
-        }                                                                                                      \
-    } while (0)
-
-    f32x2 acc[2][2][2][2][3];  // [strip row][pair of strip positions][py][px][co]
-#pragma unroll
-    for (int sr = 0; sr < 2; ++sr)
-#pragma unroll
-        for (int qp = 0; qp < 2; ++qp)
-#pragma unroll
-            for (int py = 0; py < 2; ++py)
-#pragma unroll
-                for (int px = 0; px < 2; ++px)
-#pragma unroll
-                    for (int co = 0; co < 3; ++co) acc[sr][qp][py][px][co] = f32x2{0.f, 0.f};
-
-    BASIC_SM2_ISSUE(0);
-    for (int stg = 0; stg < nstages; ++stg) {
-        __syncthreads();
-        if (stg + 1 < nstages) BASIC_SM2_ISSUE(stg + 1);
-        const float *st = buf + (stg & 1) * kSm2Stage;
-        const int c0 = stg * kSm2CK;
-        const int cmax = (g.cin - c0 < kSm2CK) ? g.cin - c0 : kSm2CK;
-        for (int ci = 0; ci < cmax; ++ci) {
-            // rows 2 ly .. 2 ly + 3 of the patch = rows my - 1 .. my + 2 of the image: strip row sr uses patch rows sr .. sr + 2
-            f32x2 pr[4][5];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const float *row = st + ((ci * kSm2PH + 2 * ly + a) * kSmDRow + lxq) * 4 + 3;
-                const float v0 = row[0], v5 = row[5];
-                const f32x4 mid = *reinterpret_cast<const f32x4 *>(row + 1);
-                pr[a][0] = f32x2{v0, mid[0]};
-                pr[a][1] = f32x2{mid[0], mid[1]};
-                pr[a][2] = f32x2{mid[1], mid[2]};
-                pr[a][3] = f32x2{mid[2], mid[3]};
-                pr[a][4] = f32x2{mid[3], v5};
-            }
-            const cf32x16s *w16 = (const cf32x16s *)(g.wsm + static_cast<int64_t>(c0 + ci) * kSmWRow);
-            const f32x16s w0 = w16[0], w1 = w16[1], w2 = w16[2], w3 = w16[3], w4 = w16[4];
-#pragma unroll
-            for (int ky = 0; ky < 5; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 5; ++kx) {
-                    const int py = ky & 1, px = kx & 1;
-                    const int dy = (py + 2 - ky) / 2, dx = (px + 2 - kx) / 2;
-#pragma unroll
-                    for (int co = 0; co < 3; ++co) {
-                        const int wi = (ky * 5 + kx) * 3 + co;
-                        const float w = wi < 16 ? w0[wi & 15] : wi < 32 ? w1[wi & 15] : wi < 48 ? w2[wi & 15] : wi < 64 ? w3[wi & 15] : w4[wi & 15];
-                        const f32x2 ww = {w, w};
-#pragma unroll
-                        for (int sr = 0; sr < 2; ++sr)
-#pragma unroll
-                            for (int qp = 0; qp < 2; ++qp)
-                                acc[sr][qp][py][px][co] = __builtin_elementwise_fma(pr[sr + dy + 1][2 * qp + dx + 1], ww, acc[sr][qp][py][px][co]);
-                    }
-                }
-        }
-    }
-#undef BASIC_SM2_ISSUE
-    const int oh = 2 * g.in_h, ow = 2 * g.in_w;
-#pragma unroll
-    for (int sr = 0; sr < 2; ++sr) {
-        if (my + sr >= g.in_h) break;
-#pragma unroll
-        for (int co = 0; co < 3; ++co) {
-            if (co >= g.cout) break;
-            const float bv = g.bias[co];
-            float *o = g.out + (static_cast<int64_t>(b) * g.cout + co) * oh * ow + static_cast<int64_t>(2 * (my + sr)) * ow + 2 * mx0;
-#pragma unroll
-            for (int py = 0; py < 2; ++py)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (mx0 + q >= g.in_w) break;
-                    float2 r;
-                    r.x = apply_act(acc[sr][q >> 1][py][0][co][q & 1] + bv, g.act);
-                    r.y = apply_act(acc[sr][q >> 1][py][1][co][q & 1] + bv, g.act);
-                    *reinterpret_cast<float2 *>(o + py * ow + 2 * q) = r;
-                }
-        }
-    }
+    sm_store<STRIPS>(acc, g, b, my, mx0);
 }
 
 struct Phase {
@@ -1928,6 +1852,52 @@ LaunchChoice choose_launches(const basic_conv_plan *p, int batch, int oh, int ow
     c.split_patch = !(dbg & 1024);
     return c;
 }
+
+// The launches of one forward call: the chosen chunk list x the chosen phase list, without the phases whose m-grid (the
+// output positions oy0 + s_out * my, ox0 + s_out * mx) is empty.  fn(chunk, phase, mh, mw) returns BASIC_OK to go on.
+template <class F>
+int for_each_launch(const basic_conv_plan *p, const LaunchChoice &c, int oh, int ow, F &&fn)
+{
+    for (const Chunk &ch : (c.use_split ? p->split : p->chunks))
+        for (const Phase &ph : ((c.fuse_ok && !ch.fused.empty()) ? ch.fused : ch.phases)) {
+            const int mh = (oh - ph.oy0 + p->s_out - 1) / p->s_out, mw = (ow - ph.ox0 + p->s_out - 1) / p->s_out;
+            if (mh <= 0 || mw <= 0) continue;
+            const int rc = fn(ch, ph, mh, mw);
+            if (rc) return rc;
+        }
+    return BASIC_OK;
+}
+
+// tile shape: tile_pos positions = TB images x TH x TW, powers of two, preferring wide rows
+struct TileShape { int tw, th, tb; };
+TileShape tile_shape(int mh, int mw, int tile_pos)
+{
+    TileShape t;
+    t.tw = pow2_ceil(mw); if (t.tw > 16) t.tw = 16;
+    t.th = pow2_ceil(mh); if (t.th > tile_pos / t.tw) t.th = tile_pos / t.tw;
+    t.tb = tile_pos / (t.tw * t.th);
+    return t;
+}
+
+// The Cout <= 3 output layer, one launch: LDS-DMA staging where every 16-byte chunk of an input row is whole and aligned,
+// with two strips per lane from 64 rows up (measured in round 4); plain staging otherwise.
+int launch_small_deconv(const basic_conv_plan *p, const float *d_in, int batch, int in_h, int in_w, float *d_out, hipStream_t st)
+{
+    SmallLaunch g{};
+    g.in = d_in; g.out = d_out; g.wsm = p->d_wsm; g.bias = p->d_bias4;
+    g.batch = batch; g.cin = p->cin; g.cout = p->cout; g.in_h = in_h; g.in_w = in_w; g.act = p->act;
+    const bool dma_ok = in_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0;
+    const bool two_strips = dma_ok && in_h >= 64;
+    const int tile_h = two_strips ? SmTile<2>::kTileH : SmTile<1>::kTileH;
+    g.tiles_y = (in_h + tile_h - 1) / tile_h;
+    g.tiles_x = (in_w + kSmTileW - 1) / kSmTileW;
+    const dim3 grid(batch * g.tiles_y * g.tiles_x);
+    if (two_strips) hipLaunchKernelGGL(deconv5s2_cout3_dma_kernel<2>, grid, dim3(256), 0, st, g);
+    else if (dma_ok) hipLaunchKernelGGL(deconv5s2_cout3_dma_kernel<1>, grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(deconv5s2_cout3_kernel, grid, dim3(256), 0, st, g);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
 }  // namespace
 
 extern "C" int basic_conv_plan_launches(const basic_conv_plan *p, int batch, int in_h, int in_w)
@@ -1935,13 +1905,8 @@ extern "C" int basic_conv_plan_launches(const basic_conv_plan *p, int batch, int
     int oh = 0, ow = 0;
     if (!p || batch < 1 || basic_conv_plan_out_hw(p, in_h, in_w, &oh, &ow)) return -1;
     if (p->d_wsm) return 1;
-    const LaunchChoice c = choose_launches(p, batch, oh, ow, nullptr);
     int n = 0;
-    for (const Chunk &ch : (c.use_split ? p->split : p->chunks))
-        for (const Phase &ph : ((c.fuse_ok && !ch.fused.empty()) ? ch.fused : ch.phases)) {
-            const int mh = (oh - ph.oy0 + p->s_out - 1) / p->s_out, mw = (ow - ph.ox0 + p->s_out - 1) / p->s_out;
-            if (mh > 0 && mw > 0) ++n;
-        }
+    for_each_launch(p, choose_launches(p, batch, oh, ow, nullptr), oh, ow, [&](const Chunk &, const Phase &, int, int) { ++n; return BASIC_OK; });
     return n;
 }
 
@@ -1952,38 +1917,17 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
     int oh = 0, ow = 0;
     int rc = basic_conv_plan_out_hw(p, in_h, in_w, &oh, &ow);
     if (rc) return rc;
-    if (p->d_wsm) {
-        SmallLaunch g{};
-        g.in = d_in; g.out = d_out; g.wsm = p->d_wsm; g.bias = p->d_bias4;
-        g.batch = batch; g.cin = p->cin; g.cout = p->cout; g.in_h = in_h; g.in_w = in_w; g.act = p->act;
-        g.tiles_y = (in_h + kSmTileH - 1) / kSmTileH;
-        g.tiles_x = (in_w + kSmTileW - 1) / kSmTileW;
-        const int blocks = batch * g.tiles_y * g.tiles_x;
-        const bool dma_ok = in_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0;
-        if (dma_ok && in_h >= 64) {   // two strips per lane
-            g.tiles_y = (in_h + kSm2TileH - 1) / kSm2TileH;
-            hipLaunchKernelGGL(deconv5s2_cout3_dma2_kernel, dim3(batch * g.tiles_y * g.tiles_x), dim3(256), 0, as_stream(hip_stream), g);
-        } else if (dma_ok)
-            hipLaunchKernelGGL(deconv5s2_cout3_dma_kernel, dim3(blocks), dim3(256), 0, as_stream(hip_stream), g);
-        else
-            hipLaunchKernelGGL(deconv5s2_cout3_kernel, dim3(blocks), dim3(256), 0, as_stream(hip_stream), g);
-        BASIC_HIP_TRY(hipGetLastError());
-        return BASIC_OK;
-    }
+    if (p->d_wsm) return launch_small_deconv(p, d_in, batch, in_h, in_w, d_out, as_stream(hip_stream));
     // small position grids: spread the output channels over gridDim.y instead of looping them inside a block;
     // fused column phases: even output width (both phases have the same m-grid) and 8-byte aligned rows for the pair stores
     const LaunchChoice choice = choose_launches(p, batch, oh, ow, d_out);
-    const bool use_split = choice.use_split, fuse_ok = choice.fuse_ok;
-    for (const Chunk &ch : (use_split ? p->split : p->chunks))
-    for (const Phase &ph : ((fuse_ok && !ch.fused.empty()) ? ch.fused : ch.phases)) {
+    return for_each_launch(p, choice, oh, ow, [&](const Chunk &ch, const Phase &ph, int mh, int mw) -> int {
         TapLaunch g{};
         g.in = d_in; g.out = d_out; g.wpack = ph.d_wpack; g.wrow = ph.d_wrow; g.split_wstride = ph.split_wstride; g.bias = ch.d_bias; g.gammaT = p->d_gammaT; g.beta = p->d_beta;
         g.batch = batch; g.cin = p->cin; g.cin_pad = ph.ntaps ? ph.cin_pad : 0; g.cout = ch.cout; g.coutp = ch.coutp; g.out_ctotal = p->cout; g.co_base = ch.co0;
         g.in_h = in_h; g.in_w = in_w; g.out_h = oh; g.out_w = ow;
         g.s_in = p->s_in; g.s_out = p->s_out; g.oy0 = ph.oy0; g.ox0 = ph.ox0;
-        g.mh = (oh - ph.oy0 + p->s_out - 1) / p->s_out;
-        g.mw = (ow - ph.ox0 + p->s_out - 1) / p->s_out;
-        if (g.mh <= 0 || g.mw <= 0) continue;
+        g.mh = mh; g.mw = mw;
         g.ntaps = ph.ntaps; g.dymin = ph.dymin; g.dxmin = ph.dxmin;
         std::memcpy(g.dy, ph.dy, sizeof(g.dy));
         std::memcpy(g.dx, ph.dx, sizeof(g.dx));
@@ -1991,9 +1935,8 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
         const int kCK = ph.ck;
         if (choice.bf16x3 && ph.d_wsplit) {
             // split-bf16 path: 256 positions per workgroup, weights through LDS, activations by buffer loads
-            int tw = pow2_ceil(g.mw); if (tw > 16) tw = 16;
-            int th = pow2_ceil(g.mh); if (th > kSplitWaves * 32 / tw) th = kSplitWaves * 32 / tw;
-            const int tb = kSplitWaves * 32 / (tw * th);
+            const TileShape ts = tile_shape(g.mh, g.mw, kSplitWaves * 32);
+            const int tw = ts.tw, th = ts.th, tb = ts.tb;
             if (static_cast<int64_t>(tb) * p->cin * in_h * in_w * 4 < (1ll << 31)) {  // one buffer resource per tile's images
                 g.tw_log = ilog2(tw); g.th_log = ilog2(th); g.tb_log = ilog2(tb);
                 g.tiles_y = (g.mh + th - 1) / th;
@@ -2007,14 +1950,13 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
                 const hipError_t e = ph.kh == 3 ? (patch ? launch_split<3, true>(g, ws, blocks, st) : launch_split<3, false>(g, ws, blocks, st))
                                                 : (patch ? launch_split<2, true>(g, ws, blocks, st) : launch_split<2, false>(g, ws, blocks, st));
                 BASIC_HIP_TRY(e);
-                continue;
+                return BASIC_OK;
             }
         }
-        // tile shape: 128 positions = TB images x TH x TW, powers of two, preferring wide rows
-        int tw = pow2_ceil(g.mw); if (tw > 16) tw = 16;
         const int threads = 64 * ph.waves, tile_pos = 32 * ph.waves;  // one position per half-wave lane
-        int th = pow2_ceil(g.mh); if (th > tile_pos / tw) th = tile_pos / tw;
-        int tb = tile_pos / (tw * th);
+        const TileShape ts = tile_shape(g.mh, g.mw, tile_pos);
+        const int tw = ts.tw, th = ts.th;
+        int tb = ts.tb;
         const bool first_layer_path = ch.mt == 4 && ch.nsplit == 1 && ph.waves == 8 && ph.kh == 5 && ph.kw == 5 &&
                                       ph.cin_pad == kCK && kCK == 4 && ch.cout == 128 && p->d_gammaT;
         g.ph = (th - 1) * g.s_in + ph.span_y;
@@ -2070,7 +2012,7 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
                 if (rows) hipLaunchKernelGGL(conv5x5_cin4_gdn_persistent_kernel<true>, dim3(grid), dim3(512), lds1, st, g, blocks, sched);
                 else hipLaunchKernelGGL(conv5x5_cin4_gdn_persistent_kernel<false>, dim3(grid), dim3(512), lds1, st, g, blocks, sched);
                 BASIC_HIP_TRY(hipGetLastError());
-                continue;
+                return BASIC_OK;
             }
         }
         if (ph.kwb) {
@@ -2081,8 +2023,7 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
                 case 4: rc = launch_fused<4>(g, ph.kh, ph.kw, ph.kwb, ph.ck, ph.waves, blocks, ch.nsplit, lds_bytes, st); break;
                 default: set_error("conv_forward: fused phases need <= 4 accumulator tiles"); rc = BASIC_ERR_INVALID;
             }
-            if (rc) return rc;
-            continue;
+            return rc;
         }
         switch (ch.mt) {
             case 1: rc = launch_mt<1>(g, ph.kh, ph.kw, ph.ck, ph.waves, blocks, ch.nsplit, lds_bytes, st); break;
@@ -2093,7 +2034,6 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
             case 6: rc = launch_mt<6>(g, ph.kh, ph.kw, ph.ck, ph.waves, blocks, ch.nsplit, lds_bytes, st); break;
             default: set_error("conv_forward: cout > 192 unsupported"); rc = BASIC_ERR_INVALID;
         }
-        if (rc) return rc;
-    }
-    return BASIC_OK;
+        return rc;
+    });
 }

@@ -19,10 +19,10 @@ Launch paths (basic_conv_forward_dev / choose_launches) and the PATHS cases belo
   chunked cout > 192                            balanced chunks rounded to whole M-tiles                  test_chunks_and_slices (193, 200, 257, 400)
   conv5x5_cin4_gdn_persistent_kernel<true>      5x5 GDN conv, 128 channels, cin 1..3                      first_cin1, first_cin3
   conv5x5_cin4_gdn_persistent_kernel<false>     ... cin 4                                                 first_cin4
-  deconv5s2_cout3_kernel                        k5 s2 p2 op1 transposed, cout <= 3, no GDN, input not     cout3_plain (in_w % 4 != 0), guard runs at
-                                                16-byte aligned or in_w % 4 != 0                          input offsets 1 and 2
-  deconv5s2_cout3_dma_kernel                    ... in_w % 4 == 0, 16-byte aligned input, in_h < 64       cout3_dma
-  deconv5s2_cout3_dma2_kernel                   ... and in_h >= 64                                        cout3_dma2
+  deconv5s2_cout3_kernel                        k5 s2 p2 op1 transposed, cout <= 3, no GDN, input not     cout3_plain, cout3_plain_ragged (in_w % 4 != 0),
+                                                16-byte aligned or in_w % 4 != 0                          guard runs at input offsets 1 and 2
+  deconv5s2_cout3_dma_kernel<1>                 ... in_w % 4 == 0, 16-byte aligned input, in_h < 64       cout3_dma, cout3_dma_ragged
+  deconv5s2_cout3_dma_kernel<2>                 ... and in_h >= 64 (two strips per lane)                  cout3_dma2, cout3_dma2_ragged
   conv_split_bf16_kernel<3,3,2> and <2,3,2>     fused IGDN launch, 97..128 channels, cin % 16 == 0 (the   split_* and SPLIT_CASES (both instantiations
                                                 two row phases of one layer)                              run in every such layer)
 
@@ -83,6 +83,11 @@ PATHS = {
     "cout3_plain": Case(40, 3, 5, 2, 2, 1, True, "leaky", 2, 9, 13, "", 1),
     "cout3_dma": Case(24, 2, 5, 2, 2, 1, True, "relu", 1, 20, 16, "", 1),
     "cout3_dma2": Case(8, 1, 5, 2, 2, 1, True, "none", 1, 66, 12, "", 1),
+    # ragged last channel stage, partial row and column tiles, every output channel
+    "cout3_dma_ragged": Case(5, 3, 5, 2, 2, 1, True, "leaky", 1, 17, 68, "", 1),
+    # ... odd height (a lane's second strip out of range), 18 workgroups (xcd_tile remaps 16 and passes 2 through)
+    "cout3_dma2_ragged": Case(3, 3, 5, 2, 2, 1, True, "relu", 3, 65, 68, "", 1),
+    "cout3_plain_ragged": Case(9, 2, 5, 2, 2, 1, True, "none", 1, 17, 66, "", 1),   # 2 x 2 tiles, ragged second stage
     "split_cin192": Case(192, 128, 5, 2, 2, 1, True, "igdn", 1, 8, 12, "", 2),
     "split_ragged": Case(48, 100, 5, 2, 2, 1, True, "igdn", 3, 3, 5, "", 2),
 }
@@ -281,7 +286,8 @@ def test_path_gdn_real_gamma(name, monkeypatch):
 # 4: guard bands and alignment
 
 GUARDED = ["mt1_k3", "mt4_k5_gdn_8w", "mt6_k5", "bias_only_k1s2", "fused_mt2", "fused_mt4_fp32", "slices_tr_70",
-           "first_cin3", "first_cin4", "cout3_plain", "cout3_dma", "cout3_dma2", "split_cin192", "split_ragged"]
+           "first_cin3", "first_cin4", "cout3_plain", "cout3_dma", "cout3_dma2", "cout3_dma_ragged", "cout3_dma2_ragged",
+           "split_cin192", "split_ragged"]
 BAND = 256  # floats of guard band on each side of a view
 
 
@@ -338,8 +344,9 @@ def test_guard_bands_exact(name, monkeypatch):
 @pytest.mark.parametrize("name", GUARDED)
 def test_guard_bands_randn(name, monkeypatch):
     """randn data: aligned views give the plain run bit for bit; misaligned inputs (4-byte patch pieces, the plain
-    cout <= 3 kernel) meet the fp64 bound; a 4-byte misaligned output takes the four-phase fallback, which gives the
-    BASIC_CONV_DEBUG=512 run bit for bit."""
+    cout <= 3 kernel) meet the fp64 bound, and the plain cout <= 3 kernel gives the LDS-DMA kernels' result bit for
+    bit (the same FMA chain per output in all three kernels); a 4-byte misaligned output takes the four-phase
+    fallback, which gives the BASIC_CONV_DEBUG=512 run bit for bit."""
     c = PATHS[name]
     x, w, b, gamma, beta = _layer(c, False, _seed(name, "randn"))
     plan = _plan(c, w, b, gamma, beta)
@@ -347,7 +354,10 @@ def test_guard_bands_randn(name, monkeypatch):
     plain = _run(plan, x, monkeypatch, c.debug)
     assert torch.equal(_guarded_run(plan, c, x, 64, 64, monkeypatch, c.debug), plain)
     for in_off in (1, 2):
-        _check_bound(c, _guarded_run(plan, c, x, in_off, 64, monkeypatch, c.debug), lin, A, f"{name} in+{in_off}")
+        got = _guarded_run(plan, c, x, in_off, 64, monkeypatch, c.debug)
+        _check_bound(c, got, lin, A, f"{name} in+{in_off}")
+        if c.cout <= 3:   # the plain kernel: the same FMA chain per output as the LDS-DMA kernels
+            assert torch.equal(got, plain), f"{name} in+{in_off}: the plain kernel's result differs from the aligned run's"
     if c.cout > 3:
         got = _guarded_run(plan, c, x, 64, 1, monkeypatch, c.debug)
         _check_bound(c, got, lin, A, f"{name} out+1")
