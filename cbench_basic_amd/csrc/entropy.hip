@@ -99,6 +99,25 @@ __global__ void i32_to_f32_kernel(const int32_t *__restrict__ in, int64_t n, flo
         out[i] = static_cast<float>(in[i]);
 }
 
+// lane streams of the scan-line coder: both arrays from coding order [B][P][K][L] to one run per lane stream, [B][K][P][L].
+// A thread owns an output element: stores are contiguous, loads contiguous in runs of L (>= 16 elements, 64 bytes).
+__global__ void lanes_pack_kernel(const int32_t *__restrict__ sym, const int32_t *__restrict__ idx, int64_t total, int positions,
+                                  int lanes, int width, int32_t *__restrict__ sym_out, int32_t *__restrict__ idx_out)
+{
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
+         i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int64_t run = i / width;   // (b * K + k) * P + p
+        const int l = static_cast<int>(i - run * width);
+        const int64_t bk = run / positions;
+        const int p = static_cast<int>(run - bk * positions);
+        const int64_t b = bk / lanes;
+        const int k = static_cast<int>(bk - b * lanes);
+        const int64_t src = ((b * positions + p) * lanes + k) * width + l;
+        sym_out[i] = sym[src];
+        idx_out[i] = idx[src];
+    }
+}
+
 // argmin_j |s - table[j]|, first minimum (torch.argmin on CPU returns the first occurrence).
 __device__ __forceinline__ int nearest_scale(float s, const float *tab, int n)
 {
@@ -314,6 +333,19 @@ extern "C" int basic_i32_to_f32_dev(const int32_t *d_in, int64_t n, float *d_out
     BASIC_REQUIRE(d_in && d_out && n >= 0, "i32_to_f32: bad argument");
     if (n == 0) return BASIC_OK;
     hipLaunchKernelGGL(i32_to_f32_kernel, dim3(grid_for(n)), dim3(kBlock), 0, as_stream(hip_stream), d_in, n, d_out);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_lanes_pack_dev(const int32_t *d_sym, const int32_t *d_idx, int batch, int positions, int channels, int lanes,
+                                    int32_t *d_sym_out, int32_t *d_idx_out, void *hip_stream)
+{
+    BASIC_REQUIRE(d_sym && d_idx && d_sym_out && d_idx_out && batch >= 1 && positions >= 1 && channels >= 1 && lanes >= 1 &&
+                      channels % lanes == 0 && d_sym_out != d_sym && d_idx_out != d_idx,
+                  "lanes_pack: bad argument");
+    const int64_t total = static_cast<int64_t>(batch) * positions * channels;
+    hipLaunchKernelGGL(lanes_pack_kernel, dim3(grid_for(total)), dim3(kBlock), 0, as_stream(hip_stream), d_sym, d_idx, total, positions,
+                       lanes, channels / lanes, d_sym_out, d_idx_out);
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
 }

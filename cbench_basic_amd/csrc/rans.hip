@@ -384,8 +384,18 @@ struct TablesDev {
     const int2 *rowinfo;     // [rows] (offset, max_value)
 };
 
-// Alternative to a seg[] array: stream b codes the elements [first + b*stride, first + b*stride + count).
-struct StridedSeg { int64_t first, stride, count; };
+// Alternative to a seg[] array: stream b codes the elements [first + b*stride, first + b*stride + count).  With `lanes` > 1
+// (lane streams of the scan-line coder) stream s = b*lanes + k codes the `count` elements from first + b*stride + k*count on.
+struct StridedSeg {
+    int64_t first, stride, count;
+    int lanes = 1;
+    __device__ __forceinline__ int64_t begin(int stream) const
+    {
+        if (lanes == 1) return first + stream * stride;
+        const int b = stream / lanes;
+        return first + b * stride + (stream - b * lanes) * count;
+    }
+};
 
 struct ArDev {
     const int32_t *tab;  // nullptr = no AR remap
@@ -831,7 +841,7 @@ __global__ __launch_bounds__(64) void rans_decode_kernel(TablesDev T, ArDev ar, 
     const uint16_t *lds16 = reinterpret_cast<const uint16_t *>(lds_words);
     const int stream = blockIdx.x;
     const int lane = threadIdx.x;
-    const int64_t beg = seg ? seg[stream] : ss.first + stream * ss.stride;
+    const int64_t beg = seg ? seg[stream] : ss.begin(stream);
     const int64_t n = seg ? seg[stream + 1] - beg : ss.count;
     const int32_t *idx = indexes + beg;
     int32_t *out = out_symbols + beg;
@@ -986,7 +996,7 @@ __global__ __launch_bounds__(64 * WPB) void rans_decode_fast_kernel(TablesDev T,
     const int stream_raw = blockIdx.x * WPB + (WPB > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0);
     const bool live = stream_raw < nstreams;           // a surplus wave of the last workgroup only helps to copy the image
     const int stream = live ? stream_raw : nstreams - 1;
-    const int64_t beg = seg ? seg[stream] : ss.first + stream * ss.stride;
+    const int64_t beg = seg ? seg[stream] : ss.begin(stream);
     const int n = static_cast<int>(seg ? seg[stream + 1] - beg : ss.count);
     const int32_t *idx = indexes + beg;
     int32_t *out = out_symbols + beg;
@@ -1305,6 +1315,24 @@ extern "C" int basic_rans_decode_batch_strided_dev(const basic_rans_tables *t, c
     ArDev ar{};
     return launch_decode(t, ar, nstreams, as_stream(hip_stream), d_words, d_word_off, d_indexes, nullptr, d_out_symbols, d_state,
                          d_pos, StridedSeg{first, stride, count});
+}
+
+// The same step for lane streams (scan-line coder, stream_lanes = `lanes`): `nimages * lanes` streams, stream s = b * lanes + k
+// continues with the `count` symbols at first + b * stride + k * count.  lanes == 1 is basic_rans_decode_batch_strided_dev.
+extern "C" int basic_rans_decode_batch_lanes_dev(const basic_rans_tables *t, const uint32_t *d_words, const int64_t *d_word_off,
+                                                 const int32_t *d_indexes, int64_t first, int64_t stride, int lanes, int64_t count,
+                                                 int nimages, int32_t *d_out_symbols, uint64_t *d_state, int64_t *d_pos,
+                                                 void *hip_stream)
+{
+    if (!t) { set_error("ANS not initialized!"); return BASIC_ERR_NOT_INIT; }
+    BASIC_REQUIRE(d_words && d_word_off && d_indexes && d_out_symbols && d_state && d_pos && nimages >= 1 && lanes >= 1 && first >= 0 &&
+                      stride >= 0 && count >= 0 && static_cast<int64_t>(nimages) * lanes < (1ll << 31),
+                  "rans_decode_batch_lanes: bad argument");
+    BASIC_REQUIRE(!t->d_ar, "rans_decode_batch_lanes: AR tables are only supported by the host-buffer entry points");
+    if (count == 0) return BASIC_OK;
+    ArDev ar{};
+    return launch_decode(t, ar, nimages * lanes, as_stream(hip_stream), d_words, d_word_off, d_indexes, nullptr, d_out_symbols, d_state,
+                         d_pos, StridedSeg{first, stride, count, lanes});
 }
 
 // ---------------------------------------------------------------------------------------

@@ -75,7 +75,7 @@ struct ScanArgs {
     int tap_off[kMaxTaps], tap_dy[kMaxTaps], tap_dx[kMaxTaps];
     int bc, xs_off, ps_off, tab_off, part_off, part_floats, flag_off, bias_off;   // LDS float offsets (the whole LDS is dynamic)
     int x0_off, early_off, desc_off;   // pipelined kernel only: context window [B][K0], early sums, unit descriptors
-    int ncompute;          // workgroups [0, ncompute) compute, the rest decode (4 image streams each)
+    int ncompute;          // workgroups [0, ncompute) compute, the rest decode (4 streams each)
     unsigned *bar;
     int *err;
     long long *prof;   // BASIC_SCAN_PROFILE=1: [layer][4] 100 MHz ticks of workgroup 0 spent staging (incl. waiting) / in the block dots / finishing / in the
@@ -85,7 +85,8 @@ struct ScanArgs {
     uint64_t *idx_step;    // [B][C] table rows of the current step, granules (the row's bits in the value half)
     RansFastView tv;
     const uint32_t *words; // all streams back to back
-    const int64_t *word_off;   // [B + 1]
+    const int64_t *word_off;   // [B * lanes + 1]
+    int lanes, lane_w;     // lane streams per image (stream b * lanes + k: channels [k * lane_w, (k + 1) * lane_w)); lanes * lane_w == C
     // batched kernel only (scanline_batched_kernel; nbt == 0 for the other two): the batch is the fastest dimension of every
     // exchanged array -- yT [HW][C][nbt], act[l] [rows_l][nbt], priorT [HW][P][nbt]; mu / idx_step stay [image][C]
     int nbt;               // columns of the exchange arrays: 32 * column tiles (a column tile = 32 images = the N of an MFMA tile)
@@ -283,8 +284,15 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 using wavedec::static_pairs;
 using wavedec::WaveDecoder;   // the serial rANS chain of one stream (wave_decoder.h)
 
-// ================= decoder workgroups: one wavefront per image stream, the search image in LDS =================
-__device__ __forceinline__ void decoder_workgroup(const ScanArgs &a, float *lds)
+// ================= decoder workgroups: one wavefront per stream, the search image in LDS =================
+// An image is one stream, or -- the lane-stream format, a.lanes > 1 -- a.lanes of them: stream b * lanes + k carries the symbols of
+// channels [k * lane_w, (k + 1) * lane_w) in coding order, so the waves of an image's lanes decode a position side by side, each
+// fetching its own channels' (row, mean) granules and publishing at its own channels.  lane_w is a multiple of 16: the batched
+// exchange layout stays linear in a chunk's first channel (multiples of 4), and a chunk's stores stay whole 64-byte runs.
+// LANES = false is the one-stream loop with its bounds as they always were (stream = image, channels [0, C)): a call without
+// lanes runs the code it ran before the format existed.
+template <bool LANES>
+__device__ __forceinline__ void decoder_loop(const ScanArgs &a, float *lds)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wg = blockIdx.x;
@@ -296,13 +304,15 @@ __device__ __forceinline__ void decoder_workgroup(const ScanArgs &a, float *lds)
     for (int r = tid; r < a.tv.rows; r += kThreads)
         rowtab[r] = u32x4{a.tv.meta[r], static_cast<uint32_t>(a.tv.sizes[r]), static_cast<uint32_t>(a.tv.offsets[r]), 0u};
     __syncthreads();
-    const int b = (wg - a.ncompute) * (kThreads / 64) + wave;
-    if (b >= a.B) return;
+    const int s = (wg - a.ncompute) * (kThreads / 64) + wave;
+    if (s >= (LANES ? a.B * a.lanes : a.B)) return;
+    const int b = LANES ? s / a.lanes : s;
+    const int cbeg = LANES ? (s - b * a.lanes) * a.lane_w : 0, cend = LANES ? cbeg + a.lane_w : a.C;   // this stream's channels
     __builtin_amdgcn_s_setprio(3);   // a serial chain: never lose the issue arbitration to the waves spinning beside it
     WaveDecoder d;
     {
-        const int64_t w0 = a.word_off[b];
-        d.init(img, a.words + w0, static_cast<int>(a.word_off[b + 1] - w0), a.tv.precision, a.tv.bypass_precision, a.tv.bypass != 0, -1, 0ull, lane);
+        const int64_t w0 = a.word_off[s];
+        d.init(img, a.words + w0, static_cast<int>(a.word_off[s + 1] - w0), a.tv.precision, a.tv.bypass_precision, a.tv.bypass != 0, -1, 0ull, lane);
     }
     const uint64_t *pi0 = a.idx_step + static_cast<int64_t>(b) * a.C, *pm0 = a.mu + static_cast<int64_t>(b) * a.C;
     // where a chunk's results go: a uniform pointer per (step, chunk) + a lane term that never changes (channel c0 + lane; the
@@ -315,26 +325,26 @@ __device__ __forceinline__ void decoder_workgroup(const ScanArgs &a, float *lds)
         // this step's (table row, mean) granules come from the compute workgroups that own the channels; the next chunk's
         // are requested before the current chunk is decoded
         uint64_t gi = 0ull, gm = 0ull;
-        if (lane < a.C) { gi = ld_gran(pi0 + lane); gm = ld_gran(pm0 + lane); }
-        for (int c0 = 0; c0 < a.C; c0 += 64) {
+        if (cbeg + lane < cend) { gi = ld_gran(pi0 + cbeg + lane); gm = ld_gran(pm0 + cbeg + lane); }
+        for (int c0 = cbeg; c0 < cend; c0 += 64) {
             const int c = c0 + lane;
             bool ok = true;
             d.line_up(lane);   // the chunk's 64 stream words, cut while the step's parameters are still on their way
             const long long tw0 = a.prof ? wall_clock64() : 0;
-            if (c < a.C) ok = wait_gran(a, pi0 + c, tag, gi) && wait_gran(a, pm0 + c, tag, gm);
+            if (c < cend) ok = wait_gran(a, pi0 + c, tag, gi) && wait_gran(a, pm0 + c, tag, gm);
             if (__ballot(!ok) != 0ull) return;   // poisoned launch: wave-uniform exit
             const long long tw1 = a.prof ? wall_clock64() : 0;
             int32_t row = static_cast<int32_t>(static_cast<uint32_t>(gi));
             const float mu = __uint_as_float(static_cast<uint32_t>(gm));
             gi = 0ull; gm = 0ull;
-            if (c + 64 < a.C) { gi = ld_gran(pi0 + c + 64); gm = ld_gran(pm0 + c + 64); }
+            if (c + 64 < cend) { gi = ld_gran(pi0 + c + 64); gm = ld_gran(pm0 + c + 64); }
             row = row < 0 ? 0 : (row >= a.tv.rows ? a.tv.rows - 1 : row);
             const u32x4 rt = rowtab[row];
-            const int cnt = (a.C - c0) < 64 ? (a.C - c0) : 64;
+            const int cnt = (cend - c0) < 64 ? (cend - c0) : 64;
             const long long tc2 = a.prof ? clock64() : 0;
             const int32_t mine = d.decode_chunk(rt[0], static_cast<int32_t>(rt[1]), cnt, lane) - 1;
             const long long tc3 = a.prof ? clock64() : 0;
-            if (c < a.C) {
+            if (c < cend) {
                 const int32_t value = mine + static_cast<int32_t>(rt[2]);
                 const float v = static_cast<float>(value) + mu;           // pgm_coder.py:973-978
                 const int64_t at = bC * HW + static_cast<int64_t>(p) * a.C + c0;   // [b][p][c0] of sym / idx
@@ -346,7 +356,7 @@ __device__ __forceinline__ void decoder_workgroup(const ScanArgs &a, float *lds)
             }
             if (a.prof) {   // first stream: ticks waiting for the step's parameters / decoding and publishing
                 const long long tc4 = clock64(), tw4 = wall_clock64();   // (read before the slots are touched: their updates wait for memory)
-                if (b == 0 && lane == 0) {
+                if (s == 0 && lane == 0) {
                     a.prof[4 * kMaxLayers + 2] += tw1 - tw0;
                     a.prof[4 * kMaxLayers + 3] += tw4 - tw1;
                     a.prof[4 * kMaxLayers + 4] += tc3 - tc2;            // shader clocks inside decode_chunk
@@ -356,6 +366,12 @@ __device__ __forceinline__ void decoder_workgroup(const ScanArgs &a, float *lds)
             }
         }
     }
+}
+
+__device__ __forceinline__ void decoder_workgroup(const ScanArgs &a, float *lds)
+{
+    if (a.lanes > 1) decoder_loop<true>(a, lds);
+    else decoder_loop<false>(a, lds);
 }
 
 template <bool DECODE>
@@ -2011,8 +2027,8 @@ int lane_lds(const basic_scanline_plan *p, int batch, int w, int table_len, Scan
 // ---- batched kernel: when it serves a call
 constexpr int kBatchedMaxTiles = 2;   // column tiles of 32 images per launch
 
-// decoder workgroups of `batch` image streams (one wavefront per stream)
-int decoder_workgroups(int batch) { return (batch + kThreads / 64 - 1) / (kThreads / 64); }
+// decoder workgroups of `streams` streams (one wavefront per stream; a decode call has batch * lanes of them)
+int decoder_workgroups(int streams) { return (streams + kThreads / 64 - 1) / (kThreads / 64); }
 
 // LDS of a decoder workgroup: the fast search image of the table set
 size_t decoder_lds_bytes(const RansFastView &tv)
@@ -2030,10 +2046,10 @@ bool batched_fits(const basic_scanline_plan *p, int batch, int w, int ndec, int 
 }
 
 // basic_scanline_batched_max: the largest whole number of column tiles that fits, in images
-int batched_max_batch(const basic_scanline_plan *p, int w, bool decode, int cus)
+int batched_max_batch(const basic_scanline_plan *p, int w, bool decode, int cus, int lanes = 1)
 {
     for (int b = 32 * kBatchedMaxTiles; b >= 1; b -= 32)
-        if (batched_fits(p, b, w, decode ? decoder_workgroups(b) : 0, cus)) return b;
+        if (batched_fits(p, b, w, decode ? decoder_workgroups(b * lanes) : 0, cus)) return b;
     return 0;
 }
 
@@ -2151,6 +2167,7 @@ bool lane_grid_resident(const basic_scanline_plan *p, int ndec, int cus) { retur
 // ---- The planner: the one place that decides how a scan-line call runs.  Pure: it asks nothing of the device or the environment.
 struct ScanRequest {
     int batch = 1, h = 0, w = 0;     // h or w < 1: not known -- no kernel of the batched family is considered then
+    int lanes = 1;                   // decode: lane streams per image (a decoder wavefront each); encode launches do not depend on it
     int table_len = 1;
     bool decode = false;
     bool fast_image = false;         // decode: the table set has a fast search image ...
@@ -2193,7 +2210,7 @@ int plan_scan(const basic_scanline_plan *p, const ScanRequest &q, ScanLaunch *L)
     L->cus = q.cus;
     const bool decode = q.decode;
     const int batch = q.batch, h = q.h, w = q.w, cus = q.cus;
-    const int ndec = decode ? decoder_workgroups(batch) : 0;
+    const int ndec = decode ? decoder_workgroups(batch * q.lanes) : 0;
     int schedule = q.schedule;
     ScanKernel force = q.force;
     if (decode && force != ScanKernel::kNone && !row_of(force, true).fn) force = ScanKernel::kNone;   // encode only: a decode call ignores it
@@ -2204,7 +2221,7 @@ int plan_scan(const basic_scanline_plan *p, const ScanRequest &q, ScanLaunch *L)
         if (decode && !q.fast_image) return BASIC_OK;
         // a forced band serves any batch: the call is cut into launches over whole images
         const bool band_asked = !decode && schedule == BASIC_SCAN_SCHEDULE_BAND && band_images() >= 1;
-        if (!band_asked && batch > q.lane_max_batch && batch > batched_max_batch(p, w, decode, cus)) {
+        if (!band_asked && batch > q.lane_max_batch && batch > batched_max_batch(p, w, decode, cus, q.lanes)) {
             // no raster kernel serves this batch; an encode call may still run as a wavefront (a narrow latent, for one), or, in
             // auto, as a band where that beats the per-step path.  (kept as it is: a forced wavefront that does not fit is not
             // refused here but left to the per-step path)
@@ -2272,12 +2289,13 @@ int make_request(const basic_rans_tables *tables, int batch, int h, int w, int t
 }
 
 // Plans a *_dev call: the plan's encode schedule, no coder gates; `tables` != nullptr: decode
-int prepare_launch(const basic_scanline_plan *p, int batch, int h, int w, int table_len, const basic_rans_tables *tables, RansFastView *tv,
+int prepare_launch(const basic_scanline_plan *p, int batch, int lanes, int h, int w, int table_len, const basic_rans_tables *tables, RansFastView *tv,
                    ScanLaunch *L)
 {
     ScanRequest q;
     const int rc = make_request(tables, batch, h, w, table_len, p->encode_schedule, -1, &q, tv);
     if (rc) return rc;
+    q.lanes = lanes;
     if (tables && !q.fast_image) return rans_fast_view(tables, tv);   // no fast search image: its error
     return plan_scan(p, q, L);
 }
@@ -2452,7 +2470,7 @@ int run_call(basic_scanline_plan *p, const ScanArgs &io, int batch, int h, int w
 {
     ScanLaunch L;
     RansFastView tv;
-    int rc = prepare_launch(p, batch, h, w, table_len, tables, &tv, &L);
+    int rc = prepare_launch(p, batch, io.lanes, h, w, table_len, tables, &tv, &L);
     if (rc) return rc;
     const bool decode = tables != nullptr;
     const int64_t img_lat = static_cast<int64_t>(p->C) * h * w, img_prior = static_cast<int64_t>(p->P) * h * w;
@@ -2470,6 +2488,9 @@ int run_call(basic_scanline_plan *p, const ScanArgs &io, int batch, int h, int w
     return BASIC_OK;
 }
 
+// lane streams: `lanes` runs of C / lanes channels, each a multiple of 16 (see decoder_workgroup); 1 = one stream per image
+bool valid_lanes(const basic_scanline_plan *p, int lanes) { return lanes == 1 || (lanes > 1 && p->C % lanes == 0 && (p->C / lanes) % 16 == 0); }
+
 }  // namespace
 
 extern "C" int basic_scanline_encode_dev(basic_scanline_plan *p, const float *d_y, const float *d_prior, int batch, int h, int w,
@@ -2481,39 +2502,63 @@ extern "C" int basic_scanline_encode_dev(basic_scanline_plan *p, const float *d_
                   "scanline_encode: bad argument");
     ScanArgs io{};
     io.y = d_y; io.ybuf = d_ybuf; io.sym = d_symbols; io.idx = d_indexes;
+    io.lanes = 1; io.lane_w = p->C;
     return run_call(p, io, batch, h, w, d_prior, d_table, table_len, nullptr, as_stream(hip_stream));
+}
+
+extern "C" int basic_scanline_decode_lanes_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
+                                               const int64_t *d_word_off, const float *d_prior, int batch, int lanes, int h, int w,
+                                               const float *d_table, int table_len, int32_t *d_symbols, int32_t *d_indexes, float *d_ybuf,
+                                               void *hip_stream)
+{
+    BASIC_REQUIRE(p && tables && d_words && d_word_off && d_table && d_symbols && d_indexes && d_ybuf && batch >= 1 && h >= 1 && w >= 1 &&
+                      table_len >= 1 && table_len <= 4096 && (d_prior || p->P == 0),
+                  "scanline_decode: bad argument");
+    BASIC_REQUIRE(valid_lanes(p, lanes) && static_cast<int64_t>(batch) * lanes < (1ll << 30),
+                  "scanline_decode: lanes must divide the channels into runs of a multiple of 16");
+    ScanArgs io{};
+    io.ybuf = d_ybuf; io.sym = d_symbols; io.idx = d_indexes; io.words = d_words; io.word_off = d_word_off;
+    io.lanes = lanes; io.lane_w = p->C / lanes;
+    return run_call(p, io, batch, h, w, d_prior, d_table, table_len, tables, as_stream(hip_stream));
 }
 
 extern "C" int basic_scanline_decode_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
                                          const int64_t *d_word_off, const float *d_prior, int batch, int h, int w, const float *d_table,
                                          int table_len, int32_t *d_symbols, int32_t *d_indexes, float *d_ybuf, void *hip_stream)
 {
-    BASIC_REQUIRE(p && tables && d_words && d_word_off && d_table && d_symbols && d_indexes && d_ybuf && batch >= 1 && h >= 1 && w >= 1 &&
-                      table_len >= 1 && table_len <= 4096 && (d_prior || p->P == 0),
-                  "scanline_decode: bad argument");
-    ScanArgs io{};
-    io.ybuf = d_ybuf; io.sym = d_symbols; io.idx = d_indexes; io.words = d_words; io.word_off = d_word_off;
-    return run_call(p, io, batch, h, w, d_prior, d_table, table_len, tables, as_stream(hip_stream));
+    return basic_scanline_decode_lanes_dev(p, tables, d_words, d_word_off, d_prior, batch, 1, h, w, d_table, table_len, d_symbols, d_indexes,
+                                           d_ybuf, hip_stream);
 }
 
-// What a basic_scanline_encode_dev (tables == nullptr) or basic_scanline_decode_dev call with these arguments would run, after the
+// What a basic_scanline_encode_dev (tables == nullptr) or basic_scanline_decode_lanes_dev call (basic_scanline_decode_dev: lanes = 1)
+// with these arguments would run -- a decode call's decoder workgroups are those of its batch * lanes streams --, after the
 // coder's gates (ScanRequest::lane_max_batch): *kernel = BASIC_SCAN_KERNEL_NONE leaves the call to the per-step path, which codes
 // the same integers.  Launches nothing.
-extern "C" int basic_scanline_choose(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int h, int w, int table_len,
-                                     int schedule, int lane_max_batch, int *kernel, int *launches)
+extern "C" int basic_scanline_choose_lanes(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int lanes, int h, int w,
+                                           int table_len, int schedule, int lane_max_batch, int *kernel, int *launches)
 {
     BASIC_REQUIRE(p && kernel && batch >= 1 && h >= 0 && w >= 0 && table_len >= 1 && table_len <= 4096 && lane_max_batch >= 0 &&
                       schedule >= BASIC_SCAN_SCHEDULE_AUTO && schedule <= BASIC_SCAN_SCHEDULE_BAND,
                   "scanline_choose: bad argument");
+    BASIC_REQUIRE(valid_lanes(p, lanes) && static_cast<int64_t>(batch) * lanes < (1ll << 30),
+                  "scanline_choose: lanes must divide the channels into runs of a multiple of 16");
     ScanRequest q;
     RansFastView tv;
     ScanLaunch L;
     int rc = make_request(tables, batch, h, w, table_len, schedule, lane_max_batch, &q, &tv);
-    if (!rc) rc = plan_scan(p, q, &L);
+    if (rc) return rc;
+    q.lanes = lanes;
+    rc = plan_scan(p, q, &L);
     if (rc) return rc;
     *kernel = L.kernel == ScanKernel::kNone ? BASIC_SCAN_KERNEL_NONE : row_of(L.kernel).id;
     if (launches) *launches = L.launches;
     return BASIC_OK;
+}
+
+extern "C" int basic_scanline_choose(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int h, int w, int table_len,
+                                     int schedule, int lane_max_batch, int *kernel, int *launches)
+{
+    return basic_scanline_choose_lanes(p, tables, batch, 1, h, w, table_len, schedule, lane_max_batch, kernel, launches);
 }
 
 // Whether basic_scanline_decode_dev can serve `batch` streams of this table set on the current device (the set has a fast

@@ -201,6 +201,38 @@ class _GroupPlan:
         return self._pos_cache[key]
 
 
+def check_stream_lanes(lanes, in_channels, channel_groups, method, batch_stream_mode) -> int:
+    """Validates a coder's ``stream_lanes``; 1 is the reference's format and always allowed.  Lanes need a position-major coding
+    order with one channel group (the scan-line schedule), lanes of a multiple of 16 channels (the batched exchange layout is linear
+    in a lane's first channel only at multiples of 4; 16 keeps a lane's stores whole) and the per-image framing."""
+    if isinstance(lanes, bool) or not isinstance(lanes, (int, np.integer)) or lanes < 1:
+        raise ValueError(f"stream_lanes must be an integer >= 1, not {lanes!r}")
+    lanes = int(lanes)
+    if lanes == 1:
+        return 1
+    if method != "scanline" or channel_groups != 1:
+        raise ValueError("stream_lanes > 1 needs default_topo_group_method='scanline' and channel_groups=1")
+    if in_channels % lanes or (in_channels // lanes) % 16:
+        raise ValueError(f"stream_lanes={lanes} must cut {in_channels} channels into lanes of a multiple of 16")
+    if batch_stream_mode == "reference":
+        raise ValueError("stream_lanes > 1 writes one stream per image and lane: batch_stream_mode='reference' cannot hold it")
+    return lanes
+
+
+def parse_stream_lengths(body, nstreams):
+    """Per-image framing <I n> <n x I byte length> streams -> (int64 byte lengths [n], payload offset); ValueError unless n is
+    ``nstreams`` and the length fields fit the body."""
+    if len(body) < 4:
+        raise ValueError("stream body shorter than its count field")
+    (nb,) = struct.unpack("<I", bytes(body[:4]))
+    if nb != nstreams:
+        raise ValueError(f"stream body holds {nb} streams, this coder's configuration needs {nstreams}")
+    if len(body) < 4 + 4 * nstreams:
+        raise ValueError("stream body shorter than its length fields")
+    lens = np.frombuffer(body, dtype="<u4", count=nstreams, offset=4).astype(np.int64)
+    return lens, 4 + 4 * nstreams
+
+
 class _Kernel:
     """(weight, bias) standing in for a convolution module when the kernel comes with the call."""
 
@@ -218,7 +250,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
                  lower_bound_scale=0.11, quantizer_params=None, fixed_input_shape=None,
                  force_input_prior_shape_aligned=True, batch_stream_mode="auto", topo_group_predictor=None,
                  pgm_include_dynamic_kernel=False, pgm_include_dynamic_kernel_full=False, pgm_dynamic_kernel_enable_tiling=False,
-                 pgm_dynamic_kernel_add_self=False, training_no_quantize_for_likelihood=False, **kwargs):
+                 pgm_dynamic_kernel_add_self=False, training_no_quantize_for_likelihood=False, stream_lanes=1, **kwargs):
         super().__init__()
         # pgm_coder.py:225,376-387,413-416: the rate estimate is taken on the residual y - mu under the zero-mean density
         # (eval: round(y - mu); train-mode proxy: y - mu + fresh uniform noise) instead of on the quantised latent.  The
@@ -281,6 +313,10 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         self.fixed_input_shape = fixed_input_shape
         self.force_input_prior_shape_aligned = force_input_prior_shape_aligned
         self.batch_stream_mode = batch_stream_mode
+        # Lane streams ("Lane streams"; NOT a format the reference reads): the channels are cut into stream_lanes
+        # runs of in_channels / stream_lanes, each its own rANS stream, so that the in-kernel decoder runs stream_lanes wavefronts
+        # per image and the y encode stream_lanes streams.  Coder configuration like the tables: not written into the stream.
+        self.stream_lanes = check_stream_lanes(stream_lanes, in_channels, channel_groups, default_topo_group_method, batch_stream_mode)
         self.eps = kwargs.get("eps", 1e-7)
         self.estimate_rate = False
         if default_topo_group_method in ("channelwise-g10", "elic"):  # pgm_coder.py:1164-1171
@@ -570,6 +606,8 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         return None if prior is None else prior.contiguous()
 
     def _per_image(self, B):
+        if self.stream_lanes > 1:   # lane streams use the per-image framing at every batch size
+            return True
         mode = self.batch_stream_mode
         if mode == "auto":
             return B > 1
@@ -596,6 +634,10 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
     # 31 s columns wide, as many launches as the batch needs; a call it does not fit raises) or "auto" (the library takes the
     # wavefront where it fits and measured faster).  The integers are the same.
     scanline_encode_schedule = "auto"
+
+    def _check_lanes_call(self, pgm):
+        if self.stream_lanes > 1 and pgm is not None:
+            raise ValueError("stream_lanes > 1 codes the default scan-line order only: a call may not bring its own pgm")
 
     def _scanline_plan(self, plan, prior, batch=1, decode=False, width=None, height=None):
         """The ScanlinePlan serving this call, or None (then the per-step path codes the same integers): the configuration
@@ -626,7 +668,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         known = width is not None and height is not None
         schedule = self.scanline_encode_schedule if known else "auto"
         kernel, _ = sl.choose(batch, height or 0, width or 0, self._scale_table_dev.numel(), schedule, self.persistent_scanline_max_batch,
-                              self._tables if decode else None)
+                              self._tables if decode else None, lanes=self.stream_lanes if decode else 1)
         if kernel is None:
             return None
         if not decode:   # (a wavefront or a band the planner took for this call is pinned: the launch plans without the coder's gates)
@@ -712,6 +754,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
             self._leave_dynamic(saved)
 
     def encode(self, input, *args, prior=None, pgm=None, quantizer_params=None, **kwargs) -> bytes:
+        self._check_lanes_call(pgm)
         pgm, kernel = self._split_dynamic_pgm(pgm)
         q = self._quantizer(quantizer_params)
         saved = self._enter_dynamic(kernel)
@@ -721,6 +764,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
             self._leave_dynamic(saved)
 
     def decode(self, byte_string: bytes, *args, prior=None, pgm=None, quantizer_params=None, **kwargs):
+        self._check_lanes_call(pgm)
         pgm, kernel = self._split_dynamic_pgm(pgm)
         q = self._quantizer(quantizer_params)
         saved = self._enter_dynamic(kernel)
@@ -763,6 +807,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         return q
 
     def _encode_impl(self, input, *args, prior=None, pgm=None, quantizer_params=None, **kwargs) -> bytes:
+        self._check_lanes_call(pgm)
         self._ready()
         input = input.contiguous()
         prior = self._check_prior(input.shape, prior)
@@ -770,7 +815,14 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         sym, idx, _, plan = self._run_encode(input, prior, pgm)
         plans = plan if isinstance(plan, list) else None
         n = (plans[0] if plans else plan).per_image
-        if self._per_image(B):
+        if self.stream_lanes > 1:
+            # lane streams: [B][P][K][L] -> [B][K][P][L], then B * K contiguous streams of P * L symbols on the batched encoder
+            Kl, C = self.stream_lanes, self.in_channels
+            ps, pi = K.lanes_pack(sym, idx, B, n // C, C, Kl)
+            host, off = self._tables.encode_batch_end(self._tables.encode_batch_begin(ps.reshape(-1), pi.reshape(-1), n // Kl))
+            lens = (np.diff(off) * 4).astype("<u4")
+            body = b"".join([struct.pack("<I", B * Kl), lens.tobytes(), memoryview(host[: int(off[-1])])])
+        elif self._per_image(B):
             host, off = self._tables.encode_batch_end(self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), n))
             lens = (np.diff(off) * 4).astype("<u4")
             body = b"".join([struct.pack("<I", B), lens.tobytes(), memoryview(host[: int(off[-1])])])   # one copy of the words
@@ -799,6 +851,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         return head + body
 
     def _decode_impl(self, byte_string: bytes, *args, prior=None, pgm=None, quantizer_params=None, **kwargs):
+        self._check_lanes_call(pgm)
         self._ready()
         ptr = 0
         if self.fixed_input_shape is not None:
@@ -818,7 +871,10 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
             return self._decode_per_sample(body, prior, B, H, W, plan)
         n, C = plan.per_image, self.in_channels
         per_image = self._per_image(B)
-        if per_image:
+        Kl = self.stream_lanes
+        if Kl > 1:
+            lens, payload = parse_stream_lengths(body, B * Kl)
+        elif per_image:
             (nb,) = struct.unpack("<I", body[:4])
             assert nb == B
             lens = np.frombuffer(body, dtype="<u4", count=B, offset=4).astype(np.int64)
@@ -834,12 +890,12 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         stage.numpy()[:] = np.frombuffer(body, dtype=np.int32, count=int(woff[-1]), offset=payload)
         words_np = stage.numpy()
         sl = self._scanline_plan(plan, prior, B, decode=True, width=W, height=H)
-        if sl is not None:   # persistent scan-line launch (see _run_encode); one stream per image
+        if sl is not None:   # persistent scan-line launch (see _run_encode); one stream per image (and lane)
             d_words = stage.to(dev, non_blocking=True)
             self._tables._pin_in_event = torch.cuda.Event()
             self._tables._pin_in_event.record(torch.cuda.current_stream(dev))
             d_woff = torch.from_numpy(woff).to(dev)
-            _, _, ybuf = sl.decode(self._tables, d_words, d_woff, prior, B, H, W, self._scale_table_dev)
+            _, _, ybuf = sl.decode(self._tables, d_words, d_woff, prior, B, H, W, self._scale_table_dev, lanes=Kl)
             sl.check()
             return ybuf
         use_graph = len(plan.groups) >= self.GRAPH_MIN_GROUPS and getattr(self, "use_hip_graphs", True) and per_image
@@ -850,12 +906,12 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
             d_woff = torch.from_numpy(woff).to(dev)
             return self._run_decode_impl(d_words, d_woff, prior, B, H, W, per_image, plan)
         # static buffers: per-image streams never exceed the encoder's slot bound plus slack
-        cap = B * (3 * n + 4)
-        key = ("dec", B, H, W, prior is not None, plan.key)
+        cap = B * (3 * n + 4 * Kl)
+        key = ("dec", B, H, W, prior is not None, plan.key, Kl)
         entry = self._graphs.get(key)
         if entry is None:
             sw = torch.zeros((cap,), device=dev, dtype=torch.int32)
-            so = torch.zeros((B + 1,), device=dev, dtype=torch.int64)
+            so = torch.zeros((B * Kl + 1,), device=dev, dtype=torch.int64)
             sp = torch.empty_like(prior) if prior is not None else None
             sw[: words_np.size].copy_(stage)
             so.copy_(torch.from_numpy(woff))
@@ -942,7 +998,10 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
     def _run_decode_impl(self, d_words, d_woff, prior, B, H, W, per_image, plan):
         dev, C = self.device, self.in_channels
         n = plan.per_image
-        ns = B if per_image else 1
+        Kl = self.stream_lanes if per_image else 1
+        ns = B * Kl if per_image else 1
+        if Kl > 1 and any(grp["n"] % Kl for grp in plan.groups):
+            raise ValueError("stream_lanes: a coding step does not divide into the lanes")
         state = torch.zeros((ns,), device=dev, dtype=torch.int64)
         pos = torch.full((ns,), -1, device=dev, dtype=torch.int64)
         ws = self._alloc(B, H, W, prior, plan)
@@ -960,9 +1019,10 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
             if per_image:
                 # stream b continues (decode_stream semantics, pgm_coder.py:971) with its ng symbols of this group,
                 # in place on the dense [B][n] arrays
-                _lib.check(L.basic_rans_decode_batch_strided_dev(self._tables._h, d_words.data_ptr(), d_woff.data_ptr(), idx.data_ptr(),
-                                                                 grp["base"], n, ng, B, sym.data_ptr(), state.data_ptr(), pos.data_ptr(),
-                                                                 K._stream()))
+                # (lane streams: stream b * Kl + k with the ng / Kl symbols of its lane)
+                _lib.check(L.basic_rans_decode_batch_lanes_dev(self._tables._h, d_words.data_ptr(), d_woff.data_ptr(), idx.data_ptr(),
+                                                               grp["base"], n, Kl, ng // Kl, B, sym.data_ptr(), state.data_ptr(),
+                                                               pos.data_ptr(), K._stream()))
             else:
                 # single stream over the whole batch: gather this group's indexes batch-major
                 gi = idx[:, grp["base"]: grp["base"] + ng].reshape(-1).contiguous()

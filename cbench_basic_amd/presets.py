@@ -53,7 +53,7 @@ def topogroup_ar_codec(method="checkerboard", N=128, M=192, channel_groups=1, ex
 BASIC_WIDTHS = [48, 72, 96, 144, 192]
 
 
-def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset=None, combined_entropy_coder=False):
+def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset=None, combined_entropy_coder=False, stream_lanes=1):
     """BaSIC "hyperprior-ar-sc-slimmable-full-dynamic" (configs/presets/lossy_latent_graph_scalable_ar_models.py:
     73-197): slimmable g_a/g_s, MS-slimmable h_a/h_s, 192-ch EntropyBottleneck, scanline AR y-coder with the
     masked-conv context model, four slim controller nodes selected per complexity level.
@@ -65,7 +65,10 @@ def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset
     ``combined_entropy_coder`` = the "...-combined-dynamic-entropy-coder" variant (:198-372): the y-coder is a bank
     {scanline AR, 8-, 6-, 4-, 2-stage grouped coders with learned topo groups} selected by a fifth controller node
     ``pgmy`` (blend_weight); the learned groups are the coders' ``topo_group_predictor_cache`` buffers (random logits
-    until a checkpoint is loaded)."""
+    until a checkpoint is loaded).
+
+    ``stream_lanes`` = K > 1: the scan-line y-coder writes K lane streams per image ("Lane streams": a format of
+    this library, not readable by the reference); in the combined bank only the scan-line member gets it."""
     from .modules.prior_model.prior_coder.pgm_coder import (CombinedNNTrainablePGMPriorCoder,
                                                             GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder,
                                                             TopoGroupDynamicMaskConv2dContextModel)
@@ -88,7 +91,7 @@ def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset
         g = torch.Generator().manual_seed(1234)
         logits = lambda G, L: torch.randn(1, G * L, 2, 2, generator=g)   # predictor output: out_channels = G * L, 2 x 2 patch
         y_coder = CombinedNNTrainablePGMPriorCoder([
-            ar_coder(default_topo_group_method="scanline"),
+            ar_coder(default_topo_group_method="scanline", stream_lanes=stream_lanes),
             ar_coder(channel_groups=4, topo_group_predictor=logits(4, 8)),    # 8-stage (:270-289)
             ar_coder(channel_groups=4, topo_group_predictor=logits(4, 6)),    # 6-stage
             ar_coder(topo_group_predictor=logits(1, 16)),                      # 4-stage (channel_groups 1, 16 logits)
@@ -101,7 +104,7 @@ def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset
         controllers.append("pgmy")
         y_mapping = {"pgmy": "blend_weight", "z": "prior"}
     else:
-        y_coder = ar_coder(default_topo_group_method="scanline")
+        y_coder = ar_coder(default_topo_group_method="scanline", stream_lanes=stream_lanes)
 
     def slim_node():
         return IndexSelectParameterGeneratorWrapper(

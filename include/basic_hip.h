@@ -140,6 +140,12 @@ int basic_rans_decode_batch_strided_dev(const basic_rans_tables *t, const uint32
                                         const int64_t *d_word_off, const int32_t *d_indexes, int64_t first,
                                         int64_t stride, int64_t count, int nstreams, int32_t *d_out_symbols,
                                         uint64_t *d_state, int64_t *d_pos, void *hip_stream);
+/* The same step for the LANE STREAMS of the scan-line coder (stream_lanes = `lanes`): nimages * lanes streams,
+ * stream s = b * lanes + k continues with the `count` symbols whose indexes sit at d_indexes[first + b*stride + k*count ...]
+ * (d_state / d_pos / d_word_off are indexed by s).  lanes == 1 is basic_rans_decode_batch_strided_dev; same kernel. */
+int basic_rans_decode_batch_lanes_dev(const basic_rans_tables *t, const uint32_t *d_words, const int64_t *d_word_off,
+                                      const int32_t *d_indexes, int64_t first, int64_t stride, int lanes, int64_t count,
+                                      int nimages, int32_t *d_out_symbols, uint64_t *d_state, int64_t *d_pos, void *hip_stream);
 
 /* ======================================================================================
  * 4. Entropy-parameter kernels (coalesced elementwise, fused quantise + table index).
@@ -150,6 +156,11 @@ int basic_rans_decode_batch_strided_dev(const basic_rans_tables *t, const uint32
 int basic_gc_quantize_index_dev(const float *d_y, const float *d_scales, int64_t n, const float *d_table,
                                 int table_len, float scale_bound, int32_t *d_symbols, int32_t *d_indexes,
                                 float *d_yhat, void *hip_stream);
+/* Lane streams of the scan-line coder: repacks d_sym / d_idx, int32 [B][positions][channels] in coding order, to
+ * [B][lanes][positions][channels / lanes] (lane k = channels [k L, (k + 1) L), L = channels / lanes), so that
+ * basic_rans_encode_batch_dev codes B * lanes contiguous streams of positions * L symbols.  Out of place; lanes == 1 copies. */
+int basic_lanes_pack_dev(const int32_t *d_sym, const int32_t *d_idx, int batch, int positions, int channels, int lanes,
+                         int32_t *d_sym_out, int32_t *d_idx_out, void *hip_stream);
 /* EntropyBottleneck path (compressai_coder.py:230-245): sym = round(z - median[c]),
  * idx = c, zhat = sym + median[c].  Layout [B][C][HW]. */
 int basic_eb_quantize_index_dev(const float *d_z, const float *d_medians, int batch, int channels, int hw,
@@ -371,6 +382,15 @@ int basic_scanline_encode_dev(basic_scanline_plan *p, const float *d_y, const fl
 int basic_scanline_decode_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
                               const int64_t *d_word_off, const float *d_prior, int batch, int h, int w, const float *d_table,
                               int table_len, int32_t *d_symbols, int32_t *d_indexes, float *d_ybuf, void *hip_stream);
+/* The decoder for LANE STREAMS (stream_lanes = `lanes`; not a format the reference reads): the channels are cut
+ * into `lanes` runs of L = C / lanes (C % lanes == 0, L % 16 == 0), stream s = b * lanes + k = d_words[d_word_off[s] ..
+ * d_word_off[s + 1]) carries image b's symbols of channels [k L, (k + 1) L) in coding order, and the launch adds
+ * ceil(B * lanes / 4) decoder workgroups: one wavefront per lane stream, `lanes` of them decoding a position side by side.
+ * Everything written is what basic_scanline_decode_dev writes; lanes == 1 IS basic_scanline_decode_dev. */
+int basic_scanline_decode_lanes_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
+                                    const int64_t *d_word_off, const float *d_prior, int batch, int lanes, int h, int w,
+                                    const float *d_table, int table_len, int32_t *d_symbols, int32_t *d_indexes, float *d_ybuf,
+                                    void *hip_stream);
 /* *ok = 1 when basic_scanline_decode_dev can serve `batch` streams of `tables` on the current device (fast search image that
  * fits the LDS; compute + decoder workgroups <= compute units); otherwise the caller decodes with the per-step path, which
  * codes the same integers. */
@@ -431,6 +451,11 @@ int basic_scanline_set_encode_schedule(basic_scanline_plan *p, int schedule);
  * launch would: BASIC_ERR_INVALID ("does not fit"). */
 int basic_scanline_choose(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int h, int w, int table_len,
                           int schedule, int lane_max_batch, int *kernel, int *launches);
+/* basic_scanline_choose for a decode call over lane streams (basic_scanline_decode_lanes_dev): the decoder workgroups counted
+ * are those of batch * lanes streams, so a call whose decoder wavefronts no longer fit beside the compute workgroups is left to
+ * the per-step path.  Encode calls do not depend on `lanes`; lanes == 1 is basic_scanline_choose. */
+int basic_scanline_choose_lanes(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int lanes, int h, int w,
+                                int table_len, int schedule, int lane_max_batch, int *kernel, int *launches);
 int basic_scanline_status(basic_scanline_plan *p, void *hip_stream, int *poisoned);
 void basic_scanline_plan_destroy(basic_scanline_plan *p);
 

@@ -13,6 +13,85 @@ with torch.no_grad():
         p.copy_(torch.randn(p.shape, generator=g) * (0.03 if p.dim() > 1 else 0.02))
 c = c.eval().cuda()
 c.update_state()
+
+
+def lanes_probe(lanes_list, shapes, runs):
+    """--lanes K [K ...]: lane streams (stream_lanes = K) against one stream per image.  Per shape and K, `runs` runs of five calls
+    each (the median of a run is its figure; min - max over the runs is the spread): GPU time of the persistent decode launch
+    (ScanlinePlan.decode, or the whole per-step decode where the planner leaves the call to it), GPU time of the y rANS encode (pack
+    + batched encoder), wall time of coder.encode / coder.decode, and the bytes.  K = 1 uses only what the library had before lanes,
+    so the same script measures the commit before them.  BASIC_SCAN_PROFILE=1 adds the kernel's per-step split (stderr)."""
+    import numpy as np
+    from cbench_basic_amd.nn import kernels as K
+
+    def gpu_ms(fn, n=5):
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record(); e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return float(np.median(ts))
+
+    def wall_ms(fn, n=5):
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize(); t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts))
+
+    spread = lambda v: f"{np.median(v):8.3f} ({min(v):.3f} - {max(v):.3f})"
+    for B, H, W in shapes:
+        y = (torch.randn(B, C, H, W, generator=g) * 2).cuda()
+        prior = torch.stack([torch.randn(B, C, H, W, generator=g), torch.rand(B, C, H, W, generator=g) * 3 + 0.1], 2).reshape(B, 2 * C, H, W).cuda()
+        n = H * W * C
+        for lanes in lanes_list:
+            if hasattr(c, "stream_lanes"):   # (set on every row; a library from before the lanes has no such attribute and runs K = 1 only)
+                c.stream_lanes = lanes
+            elif lanes != 1:
+                raise SystemExit("this library has no lane streams: --lanes 1 only")
+            c.batch_stream_mode = "per_image"   # (K = 1 at batch 1: framed like the lanes, so that the bytes compare)
+            sym, idx, _, plan = c._run_encode(y, prior)
+            data = c.encode(y, prior=prior)
+            nstreams = B * lanes
+            lens = np.frombuffer(data, dtype="<u4", count=nstreams, offset=4).astype(np.int64)
+            woff = np.concatenate([[0], np.cumsum(lens // 4)]).astype(np.int64)
+            d_words = torch.from_numpy(np.frombuffer(data, dtype=np.int32, count=int(woff[-1]), offset=4 + 4 * nstreams).copy()).cuda()
+            d_woff = torch.from_numpy(woff).cuda()
+            sl = c._scanline_plan(plan, prior, B, decode=True, width=W, height=H)
+            if sl is None:
+                dec, served = (lambda: c._run_decode_impl(d_words, d_woff, prior, B, H, W, True, plan)), "per-step"
+            elif lanes == 1:
+                dec, served = (lambda: sl.decode(c._tables, d_words, d_woff, prior, B, H, W, c._scale_table_dev)), None
+            else:
+                dec, served = (lambda: sl.decode(c._tables, d_words, d_woff, prior, B, H, W, c._scale_table_dev, lanes=lanes)), None
+            if lanes == 1:
+                rans = lambda: c._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), n)
+            else:
+                rans = lambda: c._tables.encode_batch_begin(*[t.reshape(-1) for t in K.lanes_pack(sym, idx, B, H * W, C, lanes)], n // lanes)
+            dec(); rans()
+            if sl is not None:
+                sl.check()
+                served = sl.last_kernel()
+            out = c.decode(data, prior=prior)
+            assert torch.equal(out, c.decode(data, prior=prior))
+            r = dict(dec=[], rans=[], enc_wall=[], dec_wall=[])
+            for _ in range(runs):
+                r["dec"].append(gpu_ms(dec)); r["rans"].append(gpu_ms(rans))
+                r["enc_wall"].append(wall_ms(lambda: c.encode(y, prior=prior))); r["dec_wall"].append(wall_ms(lambda: c.decode(data, prior=prior)))
+            print(f"B={B:3d} {H}x{W} K={lanes:2d} [{served}]: decode launch {spread(r['dec'])} ms | y rANS encode {spread(r['rans'])} ms | "
+                  f"coder.encode {spread(r['enc_wall'])} ms | coder.decode {spread(r['dec_wall'])} ms | {len(data)} bytes ({len(data) / B:.0f} per image)", flush=True)
+
+
+if "--lanes" in sys.argv:
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lanes", type=int, nargs="+", required=True, help="lane counts to measure (1 = one stream per image)")
+    ap.add_argument("--shapes", type=int, nargs="+", default=[1, 32, 48, 64, 16, 16], help="B H W [B H W ...]")
+    ap.add_argument("--runs", type=int, default=3)
+    a = ap.parse_args()
+    lanes_probe(a.lanes, [tuple(a.shapes[i: i + 3]) for i in range(0, len(a.shapes), 3)], a.runs)
+    sys.exit(0)
+
 shapes = ((1, 32, 48), (8, 16, 16), (64, 16, 16), (24, 32, 48))
 if os.environ.get("PROBE_SMALL_BATCHES"):   # where does the per-step path take over?
     shapes = ((2, 32, 48), (3, 32, 48), (4, 32, 48), (6, 32, 48))

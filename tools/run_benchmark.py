@@ -42,8 +42,12 @@ def main():
     ap.add_argument("--workers", type=int, default=0,
                     help="num_testing_workers: concurrent stream workers on the GPU, each with its own replica of the codec; dataset "
                          "items are coded concurrently (the reference's multiprocessing pool, basic_benchmark.py:829-858, GPU-native)")
+    ap.add_argument("--stream-lanes", type=int, default=1,
+                    help="--codec basic: lane streams per image of the scan-line y-coder (a format the reference does not read)")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
+    if args.stream_lanes != 1 and args.codec != "basic":
+        ap.error("--stream-lanes needs --codec basic")
     if args.workers > 1:   # before HIP initialises: one hardware queue per worker stream
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         os.environ.setdefault("BASIC_RANS_WPB", "8")
@@ -58,9 +62,9 @@ def main():
     else:
         ds = RandomImageDataset(num=args.synthetic or 8, size=(3, args.height or args.size, args.width or args.size))
     batches = list(batched(ds, args.batch_size))
-    builders = dict(hyperprior=presets.hyperprior_codec, basic=presets.basic_codec,
+    builders = dict(hyperprior=presets.hyperprior_codec, basic=lambda **kw: presets.basic_codec(stream_lanes=args.stream_lanes, **kw),
                     topogroup=lambda: presets.topogroup_ar_codec(method=args.method))
-    codec = presets.basic_codec(search_dataset=batches) if (args.codec == "basic" and args.complexity_search) else builders[args.codec]()
+    codec = builders["basic"](search_dataset=batches) if (args.codec == "basic" and args.complexity_search) else builders[args.codec]()
     if args.checkpoint:
         sd = torch.load(args.checkpoint, map_location="cpu")
         sd = sd.get("state_dict", sd)
