@@ -50,6 +50,7 @@ _SIGNATURES = {
     "basic_rans_decode_batch_dev": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "basic_rans_decode_batch_strided_dev": (_I, [_P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P]),
     "basic_rans_decode_batch_lanes_dev": (_I, [_P, _P, _P, _P, _L, _L, _I, _L, _I, _P, _P, _P, _P]),
+    "basic_rans_decode_batch_streams_dev": (_I, [_P, _P, _P, _P, _L, _L, _I, _L, _I, _I, _I, _P, _P, _P, _P]),
     "basic_lanes_pack_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "basic_gc_quantize_index_dev": (_I, [_P, _P, _L, _P, _I, _F, _P, _P, _P, _P]),
     "basic_eb_quantize_index_dev": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
@@ -86,6 +87,7 @@ _SIGNATURES = {
     "basic_scanline_encode_dev": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "basic_scanline_decode_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "basic_scanline_decode_lanes_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "basic_scanline_decode_rows_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "basic_scanline_can_decode": (_I, [_P, _P, _I, _P]),
     "basic_scanline_batched_max": (_I, [_P, _I, _I, _P]),
     "basic_scanline_wavefront_max": (_I, [_P, _I, _I, _P]),
@@ -94,6 +96,7 @@ _SIGNATURES = {
     "basic_scanline_set_encode_schedule": (_I, [_P, _I]),
     "basic_scanline_choose": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "basic_scanline_choose_lanes": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "basic_scanline_choose_rows": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "basic_scanline_status": (_I, [_P, _P, _P]),
     "basic_scanline_plan_destroy": (None, [_P]),
     "basic_mse_per_image_dev": (_I, [_P, _P, _I, _L, _P, _P]),

@@ -386,9 +386,18 @@ struct TablesDev {
 
 // Alternative to a seg[] array: stream b codes the elements [first + b*stride, first + b*stride + count).  With `lanes` > 1
 // (lane streams of the scan-line coder) stream s = b*lanes + k codes the `count` elements from first + b*stride + k*count on.
+// `stream_stride` >= 0 (row streams of the scan-line coder): the launch's stream s = b*lanes + k is stream stream_first +
+// b*stream_stride + k of d_word_off / d_state / d_pos; otherwise the launch's own index.
 struct StridedSeg {
     int64_t first, stride, count;
     int lanes = 1;
+    int stream_first = 0, stream_stride = -1;
+    __device__ __forceinline__ int id(int stream) const
+    {
+        if (stream_stride < 0) return stream;
+        const int b = stream / lanes;
+        return stream_first + b * stream_stride + (stream - b * lanes);
+    }
     __device__ __forceinline__ int64_t begin(int stream) const
     {
         if (lanes == 1) return first + stream * stride;
@@ -852,10 +861,11 @@ __global__ __launch_bounds__(64) void rans_decode_kernel(TablesDev T, ArDev ar, 
     }
 
     WordReader rd;
-    rd.words = words_all + word_off[stream];
-    rd.limit = word_off[stream + 1] - word_off[stream];
+    const int sid = seg ? stream : ss.id(stream);   // the stream's place in word_off / state / pos_io
+    rd.words = words_all + word_off[sid];
+    rd.limit = word_off[sid + 1] - word_off[sid];
     uint64_t x;
-    int64_t p0 = pos_io[stream];
+    int64_t p0 = pos_io[sid];
     if (p0 < 0) {
         rd.pos = 0;
         rd.fill(lane);
@@ -864,7 +874,7 @@ __global__ __launch_bounds__(64) void rans_decode_kernel(TablesDev T, ArDev ar, 
     } else {
         rd.pos = p0;
         rd.fill(lane);
-        x = state[stream];
+        x = state[sid];
     }
     x = uniform_u64(x);
     const uint32_t prec = static_cast<uint32_t>(T.precision);
@@ -974,7 +984,7 @@ __global__ __launch_bounds__(64) void rans_decode_kernel(TablesDev T, ArDev ar, 
         }
         if (!AR && i < n) out[i] = result;
     }
-    if (lane == 0) { state[stream] = x; pos_io[stream] = rd.pos; }
+    if (lane == 0) { state[sid] = x; pos_io[sid] = rd.pos; }
 }
 
 // Fast decoder for the common case (no AR remap, search image resident in LDS, rows <= 4096 entries): one wavefront per
@@ -1022,11 +1032,12 @@ __global__ __launch_bounds__(64 * WPB) void rans_decode_fast_kernel(TablesDev T,
     __syncthreads();
     if (!live) return;
 
+    const int sid = seg ? stream : ss.id(stream);   // the stream's place in word_off / state / pos_io
     wavedec::WaveDecoder d;
     {
-        const int64_t p0 = pos_io[stream];   // < 0: a fresh stream; otherwise resume behind an earlier call (state[], pos_io[])
-        d.init(img, words_all + word_off[stream], static_cast<int>(word_off[stream + 1] - word_off[stream]), T.precision, T.bypass_precision, T.bypass != 0,
-               p0 < 0 ? -1 : static_cast<int>(p0), p0 < 0 ? 0ull : uniform_u64(state[stream]), lane);
+        const int64_t p0 = pos_io[sid];   // < 0: a fresh stream; otherwise resume behind an earlier call (state[], pos_io[])
+        d.init(img, words_all + word_off[sid], static_cast<int>(word_off[sid + 1] - word_off[sid]), T.precision, T.bypass_precision, T.bypass != 0,
+               p0 < 0 ? -1 : static_cast<int>(p0), p0 < 0 ? 0ull : uniform_u64(state[sid]), lane);
     }
     for (int c0 = 0; c0 < n; c0 += 64) {
         const int i = c0 + lane;
@@ -1044,8 +1055,8 @@ __global__ __launch_bounds__(64 * WPB) void rans_decode_fast_kernel(TablesDev T,
         if (i < n) out[i] = result - 1 + off_l;
     }
     if (lane == 0) {
-        state[stream] = d.x;
-        pos_io[stream] = d.position();
+        state[sid] = d.x;
+        pos_io[sid] = d.position();
     }
 }
 
@@ -1333,6 +1344,28 @@ extern "C" int basic_rans_decode_batch_lanes_dev(const basic_rans_tables *t, con
     ArDev ar{};
     return launch_decode(t, ar, nimages * lanes, as_stream(hip_stream), d_words, d_word_off, d_indexes, nullptr, d_out_symbols, d_state,
                          d_pos, StridedSeg{first, stride, count, lanes});
+}
+
+// basic_rans_decode_batch_lanes_dev with a stream base and stride (row streams of the scan-line coder, stream_rows): the launch's
+// stream (b, k) is stream stream_first + b * stream_stride + k of d_word_off / d_state / d_pos and continues with the `count`
+// symbols at first + b * stride + k * count.  stream_first = 0, stream_stride = lanes is basic_rans_decode_batch_lanes_dev.
+extern "C" int basic_rans_decode_batch_streams_dev(const basic_rans_tables *t, const uint32_t *d_words, const int64_t *d_word_off,
+                                                   const int32_t *d_indexes, int64_t first, int64_t stride, int lanes, int64_t count,
+                                                   int nimages, int stream_first, int stream_stride, int32_t *d_out_symbols,
+                                                   uint64_t *d_state, int64_t *d_pos, void *hip_stream)
+{
+    if (!t) { set_error("ANS not initialized!"); return BASIC_ERR_NOT_INIT; }
+    BASIC_REQUIRE(d_words && d_word_off && d_indexes && d_out_symbols && d_state && d_pos && nimages >= 1 && lanes >= 1 && first >= 0 &&
+                      stride >= 0 && count >= 0 && static_cast<int64_t>(nimages) * lanes < (1ll << 31) && stream_first >= 0 &&
+                      stream_stride >= lanes && stream_first + static_cast<int64_t>(nimages) * stream_stride < (1ll << 31),
+                  "rans_decode_batch_streams: bad argument");
+    BASIC_REQUIRE(!t->d_ar, "rans_decode_batch_streams: AR tables are only supported by the host-buffer entry points");
+    if (count == 0) return BASIC_OK;
+    ArDev ar{};
+    StridedSeg ss{first, stride, count, lanes};
+    ss.stream_first = stream_first; ss.stream_stride = stream_stride;
+    return launch_decode(t, ar, nimages * lanes, as_stream(hip_stream), d_words, d_word_off, d_indexes, nullptr, d_out_symbols, d_state,
+                         d_pos, ss);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -87,6 +87,7 @@ struct ScanArgs {
     const uint32_t *words; // all streams back to back
     const int64_t *word_off;   // [B * lanes + 1]
     int lanes, lane_w;     // lane streams per image (stream b * lanes + k: channels [k * lane_w, (k + 1) * lane_w)); lanes * lane_w == C
+    int row_streams;       // 1: the row-stream format -- stream (b * H + r) * lanes + k carries row r of image b (word_off [B * H * lanes + 1])
     // batched kernel only (scanline_batched_kernel; nbt == 0 for the other two): the batch is the fastest dimension of every
     // exchanged array -- yT [HW][C][nbt], act[l] [rows_l][nbt], priorT [HW][P][nbt]; mu / idx_step stay [image][C]
     int nbt;               // columns of the exchange arrays: 32 * column tiles (a column tile = 32 images = the N of an MFMA tile)
@@ -291,9 +292,24 @@ using wavedec::WaveDecoder;   // the serial rANS chain of one stream (wave_decod
 // exchange layout stays linear in a chunk's first channel (multiples of 4), and a chunk's stores stay whole 64-byte runs.
 // LANES = false is the one-stream loop with its bounds as they always were (stream = image, channels [0, C)): a call without
 // lanes runs the code it ran before the format existed.
-template <bool LANES>
+//
+// ROWS: the row-stream format (a.row_streams): stream (b * H + r) * lanes + k carries row r only.  (ROWS = 1 is instantiated for LANES
+// false and true like the loop without rows -- with run-time lanes it left the pipelined kernel 20 bytes of private segment --,
+// ROWS = 2 takes its lanes at run time, 1 included.)
+//   * ROWS = 1, the raster kernels: a wave still serves (image, lane) and walks all H * W steps, but at every row start it
+//     re-initialises its WaveDecoder on the row's stream: its word offsets and the head's three 64-word blocks are loaded there,
+//     two dependent round trips per row on the step's path (kept there on purpose: see DESIGN.md section 3).
+//   * ROWS = 2, the wavefront decode launch (scanline_batched_kernel<true, true>): one wave per (column, lane) = per stream.  Row r
+//     starts in step wf_s * r; until then the wave sleeps between polls of its first granule (a wave polling at full rate for up to
+//     wf_s * (H - 1) steps would take issue slots and memory requests from the decoder waves at work beside it), bounded like
+//     every spin.  Then W times "wait for the column's (row, mean) granules with the step's tag -> decode_chunk -> publish" into
+//     slab wf_s * r + c at the row's true column, and into sym / idx / ybuf at position r * W + c; then it returns.  The zeros of
+//     the steps in which the column is idle are published by the compute workgroups, never from here (they pace the tile's
+//     context workgroups: see the band section in front of scanline_batched_kernel).
+template <bool LANES, int ROWS = 0>
 __device__ __forceinline__ void decoder_loop(const ScanArgs &a, float *lds)
 {
+    static_assert(ROWS != 2 || LANES, "the wavefront's row streams take their lanes at run time");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wg = blockIdx.x;
     const int HW = a.H * a.W;
@@ -305,23 +321,55 @@ __device__ __forceinline__ void decoder_loop(const ScanArgs &a, float *lds)
         rowtab[r] = u32x4{a.tv.meta[r], static_cast<uint32_t>(a.tv.sizes[r]), static_cast<uint32_t>(a.tv.offsets[r]), 0u};
     __syncthreads();
     const int s = (wg - a.ncompute) * (kThreads / 64) + wave;
-    if (s >= (LANES ? a.B * a.lanes : a.B)) return;
-    const int b = LANES ? s / a.lanes : s;
-    const int cbeg = LANES ? (s - b * a.lanes) * a.lane_w : 0, cend = LANES ? cbeg + a.lane_w : a.C;   // this stream's channels
-    __builtin_amdgcn_s_setprio(3);   // a serial chain: never lose the issue arbitration to the waves spinning beside it
+    if (s >= (ROWS == 2 ? a.wf_cols * a.lanes : LANES ? a.B * a.lanes : a.B)) return;
+    const int q = LANES ? s / a.lanes : s;             // the column of mu / idx_step: the image, or (ROWS = 2) image * H + row
+    const int b = ROWS == 2 ? q / a.H : q;
+    const int wr = ROWS == 2 ? q - b * a.H : 0;        // ROWS = 2: this stream's row,
+    const int t0 = ROWS == 2 ? a.wf_s * wr : 0;        // the step it starts in
+    const int kl = LANES ? s - q * a.lanes : 0;
+    const int cbeg = LANES ? kl * a.lane_w : 0, cend = LANES ? cbeg + a.lane_w : a.C;   // this stream's channels
+    const uint64_t *pi0 = a.idx_step + static_cast<int64_t>(q) * a.C, *pm0 = a.mu + static_cast<int64_t>(q) * a.C;
+    // a serial chain: never lose the issue arbitration to the waves spinning beside it (a wavefront row: once it has started)
+    if constexpr (ROWS != 2) __builtin_amdgcn_s_setprio(3);
     WaveDecoder d;
+    const int nl = LANES ? a.lanes : 1;
+    int sr = ROWS == 1 ? b * a.H * nl + kl : s, left = a.W;   // ROWS = 1: the current row's stream, the positions left in that row
     {
-        const int64_t w0 = a.word_off[s];
-        d.init(img, a.words + w0, static_cast<int>(a.word_off[s + 1] - w0), a.tv.precision, a.tv.bypass_precision, a.tv.bypass != 0, -1, 0ull, lane);
+        const int64_t w0 = a.word_off[sr];
+        d.init(img, a.words + w0, static_cast<int>(a.word_off[sr + 1] - w0), a.tv.precision, a.tv.bypass_precision, a.tv.bypass != 0, -1, 0ull, lane);
     }
-    const uint64_t *pi0 = a.idx_step + static_cast<int64_t>(b) * a.C, *pm0 = a.mu + static_cast<int64_t>(b) * a.C;
+    if constexpr (ROWS == 2) {
+        if (t0 > 0) {   // a row that starts late: one granule, polled between sleeps (wave-uniform: every lane reads the same word)
+            unsigned spins = 0;
+            while (static_cast<uint32_t>(ld_gran(pi0 + cbeg) >> 32) != static_cast<uint32_t>(t0 + 1)) {
+                if (++spins > kSpinLimit || (spins % 64u == 0u && __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+                    __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    return;
+                }
+                __builtin_amdgcn_s_sleep(32);   // 32 x 64 clocks: about a microsecond, a twentieth of a step
+            }
+        }
+        __builtin_amdgcn_s_setprio(3);
+    }
     // where a chunk's results go: a uniform pointer per (step, chunk) + a lane term that never changes (channel c0 + lane; the
     // batched exchange layout is linear in c0: bm_gran(c0 + l) = bm_gran(l) + c0 * nbt for chunk starts c0)
     const int64_t bC = static_cast<int64_t>(b) * a.C;
-    const uint32_t lane_g = a.nbt ? static_cast<uint32_t>(bm_gran(lane, b, a.nbt)) : static_cast<uint32_t>(lane);
+    const int YW = ROWS == 2 ? a.wf_yw : a.nbt;        // columns of a slab of the coded latent (wavefront: with the pad columns)
+    const int ycol = ROWS == 2 ? b * (a.H + a.wf_s - 2) + a.wf_s - 2 + wr : b;
+    const uint32_t lane_g = YW ? static_cast<uint32_t>(bm_gran(lane, ycol, YW)) : static_cast<uint32_t>(lane);
     const uint32_t lane_y = static_cast<uint32_t>(lane) * static_cast<uint32_t>(HW);
-    for (int p = 0; p < HW; ++p) {
-        const uint32_t tag = static_cast<uint32_t>(p + 1);
+    for (int i = 0; i < (ROWS == 2 ? a.W : HW); ++i) {
+        const int p = ROWS == 2 ? wr * a.W + i : i;   // the position inside the image,
+        const int sl = ROWS == 2 ? t0 + i : i;        // the step: its tag, and its slab of the coded latent
+        const uint32_t tag = static_cast<uint32_t>(sl + 1);
+        if constexpr (ROWS == 1) {
+            if (left == 0) {   // a row start: the row's stream
+                sr += nl; left = a.W;
+                const int64_t w0 = a.word_off[sr];
+                d.restart(a.words + w0, static_cast<int>(a.word_off[sr + 1] - w0), lane);
+            }
+            --left;
+        }
         // this step's (table row, mean) granules come from the compute workgroups that own the channels; the next chunk's
         // are requested before the current chunk is decoded
         uint64_t gi = 0ull, gm = 0ull;
@@ -348,7 +396,7 @@ __device__ __forceinline__ void decoder_loop(const ScanArgs &a, float *lds)
                 const int32_t value = mine + static_cast<int32_t>(rt[2]);
                 const float v = static_cast<float>(value) + mu;           // pgm_coder.py:973-978
                 const int64_t at = bC * HW + static_cast<int64_t>(p) * a.C + c0;   // [b][p][c0] of sym / idx
-                uint64_t *yt = a.yT + (a.nbt ? (static_cast<int64_t>(p) * a.C + c0) * a.nbt : (static_cast<int64_t>(b) * HW + p) * a.C + c0);
+                uint64_t *yt = a.yT + (YW ? (static_cast<int64_t>(sl) * a.C + c0) * YW : (static_cast<int64_t>(b) * HW + p) * a.C + c0);
                 st_gran(yt + lane_g, v, tag);   // first: the compute workgroups wait for it
                 (a.sym + at)[lane] = value;
                 (a.idx + at)[lane] = row;
@@ -368,9 +416,13 @@ __device__ __forceinline__ void decoder_loop(const ScanArgs &a, float *lds)
     }
 }
 
+// WF: the decoder workgroups of the wavefront decode launch (row streams only: nothing else has one)
+template <bool WF = false>
 __device__ __forceinline__ void decoder_workgroup(const ScanArgs &a, float *lds)
 {
-    if (a.lanes > 1) decoder_loop<true>(a, lds);
+    if constexpr (WF) decoder_loop<true, 2>(a, lds);
+    else if (a.row_streams) { if (a.lanes > 1) decoder_loop<true, 1>(a, lds); else decoder_loop<false, 1>(a, lds); }
+    else if (a.lanes > 1) decoder_loop<true>(a, lds);
     else decoder_loop<false>(a, lds);
 }
 
@@ -1140,7 +1192,7 @@ __device__ __forceinline__ f4 b_leaky(f4 v)
     return v;
 }
 
-// WF: the wavefront encode schedule (see ScanArgs): the same chains, block order, LDS sums and tag protocol; a column is a row of
+// WF: the wavefront schedule (see ScanArgs; encode, and the decode of row streams -- decoder_loop, ROWS = 2): the same chains, block order, LDS sums and tag protocol; a column is a row of
 // an image, a step codes one position of every row that is inside its image in that step, the slabs of the coded latent and of
 // the prior are indexed by step.  Causal tap (dy, dx) of step t is column col + dy of slab t + dx + wf_s * dy (tap_off holds
 // dx + wf_s * dy); a column outside its row's [0, W) publishes zero granules with the step's tag, and the pad columns in front
@@ -1179,12 +1231,12 @@ __device__ __forceinline__ f4 b_leaky(f4 v)
 template <bool DECODE, bool WF = false, bool BAND = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void scanline_batched_kernel(const ScanArgs a)
 {
-    static_assert(!(DECODE && WF), "the wavefront schedule is encode only: the decoder reads one serial rANS stream");
+    static_assert(!(DECODE && BAND), "the band schedule is encode only (a wavefront decode call reads one rANS stream per row)");
     static_assert(WF || !BAND, "the band schedule is a wavefront schedule");
     extern __shared__ float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wg = blockIdx.x;
-    if (DECODE && wg >= a.ncompute) { decoder_workgroup(a, lds); return; }
+    if (DECODE && wg >= a.ncompute) { decoder_workgroup<WF>(a, lds); return; }
     const int HW = a.H * a.W, C = a.C, NBT = a.nbt, T = NBT >> 5;
     const int t = wg % T, j = wg / T;                  // column tile; role index inside the tile's set of workgroups
     const int h = lane >> 5, n = lane & 31, col = t * 32 + n;
@@ -1500,7 +1552,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
                 // latent (encoder) -- the table search and the plain outputs follow in its shadow
                 uint32_t yo = yoff, oo = ooff, to = toff, mo = moff;
                 asm volatile("" : "+v"(yo), "+v"(oo), "+v"(to), "+v"(mo));
-                if (DECODE) {
+                uint64_t *ypos = a.yT + static_cast<int64_t>(p) * C * YW;
+                if constexpr (BAND) to += b_to;
+                if (WF && !active) {   // an idle column: the zero padding left and right of its row (band: of a slot with a row) -- in
+                    if (b_has) {       // a decode launch too: the row's decoder wavefront publishes the row's own positions only
+                        st_gran(ypos + to, 0.f, tag);
+                        st_gran(ypos + (to + static_cast<uint32_t>(2 * YW)), 0.f, tag);
+                    }
+                } else if (DECODE) {   // (wavefront: mu / idx_step are indexed by column, and so read by the column's decoder wavefronts)
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
                         const int row = nearest_scale(v[2 * i + 1], tab, a.table_len, tab_sorted);
@@ -1509,26 +1568,17 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
                     }
                 } else {
                     const float q0 = rintf(y_pre0 - v[0]), q1 = rintf(y_pre1 - v[2]);          // torch.round: half to even
-                    uint64_t *ypos = a.yT + static_cast<int64_t>(p) * C * YW;
-                    if constexpr (BAND) to += b_to;
-                    if (WF && !active) {   // an idle column: the zero padding left and right of its row (band: of a slot with a row)
-                        if (b_has) {
-                            st_gran(ypos + to, 0.f, tag);
-                            st_gran(ypos + (to + static_cast<uint32_t>(2 * YW)), 0.f, tag);
-                        }
-                    } else {
-                        st_gran(ypos + to, q0 + v[0], tag);
-                        st_gran(ypos + (to + static_cast<uint32_t>(2 * YW)), q1 + v[2], tag);     // channel c0 + 1: the odd-parity piece of the same quad
-                        const int op = WF ? 0 : p;
-                        if constexpr (WF) { oo += static_cast<uint32_t>(wc * C); yo += static_cast<uint32_t>(wc); }
+                    st_gran(ypos + to, q0 + v[0], tag);
+                    st_gran(ypos + (to + static_cast<uint32_t>(2 * YW)), q1 + v[2], tag);     // channel c0 + 1: the odd-parity piece of the same quad
+                    const int op = WF ? 0 : p;
+                    if constexpr (WF) { oo += static_cast<uint32_t>(wc * C); yo += static_cast<uint32_t>(wc); }
 #pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            const float mu = v[2 * i], qq = i ? q1 : q0;
-                            const int row = nearest_scale(v[2 * i + 1], tab, a.table_len, tab_sorted);
-                            (a.idx + static_cast<int64_t>(op) * C)[oo + i] = row;
-                            (a.sym + static_cast<int64_t>(op) * C)[oo + i] = static_cast<int32_t>(qq);
-                            (a.ybuf + op)[yo + static_cast<uint32_t>(i * HW)] = qq + mu;
-                        }
+                    for (int i = 0; i < 2; ++i) {
+                        const float mu = v[2 * i], qq = i ? q1 : q0;
+                        const int row = nearest_scale(v[2 * i + 1], tab, a.table_len, tab_sorted);
+                        (a.idx + static_cast<int64_t>(op) * C)[oo + i] = row;
+                        (a.sym + static_cast<int64_t>(op) * C)[oo + i] = static_cast<int32_t>(qq);
+                        (a.ybuf + op)[yo + static_cast<uint32_t>(i * HW)] = qq + mu;
                     }
                 }
             }
@@ -1877,11 +1927,11 @@ struct ScanKernelRow {
     int id;              // BASIC_SCAN_KERNEL_*: what basic_scanline_last_kernel and basic_scanline_choose report
     const char *env;     // its spelling in the BASIC_SCAN_KERNEL environment variable
     const char *label;   // ScanProfile
-    ScanFn fn;           // nullptr: the schedule is encode only
+    ScanFn fn;           // nullptr: the schedule is encode only (the wavefront's decode row serves row-stream calls only)
 };
 template <bool DECODE> constexpr ScanKernelRow kScanKernels[] = {
     {BASIC_SCAN_KERNEL_BAND, "band", "encode (band)", DECODE ? nullptr : scanline_batched_kernel<false, true, true>},
-    {BASIC_SCAN_KERNEL_WAVEFRONT, "wavefront", "encode (wavefront)", DECODE ? nullptr : scanline_batched_kernel<false, true>},
+    {BASIC_SCAN_KERNEL_WAVEFRONT, "wavefront", DECODE ? "decode (wavefront)" : "encode (wavefront)", scanline_batched_kernel<DECODE, true>},
     {BASIC_SCAN_KERNEL_BATCHED, "batched", DECODE ? "decode (batched)" : "encode (batched)", scanline_batched_kernel<DECODE>},
     {BASIC_SCAN_KERNEL_PIPELINED, "pipelined", DECODE ? "decode" : "encode", scanline_pipelined_kernel<DECODE>},
     {BASIC_SCAN_KERNEL_GENERIC, "generic", DECODE ? "decode" : "encode", scanline_persistent_kernel<DECODE>},
@@ -2078,6 +2128,27 @@ bool wavefront_auto(const basic_scanline_plan *p, int batch, int h, int w)
     return 2 * wavefront_steps(p, h, w) <= static_cast<int64_t>(h) * w;
 }
 
+// ---- wavefront decode launch (row streams only): the wavefront's columns, plus one decoder wavefront per stream -- batch * h * lanes
+// of them, four to a workgroup, resident beside the compute workgroups.
+bool wavefront_decode_fits(const basic_scanline_plan *p, int batch, int h, int lanes, int cus)
+{
+    if (!wavefront_fits(p, batch, h, cus)) return false;
+    const int tiles = (batch * h + 31) / 32;
+    return static_cast<int64_t>(tiles) * p->b_nw + decoder_workgroups(batch * h * lanes) <= cus;
+}
+
+// The row-stream decode calls that take the wavefront launch when nothing forces a choice: none yet.  The rule is to be the encode
+// rule (wavefront_auto: at most half the raster steps) cut down to the shapes where the launch MEASURED faster than the raster
+// decode launch of the same shape and lane count by more than the run-to-run spread.  Its step is new -- the batched kernel's
+// wavefront step (17.5-20.5 us in the encode launch) plus an in-loop decode of lane_w symbols per stream -- and no step cost has
+// been measured (scripts/scanline_probe.py --rows measures it), so until one is, only
+// BASIC_SCAN_KERNEL=wavefront sends a call here and auto keeps every row-stream call on the raster kernels.
+bool wavefront_decode_auto(const basic_scanline_plan *p, int batch, int h, int w, int lanes)
+{
+    (void)p; (void)batch; (void)h; (void)w; (void)lanes;
+    return false;
+}
+
 // ---- band encode schedule of the batched kernel (see the band section in front of it): an image owns band_slots() lanes of one
 // column tile whatever its height, so a launch of T tiles codes T * (32 / slots) images in the wavefront's W + s (H - 1) steps, and
 // a larger batch is coded by successive launches over whole images.
@@ -2168,6 +2239,7 @@ bool lane_grid_resident(const basic_scanline_plan *p, int ndec, int cus) { retur
 struct ScanRequest {
     int batch = 1, h = 0, w = 0;     // h or w < 1: not known -- no kernel of the batched family is considered then
     int lanes = 1;                   // decode: lane streams per image (a decoder wavefront each); encode launches do not depend on it
+    bool rows = false;               // decode: the row-stream format (batch * h * lanes streams): the wavefront launch may serve the call
     int table_len = 1;
     bool decode = false;
     bool fast_image = false;         // decode: the table set has a fast search image ...
@@ -2200,7 +2272,10 @@ int compute_workgroups(const basic_scanline_plan *p, ScanKernel k, int images, i
 // `force` names one, with identical results), in how many launches, with which grid and LDS.
 // Encode calls have a second schedule, the wavefront one of the batched kernel: forced by BASIC_SCAN_KERNEL=wavefront or by the
 // requested schedule (the environment wins), taken in auto where wavefront_auto says so; the raster schedule is the choice
-// above, whatever wavefront_auto says.  Decode calls ignore both.
+// above, whatever wavefront_auto says.  Decode calls ignore both -- unless the call brings row streams (q.rows): then
+// BASIC_SCAN_KERNEL=wavefront forces the wavefront decode launch, and auto takes it where wavefront_decode_fits and
+// wavefront_decode_auto say so; where it does not fit, the raster kernels read the row streams (decoder workgroups of batch * lanes
+// streams, as without rows), then the per-step path.  With rows off every request is planned as before the format existed.
 // And a third, the band (BASIC_SCAN_KERNEL=band, BASIC_SCAN_SCHEDULE_BAND): any batch and height, in as many launches as the
 // batch needs.  In auto it is looked at only where the wavefront does not fit, and taken where band_auto says so.
 // A forced kernel or schedule that the call does not fit is refused (BASIC_ERR_INVALID, "does not fit").
@@ -2213,8 +2288,12 @@ int plan_scan(const basic_scanline_plan *p, const ScanRequest &q, ScanLaunch *L)
     const int ndec = decode ? decoder_workgroups(batch * q.lanes) : 0;
     int schedule = q.schedule;
     ScanKernel force = q.force;
-    if (decode && force != ScanKernel::kNone && !row_of(force, true).fn) force = ScanKernel::kNone;   // encode only: a decode call ignores it
-    const bool wf_fits = !decode && wavefront_fits(p, batch, h, cus);
+    // encode only: a decode call ignores it (the wavefront: unless it brings row streams)
+    if (decode && force != ScanKernel::kNone && (!row_of(force, true).fn || (force == ScanKernel::kWavefront && !q.rows))) force = ScanKernel::kNone;
+    const bool wf_fits = decode ? q.rows && h >= 1 && w >= 1 && wavefront_decode_fits(p, batch, h, q.lanes, cus) && q.decoder_lds <= kMaxLds
+                                : wavefront_fits(p, batch, h, cus);
+    // a row-stream decode call that goes to the wavefront launch: forced, or in auto where it fits and its rule says so
+    const bool wf_decode = decode && wf_fits && (force == ScanKernel::kWavefront || (force == ScanKernel::kNone && wavefront_decode_auto(p, batch, h, w, q.lanes)));
     int band_n = -1;   // band_images_per_launch, when somebody asks
     auto band_images = [&] { return band_n >= 0 ? band_n : (band_n = band_images_per_launch(p, h, w, cus)); };
     if (q.lane_max_batch >= 0) {
@@ -2225,26 +2304,29 @@ int plan_scan(const basic_scanline_plan *p, const ScanRequest &q, ScanLaunch *L)
             // no raster kernel serves this batch; an encode call may still run as a wavefront (a narrow latent, for one), or, in
             // auto, as a band where that beats the per-step path.  (kept as it is: a forced wavefront that does not fit is not
             // refused here but left to the per-step path)
-            if (decode || schedule == BASIC_SCAN_SCHEDULE_RASTER) return BASIC_OK;
-            if (wf_fits) schedule = BASIC_SCAN_SCHEDULE_WAVEFRONT;
+            if (decode) {
+                if (!wf_decode) return BASIC_OK;   // (row streams: the wavefront decode launch serves the call, chosen below)
+            } else if (schedule == BASIC_SCAN_SCHEDULE_RASTER) return BASIC_OK;
+            else if (wf_fits) schedule = BASIC_SCAN_SCHEDULE_WAVEFRONT;
             else if (schedule == BASIC_SCAN_SCHEDULE_AUTO && band_beats_per_step(p, batch, h, w, band_images())) schedule = BASIC_SCAN_SCHEDULE_BAND;
             else return BASIC_OK;
         }
-        if (!lane_grid_resident(p, ndec, cus) || (decode && q.decoder_lds > kMaxLds)) return BASIC_OK;
+        if (!wf_decode && (!lane_grid_resident(p, ndec, cus) || (decode && q.decoder_lds > kMaxLds))) return BASIC_OK;
     }
     if (force == ScanKernel::kNone && !decode && schedule == BASIC_SCAN_SCHEDULE_WAVEFRONT) force = ScanKernel::kWavefront;
     if (force == ScanKernel::kNone && !decode && schedule == BASIC_SCAN_SCHEDULE_BAND) force = ScanKernel::kBand;
     const bool automatic = force == ScanKernel::kNone && schedule == BASIC_SCAN_SCHEDULE_AUTO;
     const bool fits = batched_fits(p, batch, w, ndec, cus);
     if (force == ScanKernel::kBatched) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=batched, but this call does not fit the batched kernel");
-    if (force == ScanKernel::kWavefront) BASIC_REQUIRE(wf_fits, "scanline: the wavefront encode schedule was asked for, but this call does not fit it");
+    if (force == ScanKernel::kWavefront) BASIC_REQUIRE(wf_fits, decode ? "scanline: BASIC_SCAN_KERNEL=wavefront, but this row-stream decode call does not fit the wavefront launch"
+                                                                       : "scanline: the wavefront encode schedule was asked for, but this call does not fit it");
     const int per_launch = !decode && (force == ScanKernel::kBand || (automatic && !wf_fits)) ? band_images() : 0;
     if (force == ScanKernel::kBand) BASIC_REQUIRE(per_launch >= 1, "scanline: the band encode schedule was asked for, but this call does not fit it");
     L->images = batch;
     if (force == ScanKernel::kBand || (per_launch >= 1 && band_auto(p, batch, h, w, per_launch))) {
         L->kernel = ScanKernel::kBand;
         L->images = std::min(per_launch, batch);
-    } else if (force == ScanKernel::kWavefront || (automatic && wf_fits && wavefront_auto(p, batch, h, w))) {
+    } else if (force == ScanKernel::kWavefront || wf_decode || (!decode && automatic && wf_fits && wavefront_auto(p, batch, h, w))) {
         L->kernel = ScanKernel::kWavefront;
     } else if (force == ScanKernel::kBatched || (force == ScanKernel::kNone && fits && batch >= 3)) {
         L->kernel = ScanKernel::kBatched;
@@ -2258,7 +2340,8 @@ int plan_scan(const basic_scanline_plan *p, const ScanRequest &q, ScanLaunch *L)
     if (L->kernel != ScanKernel::kGeneric && L->kernel != ScanKernel::kPipelined)
         L->lds_bytes = (align4(q.table_len) + 4 + 96 + static_cast<size_t>(p->b_tiles) * kBTile) * sizeof(float);   // table, flags, biases, partial tiles
     L->launches = (batch + L->images - 1) / L->images;
-    L->grid = compute_workgroups(p, L->kernel, L->images, h, w) + ndec;
+    // (the wavefront decode launch: a decoder wavefront per row stream)
+    L->grid = compute_workgroups(p, L->kernel, L->images, h, w) + (decode && L->kernel == ScanKernel::kWavefront ? decoder_workgroups(batch * h * q.lanes) : ndec);
     if (decode) L->lds_bytes = std::max(L->lds_bytes, q.decoder_lds);
     if (L->lds_bytes < kMinLds) L->lds_bytes = kMinLds;
     BASIC_REQUIRE(L->lds_bytes <= kMaxLds, L->kernel == ScanKernel::kBand ? "scanline: a workgroup's LDS does not fit"
@@ -2289,13 +2372,13 @@ int make_request(const basic_rans_tables *tables, int batch, int h, int w, int t
 }
 
 // Plans a *_dev call: the plan's encode schedule, no coder gates; `tables` != nullptr: decode
-int prepare_launch(const basic_scanline_plan *p, int batch, int lanes, int h, int w, int table_len, const basic_rans_tables *tables, RansFastView *tv,
-                   ScanLaunch *L)
+int prepare_launch(const basic_scanline_plan *p, int batch, int lanes, bool rows, int h, int w, int table_len, const basic_rans_tables *tables,
+                   RansFastView *tv, ScanLaunch *L)
 {
     ScanRequest q;
     const int rc = make_request(tables, batch, h, w, table_len, p->encode_schedule, -1, &q, tv);
     if (rc) return rc;
-    q.lanes = lanes;
+    q.lanes = lanes; q.rows = rows;
     if (tables && !q.fast_image) return rans_fast_view(tables, tv);   // no fast search image: its error
     return plan_scan(p, q, L);
 }
@@ -2451,7 +2534,7 @@ int run_launch(basic_scanline_plan *p, ScanArgs &a, const ScanLaunch &L, int gri
 {
     const ScanKernelRow &k = row_of(L.kernel, decode);
     const ScanFn fn = k.fn;
-    BASIC_REQUIRE(fn, "scanline: the wavefront and band schedules are encode only");
+    BASIC_REQUIRE(fn, "scanline: the band schedule is encode only");
     BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(fn)));
     ScanProfile prof;
     int rc = prof.begin(a, st);
@@ -2470,7 +2553,7 @@ int run_call(basic_scanline_plan *p, const ScanArgs &io, int batch, int h, int w
 {
     ScanLaunch L;
     RansFastView tv;
-    int rc = prepare_launch(p, batch, io.lanes, h, w, table_len, tables, &tv, &L);
+    int rc = prepare_launch(p, batch, io.lanes, io.row_streams != 0, h, w, table_len, tables, &tv, &L);
     if (rc) return rc;
     const bool decode = tables != nullptr;
     const int64_t img_lat = static_cast<int64_t>(p->C) * h * w, img_prior = static_cast<int64_t>(p->P) * h * w;
@@ -2506,20 +2589,43 @@ extern "C" int basic_scanline_encode_dev(basic_scanline_plan *p, const float *d_
     return run_call(p, io, batch, h, w, d_prior, d_table, table_len, nullptr, as_stream(hip_stream));
 }
 
+namespace {
+
+// a decode call over lane streams (rows == false: stream b * lanes + k) or row streams (stream (b * h + r) * lanes + k)
+int decode_call(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words, const int64_t *d_word_off, const float *d_prior,
+                int batch, int lanes, bool rows, int h, int w, const float *d_table, int table_len, int32_t *d_symbols, int32_t *d_indexes,
+                float *d_ybuf, void *hip_stream)
+{
+    BASIC_REQUIRE(p && tables && d_words && d_word_off && d_table && d_symbols && d_indexes && d_ybuf && batch >= 1 && h >= 1 && w >= 1 &&
+                      table_len >= 1 && table_len <= 4096 && (d_prior || p->P == 0),
+                  "scanline_decode: bad argument");
+    BASIC_REQUIRE(valid_lanes(p, lanes) && static_cast<int64_t>(batch) * lanes * (rows ? h : 1) < (1ll << 30),
+                  "scanline_decode: lanes must divide the channels into runs of a multiple of 16");
+    ScanArgs io{};
+    io.ybuf = d_ybuf; io.sym = d_symbols; io.idx = d_indexes; io.words = d_words; io.word_off = d_word_off;
+    io.lanes = lanes; io.lane_w = p->C / lanes; io.row_streams = rows ? 1 : 0;
+    return run_call(p, io, batch, h, w, d_prior, d_table, table_len, tables, as_stream(hip_stream));
+}
+
+}  // namespace
+
 extern "C" int basic_scanline_decode_lanes_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
                                                const int64_t *d_word_off, const float *d_prior, int batch, int lanes, int h, int w,
                                                const float *d_table, int table_len, int32_t *d_symbols, int32_t *d_indexes, float *d_ybuf,
                                                void *hip_stream)
 {
-    BASIC_REQUIRE(p && tables && d_words && d_word_off && d_table && d_symbols && d_indexes && d_ybuf && batch >= 1 && h >= 1 && w >= 1 &&
-                      table_len >= 1 && table_len <= 4096 && (d_prior || p->P == 0),
-                  "scanline_decode: bad argument");
-    BASIC_REQUIRE(valid_lanes(p, lanes) && static_cast<int64_t>(batch) * lanes < (1ll << 30),
-                  "scanline_decode: lanes must divide the channels into runs of a multiple of 16");
-    ScanArgs io{};
-    io.ybuf = d_ybuf; io.sym = d_symbols; io.idx = d_indexes; io.words = d_words; io.word_off = d_word_off;
-    io.lanes = lanes; io.lane_w = p->C / lanes;
-    return run_call(p, io, batch, h, w, d_prior, d_table, table_len, tables, as_stream(hip_stream));
+    return decode_call(p, tables, d_words, d_word_off, d_prior, batch, lanes, false, h, w, d_table, table_len, d_symbols, d_indexes, d_ybuf, hip_stream);
+}
+
+// basic_scanline_decode_lanes_dev for ROW STREAMS: batch * h * lanes streams, stream (b * h + r) * lanes + k carries row r of image
+// b, lane k.  Where the call fits (wavefront_decode_fits) and the rule or BASIC_SCAN_KERNEL=wavefront says so, the wavefront decode
+// launch; otherwise the raster kernels, whose decoder wavefronts change stream at every row start.
+extern "C" int basic_scanline_decode_rows_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
+                                              const int64_t *d_word_off, const float *d_prior, int batch, int lanes, int h, int w,
+                                              const float *d_table, int table_len, int32_t *d_symbols, int32_t *d_indexes, float *d_ybuf,
+                                              void *hip_stream)
+{
+    return decode_call(p, tables, d_words, d_word_off, d_prior, batch, lanes, true, h, w, d_table, table_len, d_symbols, d_indexes, d_ybuf, hip_stream);
 }
 
 extern "C" int basic_scanline_decode_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
@@ -2531,28 +2637,36 @@ extern "C" int basic_scanline_decode_dev(basic_scanline_plan *p, const basic_ran
 }
 
 // What a basic_scanline_encode_dev (tables == nullptr) or basic_scanline_decode_lanes_dev call (basic_scanline_decode_dev: lanes = 1)
-// with these arguments would run -- a decode call's decoder workgroups are those of its batch * lanes streams --, after the
+// with these arguments would run -- a decode call's decoder workgroups are those of its batch * lanes streams (the wavefront decode
+// launch of a row-stream call: batch * h * lanes) --, after the
 // coder's gates (ScanRequest::lane_max_batch): *kernel = BASIC_SCAN_KERNEL_NONE leaves the call to the per-step path, which codes
 // the same integers.  Launches nothing.
-extern "C" int basic_scanline_choose_lanes(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int lanes, int h, int w,
-                                           int table_len, int schedule, int lane_max_batch, int *kernel, int *launches)
+// (rows != 0: a decode call over row streams, basic_scanline_decode_rows_dev; encode calls do not depend on it)
+extern "C" int basic_scanline_choose_rows(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int lanes, int rows, int h,
+                                          int w, int table_len, int schedule, int lane_max_batch, int *kernel, int *launches)
 {
     BASIC_REQUIRE(p && kernel && batch >= 1 && h >= 0 && w >= 0 && table_len >= 1 && table_len <= 4096 && lane_max_batch >= 0 &&
                       schedule >= BASIC_SCAN_SCHEDULE_AUTO && schedule <= BASIC_SCAN_SCHEDULE_BAND,
                   "scanline_choose: bad argument");
-    BASIC_REQUIRE(valid_lanes(p, lanes) && static_cast<int64_t>(batch) * lanes < (1ll << 30),
+    BASIC_REQUIRE(valid_lanes(p, lanes) && static_cast<int64_t>(batch) * lanes * (rows && h > 0 ? h : 1) < (1ll << 30),
                   "scanline_choose: lanes must divide the channels into runs of a multiple of 16");
     ScanRequest q;
     RansFastView tv;
     ScanLaunch L;
     int rc = make_request(tables, batch, h, w, table_len, schedule, lane_max_batch, &q, &tv);
     if (rc) return rc;
-    q.lanes = lanes;
+    q.lanes = lanes; q.rows = rows != 0 && tables != nullptr;
     rc = plan_scan(p, q, &L);
     if (rc) return rc;
     *kernel = L.kernel == ScanKernel::kNone ? BASIC_SCAN_KERNEL_NONE : row_of(L.kernel).id;
     if (launches) *launches = L.launches;
     return BASIC_OK;
+}
+
+extern "C" int basic_scanline_choose_lanes(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int lanes, int h, int w,
+                                           int table_len, int schedule, int lane_max_batch, int *kernel, int *launches)
+{
+    return basic_scanline_choose_rows(p, tables, batch, lanes, 0, h, w, table_len, schedule, lane_max_batch, kernel, launches);
 }
 
 extern "C" int basic_scanline_choose(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int h, int w, int table_len,

@@ -152,6 +152,16 @@ struct WaveDecoder {
         cur = wa;
         x = start < 0 ? (static_cast<uint64_t>(bc32(wa, 0)) | (static_cast<uint64_t>(bc32(wa, 1)) << 32)) : x_saved;
     }
+    // the same decoder on another fresh stream (row streams of the scan-line coder: a wave changes stream at every row start)
+    __device__ __forceinline__ void restart(const uint32_t *w, int nwords, int lane)
+    {
+        words = w; limit = nwords;
+        wbase = 0;
+        wa = load_block(0, lane); wb = load_block(64, lane); wc = load_block(128, lane);
+        pos0 = 0; k = 2;
+        cur = wa;
+        x = static_cast<uint64_t>(bc32(wa, 0)) | (static_cast<uint64_t>(bc32(wa, 1)) << 32);
+    }
     __device__ __forceinline__ int position() const { return pos0 + k; }
     // `cur` := the 64 words from the next unread one on (k := 0).  Before every chunk and after a bypass value.
     __device__ __forceinline__ void line_up(int lane)

@@ -219,6 +219,21 @@ def check_stream_lanes(lanes, in_channels, channel_groups, method, batch_stream_
     return lanes
 
 
+def check_stream_rows(rows, channel_groups, method, batch_stream_mode) -> bool:
+    """Validates a coder's ``stream_rows``; False is the reference's format and always allowed.  Row streams need what lanes need of
+    the coding order (position-major and raster with one channel group: the scan-line schedule, so that a latent row is a contiguous
+    run of the coding order) and the per-image framing."""
+    if not isinstance(rows, (bool, np.bool_)):
+        raise ValueError(f"stream_rows must be True or False, not {rows!r}")
+    if not rows:
+        return False
+    if method != "scanline" or channel_groups != 1:
+        raise ValueError("stream_rows=True needs default_topo_group_method='scanline' and channel_groups=1")
+    if batch_stream_mode == "reference":
+        raise ValueError("stream_rows=True writes one stream per image, row and lane: batch_stream_mode='reference' cannot hold it")
+    return True
+
+
 def parse_stream_lengths(body, nstreams):
     """Per-image framing <I n> <n x I byte length> streams -> (int64 byte lengths [n], payload offset); ValueError unless n is
     ``nstreams`` and the length fields fit the body."""
@@ -250,7 +265,8 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
                  lower_bound_scale=0.11, quantizer_params=None, fixed_input_shape=None,
                  force_input_prior_shape_aligned=True, batch_stream_mode="auto", topo_group_predictor=None,
                  pgm_include_dynamic_kernel=False, pgm_include_dynamic_kernel_full=False, pgm_dynamic_kernel_enable_tiling=False,
-                 pgm_dynamic_kernel_add_self=False, training_no_quantize_for_likelihood=False, stream_lanes=1, **kwargs):
+                 pgm_dynamic_kernel_add_self=False, training_no_quantize_for_likelihood=False, stream_lanes=1, stream_rows=False,
+                 **kwargs):
         super().__init__()
         # pgm_coder.py:225,376-387,413-416: the rate estimate is taken on the residual y - mu under the zero-mean density
         # (eval: round(y - mu); train-mode proxy: y - mu + fresh uniform noise) instead of on the quantised latent.  The
@@ -317,6 +333,10 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         # runs of in_channels / stream_lanes, each its own rANS stream, so that the in-kernel decoder runs stream_lanes wavefronts
         # per image and the y encode stream_lanes streams.  Coder configuration like the tables: not written into the stream.
         self.stream_lanes = check_stream_lanes(stream_lanes, in_channels, channel_groups, default_topo_group_method, batch_stream_mode)
+        # Row streams ("Row streams"; NOT a format the reference reads either): every latent row of every image (and
+        # lane) is its own rANS stream, so that the decode launch can walk an image's rows in parallel (the wavefront schedule) and
+        # the y encode codes B * H * stream_lanes short streams side by side.  Coder configuration too: not written into the stream.
+        self.stream_rows = check_stream_rows(stream_rows, channel_groups, default_topo_group_method, batch_stream_mode)
         self.eps = kwargs.get("eps", 1e-7)
         self.estimate_rate = False
         if default_topo_group_method in ("channelwise-g10", "elic"):  # pgm_coder.py:1164-1171
@@ -606,7 +626,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         return None if prior is None else prior.contiguous()
 
     def _per_image(self, B):
-        if self.stream_lanes > 1:   # lane streams use the per-image framing at every batch size
+        if self.stream_lanes > 1 or self.stream_rows:   # lane and row streams use the per-image framing at every batch size
             return True
         mode = self.batch_stream_mode
         if mode == "auto":
@@ -638,6 +658,8 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
     def _check_lanes_call(self, pgm):
         if self.stream_lanes > 1 and pgm is not None:
             raise ValueError("stream_lanes > 1 codes the default scan-line order only: a call may not bring its own pgm")
+        if self.stream_rows and pgm is not None:
+            raise ValueError("stream_rows=True codes the default scan-line order only: a call may not bring its own pgm")
 
     def _scanline_plan(self, plan, prior, batch=1, decode=False, width=None, height=None):
         """The ScanlinePlan serving this call, or None (then the per-step path codes the same integers): the configuration
@@ -668,7 +690,8 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         known = width is not None and height is not None
         schedule = self.scanline_encode_schedule if known else "auto"
         kernel, _ = sl.choose(batch, height or 0, width or 0, self._scale_table_dev.numel(), schedule, self.persistent_scanline_max_batch,
-                              self._tables if decode else None, lanes=self.stream_lanes if decode else 1)
+                              self._tables if decode else None, lanes=self.stream_lanes if decode else 1,
+                              rows=self.stream_rows and decode)
         if kernel is None:
             return None
         if not decode:   # (a wavefront or a band the planner took for this call is pinned: the launch plans without the coder's gates)
@@ -815,13 +838,16 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         sym, idx, _, plan = self._run_encode(input, prior, pgm)
         plans = plan if isinstance(plan, list) else None
         n = (plans[0] if plans else plan).per_image
-        if self.stream_lanes > 1:
-            # lane streams: [B][P][K][L] -> [B][K][P][L], then B * K contiguous streams of P * L symbols on the batched encoder
+        if self.stream_lanes > 1 or self.stream_rows:
+            # lane streams: [B][P][K][L] -> [B][K][P][L], then B * K contiguous streams of P * L symbols on the batched encoder.
+            # Row streams: the coding order is raster, so an image's rows are contiguous -- the same pack with batch := B * H and
+            # positions := W gives the B * H * K streams (row, lane); with one lane nothing moves at all.
             Kl, C = self.stream_lanes, self.in_channels
-            ps, pi = K.lanes_pack(sym, idx, B, n // C, C, Kl)
-            host, off = self._tables.encode_batch_end(self._tables.encode_batch_begin(ps.reshape(-1), pi.reshape(-1), n // Kl))
+            R = input.shape[2] if self.stream_rows else 1   # streams per image and lane
+            ps, pi = K.lanes_pack(sym, idx, B * R, n // C // R, C, Kl) if Kl > 1 else (sym, idx)
+            host, off = self._tables.encode_batch_end(self._tables.encode_batch_begin(ps.reshape(-1), pi.reshape(-1), n // Kl // R))
             lens = (np.diff(off) * 4).astype("<u4")
-            body = b"".join([struct.pack("<I", B * Kl), lens.tobytes(), memoryview(host[: int(off[-1])])])
+            body = b"".join([struct.pack("<I", B * R * Kl), lens.tobytes(), memoryview(host[: int(off[-1])])])
         elif self._per_image(B):
             host, off = self._tables.encode_batch_end(self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), n))
             lens = (np.diff(off) * 4).astype("<u4")
@@ -872,8 +898,9 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         n, C = plan.per_image, self.in_channels
         per_image = self._per_image(B)
         Kl = self.stream_lanes
-        if Kl > 1:
-            lens, payload = parse_stream_lengths(body, B * Kl)
+        R = H if self.stream_rows else 1   # streams per image and lane
+        if Kl > 1 or self.stream_rows:
+            lens, payload = parse_stream_lengths(body, B * R * Kl)
         elif per_image:
             (nb,) = struct.unpack("<I", body[:4])
             assert nb == B
@@ -895,7 +922,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
             self._tables._pin_in_event = torch.cuda.Event()
             self._tables._pin_in_event.record(torch.cuda.current_stream(dev))
             d_woff = torch.from_numpy(woff).to(dev)
-            _, _, ybuf = sl.decode(self._tables, d_words, d_woff, prior, B, H, W, self._scale_table_dev, lanes=Kl)
+            _, _, ybuf = sl.decode(self._tables, d_words, d_woff, prior, B, H, W, self._scale_table_dev, lanes=Kl, rows=self.stream_rows)
             sl.check()
             return ybuf
         use_graph = len(plan.groups) >= self.GRAPH_MIN_GROUPS and getattr(self, "use_hip_graphs", True) and per_image
@@ -906,12 +933,12 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
             d_woff = torch.from_numpy(woff).to(dev)
             return self._run_decode_impl(d_words, d_woff, prior, B, H, W, per_image, plan)
         # static buffers: per-image streams never exceed the encoder's slot bound plus slack
-        cap = B * (3 * n + 4 * Kl)
-        key = ("dec", B, H, W, prior is not None, plan.key, Kl)
+        cap = B * (3 * n + 4 * Kl * R)
+        key = ("dec", B, H, W, prior is not None, plan.key, Kl, R)
         entry = self._graphs.get(key)
         if entry is None:
             sw = torch.zeros((cap,), device=dev, dtype=torch.int32)
-            so = torch.zeros((B * Kl + 1,), device=dev, dtype=torch.int64)
+            so = torch.zeros((B * R * Kl + 1,), device=dev, dtype=torch.int64)
             sp = torch.empty_like(prior) if prior is not None else None
             sw[: words_np.size].copy_(stage)
             so.copy_(torch.from_numpy(woff))
@@ -999,9 +1026,12 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         dev, C = self.device, self.in_channels
         n = plan.per_image
         Kl = self.stream_lanes if per_image else 1
-        ns = B * Kl if per_image else 1
+        R = H if per_image and self.stream_rows else 1
+        ns = B * R * Kl if per_image else 1
         if Kl > 1 and any(grp["n"] % Kl for grp in plan.groups):
             raise ValueError("stream_lanes: a coding step does not divide into the lanes")
+        if R > 1 and len(plan.groups) != H * W:
+            raise ValueError("stream_rows: the coding steps are not the latent's positions in raster order")
         state = torch.zeros((ns,), device=dev, dtype=torch.int64)
         pos = torch.full((ns,), -1, device=dev, dtype=torch.int64)
         ws = self._alloc(B, H, W, prior, plan)
@@ -1019,10 +1049,11 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
             if per_image:
                 # stream b continues (decode_stream semantics, pgm_coder.py:971) with its ng symbols of this group,
                 # in place on the dense [B][n] arrays
-                # (lane streams: stream b * Kl + k with the ng / Kl symbols of its lane)
-                _lib.check(L.basic_rans_decode_batch_lanes_dev(self._tables._h, d_words.data_ptr(), d_woff.data_ptr(), idx.data_ptr(),
-                                                               grp["base"], n, Kl, ng // Kl, B, sym.data_ptr(), state.data_ptr(),
-                                                               pos.data_ptr(), K._stream()))
+                # (lane streams: stream b * Kl + k with the ng / Kl symbols of its lane; row streams: step g is position g, whose
+                # row g // W has the streams (b * H + g // W) * Kl + k.  Without rows: stream base 0, stride Kl -- the lanes entry)
+                _lib.check(L.basic_rans_decode_batch_streams_dev(self._tables._h, d_words.data_ptr(), d_woff.data_ptr(), idx.data_ptr(),
+                                                                 grp["base"], n, Kl, ng // Kl, B, (g // W) * Kl if R > 1 else 0, R * Kl,
+                                                                 sym.data_ptr(), state.data_ptr(), pos.data_ptr(), K._stream()))
             else:
                 # single stream over the whole batch: gather this group's indexes batch-major
                 gi = idx[:, grp["base"]: grp["base"] + ng].reshape(-1).contiguous()

@@ -272,6 +272,14 @@ class RansTables:
                                                                 state.data_ptr(), pos.data_ptr(), _stream()))
         return out, state, pos
 
+    def decode_batch_streams(self, words, word_off, indexes, first, stride, lanes, count, nimages, stream_first, stream_stride, out, state, pos):
+        """basic_rans_decode_batch_streams_dev: decode_batch_lanes with a stream base and stride -- the launch's stream (b, k) is
+        stream stream_first + b * stream_stride + k of ``word_off`` / ``state`` / ``pos``."""
+        _lib.check(_lib.lib().basic_rans_decode_batch_streams_dev(self._h, words.data_ptr(), word_off.data_ptr(), indexes.data_ptr(), int(first),
+                                                                  int(stride), int(lanes), int(count), int(nimages), int(stream_first),
+                                                                  int(stream_stride), out.data_ptr(), state.data_ptr(), pos.data_ptr(), _stream()))
+        return out, state, pos
+
     def decode_batch(self, words, word_off, indexes, seg, out=None, state=None, pos=None):
         words, word_off = _dev(words, torch.int32), _dev(word_off, torch.int64)
         indexes, seg = _dev(indexes, torch.int32), _dev(seg, torch.int64)
@@ -619,25 +627,26 @@ class ScanlinePlan:
             raise ValueError(f"encode schedule must be one of {SCAN_SCHEDULES}, not {schedule!r}")
         _lib.check(_lib.lib().basic_scanline_set_encode_schedule(self._h, SCAN_SCHEDULES.index(schedule)))
 
-    def choose(self, batch, height, width, table_len, schedule="auto", lane_max_batch=0, tables=None, lanes=1):
+    def choose(self, batch, height, width, table_len, schedule="auto", lane_max_batch=0, tables=None, lanes=1, rows=False):
         """What an encode call (tables None) or a decode call with that table set would run for `batch` images of a `height` x
         `width` latent (0: not known), as the library's one planner decides it -- without launching: -> (kernel, launches), kernel
         one of SCAN_KERNELS, or None where the call is left to the per-step path.  `schedule` stands for the plan's encode schedule
         (BASIC_SCAN_KERNEL wins over it); batches above `lane_max_batch` are not given to the generic and pipelined kernels.  A
         forced kernel or schedule the call does not fit raises, as the launch would.  `lanes`: the lane streams per image of a decode
-        call (a decoder wavefront each)."""
+        call (a decoder wavefront each); `rows`: the decode call brings row streams (the wavefront decode launch may serve it)."""
         if schedule not in SCAN_SCHEDULES:
             raise ValueError(f"encode schedule must be one of {SCAN_SCHEDULES}, not {schedule!r}")
         # the answer depends on nothing but these, so a repeated call (every step of a stream worker) asks the library once: a
         # library call releases the interpreter lock, and with several workers each release is a chance to wait for it again
         key = (int(batch), int(height), int(width), int(table_len), schedule, int(lane_max_batch), id(tables), os.environ.get("BASIC_SCAN_KERNEL"),
-               torch.cuda.current_device(), int(lanes))
+               torch.cuda.current_device(), int(lanes), bool(rows))
         cache = self.__dict__.setdefault("_chosen", {})
         if key not in cache:
             k, n = ctypes.c_int(), ctypes.c_int()
-            _lib.check(_lib.lib().basic_scanline_choose_lanes(self._h, tables._h if tables is not None else None, int(batch), int(lanes),
-                                                              int(height), int(width), int(table_len), SCAN_SCHEDULES.index(schedule),
-                                                              int(lane_max_batch), ctypes.byref(k), ctypes.byref(n)))
+            _lib.check(_lib.lib().basic_scanline_choose_rows(self._h, tables._h if tables is not None else None, int(batch), int(lanes),
+                                                             int(bool(rows)), int(height), int(width), int(table_len),
+                                                             SCAN_SCHEDULES.index(schedule), int(lane_max_batch), ctypes.byref(k),
+                                                             ctypes.byref(n)))
             cache[key] = ((SCAN_KERNELS[k.value] if k.value >= 0 else None), n.value, tables)   # (tables: keeps its id its own)
         return cache[key][:2]
 
@@ -646,9 +655,10 @@ class ScanlinePlan:
         _lib.check(_lib.lib().basic_scanline_can_decode(self._h, tables._h, int(batch), ctypes.byref(ok)))
         return bool(ok.value)
 
-    def decode(self, tables, d_words, d_word_off, prior, batch, h, w, table, lanes=1):
+    def decode(self, tables, d_words, d_word_off, prior, batch, h, w, table, lanes=1, rows=False):
         """-> (symbols, indexes int32 [B, H*W*C] in coding order, y_hat [B, C, H, W]).  `lanes` > 1: d_word_off holds the
-        batch * lanes + 1 offsets of the lane streams (basic_scanline_decode_lanes_dev)."""
+        batch * lanes + 1 offsets of the lane streams (basic_scanline_decode_lanes_dev); `rows`: the batch * h * lanes + 1 offsets
+        of the row streams (basic_scanline_decode_rows_dev)."""
         table = _dev(table, torch.float32)
         prior = _dev(prior, torch.float32) if prior is not None else None
         d_words, d_word_off = _dev(d_words, torch.int32), _dev(d_word_off, torch.int64)
@@ -656,10 +666,9 @@ class ScanlinePlan:
         sym = torch.empty((batch, h * w * C), device=table.device, dtype=torch.int32)
         idx = torch.empty((batch, h * w * C), device=table.device, dtype=torch.int32)
         ybuf = torch.empty((batch, C, h, w), device=table.device, dtype=torch.float32)
-        _lib.check(_lib.lib().basic_scanline_decode_lanes_dev(self._h, tables._h, d_words.data_ptr(), d_word_off.data_ptr(),
-                                                              prior.data_ptr() if prior is not None else None, batch, int(lanes), h, w,
-                                                              table.data_ptr(), table.numel(), sym.data_ptr(), idx.data_ptr(),
-                                                              ybuf.data_ptr(), _stream()))
+        entry = _lib.lib().basic_scanline_decode_rows_dev if rows else _lib.lib().basic_scanline_decode_lanes_dev
+        _lib.check(entry(self._h, tables._h, d_words.data_ptr(), d_word_off.data_ptr(), prior.data_ptr() if prior is not None else None, batch,
+                         int(lanes), h, w, table.data_ptr(), table.numel(), sym.data_ptr(), idx.data_ptr(), ybuf.data_ptr(), _stream()))
         return sym, idx, ybuf
 
     def check(self):

@@ -53,7 +53,8 @@ def topogroup_ar_codec(method="checkerboard", N=128, M=192, channel_groups=1, ex
 BASIC_WIDTHS = [48, 72, 96, 144, 192]
 
 
-def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset=None, combined_entropy_coder=False, stream_lanes=1):
+def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset=None, combined_entropy_coder=False, stream_lanes=1,
+                stream_rows=False):
     """BaSIC "hyperprior-ar-sc-slimmable-full-dynamic" (configs/presets/lossy_latent_graph_scalable_ar_models.py:
     73-197): slimmable g_a/g_s, MS-slimmable h_a/h_s, 192-ch EntropyBottleneck, scanline AR y-coder with the
     masked-conv context model, four slim controller nodes selected per complexity level.
@@ -68,7 +69,11 @@ def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset
     until a checkpoint is loaded).
 
     ``stream_lanes`` = K > 1: the scan-line y-coder writes K lane streams per image ("Lane streams": a format of
-    this library, not readable by the reference); in the combined bank only the scan-line member gets it."""
+    this library, not readable by the reference); in the combined bank only the scan-line member gets it.
+
+    ``stream_rows`` = True: the scan-line y-coder writes one stream per latent row (and lane) of every image ("Row
+    streams": not readable by the reference either), which lets the decode launch walk an image's rows in parallel; in the combined
+    bank only the scan-line member gets it."""
     from .modules.prior_model.prior_coder.pgm_coder import (CombinedNNTrainablePGMPriorCoder,
                                                             GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder,
                                                             TopoGroupDynamicMaskConv2dContextModel)
@@ -91,7 +96,7 @@ def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset
         g = torch.Generator().manual_seed(1234)
         logits = lambda G, L: torch.randn(1, G * L, 2, 2, generator=g)   # predictor output: out_channels = G * L, 2 x 2 patch
         y_coder = CombinedNNTrainablePGMPriorCoder([
-            ar_coder(default_topo_group_method="scanline", stream_lanes=stream_lanes),
+            ar_coder(default_topo_group_method="scanline", stream_lanes=stream_lanes, stream_rows=stream_rows),
             ar_coder(channel_groups=4, topo_group_predictor=logits(4, 8)),    # 8-stage (:270-289)
             ar_coder(channel_groups=4, topo_group_predictor=logits(4, 6)),    # 6-stage
             ar_coder(topo_group_predictor=logits(1, 16)),                      # 4-stage (channel_groups 1, 16 logits)
@@ -104,7 +109,7 @@ def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset
         controllers.append("pgmy")
         y_mapping = {"pgmy": "blend_weight", "z": "prior"}
     else:
-        y_coder = ar_coder(default_topo_group_method="scanline", stream_lanes=stream_lanes)
+        y_coder = ar_coder(default_topo_group_method="scanline", stream_lanes=stream_lanes, stream_rows=stream_rows)
 
     def slim_node():
         return IndexSelectParameterGeneratorWrapper(

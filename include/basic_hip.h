@@ -146,6 +146,14 @@ int basic_rans_decode_batch_strided_dev(const basic_rans_tables *t, const uint32
 int basic_rans_decode_batch_lanes_dev(const basic_rans_tables *t, const uint32_t *d_words, const int64_t *d_word_off,
                                       const int32_t *d_indexes, int64_t first, int64_t stride, int lanes, int64_t count,
                                       int nimages, int32_t *d_out_symbols, uint64_t *d_state, int64_t *d_pos, void *hip_stream);
+/* basic_rans_decode_batch_lanes_dev with a stream base and stride, for the ROW STREAMS of the scan-line coder (stream_rows,
+ * INTEGRATION.md): the launch's stream (b, k), b < nimages, k < lanes, is stream stream_first + b*stream_stride + k of d_word_off /
+ * d_state / d_pos and continues with the `count` symbols at first + b*stride + k*count.  The coder calls it per position p with
+ * stream_first = (p / W) * lanes, stream_stride = H * lanes.  stream_stride >= lanes; (0, lanes) is the lanes entry; same kernel. */
+int basic_rans_decode_batch_streams_dev(const basic_rans_tables *t, const uint32_t *d_words, const int64_t *d_word_off,
+                                        const int32_t *d_indexes, int64_t first, int64_t stride, int lanes, int64_t count,
+                                        int nimages, int stream_first, int stream_stride, int32_t *d_out_symbols,
+                                        uint64_t *d_state, int64_t *d_pos, void *hip_stream);
 
 /* ======================================================================================
  * 4. Entropy-parameter kernels (coalesced elementwise, fused quantise + table index).
@@ -391,6 +399,17 @@ int basic_scanline_decode_lanes_dev(basic_scanline_plan *p, const basic_rans_tab
                                     const int64_t *d_word_off, const float *d_prior, int batch, int lanes, int h, int w,
                                     const float *d_table, int table_len, int32_t *d_symbols, int32_t *d_indexes, float *d_ybuf,
                                     void *hip_stream);
+/* basic_scanline_decode_lanes_dev for ROW STREAMS (stream_rows; not a format the reference reads): batch * h * lanes
+ * streams, stream s = (b * h + r) * lanes + k = d_words[d_word_off[s] .. d_word_off[s + 1]) carries the symbols of row r of image
+ * b, channels [k L, (k + 1) L), in coding order (lanes == 1: the whole row).  Where batch * h <= 64 columns and the compute
+ * workgroups plus ceil(batch * h * lanes / 4) decoder workgroups are resident, the call may run as the WAVEFRONT decode launch
+ * (w + (ksize / 2 + 2) * (h - 1) steps, one decoder wavefront per stream; BASIC_SCAN_KERNEL=wavefront forces it, "does not fit"
+ * otherwise); else the raster kernels read the same streams, a decoder wavefront changing stream at every row start.
+ * Everything written is what basic_scanline_decode_dev writes. */
+int basic_scanline_decode_rows_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
+                                   const int64_t *d_word_off, const float *d_prior, int batch, int lanes, int h, int w,
+                                   const float *d_table, int table_len, int32_t *d_symbols, int32_t *d_indexes, float *d_ybuf,
+                                   void *hip_stream);
 /* *ok = 1 when basic_scanline_decode_dev can serve `batch` streams of `tables` on the current device (fast search image that
  * fits the LDS; compute + decoder workgroups <= compute units); otherwise the caller decodes with the per-step path, which
  * codes the same integers. */
@@ -456,6 +475,11 @@ int basic_scanline_choose(const basic_scanline_plan *p, const basic_rans_tables 
  * the per-step path.  Encode calls do not depend on `lanes`; lanes == 1 is basic_scanline_choose. */
 int basic_scanline_choose_lanes(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int lanes, int h, int w,
                                 int table_len, int schedule, int lane_max_batch, int *kernel, int *launches);
+/* basic_scanline_choose_lanes with `rows` != 0 for a decode call over row streams (basic_scanline_decode_rows_dev): the wavefront
+ * decode launch is considered (its decoder workgroups: batch * h * lanes streams), the raster kernels count batch * lanes.  Encode
+ * calls do not depend on `rows`; rows == 0 is basic_scanline_choose_lanes. */
+int basic_scanline_choose_rows(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int lanes, int rows, int h, int w,
+                               int table_len, int schedule, int lane_max_batch, int *kernel, int *launches);
 int basic_scanline_status(basic_scanline_plan *p, void *hip_stream, int *poisoned);
 void basic_scanline_plan_destroy(basic_scanline_plan *p);
 

@@ -15,12 +15,15 @@ c = c.eval().cuda()
 c.update_state()
 
 
-def lanes_probe(lanes_list, shapes, runs):
+def lanes_probe(lanes_list, shapes, runs, rows=False):
     """--lanes K [K ...]: lane streams (stream_lanes = K) against one stream per image.  Per shape and K, `runs` runs of five calls
     each (the median of a run is its figure; min - max over the runs is the spread): GPU time of the persistent decode launch
     (ScanlinePlan.decode, or the whole per-step decode where the planner leaves the call to it), GPU time of the y rANS encode (pack
     + batched encoder), wall time of coder.encode / coder.decode, and the bytes.  K = 1 uses only what the library had before lanes,
-    so the same script measures the commit before them.  BASIC_SCAN_PROFILE=1 adds the kernel's per-step split (stderr)."""
+    so the same script measures the commit before them.  BASIC_SCAN_PROFILE=1 adds the kernel's per-step split (stderr).
+    --rows: the same figures with row streams (stream_rows = True: one stream per latent row and lane; the decode launch is the
+    wavefront's where the planner takes it, BASIC_SCAN_KERNEL forces another); without it the script uses nothing the library lacked
+    before row streams, so the same --lanes run on the commit before them is the yardstick."""
     import numpy as np
     from cbench_basic_amd.nn import kernels as K
 
@@ -49,10 +52,13 @@ def lanes_probe(lanes_list, shapes, runs):
                 c.stream_lanes = lanes
             elif lanes != 1:
                 raise SystemExit("this library has no lane streams: --lanes 1 only")
+            if rows:
+                c.stream_rows = True
             c.batch_stream_mode = "per_image"   # (K = 1 at batch 1: framed like the lanes, so that the bytes compare)
+            R = H if rows else 1   # streams per image and lane
             sym, idx, _, plan = c._run_encode(y, prior)
             data = c.encode(y, prior=prior)
-            nstreams = B * lanes
+            nstreams = B * R * lanes
             lens = np.frombuffer(data, dtype="<u4", count=nstreams, offset=4).astype(np.int64)
             woff = np.concatenate([[0], np.cumsum(lens // 4)]).astype(np.int64)
             d_words = torch.from_numpy(np.frombuffer(data, dtype=np.int32, count=int(woff[-1]), offset=4 + 4 * nstreams).copy()).cuda()
@@ -60,11 +66,16 @@ def lanes_probe(lanes_list, shapes, runs):
             sl = c._scanline_plan(plan, prior, B, decode=True, width=W, height=H)
             if sl is None:
                 dec, served = (lambda: c._run_decode_impl(d_words, d_woff, prior, B, H, W, True, plan)), "per-step"
+            elif rows:
+                dec, served = (lambda: sl.decode(c._tables, d_words, d_woff, prior, B, H, W, c._scale_table_dev, lanes=lanes, rows=True)), None
             elif lanes == 1:
                 dec, served = (lambda: sl.decode(c._tables, d_words, d_woff, prior, B, H, W, c._scale_table_dev)), None
             else:
                 dec, served = (lambda: sl.decode(c._tables, d_words, d_woff, prior, B, H, W, c._scale_table_dev, lanes=lanes)), None
-            if lanes == 1:
+            if rows:
+                pack = (lambda: K.lanes_pack(sym, idx, B * H, W, C, lanes)) if lanes > 1 else (lambda: (sym, idx))
+                rans = lambda: c._tables.encode_batch_begin(*[t.reshape(-1) for t in pack()], n // lanes // H)
+            elif lanes == 1:
                 rans = lambda: c._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), n)
             else:
                 rans = lambda: c._tables.encode_batch_begin(*[t.reshape(-1) for t in K.lanes_pack(sym, idx, B, H * W, C, lanes)], n // lanes)
@@ -78,18 +89,19 @@ def lanes_probe(lanes_list, shapes, runs):
             for _ in range(runs):
                 r["dec"].append(gpu_ms(dec)); r["rans"].append(gpu_ms(rans))
                 r["enc_wall"].append(wall_ms(lambda: c.encode(y, prior=prior))); r["dec_wall"].append(wall_ms(lambda: c.decode(data, prior=prior)))
-            print(f"B={B:3d} {H}x{W} K={lanes:2d} [{served}]: decode launch {spread(r['dec'])} ms | y rANS encode {spread(r['rans'])} ms | "
+            print(f"B={B:3d} {H}x{W} K={lanes:2d}{' rows' if rows else ''} [{served}]: decode launch {spread(r['dec'])} ms | y rANS encode {spread(r['rans'])} ms | "
                   f"coder.encode {spread(r['enc_wall'])} ms | coder.decode {spread(r['dec_wall'])} ms | {len(data)} bytes ({len(data) / B:.0f} per image)", flush=True)
 
 
-if "--lanes" in sys.argv:
+if "--lanes" in sys.argv or "--rows" in sys.argv:
     import argparse
     ap = argparse.ArgumentParser()
-    ap.add_argument("--lanes", type=int, nargs="+", required=True, help="lane counts to measure (1 = one stream per image)")
+    ap.add_argument("--lanes", type=int, nargs="+", default=[1], help="lane counts to measure (1 = one stream per image)")
     ap.add_argument("--shapes", type=int, nargs="+", default=[1, 32, 48, 64, 16, 16], help="B H W [B H W ...]")
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--rows", action="store_true", help="row streams (stream_rows = True) at every lane count")
     a = ap.parse_args()
-    lanes_probe(a.lanes, [tuple(a.shapes[i: i + 3]) for i in range(0, len(a.shapes), 3)], a.runs)
+    lanes_probe(a.lanes, [tuple(a.shapes[i: i + 3]) for i in range(0, len(a.shapes), 3)], a.runs, rows=a.rows)
     sys.exit(0)
 
 shapes = ((1, 32, 48), (8, 16, 16), (64, 16, 16), (24, 32, 48))

@@ -44,8 +44,12 @@ def main():
                          "items are coded concurrently (the reference's multiprocessing pool, basic_benchmark.py:829-858, GPU-native)")
     ap.add_argument("--stream-lanes", type=int, default=1,
                     help="--codec basic: lane streams per image of the scan-line y-coder (a format the reference does not read)")
+    ap.add_argument("--stream-rows", action="store_true",
+                    help="--codec basic: one stream per latent row of the scan-line y-coder (a format the reference does not read)")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
+    if args.stream_rows and args.codec != "basic":
+        ap.error("--stream-rows needs --codec basic")
     if args.stream_lanes != 1 and args.codec != "basic":
         ap.error("--stream-lanes needs --codec basic")
     if args.workers > 1:   # before HIP initialises: one hardware queue per worker stream
@@ -62,7 +66,7 @@ def main():
     else:
         ds = RandomImageDataset(num=args.synthetic or 8, size=(3, args.height or args.size, args.width or args.size))
     batches = list(batched(ds, args.batch_size))
-    builders = dict(hyperprior=presets.hyperprior_codec, basic=lambda **kw: presets.basic_codec(stream_lanes=args.stream_lanes, **kw),
+    builders = dict(hyperprior=presets.hyperprior_codec, basic=lambda **kw: presets.basic_codec(stream_lanes=args.stream_lanes, stream_rows=args.stream_rows, **kw),
                     topogroup=lambda: presets.topogroup_ar_codec(method=args.method))
     codec = builders["basic"](search_dataset=batches) if (args.codec == "basic" and args.complexity_search) else builders[args.codec]()
     if args.checkpoint:
