@@ -16,6 +16,11 @@ class BasicHipError(RuntimeError):
     pass
 
 
+class BasicHipInvalid(BasicHipError, ValueError):
+    """A call the library refuses (BASIC_ERR_INVALID / BASIC_ERR_NOT_INIT): a ValueError, as the reference's pybind11 layer
+    raises, and like every other failure of the library a BasicHipError."""
+
+
 _lib = None
 
 c_i32p = ctypes.c_void_p  # all array arguments are passed as raw addresses
@@ -81,6 +86,8 @@ _SIGNATURES = {
     "basic_mconv_forward_pos_dev": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _I, _I, _P]),
     "basic_mconv_forward_step_dev": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _I, _I, _I, _P, _P]),
     "basic_mconv_forward_ex_dev": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "basic_mconv_last_kernel": (_I, [_P, _P]),
+    "basic_mconv_choose": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _L, _P]),
     "basic_mconv_plan_destroy": (None, [_P]),
     "basic_scanline_plan_create": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "basic_scanline_plan_info": (_I, [_P, _P, _P]),
@@ -143,7 +150,7 @@ def check(rc):
         return
     msg = last_error()
     if rc in (ERR_INVALID, ERR_NOT_INIT):
-        raise ValueError(msg)  # py::value_error in the reference
+        raise BasicHipInvalid(msg)  # py::value_error in the reference
     if rc == ERR_NO_DEVICE:
         raise BasicHipError("no MI355X/HIP device available: " + msg)
     if rc == ERR_OVERFLOW:

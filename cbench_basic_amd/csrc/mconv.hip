@@ -437,8 +437,10 @@ __global__ __launch_bounds__(kDmaThreads, 2) void masked_conv_dma_kernel(const M
     }
     __syncthreads();
     if (g.step != kNoStep && s_open[2] == 0u) return;   // workgroup-uniform
-    uint64_t todo = static_cast<uint64_t>(__builtin_amdgcn_readfirstlane(s_open[0])) |
-                    (static_cast<uint64_t>(__builtin_amdgcn_readfirstlane(s_open[1])) << 32);
+    // (readfirstlane returns an int: without the uint32_t step an open slab 31 sign-extends into phantom slabs 32 .. 63, whose
+    // weight stages are read past the end of the packed weights -- times zero activations, so only NaN / Inf garbage shows)
+    uint64_t todo = static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(s_open[0]))) |
+                    (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(s_open[1]))) << 32);
     const int stages_per_slab = g.gs_in / kDmaCK;
     const int nstages = __builtin_popcountll(todo) * stages_per_slab;
 
@@ -589,6 +591,7 @@ struct basic_mconv_plan {
     mutable std::mutex mu;
     mutable float *d_scratch = nullptr;
     mutable int32_t *d_flags = nullptr;
+    mutable int last_kernel = -1;   // basic_mconv_last_kernel
 };
 
 extern "C" void basic_mconv_plan_destroy(basic_mconv_plan *p)
@@ -603,10 +606,53 @@ extern "C" void basic_mconv_plan_destroy(basic_mconv_plan *p)
     delete p;
 }
 
-static bool dma_layer_ok(const basic_mconv_plan *p)
+static bool dma_layer_ok(int cin, int cout, int ksize, int gi, int go)
 {
-    const int gs_in = p->cin / p->gi, gs_out = p->cout / p->go;
-    return gs_in % kKB == 0 && gs_out % kDmaRows == 0 && p->ksize * p->ksize * p->gi <= kDmaMaxSlabs;
+    const int gs_in = cin / gi, gs_out = cout / go;
+    return gs_in % kKB == 0 && gs_out % kDmaRows == 0 && ksize * ksize * gi <= kDmaMaxSlabs;
+}
+
+// Which kernel serves a launch: every one of them sums in the canonical order, so this is a matter of speed only and may
+// depend on the launch size.  BASIC_MCONV_KERNEL = dma | gather | block forces one where it applies (tests drive all three
+// over the same inputs and require identical bits); a forced kernel that does not apply leaves the launch to the gather
+// kernel.  The switch-overs are in (position tile x row tile) counts.  Pure host code: mconv_forward and basic_mconv_choose
+// both ask here.  dma_ok = the layer has the LDS-DMA kernel's weight image (dma_layer_ok).
+static int choose_kernel(int cin, int cout, int ksize, int gi, int go, int batch, int h, int w, int64_t n_pos, bool dma_ok)
+{
+    constexpr int64_t kBlockBelow = 256, kDmaFrom = 4096;
+    const int gs_in = cin / gi, gs_out = cout / go;
+    const int64_t ptiles = (n_pos + 31) / 32, rtiles = static_cast<int64_t>((gs_out + 31) / 32) * go;
+    const int64_t tiles = ptiles * rtiles;
+    const int64_t x_bytes = static_cast<int64_t>(batch) * cin * h * w * 4;
+    const int64_t units = static_cast<int64_t>(ksize) * ksize * gi * ((gs_in + kKB - 1) / kKB);
+    const bool dma_fits = dma_ok && x_bytes < (1ll << 31), block_fits = tiles * units <= kMaxUnits;
+    bool use_dma = dma_fits && tiles >= kDmaFrom;
+    bool use_block = !use_dma && tiles < kBlockBelow && block_fits;
+    if (const char *force = std::getenv("BASIC_MCONV_KERNEL")) {
+        if (!std::strcmp(force, "dma")) { use_dma = dma_fits; use_block = false; }
+        else if (!std::strcmp(force, "block")) { use_dma = false; use_block = block_fits; }
+        else if (!std::strcmp(force, "gather")) { use_dma = false; use_block = false; }
+    }
+    return use_dma ? BASIC_MCONV_KERNEL_DMA : use_block ? BASIC_MCONV_KERNEL_BLOCK : BASIC_MCONV_KERNEL_GATHER;
+}
+
+extern "C" int basic_mconv_choose(int cin, int cout, int ksize, int in_groups, int out_groups, int batch, int h, int w,
+                                  int64_t n_pos, int *kernel)
+{
+    BASIC_REQUIRE(kernel && cin >= 1 && cout >= 1 && (ksize == 1 || ksize == 3 || ksize == 5) && in_groups >= 1 && out_groups >= 1 &&
+                  cin % in_groups == 0 && cout % out_groups == 0 && batch >= 1 && h >= 1 && w >= 1 && n_pos >= 0,
+                  "mconv_choose: bad argument");
+    *kernel = n_pos == 0 ? BASIC_MCONV_KERNEL_NONE
+                         : choose_kernel(cin, cout, ksize, in_groups, out_groups, batch, h, w, n_pos,
+                                         dma_layer_ok(cin, cout, ksize, in_groups, out_groups));
+    return BASIC_OK;
+}
+
+extern "C" int basic_mconv_last_kernel(const basic_mconv_plan *p, int *kernel)
+{
+    BASIC_REQUIRE(p && kernel, "mconv_last_kernel: bad argument");
+    *kernel = p->last_kernel;
+    return BASIC_OK;
 }
 
 extern "C" int basic_mconv_plan_create(const float *weight, const float *bias, int cin, int cout, int ksize,
@@ -638,7 +684,7 @@ extern "C" int basic_mconv_plan_create(const float *weight, const float *bias, i
     const int span = 32 * p->mt;
     std::vector<float> wp(static_cast<size_t>(ntaps) * cin * p->coutp, 0.f), hb(p->coutp, 0.f);
     std::vector<float> w1(p->mt > 1 ? wp.size() : 0, 0.f);
-    const bool dma = dma_layer_ok(p);
+    const bool dma = dma_layer_ok(cin, cout, ksize, in_groups, out_groups);
     std::vector<float> wa(dma ? static_cast<size_t>(ntaps) * cin * cout : 0, 0.f);
     for (int o = 0; o < cout; ++o) {
         const int grp = o / gs_out, r = o - grp * gs_out;
@@ -709,8 +755,8 @@ static int mconv_forward(const basic_mconv_plan *p, const float *d_x, const int3
                          int out_channel_offset, int step, const int32_t *d_first, const int32_t *d_in_perm,
                          const int32_t *d_out_perm, void *hip_stream)
 {
-    BASIC_REQUIRE(p && d_x && d_topo_in && d_topo_out && d_pos && d_y && batch >= 1 && h >= 1 && w >= 1 && n_pos >= 0,
-                  "mconv_forward_pos: bad argument");
+    BASIC_REQUIRE(p && d_x && d_topo_in && d_topo_out && (d_pos || n_pos == 0) && d_y && batch >= 1 && h >= 1 && w >= 1 && n_pos >= 0,
+                  "mconv_forward_pos: bad argument");   // an empty position list may come without an address
     BASIC_REQUIRE(out_channel_offset >= 0 && out_channel_offset + p->cout <= out_channels_total,
                   "mconv_forward_pos: output channel window out of range");
     BASIC_REQUIRE(static_cast<int64_t>(batch) * h * w < (1ll << 31), "mconv_forward_pos: position index overflow");
@@ -725,22 +771,11 @@ static int mconv_forward(const basic_mconv_plan *p, const float *d_x, const int3
     g.mt = p->mt; g.step = step; g.first = d_first; g.in_perm = d_in_perm; g.out_perm = d_out_perm;
     const unsigned ptiles = static_cast<unsigned>((n_pos + 31) / 32), rtiles = static_cast<unsigned>(g.tiles_per_group * g.go);
     hipStream_t st = as_stream(hip_stream);
-    // Which kernel: every one of them sums in the canonical order, so this is a matter of speed only and may depend on the
-    // launch size.  BASIC_MCONV_KERNEL = dma | gather | block forces one where it applies (tests drive all three over the
-    // same inputs and require identical bits).  The switch-overs are in (position tile x row tile) counts.
-    const int64_t tiles = static_cast<int64_t>(ptiles) * rtiles;
-    constexpr int64_t kBlockBelow = 256, kDmaFrom = 4096;
-    const char *force = std::getenv("BASIC_MCONV_KERNEL");
     const int64_t x_bytes = static_cast<int64_t>(batch) * p->cin * h * w * 4;
     const int blocks_per_slab = (g.gs_in + kKB - 1) / kKB;
     const int64_t units = static_cast<int64_t>(g.ntaps) * g.gi * blocks_per_slab;
-    bool use_dma = p->d_wa && x_bytes < (1ll << 31) && tiles >= kDmaFrom;
-    bool use_block = !use_dma && tiles < kBlockBelow && tiles * units <= kMaxUnits;
-    if (force) {
-        if (!std::strcmp(force, "dma")) { use_dma = p->d_wa && x_bytes < (1ll << 31); use_block = false; }
-        else if (!std::strcmp(force, "block")) { use_dma = false; use_block = tiles * units <= kMaxUnits; }
-        else if (!std::strcmp(force, "gather")) { use_dma = false; use_block = false; }
-    }
+    const int kernel = choose_kernel(p->cin, p->cout, p->ksize, p->gi, p->go, batch, h, w, n_pos, p->d_wa != nullptr);
+    const bool use_dma = kernel == BASIC_MCONV_KERNEL_DMA, use_block = kernel == BASIC_MCONV_KERNEL_BLOCK;
     if (use_dma) {
         g.w = p->d_wa;
         g.n_rchunks = p->cout / kDmaRows;
@@ -775,5 +810,6 @@ static int mconv_forward(const basic_mconv_plan *p, const float *d_x, const int3
     else
         hipLaunchKernelGGL((masked_conv_gather_kernel<1>), dim3(ptiles, rtiles), dim3(64), 0, st, g);
     BASIC_HIP_TRY(hipGetLastError());
+    p->last_kernel = kernel;
     return BASIC_OK;
 }

@@ -89,6 +89,18 @@ class ConvPlan:
         return out
 
 
+MCONV_KERNEL_NONE, MCONV_KERNEL_GATHER, MCONV_KERNEL_BLOCK, MCONV_KERNEL_DMA = -1, 0, 1, 2
+
+
+def mconv_choose(cin, cout, ksize, in_groups, out_groups, batch, h, w, n_pos):
+    """MCONV_KERNEL_* a MaskedConvPlan of this layer would launch for n_pos listed positions of `batch` h x w maps
+    (basic_mconv_choose: host code, no device needed; honours BASIC_MCONV_KERNEL)."""
+    k = ctypes.c_int(MCONV_KERNEL_NONE)
+    _lib.check(_lib.lib().basic_mconv_choose(int(cin), int(cout), int(ksize), int(in_groups), int(out_groups), int(batch), int(h),
+                                             int(w), int(n_pos), ctypes.byref(k)))
+    return k.value
+
+
 class MaskedConvPlan:
     """basic_mconv_plan_*: topo-group masked conv evaluated at a position list."""
 
@@ -109,6 +121,13 @@ class MaskedConvPlan:
                 _lib.lib().basic_mconv_plan_destroy(h)
             except Exception:
                 pass
+
+    @property
+    def last_kernel(self):
+        """MCONV_KERNEL_* the last call launched; MCONV_KERNEL_NONE before any launch."""
+        k = ctypes.c_int(MCONV_KERNEL_NONE)
+        _lib.check(_lib.lib().basic_mconv_last_kernel(self._h, ctypes.byref(k)))
+        return k.value
 
     def __call__(self, x, topo_in, topo_out, pos, out, out_offset=0, step=None, first_step=None, in_perm=None, out_perm=None):
         """step / first_step: the coding-loop variant that only evaluates the (output group, position) pairs of the current

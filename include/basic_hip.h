@@ -294,6 +294,20 @@ int basic_mconv_forward_ex_dev(const basic_mconv_plan *p, const float *d_x, cons
                                float *d_y, int out_channels_total, int out_channel_offset, int use_step, int step,
                                const int32_t *d_first_step, const int32_t *d_in_perm, const int32_t *d_out_perm,
                                void *hip_stream);
+/* Which kernel serves a launch (csrc/mconv.hip: all of them sum in one canonical order, so the choice is a matter of speed). */
+#define BASIC_MCONV_KERNEL_NONE (-1) /* no launch yet, or nothing to launch (n_pos == 0) */
+#define BASIC_MCONV_KERNEL_GATHER 0
+#define BASIC_MCONV_KERNEL_BLOCK 1
+#define BASIC_MCONV_KERNEL_DMA 2
+/* *kernel = what the last forward call on this plan launched; BASIC_MCONV_KERNEL_NONE before any launch. */
+int basic_mconv_last_kernel(const basic_mconv_plan *p, int *kernel);
+/* What a forward call of such a layer would launch for n_pos listed positions of `batch` h x w maps, without a plan or a
+ * device: one host function in csrc/mconv.hip answers this and picks the kernel of every forward call.  It honours the
+ * environment variable BASIC_MCONV_KERNEL = gather | block | dma; a forced kernel that does not serve the launch (block: more
+ * than 4096 (tile, block) units; dma: a layer without 64-channel input groups, 128-row output groups and at most 64 (tap,
+ * input group) slabs) leaves it to the gather kernel. */
+int basic_mconv_choose(int cin, int cout, int ksize, int in_groups, int out_groups, int batch, int h, int w, int64_t n_pos,
+                       int *kernel);
 void basic_mconv_plan_destroy(basic_mconv_plan *p);
 
 /* ======================================================================================

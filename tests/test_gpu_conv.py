@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import mconv_exact
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
@@ -207,10 +209,12 @@ def test_masked_conv_positions(cfg):
 
 
 def _run_mconv_variants(plans, x, topo_in, topo_out, sel, cout, off, variants, **call):
-    """The same launch through several (plan, BASIC_MCONV_KERNEL) variants; returns the outputs on the host."""
+    """The same launch through several (plan, BASIC_MCONV_KERNEL) variants; returns the outputs on the host and the kernel
+    that ran each of them (MaskedConvPlan.last_kernel: a forced kernel that does not take the launch leaves it to the gather
+    kernel)."""
     import os
     B, _, H, W = x.shape
-    outs = []
+    outs, ran = [], []
     for pl, kernel in variants:
         os.environ["BASIC_MCONV_KERNEL"] = kernel
         try:
@@ -220,7 +224,8 @@ def _run_mconv_variants(plans, x, topo_in, topo_out, sel, cout, off, variants, *
         finally:
             del os.environ["BASIC_MCONV_KERNEL"]
         outs.append(out.cpu())
-    return outs
+        ran.append(plans[pl].last_kernel)
+    return outs, ran
 
 
 @pytest.mark.parametrize("seed", range(40))
@@ -232,17 +237,8 @@ def test_masked_conv_fuzz(seed):
     bit: which kernel serves a launch may depend on the batch, the integers the coder derives from the sums may not."""
     import os
     from cbench_basic_amd.nn import kernels as K
-    rng = np.random.default_rng(900 + seed)
-    gi, go = int(rng.choice([1, 2, 3, 4, 6])), int(rng.choice([1, 2, 3, 4, 6]))
-    cin, cout = gi * int(rng.integers(1, 40)), go * int(rng.integers(1, 40))
-    if seed % 2:  # whole 32-row tiles per group: 1..6 tiles -> the 1/2/3/4-tiles-per-wave variants
-        cout = go * 32 * int(rng.integers(1, 7))
-    if seed % 4 == 3:  # a layer the LDS-DMA kernel takes: 128-row chunks, 32-channel stages (blocks of 64 and a 32 / 96 remainder)
-        gi, go = int(rng.choice([1, 2])), int(rng.choice([1, 2]))
-        cin, cout = gi * 32 * int(rng.integers(1, 6)), go * 128 * int(rng.integers(1, 3))
-    k = int(rng.choice([1, 3, 5]))
-    same = bool(rng.integers(0, 2))
-    B, H, W = int(rng.integers(1, 4)), int(rng.integers(2, 20)), int(rng.integers(2, 20))
+    geo = mconv_exact.fuzz_geometry(seed)   # shared with test_cpu_mconv_exact.py, which counts the kernels the seeds reach
+    gi, go, cin, cout, k, same, B, H, W = (geo[n] for n in ("gi", "go", "cin", "cout", "k", "same", "B", "H", "W"))
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(B, cin, H, W, generator=g)
     w = torch.randn(cout, cin, k, k, generator=g) * (1.0 / (cin * k * k) ** 0.5)
@@ -256,11 +252,17 @@ def test_masked_conv_fuzz(seed):
         plan_mt1 = K.MaskedConvPlan(w, b, gi, go, same)
     finally:
         del os.environ["BASIC_MCONV_MAX_MT"]
-    npos = int(rng.integers(1, B * H * W + 1))
+    npos, off = geo["npos"], geo["off"]
     sel = torch.randperm(B * H * W, generator=g)[:npos].sort().values.int()
-    off = int(rng.choice([0, 3]))
-    outs = _run_mconv_variants(dict(p=plan, p1=plan_mt1), x, topo_in, topo_out, sel, cout, off,
-                               [("p", "gather"), ("p1", "gather"), ("p", "block"), ("p", "dma")])
+    variants = [("p", "gather"), ("p1", "gather"), ("p", "block"), ("p", "dma")]
+    outs, ran = _run_mconv_variants(dict(p=plan, p1=plan_mt1), x, topo_in, topo_out, sel, cout, off, variants)
+    for (_, kernel), got in zip(variants, ran):   # the kernel the library's chooser names for this launch really ran
+        os.environ["BASIC_MCONV_KERNEL"] = kernel
+        try:
+            assert got == K.mconv_choose(cin, cout, k, gi, go, B, H, W, npos), f"forced {kernel}: kernel {got} ran"
+        finally:
+            del os.environ["BASIC_MCONV_KERNEL"]
+    assert ran[0] == ran[1] == K.MCONV_KERNEL_GATHER
     for i in (1, 2, 3):
         assert torch.equal(outs[0], outs[i]), f"kernel variant {i} differs from the gather kernel"
     mask = torch.zeros(B * H * W, dtype=torch.bool)
@@ -312,10 +314,24 @@ def test_masked_conv_codec_sized_layers_all_kernels_identical(case):
         x_in = xp.reshape(B, cin, H, W)
     else:
         perm, x_in = None, x
-    outs = _run_mconv_variants(dict(p=plan), x_in, topo_in, topo_out, sel, cout, 0,
-                               [("p", "gather"), ("p", "dma"), ("p", "block")], **call)
+    outs, ran = _run_mconv_variants(dict(p=plan), x_in, topo_in, topo_out, sel, cout, 0,
+                                    [("p", "gather"), ("p", "dma"), ("p", "block")], **call)
+    assert ran[:2] == [K.MCONV_KERNEL_GATHER, K.MCONV_KERNEL_DMA]
     assert torch.equal(outs[0], outs[1]), "LDS-DMA kernel differs from the gather kernel"
     assert torch.equal(outs[0], outs[2]), "block kernel differs from the gather kernel"
+    # 1024 positions are more (tile, block) units than the block kernel takes (18432 / 28800 / 18432 > 4096: the third run above
+    # fell back to the gather kernel); the first 64 listed positions are 1152 / 1800 / 1152 units, and the block kernel runs
+    few, ran_few = _run_mconv_variants(dict(p=plan), x_in, topo_in, topo_out, sel[:64], cout, 0, [("p", "gather"), ("p", "block")], **call)
+    assert ran_few == [K.MCONV_KERNEL_GATHER, K.MCONV_KERNEL_BLOCK]
+    assert torch.equal(few[0], few[1]), "block kernel differs from the gather kernel"
+    in_few = torch.zeros(B * H * W, dtype=torch.bool)
+    in_few[sel[:64].long()] = True
+    in_few = in_few.reshape(B, H * W)
+    if perm is not None:
+        in_few = in_few[:, torch.argsort(perm.long())]   # slot -> position
+    in_few = in_few.reshape(B, 1, H, W).expand(B, cout, H, W)
+    assert torch.equal(few[1][in_few], outs[0][in_few]), "a launch of 64 positions differs from the launch of all 1024"
+    assert torch.all(few[1][~in_few] == -7.0)
     if perm is not None:   # back to row-major planes for the comparison with the reference
         outs = [o.reshape(B, cout, H * W)[:, :, perm.long()].reshape(B, cout, H, W) for o in outs]
     if case != "step":
@@ -328,6 +344,14 @@ def test_masked_conv_codec_sized_layers_all_kernels_identical(case):
     else:   # only (group, position) pairs whose id equals the step were written
         wrote = (outs[1] != -7.0).reshape(B, 4, cout // 4, H, W).any(2)
         assert torch.equal(wrote, ((topo_out == 3)[None] & (cb == 1)[None, None]).expand(B, -1, -1, -1))
+        # ... with the values of the operator (mconv_exact.reference: fp64, and its own statement of the step rule)
+        r = mconv_exact.reference(w.numpy(), b.numpy(), x.numpy(), topo_in.numpy(), topo_out.numpy(), same, mconv_exact.ACT_LEAKY,
+                                  sel.numpy(), 3, topo_in.min(0).values.numpy())
+        needs = torch.from_numpy(np.repeat(r["needs"], cout // 4, axis=1))
+        assert torch.equal(needs, outs[1] != -7.0)
+        ref = torch.from_numpy(r["out"])
+        err = (outs[1] - ref).abs()[needs].max()
+        assert err <= TOL * max(1.0, float(ref[needs].abs().max())), float(err)
 
 
 def test_entropy_param_kernels():
