@@ -5,25 +5,16 @@
 #include <stdio.h>
 #include <string>
 
-#include "../../include/basic_hip.h"
+#include "common_host.h"   // what needs no HIP: the C ABI, set_error, BASIC_REQUIRE, BASIC_MCONV_BLOCK_CHANNELS
 
 namespace basic {
 
-void set_error(const std::string &msg);
 int hip_fail(hipError_t e, const char *what, const char *file, int line);
 
 #define BASIC_HIP_TRY(expr)                                                      \
     do {                                                                         \
         hipError_t _e = (expr);                                                  \
         if (_e != hipSuccess) return ::basic::hip_fail(_e, #expr, __FILE__, __LINE__); \
-    } while (0)
-
-#define BASIC_REQUIRE(cond, msg)            \
-    do {                                    \
-        if (!(cond)) {                      \
-            ::basic::set_error(msg);        \
-            return BASIC_ERR_INVALID;       \
-        }                                   \
     } while (0)
 
 // Fails (BASIC_ERR_NO_DEVICE) unless a HIP device is usable.  Never falls back to the CPU.
@@ -45,10 +36,6 @@ int set_rans_waves(int waves_per_block);
 bool set_dynamic_tiles(bool on);
 
 constexpr int kWave = 64;  // CDNA wavefront
-
-// Canonical summation block of the masked convolution (mconv.hip header comment): channels of one (tap, input group) slab
-// whose products form ONE fp32 MFMA / FMA chain; the persistent scan-line kernel (scanline.hip) sums in the same blocks.
-#define BASIC_MCONV_BLOCK_CHANNELS 64
 
 // Device view of a table set's fast-decoder search image (rans.hip), for kernels outside rans.hip that decode in place.
 struct RansFastView {

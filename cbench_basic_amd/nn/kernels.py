@@ -569,6 +569,9 @@ class ScanlinePlan:
         bp = (ctypes.c_void_p * n)(*[(b.ctypes.data if b is not None else None) for b in bs])
         outs = np.array([w.shape[0] for w in ws], dtype=np.int32)
         acts = np.array([int(bool(ctx_act))] + [int(bool(a)) for _, _, a in dense], dtype=np.int32)
+        # the layer sizes basic_scanline_plan_create gets: all the library's planner knows of the layers (csrc/scan_plan.h)
+        self.layer_sizes = dict(channels=int(self.channels), ctx_out=int(cw.shape[0]), ksize=int(self.ksize), prior_channels=int(prior_channels),
+                                dense_out=outs.tolist(), act_after=acts.tolist(), dense_in_groups=groups.tolist())
         h = ctypes.c_void_p()
         _lib.check(_lib.lib().basic_scanline_plan_create(cw.ctypes.data, cb.ctypes.data if cb is not None else None, self.channels,
                                                          cw.shape[0], self.ksize, int(prior_channels), n, wp, bp, outs.ctypes.data,

@@ -172,6 +172,21 @@ def check_codec_level(schedule, level, shape):
 
 # ---- the dispatch table (tests/golden/scanline_dispatch.json, written by scripts/scanline_dispatch_table.py): which kernel serves a call
 DISPATCH_FIELDS = ("kind", "C", "batch", "H", "W", "direction", "schedule", "env")
+STREAM_FIELDS = DISPATCH_FIELDS + ("lanes", "rows")   # its `streams` section: decode calls over lane and row streams, asked of choose alone
+
+
+def dispatch_plan(coder, sl, shapes):
+    """A coder's entry of the table's `plans` section: the layer sizes its ScanlinePlan was made of, the coder's table length and
+    gate, and what the library reports of the plan -- basic_scanline_plan_info, and per (H, W) of `shapes` the batched kernel's
+    largest batch (encode, decode), the wavefront's, and the band's images per launch.  `batched` and `tile_workgroups` (the
+    workgroups of one column tile of the batched family: the context layer's 32-row tiles plus the largest dense layer's) are
+    not reported by any entry: the first is what batched_max says of a wide latent, the second is restated here from the layers."""
+    layers = sl.layer_sizes
+    batched = sl.batched_max(64) > 0
+    return dict(layers=layers, table_len=int(coder._scale_table_dev.numel()), lane_max_batch=int(coder.persistent_scanline_max_batch),
+                workgroups=sl.workgroups, lds_weight_bytes=sl.lds_weight_bytes, batched=batched,
+                tile_workgroups=layers["ctx_out"] // 32 + max(r // 32 for r in layers["dense_out"]) if batched else 0,
+                limits=[[H, W, sl.batched_max(W), sl.batched_max(W, decode=True), sl.wavefront_max(H, W), sl.band_max(H, W)] for H, W in shapes])
 
 
 def dispatch_stream(coder, row, cache):
@@ -192,7 +207,7 @@ def dispatch_choose(coder, sl, row):
         os.environ["BASIC_SCAN_KERNEL"] = row["env"]
     try:
         kernel, launches = sl.choose(row["batch"], row["H"], row["W"], coder._scale_table_dev.numel(), row["schedule"], coder.persistent_scanline_max_batch,
-                              coder._tables if row["direction"] == "decode" else None)
+                              coder._tables if row["direction"] == "decode" else None, lanes=row.get("lanes", 1), rows=row.get("rows", False))
     except (RuntimeError, ValueError) as e:
         if "does not fit" not in str(e):
             raise

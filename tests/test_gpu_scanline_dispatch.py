@@ -3,7 +3,10 @@
 BASIC_SCAN_KERNEL -- ran when it was recorded: a kernel's name, "per-step" (the coder leaves the call to its per-step path) or
 "raises" (a refusal).  Every row must come out of ScanlinePlan.choose without a launch, with the launches the kernel needs, and
 out of the coder's own path again: _scanline_plan, then the call where it leaves one, which must run that kernel.  The rules
-count workgroups against the device's compute units, so the table holds for the device it names."""
+count workgroups against the device's compute units, so the table holds for the device it names.
+tests/test_cpu_scan_plan.py replays the same table through the planner alone (csrc/scan_plan.h) on the CPU, with each coder's layer
+sizes taken from the table's `plans` section: the live coders must still have those, and the `streams` section (decode calls over
+lane and row streams) must come out of ScanlinePlan.choose as recorded."""
 import json
 import os
 
@@ -18,6 +21,7 @@ with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sc
     TABLE = json.load(_f)
 ROWS = [dict(zip(TABLE["fields"], r)) for r in TABLE["rows"]]
 SHAPES = sorted({(r["kind"], r["C"], r["batch"], r["H"], r["W"]) for r in ROWS}, key=str)
+STREAMS = [dict(zip(TABLE["stream_fields"], r)) for r in TABLE["streams"]]
 _STREAMS = {}
 
 
@@ -45,4 +49,32 @@ def test_dispatch_table_replays(kind, C, B, H, W):
         ran = sc.dispatch_run(coder, row, _STREAMS)   # the coder's own path: _scanline_plan, then the call where there is one
         if ran != row["outcome"]:
             wrong.append(f"{call}: ran {ran}, recorded {row['outcome']}")
+    assert not wrong, "\n".join(wrong)
+
+
+@pytest.mark.parametrize("kind,C", sorted({s[:2] for s in SHAPES}))
+def test_recorded_plans_are_the_live_coders(kind, C):
+    """The fixture cannot drift from the coders: layer sizes, table length, gate and basic_scanline_plan_info are the recorded ones
+    on any device; what counts compute units, on the table's."""
+    recorded = next(p for p in TABLE["plans"] if (p["kind"], p["C"]) == (kind, C))
+    coder = sc._shared_coder(kind, C)
+    sl = sc._plan_of(coder, C)
+    live = sc.dispatch_plan(coder, sl, [tuple(lim[:2]) for lim in recorded["limits"]])
+    for k in ("layers", "table_len", "lane_max_batch", "workgroups", "lds_weight_bytes"):
+        assert live[k] == recorded[k], k
+    if torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count == TABLE["compute_units"]:
+        assert live == {k: recorded[k] for k in live}
+
+
+@pytest.mark.parametrize("kind,C", sorted({(r["kind"], r["C"]) for r in STREAMS}))
+def test_stream_rows_replay(kind, C):
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    if cus != TABLE["compute_units"]:
+        pytest.skip(f"the table was recorded on a device of {TABLE['compute_units']} compute units, this one has {cus}")
+    coder = sc._shared_coder(kind, C)
+    sl = sc._plan_of(coder, C)
+    before = sl.last_kernel()
+    wrong = [f"{row}: choose says {got}" for row in STREAMS if (row["kind"], row["C"]) == (kind, C)
+             for got in [sc.dispatch_choose(coder, sl, row)] if got != (row["outcome"], row["launches"])]
+    assert sl.last_kernel() == before   # choose launches nothing
     assert not wrong, "\n".join(wrong)
