@@ -107,6 +107,8 @@ _SIGNATURES = {
     "basic_scanline_status": (_I, [_P, _P, _P]),
     "basic_scanline_plan_destroy": (None, [_P]),
     "basic_mse_per_image_dev": (_I, [_P, _P, _I, _L, _P, _P]),
+    "basic_msssim_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "basic_msssim_per_image_dev": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _L, _P, _P, _P]),
     "basic_tans_tables_create": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
     "basic_tans_tables_set_ar": (_I, [_P, _P, _I, _I, _I, _I]),
     "basic_tans_tables_get_row": (_I, [_P, _I, _P, _P, _P, _P]),

@@ -5,7 +5,9 @@ under /root/reference, so this file is PARITY-UNPINNED: it follows that package'
 (sigma 1.5) applied separably WITHOUT padding per channel, K = (0.01, 0.03), five scales with weights
 (0.0448, 0.2856, 0.3001, 0.2363, 0.1333), 2 x 2 average pooling between scales (odd sizes padded), contrast-structure terms of the
 first four scales and the full SSIM of the last, each clamped at zero, combined as a weighted product per channel, then the mean over
-channels -- but no output of the package could be compared here.  Plain torch ops on whatever device the images live on: a
+channels -- but no output of the package could be compared here.  The torch ops below are the CPU path and the parity
+statement; CUDA tensors with the default window, weights and K go to the fused HIP evaluation of the same algorithm
+(csrc/msssim.hip, ``nn/kernels.py::ms_ssim_per_image``), which tests/test_gpu_msssim.py holds against an fp64 evaluation.  A
 forward / benchmark metric, not part of the coding path."""
 import torch
 import torch.nn.functional as F
@@ -43,13 +45,22 @@ def _ssim_terms(x, y, win, data_range, K):
     return ssim_map.flatten(2).mean(-1), cs_map.flatten(2).mean(-1)   # [B, C] each
 
 
-def ms_ssim(x, y, data_range=1.0, size_average=True, win_size=11, win_sigma=1.5, weights=_WEIGHTS, K=(0.01, 0.03)):
+def ms_ssim(x, y, data_range=1.0, size_average=True, win_size=11, win_sigma=1.5, weights=_WEIGHTS, K=(0.01, 0.03), impl=None):
     """[B, C, H, W] images -> MS-SSIM per image ([B]) or its mean (size_average).  The smaller side must exceed
-    (win_size - 1) * 2**4 = 160 pixels (four halvings must leave room for the window), as the package requires."""
+    (win_size - 1) * 2**4 = 160 pixels (four halvings must leave room for the window), as the package requires.
+    ``impl``: None = the HIP kernel for CUDA tensors with the default window, weights and K and the torch ops below for
+    everything else; "torch" = the torch ops on any device."""
+    if impl not in (None, "torch"):
+        raise ValueError(f"impl should be None or 'torch', not {impl!r}")
     if x.shape != y.shape or x.dim() != 4:
         raise ValueError("ms_ssim takes two [B, C, H, W] tensors of one shape")
     if min(x.shape[2:]) <= (win_size - 1) * 2 ** (len(weights) - 1):
         raise ValueError(f"image side should be larger than {(win_size - 1) * 2 ** (len(weights) - 1)} for {len(weights)} scales of a {win_size}-tap window")
+    if (impl is None and x.is_cuda and y.is_cuda and win_size == 11 and win_sigma == 1.5
+            and tuple(weights) == _WEIGHTS and tuple(K) == (0.01, 0.03)):
+        from ..nn import kernels
+        val = kernels.ms_ssim_per_image(x, y, data_range=data_range)
+        return val.mean() if size_average else val
     x, y = x.float(), y.float()
     win = _gauss_window(win_size, win_sigma, x.device, x.dtype)
     w = torch.tensor(weights, device=x.device, dtype=x.dtype)

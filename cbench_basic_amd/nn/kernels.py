@@ -374,6 +374,31 @@ def mse_per_image(a, b):
     return out
 
 
+def ms_ssim_per_image(x, y, data_range=1.0, return_terms=False, workspace=None):
+    """MS-SSIM of each image of two [B, C, H, W] batches (basic_msssim_per_image_dev): [B], and with ``return_terms`` also the
+    [B, C, 5] terms before the weights (relu(cs) of scales 0-3, relu(ssim) of scale 4).  Inputs are made fp32 and contiguous;
+    the workspace is a ``torch.empty`` on their device (or ``workspace``, a uint8 tensor there); the call runs on the
+    current stream."""
+    if not (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor)) or x.dim() != 4 or x.shape != y.shape:
+        raise ValueError("ms_ssim_per_image takes two [B, C, H, W] tensors of one shape")
+    x, y = _dev(x).float().contiguous(), _dev(y).float().contiguous()
+    if y.device != x.device:
+        raise ValueError("ms_ssim_per_image: the two batches live on different devices")
+    B, C, H, W = x.shape
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        need = L.basic_msssim_workspace_bytes(B, C, H, W)
+        if workspace is None and need > 0:
+            workspace = torch.empty((need,), device=x.device, dtype=torch.uint8)
+        out = torch.empty((B,), device=x.device, dtype=torch.float32)
+        terms = torch.empty((B, C, 5), device=x.device, dtype=torch.float32) if return_terms else None
+        # a refused shape (need == -1) goes to the library all the same: the message is its own
+        _lib.check(L.basic_msssim_per_image_dev(x.data_ptr(), y.data_ptr(), B, C, H, W, float(data_range), _lib.ptr(workspace),
+                                                workspace.numel() * workspace.element_size() if workspace is not None else 0,
+                                                out.data_ptr(), _lib.ptr(terms), _stream()))
+    return (out, terms) if return_terms else out
+
+
 def gauss_nll_per_image(q, scales_or_params, interleaved, scale_bound=0.11, likelihood_bound=1e-9):
     """Rate estimate (nats per image) of a Gaussian-coded latent; see basic_gauss_nll_per_image_dev."""
     q, sp = _dev(q, torch.float32), _dev(scales_or_params, torch.float32)

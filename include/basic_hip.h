@@ -316,6 +316,22 @@ void basic_mconv_plan_destroy(basic_mconv_plan *p);
  * ==================================================================================== */
 int basic_mse_per_image_dev(const float *d_a, const float *d_b, int batch, int64_t elems_per_image,
                             float *d_mse, void *hip_stream);
+/* MS-SSIM per image: pytorch_msssim.ms_ssim(x_hat, x, data_range, size_average) as consumed at
+ * cbench/benchmark/metrics/pytorch_distortion.py:8,17-18 and cbench/modules/entropy_coder/latent_graph.py:14,92-96, with that
+ * package's defaults (11-tap Gaussian window of sigma 1.5 without padding, K = (0.01, 0.03), five scales with weights
+ * (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)).  PARITY-UNPINNED: the package is not available; the kernels (csrc/msssim.hip)
+ * evaluate what benchmark/ms_ssim.py states.  min(h, w) must exceed 160 (four halvings must leave room for the window).
+ * Bytes of device workspace a call for this shape needs (pooled pyramids of both images, one partial sum per map tile):
+ * pure host arithmetic, no device needed; does not decrease in any argument; -1 on bad arguments. */
+int64_t basic_msssim_workspace_bytes(int batch, int channels, int h, int w);
+/* d_x, d_y: float32 [batch][channels][h][w].  d_msssim[b] = mean over channels of the weighted product of the five terms;
+ * d_terms (may be NULL): float32 [batch][channels][5], the terms before the weights: relu(mean cs) of scales 0-3 and
+ * relu(mean ssim) of scale 4.  Ten launches on hip_stream; nothing is allocated and nothing synchronised inside the call,
+ * and no float atomics: the value of an image is bit-for-bit the same at any batch size, batch position and stream.
+ * d_workspace: at least workspace_bytes >= basic_msssim_workspace_bytes of device memory, float-aligned, private to the call
+ * until the stream has passed it.  BASIC_ERR_INVALID for a null pointer, a side <= 160 or a workspace that is too small. */
+int basic_msssim_per_image_dev(const float *d_x, const float *d_y, int batch, int channels, int h, int w, float data_range,
+                               void *d_workspace, int64_t workspace_bytes, float *d_msssim, float *d_terms, void *hip_stream);
 
 /* ======================================================================================
  * 8. Fused image entry points of the plain hyperprior latent graph (SURVEY 8b "basic_encode_image / decode_image"):

@@ -46,6 +46,8 @@ def main():
                     help="--codec basic: lane streams per image of the scan-line y-coder (a format the reference does not read)")
     ap.add_argument("--stream-rows", action="store_true",
                     help="--codec basic: one stream per latent row of the scan-line y-coder (a format the reference does not read)")
+    ap.add_argument("--metrics", nargs="+", choices=["psnr", "ms-ssim"], default=["psnr"],
+                    help="distortion metrics of the reconstruction (ms-ssim needs images with both sides above 160)")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     if args.stream_rows and args.codec != "basic":
@@ -85,7 +87,7 @@ def main():
                 codec.set_complex_level(lvl)
             codec.decompress(codec.compress(batches[0].to("cuda")))
     bench = BasicLosslessCompressionBenchmark(codec, batches,
-                                              distortion_metric=PytorchBatchedDistortion(),
+                                              distortion_metric=PytorchBatchedDistortion(metrics=args.metrics),
                                               nn_codec_use_forward_pass=args.forward_pass,
                                               testing_complexity_levels=args.complexity_levels,
                                               testing_variable_rate_levels=args.rate_levels, output_dir=args.out,
