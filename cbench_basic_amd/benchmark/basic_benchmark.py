@@ -14,6 +14,11 @@ concurrent stream workers on the ONE GPU (stream_workers.py: host threads, each 
 the codec built by ``codec_builder``), so dataset items are coded concurrently: one item's serial rANS chains and launch-bound
 AR steps run beside another item's transforms.  Per-item times are the latencies of the calls as they ran (concurrently);
 ``time_wall_dataset`` / ``speed_wall_dataset`` give the wall time and MiB/s of the whole dataset pass.
+
+``testing_coalesce_items`` (not in the reference; INTEGRATION.md, "Coalesced items"): a dataset of batch-1 items is coded in calls of
+up to that many items of one shape (``codec.compress_items`` / ``decompress_items``); every item keeps the bytes and the
+reconstruction of its own batch-1 call, the metrics are logged per item with the keys of the sequential pass, and a call's time is
+shared equally among its items.
 """
 import copy
 import csv
@@ -33,7 +38,7 @@ class BasicLosslessCompressionBenchmark:
                  nn_codec_use_forward_pass=False, nn_codec_forward_pass_skip_compression=False,
                  testing_variable_rate_levels=None, testing_variable_rate_bj_delta_metric=None,
                  testing_complexity_levels=None, force_testing_device="cuda", output_dir=None, num_repeats=1,
-                 num_testing_workers=0, codec_builder=None, worker_transform_token=None, **kwargs):
+                 num_testing_workers=0, codec_builder=None, worker_transform_token=None, testing_coalesce_items=0, **kwargs):
         self.codec = codec
         self.dataloader = dataloader
         self.distortion_metric = distortion_metric
@@ -56,6 +61,11 @@ class BasicLosslessCompressionBenchmark:
         if self.num_testing_workers > 1 and codec_builder is None:
             raise ValueError("num_testing_workers > 1 needs codec_builder: a callable returning a fresh codec of the same "
                              "architecture (every worker codes with its own replica; weights and levels are copied from `codec`)")
+        # coalesced items ("Coalesced items"): a dataset of batch-1 items is coded in calls of up to this many items
+        # of one shape (codec.compress_items / decompress_items), every item keeping its own bytes; 0 / 1 = one call per item
+        self.testing_coalesce_items = int(testing_coalesce_items or 0)
+        if self.testing_coalesce_items < 0:
+            raise ValueError("testing_coalesce_items must be >= 0")
         self._pool = None
 
     # ---- files (base.py:41-52)
@@ -126,12 +136,14 @@ class BasicLosslessCompressionBenchmark:
             if dm is not None:
                 dm(decompressed, data_target)
 
-    def _worker_pool(self, first_item=None):
-        """The stream workers and their codec replicas, brought to the main codec's weights, levels and tables."""
+    def _worker_pool(self, first_item=None, batch=None):
+        """The stream workers and their codec replicas, brought to the main codec's weights, levels and tables.  ``batch``: the
+        images per call when that is not the first item's batch (coalesced items)."""
         from .stream_workers import StreamWorkerPool
         if self._pool is None:
-            self._token_on = self.worker_transform_token if self.worker_transform_token is not None else \
-                bool(first_item is not None and hasattr(first_item, "shape") and len(first_item.shape) == 4 and first_item.shape[0] >= 8)
+            if batch is None and first_item is not None and hasattr(first_item, "shape") and len(first_item.shape) == 4:
+                batch = first_item.shape[0]
+            self._token_on = self.worker_transform_token if self.worker_transform_token is not None else bool(batch is not None and batch >= 8)
             def make():
                 c = self.codec_builder()
                 if hasattr(c, "eval"):
@@ -191,7 +203,102 @@ class BasicLosslessCompressionBenchmark:
         if self._pool is not None:
             self._pool._synced_to = None
 
+    # ---- coalesced items: chunks of batch-1 items of one shape, one timed compress_items / decompress_items per chunk
+    def _run_chunk(self, chunk, items, records, codec=None):
+        """Codes items[i] for i in chunk in one call each way and fills records[i] = (metric updates, distortion results) with
+        exactly the keys _run_step logs; a chunk's call time is shared equally among its items."""
+        codec = self.codec if codec is None else codec
+        dm = self.distortion_metric   # asked with cache_metrics=False only: nothing is logged before the pass is over
+        data = [items[i] for i in chunk]
+        targets = [d.to(self.force_testing_device) if self.force_testing_device else d for d in data]
+        lengths = [self._estimate_byte_length(d) for d in data]
+        n = len(chunk)
+        for i, L in zip(chunk, lengths):
+            records[i] = (OrderedDict(original_length=L), [])
+        if self.nn_codec_use_forward_pass and hasattr(codec, "forward_estimate_bitlen"):
+            for i, d, t, L in zip(chunk, data, targets, lengths):   # the forward estimate stays one call per item
+                decompressed, compressed_length = codec.forward_estimate_bitlen(d)
+                compressed_length = float(compressed_length)
+                records[i][0].update(compression_ratio_nn_forward=compressed_length / L, compressed_length_nn_forward=compressed_length)
+                if dm is not None:
+                    records[i][1].append(dm(decompressed, t, cache_metrics=False))
+            if self.nn_codec_forward_pass_skip_compression:
+                return
+        self._sync()
+        t0 = time.time()
+        compressed = codec.compress_items(data, max_batch=n)
+        self._sync()
+        time_compress = (time.time() - t0) / n
+        if len(compressed) != n:
+            raise ValueError(f"compress_items returned {len(compressed)} strings for {n} items")
+        for i, c, L in zip(chunk, compressed, lengths):
+            compressed_length = self._estimate_byte_length(c)
+            records[i][0].update(compression_ratio=compressed_length / L, compressed_length=compressed_length,
+                                 time_compress=time_compress * 1000, speed_compress=L / time_compress / 1024 / 1024)
+        if not self.skip_decompress:
+            t0 = time.time()
+            decompressed = codec.decompress_items(compressed, max_batch=n)
+            self._sync()
+            time_decompress = (time.time() - t0) / n
+            for i, L in zip(chunk, lengths):
+                records[i][0].update(time_decompress=time_decompress * 1000, speed_decompress=L / time_decompress / 1024 / 1024,
+                                     time_total=(time_compress + time_decompress) * 1000,
+                                     speed_total=L / (time_compress + time_decompress) / 1024 / 1024)
+            if dm is not None:
+                for i, r in zip(chunk, dm.per_item(list(decompressed), targets, cache_metrics=False)):
+                    records[i][1].append(r)
+
+    def _run_dataset_coalesced(self):
+        from ..utils.item_framing import coalesce_chunks
+        logger = MetricLogger()
+        self._sync()
+        t0 = time.time()   # the sequential pass loads inside its wall time; so does this one (the worker pass restarts the clock, as today)
+        items = list(self.dataloader)
+        for d in items:
+            if not hasattr(d, "shape") or len(d.shape) != 4 or d.shape[0] != 1:
+                raise ValueError("testing_coalesce_items codes a dataset of batch-1 items ([1, C, H, W]); got "
+                                 f"{tuple(d.shape) if hasattr(d, 'shape') else type(d)}: coalescing and dataloader batching do not combine")
+        if not (hasattr(self.codec, "compress_items") and hasattr(self.codec, "decompress_items")):
+            raise ValueError("testing_coalesce_items needs a codec with compress_items / decompress_items")
+        if self.distortion_metric is not None and not hasattr(self.distortion_metric, "per_item"):
+            raise ValueError("testing_coalesce_items needs a distortion metric with per_item")
+        chunks = coalesce_chunks([(tuple(d.shape), getattr(d, "dtype", None)) for d in items], self.testing_coalesce_items)
+        records = [None] * len(items)
+        if self.num_testing_workers > 1 and (self.force_testing_device or "cuda").startswith("cuda"):
+            pool = self._worker_pool(items[0] if items else None, batch=max((len(c) for c in chunks), default=None))
+            W = min(self.num_testing_workers, max(1, len(chunks)))
+            base, extra = divmod(len(chunks), W)
+            bounds = [0]   # whole chunks, contiguous ranges of the chunk list
+            for w in range(W):
+                bounds.append(bounds[-1] + base + (1 if w < extra else 0))
+            self._sync()
+            t0 = time.time()
+
+            def work(codec, w):
+                for c in range(bounds[w], bounds[w + 1]):
+                    self._run_chunk(chunks[c], items, records, codec=codec)
+                return None
+            pool.map(work, list(range(W)))
+        else:
+            for chunk in chunks:
+                self._run_chunk(chunk, items, records)
+        self._sync()
+        wall = time.time() - t0
+        n_bytes = 0
+        for d, (updates, distortions) in zip(items, records):   # logged per item, in DATASET order
+            logger.update(**updates)
+            for r in distortions:
+                self.distortion_metric.metric_logger.update(**r)
+            n_bytes += self._estimate_byte_length(d)
+        out = logger.get_global_average()
+        if items:
+            out["time_wall_dataset"] = wall * 1000
+            out["speed_wall_dataset"] = n_bytes / wall / 1024 / 1024
+        return out
+
     def _run_dataset(self):
+        if self.testing_coalesce_items > 1:
+            return self._run_dataset_coalesced()
         logger = MetricLogger()
         n_items, n_bytes = 0, 0
         self._sync()

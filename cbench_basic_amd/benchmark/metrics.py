@@ -75,6 +75,37 @@ class PytorchBatchedDistortion:
             self.metric_logger.update(**result)
         return result
 
+    def per_item(self, output, target, cache_metrics=True):
+        """One result dict PER IMAGE of a batch (or of a list of ``[1, C, H, W]`` tensors of one shape), each what ``__call__`` gives
+        for that image alone: psnr from the image's own mean squared error, ms-ssim from its own per-image value.  Every dict is
+        logged as one update, so the running means equal those of N batch-1 calls."""
+        if isinstance(output, (list, tuple)):
+            output = output[0] if len(output) == 1 else torch.cat(list(output))
+        if isinstance(target, (list, tuple)):
+            target = target[0] if len(target) == 1 else torch.cat(list(target))
+        output = output.type_as(target)[..., :target.shape[-2], :target.shape[-1]]  # make spatial size equal
+        N = target.shape[0]
+        cols = {}
+        if "psnr" in self._metrics:
+            if output.is_cuda:
+                from ..nn import kernels as K
+                mse = K.mse_per_image(output.contiguous(), target.contiguous()).double().tolist()
+            else:
+                mse = [torch.mean((output[i:i + 1] - target[i:i + 1]) ** 2).item() for i in range(N)]
+            cols["psnr"] = [20 * np.log10(self.max_val) - 10 * np.log10(m) for m in mse]
+        if "ms-ssim" in self._metrics:
+            from .ms_ssim import ms_ssim
+            if output.is_cuda:   # the fused kernel reduces image by image
+                cols["ms-ssim"] = ms_ssim(output, target, data_range=self.max_val, size_average=False).tolist()
+            else:                # image by image: a batched convolution may block its sums differently
+                cols["ms-ssim"] = [float(ms_ssim(output[i:i + 1], target[i:i + 1], data_range=self.max_val, size_average=False)[0])
+                                   for i in range(N)]
+        results = [{m: cols[m][i] for m in self._metrics} for i in range(N)]   # the reference's order
+        if cache_metrics:
+            for r in results:
+                self.metric_logger.update(**r)
+        return results
+
     def collect_metrics(self):
         return self.metric_logger.get_global_average()
 

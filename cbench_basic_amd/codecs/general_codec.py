@@ -29,6 +29,21 @@ class GeneralCodec(HotPathModule, CodecInterface, VariableRateCodecInterface, Va
         with self.profiler.start_time_profile("time_decompress_entropy_coder"):
             return self.entropy_coder.decode(data, *args, prior=None, **kwargs)
 
+    def compress_items(self, items, *args, max_batch=None, **kwargs):
+        """N batch-1 items -> exactly ``[self.compress(x) for x in items]``, items of one shape coded in shared batches
+        (entropy coder's ``encode_items``; not part of the reference's codec interface)."""
+        with self.profiler.start_time_profile("time_compress_entropy_coder"):
+            return self.entropy_coder.encode_items(items, *args, max_batch=max_batch, **kwargs)
+
+    def decompress_items(self, strings, *args, max_batch=None, **kwargs):
+        """N batch-1 strings -> their reconstructions, ``[1, C, H, W]`` each, equal to ``self.decompress(s)`` of every string."""
+        with self.profiler.start_time_profile("time_decompress_entropy_coder"):
+            return self.entropy_coder.decode_items(strings, *args, max_batch=max_batch, **kwargs)
+
+    @property
+    def last_items_calls(self):
+        return self.entropy_coder.last_items_calls
+
     def forward(self, data, *args, **kwargs):
         return self.entropy_coder(data, *args, **kwargs)
 

@@ -87,6 +87,16 @@ class GroupedVariableRateCodec(HotPathModule, CodecInterface, VariableRateCodecI
     def decompress(self, data: bytes, *args, **kwargs):
         return self.active_codec.decompress(data, *args, **kwargs)
 
+    def compress_items(self, items, *args, **kwargs):
+        return self.active_codec.compress_items(items, *args, **kwargs)
+
+    def decompress_items(self, strings, *args, **kwargs):
+        return self.active_codec.decompress_items(strings, *args, **kwargs)
+
+    @property
+    def last_items_calls(self):
+        return self.active_codec.last_items_calls
+
     def forward(self, *args, **kwargs):
         # every member is run (the reference needs that for joint training, base.py:213-221); the active one's result counts
         for codec in self.codecs:

@@ -25,6 +25,7 @@ from ...base import HotPathModule
 from ...codecs.base import (VariableComplexityCodecInterface, VariableRateCodecInterface,
                             VariableTaskCodecInterface)
 from ...utils.bytes_ops import merge_bodies, merge_bytes, split_merged_bytes, split_merged_views
+from ...utils import item_framing
 from .complexity_search import search_complexity_levels
 
 
@@ -73,6 +74,18 @@ class LossyDummyEntropyCoder(HotPathModule):
 
     def update_state(self, *args, **kwargs):
         pass
+
+    # item framing (utils/item_framing.py): a node without bits has an empty body at any batch size
+    can_split_items = True
+
+    def split_items(self, body, n, **ctx):
+        return item_framing.empty_split(body, n)
+
+    def merge_items(self, bodies, **ctx):
+        return item_framing.empty_merge(bodies)
+
+    def item_shape(self, body, **ctx):
+        return None
 
 
 class ParamDictModuleWrapper(nn.Module):
@@ -491,6 +504,92 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             with self.profiler.start_time_profile("decode_generative"):
                 data_dict, _ = self._generative_process(input_dict, prior_dict=prior_dict, **node_dict)
             return data_dict[self.DEFAULT_INPUT_NODE_NAME]
+
+    # ---- coalesced items: N batch-1 items coded in chip-filling calls, every item keeping the bytes of its own batch-1 call
+    last_items_calls = 0   # encode() / decode() calls the last encode_items() / decode_items() made
+
+    def _items_ctx(self, node, node_dict):
+        """What the graph knows about a coded node and its coder's framing may depend on: whether the node is coded under a prior
+        (the PGM coders then write no shape head) and the controller values mapped onto the coder's arguments (``blend_weight``)."""
+        sym = self.DEFAULT_EDGE_SPLIT_SYMBOL
+        ctx = dict(has_prior=any(e.split(sym)[1] == node for e in self.latent_generative_modules))
+        for nk, ik in self.latent_generative_input_mapping.get(node, {}).items():
+            if nk in node_dict:
+                ctx[ik] = node_dict[nk]
+        return ctx
+
+    def _items_framing(self):
+        """[(coder, ctx)] of the coded nodes in stream order, or None when one of them cannot give every image its own body."""
+        node_dict = self._node_generate_process(**self._get_default_node_dict(force_add_default_dynamic_nodes=True))
+        out = []
+        for node in self._coded_nodes():
+            coder = self.latent_node_entropy_coders[node]
+            if not (hasattr(coder, "split_items") and hasattr(coder, "merge_items") and getattr(coder, "can_split_items", False)):
+                return None
+            out.append((coder, self._items_ctx(node, node_dict)))
+        return out
+
+    @staticmethod
+    def _check_item(x):
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[0] != 1:
+            raise ValueError("an item is a [1, C, H, W] tensor" + (f", not {tuple(x.shape)}" if isinstance(x, torch.Tensor) else ""))
+
+    def encode_items(self, items, *args, max_batch=None, **kwargs) -> List[bytes]:
+        """N batch-1 items -> their N byte strings, EXACTLY what ``[self.encode(x) for x in items]`` returns, from as few encode()
+        calls as the shapes allow: items of one shape share a batch (utils/item_framing.coalesce_chunks), the batch's string is split
+        node by node.  One call per item when there is nothing to share, a coder cannot split, or the call brings arguments."""
+        items = list(items)
+        for x in items:
+            self._check_item(x)
+        self.last_items_calls = 0
+        framing = self._items_framing() if not (args or kwargs or self.training) else None
+        if framing is None:
+            chunks = [[i] for i in range(len(items))]
+        else:
+            chunks = item_framing.coalesce_chunks([(tuple(x.shape), x.dtype) for x in items], max_batch)
+        out = [None] * len(items)
+        for chunk in chunks:
+            self.last_items_calls += 1
+            if len(chunk) == 1:
+                out[chunk[0]] = self.encode(items[chunk[0]], *args, **kwargs)
+                continue
+            first = items[chunk[0]]
+            # the chunk's ONE device batch, filled item by item on the current stream (no host-side stack of the items)
+            batch = torch.empty((len(chunk),) + tuple(first.shape[1:]), dtype=first.dtype, device=self.device)
+            for j, i in enumerate(chunk):
+                batch[j:j + 1].copy_(items[i], non_blocking=True)
+            data = self.encode(batch)
+            splitters = [(lambda body, n, c=c, ctx=ctx: c.split_items(body, n, **ctx)) for c, ctx in framing]
+            for i, one in zip(chunk, item_framing.split_codec_string(data, len(chunk), splitters)):
+                out[i] = one
+        return out
+
+    def decode_items(self, strings, *args, max_batch=None, **kwargs) -> List[torch.Tensor]:
+        """N batch-1 strings -> their N reconstructions ([1, C, H, W] views of the batches' outputs, in input order), each equal to
+        ``self.decode(string)``.  Strings share a call when the shapes their own headers state agree on every node (a body without
+        a header, the AR body under an aligned prior, follows the others)."""
+        strings = list(strings)
+        self.last_items_calls = 0
+        framing = self._items_framing() if not (args or kwargs or self.training) else None
+        if framing is None:
+            chunks = [[i] for i in range(len(strings))]
+        else:
+            keys = []
+            for s in strings:
+                segs = split_merged_bytes(bytes(s), num_segments=len(framing))
+                keys.append(tuple(c.item_shape(seg, **ctx) if hasattr(c, "item_shape") else None for (c, ctx), seg in zip(framing, segs)))
+            chunks = item_framing.coalesce_chunks(keys, max_batch)
+        out = [None] * len(strings)
+        for chunk in chunks:
+            self.last_items_calls += 1
+            if len(chunk) == 1:
+                out[chunk[0]] = self.decode(strings[chunk[0]], *args, **kwargs)
+                continue
+            mergers = [(lambda bodies, c=c, ctx=ctx: c.merge_items(bodies, **ctx)) for c, ctx in framing]
+            rec = self.decode(item_framing.merge_codec_strings([strings[i] for i in chunk], mergers))
+            for j, i in enumerate(chunk):
+                out[i] = rec[j:j + 1]
+        return out
 
     def forward(self, data, *args, **kwargs):
         """Eval-mode forward: quantised reconstruction without entropy coding (latent_graph.py:870-1230

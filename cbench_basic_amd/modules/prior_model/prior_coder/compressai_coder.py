@@ -24,6 +24,7 @@ import torch.nn.functional as F
 from ....base import HotPathModule
 from ....nn import kernels as K
 from .... import ans as _ans
+from ....utils import item_framing as _items
 
 SCALES_MIN, SCALES_MAX, SCALES_LEVELS = 0.11, 256, 64
 
@@ -229,7 +230,29 @@ class EntropyBottleneck(nn.Module):
         return self.host_tables()
 
 
-class CompressAIEntropyBottleneckPriorCoder(HotPathModule):
+class CompressAIItemFraming:
+    """split_items / merge_items of the coders that frame with write_body (utils/item_framing.py): a body of n streams <-> the n
+    bodies its images get when they are coded one per call.  ``ctx`` (what the graph knows about the node) is not needed."""
+
+    can_split_items = True
+
+    def split_items(self, body, n, **ctx):
+        parts = _items.split_compressai_body(body)
+        if len(parts) != int(n):
+            raise ValueError(f"body of {len(parts)} streams, {n} items expected")
+        return parts
+
+    def merge_items(self, bodies, **ctx):
+        return _items.merge_compressai_bodies(bodies)
+
+    def item_shape(self, body, **ctx):
+        h, w, n = _items.compressai_body_shape(body)
+        if n != 1:
+            raise ValueError(f"an item body holds one stream, not {n}")
+        return (h, w)
+
+
+class CompressAIEntropyBottleneckPriorCoder(CompressAIItemFraming, HotPathModule):
     """compressai_coder.py:87-248."""
 
     def __init__(self, entropy_bottleneck_channels=256, eps=1e-7, use_inner_aux_opt=False, use_bit_rate_loss=True,
@@ -295,7 +318,7 @@ class CompressAIEntropyBottleneckPriorCoder(HotPathModule):
         return zhat
 
 
-class CompressAISlimmableEntropyBottleneckPriorCoder(HotPathModule):
+class CompressAISlimmableEntropyBottleneckPriorCoder(CompressAIItemFraming, HotPathModule):
     """compressai_coder.py:251-338: one EntropyBottleneck per slimmable width."""
 
     def __init__(self, entropy_bottleneck_channels_list=[256], **kwargs):
@@ -392,7 +415,7 @@ class GaussianConditional(nn.Module):
                 self._offset.cpu().numpy().astype(np.int32).reshape(-1))
 
 
-class CompressAIGaussianConditionalCoder(HotPathModule):
+class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
     """compressai_coder.py:341-397: zero-mean Gaussian with hyperprior scales."""
 
     def __init__(self, use_bit_rate_loss=True, training_output_straight_through=False, scale_bound=0.11, **kwargs):

@@ -32,6 +32,7 @@ import torch.nn as nn
 from ....base import HotPathModule
 from ....nn import kernels as K
 from .... import _lib
+from ....utils import item_framing as _items
 from .compressai_coder import get_scale_table
 from .torch_ans import gaussian_ans_params
 
@@ -633,6 +634,29 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
             return B > 1
         return mode == "per_image"
 
+    # ---- item framing (utils/item_framing.py): the body of a batch <-> the bodies of its images coded one per call
+    @property
+    def can_split_items(self):
+        """False for ``batch_stream_mode="reference"``: one serial stream over the whole batch has no per-image parts."""
+        return self._per_image(2)
+
+    def _writes_head(self, has_prior):
+        return self.fixed_input_shape is None and not (self.force_input_prior_shape_aligned and has_prior)
+
+    def split_items(self, body, n, has_prior=False, **ctx):
+        if not self.can_split_items:
+            raise ValueError("batch_stream_mode='reference' writes one stream for the whole batch: it has no item bodies")
+        return _items.split_pgm_body(body, n, has_head=self._writes_head(has_prior), item_tabled=self._per_image(1))
+
+    def merge_items(self, bodies, has_prior=False, **ctx):
+        if not self.can_split_items:
+            raise ValueError("batch_stream_mode='reference' writes one stream for the whole batch: item bodies do not merge into it")
+        return _items.merge_pgm_bodies(bodies, has_head=self._writes_head(has_prior), item_tabled=self._per_image(1))
+
+    def item_shape(self, body, has_prior=False, **ctx):
+        """The spatial shape the body's own head states, or None when it carries none (aligned prior, fixed input shape)."""
+        return _items.pgm_body_shape(body, has_head=self._writes_head(has_prior))
+
     # Many-group patterns (scanline: H*W groups) are launch-bound: ~5 tiny kernels per group.  Their whole
     # per-group launch sequence is captured once per (batch, H, W) into a HIP graph and replayed.
     GRAPH_MIN_GROUPS = 8
@@ -1114,6 +1138,19 @@ class CombinedNNTrainablePGMPriorCoder(HotPathModule):
 
     def decode(self, byte_string: bytes, *args, prior=None, blend_weight=None, **kwargs):
         return self._select(blend_weight).decode(byte_string, prior=prior, **kwargs)
+
+    @property
+    def can_split_items(self):
+        return all(getattr(c, "can_split_items", False) for c in self.coders)
+
+    def split_items(self, body, n, blend_weight=None, **ctx):
+        return self._select(blend_weight).split_items(body, n, **ctx)
+
+    def merge_items(self, bodies, blend_weight=None, **ctx):
+        return self._select(blend_weight).merge_items(bodies, **ctx)
+
+    def item_shape(self, body, blend_weight=None, **ctx):
+        return self._select(blend_weight).item_shape(body, **ctx)
 
     def update_state(self, *args, **kwargs) -> None:
         for coder in self.coders:

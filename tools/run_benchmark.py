@@ -42,6 +42,9 @@ def main():
     ap.add_argument("--workers", type=int, default=0,
                     help="num_testing_workers: concurrent stream workers on the GPU, each with its own replica of the codec; dataset "
                          "items are coded concurrently (the reference's multiprocessing pool, basic_benchmark.py:829-858, GPU-native)")
+    ap.add_argument("--coalesce", type=int, default=0,
+                    help="testing_coalesce_items: code the batch-1 items of the dataset in calls of up to this many items of one shape; "
+                         "every item keeps the bytes of its own batch-1 call (needs --batch-size 1)")
     ap.add_argument("--stream-lanes", type=int, default=1,
                     help="--codec basic: lane streams per image of the scan-line y-coder (a format the reference does not read)")
     ap.add_argument("--stream-rows", action="store_true",
@@ -54,6 +57,10 @@ def main():
         ap.error("--stream-rows needs --codec basic")
     if args.stream_lanes != 1 and args.codec != "basic":
         ap.error("--stream-lanes needs --codec basic")
+    if args.coalesce and args.batch_size != 1:
+        ap.error("--coalesce codes batch-1 items: it does not combine with --batch-size other than 1")
+    if args.coalesce < 0:
+        ap.error("--coalesce must be >= 0")
     if args.workers > 1:   # before HIP initialises: one hardware queue per worker stream
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         os.environ.setdefault("BASIC_RANS_WPB", "8")
@@ -80,27 +87,39 @@ def main():
     else:
         presets.seed_synthetic_weights(codec, seed=0)
     codec = codec.eval().to("cuda")
+    warm_chunks = []
+    if args.coalesce > 1:
+        from cbench_basic_amd.utils.item_framing import coalesce_chunks
+        seen = set()
+        for chunk in coalesce_chunks([tuple(b.shape) for b in batches], args.coalesce):
+            if len(chunk) > 1 and (tuple(batches[chunk[0]].shape), len(chunk)) not in seen:
+                seen.add((tuple(batches[chunk[0]].shape), len(chunk)))
+                warm_chunks.append([batches[i] for i in chunk])
     if args.warmup:
         codec.update_state()
         for lvl in (args.complexity_levels or [None]):
             if lvl is not None:
                 codec.set_complex_level(lvl)
             codec.decompress(codec.compress(batches[0].to("cuda")))
+            for chunk in warm_chunks:   # the coalesced calls' one-time costs: one chunk per (shape, size) the pass will make
+                codec.decompress_items(codec.compress_items(chunk))
     bench = BasicLosslessCompressionBenchmark(codec, batches,
                                               distortion_metric=PytorchBatchedDistortion(metrics=args.metrics),
                                               nn_codec_use_forward_pass=args.forward_pass,
                                               testing_complexity_levels=args.complexity_levels,
                                               testing_variable_rate_levels=args.rate_levels, output_dir=args.out,
-                                              num_testing_workers=args.workers,
+                                              num_testing_workers=args.workers, testing_coalesce_items=args.coalesce,
                                               codec_builder=(lambda: presets.seed_synthetic_weights(builders[args.codec](), seed=0)) if args.workers > 1 else None)
     if args.workers > 1 and args.warmup:   # the replicas' one-time costs too, one replica at a time (HIP-graph capture)
-        pool = bench._worker_pool(batches[0])
+        pool = bench._worker_pool(batches[0], batch=max((len(c) for c in warm_chunks), default=None))
         for r, st in zip(pool.codecs, pool.streams):
             with torch.cuda.stream(st):
                 for lvl in (args.complexity_levels or [None]):
                     if lvl is not None:
                         r.set_complex_level(lvl)
                     r.decompress(r.compress(batches[0].to("cuda")))
+                    for chunk in warm_chunks:
+                        r.decompress_items(r.compress_items(chunk))
             torch.cuda.synchronize()
     metrics = bench.run_benchmark(ignore_exist_metrics=True)
     bench.close()
