@@ -56,6 +56,8 @@ _SIGNATURES = {
     "basic_rans_decode_batch_strided_dev": (_I, [_P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P]),
     "basic_rans_decode_batch_lanes_dev": (_I, [_P, _P, _P, _P, _L, _L, _I, _L, _I, _P, _P, _P, _P]),
     "basic_rans_decode_batch_streams_dev": (_I, [_P, _P, _P, _P, _L, _L, _I, _L, _I, _I, _I, _P, _P, _P, _P]),
+    "basic_rans_last_launch": (_I, [_P, _P]),
+    "basic_rans_set_waves": (_I, [_I, _P]),
     "basic_lanes_pack_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "basic_gc_quantize_index_dev": (_I, [_P, _P, _L, _P, _I, _F, _P, _P, _P, _P]),
     "basic_eb_quantize_index_dev": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
@@ -118,6 +120,7 @@ _SIGNATURES = {
     "basic_tans_encode_bound_words": (_L, [_P, _L]),
     "basic_tans_encode_batch_dev": (_I, [_P, _P, _P, _P, _I, _P, _L, _P, _P]),
     "basic_tans_decode_batch_dev": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "basic_tans_last_launch": (_I, [_P]),
 }
 
 

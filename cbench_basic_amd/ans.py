@@ -389,6 +389,17 @@ class Rans64Decoder(_Rans64Base):
         return out
 
 
+# BASIC_TANS_KERNEL_* (include/basic_hip.h): what a tANS launch ran
+TANS_KERNEL_NONE, TANS_KERNEL_ENC_LDS, TANS_KERNEL_ENC_GLOBAL, TANS_KERNEL_DEC_LDS, TANS_KERNEL_DEC_GLOBAL = range(-1, 4)
+
+
+def tans_last_launch():
+    """TANS_KERNEL_* of the calling thread's last tANS launch (host or batched entry point); TANS_KERNEL_NONE before any."""
+    k = ctypes.c_int(TANS_KERNEL_NONE)
+    _lib.check(_lib.lib().basic_tans_last_launch(ctypes.byref(k)))
+    return k.value
+
+
 class _TansBase:
     """TansBase, csrc/ans/tans.hpp:37-71 (constructor defaults: FSE_DEFAULT_TABLELOG = 11, FSE_MAX_SYMBOL_VALUE = 255,
     fse.h:590,610)."""
@@ -458,6 +469,8 @@ class _TansBase:
         _lib.check(_lib.lib().basic_tans_tables_get_row(self._tables, int(row), nxt.ctypes.data, db.ctypes.data, ds.ctypes.data,
                                                         dec.ctypes.data))
         return nxt, db, ds, dec
+
+    last_launch = staticmethod(tans_last_launch)
 
     _ar_args = _Rans64Base._ar_args
     _ar_rows = _Rans64Base._ar_rows

@@ -161,6 +161,8 @@ int upload_tables(basic_rans_tables *t)
     }
     for (int l = 0; l < 256; ++l) t->image.push_back(0x7FFFFFFFu);  // lanes 1..63 of a trailing wide row stay inside
     if (t->image.size() * 4 > 156 * 1024) t->fast_ok = false;
+    // precision >= 7, as for the fast encoder below: the wave decoder's 24-bit multiply takes the high word of x >> p, under 2^(31-p)
+    if (t->precision < 7) t->fast_ok = false;
     if (t->fast_ok) {
         BASIC_HIP_TRY(hipMalloc(&t->d_image, t->image.size() * sizeof(uint32_t)));
         BASIC_HIP_TRY(hipMalloc(&t->d_meta, t->meta.size() * sizeof(uint32_t)));
@@ -168,7 +170,8 @@ int upload_tables(basic_rans_tables *t)
         BASIC_HIP_TRY(hipMemcpy(t->d_meta, t->meta.data(), t->meta.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     // fast-encoder image
-    t->fast_enc_ok = t->rows <= 2048 && static_cast<size_t>(t->rows) * t->stride <= (4u << 20);
+    // precision >= 7: the kernel's 24-bit multiply takes the high word of q = x / freq, and q < 2^(63-p) keeps it under 2^(31-p)
+    t->fast_enc_ok = t->rows <= 2048 && static_cast<size_t>(t->rows) * t->stride <= (4u << 20) && t->precision >= 7;
     if (t->fast_enc_ok) {
         const uint32_t one = 1u << t->precision;
         t->enc.assign(static_cast<size_t>(t->rows) * t->stride * 4, 0u);
@@ -1101,6 +1104,10 @@ constexpr size_t kLdsTableBudget = 144 * 1024;  // of the 160 KiB per CU
 // which the decoder's 124 KB search image would otherwise claim -- to transforms running on other HIP streams.
 thread_local int g_wpb_override = 0;   // set by a codec session around its launches (basic::set_rans_waves)
 
+// What this thread launched last (basic_rans_last_launch): written where a kernel is chosen, read by tests.
+thread_local int g_last_kernel = BASIC_RANS_KERNEL_NONE, g_last_waves = 0;
+inline void note_launch(int kernel, int waves) { g_last_kernel = kernel; g_last_waves = waves; }
+
 int rans_waves_per_block(int nstreams)
 {
     static const int forced = [] { const char *e = getenv("BASIC_RANS_WPB"); return e ? atoi(e) : 0; }();
@@ -1120,6 +1127,8 @@ int launch_decode_v(const basic_rans_tables *t, const ArDev &ar, int nstreams, h
 {
     const size_t lds = LDS ? t->cdf16.size() * sizeof(uint16_t) : 0;
     if (LDS) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(rans_decode_kernel<AR, LDS>)));
+    note_launch(AR ? (LDS ? BASIC_RANS_KERNEL_DEC_AR_LDS : BASIC_RANS_KERNEL_DEC_AR_GLOBAL)
+                   : (LDS ? BASIC_RANS_KERNEL_DEC_GENERAL_LDS : BASIC_RANS_KERNEL_DEC_GENERAL_GLOBAL), 1);
     hipLaunchKernelGGL((rans_decode_kernel<AR, LDS>), dim3(nstreams), dim3(64), lds, st, dev_view(t), ar, d_words, d_word_off,
                        d_indexes, d_seg, d_out, d_state, d_pos, ss);
     BASIC_HIP_TRY(hipGetLastError());
@@ -1138,6 +1147,7 @@ int launch_decode(const basic_rans_tables *t, const ArDev &ar, int nstreams, hip
     if (!ar.tab && t->fast_ok) {
         const size_t lds_img = t->image.size() * sizeof(uint32_t);
         const int wpb = rans_waves_per_block(nstreams);
+        note_launch(BASIC_RANS_KERNEL_DEC_FAST, wpb);
 #define BASIC_DEC_LAUNCH(W)                                                                                              \
         do {                                                                                                             \
             BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(rans_decode_fast_kernel<W>)));                   \
@@ -1168,7 +1178,7 @@ namespace basic {
 int rans_fast_view(const basic_rans_tables *t, RansFastView *out)
 {
     BASIC_REQUIRE(t && out, "rans_fast_view: null argument");
-    BASIC_REQUIRE(t->fast_ok && !t->d_ar, "rans_fast_view: this table set has no fast-decoder image (rows > 4096 entries, image > 156 KB, or AR remap)");
+    BASIC_REQUIRE(t->fast_ok && !t->d_ar, "rans_fast_view: this table set has no fast-decoder image (rows > 4096 entries, image > 156 KB, precision < 7, or AR remap)");
     out->image = t->d_image; out->meta = t->d_meta; out->sizes = t->d_sizes; out->offsets = t->d_offsets;
     out->image_words = static_cast<int>(t->image.size()); out->rows = t->rows; out->precision = t->precision;
     out->bypass = t->bypass ? 1 : 0; out->bypass_precision = t->bypass_precision;
@@ -1182,6 +1192,24 @@ int set_rans_waves(int waves_per_block)
     return prev;
 }
 }  // namespace basic
+
+extern "C" int basic_rans_last_launch(int *kernel, int *waves)
+{
+    BASIC_REQUIRE(kernel || waves, "rans_last_launch: null argument");
+    if (kernel) *kernel = g_last_kernel;
+    if (waves) *waves = g_last_waves;
+    return BASIC_OK;
+}
+
+extern "C" int basic_rans_set_waves(int waves_per_block, int *previous)
+{
+    BASIC_REQUIRE(waves_per_block == 0 || waves_per_block == 1 || waves_per_block == 2 || waves_per_block == 4 || waves_per_block == 8 ||
+                      waves_per_block == 16,
+                  "rans_set_waves: waves per workgroup must be 0 (environment), 1, 2, 4, 8 or 16");
+    const int prev = basic::set_rans_waves(waves_per_block);
+    if (previous) *previous = prev;
+    return BASIC_OK;
+}
 
 namespace {
 inline void put_be32(uint8_t *p, uint32_t v) { p[0] = v >> 24; p[1] = (v >> 16) & 0xFF; p[2] = (v >> 8) & 0xFF; p[3] = v & 0xFF; }
@@ -1260,6 +1288,7 @@ extern "C" int basic_rans_encode_batch_dev(const basic_rans_tables *t, const int
         const int wpb_ = rans_waves_per_block(nstreams);
         size_t lds_rows = static_cast<size_t>(t->rows) * sizeof(int2);
         if (wpb_ > 1 && lds_rows < 159 * 1024) lds_rows = 159 * 1024;
+        note_launch(BASIC_RANS_KERNEL_ENC_FAST, wpb_);
 #define BASIC_ENC_LAUNCH(W)                                                                                          \
         do {                                                                                                         \
         if (lds_rows > 64 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(rans_encode_fast_kernel<W>))); \
@@ -1279,6 +1308,7 @@ extern "C" int basic_rans_encode_batch_dev(const basic_rans_tables *t, const int
         return BASIC_OK;
     }
     ArDev ar{};
+    note_launch(BASIC_RANS_KERNEL_ENC_GENERAL, 1);
     hipLaunchKernelGGL(rans_encode_kernel, dim3(nstreams), dim3(64), 0, as_stream(hip_stream), dev_view(t), ar,
                        d_symbols, d_indexes, d_seg, d_out_words, slot_words, d_out_nwords);
     BASIC_HIP_TRY(hipGetLastError());
@@ -1465,6 +1495,7 @@ int encode_host_impl(const basic_rans_tables *t, const int32_t *symbols, const i
     ArDev ar{};
     int rc = use_ar ? stage_ar(t, n, ar_indexes, ar_off0, ar_off1, ar_off2, b_ai, b_o0, b_o1, b_o2, ar) : BASIC_OK;
     if (rc) return rc;
+    note_launch(!ar.tab && t->fast_enc_ok ? BASIC_RANS_KERNEL_ENC_FAST : ar.tab ? BASIC_RANS_KERNEL_ENC_GENERAL_AR : BASIC_RANS_KERNEL_ENC_GENERAL, 1);
     if (!ar.tab && t->fast_enc_ok)  // same kernel choice as the batched device entry point
         hipLaunchKernelGGL(rans_encode_fast_kernel<1>, dim3(1), dim3(64), static_cast<size_t>(t->rows) * sizeof(int2), nullptr,
                            dev_view(t), b_sym.as<int32_t>(), b_idx.as<int32_t>(), b_seg.as<int64_t>(), b_out.as<uint32_t>(),

@@ -669,6 +669,9 @@ size_t tans_lds_bytes(const basic_tans_tables *t, bool decoder)
     return bytes <= 144 * 1024 ? bytes : 0;
 }
 
+// What this thread launched last (basic_tans_last_launch): written where a kernel is chosen, read by tests.
+thread_local int g_last_kernel = BASIC_TANS_KERNEL_NONE;
+
 TansDev dev_view(const basic_tans_tables *t)
 {
     TansDev T{};
@@ -700,6 +703,7 @@ extern "C" int basic_tans_encode_batch_dev(const basic_tans_tables *t, const int
     const size_t lds = tans_lds_bytes(t, false);
     T.lds_words = static_cast<int>(lds / 4);
     if (lds > 48 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(tans_encode_kernel<true>)));
+    g_last_kernel = lds ? BASIC_TANS_KERNEL_ENC_LDS : BASIC_TANS_KERNEL_ENC_GLOBAL;
     if (lds) hipLaunchKernelGGL(tans_encode_kernel<true>, dim3(nstreams), dim3(64), lds, as_stream(hip_stream), T, d_symbols, d_indexes, d_seg,
                                 d_out_words, slot_words, d_out_info);
     else hipLaunchKernelGGL(tans_encode_kernel<false>, dim3(nstreams), dim3(64), 0, as_stream(hip_stream), T, d_symbols, d_indexes, d_seg,
@@ -720,6 +724,7 @@ extern "C" int basic_tans_decode_batch_dev(const basic_tans_tables *t, const uin
     const size_t lds = tans_lds_bytes(t, true);
     T.lds_words = static_cast<int>(lds / 4);
     if (lds > 48 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(tans_decode_kernel<true>)));
+    g_last_kernel = lds ? BASIC_TANS_KERNEL_DEC_LDS : BASIC_TANS_KERNEL_DEC_GLOBAL;
     if (lds) hipLaunchKernelGGL(tans_decode_kernel<true>, dim3(nstreams), dim3(64), lds, as_stream(hip_stream), T, d_bytes, d_byte_off, d_indexes,
                                 d_seg, d_out_symbols, d_status);
     else hipLaunchKernelGGL(tans_decode_kernel<false>, dim3(nstreams), dim3(64), 0, as_stream(hip_stream), T, d_bytes, d_byte_off, d_indexes,
@@ -791,6 +796,7 @@ extern "C" int basic_tans_encode_host(const basic_tans_tables *t, const int32_t 
     const size_t lds = n >= 2048 ? tans_lds_bytes(t, false) : 0;   // short streams: the copy would cost more than it saves
     T.lds_words = static_cast<int>(lds / 4);
     if (lds > 48 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(tans_encode_kernel<true>)));
+    g_last_kernel = lds ? BASIC_TANS_KERNEL_ENC_LDS : BASIC_TANS_KERNEL_ENC_GLOBAL;
     if (lds) hipLaunchKernelGGL(tans_encode_kernel<true>, dim3(1), dim3(64), lds, nullptr, T, b_sym.as<int32_t>(), b_idx.as<int32_t>(), b_seg.as<int64_t>(),
                                 b_out.as<uint32_t>(), slot_words, b_info.as<int64_t>());
     else hipLaunchKernelGGL(tans_encode_kernel<false>, dim3(1), dim3(64), 0, nullptr, T, b_sym.as<int32_t>(), b_idx.as<int32_t>(), b_seg.as<int64_t>(),
@@ -836,6 +842,7 @@ extern "C" int basic_tans_decode_host(const basic_tans_tables *t, const uint8_t 
     const size_t lds = n >= 2048 ? tans_lds_bytes(t, true) : 0;
     T.lds_words = static_cast<int>(lds / 4);
     if (lds > 48 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(tans_decode_kernel<true>)));
+    g_last_kernel = lds ? BASIC_TANS_KERNEL_DEC_LDS : BASIC_TANS_KERNEL_DEC_GLOBAL;
     if (lds) hipLaunchKernelGGL(tans_decode_kernel<true>, dim3(1), dim3(64), lds, nullptr, T, b_bytes.as<uint8_t>(), b_boff.as<int64_t>(), b_idx.as<int32_t>(),
                                 b_seg.as<int64_t>(), b_out.as<int32_t>(), b_status.as<int32_t>());
     else hipLaunchKernelGGL(tans_decode_kernel<false>, dim3(1), dim3(64), 0, nullptr, T, b_bytes.as<uint8_t>(), b_boff.as<int64_t>(), b_idx.as<int32_t>(),
@@ -845,5 +852,12 @@ extern "C" int basic_tans_decode_host(const basic_tans_tables *t, const uint8_t 
     BASIC_HIP_TRY(hipMemcpy(&status, b_status.p, sizeof(status), hipMemcpyDeviceToHost));
     if (status) { set_error("Error (generic)"); return BASIC_ERR_INVALID; }
     if (n) BASIC_HIP_TRY(hipMemcpy(out_symbols, b_out.p, bytes, hipMemcpyDeviceToHost));
+    return BASIC_OK;
+}
+
+extern "C" int basic_tans_last_launch(int *kernel)
+{
+    BASIC_REQUIRE(kernel, "tans_last_launch: null argument");
+    *kernel = g_last_kernel;
     return BASIC_OK;
 }

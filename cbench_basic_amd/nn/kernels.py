@@ -4,6 +4,7 @@ PyTorch is used here for device memory and streams only; every operation below i
 hand-written HIP kernel.  All functions require CUDA(HIP) tensors and raise otherwise --
 there is no CPU implementation behind them.
 """
+import contextlib
 import ctypes
 import os
 
@@ -149,6 +150,34 @@ class MaskedConvPlan:
         return out
 
 
+# BASIC_RANS_KERNEL_* (include/basic_hip.h): what a rANS launch ran
+(RANS_KERNEL_NONE, RANS_KERNEL_ENC_FAST, RANS_KERNEL_ENC_GENERAL, RANS_KERNEL_ENC_GENERAL_AR, RANS_KERNEL_DEC_FAST,
+ RANS_KERNEL_DEC_GENERAL_LDS, RANS_KERNEL_DEC_GENERAL_GLOBAL, RANS_KERNEL_DEC_AR_LDS, RANS_KERNEL_DEC_AR_GLOBAL) = range(-1, 8)
+RANS_KERNEL_NAMES = {RANS_KERNEL_NONE: "NONE", RANS_KERNEL_ENC_FAST: "ENC_FAST", RANS_KERNEL_ENC_GENERAL: "ENC_GENERAL",
+                     RANS_KERNEL_ENC_GENERAL_AR: "ENC_GENERAL_AR", RANS_KERNEL_DEC_FAST: "DEC_FAST",
+                     RANS_KERNEL_DEC_GENERAL_LDS: "DEC_GENERAL_LDS", RANS_KERNEL_DEC_GENERAL_GLOBAL: "DEC_GENERAL_GLOBAL",
+                     RANS_KERNEL_DEC_AR_LDS: "DEC_AR_LDS", RANS_KERNEL_DEC_AR_GLOBAL: "DEC_AR_GLOBAL"}
+
+
+def rans_last_launch():
+    """(RANS_KERNEL_*, wavefronts per workgroup) of the calling thread's last rANS launch; (RANS_KERNEL_NONE, 0) before any."""
+    k, w = ctypes.c_int(RANS_KERNEL_NONE), ctypes.c_int(0)
+    _lib.check(_lib.lib().basic_rans_last_launch(ctypes.byref(k), ctypes.byref(w)))
+    return k.value, w.value
+
+
+@contextlib.contextmanager
+def rans_waves(w):
+    """Wavefronts (streams) per workgroup of the fast rANS kernels inside the block, for the calling thread: 1, 2, 4, 8 or 16
+    (0: the environment's BASIC_RANS_WPB).  The previous value comes back on exit."""
+    prev = ctypes.c_int(0)
+    _lib.check(_lib.lib().basic_rans_set_waves(int(w), ctypes.byref(prev)))
+    try:
+        yield
+    finally:
+        _lib.check(_lib.lib().basic_rans_set_waves(prev.value, None))
+
+
 class RansTables:
     """Device-resident CDF tables (basic_rans_tables_*) for the batched stream coder."""
 
@@ -175,6 +204,11 @@ class RansTables:
                 _lib.lib().basic_rans_tables_destroy(h)
             except Exception:
                 pass
+
+    @staticmethod
+    def last_launch():
+        """rans_last_launch(): tables do not launch on their own thread, so the record is the calling thread's."""
+        return rans_last_launch()
 
     def get_cdfs(self):
         rows, mx = ctypes.c_int(), ctypes.c_int()

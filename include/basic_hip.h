@@ -155,6 +155,25 @@ int basic_rans_decode_batch_streams_dev(const basic_rans_tables *t, const uint32
                                         int nimages, int stream_first, int stream_stride, int32_t *d_out_symbols,
                                         uint64_t *d_state, int64_t *d_pos, void *hip_stream);
 
+/* Which kernel the calling thread's last rANS launch was (host or device entry point, scan-line step decodes included), so
+ * that a test can tell which of the table-dependent paths it ran.  ENC_FAST / DEC_FAST are the lane-parallel kernels, with
+ * *waves = wavefronts (streams) per workgroup; the others run one wavefront per workgroup (*waves = 1).  LDS / GLOBAL: the
+ * packed 16-bit rows are copied to the LDS, or searched in global memory (packed copy over 144 KiB). */
+#define BASIC_RANS_KERNEL_NONE (-1) /* no launch by this thread yet */
+#define BASIC_RANS_KERNEL_ENC_FAST 0
+#define BASIC_RANS_KERNEL_ENC_GENERAL 1
+#define BASIC_RANS_KERNEL_ENC_GENERAL_AR 2
+#define BASIC_RANS_KERNEL_DEC_FAST 3
+#define BASIC_RANS_KERNEL_DEC_GENERAL_LDS 4
+#define BASIC_RANS_KERNEL_DEC_GENERAL_GLOBAL 5
+#define BASIC_RANS_KERNEL_DEC_AR_LDS 6
+#define BASIC_RANS_KERNEL_DEC_AR_GLOBAL 7
+int basic_rans_last_launch(int *kernel, int *waves);
+/* Wavefronts per workgroup of the fast kernels for the calling thread's launches: 1, 2, 4, 8 or 16; 0 hands the choice back to
+ * the environment variable BASIC_RANS_WPB (read once per process; default 1), over which any other value takes precedence.
+ * *previous (optional) = the value replaced.  A codec session sets it around its own launches (basic_hp_session_set_rans_waves). */
+int basic_rans_set_waves(int waves_per_block, int *previous);
+
 /* ======================================================================================
  * 4. Entropy-parameter kernels (coalesced elementwise, fused quantise + table index).
  * ==================================================================================== */
@@ -556,6 +575,14 @@ int basic_tans_encode_batch_dev(const basic_tans_tables *t, const int32_t *d_sym
 int basic_tans_decode_batch_dev(const basic_tans_tables *t, const uint8_t *d_bytes, const int64_t *d_byte_off,
                                 const int32_t *d_indexes, const int64_t *d_seg, int nstreams, int32_t *d_out_symbols,
                                 int32_t *d_status, void *hip_stream);
+/* Which kernel the calling thread's last tANS launch was (host or device entry point): LDS = the state-dependent image is
+ * copied to the LDS, GLOBAL = read from global memory (image over 144 KiB; host entry points: streams under 2048 symbols). */
+#define BASIC_TANS_KERNEL_NONE (-1) /* no launch by this thread yet */
+#define BASIC_TANS_KERNEL_ENC_LDS 0
+#define BASIC_TANS_KERNEL_ENC_GLOBAL 1
+#define BASIC_TANS_KERNEL_DEC_LDS 2
+#define BASIC_TANS_KERNEL_DEC_GLOBAL 3
+int basic_tans_last_launch(int *kernel);
 
 #ifdef __cplusplus
 }

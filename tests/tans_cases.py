@@ -73,3 +73,53 @@ def run(mod, case):
         dec.init_params(freqs, nsym, off)
         back = dec.decode_with_indexes(data, idx)
     return None, data, back
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# launch paths of csrc/tans.hip (tests/test_cpu_rans_cases.py, tests/test_gpu_rans_paths.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+PATH_STREAMS = 37
+# (table_log, distributions): with bypass coding on, the images hold nd + 1 rows of 2^L states -- decoder 4 bytes per state,
+# encoder 2 -- and stay in the LDS up to 144 KiB (tans_lds_bytes): at L = 12 the decoder leaves it at 9 rows, the encoder at 18
+PATH_CONFIGS = ((12, 8), (12, 9), (12, 17), (12, 18), (9, 5))
+
+
+def path_kernels(L, nd, bypass=True):
+    """(encoder, decoder) BASIC_TANS_KERNEL_* names of the batched entry points: tans_lds_bytes of tans.hip, restated."""
+    rows = nd + (1 if bypass else 0)
+    fits = lambda per_state: rows * (1 << L) * per_state <= 144 * 1024
+    return "ENC_LDS" if fits(2) else "ENC_GLOBAL", "DEC_LDS" if fits(4) else "DEC_GLOBAL"
+
+
+def path_case(L, nd):
+    """37 ragged streams (one empty, one of a single symbol) over nd distributions, bypass coding on: the shared table
+    arguments and one `run` case per stream."""
+    rng = np.random.default_rng(1000 * L + nd)
+    ns = 90 if L >= 11 else 40
+    freqs = rng.integers(1, 1024, (nd, ns)).astype(np.int32)
+    freqs[0, : ns // 2] = 1                      # a row with many symbols of the smallest count
+    nsym = rng.integers(ns // 2, ns + 1, nd).astype(np.int32)
+    nsym[0] = ns
+    off = rng.integers(-4, 4, nd).astype(np.int32)
+    lens = rng.integers(2, 700, PATH_STREAMS)
+    lens[[3, 5, 36]] = 0, 1, 64
+    streams = []
+    for n in lens.tolist():
+        idx = rng.integers(0, nd, n).astype(np.int32)
+        sym = (off[idx] + rng.integers(-2, 1 << 30, n) % (nsym[idx] + 3)).astype(np.int32)
+        sym[::17] = rng.integers(-3000, 3000, sym[::17].size)
+        streams.append((L, freqs, nsym, off, True, sym, idx))
+    return streams
+
+
+def run_raw(mod, case):
+    """(bytes, symbols coded incl. bypass digits, decoded) of one case through the ORACLE module without the reference's
+    output budget (capacity_syms: a stream that does not fit len(indexes) * table_log / 8 - 8 bytes comes back empty there, and
+    five symbols or fewer are an error; `run` keeps that rule) -- the raw stream, which is what the batched entry points write."""
+    L, freqs, nsym, off, byp, sym, idx = case
+    enc = mod.TansEncoder(L, 255, byp, 4)
+    enc.init_params(freqs, nsym, off)
+    data = enc.encode_with_indexes(sym, idx, capacity_syms=1 << 40)
+    dec = mod.TansDecoder(L, 255, byp, 4)
+    dec.init_params(freqs, nsym, off)
+    return data, enc.coded_symbols, dec.decode_with_indexes(data, idx)
