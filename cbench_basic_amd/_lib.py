@@ -59,6 +59,7 @@ _SIGNATURES = {
     "basic_rans_last_launch": (_I, [_P, _P]),
     "basic_rans_set_waves": (_I, [_I, _P]),
     "basic_lanes_pack_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "basic_group_lanes_pack_dev": (_I, [_P, _P, _I, _L, _P, _I, _I, _P, _P, _P]),
     "basic_gc_quantize_index_dev": (_I, [_P, _P, _L, _P, _I, _F, _P, _P, _P, _P]),
     "basic_eb_quantize_index_dev": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "basic_eb_dequantize_dev": (_I, [_P, _P, _I, _I, _I, _P, _P]),
@@ -79,6 +80,7 @@ _SIGNATURES = {
     "basic_hp_decoded_shape": (_I, [_P, _P, _L, _P, _P, _P, _P]),
     "basic_hp_decode_images": (_I, [_P, _P, _L, _P, _L, _P]),
     "basic_hp_session_set_rans_waves": (_I, [_P, _I]),
+    "basic_hp_session_set_stream_lanes": (_I, [_P, _I]),
     "basic_hp_session_set_transform_token": (_I, [_P, _I]),
     "basic_hp_session_destroy": (None, [_P]),
     "basic_conv_plan_destroy": (None, [_P]),

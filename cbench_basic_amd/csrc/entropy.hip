@@ -118,6 +118,35 @@ __global__ void lanes_pack_kernel(const int32_t *__restrict__ sym, const int32_t
     }
 }
 
+// lane streams of the group coders (GaussianConditional: one group; topo-group coders: the plan's groups): both arrays from
+// group-major coding order [B][n] to one run per lane stream, [B][K][n / K], where stream (b, k) is the concatenation over the
+// groups g of the k-th of K equal parts of group g.  bases[0 .. G] are the groups' first elements (bases[G] = n), every group
+// a multiple of K long (the caller's rule; an element a broken table would send past the image is left unwritten).  A thread
+// owns an output element and finds its group by bisection: stores are contiguous, loads contiguous within a part.
+__global__ void group_lanes_pack_kernel(const int32_t *__restrict__ sym, const int32_t *__restrict__ idx, int64_t total, int64_t n,
+                                        const int64_t *__restrict__ bases, int groups, int lanes, int32_t *__restrict__ sym_out,
+                                        int32_t *__restrict__ idx_out)
+{
+    const int64_t per = n / lanes;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
+         i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int64_t b = i / n, r = i - b * n;
+        const int64_t k = r / per, o = r - k * per;   // element o of lane stream (b, k)
+        const int64_t t = o * lanes;                  // the group holding it is the last one that starts at or before t
+        int lo = 0, hi = groups - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (bases[mid] <= t) lo = mid; else hi = mid - 1;
+        }
+        const int64_t gb = bases[lo], part = (bases[lo + 1] - gb) / lanes;
+        const int64_t src = gb + k * part + (o - gb / lanes);
+        if (src >= 0 && src < n) {
+            sym_out[i] = sym[b * n + src];
+            idx_out[i] = idx[b * n + src];
+        }
+    }
+}
+
 // argmin_j |s - table[j]|, first minimum (torch.argmin on CPU returns the first occurrence).
 __device__ __forceinline__ int nearest_scale(float s, const float *tab, int n)
 {
@@ -346,6 +375,19 @@ extern "C" int basic_lanes_pack_dev(const int32_t *d_sym, const int32_t *d_idx, 
     const int64_t total = static_cast<int64_t>(batch) * positions * channels;
     hipLaunchKernelGGL(lanes_pack_kernel, dim3(grid_for(total)), dim3(kBlock), 0, as_stream(hip_stream), d_sym, d_idx, total, positions,
                        lanes, channels / lanes, d_sym_out, d_idx_out);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_group_lanes_pack_dev(const int32_t *d_sym, const int32_t *d_idx, int batch, int64_t n, const int64_t *d_bases,
+                                          int groups, int lanes, int32_t *d_sym_out, int32_t *d_idx_out, void *hip_stream)
+{
+    BASIC_REQUIRE(d_sym && d_idx && d_bases && d_sym_out && d_idx_out && batch >= 1 && n >= 1 && groups >= 1 && lanes >= 1 &&
+                      lanes <= 256 && n % lanes == 0 && d_sym_out != d_sym && d_idx_out != d_idx,
+                  "group_lanes_pack: bad argument (lanes in [1, 256] must divide n; out of place)");
+    const int64_t total = static_cast<int64_t>(batch) * n;
+    hipLaunchKernelGGL(group_lanes_pack_kernel, dim3(grid_for(total)), dim3(kBlock), 0, as_stream(hip_stream), d_sym, d_idx, total, n,
+                       d_bases, groups, lanes, d_sym_out, d_idx_out);
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
 }

@@ -113,6 +113,8 @@ struct basic_hp_session {
     int z_channels = 0, y_channels = 0, x_channels = 0, out_channels = 0, n_scales = 0;
     float scale_bound = 0.11f;
     int rans_waves = 0;
+    int lanes = 1;       // y streams per image (basic_hp_session_set_stream_lanes)
+    int res_lanes = 1;   // of the encoded batch held in h_words
     DBuf d_medians, d_table;
     DBuf act[2], d_x, d_y, d_z, d_zhat, d_prior, d_scales;
     DBuf z_sym, z_idx, y_sym, y_idx, seg_z, seg_y, slots_z, slots_y, nw, off, packed, words, woff, state, pos;
@@ -371,14 +373,23 @@ extern "C" int basic_hp_session_set_rans_waves(basic_hp_session *s, int waves_pe
     return BASIC_OK;
 }
 
+extern "C" int basic_hp_session_set_stream_lanes(basic_hp_session *s, int lanes)
+{
+    BASIC_REQUIRE(s && lanes >= 1 && lanes <= 256, "hp_session_set_stream_lanes: an integer in [1, 256]");
+    s->lanes = lanes;
+    s->res_batch = 0;   // a held batch was framed for the previous lane count
+    return BASIC_OK;
+}
+
 extern "C" int64_t basic_hp_encode_bound(const basic_hp_session *s, int batch, int h, int w)
 {
     if (!s || batch < 1 || h < 1 || w < 1) return -1;
     int yh, yw, zh, zw;
     if (chain_out_hw(s->g_a, h, w, &yh, &yw) || chain_out_hw(s->h_a, yh, yw, &zh, &zw)) return -1;
     const int64_t ny = static_cast<int64_t>(s->y_channels) * yh * yw, nz = static_cast<int64_t>(s->z_channels) * zh * zw;
-    // worst case of the coder: 3 n + 4 words per stream (the retry slot of the bypass-heavy case)
-    return 4 + 2 * (12 + 4ll * batch) + 4ll * batch * ((3 * ny + 4) + (3 * nz + 4));
+    // worst case of the coder: 3 n + 4 words per stream (the retry slot of the bypass-heavy case); y: lanes streams per image
+    const int64_t K = s->lanes;
+    return 4 + (12 + 4ll * batch) + (12 + 4ll * batch * K) + 4ll * batch * ((3 * ny + 4 * K) + (3 * nz + 4));
 }
 
 namespace {
@@ -440,17 +451,22 @@ extern "C" int basic_hp_encode_images(basic_hp_session *s, const float *x, int x
     rc = run_chain(s, s->h_a, s->d_y.as<float>(), batch, yh, yw, &s->d_z, nullptr, &zh, &zw, st);
     if (rc) return rc;
     const int64_t nz = static_cast<int64_t>(s->z_channels) * zh * zw, ny = static_cast<int64_t>(s->y_channels) * yh * yw;
+    // lane streams: the y latent of image b is K contiguous runs of ny / K symbols, stream b * K + k (the z path keeps one stream)
+    const int K = s->lanes;
+    BASIC_REQUIRE(ny % K == 0, "hp_encode_images: stream_lanes does not divide the y latent (channels * h * w) of this call");
+    const int sy = batch * K;
+    const int64_t nyl = ny / K;
     // ---- node z: EntropyBottleneck symbols + de-quantised latent (compressai_coder.py:203-236), rANS
     rc = s->z_sym.ensure(sizeof(int32_t) * batch * nz);
     if (!rc) rc = s->z_idx.ensure(sizeof(int32_t) * batch * nz);
     if (!rc) rc = s->d_zhat.ensure(sizeof(float) * batch * nz);
-    if (!rc) rc = s->nw.ensure(sizeof(int32_t) * 2 * batch);
-    if (!rc) rc = s->off.ensure(sizeof(int64_t) * 2 * (batch + 1));
+    if (!rc) rc = s->nw.ensure(sizeof(int32_t) * (batch + sy));
+    if (!rc) rc = s->off.ensure(sizeof(int64_t) * ((batch + 1) + (sy + 1)));
     if (rc) return rc;
     rc = basic_eb_quantize_index_dev(s->d_z.as<float>(), s->d_medians.as<float>(), batch, s->z_channels, zh * zw,
                                      s->z_sym.as<int32_t>(), s->z_idx.as<int32_t>(), s->d_zhat.as<float>(), st);
     if (rc) return rc;
-    int64_t slot_z = nz + 2, slot_y = ny + 2;   // the reference's own buffer size (rans64.cpp:240)
+    int64_t slot_z = nz + 2, slot_y = nyl + 2;   // the reference's own buffer size (rans64.cpp:240), per stream
     int32_t *d_nw_z = s->nw.as<int32_t>(), *d_nw_y = s->nw.as<int32_t>() + batch;
     rc = encode_latent(s, s->z_tables, s->z_sym.as<int32_t>(), s->z_idx.as<int32_t>(), batch, nz, &s->seg_z, &s->slots_z, d_nw_z,
                        slot_z, st);
@@ -474,29 +490,30 @@ extern "C" int basic_hp_encode_images(basic_hp_session *s, const float *x, int x
     rc = basic_gc_quantize_index_dev(s->d_y.as<float>(), d_scales, batch * ny, s->d_table.as<float>(), s->n_scales, s->scale_bound,
                                      s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
     if (rc) return rc;
-    rc = encode_latent(s, s->y_tables, s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), batch, ny, &s->seg_y, &s->slots_y, d_nw_y,
+    rc = encode_latent(s, s->y_tables, s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), sy, nyl, &s->seg_y, &s->slots_y, d_nw_y,
                        slot_y, st);
     if (rc) return rc;
     // ---- stream lengths to the host; offsets and compaction on the device meanwhile
-    rc = s->h_nw.ensure(sizeof(int32_t) * 2 * batch + sizeof(int64_t) * 2 * (batch + 1));
+    rc = s->h_nw.ensure(sizeof(int32_t) * (batch + sy));
     if (rc) return rc;
     int32_t *h_nw = s->h_nw.as<int32_t>();
     for (int attempt = 0;; ++attempt) {
         int64_t *d_off_z = s->off.as<int64_t>(), *d_off_y = s->off.as<int64_t>() + (batch + 1);
         hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(64), 0, st, d_nw_z, batch, d_off_z);
-        hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(64), 0, st, d_nw_y, batch, d_off_y);
+        hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(64), 0, st, d_nw_y, sy, d_off_y);
         BASIC_HIP_TRY(hipGetLastError());
         // both latents' streams share one packed buffer: z first, then y (each at its own base)
-        rc = s->packed.ensure(sizeof(uint32_t) * static_cast<size_t>(batch) * (slot_z + slot_y));
+        rc = s->packed.ensure(sizeof(uint32_t) * (static_cast<size_t>(batch) * slot_z + static_cast<size_t>(sy) * slot_y));
         if (rc) return rc;
         uint32_t *d_pz = s->packed.as<uint32_t>(), *d_py = d_pz + static_cast<size_t>(batch) * slot_z;
         rc = basic_rans_compact_streams_dev(s->slots_z.as<uint32_t>(), slot_z, d_nw_z, d_off_z, batch, d_pz, st);
-        if (!rc) rc = basic_rans_compact_streams_dev(s->slots_y.as<uint32_t>(), slot_y, d_nw_y, d_off_y, batch, d_py, st);
+        if (!rc) rc = basic_rans_compact_streams_dev(s->slots_y.as<uint32_t>(), slot_y, d_nw_y, d_off_y, sy, d_py, st);
         if (rc) return rc;
-        BASIC_HIP_TRY(hipMemcpyAsync(h_nw, s->nw.p, sizeof(int32_t) * 2 * batch, hipMemcpyDeviceToHost, st));
+        BASIC_HIP_TRY(hipMemcpyAsync(h_nw, s->nw.p, sizeof(int32_t) * (batch + sy), hipMemcpyDeviceToHost, st));
         BASIC_HIP_TRY(hipStreamSynchronize(st));
         bool over_z = false, over_y = false;
-        for (int i = 0; i < batch; ++i) { over_z |= h_nw[i] < 0; over_y |= h_nw[batch + i] < 0; }
+        for (int i = 0; i < batch; ++i) over_z |= h_nw[i] < 0;
+        for (int i = 0; i < sy; ++i) over_y |= h_nw[batch + i] < 0;
         if (!over_z && !over_y) break;
         BASIC_REQUIRE(attempt == 0, "hp_encode_images: rANS slot overflow with the guaranteed slot size");
         // bypass-heavy data overflowed the reference's bound (undefined behaviour there): redo with the guaranteed one
@@ -507,16 +524,17 @@ extern "C" int basic_hp_encode_images(basic_hp_session *s, const float *x, int x
             if (rc) return rc;
         }
         if (over_y) {
-            slot_y = 3 * ny + 4;
-            rc = encode_latent(s, s->y_tables, s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), batch, ny, &s->seg_y, &s->slots_y, d_nw_y,
+            slot_y = 3 * nyl + 4;   // guaranteed per lane stream
+            rc = encode_latent(s, s->y_tables, s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), sy, nyl, &s->seg_y, &s->slots_y, d_nw_y,
                                slot_y, st);
             if (rc) return rc;
         }
     }
     s->off_z.assign(batch + 1, 0);
-    s->off_y.assign(batch + 1, 0);
-    for (int i = 0; i < batch; ++i) { s->off_z[i + 1] = s->off_z[i] + h_nw[i]; s->off_y[i + 1] = s->off_y[i] + h_nw[batch + i]; }
-    const int64_t wz = s->off_z[batch], wy = s->off_y[batch];
+    s->off_y.assign(sy + 1, 0);
+    for (int i = 0; i < batch; ++i) s->off_z[i + 1] = s->off_z[i] + h_nw[i];
+    for (int i = 0; i < sy; ++i) s->off_y[i + 1] = s->off_y[i] + h_nw[batch + i];
+    const int64_t wz = s->off_z[batch], wy = s->off_y[sy];
     rc = s->h_words.ensure(sizeof(uint32_t) * static_cast<size_t>(wz + wy));
     if (rc) return rc;
     uint32_t *h_wz = s->h_words.as<uint32_t>(), *h_wy = h_wz + wz;
@@ -526,8 +544,8 @@ extern "C" int basic_hp_encode_images(basic_hp_session *s, const float *x, int x
     BASIC_HIP_TRY(hipStreamSynchronize(st));
     rc = rejoin(s, caller_st, st);
     if (rc) return rc;
-    s->res_batch = batch; s->res_zh = zh; s->res_zw = zw; s->res_yh = yh; s->res_yw = yw;
-    *out_len = 4 + (12 + 4ll * batch + 4 * wz) + (12 + 4ll * batch + 4 * wy);
+    s->res_batch = batch; s->res_lanes = K; s->res_zh = zh; s->res_zw = zw; s->res_yh = yh; s->res_yw = yw;
+    *out_len = 4 + (12 + 4ll * batch + 4 * wz) + (12 + 4ll * sy + 4 * wy);
     if (!out) return BASIC_OK;   // the caller fetches the bytes with basic_hp_encode_result() once it knows their size
     return basic_hp_encode_result(s, out, out_capacity, out_len);
 }
@@ -536,10 +554,10 @@ extern "C" int basic_hp_encode_images(basic_hp_session *s, const float *x, int x
 extern "C" int basic_hp_encode_result(basic_hp_session *s, uint8_t *out, int64_t out_capacity, int64_t *out_len)
 {
     BASIC_REQUIRE(s && out && s->res_batch >= 1, "hp_encode_result: no encoded batch is held by this session");
-    const int batch = s->res_batch;
-    const int64_t wz = s->off_z[batch], wy = s->off_y[batch];
+    const int batch = s->res_batch, sy = batch * s->res_lanes;   // y body: the tabled form for batch * lanes streams
+    const int64_t wz = s->off_z[batch], wy = s->off_y[sy];
     const uint32_t *h_wz = s->h_words.as<uint32_t>(), *h_wy = h_wz + wz;
-    const int64_t len_z = 12 + 4ll * batch + 4 * wz, len_y = 12 + 4ll * batch + 4 * wy;
+    const int64_t len_z = 12 + 4ll * batch + 4 * wz, len_y = 12 + 4ll * sy + 4 * wy;
     if (out_len) *out_len = 4 + len_z + len_y;
     if (4 + len_z + len_y > out_capacity) { set_error("hp_encode_result: output buffer too small"); return BASIC_ERR_OVERFLOW; }
     BASIC_REQUIRE(len_z <= 0xFFFFFFFFll, "hp_encode_result: z body exceeds the 32-bit length prefix");
@@ -549,7 +567,7 @@ extern "C" int basic_hp_encode_result(basic_hp_session *s, uint8_t *out, int64_t
     int rc = basic_frame_streams(h_wz, s->off_z.data(), batch, static_cast<uint32_t>(s->res_zh), static_cast<uint32_t>(s->res_zw), out + 4,
                                  len_z, &written);
     if (rc) return rc;
-    return basic_frame_streams(h_wy, s->off_y.data(), batch, static_cast<uint32_t>(s->res_yh), static_cast<uint32_t>(s->res_yw),
+    return basic_frame_streams(h_wy, s->off_y.data(), sy, static_cast<uint32_t>(s->res_yh), static_cast<uint32_t>(s->res_yw),
                                out + 4 + len_z, len_y, &written);
 }
 
@@ -562,7 +580,7 @@ struct Body {
     int n = 0;
 };
 
-int split_bodies(const uint8_t *data, int64_t len, Body *z, Body *y)
+int split_bodies(const uint8_t *data, int64_t len, int lanes, Body *z, Body *y)
 {
     BASIC_REQUIRE(data && len >= 4 + 12 + 12, "hp_decode_images: truncated stream");
     uint32_t lz = 0;
@@ -573,7 +591,8 @@ int split_bodies(const uint8_t *data, int64_t len, Body *z, Body *y)
     int rc = basic_unframe_streams(z->p, z->len, &z->h, &z->w, &z->n, nullptr, 0, nullptr);
     if (!rc) rc = basic_unframe_streams(y->p, y->len, &y->h, &y->w, &y->n, nullptr, 0, nullptr);
     if (rc) return rc;
-    BASIC_REQUIRE(z->n == y->n && z->n >= 1, "hp_decode_images: z and y bodies hold different image counts");
+    BASIC_REQUIRE(z->n >= 1 && static_cast<int64_t>(y->n) == static_cast<int64_t>(z->n) * lanes,
+                  "hp_decode_images: the y body does not hold stream_lanes streams for every stream of the z body");
     return BASIC_OK;
 }
 
@@ -584,12 +603,12 @@ extern "C" int basic_hp_decoded_shape(const basic_hp_session *s, const uint8_t *
 {
     BASIC_REQUIRE(s, "hp_decoded_shape: null session");
     Body z, y;
-    int rc = split_bodies(data, len, &z, &y);
+    int rc = split_bodies(data, len, s->lanes, &z, &y);
     if (rc) return rc;
     int oh, ow;
     rc = chain_out_hw(s->g_s, static_cast<int>(y.h), static_cast<int>(y.w), &oh, &ow);
     if (rc) return rc;
-    if (batch) *batch = y.n;
+    if (batch) *batch = z.n;
     if (channels) *channels = s->out_channels;
     if (h) *h = oh;
     if (w) *w = ow;
@@ -603,23 +622,25 @@ extern "C" int basic_hp_decode_images(basic_hp_session *s, const uint8_t *data, 
     hipStream_t st = as_stream(hip_stream);
     WavesGuard guard(s->rans_waves, s->use_token);
     Body z, y;
-    int rc = split_bodies(data, len, &z, &y);
+    int rc = split_bodies(data, len, s->lanes, &z, &y);
     if (rc) return rc;
     hipStream_t caller_st = st;
     rc = entropy_stream(s, caller_st, &st);   // everything before g_s goes to the entropy stream
     if (rc) return rc;
-    const int batch = y.n, zh = z.h, zw = z.w, yh = y.h, yw = y.w;
+    const int batch = z.n, sy = y.n, K = s->lanes, zh = z.h, zw = z.w, yh = y.h, yw = y.w;
     int oh, ow;
     rc = chain_out_hw(s->g_s, yh, yw, &oh, &ow);
     if (rc) return rc;
     BASIC_REQUIRE(static_cast<int64_t>(batch) * s->out_channels * oh * ow <= xhat_capacity_floats, "hp_decode_images: output buffer too small");
     const int64_t nz = static_cast<int64_t>(s->z_channels) * zh * zw, ny = static_cast<int64_t>(s->y_channels) * yh * yw;
+    BASIC_REQUIRE(ny % K == 0, "hp_decode_images: stream_lanes does not divide the y latent (channels * h * w) of this stream");
+    const int64_t nyl = ny / K;   // y: stream b * K + k continues image b at symbol k * nyl -- contiguous runs of [B][ny]
     // ---- unframe both bodies into ONE pinned staging area [z words | y words | z offsets | y offsets] and upload it
-    const int64_t wz = (z.len - 12 - 4ll * batch) / 4, wy = (y.len - 12 - 4ll * batch) / 4;
+    const int64_t wz = (z.len - 12 - 4ll * batch) / 4, wy = (y.len - 12 - 4ll * sy) / 4;
     BASIC_REQUIRE(wz >= 0 && wy >= 0, "hp_decode_images: truncated body");
     const size_t words_bytes = sizeof(uint32_t) * static_cast<size_t>(wz + wy + 2);
     const size_t off_pad = (words_bytes + 7) & ~static_cast<size_t>(7);
-    const size_t total = off_pad + sizeof(int64_t) * 2 * (batch + 1);
+    const size_t total = off_pad + sizeof(int64_t) * ((batch + 1) + (sy + 1));
     if (s->in_done) BASIC_HIP_TRY(hipEventSynchronize(s->in_done));   // the previous call's upload out of h_in has finished
     else BASIC_HIP_TRY(hipEventCreateWithFlags(&s->in_done, hipEventDisableTiming));
     rc = s->h_in.ensure(total);
@@ -631,7 +652,7 @@ extern "C" int basic_hp_decode_images(basic_hp_session *s, const uint8_t *data, 
     uint32_t hh, ww;
     int nn;
     rc = basic_unframe_streams(z.p, z.len, &hh, &ww, &nn, h_oz, batch, h_wz);
-    if (!rc) rc = basic_unframe_streams(y.p, y.len, &hh, &ww, &nn, h_oy, batch, h_wy);
+    if (!rc) rc = basic_unframe_streams(y.p, y.len, &hh, &ww, &nn, h_oy, sy, h_wy);
     if (rc) return rc;
     BASIC_HIP_TRY(hipMemcpyAsync(s->words.p, hb, total, hipMemcpyHostToDevice, st));
     BASIC_HIP_TRY(hipEventRecord(s->in_done, st));
@@ -643,14 +664,14 @@ extern "C" int basic_hp_decode_images(basic_hp_session *s, const uint8_t *data, 
     if (!rc) rc = s->z_idx.ensure(sizeof(int32_t) * batch * nz);
     if (!rc) rc = s->d_zhat.ensure(sizeof(float) * batch * nz);
     if (!rc) rc = s->seg_z.ensure(sizeof(int64_t) * (batch + 1));
-    if (!rc) rc = s->seg_y.ensure(sizeof(int64_t) * (batch + 1));
-    if (!rc) rc = s->state.ensure(sizeof(uint64_t) * 2 * batch);
-    if (!rc) rc = s->pos.ensure(sizeof(int64_t) * 2 * batch);
+    if (!rc) rc = s->seg_y.ensure(sizeof(int64_t) * (sy + 1));
+    if (!rc) rc = s->state.ensure(sizeof(uint64_t) * (batch + sy));
+    if (!rc) rc = s->pos.ensure(sizeof(int64_t) * (batch + sy));
     if (rc) return rc;
     hipLaunchKernelGGL(channel_index_kernel, dim3(grid_for(batch * nz)), dim3(256), 0, st, s->z_idx.as<int32_t>(), s->z_channels, zh * zw,
                        batch * nz);
     hipLaunchKernelGGL(seg_init_kernel, dim3((batch + 256) / 256), dim3(256), 0, st, s->seg_z.as<int64_t>(), nz, batch, s->pos.as<int64_t>());
-    hipLaunchKernelGGL(seg_init_kernel, dim3((batch + 256) / 256), dim3(256), 0, st, s->seg_y.as<int64_t>(), ny, batch,
+    hipLaunchKernelGGL(seg_init_kernel, dim3((sy + 256) / 256), dim3(256), 0, st, s->seg_y.as<int64_t>(), nyl, sy,
                        s->pos.as<int64_t>() + batch);
     BASIC_HIP_TRY(hipGetLastError());
     rc = basic_rans_decode_batch_dev(s->z_tables, d_wz, d_oz, s->z_idx.as<int32_t>(), s->seg_z.as<int64_t>(), batch, s->z_sym.as<int32_t>(),
@@ -680,7 +701,7 @@ extern "C" int basic_hp_decode_images(basic_hp_session *s, const uint8_t *data, 
     rc = basic_gc_quantize_index_dev(d_scales, d_scales, batch * ny, s->d_table.as<float>(), s->n_scales, s->scale_bound,
                                      s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
     if (rc) return rc;
-    rc = basic_rans_decode_batch_dev(s->y_tables, d_wy, d_oy, s->y_idx.as<int32_t>(), s->seg_y.as<int64_t>(), batch, s->y_sym.as<int32_t>(),
+    rc = basic_rans_decode_batch_dev(s->y_tables, d_wy, d_oy, s->y_idx.as<int32_t>(), s->seg_y.as<int64_t>(), sy, s->y_sym.as<int32_t>(),
                                      s->state.as<uint64_t>() + batch, s->pos.as<int64_t>() + batch, st);
     if (rc) return rc;
     rc = basic_i32_to_f32_dev(s->y_sym.as<int32_t>(), batch * ny, s->d_y.as<float>(), st);

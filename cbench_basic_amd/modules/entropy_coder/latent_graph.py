@@ -452,6 +452,9 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         if getattr(sess, "_waves", 0) != self.fused_rans_waves:
             sess.set_rans_waves(self.fused_rans_waves)
             sess._waves = self.fused_rans_waves
+        if getattr(sess, "_lanes", 1) != yc.stream_lanes:   # the y coder's lane streams: the two paths write the same bytes
+            sess.set_stream_lanes(yc.stream_lanes)
+            sess._lanes = yc.stream_lanes
         if getattr(sess, "_token", False) != self.fused_transform_token:
             sess.set_transform_token(self.fused_transform_token)
             sess._token = self.fused_transform_token

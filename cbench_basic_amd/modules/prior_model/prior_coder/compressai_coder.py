@@ -235,20 +235,22 @@ class CompressAIItemFraming:
     bodies its images get when they are coded one per call.  ``ctx`` (what the graph knows about the node) is not needed."""
 
     can_split_items = True
+    stream_lanes = 1   # streams per item (the GaussianConditional coder's lane streams set it)
 
     def split_items(self, body, n, **ctx):
-        parts = _items.split_compressai_body(body)
+        S = self.stream_lanes
+        parts = _items.split_compressai_body(body, S)
         if len(parts) != int(n):
-            raise ValueError(f"body of {len(parts)} streams, {n} items expected")
+            raise ValueError(f"body of {len(parts) * S} streams, {n} items" + (f" of {S} streams" if S > 1 else "") + " expected")
         return parts
 
     def merge_items(self, bodies, **ctx):
-        return _items.merge_compressai_bodies(bodies)
+        return _items.merge_compressai_bodies(bodies, self.stream_lanes)
 
     def item_shape(self, body, **ctx):
         h, w, n = _items.compressai_body_shape(body)
-        if n != 1:
-            raise ValueError(f"an item body holds one stream, not {n}")
+        if n != self.stream_lanes:
+            raise ValueError(f"an item body holds {'one stream' if self.stream_lanes == 1 else '%d streams' % self.stream_lanes}, not {n}")
         return (h, w)
 
 
@@ -415,11 +417,24 @@ class GaussianConditional(nn.Module):
                 self._offset.cpu().numpy().astype(np.int32).reshape(-1))
 
 
-class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
-    """compressai_coder.py:341-397: zero-mean Gaussian with hyperprior scales."""
+def check_gc_stream_lanes(lanes) -> int:
+    """Validates ``stream_lanes`` of a coder whose whole image is one coding step: an integer in [1, 256] (1 = the reference's
+    format).  That the lanes divide a call's C * H * W symbols is checked per call."""
+    if isinstance(lanes, bool) or not isinstance(lanes, (int, np.integer)) or not 1 <= lanes <= 256:
+        raise ValueError(f"stream_lanes must be an integer in [1, 256], not {lanes!r}")
+    return int(lanes)
 
-    def __init__(self, use_bit_rate_loss=True, training_output_straight_through=False, scale_bound=0.11, **kwargs):
+
+class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
+    """compressai_coder.py:341-397: zero-mean Gaussian with hyperprior scales.
+
+    ``stream_lanes = K > 1`` (INTEGRATION.md "Lane streams"; NOT a format the reference reads): an image's C * H * W symbols, in
+    (c, h, w) order, are cut into K equal contiguous runs, each its own rANS stream -- stream b * K + k of a body of B * K streams
+    -- so that K wavefronts code one image.  Coder configuration like the tables: not written into the stream."""
+
+    def __init__(self, use_bit_rate_loss=True, training_output_straight_through=False, scale_bound=0.11, stream_lanes=1, **kwargs):
         super().__init__()
+        self.stream_lanes = check_gc_stream_lanes(stream_lanes)
         self.gaussian_conditional = GaussianConditional(scale_bound=scale_bound)
         self.scale_bound = float(scale_bound)
         self._tables = None
@@ -447,6 +462,12 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
     def _crop(prior, h, w):
         return prior[..., :h, :w].contiguous()
 
+    def _lane_length(self, n):
+        """Symbols per stream of an image of n symbols; ValueError when the lanes do not divide it."""
+        if n % self.stream_lanes:
+            raise ValueError(f"stream_lanes={self.stream_lanes} does not divide the {n} symbols (C * H * W) of an image")
+        return n // self.stream_lanes
+
     def forward(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, **kwargs):
         self._ready()
         if channel_gains is not None:
@@ -470,16 +491,21 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
             y = y * channel_gains.reshape(1, -1, 1, 1)
         sym, idx, _ = K.gc_quantize_index(y, self._crop(prior, *y.shape[-2:]), self._scale_table_dev, self.scale_bound,
                                           want_yhat=False)
-        body = PendingBody(self._tables, self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), sym[0].numel()), y.shape[-2:])
+        # lane k of image b is a contiguous run of the [B][C * H * W] arrays: B * K equal segments, nothing moves
+        per = self._lane_length(y[0].numel())
+        body = PendingBody(self._tables, self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), per), y.shape[-2:])
         return body if lazy else body.result()
 
     def decode(self, byte_string, *args, prior=None, channel_gains=None, channel_gains_inv=None, **kwargs):  # :387-393
         self._ready()
-        h, w, _ = K.frame_header(byte_string)
+        h, w, ns = K.frame_header(byte_string)
         shape = (h, w)
         scales = self._crop(prior, *shape)
+        per = self._lane_length(scales[0].numel())
+        if self.stream_lanes > 1 and ns != scales.shape[0] * self.stream_lanes:
+            raise ValueError(f"stream body holds {ns} streams, this coder's configuration needs {scales.shape[0] * self.stream_lanes}")
         _, idx, _ = K.gc_quantize_index(scales, scales, self._scale_table_dev, self.scale_bound, want_yhat=False)
-        sym = self._tables.decode_batch_from_frame(byte_string, idx.reshape(-1), idx[0].numel())
+        sym = self._tables.decode_batch_from_frame(byte_string, idx.reshape(-1), per)
         yhat = K.i32_to_f32(sym.reshape(idx.shape))
         if channel_gains_inv is not None:
             yhat = yhat * channel_gains_inv.reshape(1, -1, 1, 1)

@@ -182,6 +182,8 @@ class _GroupPlan:
             self.groups.append(dict(elems=torch.from_numpy(elems).to(device), n=int(elems.size), base=base, pos_np=pos))
             base += int(elems.size)
         self.per_image = base
+        # first element of every group and the image's length: the table the lane pack (basic_group_lanes_pack_dev) is driven by
+        self.bases_dev = torch.tensor([grp["base"] for grp in self.groups] + [base], dtype=torch.int64).to(device)
         self._pos_cache = {}
         # plane layout of the merger's PRIVATE hidden activations: positions ordered by the first step that codes them, so
         # the positions of a step are contiguous (whole cache lines per gather / store; row-major planes give a checkerboard
@@ -203,18 +205,27 @@ class _GroupPlan:
 
 
 def check_stream_lanes(lanes, in_channels, channel_groups, method, batch_stream_mode) -> int:
-    """Validates a coder's ``stream_lanes``; 1 is the reference's format and always allowed.  Lanes need a position-major coding
-    order with one channel group (the scan-line schedule), lanes of a multiple of 16 channels (the batched exchange layout is linear
-    in a lane's first channel only at multiples of 4; 16 keeps a lane's stores whole) and the per-image framing."""
-    if isinstance(lanes, bool) or not isinstance(lanes, (int, np.integer)) or lanes < 1:
-        raise ValueError(f"stream_lanes must be an integer >= 1, not {lanes!r}")
+    """Validates a coder's ``stream_lanes``: an integer in [1, 256]; 1 is the reference's format and always allowed.  Lane k of a
+    coding step is the k-th of K equal contiguous parts of the step's element list, so every method can have lanes; all need the
+    per-image framing.  The scan-line schedule (whose persistent kernels decode the lanes) needs one channel group and lanes of a
+    multiple of 16 channels (the batched exchange layout is linear in a lane's first channel only at multiples of 4; 16 keeps a
+    lane's stores whole).  For the other methods K is a power of two -- their steps are 16-channel groups and halves or quarters of
+    the positions, lengths that a factor of 3 divides only by accident of the latent's shape; a configuration with 3 lanes and a
+    method other than the scan-line one stays refused, as before -- and, the step lengths depending on the latent's shape, that
+    every step divides into the lanes is checked per call."""
+    if isinstance(lanes, bool) or not isinstance(lanes, (int, np.integer)) or not 1 <= lanes <= 256:
+        raise ValueError(f"stream_lanes must be an integer in [1, 256], not {lanes!r}")
     lanes = int(lanes)
     if lanes == 1:
         return 1
-    if method != "scanline" or channel_groups != 1:
-        raise ValueError("stream_lanes > 1 needs default_topo_group_method='scanline' and channel_groups=1")
-    if in_channels % lanes or (in_channels // lanes) % 16:
-        raise ValueError(f"stream_lanes={lanes} must cut {in_channels} channels into lanes of a multiple of 16")
+    if method == "scanline":
+        if channel_groups != 1:
+            raise ValueError("stream_lanes > 1 with default_topo_group_method='scanline' needs channel_groups=1")
+        if in_channels % lanes or (in_channels // lanes) % 16:
+            raise ValueError(f"stream_lanes={lanes} must cut {in_channels} channels into lanes of a multiple of 16")
+    elif lanes & (lanes - 1):
+        raise ValueError(f"stream_lanes={lanes}: with default_topo_group_method={method!r} the lane count must be a power of two "
+                         "(other counts need default_topo_group_method='scanline' and channel_groups=1)")
     if batch_stream_mode == "reference":
         raise ValueError("stream_lanes > 1 writes one stream per image and lane: batch_stream_mode='reference' cannot hold it")
     return lanes
@@ -681,9 +692,19 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
 
     def _check_lanes_call(self, pgm):
         if self.stream_lanes > 1 and pgm is not None:
-            raise ValueError("stream_lanes > 1 codes the default scan-line order only: a call may not bring its own pgm")
+            raise ValueError("stream_lanes > 1 codes the coder's default order only: a call may not bring its own pgm")
         if self.stream_rows and pgm is not None:
             raise ValueError("stream_rows=True codes the default scan-line order only: a call may not bring its own pgm")
+
+    def _check_lanes_steps(self, h, w):
+        """Lane k of a coding step is the k-th of stream_lanes EQUAL parts of it: every non-empty step of the h x w latent must
+        divide (the step lengths follow from the method and the shape, so this is a property of the call)."""
+        Kl = self.stream_lanes
+        if Kl > 1:
+            bad = [(g, grp["n"]) for g, grp in enumerate(self._plan(h, w).groups) if grp["n"] % Kl]
+            if bad:
+                raise ValueError(f"stream_lanes={Kl}: a coding step does not divide into the lanes (step {bad[0][0]} of the "
+                                 f"{h} x {w} latent has {bad[0][1]} elements)")
 
     def _scanline_plan(self, plan, prior, batch=1, decode=False, width=None, height=None):
         """The ScanlinePlan serving this call, or None (then the per-step path codes the same integers): the configuration
@@ -855,6 +876,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
 
     def _encode_impl(self, input, *args, prior=None, pgm=None, quantizer_params=None, **kwargs) -> bytes:
         self._check_lanes_call(pgm)
+        self._check_lanes_steps(input.shape[2], input.shape[3])
         self._ready()
         input = input.contiguous()
         prior = self._check_prior(input.shape, prior)
@@ -866,9 +888,14 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
             # lane streams: [B][P][K][L] -> [B][K][P][L], then B * K contiguous streams of P * L symbols on the batched encoder.
             # Row streams: the coding order is raster, so an image's rows are contiguous -- the same pack with batch := B * H and
             # positions := W gives the B * H * K streams (row, lane); with one lane nothing moves at all.
+            # Every other method: lane k takes the k-th of K equal parts of every group (the same picture when the groups are
+            # spatial and K divides the channels); the pack is driven by the plan's group bases.
             Kl, C = self.stream_lanes, self.in_channels
             R = input.shape[2] if self.stream_rows else 1   # streams per image and lane
-            ps, pi = K.lanes_pack(sym, idx, B * R, n // C // R, C, Kl) if Kl > 1 else (sym, idx)
+            if Kl > 1 and self.default_topo_group_method != "scanline":
+                ps, pi = K.group_lanes_pack(sym.reshape(B, n), idx.reshape(B, n), plan.bases_dev, Kl)
+            else:
+                ps, pi = K.lanes_pack(sym, idx, B * R, n // C // R, C, Kl) if Kl > 1 else (sym, idx)
             host, off = self._tables.encode_batch_end(self._tables.encode_batch_begin(ps.reshape(-1), pi.reshape(-1), n // Kl // R))
             lens = (np.diff(off) * 4).astype("<u4")
             body = b"".join([struct.pack("<I", B * R * Kl), lens.tobytes(), memoryview(host[: int(off[-1])])])
@@ -902,7 +929,6 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
 
     def _decode_impl(self, byte_string: bytes, *args, prior=None, pgm=None, quantizer_params=None, **kwargs):
         self._check_lanes_call(pgm)
-        self._ready()
         ptr = 0
         if self.fixed_input_shape is not None:
             B, spatial = self.fixed_input_shape[0], tuple(self.fixed_input_shape[1:])
@@ -916,6 +942,8 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         H, W = spatial
         prior = self._check_prior((B, self.in_channels, H, W), prior)
         body = byte_string[ptr:]
+        self._check_lanes_steps(H, W)
+        self._ready()
         plan = self._plans_for(H, W, pgm, B)
         if isinstance(plan, list):
             return self._decode_per_sample(body, prior, B, H, W, plan)

@@ -373,6 +373,23 @@ def lanes_pack(sym, idx, batch, positions, channels, lanes):
     return so, io
 
 
+def group_lanes_pack(sym, idx, bases, lanes):
+    """Lane streams of the group coders: both int32 arrays from group-major coding order [B][n] to [B * K][n / K], row b * K + k =
+    the concatenation over the groups of the k-th of K equal parts of each group of image b (basic_group_lanes_pack_dev).
+    ``bases``: int64 [G + 1] device tensor, the groups' first elements and n; every group a multiple of K long (the caller checks)."""
+    sym, idx, bases = _dev(sym, torch.int32), _dev(idx, torch.int32), _dev(bases, torch.int64)
+    if sym.dim() != 2 or idx.shape != sym.shape or bases.numel() < 2:
+        raise ValueError("group_lanes_pack: arrays must be [B, n] and bases [G + 1]")
+    B, n = sym.shape
+    if n % lanes:
+        raise ValueError(f"group_lanes_pack: {lanes} lanes do not divide {n} symbols")
+    so = torch.empty((B * lanes, n // lanes), device=sym.device, dtype=torch.int32)
+    io = torch.empty_like(so)
+    _lib.check(_lib.lib().basic_group_lanes_pack_dev(sym.data_ptr(), idx.data_ptr(), int(B), int(n), bases.data_ptr(), int(bases.numel() - 1),
+                                                     int(lanes), so.data_ptr(), io.data_ptr(), _stream()))
+    return so, io
+
+
 def eb_quantize_index(z, medians):
     z, medians = _dev(z, torch.float32), _dev(medians, torch.float32)
     B, C = z.shape[0], z.shape[1]
@@ -537,6 +554,10 @@ class HyperpriorSession:
 
     def set_rans_waves(self, waves_per_block):
         _lib.check(_lib.lib().basic_hp_session_set_rans_waves(self._h, int(waves_per_block)))
+
+    def set_stream_lanes(self, lanes):
+        """y streams per image (basic_hp_session_set_stream_lanes): 1 is the reference's format."""
+        _lib.check(_lib.lib().basic_hp_session_set_stream_lanes(self._h, int(lanes)))
 
     def set_transform_token(self, enable):
         """False / 0: no ordering; True / 1: the transform phases of all sessions one at a time; 2: two at a time."""

@@ -13,13 +13,15 @@ from .nn.models.google import (HyperpriorAnalysisModel, HyperpriorHyperAnalysisM
                                HyperpriorHyperSynthesisModel, HyperpriorSynthesisModel)
 
 
-def hyperprior_codec(N=128, M=192):
+def hyperprior_codec(N=128, M=192, stream_lanes=1):
+    """``stream_lanes`` = K > 1: the y coder writes K lane streams per image ("Lane streams": a format of this
+    library, not one the reference reads); the z body keeps the reference's format."""
     ec = LatentGraphicalANSEntropyCoder(
         latent_node_inference_topo_order=["x", "y", "z"],
         latent_node_generative_topo_order=["z", "y", "x"],
         latent_node_entropy_coder_dict=dict(
             x=LossyDummyEntropyCoder(lambda_rd=145.2225),
-            y=CompressAIGaussianConditionalCoder(),
+            y=CompressAIGaussianConditionalCoder(stream_lanes=stream_lanes),
             z=CompressAIEntropyBottleneckPriorCoder(entropy_bottleneck_channels=N, use_inner_aux_opt=True),
         ),
         latent_inference_dict=dict(x_y=HyperpriorAnalysisModel(N=N, M=M), y_z=HyperpriorHyperAnalysisModel(N=N, M=M)),
@@ -28,10 +30,12 @@ def hyperprior_codec(N=128, M=192):
     return GeneralCodec(entropy_coder=ec)
 
 
-def topogroup_ar_codec(method="checkerboard", N=128, M=192, channel_groups=1, expand_bottleneck=True, use_param_merger=True):
+def topogroup_ar_codec(method="checkerboard", N=128, M=192, channel_groups=1, expand_bottleneck=True, use_param_merger=True,
+                       stream_lanes=1):
     """configs/lossy_latent_graph_topogroup.py:203-244 ("hyperprior-ar-base" and its topo-group variants
     :253-781): hyperprior transforms, h_s = HyperpriorHyperSynthesisModel(N, 2M) giving (mean, scale)
-    interleaved, y coded by the topo-group AR Gaussian coder with the in-coder masked param merger."""
+    interleaved, y coded by the topo-group AR Gaussian coder with the in-coder masked param merger.  ``stream_lanes`` = K > 1:
+    K lane streams per image, every coding step cut into K equal parts ("Lane streams")."""
     from .modules.prior_model.prior_coder.pgm_coder import GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder
     hs = HyperpriorHyperSynthesisModel(N=N, M=2 * M)
     ec = LatentGraphicalANSEntropyCoder(
@@ -41,7 +45,8 @@ def topogroup_ar_codec(method="checkerboard", N=128, M=192, channel_groups=1, ex
             x=LossyDummyEntropyCoder(lambda_rd=145.2225),
             y=GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(in_channels=M, channel_groups=channel_groups,
                                                                    default_topo_group_method=method, use_param_merger=use_param_merger,
-                                                                   param_merger_expand_bottleneck=expand_bottleneck),
+                                                                   param_merger_expand_bottleneck=expand_bottleneck,
+                                                                   stream_lanes=stream_lanes),
             z=CompressAIEntropyBottleneckPriorCoder(entropy_bottleneck_channels=N, use_inner_aux_opt=True),
         ),
         latent_inference_dict=dict(x_y=HyperpriorAnalysisModel(N=N, M=M), y_z=HyperpriorHyperAnalysisModel(N=N, M=M)),

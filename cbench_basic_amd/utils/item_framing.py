@@ -6,6 +6,7 @@ items can be coded in ONE call and still yield exactly the N strings N calls wou
 functions over ``bytes``: no device, no tables.
 
   CompressAI-style bodies (compressai_coder.py ``write_body`` / ``read_body``):  ">III" (h, w, n), then per stream ">I" length + payload.
+      n = S * B with S streams per item (1, or the y coder's stream_lanes); an item body is the same form with n = S.
   PGM bodies (pgm_coder.py ``_encode_impl``):  the optional shape head  B(len) <H batch> <H dims...>,  then
       batched form:  <I S*B> <S*B x I length> streams       (S streams per item: 1, stream_lanes, or H * stream_lanes with rows)
       item form:     the bare rANS stream (S = 1, ``batch_stream_mode="auto"``)  or  <I S> <S x I length> streams  (``item_tabled``)
@@ -72,27 +73,38 @@ def _write_compressai(h, w, streams):
     return b"".join(parts)
 
 
-def split_compressai_body(body) -> List[bytes]:
-    """The n batch-1 bodies of a body of n streams."""
+def _check_streams_per_item(S):
+    if isinstance(S, bool) or not isinstance(S, int) or S < 1:
+        raise ValueError(f"streams per item must be an integer >= 1, not {S!r}")
+    return S
+
+
+def split_compressai_body(body, streams_per_item=1) -> List[bytes]:
+    """The batch-1 bodies of a body of n streams, ``streams_per_item`` consecutive streams each (lane streams: stream b * S + k is
+    lane k of item b)."""
+    S = _check_streams_per_item(streams_per_item)
     h, w, streams = _parse_compressai(body)
-    return [_write_compressai(h, w, [s]) for s in streams]
+    if len(streams) % S:
+        raise ValueError(f"{len(streams)} streams do not divide into items of {S}")
+    return [_write_compressai(h, w, streams[i:i + S]) for i in range(0, len(streams), S)]
 
 
-def merge_compressai_bodies(bodies) -> bytes:
+def merge_compressai_bodies(bodies, streams_per_item=1) -> bytes:
     """Inverse of split_compressai_body: batch-1 bodies of one (h, w) -> the body of the batch."""
+    S = _check_streams_per_item(streams_per_item)
     bodies = list(bodies)
     if not bodies:
         raise ValueError("no bodies to merge")
     shape, streams = None, []
     for b in bodies:
         h, w, s = _parse_compressai(b)
-        if len(s) != 1:
-            raise ValueError(f"an item body holds one stream, not {len(s)}")
+        if len(s) != S:
+            raise ValueError(f"an item body holds {'one stream' if S == 1 else '%d streams' % S}, not {len(s)}")
         if shape is None:
             shape = (h, w)
         elif shape != (h, w):
             raise ValueError(f"bodies of different shapes: {shape} and {(h, w)}")
-        streams.append(s[0])
+        streams.extend(s)
     return _write_compressai(shape[0], shape[1], streams)
 
 

@@ -188,6 +188,13 @@ int basic_gc_quantize_index_dev(const float *d_y, const float *d_scales, int64_t
  * basic_rans_encode_batch_dev codes B * lanes contiguous streams of positions * L symbols.  Out of place; lanes == 1 copies. */
 int basic_lanes_pack_dev(const int32_t *d_sym, const int32_t *d_idx, int batch, int positions, int channels, int lanes,
                          int32_t *d_sym_out, int32_t *d_idx_out, void *hip_stream);
+/* Lane streams of the group coders (GaussianConditional: groups == 1; topo-group coders: the plan's groups): repacks d_sym /
+ * d_idx, int32 [B][n] in group-major coding order, to [B][lanes][n / lanes], where stream (b, k) is the concatenation over the
+ * groups g of the k-th of `lanes` equal contiguous parts of group g.  d_bases: int64 [groups + 1] on the device, the first
+ * element of every group and n at the end; every group must be a multiple of `lanes` long (groups may be empty, and of unequal
+ * lengths).  Out of place; lanes == 1 copies.  lanes in [1, 256] and n % lanes == 0, else BASIC_ERR_INVALID. */
+int basic_group_lanes_pack_dev(const int32_t *d_sym, const int32_t *d_idx, int batch, int64_t n, const int64_t *d_bases, int groups,
+                               int lanes, int32_t *d_sym_out, int32_t *d_idx_out, void *hip_stream);
 /* EntropyBottleneck path (compressai_coder.py:230-245): sym = round(z - median[c]),
  * idx = c, zhat = sym + median[c].  Layout [B][C][HW]. */
 int basic_eb_quantize_index_dev(const float *d_z, const float *d_medians, int batch, int channels, int hw,
@@ -391,6 +398,12 @@ int basic_hp_decoded_shape(const basic_hp_session *s, const uint8_t *data, int64
  * hip_stream; the call returns once the stream words have left `data` (no final synchronisation). */
 int basic_hp_decode_images(basic_hp_session *s, const uint8_t *data, int64_t len, float *d_xhat,
                            int64_t xhat_capacity_floats, void *hip_stream);
+/* Lane streams of the y latent (INTEGRATION.md "Lane streams"): the y path codes batch * lanes rANS streams of ny / lanes
+ * symbols -- stream b * lanes + k holds symbols [k ny / lanes, (k + 1) ny / lanes) of image b in (c, h, w) order -- and the y
+ * body holds batch * lanes streams; the z body is untouched.  lanes in [1, 256]; 1 (the default) is the reference's format.
+ * A call whose ny is no multiple of lanes, or a stream whose y body does not hold lanes streams per z stream, fails with
+ * BASIC_ERR_INVALID.  Configuration of the session like its tables: not written into the stream. */
+int basic_hp_session_set_stream_lanes(basic_hp_session *s, int lanes);
 /* Wavefronts (image streams) per workgroup of this session's rANS launches: 1, 2, 4, 8 or 16 (0 = library default). */
 int basic_hp_session_set_rans_waves(basic_hp_session *s, int waves_per_block);
 /* Opt this session into the process-wide "transform token": the MFMA-heavy phases (compress: everything up to the y

@@ -46,7 +46,7 @@ def main():
                     help="testing_coalesce_items: code the batch-1 items of the dataset in calls of up to this many items of one shape; "
                          "every item keeps the bytes of its own batch-1 call (needs --batch-size 1)")
     ap.add_argument("--stream-lanes", type=int, default=1,
-                    help="--codec basic: lane streams per image of the scan-line y-coder (a format the reference does not read)")
+                    help="lane streams per image of the y-coder, any codec (a format the reference does not read)")
     ap.add_argument("--stream-rows", action="store_true",
                     help="--codec basic: one stream per latent row of the scan-line y-coder (a format the reference does not read)")
     ap.add_argument("--metrics", nargs="+", choices=["psnr", "ms-ssim"], default=["psnr"],
@@ -55,8 +55,8 @@ def main():
     args = ap.parse_args()
     if args.stream_rows and args.codec != "basic":
         ap.error("--stream-rows needs --codec basic")
-    if args.stream_lanes != 1 and args.codec != "basic":
-        ap.error("--stream-lanes needs --codec basic")
+    if not 1 <= args.stream_lanes <= 256:
+        ap.error("--stream-lanes must be in [1, 256]")
     if args.coalesce and args.batch_size != 1:
         ap.error("--coalesce codes batch-1 items: it does not combine with --batch-size other than 1")
     if args.coalesce < 0:
@@ -75,8 +75,8 @@ def main():
     else:
         ds = RandomImageDataset(num=args.synthetic or 8, size=(3, args.height or args.size, args.width or args.size))
     batches = list(batched(ds, args.batch_size))
-    builders = dict(hyperprior=presets.hyperprior_codec, basic=lambda **kw: presets.basic_codec(stream_lanes=args.stream_lanes, stream_rows=args.stream_rows, **kw),
-                    topogroup=lambda: presets.topogroup_ar_codec(method=args.method))
+    builders = dict(hyperprior=lambda: presets.hyperprior_codec(stream_lanes=args.stream_lanes), basic=lambda **kw: presets.basic_codec(stream_lanes=args.stream_lanes, stream_rows=args.stream_rows, **kw),
+                    topogroup=lambda: presets.topogroup_ar_codec(method=args.method, stream_lanes=args.stream_lanes))
     codec = builders["basic"](search_dataset=batches) if (args.codec == "basic" and args.complexity_search) else builders[args.codec]()
     if args.checkpoint:
         sd = torch.load(args.checkpoint, map_location="cpu")
