@@ -103,8 +103,10 @@ _SIGNATURES = {
     "basic_scanline_batched_max": (_I, [_P, _I, _I, _P]),
     "basic_scanline_wavefront_max": (_I, [_P, _I, _I, _P]),
     "basic_scanline_band_max": (_I, [_P, _I, _I, _P]),
+    "basic_scanline_band_decode_max": (_I, [_P, _P, _I, _I, _I, _P]),
     "basic_scanline_last_kernel": (_I, [_P, _P]),
     "basic_scanline_set_encode_schedule": (_I, [_P, _I]),
+    "basic_scanline_set_decode_schedule": (_I, [_P, _I]),
     "basic_scanline_choose": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "basic_scanline_choose_lanes": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "basic_scanline_choose_rows": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Build-time audit of scanline_batched_kernel (csrc/scanline.hip): its 256 resident weight registers are accumulator registers
 named literally in inline asm, which is only sound while the COMPILER itself never touches the accumulator file in that kernel
-(cdna_hip_programming.md 5.7 item 4).  Fails unless, for all five instantiations (encode, decode, wavefront encode, wavefront decode, band encode): no VGPR spill, no scratch, every v_accvgpr_* and
+(cdna_hip_programming.md 5.7 item 4).  Fails unless, for all six instantiations (encode, decode, wavefront encode, wavefront decode, band encode, band decode): no VGPR spill, no scratch, every v_accvgpr_* and
 every v_mfma_* sits inside an ;;#ASMSTART / ;;#ASMEND pair, and the kernel descriptor allocates all 256 accumulator registers."""
 import re
 import subprocess
@@ -12,8 +12,8 @@ asm = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", f"--offload-arch={arc
                      check=True, capture_output=True, text=True).stdout
 bad = []
 kernels = re.findall(r"^(_ZN\S*scanline_batched_kernel\S*):", asm, flags=re.M)
-if len(kernels) != 5:
-    bad.append(f"expected five scanline_batched_kernel instantiations, found {len(kernels)}")
+if len(kernels) != 6:
+    bad.append(f"expected six scanline_batched_kernel instantiations, found {len(kernels)}")
 for name in kernels:
     body = asm[asm.index("\n" + name + ":"):]
     body = body[:body.index("s_endpgm")]

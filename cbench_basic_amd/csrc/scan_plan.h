@@ -155,8 +155,8 @@ static_assert(sizeof(kScanKernelNames) / sizeof(ScanKernelName) == static_cast<i
                   scan_kernel_id(ScanKernel::kBatched) == BASIC_SCAN_KERNEL_BATCHED && scan_kernel_id(ScanKernel::kPipelined) == BASIC_SCAN_KERNEL_PIPELINED &&
                   scan_kernel_id(ScanKernel::kGeneric) == BASIC_SCAN_KERNEL_GENERIC,
               "kScanKernelNames: one row per ScanKernel, in its order, with the id include/basic_hip.h gives it");
-// whether the kernel has a decode form: the band schedule is encode only
-constexpr bool scan_kernel_decodes(ScanKernel k) { return k != ScanKernel::kBand; }
+// whether the kernel serves a decode call: the raster kernels always, the wavefront and the band only a call that brings row streams
+constexpr bool scan_kernel_decodes(ScanKernel k, bool rows) { return rows || (k != ScanKernel::kBand && k != ScanKernel::kWavefront); }
 
 constexpr size_t kMaxLds = 160 * 1024;
 // more than half of a compute unit's LDS per workgroup: exactly one workgroup per unit, as the barrier protocol assumes
@@ -394,6 +394,34 @@ inline int band_images_per_launch(const ScanGeometry *p, int h, int w, int cus)
     return 0;
 }
 
+// ---- band decode launch (row streams only): the band's compute workgroups, plus one decoder wavefront per (image, slot, lane
+// stream) -- a slot's wavefront decodes the slot's rows one after the other, so an image brings min(band_slots, h) * lanes of them
+// whatever its height --, four to a workgroup, resident beside the compute workgroups.  The images of one launch: the largest
+// n <= band_images_per_launch whose tiles' workgroups and decoder workgroups together fit the chip; 0 = never.  (The decoder's
+// search image must fit the LDS as for every decode launch: plan_scan checks it, the launch's LDS is the larger of the two.)
+// Measured (scripts/scanline_probe.py --rows --decode-schedule band, profiles/band_decode_probe.txt; C = 192, 256 compute units,
+// launch time / steps, run-to-run spread under 0.7 %): the step is the decoder wave's, not the band encode step's 18-26 us -- 64.4 us
+// (one image of 32x48, one tile) to 67.4 (8 images, four tiles) and 68.1 - 70.8 (launches of six tiles) with one lane stream,
+// 35.3 / 38.1 / 38.5 - 39.6 with three; the wavefront decode launch 64.8 - 65.3 / 35.6 - 36.2 where it fits.  The raster decode
+// launches of the same row-stream calls: 51.2 / 25.2 us per step pipelined (one image; 56.8 / 30.6 two), 60.8 - 65.6 / 34.3 - 37.5
+// batched.  So a call wins by its step count: 1 / 2 / 3 / 8 x 32x48 (172 steps against 1,536) x7.1 / x7.7 / x8.2 / x8.3 at one lane
+// and x6.4 / x7.5 / x8.3 / x8.2 at three, 16 x 32x48 (two launches) x4.1, 64 x 16x16 (76 steps against 256, two / three launches)
+// x1.56 / x1.06; no measured shape lost.  No auto rule is installed from these yet (a later change decides it and re-records the
+// dispatch table): only the decode schedule or BASIC_SCAN_KERNEL=band sends a call here.
+inline int band_decode_slots(const ScanGeometry *p, int h, int w) { return std::min(band_slots(p, w), h); }
+
+inline int band_decode_images_per_launch(const ScanGeometry *p, int h, int w, int lanes, int cus)
+{
+    if (lanes < 1) return 0;
+    const int most = band_images_per_launch(p, h, w, cus);
+    if (most < 1) return 0;
+    const int ipt = 32 / band_slots(p, w);
+    const int64_t waves = static_cast<int64_t>(band_decode_slots(p, h, w)) * lanes;   // decoder wavefronts per image
+    for (int n = most; n >= 1; --n)
+        if (static_cast<int64_t>((n + ipt - 1) / ipt) * p->b_nw + (n * waves + kThreads / 64 - 1) / (kThreads / 64) <= cus) return n;
+    return 0;
+}
+
 // The encode calls that take the band when nothing forces a choice and the wavefront does not fit.  Measured
 // (profiles/scanline_band_probe.txt): a band step costs 17.9-18.4 us with one tile in the launch, 19.1-19.8
 // with two, 20.1-21.0 with four, 23.2-25.7 with eight (more granules in flight through the same memory side); a raster step
@@ -445,7 +473,8 @@ struct ScanRequest {
     bool fast_image = false;         // decode: the table set has a fast search image ...
     size_t decoder_lds = 0;          // ... of this many LDS bytes per decoder workgroup
     int cus = 0;                     // compute units of the device
-    int schedule = BASIC_SCAN_SCHEDULE_AUTO;     // the requested encode schedule
+    int schedule = BASIC_SCAN_SCHEDULE_AUTO;     // the requested encode schedule (decode calls ignore it)
+    int decode_schedule = BASIC_SCAN_SCHEDULE_AUTO;   // the requested decode schedule: looked at only when the call brings row streams (rows)
     ScanKernel force = ScanKernel::kNone;        // BASIC_SCAN_KERNEL, parsed: wins over the schedule
     // the coder's gates (pgm_coder: persistent_scanline_max_batch): batches up to this one may take the lane kernels, and a call
     // that no persistent kernel should serve is left to the per-step path.  < 0: a library call, which is served or refused.
@@ -478,6 +507,10 @@ inline int compute_workgroups(const ScanGeometry *p, ScanKernel k, int images, i
 // streams, as without rows), then the per-step path.  With rows off every request is planned as before the format existed.
 // And a third, the band (BASIC_SCAN_KERNEL=band, BASIC_SCAN_SCHEDULE_BAND): any batch and height, in as many launches as the
 // batch needs.  In auto it is looked at only where the wavefront does not fit, and taken where band_auto says so.
+// Row-stream decode calls have a schedule of their own (ScanRequest::decode_schedule): auto is the above; raster keeps the call off the
+// wavefront and the band whatever a later auto rule says; wavefront and band force that launch, as BASIC_SCAN_KERNEL=wavefront / band
+// do (the environment wins).  The band decode launch (band_decode_images_per_launch) serves any batch and height, in as many
+// launches as the batch needs, each with the decoder workgroups of its own images.  No auto rule sends a call to it.
 // A forced kernel or schedule that the call does not fit is refused (BASIC_ERR_INVALID, "does not fit").
 inline int plan_scan(const ScanGeometry *p, const ScanRequest &q, ScanLaunch *L)
 {
@@ -488,12 +521,19 @@ inline int plan_scan(const ScanGeometry *p, const ScanRequest &q, ScanLaunch *L)
     const int ndec = decode ? decoder_workgroups(batch * q.lanes) : 0;
     int schedule = q.schedule;
     ScanKernel force = q.force;
-    // encode only: a decode call ignores it (the wavefront: unless it brings row streams)
-    if (decode && force != ScanKernel::kNone && (!scan_kernel_decodes(force) || (force == ScanKernel::kWavefront && !q.rows))) force = ScanKernel::kNone;
+    // encode only: a decode call ignores it (the wavefront and the band: unless it brings row streams)
+    if (decode && force != ScanKernel::kNone && !scan_kernel_decodes(force, q.rows)) force = ScanKernel::kNone;
+    // a row-stream decode call: its own schedule, where the environment names no kernel
+    const int dsched = decode && q.rows ? q.decode_schedule : BASIC_SCAN_SCHEDULE_AUTO;
+    if (force == ScanKernel::kNone && dsched == BASIC_SCAN_SCHEDULE_WAVEFRONT) force = ScanKernel::kWavefront;
+    if (force == ScanKernel::kNone && dsched == BASIC_SCAN_SCHEDULE_BAND) force = ScanKernel::kBand;
     const bool wf_fits = decode ? q.rows && h >= 1 && w >= 1 && wavefront_decode_fits(p, batch, h, q.lanes, cus) && q.decoder_lds <= kMaxLds
                                 : wavefront_fits(p, batch, h, cus);
     // a row-stream decode call that goes to the wavefront launch: forced, or in auto where it fits and its rule says so
-    const bool wf_decode = decode && wf_fits && (force == ScanKernel::kWavefront || (force == ScanKernel::kNone && wavefront_decode_auto(p, batch, h, w, q.lanes)));
+    const bool wf_decode = decode && wf_fits && (force == ScanKernel::kWavefront || (force == ScanKernel::kNone && dsched == BASIC_SCAN_SCHEDULE_AUTO && wavefront_decode_auto(p, batch, h, w, q.lanes)));
+    // a row-stream decode call whose band launch was asked for: the images of one launch (0: it does not fit)
+    const bool band_decode = decode && force == ScanKernel::kBand;
+    const int band_dec_n = band_decode && h >= 1 && w >= 1 && q.decoder_lds <= kMaxLds ? band_decode_images_per_launch(p, h, w, q.lanes, cus) : 0;
     int band_n = -1;   // band_images_per_launch, when somebody asks
     auto band_images = [&] { return band_n >= 0 ? band_n : (band_n = band_images_per_launch(p, h, w, cus)); };
     if (q.lane_max_batch >= 0) {
@@ -505,23 +545,24 @@ inline int plan_scan(const ScanGeometry *p, const ScanRequest &q, ScanLaunch *L)
             // auto, as a band where that beats the per-step path.  (kept as it is: a forced wavefront that does not fit is not
             // refused here but left to the per-step path)
             if (decode) {
-                if (!wf_decode) return BASIC_OK;   // (row streams: the wavefront decode launch serves the call, chosen below)
+                if (!wf_decode && band_dec_n < 1) return BASIC_OK;   // (row streams: the wavefront or band decode launch serves the call, chosen below)
             } else if (schedule == BASIC_SCAN_SCHEDULE_RASTER) return BASIC_OK;
             else if (wf_fits) schedule = BASIC_SCAN_SCHEDULE_WAVEFRONT;
             else if (schedule == BASIC_SCAN_SCHEDULE_AUTO && band_beats_per_step(p, batch, h, w, band_images())) schedule = BASIC_SCAN_SCHEDULE_BAND;
             else return BASIC_OK;
         }
-        if (!wf_decode && (!lane_grid_resident(p, ndec, cus) || (decode && q.decoder_lds > kMaxLds))) return BASIC_OK;
+        if (!wf_decode && band_dec_n < 1 && (!lane_grid_resident(p, ndec, cus) || (decode && q.decoder_lds > kMaxLds))) return BASIC_OK;
     }
     if (force == ScanKernel::kNone && !decode && schedule == BASIC_SCAN_SCHEDULE_WAVEFRONT) force = ScanKernel::kWavefront;
     if (force == ScanKernel::kNone && !decode && schedule == BASIC_SCAN_SCHEDULE_BAND) force = ScanKernel::kBand;
     const bool automatic = force == ScanKernel::kNone && schedule == BASIC_SCAN_SCHEDULE_AUTO;
     const bool fits = batched_fits(p, batch, w, ndec, cus);
     if (force == ScanKernel::kBatched) BASIC_REQUIRE(fits, "scanline: BASIC_SCAN_KERNEL=batched, but this call does not fit the batched kernel");
-    if (force == ScanKernel::kWavefront) BASIC_REQUIRE(wf_fits, decode ? "scanline: BASIC_SCAN_KERNEL=wavefront, but this row-stream decode call does not fit the wavefront launch"
+    if (force == ScanKernel::kWavefront) BASIC_REQUIRE(wf_fits, decode ? "scanline: the wavefront decode launch was asked for, but this row-stream decode call does not fit the wavefront launch"
                                                                        : "scanline: the wavefront encode schedule was asked for, but this call does not fit it");
-    const int per_launch = !decode && (force == ScanKernel::kBand || (automatic && !wf_fits)) ? band_images() : 0;
-    if (force == ScanKernel::kBand) BASIC_REQUIRE(per_launch >= 1, "scanline: the band encode schedule was asked for, but this call does not fit it");
+    const int per_launch = decode ? band_dec_n : (force == ScanKernel::kBand || (automatic && !wf_fits)) ? band_images() : 0;
+    if (force == ScanKernel::kBand) BASIC_REQUIRE(per_launch >= 1, decode ? "scanline: the band decode launch was asked for, but this row-stream decode call does not fit it"
+                                                                          : "scanline: the band encode schedule was asked for, but this call does not fit it");
     L->images = batch;
     if (force == ScanKernel::kBand || (per_launch >= 1 && band_auto(p, batch, h, w, per_launch))) {
         L->kernel = ScanKernel::kBand;
@@ -540,8 +581,11 @@ inline int plan_scan(const ScanGeometry *p, const ScanRequest &q, ScanLaunch *L)
     if (L->kernel != ScanKernel::kGeneric && L->kernel != ScanKernel::kPipelined)
         L->lds_bytes = (align4(q.table_len) + 4 + 96 + static_cast<size_t>(p->b_tiles) * kBTile) * sizeof(float);   // table, flags, biases, partial tiles
     L->launches = (batch + L->images - 1) / L->images;
-    // (the wavefront decode launch: a decoder wavefront per row stream)
-    L->grid = compute_workgroups(p, L->kernel, L->images, h, w) + (decode && L->kernel == ScanKernel::kWavefront ? decoder_workgroups(batch * h * q.lanes) : ndec);
+    // (the wavefront decode launch: a decoder wavefront per row stream; the band decode launch: one per slot and lane of its images)
+    L->grid = compute_workgroups(p, L->kernel, L->images, h, w) +
+              (decode && L->kernel == ScanKernel::kWavefront ? decoder_workgroups(batch * h * q.lanes)
+               : decode && L->kernel == ScanKernel::kBand    ? decoder_workgroups(L->images * band_decode_slots(p, h, w) * q.lanes)
+                                                             : ndec);
     if (decode) L->lds_bytes = std::max(L->lds_bytes, q.decoder_lds);
     if (L->lds_bytes < kMinLds) L->lds_bytes = kMinLds;
     BASIC_REQUIRE(L->lds_bytes <= kMaxLds, L->kernel == ScanKernel::kBand ? "scanline: a workgroup's LDS does not fit"

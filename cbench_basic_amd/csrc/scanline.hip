@@ -106,7 +106,7 @@ struct ScanArgs {
     int wf_s;              // steps a row starts after the row above it: ksize / 2 + 2
     int wf_steps;          // W + wf_s * (H - 1)
     int wf_yw;             // columns of a yT slab: per image ksize / 2 pad columns (the rows above the image: zeros), then its H rows
-    // band encode schedule only (band_A == 0 otherwise; the wf_* fields hold as for the wavefront, B = the images of THIS launch): a lane
+    // band schedule only, encode and the decode of row streams (band_A == 0 otherwise; the wf_* fields hold as for the wavefront, B = the images of THIS launch): a lane
     // of a column tile is a SLOT of an image -- image (tile * band_ipt + lane / band_A), slot lane % band_A -- that walks rows slot,
     // slot + band_A, ... of its image one after the other (see the band section in front of scanline_batched_kernel)
     int band_A;            // slots per image: W / wf_s + 1, so a slot's period band_A * wf_s exceeds W
@@ -306,10 +306,20 @@ using wavedec::WaveDecoder;   // the serial rANS chain of one stream (wave_decod
 //     slab wf_s * r + c at the row's true column, and into sym / idx / ybuf at position r * W + c; then it returns.  The zeros of
 //     the steps in which the column is idle are published by the compute workgroups, never from here (they pace the tile's
 //     context workgroups: see the band section in front of scanline_batched_kernel).
+//   * ROWS = 3, the band decode launch (scanline_batched_kernel<true, true, true>): one wave per (image, slot, lane), NOT per row --
+//     an image brings min(band_A, H) * lanes of them whatever its height, which is what lets a launch hold many and tall images.
+//     Slot j's wave decodes rows j, j + band_A, ... one after the other, each exactly as a ROWS = 2 wave decodes its only row: the
+//     sleeping wait for the tag of the row's first step wf_s * r on the slot's MFMA column of mu / idx_step (tile * 32 + image in
+//     tile * band_A + slot: where the slot's compute lane publishes), W steps of wait -> decode_chunk -> publish into slab
+//     wf_s * r + c at the row's true column and into sym / idx / ybuf at r * W + c.  Between two rows the slot idles
+//     band_A * wf_s - W steps (1 .. wf_s: its compute lane publishes zeros); the wave re-initialises its WaveDecoder on the next
+//     row's stream there (restart: the two dependent round trips that sit on the step's path in the raster kernels), before it
+//     goes to sleep on the next row's first tag -- which the slot's column cannot carry earlier: its previous tag is the last
+//     step of the row just decoded.
 template <bool LANES, int ROWS = 0>
 __device__ __forceinline__ void decoder_loop(const ScanArgs &a, float *lds)
 {
-    static_assert(ROWS != 2 || LANES, "the wavefront's row streams take their lanes at run time");
+    static_assert(ROWS < 2 || LANES, "the wavefront's and the band's row streams take their lanes at run time");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wg = blockIdx.x;
     const int HW = a.H * a.W;
@@ -321,19 +331,22 @@ __device__ __forceinline__ void decoder_loop(const ScanArgs &a, float *lds)
         rowtab[r] = u32x4{a.tv.meta[r], static_cast<uint32_t>(a.tv.sizes[r]), static_cast<uint32_t>(a.tv.offsets[r]), 0u};
     __syncthreads();
     const int s = (wg - a.ncompute) * (kThreads / 64) + wave;
-    if (s >= (ROWS == 2 ? a.wf_cols * a.lanes : LANES ? a.B * a.lanes : a.B)) return;
-    const int q = LANES ? s / a.lanes : s;             // the column of mu / idx_step: the image, or (ROWS = 2) image * H + row
-    const int b = ROWS == 2 ? q / a.H : q;
-    const int wr = ROWS == 2 ? q - b * a.H : 0;        // ROWS = 2: this stream's row,
-    const int t0 = ROWS == 2 ? a.wf_s * wr : 0;        // the step it starts in
+    const int bslots = ROWS == 3 ? (a.band_A < a.H ? a.band_A : a.H) : 1;   // ROWS = 3: the slots of an image that have a row
+    if (s >= (ROWS == 3 ? a.B * bslots * a.lanes : ROWS == 2 ? a.wf_cols * a.lanes : LANES ? a.B * a.lanes : a.B)) return;
+    const int q = LANES ? s / a.lanes : s;             // the column of mu / idx_step: the image, or (ROWS = 2) image * H + row; ROWS = 3: image * bslots + slot
+    const int b = ROWS == 3 ? q / bslots : ROWS == 2 ? q / a.H : q;
+    int wr = ROWS == 3 ? q - b * bslots : ROWS == 2 ? q - b * a.H : 0;   // ROWS = 2: this stream's row (ROWS = 3: the slot = its first row),
+    int t0 = ROWS >= 2 ? a.wf_s * wr : 0;              // the step it starts in
     const int kl = LANES ? s - q * a.lanes : 0;
     const int cbeg = LANES ? kl * a.lane_w : 0, cend = LANES ? cbeg + a.lane_w : a.C;   // this stream's channels
-    const uint64_t *pi0 = a.idx_step + static_cast<int64_t>(q) * a.C, *pm0 = a.mu + static_cast<int64_t>(q) * a.C;
+    // (ROWS = 3: the slot's MFMA column -- its image's tile, the image inside the tile, the slot)
+    const int mcol = ROWS == 3 ? (b / a.band_ipt) * 32 + (b % a.band_ipt) * a.band_A + wr : q;
+    const uint64_t *pi0 = a.idx_step + static_cast<int64_t>(mcol) * a.C, *pm0 = a.mu + static_cast<int64_t>(mcol) * a.C;
     // a serial chain: never lose the issue arbitration to the waves spinning beside it (a wavefront row: once it has started)
-    if constexpr (ROWS != 2) __builtin_amdgcn_s_setprio(3);
+    if constexpr (ROWS < 2) __builtin_amdgcn_s_setprio(3);
     WaveDecoder d;
     const int nl = LANES ? a.lanes : 1;
-    int sr = ROWS == 1 ? b * a.H * nl + kl : s, left = a.W;   // ROWS = 1: the current row's stream, the positions left in that row
+    int sr = ROWS == 3 ? (b * a.H + wr) * nl + kl : ROWS == 1 ? b * a.H * nl + kl : s, left = a.W;   // ROWS = 1 (3): the current row's stream, the positions left in that row
     {
         const int64_t w0 = a.word_off[sr];
         d.init(img, a.words + w0, static_cast<int>(a.word_off[sr + 1] - w0), a.tv.precision, a.tv.bypass_precision, a.tv.bypass != 0, -1, 0ull, lane);
@@ -351,16 +364,48 @@ __device__ __forceinline__ void decoder_loop(const ScanArgs &a, float *lds)
         }
         __builtin_amdgcn_s_setprio(3);
     }
+    // ROWS = 3: the same wait, before every row of the slot (kept apart from the block above, which stays as it was: the wavefront
+    // launch runs the code it ran before the band existed); false = poisoned launch
+    auto band_row_start = [&]() -> bool {
+        unsigned spins = 0;
+        while (static_cast<uint32_t>(ld_gran(pi0 + cbeg) >> 32) != static_cast<uint32_t>(t0 + 1)) {
+            if (++spins > kSpinLimit || (spins % 64u == 0u && __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+                __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return false;
+            }
+            __builtin_amdgcn_s_sleep(32);
+        }
+        return true;
+    };
+    if constexpr (ROWS == 3) {
+        if (t0 > 0 && !band_row_start()) return;
+        __builtin_amdgcn_s_setprio(3);
+    }
     // where a chunk's results go: a uniform pointer per (step, chunk) + a lane term that never changes (channel c0 + lane; the
     // batched exchange layout is linear in c0: bm_gran(c0 + l) = bm_gran(l) + c0 * nbt for chunk starts c0)
     const int64_t bC = static_cast<int64_t>(b) * a.C;
-    const int YW = ROWS == 2 ? a.wf_yw : a.nbt;        // columns of a slab of the coded latent (wavefront: with the pad columns)
-    const int ycol = ROWS == 2 ? b * (a.H + a.wf_s - 2) + a.wf_s - 2 + wr : b;
-    const uint32_t lane_g = YW ? static_cast<uint32_t>(bm_gran(lane, ycol, YW)) : static_cast<uint32_t>(lane);
+    const int YW = ROWS >= 2 ? a.wf_yw : a.nbt;        // columns of a slab of the coded latent (wavefront, band: with the pad columns)
+    int ycol = ROWS >= 2 ? b * (a.H + a.wf_s - 2) + a.wf_s - 2 + wr : b;
+    uint32_t lane_g = YW ? static_cast<uint32_t>(bm_gran(lane, ycol, YW)) : static_cast<uint32_t>(lane);
     const uint32_t lane_y = static_cast<uint32_t>(lane) * static_cast<uint32_t>(HW);
-    for (int i = 0; i < (ROWS == 2 ? a.W : HW); ++i) {
-        const int p = ROWS == 2 ? wr * a.W + i : i;   // the position inside the image,
-        const int sl = ROWS == 2 ? t0 + i : i;        // the step: its tag, and its slab of the coded latent
+    // ROWS = 3: the slot's rows wr, wr + band_A, ... below H, W positions each; i0 = the loop index at which the current row started
+    const int band_count = ROWS == 3 ? ((a.H - wr + a.band_A - 1) / a.band_A) * a.W : 0;
+    int i0 = 0;
+    for (int i = 0; i < (ROWS == 3 ? band_count : ROWS == 2 ? a.W : HW); ++i) {
+        if constexpr (ROWS == 3) {
+            if (left == 0) {   // the slot's next row: its stream, its first step, its column of the slabs -- in the slot's idle steps,
+                sr += a.band_A * nl; left = a.W;   // where nothing waits for this wave
+                const int64_t w0 = a.word_off[sr];
+                d.restart(a.words + w0, static_cast<int>(a.word_off[sr + 1] - w0), lane);
+                wr += a.band_A; t0 = a.wf_s * wr; i0 = i;
+                ycol += a.band_A;
+                lane_g = static_cast<uint32_t>(bm_gran(lane, ycol, YW));
+                if (!band_row_start()) return;
+            }
+            --left;
+        }
+        const int p = ROWS == 3 ? wr * a.W + i - i0 : ROWS == 2 ? wr * a.W + i : i;   // the position inside the image,
+        const int sl = ROWS == 3 ? t0 + i - i0 : ROWS == 2 ? t0 + i : i;              // the step: its tag, and its slab of the coded latent
         const uint32_t tag = static_cast<uint32_t>(sl + 1);
         if constexpr (ROWS == 1) {
             if (left == 0) {   // a row start: the row's stream
@@ -416,11 +461,12 @@ __device__ __forceinline__ void decoder_loop(const ScanArgs &a, float *lds)
     }
 }
 
-// WF: the decoder workgroups of the wavefront decode launch (row streams only: nothing else has one)
-template <bool WF = false>
+// WF: the decoder workgroups of the wavefront decode launch (row streams only: nothing else has one); BAND: of the band decode launch
+template <bool WF = false, bool BAND = false>
 __device__ __forceinline__ void decoder_workgroup(const ScanArgs &a, float *lds)
 {
-    if constexpr (WF) decoder_loop<true, 2>(a, lds);
+    if constexpr (BAND) decoder_loop<true, 3>(a, lds);
+    else if constexpr (WF) decoder_loop<true, 2>(a, lds);
     else if (a.row_streams) { if (a.lanes > 1) decoder_loop<true, 1>(a, lds); else decoder_loop<false, 1>(a, lds); }
     else if (a.lanes > 1) decoder_loop<true>(a, lds);
     else decoder_loop<false>(a, lds);
@@ -1191,7 +1237,10 @@ __device__ __forceinline__ f4 b_leaky(f4 v)
 // dx + wf_s * dy); a column outside its row's [0, W) publishes zero granules with the step's tag, and the pad columns in front
 // of every image hold zeros for every step, so a tap outside the image multiplies zeros: no predicate inside a chain.
 //
-// BAND (with WF): the band encode schedule -- the wavefront's steps, slabs, taps and tags, but a lane is no longer bound to one row.
+// BAND (with WF): the band schedule (encode, and the decode of row streams: the Gaussian step is then the wavefront decode launch's --
+// an active slot lane publishes its table rows and means into idx_step / mu at its MFMA column for the slot's decoder wavefront,
+// decoder_loop ROWS = 3, which publishes the coded granules where the encoder's lane would; everything below holds for both) --
+// the wavefront's steps, slabs, taps and tags, but a lane is no longer bound to one row.
 // Row r is in flight only during steps [s r, s r + W), so an image needs about W / s lanes, not H: it owns A = W / s + 1 SLOTS (lanes
 // of ONE column tile, 32 / A images per tile, so the tiles of a launch share nothing and never wait for each other); slot j codes
 // rows j, j + A, j + 2 A, ... back to back with period A s.  At step t the slot has u = t - s j, (n, c) = divmod(u, A s), row
@@ -1224,12 +1273,11 @@ __device__ __forceinline__ f4 b_leaky(f4 v)
 template <bool DECODE, bool WF = false, bool BAND = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void scanline_batched_kernel(const ScanArgs a)
 {
-    static_assert(!(DECODE && BAND), "the band schedule is encode only (a wavefront decode call reads one rANS stream per row)");
     static_assert(WF || !BAND, "the band schedule is a wavefront schedule");
     extern __shared__ float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wg = blockIdx.x;
-    if (DECODE && wg >= a.ncompute) { decoder_workgroup<WF>(a, lds); return; }
+    if (DECODE && wg >= a.ncompute) { decoder_workgroup<WF, BAND>(a, lds); return; }
     const int HW = a.H * a.W, C = a.C, NBT = a.nbt, T = NBT >> 5;
     const int t = wg % T, j = wg / T;                  // column tile; role index inside the tile's set of workgroups
     const int h = lane >> 5, n = lane & 31, col = t * 32 + n;
@@ -1690,6 +1738,7 @@ struct basic_scanline_plan : ScanGeometry {
     unsigned *d_bar = nullptr;   // [0] barrier counter, [1] error flag
     hipEvent_t done = nullptr;   // completion of this plan's last launch (see ScanChain)
     int encode_schedule = BASIC_SCAN_SCHEDULE_AUTO;   // basic_scanline_set_encode_schedule
+    int decode_schedule = BASIC_SCAN_SCHEDULE_AUTO;   // basic_scanline_set_decode_schedule: row-stream decode calls only
     int last_kernel = BASIC_SCAN_KERNEL_NONE;         // basic_scanline_last_kernel
 };
 
@@ -1817,10 +1866,10 @@ namespace {
 using ScanFn = void (*)(ScanArgs);
 struct ScanKernelRow {
     const char *label;   // ScanProfile
-    ScanFn fn;           // nullptr: the schedule is encode only (the wavefront's decode row serves row-stream calls only)
+    ScanFn fn;           // (the wavefront's and the band's decode rows serve row-stream calls only: scan_kernel_decodes)
 };
 template <bool DECODE> constexpr ScanKernelRow kScanKernels[] = {
-    {"encode (band)", DECODE ? nullptr : scanline_batched_kernel<false, true, true>},
+    {DECODE ? "decode (band)" : "encode (band)", scanline_batched_kernel<DECODE, true, true>},
     {DECODE ? "decode (wavefront)" : "encode (wavefront)", scanline_batched_kernel<DECODE, true>},
     {DECODE ? "decode (batched)" : "encode (batched)", scanline_batched_kernel<DECODE>},
     {DECODE ? "decode" : "encode", scanline_pipelined_kernel<DECODE>},
@@ -1832,10 +1881,10 @@ static_assert(sizeof(kScanKernels<false>) / sizeof(ScanKernelRow) == sizeof(kSca
 constexpr bool scan_kernel_rows_match()
 {
     for (int k = 0; k < static_cast<int>(ScanKernel::kNone); ++k)
-        if (!kScanKernels<false>[k].fn || !kScanKernels<true>[k].fn == scan_kernel_decodes(static_cast<ScanKernel>(k))) return false;
+        if (!kScanKernels<false>[k].fn || !kScanKernels<true>[k].fn == scan_kernel_decodes(static_cast<ScanKernel>(k), true)) return false;
     return true;
 }
-static_assert(scan_kernel_rows_match(), "kScanKernels: a row's decode fn is null exactly where scan_kernel_decodes (scan_plan.h) says the kernel has no decode form");
+static_assert(scan_kernel_rows_match(), "kScanKernels: a row's decode fn is null exactly where scan_kernel_decodes (scan_plan.h) says the kernel serves no decode call at all");
 const ScanKernelRow &row_of(ScanKernel k, bool decode = false) { return (decode ? kScanKernels<true> : kScanKernels<false>)[static_cast<int>(k)]; }
 
 // BASIC_SCAN_KERNEL = generic | pipelined | batched | wavefront | band forces a kernel (identical results); anything else: kNone
@@ -1882,14 +1931,14 @@ int make_request(const basic_rans_tables *tables, int batch, int h, int w, int t
     return device_cus(&q->cus);
 }
 
-// Plans a *_dev call: the plan's encode schedule, no coder gates; `tables` != nullptr: decode
+// Plans a *_dev call: the plan's encode and decode schedules, no coder gates; `tables` != nullptr: decode
 int prepare_launch(const basic_scanline_plan *p, int batch, int lanes, bool rows, int h, int w, int table_len, const basic_rans_tables *tables,
                    RansFastView *tv, ScanLaunch *L)
 {
     ScanRequest q;
     const int rc = make_request(tables, batch, h, w, table_len, p->encode_schedule, -1, &q, tv);
     if (rc) return rc;
-    q.lanes = lanes; q.rows = rows;
+    q.lanes = lanes; q.rows = rows; q.decode_schedule = p->decode_schedule;
     if (tables && !q.fast_image) return rans_fast_view(tables, tv);   // no fast search image: its error
     return plan_scan(p, q, L);
 }
@@ -2045,7 +2094,7 @@ int run_launch(basic_scanline_plan *p, ScanArgs &a, const ScanLaunch &L, int gri
 {
     const ScanKernelRow &k = row_of(L.kernel, decode);
     const ScanFn fn = k.fn;
-    BASIC_REQUIRE(fn, "scanline: the band schedule is encode only");
+    BASIC_REQUIRE(fn, "scanline: the kernel has no such form");
     BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(fn)));
     ScanProfile prof;
     int rc = prof.begin(a, st);
@@ -2076,7 +2125,10 @@ int run_call(basic_scanline_plan *p, const ScanArgs &io, int batch, int h, int w
         if (rc) return rc;
         if (a.y) a.y += b0 * img_lat;
         a.ybuf += b0 * img_lat; a.sym += b0 * img_lat; a.idx += b0 * img_lat;
-        rc = run_launch(p, a, L, nb == L.images ? L.grid : a.ncompute, decode, st);   // (a short last launch: the band's, no decoder)
+        // a launch after the first is the band's: a decode one reads its own images' row streams with its own decoder workgroups
+        if (decode && b0 > 0) a.word_off += static_cast<int64_t>(b0) * h * io.lanes;
+        const int short_grid = a.ncompute + (decode ? decoder_workgroups(nb * band_decode_slots(p, h, w) * io.lanes) : 0);
+        rc = run_launch(p, a, L, nb == L.images ? L.grid : short_grid, decode, st);   // (a short last launch: the band's)
         if (rc) return rc;
     }
     return BASIC_OK;
@@ -2126,8 +2178,9 @@ extern "C" int basic_scanline_decode_lanes_dev(basic_scanline_plan *p, const bas
 }
 
 // basic_scanline_decode_lanes_dev for ROW STREAMS: batch * h * lanes streams, stream (b * h + r) * lanes + k carries row r of image
-// b, lane k.  Where the call fits (wavefront_decode_fits) and the rule or BASIC_SCAN_KERNEL=wavefront says so, the wavefront decode
-// launch; otherwise the raster kernels, whose decoder wavefronts change stream at every row start.
+// b, lane k.  Where the call fits (wavefront_decode_fits) and the rule, the plan's decode schedule or BASIC_SCAN_KERNEL=wavefront says
+// so, the wavefront decode launch; under the band decode schedule or BASIC_SCAN_KERNEL=band the band decode launch(es); otherwise the
+// raster kernels, whose decoder wavefronts change stream at every row start.
 extern "C" int basic_scanline_decode_rows_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
                                               const int64_t *d_word_off, const float *d_prior, int batch, int lanes, int h, int w,
                                               const float *d_table, int table_len, int32_t *d_symbols, int32_t *d_indexes, float *d_ybuf,
@@ -2163,7 +2216,7 @@ extern "C" int basic_scanline_choose_rows(const basic_scanline_plan *p, const ba
     ScanLaunch L;
     int rc = make_request(tables, batch, h, w, table_len, schedule, lane_max_batch, &q, &tv);
     if (rc) return rc;
-    q.lanes = lanes; q.rows = rows != 0 && tables != nullptr;
+    q.lanes = lanes; q.rows = rows != 0 && tables != nullptr; q.decode_schedule = p->decode_schedule;
     rc = plan_scan(p, q, &L);
     if (rc) return rc;
     *kernel = L.kernel == ScanKernel::kNone ? BASIC_SCAN_KERNEL_NONE : scan_kernel_id(L.kernel);
@@ -2241,6 +2294,26 @@ extern "C" int basic_scanline_band_max(const basic_scanline_plan *p, int h, int 
     return BASIC_OK;
 }
 
+// The images ONE launch of the band decode launch (row streams) decodes of an h x w latent in `lanes` lane streams on the current
+// device: the largest number whose column tiles' workgroups and decoder workgroups -- one wavefront per (image, slot, lane), four to
+// a workgroup -- fit the chip together; a larger batch takes several launches inside one call.  0 = never: what
+// basic_scanline_band_max says, no room for an image's decoder wavefronts beside its tile, or a table set without a fast search
+// image that fits the LDS.
+extern "C" int basic_scanline_band_decode_max(const basic_scanline_plan *p, const basic_rans_tables *tables, int h, int w, int lanes,
+                                              int *images_per_launch)
+{
+    BASIC_REQUIRE(p && tables && images_per_launch && h >= 1 && w >= 1, "scanline_band_decode_max: bad argument");
+    BASIC_REQUIRE(valid_lanes(p, lanes), "scanline_band_decode_max: lanes must divide the channels into runs of a multiple of 16");
+    *images_per_launch = 0;
+    RansFastView tv;
+    if (rans_fast_view(tables, &tv) != BASIC_OK || decoder_lds_bytes(tv.image_words, tv.rows) > kMaxLds) return BASIC_OK;
+    int cus = 0;
+    int rc = device_cus(&cus);
+    if (rc) return rc;
+    *images_per_launch = band_decode_images_per_launch(p, h, w, lanes, cus);
+    return BASIC_OK;
+}
+
 // Which kernel the plan's last launch (either direction) ran: BASIC_SCAN_KERNEL_*; NONE before the first launch.
 extern "C" int basic_scanline_last_kernel(const basic_scanline_plan *p, int *kernel)
 {
@@ -2255,6 +2328,17 @@ extern "C" int basic_scanline_set_encode_schedule(basic_scanline_plan *p, int sc
                        schedule == BASIC_SCAN_SCHEDULE_BAND),
                   "scanline_set_encode_schedule: bad argument");
     p->encode_schedule = schedule;
+    return BASIC_OK;
+}
+
+// The schedule of the plan's row-stream decode calls (basic_scanline_decode_rows_dev; basic_scanline_choose_rows with rows != 0
+// answers for it): BASIC_SCAN_SCHEDULE_*, as for encode.  Calls without row streams never look at it.
+extern "C" int basic_scanline_set_decode_schedule(basic_scanline_plan *p, int schedule)
+{
+    BASIC_REQUIRE(p && (schedule == BASIC_SCAN_SCHEDULE_AUTO || schedule == BASIC_SCAN_SCHEDULE_RASTER || schedule == BASIC_SCAN_SCHEDULE_WAVEFRONT ||
+                       schedule == BASIC_SCAN_SCHEDULE_BAND),
+                  "scanline_set_decode_schedule: bad argument");
+    p->decode_schedule = schedule;
     return BASIC_OK;
 }
 

@@ -689,12 +689,26 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
     # 31 s columns wide, as many launches as the batch needs; a call it does not fit raises) or "auto" (the library takes the
     # wavefront where it fits and measured faster).  The integers are the same.
     scanline_encode_schedule = "auto"
+    # how the persistent DECODE launch walks the latent when the coder writes row streams (stream_rows=True: one rANS stream per
+    # latent row, so a decoder may walk the rows of an image in parallel): "auto" (today the raster kernels, which read the row
+    # streams but walk H W steps), "raster" (never anything else), "wavefront" (one decoder wavefront per row: W + s (H - 1) steps,
+    # batch * H <= 64) or "band" (the same steps for any batch and height: an image's rows share W // s + 1 column slots, a decoder
+    # wavefront per slot; as many launches as the batch needs).  "wavefront" and "band" raise where the call does not fit, and
+    # need stream_rows=True: without row streams there is one serial stream per image and no such launch.  Same integers.
+    scanline_decode_schedule = "auto"
 
     def _check_lanes_call(self, pgm):
         if self.stream_lanes > 1 and pgm is not None:
             raise ValueError("stream_lanes > 1 codes the coder's default order only: a call may not bring its own pgm")
         if self.stream_rows and pgm is not None:
             raise ValueError("stream_rows=True codes the default scan-line order only: a call may not bring its own pgm")
+
+    def _check_decode_schedule(self):
+        if self.scanline_decode_schedule not in K.SCAN_SCHEDULES:
+            raise ValueError(f"scanline_decode_schedule must be one of {K.SCAN_SCHEDULES}, not {self.scanline_decode_schedule!r}")
+        if self.scanline_decode_schedule in ("wavefront", "band") and not self.stream_rows:
+            raise ValueError(f"scanline_decode_schedule={self.scanline_decode_schedule!r} needs stream_rows=True: without row streams "
+                             "an image is one serial rANS stream, which only the raster schedule decodes")
 
     def _check_lanes_steps(self, h, w):
         """Lane k of a coding step is the k-th of stream_lanes EQUAL parts of it: every non-empty step of the h x w latent must
@@ -734,6 +748,8 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
         # call.  A call whose latent size is not given can only be asked about the kernels that need none.
         known = width is not None and height is not None
         schedule = self.scanline_encode_schedule if known else "auto"
+        if decode:   # (the plan's decode schedule holds for the planner's answer below and for the launch alike)
+            sl.set_decode_schedule(self.scanline_decode_schedule if known and self.stream_rows else "auto")
         kernel, _ = sl.choose(batch, height or 0, width or 0, self._scale_table_dev.numel(), schedule, self.persistent_scanline_max_batch,
                               self._tables if decode else None, lanes=self.stream_lanes if decode else 1,
                               rows=self.stream_rows and decode)
@@ -833,6 +849,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
 
     def decode(self, byte_string: bytes, *args, prior=None, pgm=None, quantizer_params=None, **kwargs):
         self._check_lanes_call(pgm)
+        self._check_decode_schedule()
         pgm, kernel = self._split_dynamic_pgm(pgm)
         q = self._quantizer(quantizer_params)
         saved = self._enter_dynamic(kernel)
@@ -929,6 +946,7 @@ class GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder(HotPathModule):
 
     def _decode_impl(self, byte_string: bytes, *args, prior=None, pgm=None, quantizer_params=None, **kwargs):
         self._check_lanes_call(pgm)
+        self._check_decode_schedule()
         ptr = 0
         if self.fixed_input_shape is not None:
             B, spatial = self.fixed_input_shape[0], tuple(self.fixed_input_shape[1:])

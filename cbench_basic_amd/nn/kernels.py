@@ -716,6 +716,19 @@ class ScanlinePlan:
             cache[key] = m.value
         return cache[key]
 
+    def band_decode_max(self, tables, height, width, lanes=1):
+        """Images ONE band decode launch (row streams, `lanes` lane streams per image) decodes of a `height` x `width` latent with
+        that table set on this device: the largest number whose column tiles' workgroups and decoder workgroups -- a wavefront per
+        (image, slot, lane), four to a workgroup -- fit the chip together; a larger batch takes several launches inside one call
+        (0: never)."""
+        key = (id(tables), int(height), int(width), int(lanes), torch.cuda.current_device())
+        cache = self.__dict__.setdefault("_band_decode_max", {})
+        if key not in cache:
+            m = ctypes.c_int()
+            _lib.check(_lib.lib().basic_scanline_band_decode_max(self._h, tables._h, int(height), int(width), int(lanes), ctypes.byref(m)))
+            cache[key] = (m.value, tables)   # (tables: keeps its id its own)
+        return cache[key][0]
+
     def last_kernel(self):
         """The kernel the plan's last launch ran: "generic", "pipelined", "batched", "wavefront" or "band"; None before the first."""
         k = ctypes.c_int()
@@ -729,19 +742,29 @@ class ScanlinePlan:
             raise ValueError(f"encode schedule must be one of {SCAN_SCHEDULES}, not {schedule!r}")
         _lib.check(_lib.lib().basic_scanline_set_encode_schedule(self._h, SCAN_SCHEDULES.index(schedule)))
 
+    def set_decode_schedule(self, schedule):
+        """How decode calls over ROW STREAMS are scheduled from now on: "auto" (today: the raster kernels), "raster" (never the
+        wavefront or the band), "wavefront" or "band" (always that launch: a call that does not fit it raises).  Decode calls
+        without row streams never look at it.  The decoded integers do not depend on it."""
+        if schedule not in SCAN_SCHEDULES:
+            raise ValueError(f"decode schedule must be one of {SCAN_SCHEDULES}, not {schedule!r}")
+        _lib.check(_lib.lib().basic_scanline_set_decode_schedule(self._h, SCAN_SCHEDULES.index(schedule)))
+        self._decode_schedule = schedule
+
     def choose(self, batch, height, width, table_len, schedule="auto", lane_max_batch=0, tables=None, lanes=1, rows=False):
         """What an encode call (tables None) or a decode call with that table set would run for `batch` images of a `height` x
         `width` latent (0: not known), as the library's one planner decides it -- without launching: -> (kernel, launches), kernel
         one of SCAN_KERNELS, or None where the call is left to the per-step path.  `schedule` stands for the plan's encode schedule
         (BASIC_SCAN_KERNEL wins over it); batches above `lane_max_batch` are not given to the generic and pipelined kernels.  A
         forced kernel or schedule the call does not fit raises, as the launch would.  `lanes`: the lane streams per image of a decode
-        call (a decoder wavefront each); `rows`: the decode call brings row streams (the wavefront decode launch may serve it)."""
+        call (a decoder wavefront each); `rows`: the decode call brings row streams (the wavefront or band decode launch may serve
+        it: the plan's decode schedule, set_decode_schedule, holds for the answer as for the call)."""
         if schedule not in SCAN_SCHEDULES:
             raise ValueError(f"encode schedule must be one of {SCAN_SCHEDULES}, not {schedule!r}")
         # the answer depends on nothing but these, so a repeated call (every step of a stream worker) asks the library once: a
         # library call releases the interpreter lock, and with several workers each release is a chance to wait for it again
         key = (int(batch), int(height), int(width), int(table_len), schedule, int(lane_max_batch), id(tables), os.environ.get("BASIC_SCAN_KERNEL"),
-               torch.cuda.current_device(), int(lanes), bool(rows))
+               torch.cuda.current_device(), int(lanes), bool(rows), getattr(self, "_decode_schedule", "auto"))
         cache = self.__dict__.setdefault("_chosen", {})
         if key not in cache:
             k, n = ctypes.c_int(), ctypes.c_int()

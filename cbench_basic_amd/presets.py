@@ -59,7 +59,7 @@ BASIC_WIDTHS = [48, 72, 96, 144, 192]
 
 
 def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset=None, combined_entropy_coder=False, stream_lanes=1,
-                stream_rows=False):
+                stream_rows=False, scanline_decode_schedule="auto"):
     """BaSIC "hyperprior-ar-sc-slimmable-full-dynamic" (configs/presets/lossy_latent_graph_scalable_ar_models.py:
     73-197): slimmable g_a/g_s, MS-slimmable h_a/h_s, 192-ch EntropyBottleneck, scanline AR y-coder with the
     masked-conv context model, four slim controller nodes selected per complexity level.
@@ -78,7 +78,10 @@ def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset
 
     ``stream_rows`` = True: the scan-line y-coder writes one stream per latent row (and lane) of every image ("Row
     streams": not readable by the reference either), which lets the decode launch walk an image's rows in parallel; in the combined
-    bank only the scan-line member gets it."""
+    bank only the scan-line member gets it.
+
+    ``scanline_decode_schedule`` = "auto" | "raster" | "wavefront" | "band": how the scan-line y-coder's persistent decode launch
+    walks a latent that came as row streams (the coder's attribute of that name; "wavefront" and "band" need ``stream_rows``)."""
     from .modules.prior_model.prior_coder.pgm_coder import (CombinedNNTrainablePGMPriorCoder,
                                                             GaussianChannelGroupMaskConv2DTopoGroupPGMPriorCoder,
                                                             TopoGroupDynamicMaskConv2dContextModel)
@@ -87,6 +90,11 @@ def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset
                                        MeanScaleHyperpriorHyperAnalysisSlimmableConv2dPGMModel,
                                        MeanScaleHyperpriorHyperSynthesisSlimmableConv2dPGMModel)
     n = len(widths)
+
+    if scanline_decode_schedule not in ("auto", "raster", "wavefront", "band"):
+        raise ValueError(f"scanline_decode_schedule must be auto, raster, wavefront or band, not {scanline_decode_schedule!r}")
+    if scanline_decode_schedule in ("wavefront", "band") and not stream_rows:
+        raise ValueError(f"scanline_decode_schedule={scanline_decode_schedule!r} needs stream_rows=True")
 
     def ar_coder(**kw):
         # training_no_quantize_for_likelihood as in the reference preset (lossy_latent_graph_scalable_ar_models.py:121,261-330): the
@@ -115,6 +123,9 @@ def basic_codec(widths=BASIC_WIDTHS, M=192, num_complex_levels=8, search_dataset
         y_mapping = {"pgmy": "blend_weight", "z": "prior"}
     else:
         y_coder = ar_coder(default_topo_group_method="scanline", stream_lanes=stream_lanes, stream_rows=stream_rows)
+
+    # (a knob of the scan-line member, not of the format: set on the coder, as its encode schedule is)
+    (y_coder.coders[0] if combined_entropy_coder else y_coder).scanline_decode_schedule = scanline_decode_schedule
 
     def slim_node():
         return IndexSelectParameterGeneratorWrapper(

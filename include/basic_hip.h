@@ -467,6 +467,8 @@ int basic_scanline_decode_lanes_dev(basic_scanline_plan *p, const basic_rans_tab
  * workgroups plus ceil(batch * h * lanes / 4) decoder workgroups are resident, the call may run as the WAVEFRONT decode launch
  * (w + (ksize / 2 + 2) * (h - 1) steps, one decoder wavefront per stream; BASIC_SCAN_KERNEL=wavefront forces it, "does not fit"
  * otherwise); else the raster kernels read the same streams, a decoder wavefront changing stream at every row start.
+ * Under BASIC_SCAN_SCHEDULE_BAND (basic_scanline_set_decode_schedule) or BASIC_SCAN_KERNEL=band the call runs as the BAND decode
+ * launch (basic_scanline_band_decode_max): the same steps for any batch and height, in as many launches as the batch needs.
  * Everything written is what basic_scanline_decode_dev writes. */
 int basic_scanline_decode_rows_dev(basic_scanline_plan *p, const basic_rans_tables *tables, const uint32_t *d_words,
                                    const int64_t *d_word_off, const float *d_prior, int batch, int lanes, int h, int w,
@@ -500,6 +502,17 @@ int basic_scanline_wavefront_max(const basic_scanline_plan *p, int h, int w, int
  * batched kernel's shape, A > 32 -- a latent wider than 31 * s columns --, or one image alone exceeds the scratch limit or the
  * kernel's 32-bit offsets).  Any batch fits when it is >= 1. */
 int basic_scanline_band_max(const basic_scanline_plan *p, int h, int w, int *images_per_launch);
+/* The BAND DECODE launch serves decode calls over ROW STREAMS (basic_scanline_decode_rows_dev) the same way: the band's compute
+ * workgroups, plus one decoder wavefront per (image, slot, lane stream) -- slot j's wavefront decodes rows j, j + A, ... of its
+ * image one after the other, changing stream in the slot's idle steps --, four to a workgroup, resident beside them.  An image
+ * brings min(A, h) * lanes decoder wavefronts whatever its height, so the launch takes what the wavefront decode launch cannot:
+ * more than 64 rows in all.  Opt-in: BASIC_SCAN_SCHEDULE_BAND as the plan's decode schedule, or BASIC_SCAN_KERNEL=band.
+ * *images_per_launch = the largest n <= basic_scanline_band_max with
+ *     tiles(n) * workgroups per tile + ceil(n * min(A, h) * lanes / 4) <= compute units;
+ * 0 = never (also: `tables` has no fast search image that fits the LDS).  A larger batch takes several launches inside the call,
+ * each with the decoder workgroups of its own images. */
+int basic_scanline_band_decode_max(const basic_scanline_plan *p, const basic_rans_tables *tables, int h, int w, int lanes,
+                                   int *images_per_launch);
 /* *kernel = which kernel the plan's last launch (encode or decode) ran. */
 #define BASIC_SCAN_KERNEL_NONE (-1) /* no launch yet */
 #define BASIC_SCAN_KERNEL_GENERIC 0
@@ -514,12 +527,19 @@ int basic_scanline_last_kernel(const basic_scanline_plan *p, int *kernel);
  * basic_scanline_batched_max, never the wavefront or the band.  WAVEFRONT / BAND: always; a call that does not fit it fails
  * with BASIC_ERR_INVALID ("does not fit").  The environment variable
  * BASIC_SCAN_KERNEL = generic | pipelined | batched | wavefront | band, when set, wins over the plan's schedule; decode calls
- * ignore "wavefront", "band" and the schedule. */
+ * ignore this schedule, and "wavefront" and "band" unless they bring row streams (basic_scanline_set_decode_schedule). */
 #define BASIC_SCAN_SCHEDULE_AUTO 0
 #define BASIC_SCAN_SCHEDULE_RASTER 1
 #define BASIC_SCAN_SCHEDULE_WAVEFRONT 2
 #define BASIC_SCAN_SCHEDULE_BAND 3
 int basic_scanline_set_encode_schedule(basic_scanline_plan *p, int schedule);
+/* How the plan's ROW-STREAM decode calls (basic_scanline_decode_rows_dev) are scheduled from now on, in the same values.  AUTO (the
+ * default): the raster kernels -- no step cost of the wavefront or band decode launch has been turned into a rule yet.  RASTER:
+ * never the wavefront or the band, whatever a later rule says.  WAVEFRONT / BAND: always that launch; a call that does not fit it
+ * fails with BASIC_ERR_INVALID ("does not fit") before anything is launched.  BASIC_SCAN_KERNEL, when set, wins.
+ * basic_scanline_decode_dev and basic_scanline_decode_lanes_dev cannot carry row streams and never look at this schedule (nor at
+ * BASIC_SCAN_KERNEL=wavefront / band); basic_scanline_choose_rows with rows != 0 answers for it. */
+int basic_scanline_set_decode_schedule(basic_scanline_plan *p, int schedule);
 /* What a call would run, without launching anything: tables == NULL asks about basic_scanline_encode_dev, otherwise about
  * basic_scanline_decode_dev with that table set, for `batch` images of an h x w latent (0 = not known: only the kernels that
  * need no such knowledge are considered) and a scale table of table_len entries.  One planner in csrc/scanline.hip answers this
@@ -538,8 +558,9 @@ int basic_scanline_choose(const basic_scanline_plan *p, const basic_rans_tables 
 int basic_scanline_choose_lanes(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int lanes, int h, int w,
                                 int table_len, int schedule, int lane_max_batch, int *kernel, int *launches);
 /* basic_scanline_choose_lanes with `rows` != 0 for a decode call over row streams (basic_scanline_decode_rows_dev): the wavefront
- * decode launch is considered (its decoder workgroups: batch * h * lanes streams), the raster kernels count batch * lanes.  Encode
- * calls do not depend on `rows`; rows == 0 is basic_scanline_choose_lanes. */
+ * decode launch is considered (its decoder workgroups: batch * h * lanes streams), the raster kernels count batch * lanes, and the
+ * plan's decode schedule (basic_scanline_set_decode_schedule) holds as it does for the call.  Encode calls do not depend on `rows`;
+ * rows == 0 is basic_scanline_choose_lanes. */
 int basic_scanline_choose_rows(const basic_scanline_plan *p, const basic_rans_tables *tables, int batch, int lanes, int rows, int h, int w,
                                int table_len, int schedule, int lane_max_batch, int *kernel, int *launches);
 int basic_scanline_status(basic_scanline_plan *p, void *hip_stream, int *poisoned);

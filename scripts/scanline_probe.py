@@ -15,7 +15,7 @@ c = c.eval().cuda()
 c.update_state()
 
 
-def lanes_probe(lanes_list, shapes, runs, rows=False):
+def lanes_probe(lanes_list, shapes, runs, rows=False, decode_schedule="auto"):
     """--lanes K [K ...]: lane streams (stream_lanes = K) against one stream per image.  Per shape and K, `runs` runs of five calls
     each (the median of a run is its figure; min - max over the runs is the spread): GPU time of the persistent decode launch
     (ScanlinePlan.decode, or the whole per-step decode where the planner leaves the call to it), GPU time of the y rANS encode (pack
@@ -23,7 +23,10 @@ def lanes_probe(lanes_list, shapes, runs, rows=False):
     so the same script measures the commit before them.  BASIC_SCAN_PROFILE=1 adds the kernel's per-step split (stderr).
     --rows: the same figures with row streams (stream_rows = True: one stream per latent row and lane; the decode launch is the
     wavefront's where the planner takes it, BASIC_SCAN_KERNEL forces another); without it the script uses nothing the library lacked
-    before row streams, so the same --lanes run on the commit before them is the yardstick."""
+    before row streams, so the same --lanes run on the commit before them is the yardstick.
+    --decode-schedule raster | wavefront | band (with --rows): the coder's scanline_decode_schedule -- the wavefront or the band decode
+    launch instead of the raster kernels; a shape the launch does not fit is reported and skipped.  Left at auto the script sets
+    nothing, so --rows on the commit before the schedule measures the raster decode launch the same calls took there."""
     import numpy as np
     from cbench_basic_amd.nn import kernels as K
 
@@ -54,6 +57,8 @@ def lanes_probe(lanes_list, shapes, runs, rows=False):
                 raise SystemExit("this library has no lane streams: --lanes 1 only")
             if rows:
                 c.stream_rows = True
+            if decode_schedule != "auto":
+                c.scanline_decode_schedule = decode_schedule
             c.batch_stream_mode = "per_image"   # (K = 1 at batch 1: framed like the lanes, so that the bytes compare)
             R = H if rows else 1   # streams per image and lane
             sym, idx, _, plan = c._run_encode(y, prior)
@@ -63,7 +68,13 @@ def lanes_probe(lanes_list, shapes, runs, rows=False):
             woff = np.concatenate([[0], np.cumsum(lens // 4)]).astype(np.int64)
             d_words = torch.from_numpy(np.frombuffer(data, dtype=np.int32, count=int(woff[-1]), offset=4 + 4 * nstreams).copy()).cuda()
             d_woff = torch.from_numpy(woff).cuda()
-            sl = c._scanline_plan(plan, prior, B, decode=True, width=W, height=H)
+            try:
+                sl = c._scanline_plan(plan, prior, B, decode=True, width=W, height=H)
+            except Exception as e:   # a forced schedule the call does not fit
+                if "does not fit" not in str(e):
+                    raise
+                print(f"B={B:3d} {H}x{W} K={lanes:2d} rows [{decode_schedule}]: does not fit", flush=True)
+                continue
             if sl is None:
                 dec, served = (lambda: c._run_decode_impl(d_words, d_woff, prior, B, H, W, True, plan)), "per-step"
             elif rows:
@@ -100,8 +111,12 @@ if "--lanes" in sys.argv or "--rows" in sys.argv:
     ap.add_argument("--shapes", type=int, nargs="+", default=[1, 32, 48, 64, 16, 16], help="B H W [B H W ...]")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--rows", action="store_true", help="row streams (stream_rows = True) at every lane count")
+    ap.add_argument("--decode-schedule", choices=("auto", "raster", "wavefront", "band"), default="auto",
+                    help="the coder's scanline_decode_schedule (needs --rows)")
     a = ap.parse_args()
-    lanes_probe(a.lanes, [tuple(a.shapes[i: i + 3]) for i in range(0, len(a.shapes), 3)], a.runs, rows=a.rows)
+    if a.decode_schedule != "auto" and not a.rows:
+        ap.error("--decode-schedule needs --rows: only row streams have a decode schedule")
+    lanes_probe(a.lanes, [tuple(a.shapes[i: i + 3]) for i in range(0, len(a.shapes), 3)], a.runs, rows=a.rows, decode_schedule=a.decode_schedule)
     sys.exit(0)
 
 shapes = ((1, 32, 48), (8, 16, 16), (64, 16, 16), (24, 32, 48))

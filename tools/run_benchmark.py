@@ -49,12 +49,17 @@ def main():
                     help="lane streams per image of the y-coder, any codec (a format the reference does not read)")
     ap.add_argument("--stream-rows", action="store_true",
                     help="--codec basic: one stream per latent row of the scan-line y-coder (a format the reference does not read)")
+    ap.add_argument("--scanline-decode-schedule", choices=["auto", "raster", "wavefront", "band"], default="auto",
+                    help="--stream-rows: how the scan-line y-coder's persistent decode launch walks the row streams (wavefront: one "
+                         "decoder wavefront per row, batch * H <= 64; band: any batch and height; both raise where the call does not fit)")
     ap.add_argument("--metrics", nargs="+", choices=["psnr", "ms-ssim"], default=["psnr"],
                     help="distortion metrics of the reconstruction (ms-ssim needs images with both sides above 160)")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     if args.stream_rows and args.codec != "basic":
         ap.error("--stream-rows needs --codec basic")
+    if args.scanline_decode_schedule != "auto" and not args.stream_rows:
+        ap.error("--scanline-decode-schedule needs --stream-rows: only row streams have a decode schedule")
     if not 1 <= args.stream_lanes <= 256:
         ap.error("--stream-lanes must be in [1, 256]")
     if args.coalesce and args.batch_size != 1:
@@ -75,7 +80,8 @@ def main():
     else:
         ds = RandomImageDataset(num=args.synthetic or 8, size=(3, args.height or args.size, args.width or args.size))
     batches = list(batched(ds, args.batch_size))
-    builders = dict(hyperprior=lambda: presets.hyperprior_codec(stream_lanes=args.stream_lanes), basic=lambda **kw: presets.basic_codec(stream_lanes=args.stream_lanes, stream_rows=args.stream_rows, **kw),
+    builders = dict(hyperprior=lambda: presets.hyperprior_codec(stream_lanes=args.stream_lanes), basic=lambda **kw: presets.basic_codec(stream_lanes=args.stream_lanes, stream_rows=args.stream_rows,
+                                                              scanline_decode_schedule=args.scanline_decode_schedule, **kw),
                     topogroup=lambda: presets.topogroup_ar_codec(method=args.method, stream_lanes=args.stream_lanes))
     codec = builders["basic"](search_dataset=batches) if (args.codec == "basic" and args.complexity_search) else builders[args.codec]()
     if args.checkpoint:
