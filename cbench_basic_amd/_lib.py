@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbasic_hip.so")
 
 OK, ERR_INVALID, ERR_NOT_INIT, ERR_HIP, ERR_OVERFLOW, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5
+IMAGE_CHW, IMAGE_HWC = 0, 1   # BASIC_IMAGE_*: the order of the uint8 side of an 8-bit image call
 
 
 class BasicHipError(RuntimeError):
@@ -79,6 +80,10 @@ _SIGNATURES = {
     "basic_hp_encode_result": (_I, [_P, _P, _L, _P]),
     "basic_hp_decoded_shape": (_I, [_P, _P, _L, _P, _P, _P, _P]),
     "basic_hp_decode_images": (_I, [_P, _P, _L, _P, _L, _P]),
+    "basic_image_u8_to_f32_dev": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "basic_image_f32_to_u8_dev": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "basic_hp_encode_images_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
+    "basic_hp_decode_images_u8": (_I, [_P, _P, _L, _I, _P, _I, _L, _P]),
     "basic_hp_session_set_rans_waves": (_I, [_P, _I]),
     "basic_hp_session_set_stream_lanes": (_I, [_P, _I]),
     "basic_hp_session_set_transform_token": (_I, [_P, _I]),

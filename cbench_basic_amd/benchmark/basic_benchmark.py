@@ -97,17 +97,27 @@ class BasicLosslessCompressionBenchmark:
         if torch.cuda.is_available():
             torch.cuda.current_stream().synchronize()
 
+    def _target(self, data):
+        """What a reconstruction of ``data`` is compared with: the item on the testing device; an 8-bit item converted ONCE there
+        (u8 / 255 by the library's kernel), so that its distortion is the one of the same item given as float32."""
+        target = data.to(self.force_testing_device) if self.force_testing_device else data
+        if isinstance(target, torch.Tensor) and target.dtype == torch.uint8:
+            from ..nn import kernels as K
+            target = K.image_u8_to_f32(target)
+        return target
+
     def _run_step(self, step, data, metric_logger, codec=None, distortion_metric=None):
         codec = self.codec if codec is None else codec
         # the batch stays where the loader left it (the host): codec.compress() uploads it INSIDE the timed region, as the
         # reference's does (general_codec.py:46-47 under basic_benchmark.py:199-202); only the metric's target is moved
         data_input = data
-        data_target = data.to(self.force_testing_device) if self.force_testing_device else data
-        original_length = self._estimate_byte_length(data_input)
+        data_target = self._target(data)
+        original_length = self._estimate_byte_length(data_input)   # an 8-bit item: one byte per sample, a quarter of the float item's
         metric_logger.update(original_length=original_length)
         dm = self.distortion_metric if distortion_metric is None else distortion_metric
         if self.nn_codec_use_forward_pass and hasattr(codec, "forward_estimate_bitlen"):
-            decompressed, compressed_length = codec.forward_estimate_bitlen(data_input)
+            # the forward pass is the float graph: an 8-bit item enters it converted
+            decompressed, compressed_length = codec.forward_estimate_bitlen(data_target if getattr(data_input, "dtype", None) == torch.uint8 else data_input)
             compressed_length = float(compressed_length)
             metric_logger.update(compression_ratio_nn_forward=compressed_length / original_length,
                                  compressed_length_nn_forward=compressed_length)
@@ -210,14 +220,14 @@ class BasicLosslessCompressionBenchmark:
         codec = self.codec if codec is None else codec
         dm = self.distortion_metric   # asked with cache_metrics=False only: nothing is logged before the pass is over
         data = [items[i] for i in chunk]
-        targets = [d.to(self.force_testing_device) if self.force_testing_device else d for d in data]
+        targets = [self._target(d) for d in data]
         lengths = [self._estimate_byte_length(d) for d in data]
         n = len(chunk)
         for i, L in zip(chunk, lengths):
             records[i] = (OrderedDict(original_length=L), [])
         if self.nn_codec_use_forward_pass and hasattr(codec, "forward_estimate_bitlen"):
             for i, d, t, L in zip(chunk, data, targets, lengths):   # the forward estimate stays one call per item
-                decompressed, compressed_length = codec.forward_estimate_bitlen(d)
+                decompressed, compressed_length = codec.forward_estimate_bitlen(t if getattr(d, "dtype", None) == torch.uint8 else d)
                 compressed_length = float(compressed_length)
                 records[i][0].update(compression_ratio_nn_forward=compressed_length / L, compressed_length_nn_forward=compressed_length)
                 if dm is not None:

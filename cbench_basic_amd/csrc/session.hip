@@ -137,6 +137,12 @@ struct basic_hp_session {
     hipStream_t copy = nullptr;
     hipEvent_t x_free = nullptr, x_ready = nullptr;
     bool x_read_pending = false;
+    // 8-bit images (basic_hp_*_images_u8): a uint8 batch is staged in u8_in and converted into d_x, a reconstruction is decoded
+    // into d_xhat and converted out of it (into u8_out when the caller's buffer is host memory).  u8_free: the last conversion
+    // out of u8_in; xhat_free: the last conversion out of d_xhat.  Either may have run on another stream than the next call's.
+    DBuf u8_in, u8_out, d_xhat;
+    hipEvent_t u8_free = nullptr, xhat_free = nullptr;
+    bool u8_read_pending = false, xhat_read_pending = false;
     ~basic_hp_session();
 };
 
@@ -356,7 +362,7 @@ basic_hp_session::~basic_hp_session()
                     e = nullptr;
                 }
     }
-    for (hipEvent_t e : {in_done, enc_phase, dec_phase, fork, join, x_free, x_ready})
+    for (hipEvent_t e : {in_done, enc_phase, dec_phase, fork, join, x_free, x_ready, u8_free, xhat_free})
         if (e) (void)hipEventDestroy(e);
     if (side) (void)hipStreamDestroy(side);
     if (copy) (void)hipStreamDestroy(copy);
@@ -407,39 +413,31 @@ int encode_latent(basic_hp_session *s, const basic_rans_tables *t, const int32_t
     return basic_rans_encode_batch_dev(t, d_sym, d_idx, seg->as<int64_t>(), streams, slots->as<uint32_t>(), slot, d_nw, st);
 }
 
-}  // namespace
-
-extern "C" int basic_hp_encode_images(basic_hp_session *s, const float *x, int x_on_host, int batch, int h, int w, uint8_t *out,
-                                      int64_t out_capacity, int64_t *out_len, void *hip_stream)
+// the copy stream and the events that order a session's input buffers between calls
+int ensure_copy_stream(basic_hp_session *s)
 {
-    BASIC_REQUIRE(s && x && out_len && batch >= 1 && h >= 1 && w >= 1, "hp_encode_images: bad argument");
-    s->res_batch = 0;
-    hipStream_t st = as_stream(hip_stream);
-    WavesGuard guard(s->rans_waves, s->use_token);
+    if (s->copy) return BASIC_OK;
+    BASIC_HIP_TRY(hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
+    BASIC_HIP_TRY(hipEventCreateWithFlags(&s->x_free, hipEventDisableTiming));
+    BASIC_HIP_TRY(hipEventCreateWithFlags(&s->x_ready, hipEventDisableTiming));
+    BASIC_HIP_TRY(hipEventCreateWithFlags(&s->u8_free, hipEventDisableTiming));
+    BASIC_HIP_TRY(hipEventCreateWithFlags(&s->xhat_free, hipEventDisableTiming));
+    return BASIC_OK;
+}
+
+// Everything of an encode call behind its input: d_x is float32 [batch][x_channels][h][w] on the device, complete in the order
+// of `st`.  x_in_session: d_x is the session's own buffer, whose next writer must wait for this call's analysis transform.
+int encode_body(basic_hp_session *s, const float *d_x, bool x_in_session, int batch, int h, int w, uint8_t *out, int64_t out_capacity,
+                int64_t *out_len, hipStream_t st)
+{
     int rc;
-    const float *d_x = x;
-    if (x_on_host) {   // general_codec.py:46-47: the upload belongs to compress()
-        const size_t bytes = sizeof(float) * static_cast<size_t>(batch) * s->x_channels * h * w;
-        rc = s->d_x.ensure(bytes);
-        if (rc) return rc;
-        if (!s->copy) {
-            BASIC_HIP_TRY(hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
-            BASIC_HIP_TRY(hipEventCreateWithFlags(&s->x_free, hipEventDisableTiming));
-            BASIC_HIP_TRY(hipEventCreateWithFlags(&s->x_ready, hipEventDisableTiming));
-        }
-        if (s->x_read_pending) BASIC_HIP_TRY(hipStreamWaitEvent(s->copy, s->x_free, 0));
-        BASIC_HIP_TRY(hipMemcpyAsync(s->d_x.p, x, bytes, hipMemcpyHostToDevice, s->copy));
-        BASIC_HIP_TRY(hipEventRecord(s->x_ready, s->copy));
-        BASIC_HIP_TRY(hipStreamWaitEvent(st, s->x_ready, 0));
-        d_x = s->d_x.as<float>();
-    }
     // ---- inference pass x -> y -> z (latent_graph.py:721-758)
     int yh, yw, zh, zw, ph, pw;
     TokenPhase phase(s, st, &s->enc_phase);   // the analysis transform: ~95 % of the encoder's MFMA work
     if (phase.rc) return phase.rc;
     rc = run_chain(s, s->g_a, d_x, batch, h, w, &s->d_y, nullptr, &yh, &yw, st);
     if (rc) return rc;
-    if (x_on_host) {
+    if (x_in_session) {
         BASIC_HIP_TRY(hipEventRecord(s->x_free, st));
         s->x_read_pending = true;
     }
@@ -550,6 +548,66 @@ extern "C" int basic_hp_encode_images(basic_hp_session *s, const float *x, int x
     return basic_hp_encode_result(s, out, out_capacity, out_len);
 }
 
+}  // namespace
+
+extern "C" int basic_hp_encode_images(basic_hp_session *s, const float *x, int x_on_host, int batch, int h, int w, uint8_t *out,
+                                      int64_t out_capacity, int64_t *out_len, void *hip_stream)
+{
+    BASIC_REQUIRE(s && x && out_len && batch >= 1 && h >= 1 && w >= 1, "hp_encode_images: bad argument");
+    s->res_batch = 0;
+    hipStream_t st = as_stream(hip_stream);
+    WavesGuard guard(s->rans_waves, s->use_token);
+    int rc;
+    const float *d_x = x;
+    if (x_on_host) {   // general_codec.py:46-47: the upload belongs to compress()
+        const size_t bytes = sizeof(float) * static_cast<size_t>(batch) * s->x_channels * h * w;
+        rc = s->d_x.ensure(bytes);
+        if (!rc) rc = ensure_copy_stream(s);
+        if (rc) return rc;
+        if (s->x_read_pending) BASIC_HIP_TRY(hipStreamWaitEvent(s->copy, s->x_free, 0));
+        BASIC_HIP_TRY(hipMemcpyAsync(s->d_x.p, x, bytes, hipMemcpyHostToDevice, s->copy));
+        BASIC_HIP_TRY(hipEventRecord(s->x_ready, s->copy));
+        BASIC_HIP_TRY(hipStreamWaitEvent(st, s->x_ready, 0));
+        d_x = s->d_x.as<float>();
+    }
+    return encode_body(s, d_x, x_on_host != 0, batch, h, w, out, out_capacity, out_len, st);
+}
+
+// The uint8 batch reaches d_x through a conversion on the caller's stream.  Orders kept between calls (whose streams may differ):
+// the upload into u8_in waits for the previous conversion out of it (u8_free); the conversion waits for the upload (x_ready) and,
+// as the float upload does, for the previous call's analysis transform, the last reader of d_x (x_free).
+extern "C" int basic_hp_encode_images_u8(basic_hp_session *s, const uint8_t *x, int x_on_host, int layout, int batch, int h, int w,
+                                         uint8_t *out, int64_t out_capacity, int64_t *out_len, void *hip_stream)
+{
+    BASIC_REQUIRE(s && x && out_len && batch >= 1 && h >= 1 && w >= 1, "hp_encode_images_u8: bad argument");
+    BASIC_REQUIRE(layout == BASIC_IMAGE_CHW || layout == BASIC_IMAGE_HWC, "hp_encode_images_u8: layout is BASIC_IMAGE_CHW or BASIC_IMAGE_HWC");
+    s->res_batch = 0;
+    hipStream_t st = as_stream(hip_stream);
+    WavesGuard guard(s->rans_waves, s->use_token);
+    const size_t samples = static_cast<size_t>(batch) * s->x_channels * h * w;
+    int rc = s->d_x.ensure(sizeof(float) * samples);
+    if (!rc) rc = ensure_copy_stream(s);
+    if (rc) return rc;
+    const uint8_t *d_u8 = x;
+    if (x_on_host) {
+        rc = s->u8_in.ensure(samples);
+        if (rc) return rc;
+        if (s->u8_read_pending) BASIC_HIP_TRY(hipStreamWaitEvent(s->copy, s->u8_free, 0));
+        BASIC_HIP_TRY(hipMemcpyAsync(s->u8_in.p, x, samples, hipMemcpyHostToDevice, s->copy));
+        BASIC_HIP_TRY(hipEventRecord(s->x_ready, s->copy));
+        BASIC_HIP_TRY(hipStreamWaitEvent(st, s->x_ready, 0));
+        d_u8 = s->u8_in.as<uint8_t>();
+    }
+    if (s->x_read_pending) BASIC_HIP_TRY(hipStreamWaitEvent(st, s->x_free, 0));
+    rc = basic_image_u8_to_f32_dev(d_u8, layout, batch, s->x_channels, h, w, s->d_x.as<float>(), st);
+    if (rc) return rc;
+    if (x_on_host) {
+        BASIC_HIP_TRY(hipEventRecord(s->u8_free, st));
+        s->u8_read_pending = true;
+    }
+    return encode_body(s, s->d_x.as<float>(), true, batch, h, w, out, out_capacity, out_len, st);
+}
+
 // framing: merge_bytes([z body, y body], num_segments=2) with write_body bodies (bytes_ops.py:19-33)
 extern "C" int basic_hp_encode_result(basic_hp_session *s, uint8_t *out, int64_t out_capacity, int64_t *out_len)
 {
@@ -615,11 +673,11 @@ extern "C" int basic_hp_decoded_shape(const basic_hp_session *s, const uint8_t *
     return BASIC_OK;
 }
 
-extern "C" int basic_hp_decode_images(basic_hp_session *s, const uint8_t *data, int64_t len, float *d_xhat,
-                                      int64_t xhat_capacity_floats, void *hip_stream)
+namespace {
+
+// a decode call: the reconstruction goes to d_xhat (float32 on the device), enqueued on `st`
+int decode_body(basic_hp_session *s, const uint8_t *data, int64_t len, float *d_xhat, int64_t xhat_capacity_floats, hipStream_t st)
 {
-    BASIC_REQUIRE(s && d_xhat, "hp_decode_images: bad argument");
-    hipStream_t st = as_stream(hip_stream);
     WavesGuard guard(s->rans_waves, s->use_token);
     Body z, y;
     int rc = split_bodies(data, len, s->lanes, &z, &y);
@@ -715,4 +773,45 @@ extern "C" int basic_hp_decode_images(basic_hp_session *s, const uint8_t *data, 
     rc = run_chain(s, s->g_s, s->d_y.as<float>(), batch, yh, yw, nullptr, d_xhat, nullptr, nullptr, st);
     const int rc2 = phase.close();
     return rc ? rc : rc2;
+}
+
+}  // namespace
+
+extern "C" int basic_hp_decode_images(basic_hp_session *s, const uint8_t *data, int64_t len, float *d_xhat,
+                                      int64_t xhat_capacity_floats, void *hip_stream)
+{
+    BASIC_REQUIRE(s && d_xhat, "hp_decode_images: bad argument");
+    return decode_body(s, data, len, d_xhat, xhat_capacity_floats, as_stream(hip_stream));
+}
+
+extern "C" int basic_hp_decode_images_u8(basic_hp_session *s, const uint8_t *data, int64_t len, int layout, uint8_t *xhat,
+                                         int xhat_on_host, int64_t xhat_capacity_bytes, void *hip_stream)
+{
+    BASIC_REQUIRE(s && xhat, "hp_decode_images_u8: bad argument");
+    BASIC_REQUIRE(layout == BASIC_IMAGE_CHW || layout == BASIC_IMAGE_HWC, "hp_decode_images_u8: layout is BASIC_IMAGE_CHW or BASIC_IMAGE_HWC");
+    int batch = 0, channels = 0, h = 0, w = 0;
+    int rc = basic_hp_decoded_shape(s, data, len, &batch, &channels, &h, &w);
+    if (rc) return rc;
+    BASIC_REQUIRE(batch >= 1 && channels >= 1 && h >= 1 && w >= 1, "hp_decode_images_u8: the stream states an empty picture");
+    const int64_t samples = static_cast<int64_t>(batch) * channels * h * w;
+    BASIC_REQUIRE(samples <= xhat_capacity_bytes, "hp_decode_images_u8: output buffer too small");
+    hipStream_t st = as_stream(hip_stream);
+    rc = s->d_xhat.ensure(sizeof(float) * static_cast<size_t>(samples));
+    if (!rc && xhat_on_host) rc = s->u8_out.ensure(static_cast<size_t>(samples));
+    if (!rc) rc = ensure_copy_stream(s);
+    if (rc) return rc;
+    // the previous call's conversion out of d_xhat may have run on another stream
+    if (s->xhat_read_pending) BASIC_HIP_TRY(hipStreamWaitEvent(st, s->xhat_free, 0));
+    rc = decode_body(s, data, len, s->d_xhat.as<float>(), samples, st);
+    if (rc) return rc;
+    uint8_t *d_u8 = xhat_on_host ? s->u8_out.as<uint8_t>() : xhat;
+    rc = basic_image_f32_to_u8_dev(s->d_xhat.as<float>(), batch, channels, h, w, layout, d_u8, st);
+    if (rc) return rc;
+    BASIC_HIP_TRY(hipEventRecord(s->xhat_free, st));
+    s->xhat_read_pending = true;
+    if (xhat_on_host) {   // u8_out is read by this copy alone, and the copy is over when the call returns
+        BASIC_HIP_TRY(hipMemcpyAsync(xhat, d_u8, static_cast<size_t>(samples), hipMemcpyDeviceToHost, st));
+        BASIC_HIP_TRY(hipStreamSynchronize(st));
+    }
+    return BASIC_OK;
 }

@@ -473,6 +473,9 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                 return out
             if data.device != self.device:
                 data = data.to(device=self.device)
+            if data.dtype == torch.uint8:   # an 8-bit image batch: uploaded as bytes, converted in front of the first layer
+                from ...nn import kernels as K
+                data = K.image_u8_to_f32(data)
             node_dict = self._node_generate_process(**self._get_default_node_dict(force_add_default_dynamic_nodes=True, **kwargs))
             input_dict = {self.DEFAULT_INPUT_NODE_NAME: data, **node_dict}
             prior_dict = dict() if prior is None else {self.DEFAULT_INPUT_NODE_NAME: dict(prior=prior)}
@@ -489,12 +492,17 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             bodies = [b.result() if hasattr(b, "result") else b for b in bodies]
             return merge_bytes(bodies, num_segments=len(nodes))
 
-    def decode(self, data, *args, prior=None, **kwargs):
+    def decode(self, data, *args, prior=None, output_dtype=None, **kwargs):
+        """``output_dtype``: None / torch.float32 -- the reconstruction as the graph gives it; torch.uint8 -- the picture,
+        ``nan_to_num(x, nan=0).clamp(0, 1).mul(255).round()`` as bytes, converted on the device.  The keyword is the caller's
+        wish about the RESULT: it is not one of ``kwargs``, so it neither changes the path a call takes nor reaches a node generator."""
+        if output_dtype not in (None, torch.float32, torch.uint8):
+            raise TypeError(f"output_dtype is torch.float32 or torch.uint8, not {output_dtype}")
         with torch.no_grad():
             sess = self._fused_session(kwargs, prior) if not args else None
             if sess is not None:
                 with self.profiler.start_time_profile("decode_fused"):
-                    return sess.decode(data, device=self.device)
+                    return sess.decode(data, device=self.device, output_dtype=output_dtype or torch.float32)
             node_dict = self._node_generate_process(**self._get_default_node_dict(force_add_default_dynamic_nodes=True, **kwargs))
             nodes = self._coded_nodes()
             # coders that read their stream through the buffer protocol get it in place; others get bytes
@@ -506,7 +514,11 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                 input_dict[self.DEFAULT_INPUT_NODE_NAME] = b""
             with self.profiler.start_time_profile("decode_generative"):
                 data_dict, _ = self._generative_process(input_dict, prior_dict=prior_dict, **node_dict)
-            return data_dict[self.DEFAULT_INPUT_NODE_NAME]
+            out = data_dict[self.DEFAULT_INPUT_NODE_NAME]
+            if output_dtype == torch.uint8:
+                from ...nn import kernels as K
+                out = K.image_f32_to_u8(out)
+            return out
 
     # ---- coalesced items: N batch-1 items coded in chip-filling calls, every item keeping the bytes of its own batch-1 call
     last_items_calls = 0   # encode() / decode() calls the last encode_items() / decode_items() made
@@ -557,8 +569,14 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                 out[chunk[0]] = self.encode(items[chunk[0]], *args, **kwargs)
                 continue
             first = items[chunk[0]]
-            # the chunk's ONE device batch, filled item by item on the current stream (no host-side stack of the items)
-            batch = torch.empty((len(chunk),) + tuple(first.shape[1:]), dtype=first.dtype, device=self.device)
+            # the chunk's ONE device batch, filled item by item on the current stream (no host-side stack of the items); uint8 items
+            # whose memory is [H][W][C], as an image decoder leaves them, are gathered in that order (plain copies) and converted once
+            from ...nn.kernels import image_layout_of
+            if first.dtype == torch.uint8 and all(image_layout_of(items[i]) == "hwc" for i in chunk):
+                _, C, H, W = first.shape
+                batch = torch.empty((len(chunk), H, W, C), dtype=first.dtype, device=self.device).permute(0, 3, 1, 2)
+            else:
+                batch = torch.empty((len(chunk),) + tuple(first.shape[1:]), dtype=first.dtype, device=self.device)
             for j, i in enumerate(chunk):
                 batch[j:j + 1].copy_(items[i], non_blocking=True)
             data = self.encode(batch)
@@ -567,7 +585,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                 out[i] = one
         return out
 
-    def decode_items(self, strings, *args, max_batch=None, **kwargs) -> List[torch.Tensor]:
+    def decode_items(self, strings, *args, max_batch=None, output_dtype=None, **kwargs) -> List[torch.Tensor]:
         """N batch-1 strings -> their N reconstructions ([1, C, H, W] views of the batches' outputs, in input order), each equal to
         ``self.decode(string)``.  Strings share a call when the shapes their own headers state agree on every node (a body without
         a header, the AR body under an aligned prior, follows the others)."""
@@ -586,10 +604,10 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         for chunk in chunks:
             self.last_items_calls += 1
             if len(chunk) == 1:
-                out[chunk[0]] = self.decode(strings[chunk[0]], *args, **kwargs)
+                out[chunk[0]] = self.decode(strings[chunk[0]], *args, output_dtype=output_dtype, **kwargs)
                 continue
             mergers = [(lambda bodies, c=c, ctx=ctx: c.merge_items(bodies, **ctx)) for c, ctx in framing]
-            rec = self.decode(item_framing.merge_codec_strings([strings[i] for i in chunk], mergers))
+            rec = self.decode(item_framing.merge_codec_strings([strings[i] for i in chunk], mergers), output_dtype=output_dtype)
             for j, i in enumerate(chunk):
                 out[i] = rec[j:j + 1]
         return out

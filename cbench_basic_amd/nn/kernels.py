@@ -524,6 +524,70 @@ def unframe_streams(data: bytes, out=None):
     return words[: int(word_off[-1])], word_off, (h.value, w.value)
 
 
+IMAGE_LAYOUTS = {"chw": _lib.IMAGE_CHW, "hwc": _lib.IMAGE_HWC}   # BASIC_IMAGE_*
+
+
+def image_layout_of(t):
+    """The memory order of a ``[B, C, H, W]`` tensor, from its shape and strides alone: ``"chw"`` when it is contiguous,
+    ``"hwc"`` when its memory is ``[B][H][W][C]`` (``torch.channels_last``, or what ``torch.from_numpy(a).permute(2, 0, 1)[None]``
+    gives for a decoder's array), ``None`` for anything else (the caller then makes it contiguous).  A dimension of size 1 fits
+    any stride; with one channel both readings hold and ``"chw"`` is returned."""
+    if t.dim() != 4:
+        return None
+    shape, stride = tuple(t.shape), tuple(t.stride())
+    if 0 in shape:
+        return None
+    B, C, H, W = shape
+    for name, want in (("chw", (C * H * W, H * W, W, 1)), ("hwc", (H * W * C, 1, W * C, C))):
+        if all(n == 1 or s == e for n, s, e in zip(shape, stride, want)):
+            return name
+    return None
+
+
+def _image_u8(t):
+    """(tensor, layout name) of a uint8 [B, C, H, W] tensor as the library reads it: as it lies, or made contiguous."""
+    if t.dim() != 4:
+        raise ValueError(f"an image batch is [B, C, H, W], not {tuple(t.shape)}")
+    layout = image_layout_of(t)
+    if layout is None:
+        t, layout = t.contiguous(), "chw"
+    return t, layout
+
+
+def image_u8_to_f32(t):
+    """uint8 [B, C, H, W] on the GPU, contiguous or with [B][H][W][C] memory (image_layout_of) -> float32 [B, C, H, W],
+    ``t.float().div(255)`` exactly (basic_image_u8_to_f32_dev)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        _dev(t)
+    if t.dtype != torch.uint8:
+        raise TypeError(f"expected torch.uint8, got {t.dtype}")
+    t, layout = _image_u8(t)
+    B, C, H, W = t.shape
+    with torch.cuda.device(t.device):
+        out = torch.empty((B, C, H, W), device=t.device, dtype=torch.float32)
+        _lib.check(_lib.lib().basic_image_u8_to_f32_dev(t.data_ptr(), IMAGE_LAYOUTS[layout], B, C, H, W, out.data_ptr(), _stream()))
+    return out
+
+
+def image_f32_to_u8(t, layout="chw"):
+    """float32 [B, C, H, W] on the GPU -> uint8 [B, C, H, W]: ``torch.nan_to_num(t, nan=0.0).clamp(0, 1).mul(255).round()``
+    as bytes (basic_image_f32_to_u8_dev).  layout "hwc": the result's memory is [B][H][W][C] (a permuted view, ready for an
+    image encoder after ``.permute(0, 2, 3, 1)``)."""
+    if layout not in IMAGE_LAYOUTS:
+        raise ValueError(f"layout is 'chw' or 'hwc', not {layout!r}")
+    t = _dev(t, torch.float32)
+    if t.dim() != 4:
+        raise ValueError(f"an image batch is [B, C, H, W], not {tuple(t.shape)}")
+    B, C, H, W = t.shape
+    with torch.cuda.device(t.device):
+        if layout == "hwc":
+            out = torch.empty((B, H, W, C), device=t.device, dtype=torch.uint8).permute(0, 3, 1, 2)
+        else:
+            out = torch.empty((B, C, H, W), device=t.device, dtype=torch.uint8)
+        _lib.check(_lib.lib().basic_image_f32_to_u8_dev(t.data_ptr(), B, C, H, W, IMAGE_LAYOUTS[layout], out.data_ptr(), _stream()))
+    return out
+
+
 class HyperpriorSession:
     """basic_hp_session_*: the fused compress / decompress entry points of the plain hyperprior latent graph (one C call
     per batch instead of a Python walk over the graph).  Borrows the layer plans and table sets it is given (kept alive
@@ -564,13 +628,23 @@ class HyperpriorSession:
         _lib.check(_lib.lib().basic_hp_session_set_transform_token(self._h, int(enable)))
 
     def encode(self, x) -> bytes:
-        """x: float32 [B, C, H, W], on the GPU or on the host (uploaded inside the call; pinned memory goes at DMA rate)."""
-        if x.dtype != torch.float32:
-            raise TypeError(f"expected float32, got {x.dtype}")
-        x = x.contiguous()
-        B, C, H, W = x.shape
+        """x: float32 or uint8 [B, C, H, W], on the GPU or on the host (uploaded inside the call; pinned memory goes at DMA rate).
+        A uint8 batch is read as it lies when it is contiguous or its memory is [B][H][W][C] (image_layout_of), uploaded as
+        bytes and converted on the device: the bytes written are those of ``x.float().div(255)``."""
+        if x.dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"expected float32 or uint8, got {x.dtype}")
         n = ctypes.c_int64()
-        _lib.check(_lib.lib().basic_hp_encode_images(self._h, x.data_ptr(), 0 if x.is_cuda else 1, B, H, W, None, 0, ctypes.byref(n), _stream()))
+        if x.dtype == torch.uint8:
+            x, layout = _image_u8(x)
+            B, C, H, W = x.shape
+            if C != self._keep[0][0].cin:
+                raise ValueError(f"the analysis transform expects {self._keep[0][0].cin} input channels, got {C}")
+            _lib.check(_lib.lib().basic_hp_encode_images_u8(self._h, x.data_ptr(), 0 if x.is_cuda else 1, IMAGE_LAYOUTS[layout], B, H, W,
+                                                            None, 0, ctypes.byref(n), _stream()))
+        else:
+            x = x.contiguous()
+            B, C, H, W = x.shape
+            _lib.check(_lib.lib().basic_hp_encode_images(self._h, x.data_ptr(), 0 if x.is_cuda else 1, B, H, W, None, 0, ctypes.byref(n), _stream()))
         # the final bytes object is allocated once at its exact size and the streams are framed straight into it
         api = ctypes.pythonapi
         api.PyBytes_FromStringAndSize.restype, api.PyBytes_FromStringAndSize.argtypes = ctypes.py_object, [ctypes.c_char_p, ctypes.c_ssize_t]
@@ -579,14 +653,29 @@ class HyperpriorSession:
         _lib.check(_lib.lib().basic_hp_encode_result(self._h, api.PyBytes_AsString(out), n.value, None))
         return out
 
-    def decode(self, data, device=None):
+    def decode(self, data, device=None, output_dtype=torch.float32, out=None):
+        """The reconstruction [B, C, H, W] on the GPU: float32 (the un-clamped output of g_s), or with
+        ``output_dtype=torch.uint8`` the picture, ``clamp(0, 1).mul(255).round()`` of it converted on the device.
+        ``out`` (uint8 only): a uint8 [B, C, H, W] tensor to fill instead, contiguous or with [B][H][W][C] memory, on the GPU or
+        on the host (the bytes are then copied inside the call, one per sample; it returns with them in place)."""
+        if output_dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"output_dtype is torch.float32 or torch.uint8, not {output_dtype}")
+        if out is not None and output_dtype != torch.uint8:
+            raise TypeError("out= takes a uint8 tensor and output_dtype=torch.uint8")
         buf = np.frombuffer(data, dtype=np.uint8)
         b, c, h, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         _lib.check(_lib.lib().basic_hp_decoded_shape(self._h, buf.ctypes.data, buf.size, ctypes.byref(b), ctypes.byref(c),
                                                      ctypes.byref(h), ctypes.byref(w)))
-        out = torch.empty((b.value, c.value, h.value, w.value), device=device or torch.device("cuda", torch.cuda.current_device()),
-                          dtype=torch.float32)
-        _lib.check(_lib.lib().basic_hp_decode_images(self._h, buf.ctypes.data, buf.size, out.data_ptr(), out.numel(), _stream()))
+        shape = (b.value, c.value, h.value, w.value)
+        if out is None:
+            out = torch.empty(shape, device=device or torch.device("cuda", torch.cuda.current_device()), dtype=output_dtype)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or image_layout_of(out) is None:
+            raise ValueError(f"out= must be a uint8 tensor of shape {shape} with [B][C][H][W] or [B][H][W][C] memory")
+        if output_dtype == torch.uint8:
+            _lib.check(_lib.lib().basic_hp_decode_images_u8(self._h, buf.ctypes.data, buf.size, IMAGE_LAYOUTS[image_layout_of(out)],
+                                                            out.data_ptr(), 0 if out.is_cuda else 1, out.numel(), _stream()))
+        else:
+            _lib.check(_lib.lib().basic_hp_decode_images(self._h, buf.ctypes.data, buf.size, out.data_ptr(), out.numel(), _stream()))
         return out
 
 

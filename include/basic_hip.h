@@ -416,6 +416,48 @@ int basic_hp_session_set_transform_token(basic_hp_session *s, int enable);
 void basic_hp_session_destroy(basic_hp_session *s);
 
 /* ======================================================================================
+ * 8b. 8-bit images (csrc/image.hip): uint8 in, uint8 out, converted on the device in front of the unchanged first layer
+ *    and behind the unchanged last one.  Replaces the host-side ingest of
+ *    cbench/data/datasets/torchvision_datasets.py:80-88 (PIL -> ToTensor: permute to CHW, float32, divide by 255) and the
+ *    clamp / scale / round / cast a caller runs on a reconstruction before it writes a picture.
+ *      uint8 -> float32:  f = float32(u) / float32(255), correctly rounded (a 256-entry table of host-computed quotients;
+ *                         a reciprocal multiply is NOT equal to it for all 256 inputs).
+ *      float32 -> uint8:  q = uint8(rint(min(max(x, 0), 1) * 255.0f)), rint = round-half-to-even, one fp32 multiply, NaN -> 0:
+ *                         torch.nan_to_num(x, nan=0.0).clamp(0, 1).mul(255).round().to(torch.uint8) evaluated on the CPU.
+ *    The float side is always [batch][channels][h][w]; the uint8 side is BASIC_IMAGE_CHW, [batch][channels][h][w], or
+ *    BASIC_IMAGE_HWC, [batch][h][w][channels] (what every image decoder delivers).  Element offsets are 64-bit.
+ *    Any channels, h, w >= 1 and any byte alignment of the uint8 pointer; the float pointer must be float-aligned.
+ *    A call takes the wide path (one dword of four samples per lane against 16-byte float accesses) when the uint8
+ *    pointer is 4-byte and the float pointer 16-byte aligned and, for BASIC_IMAGE_HWC, channels is 3 or 4 and h * w a
+ *    multiple of 4 (a lane then owns four consecutive pixels: `channels` dwords against one 16-byte vector per plane);
+ *    the last batch * channels * h * w % 4 samples of a BASIC_IMAGE_CHW call and every other call go sample by sample.
+ *    Both paths give the same values.  BASIC_ERR_INVALID, before any launch, for a non-positive dimension, a null
+ *    pointer, an unknown layout, a misaligned float pointer or more than 2^40 samples.
+ * ==================================================================================== */
+#define BASIC_IMAGE_CHW 0
+#define BASIC_IMAGE_HWC 1
+/* Ingest (torchvision_datasets.py:80-88 on the device): d_src uint8 in `layout`, d_dst float32 [batch][channels][h][w]. */
+int basic_image_u8_to_f32_dev(const uint8_t *d_src, int layout, int batch, int channels, int h, int w,
+                              float *d_dst, void *hip_stream);
+/* The way back (the caller's x.clamp(0, 1).mul(255).round().byte()): d_src float32 [batch][channels][h][w], d_dst uint8 in
+ * `layout`. */
+int basic_image_f32_to_u8_dev(const float *d_src, int batch, int channels, int h, int w, int layout,
+                              uint8_t *d_dst, void *hip_stream);
+/* basic_hp_encode_images for a uint8 batch in `layout` (channels = the first layer's input channels), on the device
+ * (x_on_host == 0) or in host memory: a host batch is copied as uint8 -- a quarter of the float bytes -- into a staging
+ * buffer of the session on its copy stream and converted on hip_stream into the buffer the first layer reads; from there
+ * on the call IS basic_hp_encode_images (same bytes, same basic_hp_encode_result, same lane settings).  The caller may
+ * change hip_stream between calls. */
+int basic_hp_encode_images_u8(basic_hp_session *s, const uint8_t *x, int x_on_host, int layout, int batch, int h, int w,
+                              uint8_t *out, int64_t out_capacity, int64_t *out_len, void *hip_stream);
+/* basic_hp_decode_images into a float buffer of the session, converted on hip_stream into xhat: uint8 in `layout`, on the
+ * device (xhat_on_host == 0: enqueued, as basic_hp_decode_images) or in host memory (converted into a device staging
+ * buffer and copied; the call returns with the picture complete in xhat).  xhat_capacity_bytes smaller than the
+ * basic_hp_decoded_shape of the stream: BASIC_ERR_INVALID, nothing launched. */
+int basic_hp_decode_images_u8(basic_hp_session *s, const uint8_t *data, int64_t len, int layout,
+                              uint8_t *xhat, int xhat_on_host, int64_t xhat_capacity_bytes, void *hip_stream);
+
+/* ======================================================================================
  * 9. Persistent scan-line AR coding loop (csrc/scanline.hip): ONE launch walks all H*W coding steps of
  *    TopoGroupPGMPriorCoder._encode_with_pgm / _pgm_generate (pgm_coder.py:912-981) for the "scanline" topo groups
  *    (one position per group, raster order) with one channel group: masked k x k context convolution at the coded

@@ -19,7 +19,21 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main():
+def save_reconstructions(codec, batches, directory):
+    """Decompresses every batch as 8-bit pictures (``output_dtype=torch.uint8``: converted on the GPU, one byte per sample
+    downloaded) and writes one PNG per image, ``00000.png`` ... in dataset order.  -> the files written."""
+    from PIL import Image
+    os.makedirs(directory, exist_ok=True)
+    files = []
+    for b in batches:
+        pictures = codec.decompress(codec.compress(b), output_dtype=torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
+        for a in pictures:
+            files.append(os.path.join(directory, f"{len(files):05d}.png"))
+            Image.fromarray(a[..., 0] if a.shape[-1] == 1 else a).save(files[-1])
+    return files
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--codec", choices=["hyperprior", "topogroup", "basic"], default="hyperprior")
     ap.add_argument("--method", default="checkerboard", help="topo-group pattern of --codec topogroup")
@@ -54,8 +68,13 @@ def main():
                          "decoder wavefront per row, batch * H <= 64; band: any batch and height; both raise where the call does not fit)")
     ap.add_argument("--metrics", nargs="+", choices=["psnr", "ms-ssim"], default=["psnr"],
                     help="distortion metrics of the reconstruction (ms-ssim needs images with both sides above 160)")
+    ap.add_argument("--uint8", action="store_true",
+                    help="the datasets yield 8-bit images (an image file's own bytes; synthetic: torch.randint): uploaded as bytes and "
+                         "converted on the GPU; original_length, compression_ratio and speed_* then count one byte per sample")
+    ap.add_argument("--save-reconstructions", default=None, metavar="DIR",
+                    help="after the run, decompress every item as an 8-bit picture and write one PNG per image into DIR")
     ap.add_argument("--out", required=True)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.stream_rows and args.codec != "basic":
         ap.error("--stream-rows needs --codec basic")
     if args.scanline_decode_schedule != "auto" and not args.stream_rows:
@@ -75,10 +94,11 @@ def main():
     from cbench_basic_amd import presets
     from cbench_basic_amd.benchmark import BasicLosslessCompressionBenchmark, PytorchBatchedDistortion
     from cbench_basic_amd.data import ImageFolderDataset, RandomImageDataset, batched
+    dtype = torch.uint8 if args.uint8 else torch.float32
     if args.images:
-        ds = ImageFolderDataset(args.images)
+        ds = ImageFolderDataset(args.images, dtype=dtype)
     else:
-        ds = RandomImageDataset(num=args.synthetic or 8, size=(3, args.height or args.size, args.width or args.size))
+        ds = RandomImageDataset(num=args.synthetic or 8, size=(3, args.height or args.size, args.width or args.size), dtype=dtype)
     batches = list(batched(ds, args.batch_size))
     builders = dict(hyperprior=lambda: presets.hyperprior_codec(stream_lanes=args.stream_lanes), basic=lambda **kw: presets.basic_codec(stream_lanes=args.stream_lanes, stream_rows=args.stream_rows,
                                                               scanline_decode_schedule=args.scanline_decode_schedule, **kw),
@@ -130,6 +150,9 @@ def main():
     metrics = bench.run_benchmark(ignore_exist_metrics=True)
     bench.close()
     print(json.dumps(metrics, indent=1))
+    if args.save_reconstructions:   # at the complexity and rate level the run ended on
+        files = save_reconstructions(codec, batches, args.save_reconstructions)
+        print(f"{len(files)} reconstructions written to {args.save_reconstructions}")
 
 
 if __name__ == "__main__":
