@@ -5,4 +5,4 @@ reference's artefacts (``metrics.csv``, ``metrics_2d.csv``, BD-rate), so that ``
 post-processing keeps working.  Training, caching, multiprocessing pools and logging backends are not part of it.
 """
 from .basic_benchmark import BasicLosslessCompressionBenchmark  # noqa: F401
-from .metrics import BJDeltaMetric, MetricLogger, PytorchBatchedDistortion, bj_delta  # noqa: F401
+from .metrics import BJDeltaMetric, MetricLogger, PytorchBatchedDistortion, bj_delta, psnr_from_sse  # noqa: F401

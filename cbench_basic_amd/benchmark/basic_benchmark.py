@@ -19,6 +19,10 @@ AR steps run beside another item's transforms.  Per-item times are the latencies
 up to that many items of one shape (``codec.compress_items`` / ``decompress_items``); every item keeps the bytes and the
 reconstruction of its own batch-1 call, the metrics are logged per item with the keys of the sequential pass, and a call's time is
 shared equally among its items.
+
+``metrics_on_uint8`` (not in the reference; INTEGRATION.md, "8-bit images"): the distortion is taken from the 8-bit picture the codec
+hands out -- ``codec.decompress(compressed, output_dtype=torch.uint8)``, converted inside the timed region -- against the 8-bit item
+(a float item: quantised once), as exact integers; ``on_reconstruction`` receives that very picture after the pass.
 """
 import copy
 import csv
@@ -38,7 +42,8 @@ class BasicLosslessCompressionBenchmark:
                  nn_codec_use_forward_pass=False, nn_codec_forward_pass_skip_compression=False,
                  testing_variable_rate_levels=None, testing_variable_rate_bj_delta_metric=None,
                  testing_complexity_levels=None, force_testing_device="cuda", output_dir=None, num_repeats=1,
-                 num_testing_workers=0, codec_builder=None, worker_transform_token=None, testing_coalesce_items=0, **kwargs):
+                 num_testing_workers=0, codec_builder=None, worker_transform_token=None, testing_coalesce_items=0,
+                 metrics_on_uint8=False, on_reconstruction=None, **kwargs):
         self.codec = codec
         self.dataloader = dataloader
         self.distortion_metric = distortion_metric
@@ -66,6 +71,16 @@ class BasicLosslessCompressionBenchmark:
         self.testing_coalesce_items = int(testing_coalesce_items or 0)
         if self.testing_coalesce_items < 0:
             raise ValueError("testing_coalesce_items must be >= 0")
+        # the 8-bit picture is what is measured: items and reconstructions meet the metric as uint8 ("8-bit images")
+        self.metrics_on_uint8 = bool(metrics_on_uint8)
+        # on_reconstruction(level_prefix, item_index, picture_u8): the uint8 [B, C, H, W] tensor the metric saw for dataset item
+        # `item_index` (a batch-1 item: once per image), called for every item once the pass over the dataset is over and its wall
+        # time taken, in dataset order, from the calling thread -- whatever the route and the workers' order
+        self.on_reconstruction = on_reconstruction
+        if on_reconstruction is not None and not self.metrics_on_uint8:
+            raise ValueError("on_reconstruction hands out the 8-bit picture the metric saw: it needs metrics_on_uint8=True")
+        self._level_prefix = ""
+        self._pictures = {}
         self._pool = None
 
     # ---- files (base.py:41-52)
@@ -97,14 +112,50 @@ class BasicLosslessCompressionBenchmark:
         if torch.cuda.is_available():
             torch.cuda.current_stream().synchronize()
 
+    @staticmethod
+    def _to_f32(x):
+        """An 8-bit batch as the float graph takes it: u8 / 255 (the library's kernel on the GPU)."""
+        if x.is_cuda:
+            from ..nn import kernels as K
+            return K.image_u8_to_f32(x)
+        return x.float().div(255)
+
+    @staticmethod
+    def _to_u8(x):
+        """A float batch as the 8-bit picture of it (the library's kernel on the GPU, its definition in torch ops on the CPU)."""
+        if x.is_cuda:
+            from ..nn import kernels as K
+            return K.image_f32_to_u8(x.float())
+        return torch.nan_to_num(x.float(), nan=0.0).clamp(0, 1).mul(255).round().to(torch.uint8)
+
     def _target(self, data):
         """What a reconstruction of ``data`` is compared with: the item on the testing device; an 8-bit item converted ONCE there
-        (u8 / 255 by the library's kernel), so that its distortion is the one of the same item given as float32."""
+        (u8 / 255 by the library's kernel), so that its distortion is the one of the same item given as float32.  With
+        ``metrics_on_uint8`` it is the 8-bit item itself, and a float item quantised ONCE."""
         target = data.to(self.force_testing_device) if self.force_testing_device else data
-        if isinstance(target, torch.Tensor) and target.dtype == torch.uint8:
-            from ..nn import kernels as K
-            target = K.image_u8_to_f32(target)
+        if not isinstance(target, torch.Tensor):
+            return target
+        if self.metrics_on_uint8:
+            return target if target.dtype == torch.uint8 else self._to_u8(target)
+        if target.dtype == torch.uint8:
+            target = self._to_f32(target)
         return target
+
+    def _forward_input(self, data_input, data_target):
+        """The forward pass is the float graph: an 8-bit item enters it converted."""
+        if getattr(data_input, "dtype", None) != torch.uint8:
+            return data_input
+        return self._to_f32(data_target) if self.metrics_on_uint8 else data_target
+
+    def _decompress(self, codec, compressed):
+        return codec.decompress(compressed, output_dtype=torch.uint8) if self.metrics_on_uint8 else codec.decompress(compressed)
+
+    def _deliver_pictures(self):
+        """After a pass, outside its timed regions: every item's picture to ``on_reconstruction``, in dataset order."""
+        pictures, self._pictures = self._pictures, {}
+        if self.on_reconstruction is not None:
+            for i in sorted(pictures):
+                self.on_reconstruction(self._level_prefix, i, pictures[i])
 
     def _run_step(self, step, data, metric_logger, codec=None, distortion_metric=None):
         codec = self.codec if codec is None else codec
@@ -116,13 +167,12 @@ class BasicLosslessCompressionBenchmark:
         metric_logger.update(original_length=original_length)
         dm = self.distortion_metric if distortion_metric is None else distortion_metric
         if self.nn_codec_use_forward_pass and hasattr(codec, "forward_estimate_bitlen"):
-            # the forward pass is the float graph: an 8-bit item enters it converted
-            decompressed, compressed_length = codec.forward_estimate_bitlen(data_target if getattr(data_input, "dtype", None) == torch.uint8 else data_input)
+            decompressed, compressed_length = codec.forward_estimate_bitlen(self._forward_input(data_input, data_target))
             compressed_length = float(compressed_length)
             metric_logger.update(compression_ratio_nn_forward=compressed_length / original_length,
                                  compressed_length_nn_forward=compressed_length)
             if dm is not None:
-                dm(decompressed, data_target)
+                dm(self._to_u8(decompressed) if self.metrics_on_uint8 else decompressed, data_target)
             if self.nn_codec_forward_pass_skip_compression:
                 return
         self._sync()
@@ -136,7 +186,7 @@ class BasicLosslessCompressionBenchmark:
                              speed_compress=original_length / time_compress / 1024 / 1024)
         if not self.skip_decompress:
             t0 = time.time()
-            decompressed = codec.decompress(compressed)
+            decompressed = self._decompress(codec, compressed)   # metrics_on_uint8: the picture is the product, converted in here
             self._sync()
             time_decompress = time.time() - t0
             metric_logger.update(time_decompress=time_decompress * 1000,
@@ -145,6 +195,8 @@ class BasicLosslessCompressionBenchmark:
                                  speed_total=original_length / (time_compress + time_decompress) / 1024 / 1024)
             if dm is not None:
                 dm(decompressed, data_target)
+            if self.on_reconstruction is not None:
+                self._pictures[step] = decompressed
 
     def _worker_pool(self, first_item=None, batch=None):
         """The stream workers and their codec replicas, brought to the main codec's weights, levels and tables.  ``batch``: the
@@ -227,11 +279,11 @@ class BasicLosslessCompressionBenchmark:
             records[i] = (OrderedDict(original_length=L), [])
         if self.nn_codec_use_forward_pass and hasattr(codec, "forward_estimate_bitlen"):
             for i, d, t, L in zip(chunk, data, targets, lengths):   # the forward estimate stays one call per item
-                decompressed, compressed_length = codec.forward_estimate_bitlen(t if getattr(d, "dtype", None) == torch.uint8 else d)
+                decompressed, compressed_length = codec.forward_estimate_bitlen(self._forward_input(d, t))
                 compressed_length = float(compressed_length)
                 records[i][0].update(compression_ratio_nn_forward=compressed_length / L, compressed_length_nn_forward=compressed_length)
                 if dm is not None:
-                    records[i][1].append(dm(decompressed, t, cache_metrics=False))
+                    records[i][1].append(dm(self._to_u8(decompressed) if self.metrics_on_uint8 else decompressed, t, cache_metrics=False))
             if self.nn_codec_forward_pass_skip_compression:
                 return
         self._sync()
@@ -247,7 +299,8 @@ class BasicLosslessCompressionBenchmark:
                                  time_compress=time_compress * 1000, speed_compress=L / time_compress / 1024 / 1024)
         if not self.skip_decompress:
             t0 = time.time()
-            decompressed = codec.decompress_items(compressed, max_batch=n)
+            decompressed = codec.decompress_items(compressed, max_batch=n, output_dtype=torch.uint8) if self.metrics_on_uint8 \
+                else codec.decompress_items(compressed, max_batch=n)
             self._sync()
             time_decompress = (time.time() - t0) / n
             for i, L in zip(chunk, lengths):
@@ -257,6 +310,9 @@ class BasicLosslessCompressionBenchmark:
             if dm is not None:
                 for i, r in zip(chunk, dm.per_item(list(decompressed), targets, cache_metrics=False)):
                     records[i][1].append(r)
+            if self.on_reconstruction is not None:
+                for i, picture in zip(chunk, decompressed):
+                    self._pictures[i] = picture
 
     def _run_dataset_coalesced(self):
         from ..utils.item_framing import coalesce_chunks
@@ -304,6 +360,7 @@ class BasicLosslessCompressionBenchmark:
         if items:
             out["time_wall_dataset"] = wall * 1000
             out["speed_wall_dataset"] = n_bytes / wall / 1024 / 1024
+        self._deliver_pictures()
         return out
 
     def _run_dataset(self):
@@ -349,6 +406,7 @@ class BasicLosslessCompressionBenchmark:
         if n_items:
             out["time_wall_dataset"] = wall * 1000
             out["speed_wall_dataset"] = n_bytes / wall / 1024 / 1024
+        self._deliver_pictures()
         return out
 
     def close(self):
@@ -377,6 +435,7 @@ class BasicLosslessCompressionBenchmark:
                     self.codec.update_state()
                     if self.distortion_metric is not None:
                         self.distortion_metric.reset()
+                    self._level_prefix = "_".join(([f"sclevel{clevel}"] if clevel is not None else []) + ([f"vrlevel{rlevel}"] if rlevel is not None else []))
                     current = self._run_dataset()
                     if self.distortion_metric is not None:
                         current.update(**self.distortion_metric.collect_metrics())

@@ -37,9 +37,23 @@ class MetricLogger:
             self._cnt[k] = self._cnt.get(k, 0) + other._cnt[k]
 
 
+def psnr_from_sse(sse, samples, peak=255.0):
+    """PSNR in dB of ``samples`` samples whose squared errors sum to ``sse``: ``10 log10(peak^2 samples / sse)`` in float64, ``inf``
+    for ``sse == 0``.  Scalars give a float, arrays an array.  The sum of an 8-bit picture is an exact integer
+    (``nn/kernels.py::image_sse_u8``), so this is the only rounding between the picture and its PSNR."""
+    sse, samples = np.asarray(sse, dtype=np.float64), np.asarray(samples, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        out = 10.0 * np.log10(np.float64(peak) ** 2 * samples / sse)
+    return float(out) if out.ndim == 0 else out
+
+
 class PytorchBatchedDistortion:
     """pytorch_distortion.py:21-68: ``"psnr"`` (of the mean squared error over the whole batch) and ``"ms-ssim"`` (mean over the
-    batch; benchmark/ms_ssim.py restates the absent pytorch_msssim package: parity-unpinned)."""
+    batch; benchmark/ms_ssim.py restates the absent pytorch_msssim package: parity-unpinned).
+
+    A pair of which BOTH sides are uint8 is measured as the 8-bit picture it is (not in the reference): the PSNR comes from the
+    exact integer sum of squared differences against a peak of 255 (``max_val`` must be 1.0, read as "full range", or 255), ms-ssim
+    from the pair converted to u8 / 255.  A pair with one float side takes the float path, as before."""
 
     def __init__(self, *args, metrics="psnr", max_val=1.0, **kwargs):
         self._metrics = metrics if isinstance(metrics, list) else [metrics]
@@ -57,7 +71,52 @@ class PytorchBatchedDistortion:
     def metrics(self):
         return self._metrics
 
+    # ---- both sides uint8: the 8-bit picture itself
+    @staticmethod
+    def _is_u8_pair(output, target):
+        return all(isinstance(t, torch.Tensor) and t.dtype == torch.uint8 for t in (output, target))
+
+    def _sse_u8(self, output, target):
+        """int64 [B, C] on the host: the exact sums of squared differences (the HIP kernel on the GPU, int64 torch ops on the CPU)."""
+        if self.max_val not in (1.0, 255):
+            raise ValueError(f"an 8-bit pair has a peak of 255: max_val is 1.0 (full range) or 255, not {self.max_val!r}")
+        if output.is_cuda:
+            from ..nn import kernels as K
+            return K.image_sse_u8(output, target).cpu()
+        return ((output.to(torch.int64) - target.to(torch.int64)) ** 2).sum((2, 3))
+
+    @staticmethod
+    def _ms_ssim_u8(output, target):
+        """[B] MS-SSIM of a uint8 pair: the pair as u8 / 255 against a data range of 1."""
+        if output.is_cuda:
+            from ..nn import kernels as K
+            return K.ms_ssim_per_image_u8(output, target)
+        from .ms_ssim import ms_ssim   # image by image: a batched convolution may block its sums differently
+        return torch.stack([ms_ssim(output[i:i + 1].float().div(255), target[i:i + 1].float().div(255), data_range=1.0, size_average=False)[0]
+                            for i in range(target.shape[0])])
+
+    def _per_item_u8(self, output, target):
+        output = output[..., :target.shape[-2], :target.shape[-1]]  # make spatial size equal
+        cols = {}
+        if "psnr" in self._metrics:
+            sse = self._sse_u8(output, target).sum(1).tolist()
+            cols["psnr"] = [psnr_from_sse(s, target[0].numel()) for s in sse]
+        if "ms-ssim" in self._metrics:
+            cols["ms-ssim"] = self._ms_ssim_u8(output, target).tolist()
+        return cols
+
     def __call__(self, output, target, cache_metrics=True):
+        if self._is_u8_pair(output, target):
+            output = output[..., :target.shape[-2], :target.shape[-1]]  # make spatial size equal
+            result = {}
+            if "psnr" in self._metrics:   # of the whole batch: total sum over total samples
+                result["psnr"] = psnr_from_sse(int(self._sse_u8(output, target).sum()), target.numel())
+            if "ms-ssim" in self._metrics:
+                result["ms-ssim"] = float(self._ms_ssim_u8(output, target).mean())
+            result = {m: result[m] for m in self._metrics}
+            if cache_metrics:
+                self.metric_logger.update(**result)
+            return result
         output = output.type_as(target)[..., :target.shape[-2], :target.shape[-1]]  # make spatial size equal
         result = {}
         if "psnr" in self._metrics:
@@ -83,8 +142,15 @@ class PytorchBatchedDistortion:
             output = output[0] if len(output) == 1 else torch.cat(list(output))
         if isinstance(target, (list, tuple)):
             target = target[0] if len(target) == 1 else torch.cat(list(target))
-        output = output.type_as(target)[..., :target.shape[-2], :target.shape[-1]]  # make spatial size equal
         N = target.shape[0]
+        if self._is_u8_pair(output, target):
+            cols = self._per_item_u8(output, target)
+            results = [{m: cols[m][i] for m in self._metrics} for i in range(N)]
+            if cache_metrics:
+                for r in results:
+                    self.metric_logger.update(**r)
+            return results
+        output = output.type_as(target)[..., :target.shape[-2], :target.shape[-1]]  # make spatial size equal
         cols = {}
         if "psnr" in self._metrics:
             if output.is_cuda:

@@ -12,6 +12,9 @@
 // uint8 -> float32 reads the quotient u / 255 from a 256-entry table: the compiler evaluates float(u) / 255.0f (IEEE, correctly
 // rounded) when it builds the table in constant memory, a workgroup copies it to LDS once.  float32 -> uint8 is fmax / fmin /
 // one multiply / v_rndne; nothing is contracted into it.
+// The third entry measures such pictures: the exact per-channel sum of squared differences of two uint8 batches (further down).
+#include <utility>
+
 #include "common.h"
 
 using namespace basic;
@@ -210,6 +213,183 @@ extern "C" int basic_image_f32_to_u8_dev(const float *d_src, int batch, int chan
     if (done < s.total)
         hipLaunchKernelGGL(f32_to_u8_scalar_kernel, grid_for(s.total - done), dim3(kBlock), 0, st, d_src, d_dst, s.hwc, channels, s.pixels,
                            done, s.total);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+// ---- exact sum of squared differences of two uint8 batches ----------------------------------------------------------------
+// d_sse[b][c] = sum over the pixels of (a - b)^2.  Integers only: a lane sums at most 16 squares (<= 1,040,400) in 32 bits,
+// adds them to a 64-bit sum of its own, the sums meet by wave shuffles and one LDS word per wave, and a workgroup issues ONE
+// 64-bit atomic add per destination it walked, on counters the call has cleared: the same integers for any grid and order.
+//   plane : a workgroup walks one (image, channel) plane of both operands; operand X's sample p lies at base_X + p * step_X
+//           (CHW: step 1, HWC: step `channels`).  WIDE (both CHW -- or one channel -- and both pointers 4-byte aligned): the
+//           plane's whole dwords, one of four samples per lane and operand, four loads in flight; the up to three samples in
+//           front of the first whole dword and behind the last (h * w % 4 != 0: a plane does not start on a dword, and the dword
+//           around its edge holds samples of two channels or two images) go sample by sample into the sum they belong to.
+//           Not WIDE: every sample that way, any layout and alignment.
+//   run   : C = 3, 4, at least one operand HWC, h * w % 4 == 0, both pointers 4-byte aligned: a lane owns four consecutive
+//           pixels of an image: C whole dwords of an HWC operand, one dword of each plane of a CHW one; C sums per lane.
+//           Operand a is the HWC one (the sum is symmetric: the call swaps them).
+namespace {
+
+typedef unsigned long long u64;
+constexpr int kWaves = kBlock / 64;
+constexpr int kMaxGridY = 65535;
+
+__device__ __forceinline__ uint32_t sq_diff(uint32_t x, uint32_t y)
+{
+    const int d = static_cast<int>(x) - static_cast<int>(y);
+    return static_cast<uint32_t>(d * d);
+}
+
+// the four squared differences of two dwords of samples
+__device__ __forceinline__ uint32_t sq_diff4(uint32_t x, uint32_t y)
+{
+    return (sq_diff(x & 0xffu, y & 0xffu) + sq_diff((x >> 8) & 0xffu, (y >> 8) & 0xffu)) +
+           (sq_diff((x >> 16) & 0xffu, (y >> 16) & 0xffu) + sq_diff(x >> 24, y >> 24));
+}
+
+// the workgroup's sum, in every thread; `red` may be used again at once (the next call waits for this one's readers)
+__device__ __forceinline__ u64 block_sum(u64 v, u64 *red)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u64 s = 0;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) s += red[k];
+    return s;
+}
+
+// gridDim.x workgroups share a plane, blockIdx.y strides the planes; plane = image * channels + channel
+template <bool WIDE>
+__global__ __launch_bounds__(kBlock) void sse_plane_kernel(const uint8_t *__restrict__ a, int hwc_a, const uint8_t *__restrict__ b, int hwc_b,
+                                                            int64_t planes, int channels, int64_t pixels, u64 *__restrict__ sse)
+{
+    __shared__ u64 red[kWaves];
+    const int64_t lane = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x, lanes = static_cast<int64_t>(gridDim.x) * kBlock;
+    for (int64_t plane = blockIdx.y; plane < planes; plane += gridDim.y) {
+        const int64_t hwc_base = (plane / channels) * pixels * channels + plane % channels;
+        const int64_t base_a = hwc_a ? hwc_base : plane * pixels, base_b = hwc_b ? hwc_base : plane * pixels;
+        const int64_t step_a = hwc_a ? channels : 1, step_b = hwc_b ? channels : 1;
+        u64 acc = 0;
+        int64_t head = 0, tail = 0;   // samples [head, tail) go as dwords, the others one by one
+        if (WIDE) {                   // base_a == base_b == plane * pixels, steps of 1
+            head = (4 - base_a % 4) % 4;
+            if (head > pixels) head = pixels;
+            const int64_t n4 = (pixels - head) / 4;
+            tail = head + 4 * n4;
+            const uint32_t *a4 = reinterpret_cast<const uint32_t *>(a + base_a + head), *b4 = reinterpret_cast<const uint32_t *>(b + base_b + head);
+            int64_t i = lane;
+            for (; i + 3 * lanes < n4; i += 4 * lanes) {
+                const uint32_t x0 = a4[i], x1 = a4[i + lanes], x2 = a4[i + 2 * lanes], x3 = a4[i + 3 * lanes];
+                const uint32_t y0 = b4[i], y1 = b4[i + lanes], y2 = b4[i + 2 * lanes], y3 = b4[i + 3 * lanes];
+                acc += (sq_diff4(x0, y0) + sq_diff4(x1, y1)) + (sq_diff4(x2, y2) + sq_diff4(x3, y3));   // 16 squares: below 2^20
+            }
+            for (; i < n4; i += lanes) acc += sq_diff4(a4[i], b4[i]);
+        }
+        const int64_t singles = pixels - (tail - head);
+        for (int64_t p = lane; p < singles; p += lanes) {
+            const int64_t q = p < head ? p : p - head + tail;
+            acc += sq_diff(a[base_a + q * step_a], b[base_b + q * step_b]);
+        }
+        const u64 total = block_sum(acc, red);
+        if (threadIdx.x == 0) atomicAdd(sse + plane, total);
+    }
+}
+
+// run q of image `img` = its pixels 4 q .. 4 q + 3.  a: dwords [(img * rpi + q) * C, + C); b: the same (B_HWC) or dword q of
+// plane img * C + c.  gridDim.x workgroups share an image, blockIdx.y strides the images.
+template <int C, bool B_HWC>
+__global__ __launch_bounds__(kBlock) void sse_run_kernel(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, int64_t images,
+                                                          int64_t runs_per_image, u64 *__restrict__ sse)
+{
+    __shared__ u64 red[kWaves];
+    for (int64_t img = blockIdx.y; img < images; img += gridDim.y) {
+        u64 acc[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = 0;
+        for (int64_t q = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; q < runs_per_image; q += static_cast<int64_t>(gridDim.x) * kBlock) {
+            const int64_t r = img * runs_per_image + q;
+            const Words<C> wa = *reinterpret_cast<const Words<C> *>(a + r * C);
+            Words<C> wb;
+            if (B_HWC) {
+                wb = *reinterpret_cast<const Words<C> *>(b + r * C);
+            } else {
+#pragma unroll
+                for (int c = 0; c < C; ++c) wb.w[c] = b[(img * C + c) * runs_per_image + q];
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                uint32_t part = 0;   // four squares
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const int byte = p * C + c;   // little-endian: sample `byte` of an HWC run
+                    const uint32_t x = (wa.w[byte / 4] >> (8 * (byte % 4))) & 0xffu;
+                    const uint32_t y = B_HWC ? (wb.w[byte / 4] >> (8 * (byte % 4))) & 0xffu : (wb.w[c] >> (8 * p)) & 0xffu;
+                    part += sq_diff(x, y);
+                }
+                acc[c] += part;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const u64 total = block_sum(acc[c], red);
+            if (threadIdx.x == 0) atomicAdd(sse + img * C + c, total);
+        }
+    }
+}
+
+// gridDim of `groups` planes or images of `work` lane steps each: (workgroups that share a group, groups walked side by side)
+dim3 sse_grid(int64_t work, int64_t groups)
+{
+    const int64_t gy = groups < kMaxGridY ? groups : kMaxGridY;
+    const int64_t want = (work + kBlock - 1) / kBlock, most = kMaxGrid / gy;
+    const int64_t gx = want > most ? most : want;
+    return dim3(static_cast<unsigned>(gx < 1 ? 1 : gx), static_cast<unsigned>(gy));
+}
+
+}  // namespace
+
+extern "C" int basic_image_sse_u8_dev(const uint8_t *d_a, int layout_a, const uint8_t *d_b, int layout_b, int batch, int channels,
+                                      int h, int w, uint64_t *d_sse, void *hip_stream)
+{
+    const std::string who("image_sse_u8");
+    BASIC_REQUIRE(batch >= 1 && channels >= 1 && h >= 1 && w >= 1, who + ": batch, channels, h and w must be positive");
+    BASIC_REQUIRE(d_a && d_b && d_sse, who + ": null pointer");
+    BASIC_REQUIRE((layout_a == BASIC_IMAGE_CHW || layout_a == BASIC_IMAGE_HWC) && (layout_b == BASIC_IMAGE_CHW || layout_b == BASIC_IMAGE_HWC),
+                  who + ": a layout is BASIC_IMAGE_CHW or BASIC_IMAGE_HWC");
+    BASIC_REQUIRE(reinterpret_cast<uintptr_t>(d_sse) % sizeof(uint64_t) == 0, who + ": d_sse is not 8-byte aligned");
+    const int64_t pixels = static_cast<int64_t>(h) * w, planes = static_cast<int64_t>(batch) * channels;
+    BASIC_REQUIRE(planes <= kMaxSamples / pixels, who + ": more than 2^40 samples");
+    int rc = require_device();
+    if (rc) return rc;
+    hipStream_t st = as_stream(hip_stream);
+    int hwc_a = layout_a == BASIC_IMAGE_HWC && channels > 1, hwc_b = layout_b == BASIC_IMAGE_HWC && channels > 1;   // one channel: the layouts coincide
+    const bool aligned = reinterpret_cast<uintptr_t>(d_a) % 4 == 0 && reinterpret_cast<uintptr_t>(d_b) % 4 == 0;
+    u64 *sse = reinterpret_cast<u64 *>(d_sse);
+    BASIC_HIP_TRY(hipMemsetAsync(d_sse, 0, static_cast<size_t>(planes) * sizeof(uint64_t), st));   // the workgroups add to it
+    if (aligned && (hwc_a || hwc_b) && (channels == 3 || channels == 4) && pixels % 4 == 0) {
+        if (!hwc_a) {   // the HWC operand first
+            std::swap(d_a, d_b);
+            std::swap(hwc_a, hwc_b);
+        }
+        const uint32_t *a4 = reinterpret_cast<const uint32_t *>(d_a), *b4 = reinterpret_cast<const uint32_t *>(d_b);
+        const int64_t images = batch, rpi = pixels / 4;
+        const dim3 grid = sse_grid(rpi, images);
+        if (channels == 3 && hwc_b) hipLaunchKernelGGL((sse_run_kernel<3, true>), grid, dim3(kBlock), 0, st, a4, b4, images, rpi, sse);
+        else if (channels == 3) hipLaunchKernelGGL((sse_run_kernel<3, false>), grid, dim3(kBlock), 0, st, a4, b4, images, rpi, sse);
+        else if (hwc_b) hipLaunchKernelGGL((sse_run_kernel<4, true>), grid, dim3(kBlock), 0, st, a4, b4, images, rpi, sse);
+        else hipLaunchKernelGGL((sse_run_kernel<4, false>), grid, dim3(kBlock), 0, st, a4, b4, images, rpi, sse);
+    } else if (aligned && !hwc_a && !hwc_b) {   // four dwords per lane and pass
+        hipLaunchKernelGGL(sse_plane_kernel<true>, sse_grid((pixels + 15) / 16, planes), dim3(kBlock), 0, st, d_a, 0, d_b, 0, planes, channels,
+                           pixels, sse);
+    } else {
+        hipLaunchKernelGGL(sse_plane_kernel<false>, sse_grid(pixels, planes), dim3(kBlock), 0, st, d_a, hwc_a, d_b, hwc_b, planes, channels,
+                           pixels, sse);
+    }
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
 }

@@ -588,6 +588,37 @@ def image_f32_to_u8(t, layout="chw"):
     return out
 
 
+def image_sse_u8(a, b):
+    """The exact sum of squared differences of two uint8 [B, C, H, W] batches on one GPU, per image and channel: int64 [B, C]
+    on that device (basic_image_sse_u8_dev; integer arithmetic, the same value at any batch, layout and alignment).  Each batch is
+    read as it lies when it is contiguous or its memory is [B][H][W][C] (image_layout_of), and made contiguous otherwise."""
+    for t in (a, b):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            _dev(t)
+        if t.dtype != torch.uint8:
+            raise TypeError(f"expected torch.uint8, got {t.dtype}")
+    if a.dim() != 4 or a.shape != b.shape:
+        raise ValueError(f"image_sse_u8 takes two [B, C, H, W] batches of one shape, not {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.device != b.device:
+        raise ValueError("image_sse_u8: the two batches live on different devices")
+    (a, layout_a), (b, layout_b) = _image_u8(a), _image_u8(b)
+    B, C, H, W = a.shape
+    with torch.cuda.device(a.device):
+        out = torch.empty((B, C), device=a.device, dtype=torch.int64)
+        _lib.check(_lib.lib().basic_image_sse_u8_dev(a.data_ptr(), IMAGE_LAYOUTS[layout_a], b.data_ptr(), IMAGE_LAYOUTS[layout_b], B, C, H, W,
+                                                     out.data_ptr(), _stream()))
+    return out
+
+
+def ms_ssim_per_image_u8(a, b, return_terms=False):
+    """MS-SSIM of each image of two uint8 [B, C, H, W] batches, BY DEFINITION
+    ``ms_ssim_per_image(image_u8_to_f32(a), image_u8_to_f32(b), data_range=1.0)``, and computed as exactly that: two conversions in
+    front of the float kernels.  This is a decision, not a measurement: the conversions move a small fraction of the bytes the ten
+    MS-SSIM launches move, and a uint8 load phase in csrc/msssim.hip would double its instantiations; what the two extra passes cost
+    was not measured."""
+    return ms_ssim_per_image(image_u8_to_f32(a), image_u8_to_f32(b), data_range=1.0, return_terms=return_terms)
+
+
 class HyperpriorSession:
     """basic_hp_session_*: the fused compress / decompress entry points of the plain hyperprior latent graph (one C call
     per batch instead of a Python walk over the graph).  Borrows the layer plans and table sets it is given (kept alive

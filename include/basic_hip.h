@@ -443,6 +443,22 @@ int basic_image_u8_to_f32_dev(const uint8_t *d_src, int layout, int batch, int c
  * `layout`. */
 int basic_image_f32_to_u8_dev(const float *d_src, int batch, int channels, int h, int w, int layout,
                               uint8_t *d_dst, void *hip_stream);
+/* The distortion of an 8-bit picture, exactly: d_sse[b][c] = sum over (y, x) of (a - b)^2 as an integer (PSNR of the batch
+ * or of an image = 10 log10(255^2 * samples / sum of its d_sse), in float64 on the host).  d_a and d_b are uint8 batches of
+ * one shape, EACH in its own layout (a decoded PNG is HWC, a reconstruction either).  Integer arithmetic only -- 32-bit sums
+ * of at most 16 squares, 64-bit from there on -- and the workgroups meet in 64-bit integer atomic adds, one per workgroup and
+ * destination, which commute: the result is the same at any batch, layout, alignment, launch shape and arrival order.  The
+ * call clears d_sse on hip_stream itself (one memset node in front of the one launch) and writes every element of it;
+ * nothing is allocated, nothing synchronised.  Any channels, h, w >= 1 and any byte alignment of either uint8 pointer.  With
+ * both pointers 4-byte aligned a lane reads one dword of four samples per operand: two BASIC_IMAGE_CHW operands (or one
+ * channel) by planes -- the up to three samples between a plane's ends and its whole dwords, where h * w % 4 != 0 puts two
+ * channels or two images into one dword, are added one by one --, and, with an HWC operand, channels 3 or 4 and h * w a
+ * multiple of 4, four consecutive pixels per lane (`channels` dwords of an HWC operand, one dword per plane of a CHW one).
+ * Every other call goes sample by sample.  All paths give the same integers.  BASIC_ERR_INVALID, before any launch, for a
+ * non-positive dimension, a null pointer, an unknown layout, a d_sse that is not 8-byte aligned or more than 2^40 samples. */
+int basic_image_sse_u8_dev(const uint8_t *d_a, int layout_a, const uint8_t *d_b, int layout_b,
+                           int batch, int channels, int h, int w,
+                           uint64_t *d_sse /* [batch][channels] */, void *hip_stream);
 /* basic_hp_encode_images for a uint8 batch in `layout` (channels = the first layer's input channels), on the device
  * (x_on_host == 0) or in host memory: a host batch is copied as uint8 -- a quarter of the float bytes -- into a staging
  * buffer of the session on its copy stream and converted on hip_stream into the buffer the first layer reads; from there

@@ -33,6 +33,25 @@ def save_reconstructions(codec, batches, directory):
     return files
 
 
+class ReconstructionWriter:
+    """The harness' ``on_reconstruction`` callback: writes the picture the metric saw for every image of every tested level as
+    ``directory/<level prefix>/NNNNN.png`` (no folder level without a level prefix), NNNNN = the image's place in the dataset."""
+
+    def __init__(self, directory, batches):
+        self.directory, self.files = directory, []
+        self.first_image = [0]   # of every dataset item
+        for b in batches:
+            self.first_image.append(self.first_image[-1] + int(b.shape[0]))
+
+    def __call__(self, level_prefix, item_index, picture_u8):
+        from PIL import Image
+        folder = os.path.join(self.directory, level_prefix) if level_prefix else self.directory
+        os.makedirs(folder, exist_ok=True)
+        for j, a in enumerate(picture_u8.permute(0, 2, 3, 1).cpu().numpy()):
+            self.files.append(os.path.join(folder, f"{self.first_image[item_index] + j:05d}.png"))
+            Image.fromarray(a[..., 0] if a.shape[-1] == 1 else a).save(self.files[-1])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--codec", choices=["hyperprior", "topogroup", "basic"], default="hyperprior")
@@ -72,7 +91,11 @@ def main(argv=None):
                     help="the datasets yield 8-bit images (an image file's own bytes; synthetic: torch.randint): uploaded as bytes and "
                          "converted on the GPU; original_length, compression_ratio and speed_* then count one byte per sample")
     ap.add_argument("--save-reconstructions", default=None, metavar="DIR",
-                    help="after the run, decompress every item as an 8-bit picture and write one PNG per image into DIR")
+                    help="after the run, decompress every item as an 8-bit picture and write one PNG per image into DIR "
+                         "(with --metrics-on-uint8: the pictures the run measured, DIR/<level prefix>/NNNNN.png for every tested level)")
+    ap.add_argument("--metrics-on-uint8", action="store_true",
+                    help="measure the 8-bit picture: decompress(output_dtype=torch.uint8) inside the timed region, the distortion from "
+                         "exact integers against the 8-bit item (a float item: quantised once)")
     ap.add_argument("--out", required=True)
     args = ap.parse_args(argv)
     if args.stream_rows and args.codec != "basic":
@@ -129,7 +152,8 @@ def main(argv=None):
             codec.decompress(codec.compress(batches[0].to("cuda")))
             for chunk in warm_chunks:   # the coalesced calls' one-time costs: one chunk per (shape, size) the pass will make
                 codec.decompress_items(codec.compress_items(chunk))
-    bench = BasicLosslessCompressionBenchmark(codec, batches,
+    writer = ReconstructionWriter(args.save_reconstructions, batches) if args.save_reconstructions and args.metrics_on_uint8 else None
+    bench = BasicLosslessCompressionBenchmark(codec, batches, metrics_on_uint8=args.metrics_on_uint8, on_reconstruction=writer,
                                               distortion_metric=PytorchBatchedDistortion(metrics=args.metrics),
                                               nn_codec_use_forward_pass=args.forward_pass,
                                               testing_complexity_levels=args.complexity_levels,
@@ -150,9 +174,12 @@ def main(argv=None):
     metrics = bench.run_benchmark(ignore_exist_metrics=True)
     bench.close()
     print(json.dumps(metrics, indent=1))
-    if args.save_reconstructions:   # at the complexity and rate level the run ended on
+    if writer is not None:          # the pictures the run measured, every tested level
+        print(f"{len(writer.files)} reconstructions written to {args.save_reconstructions}")
+    elif args.save_reconstructions:   # at the complexity and rate level the run ended on
         files = save_reconstructions(codec, batches, args.save_reconstructions)
         print(f"{len(files)} reconstructions written to {args.save_reconstructions}")
+    return metrics
 
 
 if __name__ == "__main__":
