@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <type_traits>
 
 #include "common_host.h"   // what needs no HIP: the C ABI, set_error, BASIC_REQUIRE, BASIC_MCONV_BLOCK_CHANNELS
 
@@ -36,6 +37,15 @@ int set_rans_waves(int waves_per_block);
 bool set_dynamic_tiles(bool on);
 
 constexpr int kWave = 64;  // CDNA wavefront
+
+// f(std::integral_constant<int, k>{}) for k = kFrom .. kTo - 1, unrolled at compile time
+template <int kFrom, int kTo, class F> __device__ __forceinline__ void static_for(F &&f)
+{
+    if constexpr (kFrom < kTo) {
+        f(std::integral_constant<int, kFrom>{});
+        static_for<kFrom + 1, kTo>(f);
+    }
+}
 
 // Device view of a table set's fast-decoder search image (rans.hip), for kernels outside rans.hip that decode in place.
 struct RansFastView {

@@ -15,7 +15,7 @@
 // few VALU ops, and only the chosen lane's new state is broadcast back; renormalisation, bypass
 // symbols and wide rows hide behind one rare-path test.  The generic kernels (AR remap, any table)
 // keep the state update on the scalar unit.
-#include "common.h"
+#include "ans_common.h"
 #include "wave_decoder.h"
 
 #include <algorithm>
@@ -409,48 +409,6 @@ struct StridedSeg {
     }
 };
 
-struct ArDev {
-    const int32_t *tab;  // nullptr = no AR remap
-    int k, order, rows, s1;
-    const int32_t *ar_indexes, *off0, *off1;  // per stream-element arrays (global element ids)
-    const int32_t *off2;                       // third back distance (custom ops only)
-    int custom;                                // tab = float [k][7]: w0 w1 w2 bias scale min max (init_custom_ar_ops)
-};
-
-
-__device__ __forceinline__ int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// AR remap of the table row (ans_interface.hpp:89-104); every index is clamped so that a
-// malformed input can never read outside the tables.
-__device__ __forceinline__ int32_t ar_row(const ArDev &ar, int32_t a, int32_t row, int32_t v0, int32_t v1)
-{
-    a = clampi(a, 0, ar.k - 1);
-    row = clampi(row, 0, ar.rows - 1);
-    v0 = clampi(v0, 0, ar.s1 - 1);
-    if (ar.order == 1) return ar.tab[(static_cast<int64_t>(a) * ar.rows + row) * ar.s1 + v0];
-    v1 = clampi(v1, 0, ar.s1 - 1);
-    return ar.tab[((static_cast<int64_t>(a) * ar.rows + row) * ar.s1 + v0) * ar.s1 + v1];
-}
-
-// ar_limited_scaled_add_linear_op::op on (index, the RAW previous symbols), csrc/ans/ar_funcs.hpp:58-87 called from
-// ar_update_index (ans_interface.hpp:60-84).  float arithmetic with every product and sum rounded on its own, as the
-// reference's x86 build does (no fused multiply-add: the intrinsics keep hipcc from contracting).
-__device__ __forceinline__ int32_t ar_custom_row(const ArDev &ar, int32_t a, int32_t row, int32_t v0, int32_t v1, int32_t v2)
-{
-    const float *op = reinterpret_cast<const float *>(ar.tab) + static_cast<int64_t>(clampi(a, 0, ar.k - 1)) * 7;
-    const float base = static_cast<float>(row), scale = op[4];
-    const float base_unscaled = floorf(__fdiv_rn(base, scale));
-    float adder = __fadd_rn(0.f, __fmul_rn(static_cast<float>(v0), op[0]));
-    if (ar.order > 1) adder = __fadd_rn(adder, __fmul_rn(static_cast<float>(v1), op[1]));
-    if (ar.order > 2) adder = __fadd_rn(adder, __fmul_rn(static_cast<float>(v2), op[2]));
-    adder = __fadd_rn(adder, op[3]);
-    float lim = __fadd_rn(base_unscaled, adder);
-    lim = lim < op[6] ? lim : op[6];
-    lim = op[5] > lim ? op[5] : lim;
-    const float step = __fmul_rn(__fsub_rn(roundf(lim), base_unscaled), scale);
-    return static_cast<int32_t>(__fadd_rn(base, step));
-}
-
 __device__ __forceinline__ uint32_t bcast_u32(uint32_t v, int lane)
 {
     return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), lane));
@@ -559,8 +517,7 @@ __device__ __noinline__ EscapeResult encode_escape(uint64_t x, uint32_t *p, uint
         direct.p = WaveEmitter::store_parked(p, lo, parked, parked_mask, lane, overflow);
         if (overflow) return EscapeResult{x, p, 1};
     }
-    int nb = 0;
-    while (nb * bprec < 32u && (r >> (nb * bprec)) != 0u) ++nb;
+    const int nb = escape_digits(r, bprec);
     for (int k = nb - 1; k >= 0; --k) put_raw(x, direct, lane, (r >> (k * bprec)) & maxbv, bprec);
     put_raw(x, direct, lane, static_cast<uint32_t>(nb) % maxbv, bprec);
     for (uint32_t k = 0; k < static_cast<uint32_t>(nb) / maxbv; ++k) put_raw(x, direct, lane, maxbv, bprec);
@@ -599,30 +556,13 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(TablesDev T, ArDev ar, 
         bool is_bypass = false;
         if (i >= 0) {
             int32_t row = idx[i];
-            if (ar.tab) {
-                const int64_t g = beg + i;
-                const int32_t a = ar.ar_indexes ? ar.ar_indexes[g] : 0;
-                const int32_t one = ar.custom ? 0 : 1;   // the table flavour indexes with symbol + 1 (0 = no predecessor)
-                const int32_t d0 = ar.off0[g];
-                const int32_t v0 = (d0 > 0 && d0 <= i) ? sym[i - d0] + one : 0;
-                int32_t v1 = 0, v2 = 0;
-                if (ar.order >= 2) {
-                    const int32_t d1 = ar.off1[g];
-                    v1 = (d1 > 0 && d1 <= i) ? sym[i - d1] + one : 0;
-                }
-                if (ar.order >= 3) {
-                    const int32_t d2 = ar.off2[g];
-                    v2 = (d2 > 0 && d2 <= i) ? sym[i - d2] + one : 0;
-                }
-                row = ar.custom ? ar_custom_row(ar, a, row, v0, v1, v2) : ar_row(ar, a, row, v0, v1);
-            }
+            if (ar.tab) row = ar_remap_row<true>(ar, row, beg + i, i, [&](int64_t k) { return sym[k]; });
             row = clampi(row, 0, T.rows - 1);
             const int32_t *cdf = T.cdfs + static_cast<int64_t>(row) * T.stride;
             const int32_t max_value = T.sizes[row] - 2;
             int32_t value = sym[i] - T.offsets[row];
             if (T.bypass) {
-                if (value < 0) { raw = static_cast<uint32_t>(-2 * value - 1); value = max_value; }
-                else if (value >= max_value) { raw = static_cast<uint32_t>(2 * (value - max_value)); value = max_value; }
+                bypass_split(value, max_value, raw);
                 is_bypass = (value == max_value);
             }
             value = clampi(value, 0, max_value);  // without bypass the reference is UB out of range
@@ -637,8 +577,7 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(TablesDev T, ArDev ar, 
             if ((bypass_mask >> j) & 1ull) {
                 // decode order: sentinel, count nibbles, payload low-first  =>  written reversed
                 const uint32_t r = bcast_u32(raw, j);
-                int nb = 0;
-                while (nb * bprec < 32u && (r >> (nb * bprec)) != 0u) ++nb;
+                const int nb = escape_digits(r, bprec);
                 for (int k = nb - 1; k >= 0; --k) put_raw(x, em, lane, (r >> (k * bprec)) & maxbv, bprec);
                 put_raw(x, em, lane, static_cast<uint32_t>(nb) % maxbv, bprec);
                 for (uint32_t k = 0; k < static_cast<uint32_t>(nb) / maxbv; ++k) put_raw(x, em, lane, maxbv, bprec);
@@ -673,8 +612,7 @@ __device__ __forceinline__ EncLane enc_prepare(const TablesDev &T, const int2 *r
         int32_t value = s - ri.x;
         uint32_t byp = 0;
         if (T.bypass) {
-            if (value < 0) { e.raw = static_cast<uint32_t>(-2 * value - 1); value = max_value; }
-            else if (value >= max_value) { e.raw = static_cast<uint32_t>(2 * (value - max_value)); value = max_value; }
+            bypass_split(value, max_value, e.raw);
             byp = (value == max_value) ? 0x80u : 0u;
         }
         value = clampi(value, 0, max_value);  // without bypass the reference is UB out of range
@@ -899,21 +837,9 @@ __global__ __launch_bounds__(64) void rans_decode_kernel(TablesDev T, ArDev ar, 
             int32_t size, offset;
             if (AR) {
                 // remap from already-decoded symbols (ans_interface.hpp:89-104); lane-uniform loads
-                const int64_t e = c0 + j, g = beg + e;
-                const int32_t a = ar.ar_indexes ? ar.ar_indexes[g] : 0;
-                const int32_t one = ar.custom ? 0 : 1;
-                const int32_t d0 = ar.off0[g];
-                const int32_t v0 = (d0 > 0 && d0 <= e) ? __hip_atomic_load(out + (e - d0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + one : 0;
-                int32_t v1 = 0, v2 = 0;
-                if (ar.order >= 2) {
-                    const int32_t d1 = ar.off1[g];
-                    v1 = (d1 > 0 && d1 <= e) ? __hip_atomic_load(out + (e - d1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + one : 0;
-                }
-                if (ar.order >= 3) {
-                    const int32_t d2 = ar.off2[g];
-                    v2 = (d2 > 0 && d2 <= e) ? __hip_atomic_load(out + (e - d2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + one : 0;
-                }
-                row = ar.custom ? ar_custom_row(ar, a, row, v0, v1, v2) : ar_row(ar, a, row, v0, v1);
+                const int64_t e = c0 + j;
+                row = ar_remap_row<true>(ar, row, beg + e, e,
+                                         [&](int64_t k) { return __hip_atomic_load(out + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); });
                 row = __builtin_amdgcn_readfirstlane(clampi(row, 0, T.rows - 1));
                 size = T.sizes[row];
                 offset = T.offsets[row];
@@ -1084,17 +1010,6 @@ TablesDev dev_view(const basic_rans_tables *t)
                      reinterpret_cast<const uint4 *>(t->d_enc), reinterpret_cast<const int2 *>(t->d_rowinfo)};
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 4); }
-    template <typename T> T *as() { return static_cast<T *>(p); }
-};
-
-}  // namespace
-
-namespace {
-
 constexpr size_t kLdsTableBudget = 144 * 1024;  // of the 160 KiB per CU
 
 // Streams (wavefronts) per workgroup of the batched fast coders.  Default: one per workgroup, spread over the chip (a
@@ -1108,68 +1023,85 @@ thread_local int g_wpb_override = 0;   // set by a codec session around its laun
 thread_local int g_last_kernel = BASIC_RANS_KERNEL_NONE, g_last_waves = 0;
 inline void note_launch(int kernel, int waves) { g_last_kernel = kernel; g_last_waves = waves; }
 
-int rans_waves_per_block(int nstreams)
+// f(std::integral_constant<int, W>{}) for the largest W of 1, 2, 4, 8, 16 that wpb reaches
+template <class F> auto dispatch_waves(int wpb, F &&f)
 {
-    static const int forced = [] { const char *e = getenv("BASIC_RANS_WPB"); return e ? atoi(e) : 0; }();
-    int w = g_wpb_override > 0 ? g_wpb_override : forced > 0 ? forced : 1;
-    (void)nstreams;
-    if (w >= 16) return 16;
-    if (w >= 8) return 8;
-    if (w >= 4) return 4;
-    if (w >= 2) return 2;
-    return 1;
+    if (wpb >= 16) return f(std::integral_constant<int, 16>{});
+    if (wpb >= 8) return f(std::integral_constant<int, 8>{});
+    if (wpb >= 4) return f(std::integral_constant<int, 4>{});
+    if (wpb >= 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 1>{});
 }
 
-template <bool AR, bool LDS>
-int launch_decode_v(const basic_rans_tables *t, const ArDev &ar, int nstreams, hipStream_t st, const uint32_t *d_words,
-                    const int64_t *d_word_off, const int32_t *d_indexes, const int64_t *d_seg, int32_t *d_out,
-                    uint64_t *d_state, int64_t *d_pos, StridedSeg ss)
+int rans_waves_per_block()
 {
-    const size_t lds = LDS ? t->cdf16.size() * sizeof(uint16_t) : 0;
-    if (LDS) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(rans_decode_kernel<AR, LDS>)));
-    note_launch(AR ? (LDS ? BASIC_RANS_KERNEL_DEC_AR_LDS : BASIC_RANS_KERNEL_DEC_AR_GLOBAL)
-                   : (LDS ? BASIC_RANS_KERNEL_DEC_GENERAL_LDS : BASIC_RANS_KERNEL_DEC_GENERAL_GLOBAL), 1);
-    hipLaunchKernelGGL((rans_decode_kernel<AR, LDS>), dim3(nstreams), dim3(64), lds, st, dev_view(t), ar, d_words, d_word_off,
-                       d_indexes, d_seg, d_out, d_state, d_pos, ss);
-    BASIC_HIP_TRY(hipGetLastError());
-    return BASIC_OK;
+    static const int forced = [] { const char *e = getenv("BASIC_RANS_WPB"); return e ? atoi(e) : 0; }();
+    return dispatch_waves(g_wpb_override > 0 ? g_wpb_override : forced, [](auto wc) { return static_cast<int>(decltype(wc)::value); });
+}
+
+// The encoder of a launch: the fast kernel unless the streams need the AR remap or the table set has no encoder image.
+// wpb = streams per workgroup of the fast kernel (the host-buffer entry point: always 1).
+int launch_encode(const basic_rans_tables *t, const ArDev &ar, int nstreams, hipStream_t st, int wpb, const int32_t *d_symbols,
+                  const int32_t *d_indexes, const int64_t *d_seg, uint32_t *d_out_words, int64_t slot_words, int32_t *d_out_nwords)
+{
+    if (ar.tab || !t->fast_enc_ok) {
+        note_launch(ar.tab ? BASIC_RANS_KERNEL_ENC_GENERAL_AR : BASIC_RANS_KERNEL_ENC_GENERAL, 1);
+        hipLaunchKernelGGL(rans_encode_kernel, dim3(nstreams), dim3(64), 0, st, dev_view(t), ar, d_symbols, d_indexes, d_seg,
+                           d_out_words, slot_words, d_out_nwords);
+        BASIC_HIP_TRY(hipGetLastError());
+        return BASIC_OK;
+    }
+    // Packed launches (several streams per workgroup) exist to share the chip with transforms on other HIP streams.
+    // The encoder needs almost no LDS, so a convolution workgroup would settle on the same compute unit -- and its
+    // LDS-DMA traffic then owns that unit's vector-memory queue: the encoder's table gathers wait behind it and the
+    // chain runs 6x slower (measured: 4.0 -> 25 ms beside conv_tap_mfma_kernel, while the decoder, whose 124 KB
+    // search image keeps its unit to itself, goes 8.1 -> 8.6 ms).  So a packed encoder workgroup claims the whole
+    // unit's LDS as well: nstreams / W units are then the coder's alone.
+    size_t lds_rows = static_cast<size_t>(t->rows) * sizeof(int2);
+    if (wpb > 1 && lds_rows < 159 * 1024) lds_rows = 159 * 1024;
+    note_launch(BASIC_RANS_KERNEL_ENC_FAST, wpb);
+    return dispatch_waves(wpb, [&](auto wc) -> int {
+        constexpr int W = decltype(wc)::value;
+        if (lds_rows > 64 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(rans_encode_fast_kernel<W>)));
+        hipLaunchKernelGGL(rans_encode_fast_kernel<W>, dim3((nstreams + W - 1) / W), dim3(64 * W), lds_rows, st, dev_view(t), d_symbols,
+                           d_indexes, d_seg, d_out_words, slot_words, d_out_nwords, nstreams);
+        BASIC_HIP_TRY(hipGetLastError());
+        return BASIC_OK;
+    });
 }
 
 int launch_decode(const basic_rans_tables *t, const ArDev &ar, int nstreams, hipStream_t st, const uint32_t *d_words,
                   const int64_t *d_word_off, const int32_t *d_indexes, const int64_t *d_seg, int32_t *d_out,
                   uint64_t *d_state, int64_t *d_pos, StridedSeg ss = StridedSeg{0, 0, 0})
 {
-    // LDS-resident tables pay a per-launch copy of the table set; worth it unless the launch is tiny.
-    const bool lds = t->cdf16.size() * sizeof(uint16_t) <= kLdsTableBudget;
-    int max_size = 0;
-    for (int v : t->sizes) max_size = v > max_size ? v : max_size;
-    (void)max_size;
     if (!ar.tab && t->fast_ok) {
         const size_t lds_img = t->image.size() * sizeof(uint32_t);
-        const int wpb = rans_waves_per_block(nstreams);
+        const int wpb = rans_waves_per_block();
         note_launch(BASIC_RANS_KERNEL_DEC_FAST, wpb);
-#define BASIC_DEC_LAUNCH(W)                                                                                              \
-        do {                                                                                                             \
-            BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(rans_decode_fast_kernel<W>)));                   \
-            hipLaunchKernelGGL(rans_decode_fast_kernel<W>, dim3((nstreams + W - 1) / W), dim3(64 * W), lds_img, st, dev_view(t), \
-                               d_words, d_word_off, d_indexes, d_seg, d_out, d_state, d_pos, ss, nstreams);              \
-        } while (0)
-        switch (wpb) {
-            case 16: BASIC_DEC_LAUNCH(16); break;
-            case 8: BASIC_DEC_LAUNCH(8); break;
-            case 4: BASIC_DEC_LAUNCH(4); break;
-            case 2: BASIC_DEC_LAUNCH(2); break;
-            default: BASIC_DEC_LAUNCH(1); break;
-        }
-#undef BASIC_DEC_LAUNCH
+        return dispatch_waves(wpb, [&](auto wc) -> int {
+            constexpr int W = decltype(wc)::value;
+            BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(rans_decode_fast_kernel<W>)));
+            hipLaunchKernelGGL(rans_decode_fast_kernel<W>, dim3((nstreams + W - 1) / W), dim3(64 * W), lds_img, st, dev_view(t),
+                               d_words, d_word_off, d_indexes, d_seg, d_out, d_state, d_pos, ss, nstreams);
+            BASIC_HIP_TRY(hipGetLastError());
+            return BASIC_OK;
+        });
+    }
+    auto general = [&](auto ar_c, auto lds_c) -> int {
+        constexpr bool AR = decltype(ar_c)::value, LDS = decltype(lds_c)::value;
+        const size_t lds = LDS ? t->cdf16.size() * sizeof(uint16_t) : 0;
+        if (LDS) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(rans_decode_kernel<AR, LDS>)));
+        note_launch(AR ? (LDS ? BASIC_RANS_KERNEL_DEC_AR_LDS : BASIC_RANS_KERNEL_DEC_AR_GLOBAL)
+                       : (LDS ? BASIC_RANS_KERNEL_DEC_GENERAL_LDS : BASIC_RANS_KERNEL_DEC_GENERAL_GLOBAL), 1);
+        hipLaunchKernelGGL((rans_decode_kernel<AR, LDS>), dim3(nstreams), dim3(64), lds, st, dev_view(t), ar, d_words, d_word_off,
+                           d_indexes, d_seg, d_out, d_state, d_pos, ss);
         BASIC_HIP_TRY(hipGetLastError());
         return BASIC_OK;
-    }
-    if (ar.tab)
-        return lds ? launch_decode_v<true, true>(t, ar, nstreams, st, d_words, d_word_off, d_indexes, d_seg, d_out, d_state, d_pos, ss)
-                   : launch_decode_v<true, false>(t, ar, nstreams, st, d_words, d_word_off, d_indexes, d_seg, d_out, d_state, d_pos, ss);
-    return lds ? launch_decode_v<false, true>(t, ar, nstreams, st, d_words, d_word_off, d_indexes, d_seg, d_out, d_state, d_pos, ss)
-               : launch_decode_v<false, false>(t, ar, nstreams, st, d_words, d_word_off, d_indexes, d_seg, d_out, d_state, d_pos, ss);
+    };
+    // LDS-resident tables pay a per-launch copy of the table set; worth it unless the launch is tiny.
+    const bool lds = t->cdf16.size() * sizeof(uint16_t) <= kLdsTableBudget;
+    if (ar.tab) return lds ? general(std::true_type{}, std::true_type{}) : general(std::true_type{}, std::false_type{});
+    return lds ? general(std::false_type{}, std::true_type{}) : general(std::false_type{}, std::false_type{});
 }
 
 }  // namespace
@@ -1278,41 +1210,8 @@ extern "C" int basic_rans_encode_batch_dev(const basic_rans_tables *t, const int
     BASIC_REQUIRE(d_symbols && d_indexes && d_seg && d_out_words && d_out_nwords && nstreams >= 1 && slot_words >= 2,
                   "rans_encode_batch: bad argument");
     BASIC_REQUIRE(!t->d_ar, "rans_encode_batch: AR tables are only supported by the host-buffer entry points");
-    if (t->fast_enc_ok) {
-        // Packed launches (several streams per workgroup) exist to share the chip with transforms on other HIP streams.
-        // The encoder needs almost no LDS, so a convolution workgroup would settle on the same compute unit -- and its
-        // LDS-DMA traffic then owns that unit's vector-memory queue: the encoder's table gathers wait behind it and the
-        // chain runs 6x slower (measured: 4.0 -> 25 ms beside conv_tap_mfma_kernel, while the decoder, whose 124 KB
-        // search image keeps its unit to itself, goes 8.1 -> 8.6 ms).  So a packed encoder workgroup claims the whole
-        // unit's LDS as well: nstreams / W units are then the coder's alone.
-        const int wpb_ = rans_waves_per_block(nstreams);
-        size_t lds_rows = static_cast<size_t>(t->rows) * sizeof(int2);
-        if (wpb_ > 1 && lds_rows < 159 * 1024) lds_rows = 159 * 1024;
-        note_launch(BASIC_RANS_KERNEL_ENC_FAST, wpb_);
-#define BASIC_ENC_LAUNCH(W)                                                                                          \
-        do {                                                                                                         \
-        if (lds_rows > 64 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(rans_encode_fast_kernel<W>))); \
-        hipLaunchKernelGGL(rans_encode_fast_kernel<W>, dim3((nstreams + W - 1) / W), dim3(64 * W), lds_rows,         \
-                           as_stream(hip_stream), dev_view(t), d_symbols, d_indexes, d_seg, d_out_words, slot_words, \
-                           d_out_nwords, nstreams);                                                                  \
-        } while (0)
-        switch (wpb_) {
-            case 16: BASIC_ENC_LAUNCH(16); break;
-            case 8: BASIC_ENC_LAUNCH(8); break;
-            case 4: BASIC_ENC_LAUNCH(4); break;
-            case 2: BASIC_ENC_LAUNCH(2); break;
-            default: BASIC_ENC_LAUNCH(1); break;
-        }
-#undef BASIC_ENC_LAUNCH
-        BASIC_HIP_TRY(hipGetLastError());
-        return BASIC_OK;
-    }
-    ArDev ar{};
-    note_launch(BASIC_RANS_KERNEL_ENC_GENERAL, 1);
-    hipLaunchKernelGGL(rans_encode_kernel, dim3(nstreams), dim3(64), 0, as_stream(hip_stream), dev_view(t), ar,
-                       d_symbols, d_indexes, d_seg, d_out_words, slot_words, d_out_nwords);
-    BASIC_HIP_TRY(hipGetLastError());
-    return BASIC_OK;
+    return launch_encode(t, ArDev{}, nstreams, as_stream(hip_stream), rans_waves_per_block(), d_symbols, d_indexes, d_seg, d_out_words,
+                         slot_words, d_out_nwords);
 }
 
 extern "C" int basic_rans_decode_batch_dev(const basic_rans_tables *t, const uint32_t *d_words,
@@ -1342,20 +1241,33 @@ extern "C" int basic_rans_compact_streams_dev(const uint32_t *d_slots, int64_t s
     return BASIC_OK;
 }
 
+namespace {
+// The three strided entry points below: the checks every one of them makes (`who` names it in the messages, args_ok is its
+// own test of the arguments), then stream s = b * lanes + k of the launch continues with `count` symbols (see StridedSeg).
+int decode_strided(const char *who, bool args_ok, const basic_rans_tables *t, const uint32_t *d_words, const int64_t *d_word_off,
+                   const int32_t *d_indexes, int64_t first, int64_t stride, int lanes, int64_t count, int nimages, int stream_first,
+                   int stream_stride, int32_t *d_out_symbols, uint64_t *d_state, int64_t *d_pos, void *hip_stream)
+{
+    if (!t) { set_error("ANS not initialized!"); return BASIC_ERR_NOT_INIT; }
+    BASIC_REQUIRE(args_ok && d_words && d_word_off && d_indexes && d_out_symbols && d_state && d_pos && nimages >= 1 && first >= 0 &&
+                      stride >= 0 && count >= 0,
+                  std::string(who) + ": bad argument");
+    BASIC_REQUIRE(!t->d_ar, std::string(who) + ": AR tables are only supported by the host-buffer entry points");
+    if (count == 0) return BASIC_OK;
+    StridedSeg ss{first, stride, count, lanes};
+    ss.stream_first = stream_first; ss.stream_stride = stream_stride;
+    return launch_decode(t, ArDev{}, nimages * lanes, as_stream(hip_stream), d_words, d_word_off, d_indexes, nullptr, d_out_symbols,
+                         d_state, d_pos, ss);
+}
+}  // namespace
+
 extern "C" int basic_rans_decode_batch_strided_dev(const basic_rans_tables *t, const uint32_t *d_words,
                                                    const int64_t *d_word_off, const int32_t *d_indexes, int64_t first,
                                                    int64_t stride, int64_t count, int nstreams, int32_t *d_out_symbols,
                                                    uint64_t *d_state, int64_t *d_pos, void *hip_stream)
 {
-    if (!t) { set_error("ANS not initialized!"); return BASIC_ERR_NOT_INIT; }
-    BASIC_REQUIRE(d_words && d_word_off && d_indexes && d_out_symbols && d_state && d_pos && nstreams >= 1 && first >= 0 &&
-                      stride >= 0 && count >= 0,
-                  "rans_decode_batch_strided: bad argument");
-    BASIC_REQUIRE(!t->d_ar, "rans_decode_batch_strided: AR tables are only supported by the host-buffer entry points");
-    if (count == 0) return BASIC_OK;
-    ArDev ar{};
-    return launch_decode(t, ar, nstreams, as_stream(hip_stream), d_words, d_word_off, d_indexes, nullptr, d_out_symbols, d_state,
-                         d_pos, StridedSeg{first, stride, count});
+    return decode_strided("rans_decode_batch_strided", true, t, d_words, d_word_off, d_indexes, first, stride, 1, count, nstreams, 0, -1,
+                          d_out_symbols, d_state, d_pos, hip_stream);
 }
 
 // The same step for lane streams (scan-line coder, stream_lanes = `lanes`): `nimages * lanes` streams, stream s = b * lanes + k
@@ -1365,15 +1277,8 @@ extern "C" int basic_rans_decode_batch_lanes_dev(const basic_rans_tables *t, con
                                                  int nimages, int32_t *d_out_symbols, uint64_t *d_state, int64_t *d_pos,
                                                  void *hip_stream)
 {
-    if (!t) { set_error("ANS not initialized!"); return BASIC_ERR_NOT_INIT; }
-    BASIC_REQUIRE(d_words && d_word_off && d_indexes && d_out_symbols && d_state && d_pos && nimages >= 1 && lanes >= 1 && first >= 0 &&
-                      stride >= 0 && count >= 0 && static_cast<int64_t>(nimages) * lanes < (1ll << 31),
-                  "rans_decode_batch_lanes: bad argument");
-    BASIC_REQUIRE(!t->d_ar, "rans_decode_batch_lanes: AR tables are only supported by the host-buffer entry points");
-    if (count == 0) return BASIC_OK;
-    ArDev ar{};
-    return launch_decode(t, ar, nimages * lanes, as_stream(hip_stream), d_words, d_word_off, d_indexes, nullptr, d_out_symbols, d_state,
-                         d_pos, StridedSeg{first, stride, count, lanes});
+    return decode_strided("rans_decode_batch_lanes", lanes >= 1 && static_cast<int64_t>(nimages) * lanes < (1ll << 31), t, d_words,
+                          d_word_off, d_indexes, first, stride, lanes, count, nimages, 0, -1, d_out_symbols, d_state, d_pos, hip_stream);
 }
 
 // basic_rans_decode_batch_lanes_dev with a stream base and stride (row streams of the scan-line coder, stream_rows): the launch's
@@ -1384,63 +1289,18 @@ extern "C" int basic_rans_decode_batch_streams_dev(const basic_rans_tables *t, c
                                                    int nimages, int stream_first, int stream_stride, int32_t *d_out_symbols,
                                                    uint64_t *d_state, int64_t *d_pos, void *hip_stream)
 {
-    if (!t) { set_error("ANS not initialized!"); return BASIC_ERR_NOT_INIT; }
-    BASIC_REQUIRE(d_words && d_word_off && d_indexes && d_out_symbols && d_state && d_pos && nimages >= 1 && lanes >= 1 && first >= 0 &&
-                      stride >= 0 && count >= 0 && static_cast<int64_t>(nimages) * lanes < (1ll << 31) && stream_first >= 0 &&
-                      stream_stride >= lanes && stream_first + static_cast<int64_t>(nimages) * stream_stride < (1ll << 31),
-                  "rans_decode_batch_streams: bad argument");
-    BASIC_REQUIRE(!t->d_ar, "rans_decode_batch_streams: AR tables are only supported by the host-buffer entry points");
-    if (count == 0) return BASIC_OK;
-    ArDev ar{};
-    StridedSeg ss{first, stride, count, lanes};
-    ss.stream_first = stream_first; ss.stream_stride = stream_stride;
-    return launch_decode(t, ar, nimages * lanes, as_stream(hip_stream), d_words, d_word_off, d_indexes, nullptr, d_out_symbols, d_state,
-                         d_pos, ss);
+    return decode_strided("rans_decode_batch_streams",
+                          lanes >= 1 && static_cast<int64_t>(nimages) * lanes < (1ll << 31) && stream_first >= 0 && stream_stride >= lanes &&
+                              stream_first + static_cast<int64_t>(nimages) * stream_stride < (1ll << 31),
+                          t, d_words, d_word_off, d_indexes, first, stride, lanes, count, nimages, stream_first, stream_stride, d_out_symbols,
+                          d_state, d_pos, hip_stream);
 }
 
 // ---------------------------------------------------------------------------------------
 // Host-buffer drop-ins (single stream): stage -> kernel -> copy back.
 // ---------------------------------------------------------------------------------------
 namespace {
-
-int stage_ar(const basic_rans_tables *t, int64_t n, const int32_t *ar_indexes, const int32_t *ar_off0,
-             const int32_t *ar_off1, const int32_t *ar_off2, DevBuf &b_ai, DevBuf &b_o0, DevBuf &b_o1, DevBuf &b_o2, ArDev &ar)
-{
-    ar = ArDev{};
-    if (!t->d_ar) return BASIC_OK;
-    if (!ar_off0 || (!t->ar_custom && t->ar_order == 2 && !ar_off1)) {
-        set_error("ar_offsets is required for ar coding!");
-        return BASIC_ERR_INVALID;
-    }
-    const size_t bytes = static_cast<size_t>(n) * sizeof(int32_t);
-    ar.tab = t->d_ar; ar.k = t->ar_k; ar.order = t->ar_order; ar.rows = t->ar_rows; ar.s1 = t->ar_s1;
-    if (t->ar_custom) {   // the op's arity is the number of offset rows of this call (ans_interface.hpp:70-84)
-        ar.custom = 1;
-        ar.order = ar_off2 ? 3 : ar_off1 ? 2 : 1;
-        if (ar_off2 && !ar_off1) { set_error("ar_offsets rows must be given in order"); return BASIC_ERR_INVALID; }
-    }
-    const int order = ar.order;
-    if (ar_indexes) {
-        BASIC_HIP_TRY(b_ai.alloc(bytes));
-        BASIC_HIP_TRY(hipMemcpy(b_ai.p, ar_indexes, bytes, hipMemcpyHostToDevice));
-        ar.ar_indexes = b_ai.as<int32_t>();
-    }
-    BASIC_HIP_TRY(b_o0.alloc(bytes));
-    BASIC_HIP_TRY(hipMemcpy(b_o0.p, ar_off0, bytes, hipMemcpyHostToDevice));
-    ar.off0 = b_o0.as<int32_t>();
-    if (order >= 2) {
-        BASIC_HIP_TRY(b_o1.alloc(bytes));
-        BASIC_HIP_TRY(hipMemcpy(b_o1.p, ar_off1, bytes, hipMemcpyHostToDevice));
-        ar.off1 = b_o1.as<int32_t>();
-    }
-    if (order >= 3) {
-        BASIC_HIP_TRY(b_o2.alloc(bytes));
-        BASIC_HIP_TRY(hipMemcpy(b_o2.p, ar_off2, bytes, hipMemcpyHostToDevice));
-        ar.off2 = b_o2.as<int32_t>();
-    }
-    return BASIC_OK;
-}
-
+ArSource ar_source(const basic_rans_tables *t) { return ArSource{t->d_ar, t->ar_k, t->ar_order, t->ar_rows, t->ar_s1, t->ar_custom}; }
 }  // namespace
 
 extern "C" int basic_rans_encode_host(const basic_rans_tables *t, const int32_t *symbols, const int32_t *indexes,
@@ -1453,8 +1313,33 @@ extern "C" int basic_rans_encode_host(const basic_rans_tables *t, const int32_t 
 namespace {
 int encode_host_impl(const basic_rans_tables *t, const int32_t *symbols, const int32_t *indexes, int64_t n, bool use_ar,
                      const int32_t *ar_indexes, const int32_t *ar_off0, const int32_t *ar_off1, const int32_t *ar_off2, uint8_t *out,
-                     int64_t out_capacity, int64_t *out_len);
+                     int64_t out_capacity, int64_t *out_len)
+{
+    if (!t) { set_error("ANS not initialized!"); return BASIC_ERR_NOT_INIT; }
+    BASIC_REQUIRE(n >= 0 && out && out_len && (n == 0 || (symbols && indexes)), "encode_with_indexes: bad argument");
+    const int64_t slot_words = basic_rans_encode_bound(n) / 4;
+    HostCall c;
+    DevBuf b_out, b_nw;
+    int rc = c.stage(symbols, indexes, n);
+    if (rc) return rc;
+    BASIC_HIP_TRY(b_out.alloc(static_cast<size_t>(slot_words) * 4));
+    BASIC_HIP_TRY(b_nw.alloc(sizeof(int32_t)));
+    ArDev ar{};
+    rc = use_ar ? stage_ar(ar_source(t), n, ar_indexes, ar_off0, ar_off1, ar_off2, c.ar, ar) : BASIC_OK;
+    if (rc) return rc;
+    rc = launch_encode(t, ar, 1, nullptr, 1, c.sym.as<int32_t>(), c.idx.as<int32_t>(), c.seg.as<int64_t>(), b_out.as<uint32_t>(), slot_words,
+                       b_nw.as<int32_t>());
+    if (rc) return rc;
+    int32_t nwords = 0;
+    BASIC_HIP_TRY(hipMemcpy(&nwords, b_nw.p, sizeof(nwords), hipMemcpyDeviceToHost));
+    if (nwords < 0) { set_error("rans encoder: slot overflow"); return BASIC_ERR_OVERFLOW; }
+    const int64_t nbytes = static_cast<int64_t>(nwords) * 4;
+    *out_len = nbytes;
+    if (nbytes > out_capacity) { set_error("encode_with_indexes: output buffer too small"); return BASIC_ERR_OVERFLOW; }
+    BASIC_HIP_TRY(hipMemcpy(out, b_out.as<uint32_t>() + (slot_words - nwords), nbytes, hipMemcpyDeviceToHost));
+    return BASIC_OK;
 }
+}  // namespace
 
 extern "C" int basic_rans_encode_host_ex(const basic_rans_tables *t, const int32_t *symbols, const int32_t *indexes,
                                          int64_t n, const int32_t *ar_indexes, const int32_t *ar_off0, const int32_t *ar_off1,
@@ -1470,50 +1355,6 @@ extern "C" int basic_rans_encode_host_rows(const basic_rans_tables *t, const int
 {
     return encode_host_impl(t, symbols, indexes, n, false, nullptr, nullptr, nullptr, nullptr, out, out_capacity, out_len);
 }
-
-namespace {
-int encode_host_impl(const basic_rans_tables *t, const int32_t *symbols, const int32_t *indexes, int64_t n, bool use_ar,
-                     const int32_t *ar_indexes, const int32_t *ar_off0, const int32_t *ar_off1, const int32_t *ar_off2, uint8_t *out,
-                     int64_t out_capacity, int64_t *out_len)
-{
-    if (!t) { set_error("ANS not initialized!"); return BASIC_ERR_NOT_INIT; }
-    BASIC_REQUIRE(n >= 0 && out && out_len && (n == 0 || (symbols && indexes)), "encode_with_indexes: bad argument");
-    const int64_t slot_words = basic_rans_encode_bound(n) / 4;
-    DevBuf b_sym, b_idx, b_seg, b_out, b_nw, b_ai, b_o0, b_o1, b_o2;
-    const size_t bytes = static_cast<size_t>(n) * sizeof(int32_t);
-    BASIC_HIP_TRY(b_sym.alloc(bytes));
-    BASIC_HIP_TRY(b_idx.alloc(bytes));
-    BASIC_HIP_TRY(b_seg.alloc(2 * sizeof(int64_t)));
-    BASIC_HIP_TRY(b_out.alloc(static_cast<size_t>(slot_words) * 4));
-    BASIC_HIP_TRY(b_nw.alloc(sizeof(int32_t)));
-    if (n) {
-        BASIC_HIP_TRY(hipMemcpy(b_sym.p, symbols, bytes, hipMemcpyHostToDevice));
-        BASIC_HIP_TRY(hipMemcpy(b_idx.p, indexes, bytes, hipMemcpyHostToDevice));
-    }
-    const int64_t seg[2] = {0, n};
-    BASIC_HIP_TRY(hipMemcpy(b_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice));
-    ArDev ar{};
-    int rc = use_ar ? stage_ar(t, n, ar_indexes, ar_off0, ar_off1, ar_off2, b_ai, b_o0, b_o1, b_o2, ar) : BASIC_OK;
-    if (rc) return rc;
-    note_launch(!ar.tab && t->fast_enc_ok ? BASIC_RANS_KERNEL_ENC_FAST : ar.tab ? BASIC_RANS_KERNEL_ENC_GENERAL_AR : BASIC_RANS_KERNEL_ENC_GENERAL, 1);
-    if (!ar.tab && t->fast_enc_ok)  // same kernel choice as the batched device entry point
-        hipLaunchKernelGGL(rans_encode_fast_kernel<1>, dim3(1), dim3(64), static_cast<size_t>(t->rows) * sizeof(int2), nullptr,
-                           dev_view(t), b_sym.as<int32_t>(), b_idx.as<int32_t>(), b_seg.as<int64_t>(), b_out.as<uint32_t>(),
-                           slot_words, b_nw.as<int32_t>(), 1);
-    else
-        hipLaunchKernelGGL(rans_encode_kernel, dim3(1), dim3(64), 0, nullptr, dev_view(t), ar, b_sym.as<int32_t>(),
-                           b_idx.as<int32_t>(), b_seg.as<int64_t>(), b_out.as<uint32_t>(), slot_words, b_nw.as<int32_t>());
-    BASIC_HIP_TRY(hipGetLastError());
-    int32_t nwords = 0;
-    BASIC_HIP_TRY(hipMemcpy(&nwords, b_nw.p, sizeof(nwords), hipMemcpyDeviceToHost));
-    if (nwords < 0) { set_error("rans encoder: slot overflow"); return BASIC_ERR_OVERFLOW; }
-    const int64_t nbytes = static_cast<int64_t>(nwords) * 4;
-    *out_len = nbytes;
-    if (nbytes > out_capacity) { set_error("encode_with_indexes: output buffer too small"); return BASIC_ERR_OVERFLOW; }
-    BASIC_HIP_TRY(hipMemcpy(out, b_out.as<uint32_t>() + (slot_words - nwords), nbytes, hipMemcpyDeviceToHost));
-    return BASIC_OK;
-}
-}  // namespace
 
 struct basic_rans_stream {
     const basic_rans_tables *t = nullptr;
@@ -1550,23 +1391,15 @@ int stream_decode(basic_rans_stream *s, const int32_t *indexes, int64_t n, const
 {
     BASIC_REQUIRE(s && n >= 0 && (n == 0 || (indexes && out_symbols)), "decode: bad argument");
     if (n == 0) return BASIC_OK;
-    const basic_rans_tables *t = s->t;
-    DevBuf b_idx, b_seg, b_out, b_ai, b_o0, b_o1, b_o2;
-    const size_t bytes = static_cast<size_t>(n) * sizeof(int32_t);
-    BASIC_HIP_TRY(b_idx.alloc(bytes));
-    BASIC_HIP_TRY(b_out.alloc(bytes));
-    BASIC_HIP_TRY(b_seg.alloc(2 * sizeof(int64_t)));
-    BASIC_HIP_TRY(hipMemcpy(b_idx.p, indexes, bytes, hipMemcpyHostToDevice));
-    const int64_t seg[2] = {0, n};
-    BASIC_HIP_TRY(hipMemcpy(b_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice));
+    HostCall c;
+    int rc = c.stage(nullptr, indexes, n);
+    if (rc) return rc;
     ArDev ar;
-    int rc = stage_ar(t, n, ar_indexes, ar_off0, ar_off1, ar_off2, b_ai, b_o0, b_o1, b_o2, ar);
+    rc = stage_ar(ar_source(s->t), n, ar_indexes, ar_off0, ar_off1, ar_off2, c.ar, ar);
     if (rc) return rc;
-    rc = launch_decode(t, ar, 1, nullptr, s->words.as<uint32_t>(), s->woff.as<int64_t>(), b_idx.as<int32_t>(),
-                       b_seg.as<int64_t>(), b_out.as<int32_t>(), s->state.as<uint64_t>(), s->pos.as<int64_t>());
-    if (rc) return rc;
-    BASIC_HIP_TRY(hipMemcpy(out_symbols, b_out.p, bytes, hipMemcpyDeviceToHost));
-    return BASIC_OK;
+    rc = launch_decode(s->t, ar, 1, nullptr, s->words.as<uint32_t>(), s->woff.as<int64_t>(), c.idx.as<int32_t>(),
+                       c.seg.as<int64_t>(), c.sym.as<int32_t>(), s->state.as<uint64_t>(), s->pos.as<int64_t>());
+    return rc ? rc : c.fetch(out_symbols);
 }
 }  // namespace
 

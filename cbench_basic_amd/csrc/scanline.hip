@@ -716,14 +716,6 @@ struct LayerRegs {
     int fin_bi, fin_r;    // this thread's finishing item: image, row (last layer: pair)
 };
 
-template <int kFrom, int kTo, class F> __device__ __forceinline__ void static_for(F &&f)
-{
-    if constexpr (kFrom < kTo) {
-        f(std::integral_constant<int, kFrom>{});
-        static_for<kFrom + 1, kTo>(f);
-    }
-}
-
 template <bool DECODE>
 __global__ __launch_bounds__(kThreads) void scanline_pipelined_kernel(const ScanArgs a)
 {

@@ -13,8 +13,7 @@
 // clamp / bypass split, the symbol's two transform words: one coalesced gather), the chain itself runs on wave-uniform
 // values; the state-dependent lookups hit the table set in L2 (a set of R rows is R x 2^L x 2 bytes for the encoder,
 // R x 2^L x 4 bytes for the decoder).
-#include <type_traits>
-#include "common.h"
+#include "ans_common.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -158,13 +157,6 @@ void free_tables(basic_tans_tables *t)
     delete t;
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 4); }
-    template <typename T> T *as() { return static_cast<T *>(p); }
-};
-
 }  // namespace
 
 extern "C" int basic_tans_tables_create(const int32_t *freqs, int rows, int freq_stride, const int32_t *nsym, const int32_t *offsets,
@@ -266,23 +258,8 @@ struct TansDev {
     const int2 *rowinfo;
     int rows, log, bypass, bypass_precision, max_nsym;
     int lds_words;           // > 0: the state-dependent image (encoder: next, decoder: dec) is copied to LDS by every workgroup
-    const int32_t *ar_tab;   // nullptr = no AR remap
-    int ar_k, ar_order, ar_s1;
-    const int32_t *ar_indexes, *off0, *off1;
+    ArDev ar;                // tab == nullptr: no AR remap; rows = the set's rows, no custom ops (basic_tans_tables_set_ar)
 };
-
-__device__ __forceinline__ int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// ans_interface.hpp:89-104; every index clamped so that malformed input cannot leave the tables
-__device__ __forceinline__ int32_t ar_row(const TansDev &T, int32_t a, int32_t row, int32_t v0, int32_t v1)
-{
-    a = clampi(a, 0, T.ar_k - 1);
-    row = clampi(row, 0, T.rows - 1);
-    v0 = clampi(v0, 0, T.ar_s1 - 1);
-    if (T.ar_order == 1) return T.ar_tab[(static_cast<int64_t>(a) * T.rows + row) * T.ar_s1 + v0];
-    v1 = clampi(v1, 0, T.ar_s1 - 1);
-    return T.ar_tab[((static_cast<int64_t>(a) * T.rows + row) * T.ar_s1 + v0) * T.ar_s1 + v1];
-}
 
 __device__ __forceinline__ uint32_t bcast(uint32_t v, int lane)
 {
@@ -351,14 +328,6 @@ template <bool LDS> __device__ __forceinline__ void tans_step_add(const TansDev 
     state = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(state)));
 }
 
-template <int kFrom, int kTo, class F> __device__ __forceinline__ void static_for(F &&f)
-{
-    if constexpr (kFrom < kTo) {
-        f(std::integral_constant<int, kFrom>{});
-        static_for<kFrom + 1, kTo>(f);
-    }
-}
-
 template <bool LDS> __device__ __forceinline__ void tans_step_bypass(const TansDev &T, BitSink &sink, uint32_t &state, uint32_t v, int lane)
 {
     const uint2 e = T.sym[static_cast<size_t>(T.rows) * T.max_nsym + v];
@@ -392,24 +361,12 @@ __global__ __launch_bounds__(64) void tans_encode_kernel(TansDev T, const int32_
         const int64_t i = hi - 64 + lane;
         if (hi > 0 && i >= 0) {
             int32_t row = idx[i];
-            if (T.ar_tab) {
-                const int64_t g = beg + i;
-                const int32_t a = T.ar_indexes ? T.ar_indexes[g] : 0;
-                const int32_t d0 = T.off0[g];
-                const int32_t v0 = (d0 > 0 && d0 <= i) ? sym[i - d0] + 1 : 0;
-                int32_t v1 = 0;
-                if (T.ar_order == 2) {
-                    const int32_t d1 = T.off1[g];
-                    v1 = (d1 > 0 && d1 <= i) ? sym[i - d1] + 1 : 0;
-                }
-                row = ar_row(T, a, row, v0, v1);
-            }
+            if (T.ar.tab) row = ar_remap_row<false>(T.ar, row, beg + i, i, [&](int64_t k) { return sym[k]; });
             row = clampi(row, 0, T.rows - 1);
             const int2 ri = T.rowinfo[row];
             const int32_t max_value = ri.y;
             int32_t value = sym[i] - ri.x;
-            if (value < 0) { q.raw = static_cast<uint32_t>(-2 * value - 1); value = max_value; }
-            else if (value >= max_value) { q.raw = static_cast<uint32_t>(2 * (value - max_value)); value = max_value; }
+            bypass_split(value, max_value, q.raw);
             q.is_bypass = T.bypass && value == max_value;
             const uint2 e = T.sym[static_cast<size_t>(row) * T.max_nsym + value];
             q.dbits = e.x; q.tbase = (static_cast<uint32_t>(row) << T.log) + e.y;   // e.y is an int32 offset: unsigned wrap-around adds it
@@ -428,8 +385,7 @@ __global__ __launch_bounds__(64) void tans_encode_kernel(TansDev T, const int32_
             if ((bypass_mask >> j) & 1ull) {
                 // decode order: sentinel, digit count (unary in units of maxbv), digits low first  =>  coded reversed
                 const uint32_t r = bcast(raw, j);
-                int nb = 0;
-                while (nb * bprec < 32u && (r >> (nb * bprec)) != 0u) ++nb;
+                const int nb = escape_digits(r, bprec);
                 for (int k = nb - 1; k >= 0; --k) tans_step_bypass<LDS>(T, sink, state, (r >> (k * bprec)) & maxbv, lane);
                 tans_step_bypass<LDS>(T, sink, state, static_cast<uint32_t>(nb) % maxbv, lane);
                 for (uint32_t k = 0; k < static_cast<uint32_t>(nb) / maxbv; ++k) tans_step_bypass<LDS>(T, sink, state, maxbv, lane);
@@ -574,8 +530,8 @@ __global__ __launch_bounds__(64) void tans_decode_kernel(TansDev T, const uint8_
         Rows r{0u, make_int2(0, 1)};
         const int64_t i = c0 + lane;
         if (i < n) {
-            r.row = static_cast<uint32_t>(T.ar_tab ? idx[i] : clampi(idx[i], 0, T.rows - 1));
-            if (!T.ar_tab) r.ri = T.rowinfo[r.row];
+            r.row = static_cast<uint32_t>(T.ar.tab ? idx[i] : clampi(idx[i], 0, T.rows - 1));
+            if (!T.ar.tab) r.ri = T.rowinfo[r.row];
         }
         return r;
     };
@@ -588,7 +544,7 @@ __global__ __launch_bounds__(64) void tans_decode_kernel(TansDev T, const uint8_
         const int2 ri_l = cur.ri;
         int32_t result = 0;
         const int cnt = (n - c0) < 64 ? static_cast<int>(n - c0) : 64;
-        if (!T.ar_tab && cnt == 64) {
+        if (!T.ar.tab && cnt == 64) {
             // a full chunk without AR remap, unrolled: lane ids as immediates, the row's table base prepared per lane, the
             // offset added lane-parallel after the chunk -- what stays per symbol is the lookup, the refill test, the field
             // and the bypass test
@@ -622,17 +578,11 @@ __global__ __launch_bounds__(64) void tans_decode_kernel(TansDev T, const uint8_
         for (int j = 0; j < cnt; ++j) {
             int32_t row = static_cast<int32_t>(bcast(row_l, j));
             int32_t offset, max_value;
-            if (T.ar_tab) {
-                const int64_t e = c0 + j, g = beg + e;
-                const int32_t a = T.ar_indexes ? T.ar_indexes[g] : 0;
-                const int32_t d0 = T.off0[g];
-                const int32_t v0 = (d0 > 0 && d0 <= e) ? __hip_atomic_load(out + (e - d0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 : 0;
-                int32_t v1 = 0;
-                if (T.ar_order == 2) {
-                    const int32_t d1 = T.off1[g];
-                    v1 = (d1 > 0 && d1 <= e) ? __hip_atomic_load(out + (e - d1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 : 0;
-                }
-                row = __builtin_amdgcn_readfirstlane(clampi(ar_row(T, a, row, v0, v1), 0, T.rows - 1));
+            if (T.ar.tab) {
+                const int64_t e = c0 + j;
+                row = ar_remap_row<false>(T.ar, row, beg + e, e,
+                                          [&](int64_t k) { return __hip_atomic_load(out + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); });
+                row = __builtin_amdgcn_readfirstlane(clampi(row, 0, T.rows - 1));
                 const int2 ri = T.rowinfo[row];
                 offset = __builtin_amdgcn_readfirstlane(ri.x);
                 max_value = __builtin_amdgcn_readfirstlane(ri.y);
@@ -653,10 +603,10 @@ __global__ __launch_bounds__(64) void tans_decode_kernel(TansDev T, const uint8_
                 if (raw & 1u) value = -value - 1; else value += max_value;
             }
             value += offset;
-            if (T.ar_tab) { if (lane == 0) __hip_atomic_store(out + c0 + j, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            if (T.ar.tab) { if (lane == 0) __hip_atomic_store(out + c0 + j, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
             else if (lane == j) result = value;
         }
-        if (!T.ar_tab && i < n) out[i] = result;
+        if (!T.ar.tab && i < n) out[i] = result;
     }
     if (lane == 0) status[stream] = 0;
 }
@@ -680,6 +630,26 @@ TansDev dev_view(const basic_tans_tables *t)
     return T;
 }
 
+template <bool DECODE, bool LDS> constexpr auto tans_kernel()
+{
+    if constexpr (DECODE) return &tans_decode_kernel<LDS>; else return &tans_encode_kernel<LDS>;
+}
+
+// One wavefront per stream; lds_bytes > 0: the kernel that first copies the state-dependent image to the LDS
+template <bool DECODE, class... Args> int launch_tans(TansDev T, size_t lds_bytes, int nstreams, hipStream_t st, Args... args)
+{
+    T.lds_words = static_cast<int>(lds_bytes / 4);
+    if (lds_bytes > 48 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(tans_kernel<DECODE, true>())));
+    g_last_kernel = DECODE ? (lds_bytes ? BASIC_TANS_KERNEL_DEC_LDS : BASIC_TANS_KERNEL_DEC_GLOBAL)
+                           : (lds_bytes ? BASIC_TANS_KERNEL_ENC_LDS : BASIC_TANS_KERNEL_ENC_GLOBAL);
+    if (lds_bytes) hipLaunchKernelGGL((tans_kernel<DECODE, true>()), dim3(nstreams), dim3(64), lds_bytes, st, T, args...);
+    else hipLaunchKernelGGL((tans_kernel<DECODE, false>()), dim3(nstreams), dim3(64), 0, st, T, args...);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+ArSource ar_source(const basic_tans_tables *t) { return ArSource{t->d_ar, t->ar_k, t->ar_order, t->rows, t->ar_s1, false}; }
+
 }  // namespace
 
 // Words a slot must hold for a stream of n symbols in the worst case (every symbol a bypass escape with eight digits).
@@ -699,17 +669,8 @@ extern "C" int basic_tans_encode_batch_dev(const basic_tans_tables *t, const int
     BASIC_REQUIRE(!t->d_ar, "tans_encode_batch_dev: AR remap needs the host entry point (per-element AR arrays)");
     BASIC_REQUIRE(nstreams >= 0 && slot_words >= 1 && d_seg && d_out_words && d_out_info, "tans_encode_batch_dev: bad argument");
     if (nstreams == 0) return BASIC_OK;
-    TansDev T = dev_view(t);
-    const size_t lds = tans_lds_bytes(t, false);
-    T.lds_words = static_cast<int>(lds / 4);
-    if (lds > 48 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(tans_encode_kernel<true>)));
-    g_last_kernel = lds ? BASIC_TANS_KERNEL_ENC_LDS : BASIC_TANS_KERNEL_ENC_GLOBAL;
-    if (lds) hipLaunchKernelGGL(tans_encode_kernel<true>, dim3(nstreams), dim3(64), lds, as_stream(hip_stream), T, d_symbols, d_indexes, d_seg,
-                                d_out_words, slot_words, d_out_info);
-    else hipLaunchKernelGGL(tans_encode_kernel<false>, dim3(nstreams), dim3(64), 0, as_stream(hip_stream), T, d_symbols, d_indexes, d_seg,
-                            d_out_words, slot_words, d_out_info);
-    BASIC_HIP_TRY(hipGetLastError());
-    return BASIC_OK;
+    return launch_tans<false>(dev_view(t), tans_lds_bytes(t, false), nstreams, as_stream(hip_stream), d_symbols, d_indexes, d_seg, d_out_words,
+                              slot_words, d_out_info);
 }
 
 extern "C" int basic_tans_decode_batch_dev(const basic_tans_tables *t, const uint8_t *d_bytes, const int64_t *d_byte_off,
@@ -720,49 +681,13 @@ extern "C" int basic_tans_decode_batch_dev(const basic_tans_tables *t, const uin
     BASIC_REQUIRE(!t->d_ar, "tans_decode_batch_dev: AR remap needs the host entry point (per-element AR arrays)");
     BASIC_REQUIRE(nstreams >= 0 && d_bytes && d_byte_off && d_seg && d_out_symbols && d_status, "tans_decode_batch_dev: bad argument");
     if (nstreams == 0) return BASIC_OK;
-    TansDev T = dev_view(t);
-    const size_t lds = tans_lds_bytes(t, true);
-    T.lds_words = static_cast<int>(lds / 4);
-    if (lds > 48 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(tans_decode_kernel<true>)));
-    g_last_kernel = lds ? BASIC_TANS_KERNEL_DEC_LDS : BASIC_TANS_KERNEL_DEC_GLOBAL;
-    if (lds) hipLaunchKernelGGL(tans_decode_kernel<true>, dim3(nstreams), dim3(64), lds, as_stream(hip_stream), T, d_bytes, d_byte_off, d_indexes,
-                                d_seg, d_out_symbols, d_status);
-    else hipLaunchKernelGGL(tans_decode_kernel<false>, dim3(nstreams), dim3(64), 0, as_stream(hip_stream), T, d_bytes, d_byte_off, d_indexes,
-                            d_seg, d_out_symbols, d_status);
-    BASIC_HIP_TRY(hipGetLastError());
-    return BASIC_OK;
+    return launch_tans<true>(dev_view(t), tans_lds_bytes(t, true), nstreams, as_stream(hip_stream), d_bytes, d_byte_off, d_indexes, d_seg,
+                             d_out_symbols, d_status);
 }
 
 // ---------------------------------------------------------------------------------------
 // Host-buffer drop-ins (single stream): stage -> kernel -> copy back.
 // ---------------------------------------------------------------------------------------
-namespace {
-
-int stage_ar(const basic_tans_tables *t, TansDev &T, int64_t n, const int32_t *ar_indexes, const int32_t *ar_off0, const int32_t *ar_off1,
-             DevBuf &b_ai, DevBuf &b_o0, DevBuf &b_o1)
-{
-    if (!t->d_ar) return BASIC_OK;
-    if (!ar_off0 || (t->ar_order == 2 && !ar_off1)) { set_error("ar_offsets is required for ar coding!"); return BASIC_ERR_INVALID; }
-    const size_t bytes = static_cast<size_t>(n) * sizeof(int32_t);
-    T.ar_tab = t->d_ar; T.ar_k = t->ar_k; T.ar_order = t->ar_order; T.ar_s1 = t->ar_s1;
-    if (ar_indexes) {
-        BASIC_HIP_TRY(b_ai.alloc(bytes));
-        BASIC_HIP_TRY(hipMemcpy(b_ai.p, ar_indexes, bytes, hipMemcpyHostToDevice));
-        T.ar_indexes = b_ai.as<int32_t>();
-    }
-    BASIC_HIP_TRY(b_o0.alloc(bytes));
-    BASIC_HIP_TRY(hipMemcpy(b_o0.p, ar_off0, bytes, hipMemcpyHostToDevice));
-    T.off0 = b_o0.as<int32_t>();
-    if (t->ar_order == 2) {
-        BASIC_HIP_TRY(b_o1.alloc(bytes));
-        BASIC_HIP_TRY(hipMemcpy(b_o1.p, ar_off1, bytes, hipMemcpyHostToDevice));
-        T.off1 = b_o1.as<int32_t>();
-    }
-    return BASIC_OK;
-}
-
-}  // namespace
-
 // TansEncoder::encode_with_indexes (tans.cpp:527-680).  capacity_syms = the symbol count the reference sizes its output
 // buffer with (-1: n; flush(): the cached count incl. bypass digits, tans.cpp:686): a capacity of 8 bytes or less is the
 // reference's "Destination buffer is too small" error, and a stream of capacity - 8 whole bytes or more is "not storable"
@@ -777,31 +702,19 @@ extern "C" int basic_tans_encode_host(const basic_tans_tables *t, const int32_t 
     const int64_t cap = (capacity_syms < 0 ? n : capacity_syms) * t->log / 8;
     BASIC_REQUIRE(cap > 8, "Destination buffer is too small");
     const int64_t slot_words = basic_tans_encode_bound_words(t, n);
-    DevBuf b_sym, b_idx, b_seg, b_out, b_info, b_ai, b_o0, b_o1;
-    const size_t bytes = static_cast<size_t>(n) * sizeof(int32_t);
-    BASIC_HIP_TRY(b_sym.alloc(bytes));
-    BASIC_HIP_TRY(b_idx.alloc(bytes));
-    BASIC_HIP_TRY(b_seg.alloc(2 * sizeof(int64_t)));
+    HostCall c;
+    DevBuf b_out, b_info;
+    int rc = c.stage(symbols, indexes, n);
+    if (rc) return rc;
     BASIC_HIP_TRY(b_out.alloc(static_cast<size_t>(slot_words) * 4));
     BASIC_HIP_TRY(b_info.alloc(2 * sizeof(int64_t)));
-    if (n) {
-        BASIC_HIP_TRY(hipMemcpy(b_sym.p, symbols, bytes, hipMemcpyHostToDevice));
-        BASIC_HIP_TRY(hipMemcpy(b_idx.p, indexes, bytes, hipMemcpyHostToDevice));
-    }
-    const int64_t seg[2] = {0, n};
-    BASIC_HIP_TRY(hipMemcpy(b_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice));
     TansDev T = dev_view(t);
-    int rc = stage_ar(t, T, n, ar_indexes, ar_off0, ar_off1, b_ai, b_o0, b_o1);
+    rc = stage_ar(ar_source(t), n, ar_indexes, ar_off0, ar_off1, nullptr, c.ar, T.ar);
     if (rc) return rc;
     const size_t lds = n >= 2048 ? tans_lds_bytes(t, false) : 0;   // short streams: the copy would cost more than it saves
-    T.lds_words = static_cast<int>(lds / 4);
-    if (lds > 48 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(tans_encode_kernel<true>)));
-    g_last_kernel = lds ? BASIC_TANS_KERNEL_ENC_LDS : BASIC_TANS_KERNEL_ENC_GLOBAL;
-    if (lds) hipLaunchKernelGGL(tans_encode_kernel<true>, dim3(1), dim3(64), lds, nullptr, T, b_sym.as<int32_t>(), b_idx.as<int32_t>(), b_seg.as<int64_t>(),
-                                b_out.as<uint32_t>(), slot_words, b_info.as<int64_t>());
-    else hipLaunchKernelGGL(tans_encode_kernel<false>, dim3(1), dim3(64), 0, nullptr, T, b_sym.as<int32_t>(), b_idx.as<int32_t>(), b_seg.as<int64_t>(),
-                            b_out.as<uint32_t>(), slot_words, b_info.as<int64_t>());
-    BASIC_HIP_TRY(hipGetLastError());
+    rc = launch_tans<false>(T, lds, 1, nullptr, c.sym.as<int32_t>(), c.idx.as<int32_t>(), c.seg.as<int64_t>(), b_out.as<uint32_t>(), slot_words,
+                            b_info.as<int64_t>());
+    if (rc) return rc;
     int64_t info[2] = {0, 0};
     BASIC_HIP_TRY(hipMemcpy(info, b_info.p, sizeof(info), hipMemcpyDeviceToHost));
     if (info[0] < 0) { set_error("tans encoder: slot overflow"); return BASIC_ERR_OVERFLOW; }
@@ -823,36 +736,24 @@ extern "C" int basic_tans_decode_host(const basic_tans_tables *t, const uint8_t 
     BASIC_REQUIRE(n >= 0 && (n == 0 || (indexes && out_symbols)), "decode_with_indexes: bad argument");
     BASIC_REQUIRE(stream && stream_len >= 1, "Src size is incorrect");
     BASIC_REQUIRE(stream[stream_len - 1] != 0, "Error (generic)");   // end mark not present
-    DevBuf b_bytes, b_boff, b_idx, b_seg, b_out, b_status, b_ai, b_o0, b_o1;
-    const size_t bytes = static_cast<size_t>(n) * sizeof(int32_t);
-    BASIC_HIP_TRY(b_bytes.alloc(static_cast<size_t>(stream_len)));
-    BASIC_HIP_TRY(b_boff.alloc(2 * sizeof(int64_t)));
-    BASIC_HIP_TRY(b_idx.alloc(bytes));
-    BASIC_HIP_TRY(b_seg.alloc(2 * sizeof(int64_t)));
-    BASIC_HIP_TRY(b_out.alloc(bytes));
-    BASIC_HIP_TRY(b_status.alloc(sizeof(int32_t)));
-    BASIC_HIP_TRY(hipMemcpy(b_bytes.p, stream, stream_len, hipMemcpyHostToDevice));
-    const int64_t boff[2] = {0, stream_len}, seg[2] = {0, n};
-    BASIC_HIP_TRY(hipMemcpy(b_boff.p, boff, sizeof(boff), hipMemcpyHostToDevice));
-    BASIC_HIP_TRY(hipMemcpy(b_seg.p, seg, sizeof(seg), hipMemcpyHostToDevice));
-    if (n) BASIC_HIP_TRY(hipMemcpy(b_idx.p, indexes, bytes, hipMemcpyHostToDevice));
-    TansDev T = dev_view(t);
-    int rc = stage_ar(t, T, n, ar_indexes, ar_off0, ar_off1, b_ai, b_o0, b_o1);
+    HostCall c;
+    DevBuf b_bytes, b_boff, b_status;
+    const int64_t boff[2] = {0, stream_len};
+    int rc = c.stage(nullptr, indexes, n);
     if (rc) return rc;
-    const size_t lds = n >= 2048 ? tans_lds_bytes(t, true) : 0;
-    T.lds_words = static_cast<int>(lds / 4);
-    if (lds > 48 * 1024) BASIC_HIP_TRY(ensure_max_lds(reinterpret_cast<const void *>(tans_decode_kernel<true>)));
-    g_last_kernel = lds ? BASIC_TANS_KERNEL_DEC_LDS : BASIC_TANS_KERNEL_DEC_GLOBAL;
-    if (lds) hipLaunchKernelGGL(tans_decode_kernel<true>, dim3(1), dim3(64), lds, nullptr, T, b_bytes.as<uint8_t>(), b_boff.as<int64_t>(), b_idx.as<int32_t>(),
-                                b_seg.as<int64_t>(), b_out.as<int32_t>(), b_status.as<int32_t>());
-    else hipLaunchKernelGGL(tans_decode_kernel<false>, dim3(1), dim3(64), 0, nullptr, T, b_bytes.as<uint8_t>(), b_boff.as<int64_t>(), b_idx.as<int32_t>(),
-                            b_seg.as<int64_t>(), b_out.as<int32_t>(), b_status.as<int32_t>());
-    BASIC_HIP_TRY(hipGetLastError());
+    BASIC_HIP_TRY(upload(b_bytes, stream, static_cast<size_t>(stream_len)));
+    BASIC_HIP_TRY(upload(b_boff, boff, 2));
+    BASIC_HIP_TRY(b_status.alloc(sizeof(int32_t)));
+    TansDev T = dev_view(t);
+    rc = stage_ar(ar_source(t), n, ar_indexes, ar_off0, ar_off1, nullptr, c.ar, T.ar);
+    if (rc) return rc;
+    rc = launch_tans<true>(T, n >= 2048 ? tans_lds_bytes(t, true) : 0, 1, nullptr, b_bytes.as<uint8_t>(), b_boff.as<int64_t>(), c.idx.as<int32_t>(),
+                           c.seg.as<int64_t>(), c.sym.as<int32_t>(), b_status.as<int32_t>());
+    if (rc) return rc;
     int32_t status = 0;
     BASIC_HIP_TRY(hipMemcpy(&status, b_status.p, sizeof(status), hipMemcpyDeviceToHost));
     if (status) { set_error("Error (generic)"); return BASIC_ERR_INVALID; }
-    if (n) BASIC_HIP_TRY(hipMemcpy(out_symbols, b_out.p, bytes, hipMemcpyDeviceToHost));
-    return BASIC_OK;
+    return c.fetch(out_symbols);
 }
 
 extern "C" int basic_tans_last_launch(int *kernel)

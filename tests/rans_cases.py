@@ -3,7 +3,7 @@
 The tables are built from CDF ROWS, not from random frequencies, so that a frequency of 1, 2^p - 1 or 2^p, a start of 2^p - 1, a
 row of exactly 64 / 65 / 4096 / 4097 entries and a precision below 12 are placed where they are wanted.  Every case names the
 kernels it must reach (BASIC_RANS_KERNEL_* of include/basic_hip.h, without the prefix); predict() restates the thresholds of
-upload_tables / launch_decode in rans.hip, and tests/test_cpu_rans_cases.py holds the two against each other, so that a case
+upload_tables / launch_encode / launch_decode in rans.hip, and tests/test_cpu_rans_cases.py holds the two against each other, so that a case
 that drifts off its path fails on the CPU before tests/test_gpu_rans_paths.py asserts the path on the GPU.
 
 Stream shapes, the same for every table: a ragged batch of 19 streams (a part-filled last workgroup at 2, 4, 8 and 16 streams
@@ -216,7 +216,7 @@ def image_bytes(c):
 
 
 def predict(c):
-    """(encoder, decoder) kernel names the library must choose for case c."""
+    """(encoder, decoder) kernel names the library must choose for case c (launch_encode, launch_decode of rans.hip)."""
     one = 1 << c.precision
     fast_dec = int(c.sizes.max()) <= 4096 and image_bytes(c) <= FAST_IMAGE_BUDGET and c.precision >= FAST_MIN_PRECISION
     lds = packed_bytes(c) <= LDS_TABLE_BUDGET

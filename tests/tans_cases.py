@@ -85,7 +85,7 @@ PATH_CONFIGS = ((12, 8), (12, 9), (12, 17), (12, 18), (9, 5))
 
 
 def path_kernels(L, nd, bypass=True):
-    """(encoder, decoder) BASIC_TANS_KERNEL_* names of the batched entry points: tans_lds_bytes of tans.hip, restated."""
+    """(encoder, decoder) BASIC_TANS_KERNEL_* names of the batched entry points: tans_lds_bytes as launch_tans of tans.hip gets it, restated."""
     rows = nd + (1 if bypass else 0)
     fits = lambda per_state: rows * (1 << L) * per_state <= 144 * 1024
     return "ENC_LDS" if fits(2) else "ENC_GLOBAL", "DEC_LDS" if fits(4) else "DEC_GLOBAL"

@@ -1,6 +1,6 @@
 """Every rANS and tANS launch path against the oracle's bytes, with the kernel that ran asserted.
 
-    path                                 selector (rans.hip / tans.hip)                              cases (tests/rans_cases.py)
+    path                                 selector (launch_encode / launch_decode / launch_tans)      cases (tests/rans_cases.py)
     rans_encode_fast_kernel<W>           fast_enc_ok: <= 2048 rows, every frequency in 1 .. 2^p,     extreme16*, lowp7 .. lowp15, row_widths_no2,
       W = 1, 2, 4, 8, 16                 precision >= 7; W from basic_rans_set_waves                 image_too_big, global_tables, rows2048, resume_*
     rans_encode_kernel                   !fast_enc_ok                                                lowp1 .. lowp6, row_widths, row_widths_4097,
