@@ -23,6 +23,10 @@ shared equally among its items.
 ``metrics_on_uint8`` (not in the reference; INTEGRATION.md, "8-bit images"): the distortion is taken from the 8-bit picture the codec
 hands out -- ``codec.decompress(compressed, output_dtype=torch.uint8)``, converted inside the timed region -- against the 8-bit item
 (a float item: quantised once), as exact integers; ``on_reconstruction`` receives that very picture after the pass.
+
+``testing_tile=(th, tw)`` (not in the reference; INTEGRATION.md, "Tiled pictures"): every item, a batch-1 picture, is coded as
+independent tiles (``codec.compress_tiled`` / ``decompress_tiled``); ``compressed_length`` is the length of the container and the
+distortion that of the whole pasted picture.  It does not combine with ``testing_coalesce_items``.
 """
 import copy
 import csv
@@ -43,7 +47,7 @@ class BasicLosslessCompressionBenchmark:
                  testing_variable_rate_levels=None, testing_variable_rate_bj_delta_metric=None,
                  testing_complexity_levels=None, force_testing_device="cuda", output_dir=None, num_repeats=1,
                  num_testing_workers=0, codec_builder=None, worker_transform_token=None, testing_coalesce_items=0,
-                 metrics_on_uint8=False, on_reconstruction=None, **kwargs):
+                 metrics_on_uint8=False, on_reconstruction=None, testing_tile=None, **kwargs):
         self.codec = codec
         self.dataloader = dataloader
         self.distortion_metric = distortion_metric
@@ -79,6 +83,14 @@ class BasicLosslessCompressionBenchmark:
         self.on_reconstruction = on_reconstruction
         if on_reconstruction is not None and not self.metrics_on_uint8:
             raise ValueError("on_reconstruction hands out the 8-bit picture the metric saw: it needs metrics_on_uint8=True")
+        # tiled pictures ("Tiled pictures"): every batch-1 item goes through compress_tiled / decompress_tiled
+        if testing_tile is not None:
+            testing_tile = (testing_tile, testing_tile) if isinstance(testing_tile, int) else tuple(int(v) for v in testing_tile)
+            if len(testing_tile) != 2 or min(testing_tile) < 1:
+                raise ValueError(f"testing_tile is (th, tw), positive, not {testing_tile!r}")
+            if self.testing_coalesce_items > 1:
+                raise ValueError("testing_tile codes one picture per call: it does not combine with testing_coalesce_items")
+        self.testing_tile = testing_tile
         self._level_prefix = ""
         self._pictures = {}
         self._pool = None
@@ -147,7 +159,17 @@ class BasicLosslessCompressionBenchmark:
             return data_input
         return self._to_f32(data_target) if self.metrics_on_uint8 else data_target
 
+    def _compress(self, codec, data):
+        if self.testing_tile is None:
+            return codec.compress(data)
+        if not isinstance(data, torch.Tensor) or data.dim() != 4 or data.shape[0] != 1:
+            raise ValueError("testing_tile codes a dataset of batch-1 pictures ([1, C, H, W]); got "
+                             f"{tuple(data.shape) if isinstance(data, torch.Tensor) else type(data).__name__}")
+        return codec.compress_tiled(data, tile=self.testing_tile)
+
     def _decompress(self, codec, compressed):
+        if self.testing_tile is not None:
+            return codec.decompress_tiled(compressed, output_dtype=torch.uint8 if self.metrics_on_uint8 else None)
         return codec.decompress(compressed, output_dtype=torch.uint8) if self.metrics_on_uint8 else codec.decompress(compressed)
 
     def _deliver_pictures(self):
@@ -177,7 +199,7 @@ class BasicLosslessCompressionBenchmark:
                 return
         self._sync()
         t0 = time.time()
-        compressed = codec.compress(data_input)
+        compressed = self._compress(codec, data_input)
         self._sync()
         time_compress = time.time() - t0
         compressed_length = self._estimate_byte_length(compressed)

@@ -40,9 +40,24 @@ class GeneralCodec(HotPathModule, CodecInterface, VariableRateCodecInterface, Va
         with self.profiler.start_time_profile("time_decompress_entropy_coder"):
             return self.entropy_coder.decode_items(strings, *args, max_batch=max_batch, **kwargs)
 
+    def compress_tiled(self, image, *args, tile=(512, 512), max_batch=None, **kwargs):
+        """One picture ``[1, C, H, W]`` -> the container of its independently coded tiles (utils/tiling.py), tile k's string exactly
+        ``self.compress(image[:, :, y:y + h, x:x + w])`` (entropy coder's ``encode_tiled``)."""
+        with self.profiler.start_time_profile("time_compress_entropy_coder"):
+            return self.entropy_coder.encode_tiled(image, *args, tile=tile, max_batch=max_batch, **kwargs)
+
+    def decompress_tiled(self, data, *args, **kwargs):
+        """A container of compress_tiled -> the picture at its own size, or the ``region`` of it (entropy coder's ``decode_tiled``)."""
+        with self.profiler.start_time_profile("time_decompress_entropy_coder"):
+            return self.entropy_coder.decode_tiled(data, *args, **kwargs)
+
     @property
     def last_items_calls(self):
         return self.entropy_coder.last_items_calls
+
+    @property
+    def last_tiles_decoded(self):
+        return self.entropy_coder.last_tiles_decoded
 
     def forward(self, data, *args, **kwargs):
         return self.entropy_coder(data, *args, **kwargs)

@@ -93,9 +93,19 @@ class GroupedVariableRateCodec(HotPathModule, CodecInterface, VariableRateCodecI
     def decompress_items(self, strings, *args, **kwargs):
         return self.active_codec.decompress_items(strings, *args, **kwargs)
 
+    def compress_tiled(self, image, *args, **kwargs):
+        return self.active_codec.compress_tiled(image, *args, **kwargs)
+
+    def decompress_tiled(self, data, *args, **kwargs):
+        return self.active_codec.decompress_tiled(data, *args, **kwargs)
+
     @property
     def last_items_calls(self):
         return self.active_codec.last_items_calls
+
+    @property
+    def last_tiles_decoded(self):
+        return self.active_codec.last_tiles_decoded
 
     def forward(self, *args, **kwargs):
         # every member is run (the reference needs that for joint training, base.py:213-221); the active one's result counts

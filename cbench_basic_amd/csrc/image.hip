@@ -13,6 +13,7 @@
 // rounded) when it builds the table in constant memory, a workgroup copies it to LDS once.  float32 -> uint8 is fmax / fmin /
 // one multiply / v_rndne; nothing is contracted into it.
 // The third entry measures such pictures: the exact per-channel sum of squared differences of two uint8 batches (further down).
+// The last two cut float tiles out of one uint8 picture and paste reconstructed tiles back into one (section 8c, at the end).
 #include <utility>
 
 #include "common.h"
@@ -49,6 +50,31 @@ __device__ __forceinline__ uint32_t quantise(float x)
     return static_cast<uint32_t>(rintf(c * 255.0f));
 }
 
+// A run is four consecutive pixels of C interleaved channels, C whole dwords (little-endian: sample p * C + c of the run is pixel
+// p, channel c).  Channel c of a run as four floats, and the other way.  Shared by the batch kernels and the tile kernels.
+template <int C>
+__device__ __forceinline__ float4 run_to_f32(const Words<C> &in, int c, const float *lut)
+{
+    float o[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int byte = p * C + c;
+        o[p] = lut[(in.w[byte / 4] >> (8 * (byte % 4))) & 0xffu];
+    }
+    return make_float4(o[0], o[1], o[2], o[3]);
+}
+
+template <int C>
+__device__ __forceinline__ void run_from_f32(Words<C> &out, int c, const float4 &v)   // ORs into `out`: clear it first
+{
+    const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int byte = p * C + c;
+        out.w[byte / 4] |= quantise(x[p]) << (8 * (byte % 4));
+    }
+}
+
 // run r = (image b, pixels 4 q .. 4 q + 3), runs = runs_per_image * batch.  uint8 side: dwords [r * C, r * C + C).  float
 // side: 16-byte vector q of plane b * C + c.  (C = 1: runs_per_image = all runs, both sides flat.)
 template <int C>
@@ -61,15 +87,7 @@ __global__ __launch_bounds__(kBlock) void u8_to_f32_wide_kernel(const uint32_t *
         const Words<C> in = *reinterpret_cast<const Words<C> *>(src + r * C);
         const int64_t b = C == 1 ? 0 : r / runs_per_image, q = C == 1 ? r : r % runs_per_image;
 #pragma unroll
-        for (int c = 0; c < C; ++c) {
-            float o[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int byte = p * C + c;   // little-endian: sample `byte` of the run
-                o[p] = lut[(in.w[byte / 4] >> (8 * (byte % 4))) & 0xffu];
-            }
-            dst[(b * C + c) * runs_per_image + q] = make_float4(o[0], o[1], o[2], o[3]);
-        }
+        for (int c = 0; c < C; ++c) dst[(b * C + c) * runs_per_image + q] = run_to_f32<C>(in, c, lut);
     }
 }
 
@@ -83,15 +101,7 @@ __global__ __launch_bounds__(kBlock) void f32_to_u8_wide_kernel(const float4 *__
 #pragma unroll
         for (int k = 0; k < C; ++k) out.w[k] = 0u;
 #pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float4 v = src[(b * C + c) * runs_per_image + q];
-            const float x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int byte = p * C + c;
-                out.w[byte / 4] |= quantise(x[p]) << (8 * (byte % 4));
-            }
-        }
+        for (int c = 0; c < C; ++c) run_from_f32<C>(out, c, src[(b * C + c) * runs_per_image + q]);
         *reinterpret_cast<Words<C> *>(dst + r * C) = out;
     }
 }
@@ -391,5 +401,220 @@ extern "C" int basic_image_sse_u8_dev(const uint8_t *d_a, int layout_a, const ui
                            pixels, sse);
     }
     BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+// ---- tiles of one picture (include/basic_hip.h section 8c) -----------------------------------------------------------------
+// A tile group is a regular ny x nx grid of th x tw tiles inside ONE uint8 picture; tile t = i * nx + j has its origin at
+// (y0 + i * step_y, x0 + j * step_x).  The float side is a batch of tiles, [ny * nx][C][fh][fw]: fh x fw = th x tw when tiles are
+// cut out of the picture, sh x sw >= th x tw when reconstructions are pasted back (their top-left th x tw).  One launch per call:
+//   wide  : a lane owns four consecutive samples of one tile row, run r = (tile, [channel,] row, q) with q < tw / 4.  PLANAR
+//           (C = 1: BASIC_IMAGE_CHW of any channel count) one dword against one 16-byte vector; C = 3, 4 (BASIC_IMAGE_HWC) the
+//           C dwords of four pixels against one vector per plane.  img_w, x0, step_x, tw (and sw) are multiples of 4, so every
+//           dword of the picture and every vector of the batch is a whole one.
+//   scalar: one sample per lane per step; cut walks the float side, paste the uint8 side (consecutive byte stores).
+// The values come from the table, quantise() and the run helpers above: the two families cannot drift apart.
+namespace {
+
+struct TileGroup {
+    int64_t img_h, img_w;                  // the picture
+    int64_t y0, x0, step_y, step_x, nx;    // the grid
+    int64_t th, tw;                        // a tile
+    int64_t fh, fw;                        // a tile's plane on the float side
+    int64_t channels;
+};
+
+thread_local int g_tiles_last_path = -1;   // basic_image_tiles_last_path: 0 scalar, 1 wide, -1 before any call
+
+// run r of a wide launch -> first sample: offset on the uint8 side (channel 0 when C > 1) and on the float side (plane stride
+// fh * fw when C > 1).  Both in samples; both multiples of 4.
+template <int C>
+__device__ __forceinline__ void locate_run(const TileGroup &g, int64_t r, int64_t *u8, int64_t *f32)
+{
+    const int64_t qn = g.tw / 4;
+    const int64_t q = r % qn, job = r / qn;
+    const int64_t row = job % g.th, t = job / g.th;
+    const int64_t c = C == 1 ? t % g.channels : 0, tile = C == 1 ? t / g.channels : t;
+    const int64_t y = g.y0 + (tile / g.nx) * g.step_y + row, x = g.x0 + (tile % g.nx) * g.step_x + 4 * q;
+    *u8 = C == 1 ? (c * g.img_h + y) * g.img_w + x : (y * g.img_w + x) * C;
+    *f32 = ((tile * g.channels + c) * g.fh + row) * g.fw + 4 * q;
+}
+
+template <int C>
+__global__ __launch_bounds__(kBlock) void tiles_u8_to_f32_wide_kernel(const uint32_t *__restrict__ img, float4 *__restrict__ dst,
+                                                                       TileGroup g, int64_t runs)
+{
+    __shared__ float lut[256];
+    load_table(lut);
+    const int64_t plane4 = g.fh * g.fw / 4;
+    for (int64_t r = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; r < runs; r += static_cast<int64_t>(gridDim.x) * kBlock) {
+        int64_t u, f;
+        locate_run<C>(g, r, &u, &f);
+        const Words<C> in = *reinterpret_cast<const Words<C> *>(img + u / 4);
+#pragma unroll
+        for (int c = 0; c < C; ++c) dst[f / 4 + c * plane4] = run_to_f32<C>(in, c, lut);
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(kBlock) void tiles_f32_to_u8_wide_kernel(const float4 *__restrict__ src, uint32_t *__restrict__ img,
+                                                                       TileGroup g, int64_t runs)
+{
+    const int64_t plane4 = g.fh * g.fw / 4;
+    for (int64_t r = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; r < runs; r += static_cast<int64_t>(gridDim.x) * kBlock) {
+        int64_t u, f;
+        locate_run<C>(g, r, &u, &f);
+        Words<C> out;
+#pragma unroll
+        for (int k = 0; k < C; ++k) out.w[k] = 0u;
+#pragma unroll
+        for (int c = 0; c < C; ++c) run_from_f32<C>(out, c, src[f / 4 + c * plane4]);
+        *reinterpret_cast<Words<C> *>(img + u / 4) = out;
+    }
+}
+
+// sample (tile, c, row, col) of a group -> its offsets on the two sides
+__device__ __forceinline__ void locate_sample(const TileGroup &g, int hwc, int64_t tile, int64_t c, int64_t row, int64_t col, int64_t *u8,
+                                              int64_t *f32)
+{
+    const int64_t y = g.y0 + (tile / g.nx) * g.step_y + row, x = g.x0 + (tile % g.nx) * g.step_x + col;
+    *u8 = hwc ? (y * g.img_w + x) * g.channels + c : (c * g.img_h + y) * g.img_w + x;
+    *f32 = ((tile * g.channels + c) * g.fh + row) * g.fw + col;
+}
+
+// walks the float side, [tile][c][row][col] (fh x fw = th x tw here)
+__global__ __launch_bounds__(kBlock) void tiles_u8_to_f32_scalar_kernel(const uint8_t *__restrict__ img, float *__restrict__ dst, int hwc,
+                                                                         TileGroup g, int64_t total)
+{
+    __shared__ float lut[256];
+    load_table(lut);
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * kBlock) {
+        const int64_t col = i % g.tw, job = i / g.tw;
+        const int64_t row = job % g.th, t = job / g.th;
+        int64_t u, f;
+        locate_sample(g, hwc, t / g.channels, t % g.channels, row, col, &u, &f);
+        dst[f] = lut[img[u]];
+    }
+}
+
+// walks the uint8 side of the tiles ([tile][c][row][col], hwc: [tile][row][col][c]), so that a wavefront's byte stores are consecutive
+__global__ __launch_bounds__(kBlock) void tiles_f32_to_u8_scalar_kernel(const float *__restrict__ src, uint8_t *__restrict__ img, int hwc,
+                                                                         TileGroup g, int64_t total)
+{
+    for (int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; j < total; j += static_cast<int64_t>(gridDim.x) * kBlock) {
+        int64_t tile, c, row, col;
+        if (hwc) {
+            c = j % g.channels;
+            const int64_t t = j / g.channels;
+            col = t % g.tw;
+            row = t / g.tw % g.th;
+            tile = t / g.tw / g.th;
+        } else {
+            col = j % g.tw;
+            const int64_t job = j / g.tw, t = job / g.th;
+            row = job % g.th;
+            c = t % g.channels;
+            tile = t / g.channels;
+        }
+        int64_t u, f;
+        locate_sample(g, hwc, tile, c, row, col, &u, &f);
+        img[u] = static_cast<uint8_t>(quantise(src[f]));
+    }
+}
+
+struct TilePlan {
+    TileGroup g;
+    int64_t total;   // samples of the tiles: ny * nx * channels * th * tw
+    int hwc;
+    int wide_c;      // channels of the wide kernel (1: planar), or 0: sample by sample
+};
+
+// the checks both directions share; fh x fw is the float side's plane (th x tw for the cut)
+int plan_tiles(const void *d_img, const void *d_f32, int layout, int channels, int img_h, int img_w, int y0, int x0, int step_y, int step_x,
+               int ny, int nx, int th, int tw, int fh, int fw, const char *what, TilePlan *p)
+{
+    const std::string who(what);
+    BASIC_REQUIRE(d_img && d_f32, who + ": null pointer");
+    BASIC_REQUIRE(layout == BASIC_IMAGE_CHW || layout == BASIC_IMAGE_HWC, who + ": layout is BASIC_IMAGE_CHW or BASIC_IMAGE_HWC");
+    BASIC_REQUIRE(channels >= 1 && img_h >= 1 && img_w >= 1 && ny >= 1 && nx >= 1 && th >= 1 && tw >= 1,
+                  who + ": channels, the picture's size, ny, nx, th and tw must be positive");
+    BASIC_REQUIRE(step_y >= 1 && step_x >= 1, who + ": step_y and step_x must be positive");
+    BASIC_REQUIRE(y0 >= 0 && x0 >= 0, who + ": y0 and x0 must not be negative");
+    BASIC_REQUIRE(step_y >= th && step_x >= tw, who + ": a step smaller than the tile (overlapping tiles)");
+    BASIC_REQUIRE(fh >= th && fw >= tw, who + ": the source tiles are smaller than th x tw");
+    BASIC_REQUIRE(static_cast<int64_t>(y0) + static_cast<int64_t>(ny - 1) * step_y + th <= img_h &&
+                      static_cast<int64_t>(x0) + static_cast<int64_t>(nx - 1) * step_x + tw <= img_w,
+                  who + ": the last tile leaves the picture");
+    BASIC_REQUIRE(reinterpret_cast<uintptr_t>(d_f32) % sizeof(float) == 0, who + ": the float32 pointer is not float-aligned");
+    // samples of the float side (the larger of the two): planes * fh * fw <= 2^40, no product overflows on the way
+    const int64_t planes = static_cast<int64_t>(ny) * nx;   // < 2^62
+    BASIC_REQUIRE(planes <= kMaxSamples / channels, who + ": more than 2^40 samples");
+    const int64_t plane = static_cast<int64_t>(fh) * fw;
+    BASIC_REQUIRE(planes * channels <= kMaxSamples / plane, who + ": more than 2^40 samples");
+    // offsets into the picture stay far inside 64 bits
+    BASIC_REQUIRE(static_cast<int64_t>(img_h) * img_w <= (int64_t(1) << 60) / channels, who + ": the picture is too large");
+    TileGroup &g = p->g;
+    g.img_h = img_h, g.img_w = img_w;
+    g.y0 = y0, g.x0 = x0, g.step_y = step_y, g.step_x = step_x, g.nx = nx;
+    g.th = th, g.tw = tw, g.fh = fh, g.fw = fw;
+    g.channels = channels;
+    p->total = planes * channels * th * tw;
+    p->hwc = layout == BASIC_IMAGE_HWC && channels > 1;   // one channel: the two layouts coincide
+    const bool aligned = reinterpret_cast<uintptr_t>(d_img) % 4 == 0 && reinterpret_cast<uintptr_t>(d_f32) % 16 == 0 && img_w % 4 == 0 &&
+                         x0 % 4 == 0 && step_x % 4 == 0 && tw % 4 == 0 && fw % 4 == 0;
+    p->wide_c = !aligned ? 0 : !p->hwc ? 1 : (channels == 3 || channels == 4) ? channels : 0;
+    return BASIC_OK;
+}
+
+}  // namespace
+
+extern "C" int basic_image_tiles_u8_to_f32_dev(const uint8_t *d_img, int layout, int channels, int img_h, int img_w, int y0, int x0,
+                                               int step_y, int step_x, int ny, int nx, int th, int tw, float *d_dst, void *hip_stream)
+{
+    TilePlan p;
+    int rc = plan_tiles(d_img, d_dst, layout, channels, img_h, img_w, y0, x0, step_y, step_x, ny, nx, th, tw, th, tw, "image_tiles_u8_to_f32", &p);
+    if (rc) return rc;
+    rc = require_device();
+    if (rc) return rc;
+    hipStream_t st = as_stream(hip_stream);
+    const uint32_t *img4 = reinterpret_cast<const uint32_t *>(d_img);
+    float4 *dst4 = reinterpret_cast<float4 *>(d_dst);
+    const int64_t runs = p.wide_c == 1 ? p.total / 4 : p.total / 4 / channels;
+    if (p.wide_c == 1) hipLaunchKernelGGL(tiles_u8_to_f32_wide_kernel<1>, grid_for(runs), dim3(kBlock), 0, st, img4, dst4, p.g, runs);
+    else if (p.wide_c == 3) hipLaunchKernelGGL(tiles_u8_to_f32_wide_kernel<3>, grid_for(runs), dim3(kBlock), 0, st, img4, dst4, p.g, runs);
+    else if (p.wide_c == 4) hipLaunchKernelGGL(tiles_u8_to_f32_wide_kernel<4>, grid_for(runs), dim3(kBlock), 0, st, img4, dst4, p.g, runs);
+    else hipLaunchKernelGGL(tiles_u8_to_f32_scalar_kernel, grid_for(p.total), dim3(kBlock), 0, st, d_img, d_dst, p.hwc, p.g, p.total);
+    g_tiles_last_path = p.wide_c ? 1 : 0;
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_image_tiles_f32_to_u8_dev(const float *d_src, int sh, int sw, int channels, int y0, int x0, int step_y, int step_x,
+                                               int ny, int nx, int th, int tw, uint8_t *d_img, int layout, int img_h, int img_w,
+                                               void *hip_stream)
+{
+    TilePlan p;
+    BASIC_REQUIRE(sh >= 1 && sw >= 1, "image_tiles_f32_to_u8: sh and sw must be positive");
+    int rc = plan_tiles(d_img, d_src, layout, channels, img_h, img_w, y0, x0, step_y, step_x, ny, nx, th, tw, sh, sw, "image_tiles_f32_to_u8", &p);
+    if (rc) return rc;
+    rc = require_device();
+    if (rc) return rc;
+    hipStream_t st = as_stream(hip_stream);
+    const float4 *src4 = reinterpret_cast<const float4 *>(d_src);
+    uint32_t *img4 = reinterpret_cast<uint32_t *>(d_img);
+    const int64_t runs = p.wide_c == 1 ? p.total / 4 : p.total / 4 / channels;
+    if (p.wide_c == 1) hipLaunchKernelGGL(tiles_f32_to_u8_wide_kernel<1>, grid_for(runs), dim3(kBlock), 0, st, src4, img4, p.g, runs);
+    else if (p.wide_c == 3) hipLaunchKernelGGL(tiles_f32_to_u8_wide_kernel<3>, grid_for(runs), dim3(kBlock), 0, st, src4, img4, p.g, runs);
+    else if (p.wide_c == 4) hipLaunchKernelGGL(tiles_f32_to_u8_wide_kernel<4>, grid_for(runs), dim3(kBlock), 0, st, src4, img4, p.g, runs);
+    else hipLaunchKernelGGL(tiles_f32_to_u8_scalar_kernel, grid_for(p.total), dim3(kBlock), 0, st, d_src, d_img, p.hwc, p.g, p.total);
+    g_tiles_last_path = p.wide_c ? 1 : 0;
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_image_tiles_last_path(int *path)
+{
+    BASIC_REQUIRE(path, "image_tiles_last_path: null argument");
+    *path = g_tiles_last_path;
     return BASIC_OK;
 }

@@ -545,6 +545,16 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         return out
 
     @staticmethod
+    def _split_string(data, n, framing):
+        """The n batch-1 strings of a batch's string, node by node (framing: _items_framing())."""
+        return item_framing.split_codec_string(data, n, [(lambda body, k, c=c, ctx=ctx: c.split_items(body, k, **ctx)) for c, ctx in framing])
+
+    @staticmethod
+    def _merge_strings(strings, framing):
+        """Inverse of _split_string: batch-1 strings -> the string of the batch of them."""
+        return item_framing.merge_codec_strings(strings, [(lambda bodies, c=c, ctx=ctx: c.merge_items(bodies, **ctx)) for c, ctx in framing])
+
+    @staticmethod
     def _check_item(x):
         if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[0] != 1:
             raise ValueError("an item is a [1, C, H, W] tensor" + (f", not {tuple(x.shape)}" if isinstance(x, torch.Tensor) else ""))
@@ -579,9 +589,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                 batch = torch.empty((len(chunk),) + tuple(first.shape[1:]), dtype=first.dtype, device=self.device)
             for j, i in enumerate(chunk):
                 batch[j:j + 1].copy_(items[i], non_blocking=True)
-            data = self.encode(batch)
-            splitters = [(lambda body, n, c=c, ctx=ctx: c.split_items(body, n, **ctx)) for c, ctx in framing]
-            for i, one in zip(chunk, item_framing.split_codec_string(data, len(chunk), splitters)):
+            for i, one in zip(chunk, self._split_string(self.encode(batch), len(chunk), framing)):
                 out[i] = one
         return out
 
@@ -606,11 +614,107 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             if len(chunk) == 1:
                 out[chunk[0]] = self.decode(strings[chunk[0]], *args, output_dtype=output_dtype, **kwargs)
                 continue
-            mergers = [(lambda bodies, c=c, ctx=ctx: c.merge_items(bodies, **ctx)) for c, ctx in framing]
-            rec = self.decode(item_framing.merge_codec_strings([strings[i] for i in chunk], mergers), output_dtype=output_dtype)
+            rec = self.decode(self._merge_strings([strings[i] for i in chunk], framing), output_dtype=output_dtype)
             for j, i in enumerate(chunk):
                 out[i] = rec[j:j + 1]
         return out
+
+    # ---- tiled pictures: one picture coded as independent tiles, every tile keeping the bytes of its own batch-1 call
+    last_tiles_decoded = 0   # tiles the last decode_tiled() decoded
+
+    @staticmethod
+    def _tile_size(tile):
+        th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
+        return int(th), int(tw)
+
+    def encode_tiled(self, image, *args, tile=(512, 512), max_batch=None, **kwargs) -> bytes:
+        """One picture ``[1, C, H, W]`` (uint8 in chw or hwc memory, or float32; host or device) -> the container of its tiles'
+        strings (utils/tiling.py), tile k's string EXACTLY ``self.encode(image[:, :, y:y + h, x:x + w])``.  Tiles of one size are cut
+        out of the uint8 picture by one kernel launch per chunk of at most ``max_batch`` and coded in one encode() call, whose string
+        is split as in encode_items; one call per tile when a coder cannot split, a chunk holds one tile, or the call brings
+        arguments.  Tiles are independent: no overlap, no blending."""
+        from ...nn import kernels as K
+        from ...utils import tiling
+        self._check_item(image)
+        if image.dtype not in (torch.uint8, torch.float32):
+            raise TypeError(f"a picture is torch.uint8 or torch.float32, not {image.dtype}")
+        _, C, H, W = image.shape
+        grid = tiling.TileGrid(H, W, *self._tile_size(tile))
+        self.last_items_calls = 0
+        framing = self._items_framing() if not (args or kwargs or self.training) else None
+        if image.device != self.device:
+            image = image.to(device=self.device)   # once, as it lies: a dense picture keeps its strides
+        out = [None] * len(grid)
+        with torch.no_grad():
+            for group in grid.groups():
+                for sub in tiling.split_group(group, 1 if framing is None else max_batch):
+                    self.last_items_calls += 1
+                    if len(sub.indices) == 1:
+                        y, x = sub.y0, sub.x0
+                        out[sub.indices[0]] = self.encode(image[:, :, y:y + sub.h, x:x + sub.w], *args, **kwargs)
+                        continue
+                    if image.dtype == torch.uint8:
+                        batch = K.image_tiles_to_f32(image, sub)
+                    else:
+                        batch = torch.empty((len(sub.indices), C, sub.h, sub.w), dtype=image.dtype, device=self.device)
+                        for j in range(len(sub.indices)):
+                            y, x = sub.y0 + j // sub.nx * sub.step_y, sub.x0 + j % sub.nx * sub.step_x
+                            batch[j].copy_(image[0, :, y:y + sub.h, x:x + sub.w])
+                    for k, one in zip(sub.indices, self._split_string(self.encode(batch), len(sub.indices), framing)):
+                        out[k] = one
+        return tiling.pack_tiled(C, H, W, grid.th, grid.tw, out)
+
+    def decode_tiled(self, data, *args, output_dtype=torch.uint8, layout="chw", region=None, max_batch=None, **kwargs):
+        """A container of encode_tiled -> the picture ``[1, C, H, W]`` at its own size: every tile's ``self.decode(string)``, cropped
+        to the tile and written at its place (``output_dtype`` None / torch.float32), or ``image_f32_to_u8`` of that (torch.uint8:
+        converted, cropped and pasted by one kernel launch per chunk).  ``layout`` "hwc": the result's memory is [H][W][C].
+        ``region=(y0, x0, y1, x1)``: only the tiles that intersect the rectangle are decoded (``last_tiles_decoded``), and the
+        rectangle is returned, equal to that slice of the full result."""
+        from ...nn import kernels as K
+        from ...utils import tiling
+        if output_dtype not in (None, torch.float32, torch.uint8):
+            raise TypeError(f"output_dtype is torch.float32 or torch.uint8, not {output_dtype}")
+        if layout not in K.IMAGE_LAYOUTS:
+            raise ValueError(f"layout is 'chw' or 'hwc', not {layout!r}")
+        C, H, W, th, tw, strings = tiling.unpack_tiled(data)
+        grid = tiling.TileGrid(H, W, th, tw)
+        if region is None:
+            groups, (ry0, rx0, ry1, rx1) = grid.groups(), (0, 0, H, W)
+        else:
+            ry0, rx0, ry1, rx1 = (int(v) for v in region)
+            groups = grid.tiles_of_region(ry0, rx0, ry1, rx1)
+        # the canvas covers the decoded tiles: the picture, or the region widened to tile borders
+        cy0, cx0 = ry0 // th * th, rx0 // tw * tw
+        ch, cw = min(H, -(-ry1 // th) * th) - cy0, min(W, -(-rx1 // tw) * tw) - cx0
+        self.last_items_calls = self.last_tiles_decoded = 0
+        framing = self._items_framing() if not (args or kwargs or self.training) else None
+        as_u8 = output_dtype == torch.uint8
+        with torch.no_grad(), torch.cuda.device(self.device):
+            dtype = torch.uint8 if as_u8 else torch.float32
+            if layout == "hwc":
+                canvas = torch.empty((1, ch, cw, C), dtype=dtype, device=self.device).permute(0, 3, 1, 2)
+            else:
+                canvas = torch.empty((1, C, ch, cw), dtype=dtype, device=self.device)
+            for group in groups:
+                for sub in tiling.split_group(group, 1 if framing is None else max_batch):
+                    self.last_items_calls += 1
+                    self.last_tiles_decoded += len(sub.indices)
+                    if len(sub.indices) == 1:
+                        rec = self.decode(strings[sub.indices[0]], *args, **kwargs)
+                    else:
+                        rec = self.decode(self._merge_strings([strings[k] for k in sub.indices], framing))
+                    if rec.dim() != 4 or rec.shape[0] != len(sub.indices) or rec.shape[1] != C or rec.shape[2] < sub.h or rec.shape[3] < sub.w:
+                        raise ValueError(f"tiles of [{len(sub.indices)}, {C}, {sub.h}, {sub.w}] decoded to {tuple(rec.shape)}")
+                    sub = sub._replace(y0=sub.y0 - cy0, x0=sub.x0 - cx0)
+                    if as_u8:
+                        K.image_tiles_from_f32(rec, canvas, sub)
+                    else:
+                        for j in range(len(sub.indices)):
+                            y, x = sub.y0 + j // sub.nx * sub.step_y, sub.x0 + j % sub.nx * sub.step_x
+                            canvas[0, :, y:y + sub.h, x:x + sub.w].copy_(rec[j, :, :sub.h, :sub.w])
+        if region is None:
+            return canvas
+        return canvas[:, :, ry0 - cy0:ry1 - cy0, rx0 - cx0:rx1 - cx0]
 
     def forward(self, data, *args, **kwargs):
         """Eval-mode forward: quantised reconstruction without entropy coding (latent_graph.py:870-1230

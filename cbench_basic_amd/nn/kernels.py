@@ -588,6 +588,62 @@ def image_f32_to_u8(t, layout="chw"):
     return out
 
 
+def image_tiles_last_path():
+    """0 (sample by sample) or 1 (wide) for the calling thread's last tiles call; -1 before any (basic_image_tiles_last_path)."""
+    p = ctypes.c_int(-1)
+    _lib.check(_lib.lib().basic_image_tiles_last_path(ctypes.byref(p)))
+    return p.value
+
+
+def _tiles_picture(img):
+    if not isinstance(img, torch.Tensor) or not img.is_cuda:
+        _dev(img)
+    if img.dtype != torch.uint8:
+        raise TypeError(f"expected torch.uint8, got {img.dtype}")
+    if img.dim() != 4 or img.shape[0] != 1:
+        raise ValueError(f"a picture is [1, C, H, W], not {tuple(img.shape)}")
+
+
+def image_tiles_to_f32(img_u8, group):
+    """The tiles of ``group`` -- ``(y0, x0, step_y, step_x, ny, nx, h, w, ...)``, a utils.tiling.TileGroup -- cut out of the uint8
+    picture ``[1, C, H, W]`` on the GPU: float32 ``[ny * nx, C, h, w]``, tile i * nx + j equal to
+    ``img[..., y:y + h, x:x + w].float().div(255)`` at its origin, in one launch (basic_image_tiles_u8_to_f32_dev).  The picture is read
+    as it lies when it is contiguous or its memory is [H][W][C] (image_layout_of), and made contiguous otherwise."""
+    _tiles_picture(img_u8)
+    y0, x0, step_y, step_x, ny, nx, h, w = (int(v) for v in tuple(group)[:8])
+    img, layout = _image_u8(img_u8)
+    _, C, H, W = img.shape
+    if min(ny, nx, h, w) < 1:
+        raise ValueError(f"a tile group has positive ny, nx, h and w, not {(ny, nx, h, w)}")
+    with torch.cuda.device(img.device):
+        out = torch.empty((ny * nx, C, h, w), device=img.device, dtype=torch.float32)
+        _lib.check(_lib.lib().basic_image_tiles_u8_to_f32_dev(img.data_ptr(), IMAGE_LAYOUTS[layout], C, H, W, y0, x0, step_y, step_x, ny, nx,
+                                                              h, w, out.data_ptr(), _stream()))
+    return out
+
+
+def image_tiles_from_f32(batch, canvas_u8, group):
+    """The way back: the top-left h x w of every ``[C, sh, sw]`` reconstruction of ``batch`` (float32 ``[ny * nx, C, sh, sw]`` on the
+    GPU) as bytes (image_f32_to_u8's values) at its tile's place in ``canvas_u8``, a uint8 ``[1, C, H, W]`` picture on the same GPU
+    that is contiguous or has [H][W][C] memory; one launch (basic_image_tiles_f32_to_u8_dev).  Bytes outside the tiles keep their
+    value.  Returns the canvas."""
+    _tiles_picture(canvas_u8)
+    batch = _dev(batch, torch.float32)
+    y0, x0, step_y, step_x, ny, nx, h, w = (int(v) for v in tuple(group)[:8])
+    layout = image_layout_of(canvas_u8)
+    if layout is None:
+        raise ValueError("the canvas must be contiguous or have [H][W][C] memory: the tiles are written into it in place")
+    _, C, H, W = canvas_u8.shape
+    if batch.dim() != 4 or batch.shape[0] != ny * nx or batch.shape[1] != C:
+        raise ValueError(f"{ny} x {nx} tiles of {C} channels need a [{ny * nx}, {C}, sh, sw] batch, not {tuple(batch.shape)}")
+    if batch.device != canvas_u8.device:
+        raise ValueError("image_tiles_from_f32: the batch and the canvas live on different devices")
+    with torch.cuda.device(batch.device):
+        _lib.check(_lib.lib().basic_image_tiles_f32_to_u8_dev(batch.data_ptr(), batch.shape[2], batch.shape[3], C, y0, x0, step_y, step_x,
+                                                              ny, nx, h, w, canvas_u8.data_ptr(), IMAGE_LAYOUTS[layout], H, W, _stream()))
+    return canvas_u8
+
+
 def image_sse_u8(a, b):
     """The exact sum of squared differences of two uint8 [B, C, H, W] batches on one GPU, per image and channel: int64 [B, C]
     on that device (basic_image_sse_u8_dev; integer arithmetic, the same value at any batch, layout and alignment).  Each batch is

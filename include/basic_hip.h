@@ -474,6 +474,43 @@ int basic_hp_decode_images_u8(basic_hp_session *s, const uint8_t *data, int64_t 
                               uint8_t *xhat, int xhat_on_host, int64_t xhat_capacity_bytes, void *hip_stream);
 
 /* ======================================================================================
+ * 8c. Tiles of one 8-bit picture (csrc/image.hip): a picture too large for one pass of the transforms, or one that is to
+ *    be read in parts, is coded as independent tiles.  These two entries are the first and the last step of that: they
+ *    cut a batch of float tiles out of ONE uint8 picture, and paste a batch of reconstructed tiles back into one, each
+ *    in one memory pass (instead of one strided copy per tile and a conversion pass over the batch).
+ *    A tile group is a regular grid of equally sized tiles inside the picture: tile (i, j), i < ny, j < nx, has its
+ *    origin at (y0 + i * step_y, x0 + j * step_x), is th x tw, and has index i * nx + j.  The picture is uint8,
+ *    [channels][img_h][img_w] (BASIC_IMAGE_CHW) or [img_h][img_w][channels] (BASIC_IMAGE_HWC); the float side is always
+ *    [ny * nx][channels][rows][cols].
+ *    Values: exactly those of section 8b, from the same device code -- in, the 256-entry table of correctly rounded
+ *    u / 255; out, uint8(rint(min(max(x, 0), 1) * 255.0f)), NaN -> 0.
+ *    Element offsets are 64-bit.  Any channels, th, tw >= 1 and any byte alignment of the uint8 pointer; the float
+ *    pointer must be float-aligned.  The paste writes only bytes inside its tiles: everything else in d_img keeps its
+ *    value.  Nothing is allocated, nothing synchronised; each call is ONE launch on hip_stream.
+ *    Wide path: a lane owns four consecutive samples of one tile row, one dword of uint8 against one 16-byte float
+ *    access; with BASIC_IMAGE_HWC and channels 3 or 4 it owns `channels` dwords (four pixels) against one vector per
+ *    plane.  Taken when the uint8 base is 4-byte and the float base 16-byte aligned, img_w, x0, step_x, tw (and sw for
+ *    the paste) are multiples of 4 and, with BASIC_IMAGE_HWC and more than one channel, channels is 3 or 4 (one channel:
+ *    the layouts coincide).  Every other call goes sample by sample.  Both paths give the same values.
+ *    BASIC_ERR_INVALID with a message, before any launch, for a null pointer, an unknown layout, a non-positive
+ *    dimension or step, a negative origin, a step smaller than the tile (overlapping tiles), a last tile that leaves the
+ *    picture (y0 + (ny - 1) * step_y + th > img_h, likewise in x), sh < th or sw < tw, a misaligned float pointer, or
+ *    more than 2^40 samples on the float side.
+ * ==================================================================================== */
+/* Cut + ingest: d_img uint8, one picture in `layout`; d_dst float32 [ny * nx][channels][th][tw]. */
+int basic_image_tiles_u8_to_f32_dev(const uint8_t *d_img, int layout, int channels, int img_h, int img_w,
+                                    int y0, int x0, int step_y, int step_x, int ny, int nx, int th, int tw,
+                                    float *d_dst, void *hip_stream);
+/* Convert + crop + paste: d_src float32 [ny * nx][channels][sh][sw] with sh >= th, sw >= tw (a synthesis transform
+ * returns its own multiple of 64); the top-left th x tw of every tile goes to its place in d_img. */
+int basic_image_tiles_f32_to_u8_dev(const float *d_src, int sh, int sw, int channels,
+                                    int y0, int x0, int step_y, int step_x, int ny, int nx, int th, int tw,
+                                    uint8_t *d_img, int layout, int img_h, int img_w, void *hip_stream);
+/* The path the calling thread's last tiles call took: 0 scalar, 1 wide; -1 before any (as basic_rans_last_launch: written
+ * where the kernel is chosen, read by tests). */
+int basic_image_tiles_last_path(int *path);
+
+/* ======================================================================================
  * 9. Persistent scan-line AR coding loop (csrc/scanline.hip): ONE launch walks all H*W coding steps of
  *    TopoGroupPGMPriorCoder._encode_with_pgm / _pgm_generate (pgm_coder.py:912-981) for the "scanline" topo groups
  *    (one position per group, raster order) with one channel group: masked k x k context convolution at the coded

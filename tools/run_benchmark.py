@@ -78,6 +78,10 @@ def main(argv=None):
     ap.add_argument("--coalesce", type=int, default=0,
                     help="testing_coalesce_items: code the batch-1 items of the dataset in calls of up to this many items of one shape; "
                          "every item keeps the bytes of its own batch-1 call (needs --batch-size 1)")
+    ap.add_argument("--tile", type=int, nargs="+", default=None, metavar=("TH", "TW"),
+                    help="testing_tile: code every picture as independent TH x TW tiles (TW = TH when omitted) through compress_tiled / "
+                         "decompress_tiled; compressed_length is the container's, the distortion the whole picture's (needs "
+                         "--batch-size 1, does not combine with --coalesce above 1)")
     ap.add_argument("--stream-lanes", type=int, default=1,
                     help="lane streams per image of the y-coder, any codec (a format the reference does not read)")
     ap.add_argument("--stream-rows", action="store_true",
@@ -108,6 +112,12 @@ def main(argv=None):
         ap.error("--coalesce codes batch-1 items: it does not combine with --batch-size other than 1")
     if args.coalesce < 0:
         ap.error("--coalesce must be >= 0")
+    if args.tile is not None:
+        if len(args.tile) > 2 or min(args.tile) < 1:
+            ap.error("--tile takes TH [TW], positive")
+        if args.coalesce > 1 or args.batch_size != 1:
+            ap.error("--tile codes one picture per call: it does not combine with --coalesce above 1 or --batch-size other than 1")
+        args.tile = (args.tile[0], args.tile[-1])
     if args.workers > 1:   # before HIP initialises: one hardware queue per worker stream
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         os.environ.setdefault("BASIC_RANS_WPB", "8")
@@ -136,6 +146,12 @@ def main(argv=None):
     else:
         presets.seed_synthetic_weights(codec, seed=0)
     codec = codec.eval().to("cuda")
+
+    def warm(c):   # one item through the route the pass takes
+        if args.tile is not None:
+            c.decompress_tiled(c.compress_tiled(batches[0].to("cuda"), tile=args.tile))
+        else:
+            c.decompress(c.compress(batches[0].to("cuda")))
     warm_chunks = []
     if args.coalesce > 1:
         from cbench_basic_amd.utils.item_framing import coalesce_chunks
@@ -149,7 +165,7 @@ def main(argv=None):
         for lvl in (args.complexity_levels or [None]):
             if lvl is not None:
                 codec.set_complex_level(lvl)
-            codec.decompress(codec.compress(batches[0].to("cuda")))
+            warm(codec)
             for chunk in warm_chunks:   # the coalesced calls' one-time costs: one chunk per (shape, size) the pass will make
                 codec.decompress_items(codec.compress_items(chunk))
     writer = ReconstructionWriter(args.save_reconstructions, batches) if args.save_reconstructions and args.metrics_on_uint8 else None
@@ -158,7 +174,7 @@ def main(argv=None):
                                               nn_codec_use_forward_pass=args.forward_pass,
                                               testing_complexity_levels=args.complexity_levels,
                                               testing_variable_rate_levels=args.rate_levels, output_dir=args.out,
-                                              num_testing_workers=args.workers, testing_coalesce_items=args.coalesce,
+                                              num_testing_workers=args.workers, testing_coalesce_items=args.coalesce, testing_tile=args.tile,
                                               codec_builder=(lambda: presets.seed_synthetic_weights(builders[args.codec](), seed=0)) if args.workers > 1 else None)
     if args.workers > 1 and args.warmup:   # the replicas' one-time costs too, one replica at a time (HIP-graph capture)
         pool = bench._worker_pool(batches[0], batch=max((len(c) for c in warm_chunks), default=None))
@@ -167,7 +183,7 @@ def main(argv=None):
                 for lvl in (args.complexity_levels or [None]):
                     if lvl is not None:
                         r.set_complex_level(lvl)
-                    r.decompress(r.compress(batches[0].to("cuda")))
+                    warm(r)
                     for chunk in warm_chunks:
                         r.decompress_items(r.compress_items(chunk))
             torch.cuda.synchronize()
