@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libbasic_hip.so")
 
 OK, ERR_INVALID, ERR_NOT_INIT, ERR_HIP, ERR_OVERFLOW, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5
 IMAGE_CHW, IMAGE_HWC = 0, 1   # BASIC_IMAGE_*: the order of the uint8 side of an 8-bit image call
+PIXEL_U8, PIXEL_F32 = 0, 1    # BASIC_PIXEL_*: what basic_image_tiles_blend_dev writes
 
 
 class BasicHipError(RuntimeError):
@@ -85,6 +86,8 @@ _SIGNATURES = {
     "basic_image_sse_u8_dev": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     "basic_image_tiles_u8_to_f32_dev": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "basic_image_tiles_f32_to_u8_dev": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
+    "basic_image_tiles_overlap_u8_to_f32_dev": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "basic_image_tiles_blend_dev": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     "basic_image_tiles_last_path": (_I, [_P]),
     "basic_hp_encode_images_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
     "basic_hp_decode_images_u8": (_I, [_P, _P, _L, _I, _P, _I, _L, _P]),

@@ -26,7 +26,8 @@ hands out -- ``codec.decompress(compressed, output_dtype=torch.uint8)``, convert
 
 ``testing_tile=(th, tw)`` (not in the reference; INTEGRATION.md, "Tiled pictures"): every item, a batch-1 picture, is coded as
 independent tiles (``codec.compress_tiled`` / ``decompress_tiled``); ``compressed_length`` is the length of the container and the
-distortion that of the whole pasted picture.  It does not combine with ``testing_coalesce_items``.
+distortion that of the whole pasted picture.  It does not combine with ``testing_coalesce_items``.  ``testing_tile_overlap`` (an int
+or ``(oy, ox)``, at most half a tile; needs ``testing_tile``): the tiles overlap and ``decompress_tiled`` cross-fades the seams.
 """
 import copy
 import csv
@@ -47,7 +48,7 @@ class BasicLosslessCompressionBenchmark:
                  testing_variable_rate_levels=None, testing_variable_rate_bj_delta_metric=None,
                  testing_complexity_levels=None, force_testing_device="cuda", output_dir=None, num_repeats=1,
                  num_testing_workers=0, codec_builder=None, worker_transform_token=None, testing_coalesce_items=0,
-                 metrics_on_uint8=False, on_reconstruction=None, testing_tile=None, **kwargs):
+                 metrics_on_uint8=False, on_reconstruction=None, testing_tile=None, testing_tile_overlap=0, **kwargs):
         self.codec = codec
         self.dataloader = dataloader
         self.distortion_metric = distortion_metric
@@ -91,6 +92,16 @@ class BasicLosslessCompressionBenchmark:
             if self.testing_coalesce_items > 1:
                 raise ValueError("testing_tile codes one picture per call: it does not combine with testing_coalesce_items")
         self.testing_tile = testing_tile
+        # overlapped tiles, seams cross-faded by decompress_tiled: an int or (oy, ox), at most half a tile
+        testing_tile_overlap = (testing_tile_overlap,) * 2 if isinstance(testing_tile_overlap, int) else tuple(int(v) for v in testing_tile_overlap)
+        if len(testing_tile_overlap) != 2 or min(testing_tile_overlap) < 0:
+            raise ValueError(f"testing_tile_overlap is (oy, ox), not negative, not {testing_tile_overlap!r}")
+        if any(testing_tile_overlap):
+            if testing_tile is None:
+                raise ValueError("testing_tile_overlap needs testing_tile")
+            if 2 * testing_tile_overlap[0] > testing_tile[0] or 2 * testing_tile_overlap[1] > testing_tile[1]:
+                raise ValueError(f"testing_tile_overlap {testing_tile_overlap} is more than half a {testing_tile} tile")
+        self.testing_tile_overlap = testing_tile_overlap
         self._level_prefix = ""
         self._pictures = {}
         self._pool = None
@@ -165,7 +176,7 @@ class BasicLosslessCompressionBenchmark:
         if not isinstance(data, torch.Tensor) or data.dim() != 4 or data.shape[0] != 1:
             raise ValueError("testing_tile codes a dataset of batch-1 pictures ([1, C, H, W]); got "
                              f"{tuple(data.shape) if isinstance(data, torch.Tensor) else type(data).__name__}")
-        return codec.compress_tiled(data, tile=self.testing_tile)
+        return codec.compress_tiled(data, tile=self.testing_tile, overlap=self.testing_tile_overlap)
 
     def _decompress(self, codec, compressed):
         if self.testing_tile is not None:

@@ -40,14 +40,16 @@ class GeneralCodec(HotPathModule, CodecInterface, VariableRateCodecInterface, Va
         with self.profiler.start_time_profile("time_decompress_entropy_coder"):
             return self.entropy_coder.decode_items(strings, *args, max_batch=max_batch, **kwargs)
 
-    def compress_tiled(self, image, *args, tile=(512, 512), max_batch=None, **kwargs):
+    def compress_tiled(self, image, *args, tile=(512, 512), max_batch=None, overlap=0, **kwargs):
         """One picture ``[1, C, H, W]`` -> the container of its independently coded tiles (utils/tiling.py), tile k's string exactly
-        ``self.compress(image[:, :, y:y + h, x:x + w])`` (entropy coder's ``encode_tiled``)."""
+        ``self.compress(image[:, :, y:y + h, x:x + w])`` (entropy coder's ``encode_tiled``).  ``overlap`` (int or ``(oy, ox)``, at most
+        half a tile): neighbouring tiles share that many rows / columns, and decompress_tiled cross-fades the seams."""
         with self.profiler.start_time_profile("time_compress_entropy_coder"):
-            return self.entropy_coder.encode_tiled(image, *args, tile=tile, max_batch=max_batch, **kwargs)
+            return self.entropy_coder.encode_tiled(image, *args, tile=tile, max_batch=max_batch, overlap=overlap, **kwargs)
 
     def decompress_tiled(self, data, *args, **kwargs):
-        """A container of compress_tiled -> the picture at its own size, or the ``region`` of it (entropy coder's ``decode_tiled``)."""
+        """A container of compress_tiled -> the picture at its own size, or the ``region`` of it (entropy coder's ``decode_tiled``);
+        the overlap of the tiles, if any, is read from the container."""
         with self.profiler.start_time_profile("time_decompress_entropy_coder"):
             return self.entropy_coder.decode_tiled(data, *args, **kwargs)
 

@@ -13,7 +13,8 @@
 // rounded) when it builds the table in constant memory, a workgroup copies it to LDS once.  float32 -> uint8 is fmax / fmin /
 // one multiply / v_rndne; nothing is contracted into it.
 // The third entry measures such pictures: the exact per-channel sum of squared differences of two uint8 batches (further down).
-// The last two cut float tiles out of one uint8 picture and paste reconstructed tiles back into one (section 8c, at the end).
+// The last entries cut float tiles out of one uint8 picture, paste reconstructed tiles back into one and, for overlapped tiles, write
+// the picture from all their reconstructions with the seams cross-faded (section 8c, at the end).
 #include <utility>
 
 #include "common.h"
@@ -531,7 +532,7 @@ struct TilePlan {
 
 // the checks both directions share; fh x fw is the float side's plane (th x tw for the cut)
 int plan_tiles(const void *d_img, const void *d_f32, int layout, int channels, int img_h, int img_w, int y0, int x0, int step_y, int step_x,
-               int ny, int nx, int th, int tw, int fh, int fw, const char *what, TilePlan *p)
+               int ny, int nx, int th, int tw, int fh, int fw, const char *what, TilePlan *p, bool may_overlap = false)
 {
     const std::string who(what);
     BASIC_REQUIRE(d_img && d_f32, who + ": null pointer");
@@ -540,7 +541,7 @@ int plan_tiles(const void *d_img, const void *d_f32, int layout, int channels, i
                   who + ": channels, the picture's size, ny, nx, th and tw must be positive");
     BASIC_REQUIRE(step_y >= 1 && step_x >= 1, who + ": step_y and step_x must be positive");
     BASIC_REQUIRE(y0 >= 0 && x0 >= 0, who + ": y0 and x0 must not be negative");
-    BASIC_REQUIRE(step_y >= th && step_x >= tw, who + ": a step smaller than the tile (overlapping tiles)");
+    BASIC_REQUIRE(may_overlap || (step_y >= th && step_x >= tw), who + ": a step smaller than the tile (overlapping tiles)");
     BASIC_REQUIRE(fh >= th && fw >= tw, who + ": the source tiles are smaller than th x tw");
     BASIC_REQUIRE(static_cast<int64_t>(y0) + static_cast<int64_t>(ny - 1) * step_y + th <= img_h &&
                       static_cast<int64_t>(x0) + static_cast<int64_t>(nx - 1) * step_x + tw <= img_w,
@@ -568,11 +569,14 @@ int plan_tiles(const void *d_img, const void *d_f32, int layout, int channels, i
 
 }  // namespace
 
-extern "C" int basic_image_tiles_u8_to_f32_dev(const uint8_t *d_img, int layout, int channels, int img_h, int img_w, int y0, int x0,
-                                               int step_y, int step_x, int ny, int nx, int th, int tw, float *d_dst, void *hip_stream)
+namespace {
+
+// the cut of both entries: the same kernels and the same wide / scalar rule, whether or not the tiles overlap (they are only read)
+int cut_tiles(const uint8_t *d_img, int layout, int channels, int img_h, int img_w, int y0, int x0, int step_y, int step_x, int ny, int nx,
+              int th, int tw, float *d_dst, void *hip_stream, const char *what, bool may_overlap)
 {
     TilePlan p;
-    int rc = plan_tiles(d_img, d_dst, layout, channels, img_h, img_w, y0, x0, step_y, step_x, ny, nx, th, tw, th, tw, "image_tiles_u8_to_f32", &p);
+    int rc = plan_tiles(d_img, d_dst, layout, channels, img_h, img_w, y0, x0, step_y, step_x, ny, nx, th, tw, th, tw, what, &p, may_overlap);
     if (rc) return rc;
     rc = require_device();
     if (rc) return rc;
@@ -587,6 +591,22 @@ extern "C" int basic_image_tiles_u8_to_f32_dev(const uint8_t *d_img, int layout,
     g_tiles_last_path = p.wide_c ? 1 : 0;
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
+}
+
+}  // namespace
+
+extern "C" int basic_image_tiles_u8_to_f32_dev(const uint8_t *d_img, int layout, int channels, int img_h, int img_w, int y0, int x0,
+                                               int step_y, int step_x, int ny, int nx, int th, int tw, float *d_dst, void *hip_stream)
+{
+    return cut_tiles(d_img, layout, channels, img_h, img_w, y0, x0, step_y, step_x, ny, nx, th, tw, d_dst, hip_stream, "image_tiles_u8_to_f32", false);
+}
+
+extern "C" int basic_image_tiles_overlap_u8_to_f32_dev(const uint8_t *d_img, int layout, int channels, int img_h, int img_w, int y0, int x0,
+                                                       int step_y, int step_x, int ny, int nx, int th, int tw, float *d_dst,
+                                                       void *hip_stream)
+{
+    return cut_tiles(d_img, layout, channels, img_h, img_w, y0, x0, step_y, step_x, ny, nx, th, tw, d_dst, hip_stream,
+                     "image_tiles_overlap_u8_to_f32", true);
 }
 
 extern "C" int basic_image_tiles_f32_to_u8_dev(const float *d_src, int sh, int sw, int channels, int y0, int x0, int step_y, int step_x,
@@ -608,6 +628,227 @@ extern "C" int basic_image_tiles_f32_to_u8_dev(const float *d_src, int sh, int s
     else if (p.wide_c == 4) hipLaunchKernelGGL(tiles_f32_to_u8_wide_kernel<4>, grid_for(runs), dim3(kBlock), 0, st, src4, img4, p.g, runs);
     else hipLaunchKernelGGL(tiles_f32_to_u8_scalar_kernel, grid_for(p.total), dim3(kBlock), 0, st, d_src, d_img, p.hwc, p.g, p.total);
     g_tiles_last_path = p.wide_c ? 1 : 0;
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+// ---- overlapped tiles: the seams cross-faded (include/basic_hip.h section 8c, "Blend") --------------------------------------
+// A gather: every output sample of the rectangle is computed from the one, two or four reconstructions that cover it, read where
+// decode() left them through a table of (pointer, sh, sw) per tile of the rows x cols grid.  Nothing is accumulated, so a sample's
+// value depends on nothing but the tiles that cover it: not on the chunks, the other table entries or the launch shape.
+//   axis  : steps s = t - o, n tiles.  Coordinate p lies in tile i = min(p / s, n - 1) at d = p - i * s; with i > 0 and d < o it
+//           lies in the band of tiles i - 1 (at d + s) and i (at d), weight ramp(d) = float((2 d + 1) / (2.0 o)).
+//   value : lerp(a, b, w) = a + w * (b - a), three rounded fp32 operations, never contracted; x first (top and bottom), then y.
+//   wide  : a lane owns four consecutive output samples of one row -- of one plane (PLANAR), or of 3 / 4 interleaved channels.
+//           rx0, sx, ox and rw are multiples of 4, so the four share their tiles and band, and their columns inside a source start
+//           on a multiple of 4: a 16-byte load where that source's address allows it, four dword loads otherwise (same values).
+//   scalar: one output sample per lane per step, walking the output (consecutive stores).
+// A null table entry: the samples that need it are not written.  In the wide path the four samples of a run need the same tiles.
+namespace {
+
+struct BlendPlan {
+    int64_t sy, sx, oy, ox, rows, cols;   // the grid
+    int64_t ry0, rx0, rh, rw;             // the output rectangle, in the picture's coordinates
+    int64_t channels;
+};
+
+struct BlendAxis {
+    int64_t ia;      // the (first) covering tile
+    int64_t la, lb;  // the coordinate inside tile ia, and inside tile ia + 1 (band only)
+    int64_t d;       // distance from the band's start (band only)
+    int band;
+};
+
+__device__ __forceinline__ BlendAxis blend_axis(int64_t p, int64_t s, int64_t o, int64_t n)
+{
+    BlendAxis a;
+    int64_t i = p / s;
+    if (i > n - 1) i = n - 1;
+    const int64_t d = p - i * s;
+    a.band = i > 0 && d < o;
+    a.ia = a.band ? i - 1 : i;
+    a.la = a.band ? d + s : d;
+    a.lb = d;
+    a.d = d;
+    return a;
+}
+
+__device__ __forceinline__ float blend_ramp(int64_t d, int64_t o)
+{
+    return static_cast<float>(static_cast<double>(static_cast<int>(2 * d + 1)) / (2.0 * static_cast<int>(o)));   // one double division, rounded once to fp32
+}
+
+__device__ __forceinline__ float blend_lerp(float a, float b, float w)
+{
+#pragma clang fp contract(off)
+    const float diff = b - a;
+    const float scaled = w * diff;
+    return a + scaled;
+}
+
+// N consecutive floats of a source plane: row `row`, columns col .. col + N - 1 of channel c
+template <int N>
+__device__ __forceinline__ void blend_load(const basic_tile_source &e, int64_t c, int64_t row, int64_t col, float *v)
+{
+    const float *p = e.src + (c * e.sh + row) * static_cast<int64_t>(e.sw) + col;
+    if constexpr (N == 4) {
+        if (reinterpret_cast<uintptr_t>(p) % 16 == 0) {
+            const float4 q = *reinterpret_cast<const float4 *>(p);
+            v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = p[k];
+}
+
+// N consecutive samples of row `row` of tile row `ti`, cross-faded in x where ax says so; false: a tile they need is missing
+template <int N>
+__device__ __forceinline__ bool blend_row(const basic_tile_source *__restrict__ table, const BlendPlan &g, int64_t ti, int64_t row, int64_t c,
+                                          const BlendAxis &ax, const float *wx, float *v)
+{
+    const basic_tile_source ea = table[ti * g.cols + ax.ia];
+    if (!ea.src) return false;
+    blend_load<N>(ea, c, row, ax.la, v);
+    if (!ax.band) return true;
+    const basic_tile_source eb = table[ti * g.cols + ax.ia + 1];
+    if (!eb.src) return false;
+    float b[N];
+    blend_load<N>(eb, c, row, ax.lb, b);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = blend_lerp(v[k], b[k], wx[k]);
+    return true;
+}
+
+// N consecutive samples of picture row y (channel c) that start at the column ax describes
+template <int N>
+__device__ __forceinline__ bool blend_samples(const basic_tile_source *__restrict__ table, const BlendPlan &g, int64_t c, const BlendAxis &ay,
+                                              const BlendAxis &ax, const float *wx, float *v)
+{
+    if (!blend_row<N>(table, g, ay.ia, ay.la, c, ax, wx, v)) return false;
+    if (!ay.band) return true;
+    float bottom[N];
+    if (!blend_row<N>(table, g, ay.ia + 1, ay.lb, c, ax, wx, bottom)) return false;
+    const float wy = blend_ramp(ay.d, g.oy);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = blend_lerp(v[k], bottom[k], wy);
+    return true;
+}
+
+// run r: C == 1 (planar) = (channel, row, q) of the rectangle, its four samples at output elements [4 r, 4 r + 4);
+// C = 3, 4 (interleaved) = (row, q), its 4 C samples at output elements [4 C r, 4 C r + 4 C), sample p * C + c = pixel p, channel c
+template <int C, bool U8>
+__global__ __launch_bounds__(kBlock) void tiles_blend_wide_kernel(const basic_tile_source *__restrict__ table, void *__restrict__ out, BlendPlan g,
+                                                                   int64_t runs)
+{
+    const int64_t qn = g.rw / 4;
+    for (int64_t r = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; r < runs; r += static_cast<int64_t>(gridDim.x) * kBlock) {
+        const int64_t q = r % qn, job = r / qn;
+        const int64_t row = C == 1 ? job % g.rh : job, c0 = C == 1 ? job / g.rh : 0;
+        const BlendAxis ay = blend_axis(g.ry0 + row, g.sy, g.oy, g.rows), ax = blend_axis(g.rx0 + 4 * q, g.sx, g.ox, g.cols);
+        float wx[4] = {0.f, 0.f, 0.f, 0.f};
+        if (ax.band) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) wx[k] = blend_ramp(ax.d + k, g.ox);
+        }
+        float v[C][4];
+        bool ok = true;
+#pragma unroll
+        for (int c = 0; c < C; ++c) ok = ok && blend_samples<4>(table, g, c0 + c, ay, ax, wx, v[c]);
+        if (!ok) continue;   // a tile is missing: the run keeps its bytes
+        if (U8) {
+            Words<C> w;
+#pragma unroll
+            for (int k = 0; k < C; ++k) w.w[k] = 0u;
+#pragma unroll
+            for (int c = 0; c < C; ++c) run_from_f32<C>(w, c, make_float4(v[c][0], v[c][1], v[c][2], v[c][3]));
+            *reinterpret_cast<Words<C> *>(static_cast<uint32_t *>(out) + r * C) = w;
+        } else {
+            float o[4 * C];
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+#pragma unroll
+                for (int p = 0; p < 4; ++p) o[p * C + c] = v[c][p];
+#pragma unroll
+            for (int k = 0; k < C; ++k) static_cast<float4 *>(out)[r * C + k] = make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+        }
+    }
+}
+
+// output element j of the rectangle: [c][row][col], hwc: [row][col][c]
+template <bool U8>
+__global__ __launch_bounds__(kBlock) void tiles_blend_scalar_kernel(const basic_tile_source *__restrict__ table, void *__restrict__ out, int hwc,
+                                                                     BlendPlan g, int64_t total)
+{
+    for (int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; j < total; j += static_cast<int64_t>(gridDim.x) * kBlock) {
+        int64_t c, row, col;
+        if (hwc) {
+            c = j % g.channels;
+            const int64_t t = j / g.channels;
+            col = t % g.rw;
+            row = t / g.rw;
+        } else {
+            col = j % g.rw;
+            const int64_t t = j / g.rw;
+            row = t % g.rh;
+            c = t / g.rh;
+        }
+        const BlendAxis ay = blend_axis(g.ry0 + row, g.sy, g.oy, g.rows), ax = blend_axis(g.rx0 + col, g.sx, g.ox, g.cols);
+        const float wx = ax.band ? blend_ramp(ax.d, g.ox) : 0.f;
+        float v;
+        if (!blend_samples<1>(table, g, c, ay, ax, &wx, &v)) continue;
+        if (U8) static_cast<uint8_t *>(out)[j] = static_cast<uint8_t>(quantise(v));
+        else static_cast<float *>(out)[j] = v;
+    }
+}
+
+template <bool U8>
+void launch_blend(int wide_c, const basic_tile_source *table, void *out, int hwc, const BlendPlan &g, int64_t total, hipStream_t st)
+{
+    const int64_t runs = wide_c == 1 ? total / 4 : wide_c ? total / 4 / wide_c : 0;
+    if (wide_c == 1) hipLaunchKernelGGL((tiles_blend_wide_kernel<1, U8>), grid_for(runs), dim3(kBlock), 0, st, table, out, g, runs);
+    else if (wide_c == 3) hipLaunchKernelGGL((tiles_blend_wide_kernel<3, U8>), grid_for(runs), dim3(kBlock), 0, st, table, out, g, runs);
+    else if (wide_c == 4) hipLaunchKernelGGL((tiles_blend_wide_kernel<4, U8>), grid_for(runs), dim3(kBlock), 0, st, table, out, g, runs);
+    else hipLaunchKernelGGL(tiles_blend_scalar_kernel<U8>, grid_for(total), dim3(kBlock), 0, st, table, out, hwc, g, total);
+}
+
+}  // namespace
+
+extern "C" int basic_image_tiles_blend_dev(const basic_tile_source *d_table, int img_h, int img_w, int th, int tw, int oy, int ox, int channels,
+                                           int ry0, int rx0, int rh, int rw, void *d_out, int out_kind, int layout, void *hip_stream)
+{
+    const std::string who("image_tiles_blend");
+    BASIC_REQUIRE(d_table && d_out, who + ": null pointer");
+    BASIC_REQUIRE(layout == BASIC_IMAGE_CHW || layout == BASIC_IMAGE_HWC, who + ": layout is BASIC_IMAGE_CHW or BASIC_IMAGE_HWC");
+    BASIC_REQUIRE(out_kind == BASIC_PIXEL_U8 || out_kind == BASIC_PIXEL_F32, who + ": out_kind is BASIC_PIXEL_U8 or BASIC_PIXEL_F32");
+    BASIC_REQUIRE(channels >= 1 && img_h >= 1 && img_w >= 1 && th >= 1 && tw >= 1 && rh >= 1 && rw >= 1,
+                  who + ": channels, the picture's size, th, tw, rh and rw must be positive");
+    BASIC_REQUIRE(oy >= 0 && ox >= 0, who + ": oy and ox must not be negative");
+    BASIC_REQUIRE(static_cast<int64_t>(2) * oy <= th && static_cast<int64_t>(2) * ox <= tw, who + ": an overlap of more than half a tile");
+    BASIC_REQUIRE(ry0 >= 0 && rx0 >= 0 && static_cast<int64_t>(ry0) + rh <= img_h && static_cast<int64_t>(rx0) + rw <= img_w,
+                  who + ": the rectangle leaves the picture");
+    BASIC_REQUIRE(out_kind != BASIC_PIXEL_F32 || reinterpret_cast<uintptr_t>(d_out) % sizeof(float) == 0,
+                  who + ": the float32 output is not float-aligned");
+    const int64_t plane = static_cast<int64_t>(rh) * rw;
+    BASIC_REQUIRE(channels <= kMaxSamples / plane, who + ": more than 2^40 samples");
+    BlendPlan g;
+    g.sy = th - oy, g.sx = tw - ox, g.oy = oy, g.ox = ox;
+    g.rows = (img_h - oy + g.sy - 1) / g.sy, g.cols = (img_w - ox + g.sx - 1) / g.sx;   // a picture no larger than the overlap: one tile
+    if (g.rows < 1) g.rows = 1;
+    if (g.cols < 1) g.cols = 1;
+    g.ry0 = ry0, g.rx0 = rx0, g.rh = rh, g.rw = rw;
+    g.channels = channels;
+    int rc = require_device();
+    if (rc) return rc;
+    const int64_t total = plane * channels;
+    const int hwc = layout == BASIC_IMAGE_HWC && channels > 1;   // one channel: the two layouts coincide
+    const bool u8 = out_kind == BASIC_PIXEL_U8;
+    const bool aligned = reinterpret_cast<uintptr_t>(d_out) % (u8 ? 4 : 16) == 0 && rw % 4 == 0 && rx0 % 4 == 0 && g.sx % 4 == 0 && ox % 4 == 0;
+    const int wide_c = !aligned ? 0 : !hwc ? 1 : (channels == 3 || channels == 4) ? channels : 0;
+    hipStream_t st = as_stream(hip_stream);
+    if (u8) launch_blend<true>(wide_c, d_table, d_out, hwc, g, total, st);
+    else launch_blend<false>(wide_c, d_table, d_out, hwc, g, total, st);
+    g_tiles_last_path = wide_c ? 1 : 0;
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
 }

@@ -627,19 +627,21 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
         return int(th), int(tw)
 
-    def encode_tiled(self, image, *args, tile=(512, 512), max_batch=None, **kwargs) -> bytes:
+    def encode_tiled(self, image, *args, tile=(512, 512), max_batch=None, overlap=0, **kwargs) -> bytes:
         """One picture ``[1, C, H, W]`` (uint8 in chw or hwc memory, or float32; host or device) -> the container of its tiles'
         strings (utils/tiling.py), tile k's string EXACTLY ``self.encode(image[:, :, y:y + h, x:x + w])``.  Tiles of one size are cut
         out of the uint8 picture by one kernel launch per chunk of at most ``max_batch`` and coded in one encode() call, whose string
         is split as in encode_items; one call per tile when a coder cannot split, a chunk holds one tile, or the call brings
-        arguments.  Tiles are independent: no overlap, no blending."""
+        arguments.  Tiles are coded independently.  ``overlap`` (an int, or ``(oy, ox)``, at most half a tile): neighbouring tiles
+        share that many rows and columns (utils/tiling.py), the container is BTL2, and decode_tiled cross-fades the seams; with 0,
+        the default, the tiles abut and every byte of the container is what it was before overlaps existed."""
         from ...nn import kernels as K
         from ...utils import tiling
         self._check_item(image)
         if image.dtype not in (torch.uint8, torch.float32):
             raise TypeError(f"a picture is torch.uint8 or torch.float32, not {image.dtype}")
         _, C, H, W = image.shape
-        grid = tiling.TileGrid(H, W, *self._tile_size(tile))
+        grid = tiling.TileGrid(H, W, *self._tile_size(tile), overlap=overlap)
         self.last_items_calls = 0
         framing = self._items_framing() if not (args or kwargs or self.training) else None
         if image.device != self.device:
@@ -662,22 +664,26 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                             batch[j].copy_(image[0, :, y:y + sub.h, x:x + sub.w])
                     for k, one in zip(sub.indices, self._split_string(self.encode(batch), len(sub.indices), framing)):
                         out[k] = one
-        return tiling.pack_tiled(C, H, W, grid.th, grid.tw, out)
+        return tiling.pack_tiled(C, H, W, grid.th, grid.tw, out, overlap=grid.overlap)
 
     def decode_tiled(self, data, *args, output_dtype=torch.uint8, layout="chw", region=None, max_batch=None, **kwargs):
         """A container of encode_tiled -> the picture ``[1, C, H, W]`` at its own size: every tile's ``self.decode(string)``, cropped
         to the tile and written at its place (``output_dtype`` None / torch.float32), or ``image_f32_to_u8`` of that (torch.uint8:
         converted, cropped and pasted by one kernel launch per chunk).  ``layout`` "hwc": the result's memory is [H][W][C].
         ``region=(y0, x0, y1, x1)``: only the tiles that intersect the rectangle are decoded (``last_tiles_decoded``), and the
-        rectangle is returned, equal to that slice of the full result."""
+        rectangle is returned, equal to that slice of the full result.
+        Overlapped tiles (a BTL2 container; the overlap is read from it): the tiles that cover a sample of the picture or region are
+        decoded as above, and ONE blend launch (nn.kernels.image_tiles_blend) writes the result from their reconstructions, the
+        seams cross-faded as include/basic_hip.h section 8c defines.  The reconstructions of ALL decoded tiles are resident until
+        that launch: 4 * C * sh * sw bytes per tile on top of the result, where the abutting path holds one chunk at a time."""
         from ...nn import kernels as K
         from ...utils import tiling
         if output_dtype not in (None, torch.float32, torch.uint8):
             raise TypeError(f"output_dtype is torch.float32 or torch.uint8, not {output_dtype}")
         if layout not in K.IMAGE_LAYOUTS:
             raise ValueError(f"layout is 'chw' or 'hwc', not {layout!r}")
-        C, H, W, th, tw, strings = tiling.unpack_tiled(data)
-        grid = tiling.TileGrid(H, W, th, tw)
+        C, H, W, th, tw, overlap, strings = tiling.unpack_tiled_any(data)
+        grid = tiling.TileGrid(H, W, th, tw, overlap)
         if region is None:
             groups, (ry0, rx0, ry1, rx1) = grid.groups(), (0, 0, H, W)
         else:
@@ -689,6 +695,10 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         self.last_items_calls = self.last_tiles_decoded = 0
         framing = self._items_framing() if not (args or kwargs or self.training) else None
         as_u8 = output_dtype == torch.uint8
+        blend = overlap != (0, 0)
+        if blend:   # the result is the rectangle itself: the blend launch writes nothing else
+            cy0, cx0, ch, cw = ry0, rx0, ry1 - ry0, rx1 - rx0
+        recs = []
         with torch.no_grad(), torch.cuda.device(self.device):
             dtype = torch.uint8 if as_u8 else torch.float32
             if layout == "hwc":
@@ -705,6 +715,9 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                         rec = self.decode(self._merge_strings([strings[k] for k in sub.indices], framing))
                     if rec.dim() != 4 or rec.shape[0] != len(sub.indices) or rec.shape[1] != C or rec.shape[2] < sub.h or rec.shape[3] < sub.w:
                         raise ValueError(f"tiles of [{len(sub.indices)}, {C}, {sub.h}, {sub.w}] decoded to {tuple(rec.shape)}")
+                    if blend:
+                        recs.append((rec, sub.indices))
+                        continue
                     sub = sub._replace(y0=sub.y0 - cy0, x0=sub.x0 - cx0)
                     if as_u8:
                         K.image_tiles_from_f32(rec, canvas, sub)
@@ -712,6 +725,8 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                         for j in range(len(sub.indices)):
                             y, x = sub.y0 + j // sub.nx * sub.step_y, sub.x0 + j % sub.nx * sub.step_x
                             canvas[0, :, y:y + sub.h, x:x + sub.w].copy_(rec[j, :, :sub.h, :sub.w])
+            if blend:
+                K.image_tiles_blend(recs, grid, canvas, (ry0, rx0, ry1, rx1))
         if region is None:
             return canvas
         return canvas[:, :, ry0 - cy0:ry1 - cy0, rx0 - cx0:rx1 - cx0]

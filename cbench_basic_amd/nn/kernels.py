@@ -607,8 +607,9 @@ def _tiles_picture(img):
 def image_tiles_to_f32(img_u8, group):
     """The tiles of ``group`` -- ``(y0, x0, step_y, step_x, ny, nx, h, w, ...)``, a utils.tiling.TileGroup -- cut out of the uint8
     picture ``[1, C, H, W]`` on the GPU: float32 ``[ny * nx, C, h, w]``, tile i * nx + j equal to
-    ``img[..., y:y + h, x:x + w].float().div(255)`` at its origin, in one launch (basic_image_tiles_u8_to_f32_dev).  The picture is read
-    as it lies when it is contiguous or its memory is [H][W][C] (image_layout_of), and made contiguous otherwise."""
+    ``img[..., y:y + h, x:x + w].float().div(255)`` at its origin, in one launch (basic_image_tiles_u8_to_f32_dev; a group whose steps
+    are smaller than its tiles, overlapped tiles, goes to basic_image_tiles_overlap_u8_to_f32_dev).  The picture is read as it lies
+    when it is contiguous or its memory is [H][W][C] (image_layout_of), and made contiguous otherwise."""
     _tiles_picture(img_u8)
     y0, x0, step_y, step_x, ny, nx, h, w = (int(v) for v in tuple(group)[:8])
     img, layout = _image_u8(img_u8)
@@ -617,8 +618,9 @@ def image_tiles_to_f32(img_u8, group):
         raise ValueError(f"a tile group has positive ny, nx, h and w, not {(ny, nx, h, w)}")
     with torch.cuda.device(img.device):
         out = torch.empty((ny * nx, C, h, w), device=img.device, dtype=torch.float32)
-        _lib.check(_lib.lib().basic_image_tiles_u8_to_f32_dev(img.data_ptr(), IMAGE_LAYOUTS[layout], C, H, W, y0, x0, step_y, step_x, ny, nx,
-                                                              h, w, out.data_ptr(), _stream()))
+        L = _lib.lib()
+        cut = L.basic_image_tiles_overlap_u8_to_f32_dev if (1 <= step_y < h or 1 <= step_x < w) else L.basic_image_tiles_u8_to_f32_dev
+        _lib.check(cut(img.data_ptr(), IMAGE_LAYOUTS[layout], C, H, W, y0, x0, step_y, step_x, ny, nx, h, w, out.data_ptr(), _stream()))
     return out
 
 
@@ -642,6 +644,55 @@ def image_tiles_from_f32(batch, canvas_u8, group):
         _lib.check(_lib.lib().basic_image_tiles_f32_to_u8_dev(batch.data_ptr(), batch.shape[2], batch.shape[3], C, y0, x0, step_y, step_x,
                                                               ny, nx, h, w, canvas_u8.data_ptr(), IMAGE_LAYOUTS[layout], H, W, _stream()))
     return canvas_u8
+
+
+def image_tiles_blend(sources, grid, out, region=None):
+    """The picture of overlapped tiles, seams cross-faded, in ONE launch (basic_image_tiles_blend_dev; the values are defined in
+    include/basic_hip.h section 8c).  ``sources``: a list of ``(batch, tile_indices)``, batch float32 ``[n, C, sh, sw]`` on the GPU --
+    the reconstructions as decode() left them, any sh x sw that holds the tiles -- and the n row-major tile numbers of ``grid``, a
+    utils.tiling.TileGrid, they belong to.  ``out``: uint8 or float32 ``[1, C, rh, rw]`` on the same GPU, contiguous or with [H][W][C]
+    memory, the rectangle ``region = (y0, x0, y1, x1)`` of the picture (default: all of it); every sample of it is written.
+    ValueError when the rectangle needs a tile nobody supplied.  The batches are read in place: keep them alive (and unchanged)
+    until the launch has run.  Returns ``out``."""
+    if not isinstance(out, torch.Tensor) or not out.is_cuda:
+        _dev(out)
+    if out.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"the output is torch.uint8 or torch.float32, not {out.dtype}")
+    y0, x0, y1, x1 = (0, 0, grid.H, grid.W) if region is None else (int(v) for v in region)
+    if not (0 <= y0 < y1 <= grid.H and 0 <= x0 < x1 <= grid.W):
+        raise ValueError(f"region {(y0, x0, y1, x1)} is empty or leaves the {grid.H} x {grid.W} picture")
+    if out.dim() != 4 or out.shape[0] != 1 or tuple(out.shape[2:]) != (y1 - y0, x1 - x0):
+        raise ValueError(f"the output of region {(y0, x0, y1, x1)} is [1, C, {y1 - y0}, {x1 - x0}], not {tuple(out.shape)}")
+    layout = image_layout_of(out)
+    if layout is None:
+        raise ValueError("the output must be contiguous or have [H][W][C] memory: it is written in place")
+    C = out.shape[1]
+    table = np.zeros(len(grid), dtype=np.dtype([("src", "<u8"), ("sh", "<i4"), ("sw", "<i4")]))   # basic_tile_source
+    keep = []   # a batch that had to be made contiguous lives until the launch is enqueued (the allocator is stream-ordered)
+    for batch, indices in sources:
+        batch = _dev(batch, torch.float32)
+        keep.append(batch)
+        indices = [int(k) for k in indices]
+        if batch.dim() != 4 or batch.shape[0] != len(indices) or batch.shape[1] != C:
+            raise ValueError(f"{len(indices)} tiles of {C} channels need a [{len(indices)}, {C}, sh, sw] batch, not {tuple(batch.shape)}")
+        if batch.device != out.device:
+            raise ValueError("image_tiles_blend: a batch and the output live on different devices")
+        sh, sw = int(batch.shape[2]), int(batch.shape[3])
+        for n, k in enumerate(indices):
+            _, _, h, w = grid.tile_rect(k)
+            if sh < h or sw < w:
+                raise ValueError(f"tile {k} is {h} x {w}; its reconstruction is {sh} x {sw}")
+            table[k] = (batch.data_ptr() + 4 * n * C * sh * sw, sh, sw)
+    missing = [k for g in grid.tiles_of_region(y0, x0, y1, x1) for k in g.indices if not table["src"][k]]
+    if missing:
+        raise ValueError(f"region {(y0, x0, y1, x1)} needs tiles {missing}, which no source supplies")
+    with torch.cuda.device(out.device):
+        d_table = torch.from_numpy(table.view(np.uint8)).to(out.device)
+        _lib.check(_lib.lib().basic_image_tiles_blend_dev(d_table.data_ptr(), grid.H, grid.W, grid.th, grid.tw, grid.oy, grid.ox, C, y0, x0,
+                                                          y1 - y0, x1 - x0, out.data_ptr(), _lib.PIXEL_U8 if out.dtype == torch.uint8 else
+                                                          _lib.PIXEL_F32, IMAGE_LAYOUTS[layout], _stream()))
+    del keep
+    return out
 
 
 def image_sse_u8(a, b):

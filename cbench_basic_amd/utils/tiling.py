@@ -10,6 +10,13 @@ row-major order.  It states the picture's own size, which a tile's string does n
 size), and where each tile's string lies, which random access needs.  It says nothing about how the tiles' strings were written
 (stream lanes, row streams, levels): that stays the coder's configuration.
 
+Overlapped tiles (``overlap=(oy, ox)``, 0 <= 2 * oy <= th, 0 <= 2 * ox <= tw): the tiles' origins are ``sy = th - oy`` and ``sx = tw - ox``
+apart, ``rows = max(1, ceil((H - oy) / sy))`` (columns likewise), tile (i, j) starts at (i * sy, j * sx) and is th x tw, cut off at
+the picture's edge.  A sample is covered by at most two tiles per axis; the doubly covered samples of an axis are the bands
+``[(i + 1) * s, (i + 1) * s + o)``, over which a decoder cross-fades the two reconstructions (include/basic_hip.h section 8c); a last
+tile is always longer than the overlap.  Such a picture's container is  b"BTL2"  <B channels> <I H> <I W> <I th> <I tw> <I oy> <I ox>
+<I n>,  then lengths and strings as above; with overlap (0, 0) the container is BTL1, byte for byte.
+
 Pure host code: no torch, no device.
 """
 import struct
@@ -17,6 +24,8 @@ from typing import Iterator, List, NamedTuple, Sequence, Tuple
 
 MAGIC = b"BTL1"
 _HEAD = struct.Struct("<4sBIIIII")
+MAGIC2 = b"BTL2"
+_HEAD2 = struct.Struct("<4sBIIIIIII")
 
 
 class TileGroup(NamedTuple):
@@ -39,13 +48,29 @@ def _positive_int(name, v):
     return v
 
 
-class TileGrid:
-    """The tiles of an H x W picture cut into th x tw tiles (the edge tiles smaller)."""
+def _overlap_pair(overlap):
+    """``overlap`` -- an int or (oy, ox) -- as a pair of non-negative ints."""
+    try:
+        pair = (overlap, overlap) if isinstance(overlap, int) else tuple(overlap)
+    except TypeError:
+        pair = ()
+    if len(pair) != 2 or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in pair):
+        raise ValueError(f"overlap is a non-negative integer or (oy, ox), not {overlap!r}")
+    return pair
 
-    def __init__(self, H, W, th, tw):
+
+class TileGrid:
+    """The tiles of an H x W picture cut into th x tw tiles (the edge tiles smaller) whose neighbours share ``overlap = (oy, ox)``
+    rows and columns (none by default)."""
+
+    def __init__(self, H, W, th, tw, overlap=(0, 0)):
         self.H, self.W = _positive_int("H", H), _positive_int("W", W)
         self.th, self.tw = _positive_int("th", th), _positive_int("tw", tw)
-        self.rows, self.cols = -(-self.H // self.th), -(-self.W // self.tw)
+        self.oy, self.ox = self.overlap = _overlap_pair(overlap)
+        if 2 * self.oy > self.th or 2 * self.ox > self.tw:
+            raise ValueError(f"an overlap of {self.overlap} is more than half a {self.th} x {self.tw} tile")
+        self.sy, self.sx = self.th - self.oy, self.tw - self.ox   # the steps between the tiles' origins
+        self.rows, self.cols = max(1, -(-(self.H - self.oy) // self.sy)), max(1, -(-(self.W - self.ox) // self.sx))
 
     def __len__(self):
         return self.rows * self.cols
@@ -55,13 +80,13 @@ class TileGrid:
         if not 0 <= k < len(self):
             raise IndexError(f"tile {k} of {len(self)}")
         i, j = divmod(k, self.cols)
-        y, x = i * self.th, j * self.tw
+        y, x = i * self.sy, j * self.sx
         return y, x, min(self.th, self.H - y), min(self.tw, self.W - x)
 
-    def _bands(self, n, size, total, lo=0, hi=None):
+    def _bands(self, n, size, step, total, lo=0, hi=None):
         """Index ranges [a, b) of one axis within [lo, hi) that hold tiles of one size: the full ones, then the smaller last one."""
         hi = n if hi is None else hi
-        last = total - (n - 1) * size   # size of tile n - 1
+        last = total - (n - 1) * step   # size of tile n - 1
         if last == size or hi < n:
             return [(lo, hi, size)] if hi > lo else []
         out = [(lo, n - 1, size)] if n - 1 > lo else []
@@ -69,9 +94,9 @@ class TileGrid:
         return out
 
     def _groups(self, i0, i1, j0, j1) -> Iterator[TileGroup]:
-        for a, b, h in self._bands(self.rows, self.th, self.H, i0, i1):
-            for c, d, w in self._bands(self.cols, self.tw, self.W, j0, j1):
-                yield TileGroup(a * self.th, c * self.tw, self.th, self.tw, b - a, d - c, h, w,
+        for a, b, h in self._bands(self.rows, self.th, self.sy, self.H, i0, i1):
+            for c, d, w in self._bands(self.cols, self.tw, self.sx, self.W, j0, j1):
+                yield TileGroup(a * self.sy, c * self.sx, self.sy, self.sx, b - a, d - c, h, w,
                                 tuple(i * self.cols + j for i in range(a, b) for j in range(c, d)))
 
     def groups(self) -> List[TileGroup]:
@@ -79,10 +104,13 @@ class TileGrid:
         return list(self._groups(0, self.rows, 0, self.cols))
 
     def tiles_of_region(self, y0, x0, y1, x1) -> List[TileGroup]:
-        """The groups (sub-grids) of the tiles that intersect the rectangle [y0, y1) x [x0, x1)."""
+        """The groups (sub-grids) of the tiles that cover a sample of the rectangle [y0, y1) x [x0, x1): with an overlap, both
+        tiles of every band the rectangle touches."""
         if not (0 <= y0 < y1 <= self.H and 0 <= x0 < x1 <= self.W):
             raise ValueError(f"region {(y0, x0, y1, x1)} is empty or leaves the {self.H} x {self.W} picture")
-        return list(self._groups(y0 // self.th, -(-y1 // self.th), x0 // self.tw, -(-x1 // self.tw)))
+        # tile i of an axis covers [i * s, i * s + t): the first with i * s + t > lo, up to the last with i * s < hi
+        return list(self._groups(max(0, (y0 - self.th) // self.sy + 1), min(self.rows, -(-y1 // self.sy)),
+                                 max(0, (x0 - self.tw) // self.sx + 1), min(self.cols, -(-x1 // self.sx))))
 
 
 def split_group(group: TileGroup, max_batch=None) -> List[TileGroup]:
@@ -110,9 +138,9 @@ def split_group(group: TileGroup, max_batch=None) -> List[TileGroup]:
     return out
 
 
-def pack_tiled(channels, H, W, th, tw, strings: Sequence[bytes]) -> bytes:
-    """The container of a picture's tile strings (row-major order)."""
-    grid = TileGrid(H, W, th, tw)
+def pack_tiled(channels, H, W, th, tw, strings: Sequence[bytes], overlap=(0, 0)) -> bytes:
+    """The container of a picture's tile strings (row-major order): BTL1, or BTL2 when the tiles overlap."""
+    grid = TileGrid(H, W, th, tw, overlap)
     strings = [bytes(s) for s in strings]
     if len(strings) != len(grid):
         raise ValueError(f"{len(strings)} strings for {grid.rows} x {grid.cols} tiles")
@@ -120,24 +148,35 @@ def pack_tiled(channels, H, W, th, tw, strings: Sequence[bytes]) -> bytes:
         raise ValueError(f"channels must be in 1..255, not {channels!r}")
     if max(H, W, th, tw, len(strings), *[len(s) for s in strings]) >= 1 << 32:
         raise ValueError("a field of the container does not fit 32 bits")
-    return b"".join([_HEAD.pack(MAGIC, channels, H, W, th, tw, len(strings)),
+    head = _HEAD.pack(MAGIC, channels, H, W, th, tw, len(strings)) if grid.overlap == (0, 0) else \
+        _HEAD2.pack(MAGIC2, channels, H, W, th, tw, grid.oy, grid.ox, len(strings))
+    return b"".join([head,
                      struct.pack("<%dI" % len(strings), *[len(s) for s in strings])] + strings)
 
 
-def unpack_tiled(data):
-    """(channels, H, W, th, tw, [tile strings]) of a container; ValueError for anything that is not exactly one."""
+def unpack_tiled_any(data):
+    """(channels, H, W, th, tw, (oy, ox), [tile strings]) of a BTL1 or BTL2 container; ValueError for anything that is not exactly one."""
     data = bytes(data)
-    if data[:4] != MAGIC:
+    if data[:4] == MAGIC:
+        head, overlapped = _HEAD, False
+    elif data[:4] == MAGIC2:
+        head, overlapped = _HEAD2, True
+    else:
         raise ValueError("not a tiled picture: wrong magic")
-    if len(data) < _HEAD.size:
+    if len(data) < head.size:
         raise ValueError("truncated tiled picture: head cut short")
-    _, channels, H, W, th, tw, n = _HEAD.unpack_from(data)
+    fields = head.unpack_from(data)
+    channels, H, W, th, tw = fields[1:6]
+    oy, ox = fields[6:8] if overlapped else (0, 0)
+    n = fields[-1]
     if min(channels, H, W, th, tw) < 1:
         raise ValueError("tiled picture: a dimension is zero")
-    grid = TileGrid(H, W, th, tw)
+    if 2 * oy > th or 2 * ox > tw:
+        raise ValueError(f"tiled picture: an overlap of {(oy, ox)} is more than half a {th} x {tw} tile")
+    grid = TileGrid(H, W, th, tw, (oy, ox))
     if n != len(grid):
         raise ValueError(f"tiled picture: {n} tiles stated, {grid.rows} x {grid.cols} expected")
-    cur = _HEAD.size
+    cur = head.size
     if cur + 4 * n > len(data):
         raise ValueError("truncated tiled picture: length table cut short")
     lens = struct.unpack_from("<%dI" % n, data, cur)
@@ -150,4 +189,12 @@ def unpack_tiled(data):
         cur += L
     if cur != len(data):
         raise ValueError(f"tiled picture: {len(data) - cur} bytes after the last tile")
+    return channels, H, W, th, tw, (oy, ox), strings
+
+
+def unpack_tiled(data):
+    """(channels, H, W, th, tw, [tile strings]) of a BTL1 container; ValueError for anything that is not exactly one."""
+    if bytes(data[:4]) != MAGIC:
+        raise ValueError("not a tiled picture: wrong magic")
+    channels, H, W, th, tw, _, strings = unpack_tiled_any(data)
     return channels, H, W, th, tw, strings

@@ -475,9 +475,11 @@ int basic_hp_decode_images_u8(basic_hp_session *s, const uint8_t *data, int64_t 
 
 /* ======================================================================================
  * 8c. Tiles of one 8-bit picture (csrc/image.hip): a picture too large for one pass of the transforms, or one that is to
- *    be read in parts, is coded as independent tiles.  These two entries are the first and the last step of that: they
- *    cut a batch of float tiles out of ONE uint8 picture, and paste a batch of reconstructed tiles back into one, each
- *    in one memory pass (instead of one strided copy per tile and a conversion pass over the batch).
+ *    be read in parts, is coded as independent tiles.  The first two entries are the first and the last step of that:
+ *    they cut a batch of float tiles out of ONE uint8 picture, and paste a batch of reconstructed tiles back into one,
+ *    each in one memory pass (instead of one strided copy per tile and a conversion pass over the batch).  Tiles that
+ *    OVERLAP, so that the seams between them can be cross-faded, have two entries of their own further down: a cut that
+ *    accepts them, and the blend that writes the picture from all their reconstructions.
  *    A tile group is a regular grid of equally sized tiles inside the picture: tile (i, j), i < ny, j < nx, has its
  *    origin at (y0 + i * step_y, x0 + j * step_x), is th x tw, and has index i * nx + j.  The picture is uint8,
  *    [channels][img_h][img_w] (BASIC_IMAGE_CHW) or [img_h][img_w][channels] (BASIC_IMAGE_HWC); the float side is always
@@ -506,6 +508,53 @@ int basic_image_tiles_u8_to_f32_dev(const uint8_t *d_img, int layout, int channe
 int basic_image_tiles_f32_to_u8_dev(const float *d_src, int sh, int sw, int channels,
                                     int y0, int x0, int step_y, int step_x, int ny, int nx, int th, int tw,
                                     uint8_t *d_img, int layout, int img_h, int img_w, void *hip_stream);
+/* The cut for OVERLAPPED tiles: basic_image_tiles_u8_to_f32_dev without the refusal of a step smaller than the tile
+ * (step_y, step_x >= 1 is all that is asked; the tiles are only read, so they may share samples).  The same kernels, the
+ * same values, the same wide / scalar rule and the same basic_image_tiles_last_path report. */
+int basic_image_tiles_overlap_u8_to_f32_dev(const uint8_t *d_img, int layout, int channels, int img_h, int img_w,
+                                            int y0, int x0, int step_y, int step_x, int ny, int nx, int th, int tw,
+                                            float *d_dst, void *hip_stream);
+/* Blend: the way back for overlapped tiles.  The grid is that of a whole picture (cbench_basic_amd/utils/tiling.py):
+ * steps sy = th - oy, sx = tw - ox with 0 <= 2 oy <= th, 0 <= 2 ox <= tw; rows = max(1, ceil((img_h - oy) / sy)), cols
+ * likewise; tile (i, j) has its origin at (i * sy, j * sx) and is th x tw, cut off at the picture's edge.  Along an axis
+ * the samples [(i + 1) * s, (i + 1) * s + o) are covered by tiles i and i + 1, every other sample by one tile.
+ * ONE launch writes the rectangle [ry0, ry0 + rh) x [rx0, rx0 + rw) of the picture, as a picture of its own --
+ * [channels][rh][rw] (BASIC_IMAGE_CHW) or [rh][rw][channels] (BASIC_IMAGE_HWC), uint8 (BASIC_PIXEL_U8) or float32
+ * (BASIC_PIXEL_F32) -- from the reconstructions of the tiles that cover it.  It is a gather: d_table, in DEVICE memory, has
+ * one basic_tile_source per tile in row-major order; entry i * cols + j describes the float32 [channels][sh][sw]
+ * reconstruction of tile (i, j), sh and sw at least the tile's own height and width (the caller's duty: the table cannot
+ * be read from the host), wherever the decoder left it.  Entries of one table may differ in sh x sw.  No staging copy,
+ * no accumulation buffer, no read of the output.
+ * Values.  ramp[d] = (float)((2 * d + 1) / (2.0 * o)), d = 0 .. o - 1: a double division rounded once to fp32.
+ * lerp(a, b, w) = a + w * (b - a): one fp32 subtract, one multiply, one add, each rounded, never a fused multiply-add.
+ * A sample at distance d into the band of tiles i and i + 1 of one axis is lerp(a, b, ramp[d]), a from tile i, b from
+ * tile i + 1.  In a band of both axes: top = lerp(r[i][j], r[i][j + 1], wx), bottom = lerp(r[i + 1][j], r[i + 1][j + 1],
+ * wx), v = lerp(top, bottom, wy).  In no band: its tile's value.  The float output is v, the uint8 output section 8b's
+ * uint8(rint(min(max(v, 0), 1) * 255.0f)), NaN -> 0, from the same device code.  So: where the covering tiles agree (and
+ * are finite) the result is that value; with overlap 0 it is the paste; and a sample's value depends on the tiles that
+ * cover it alone, not on the other entries, the chunks they came from or the launch shape.
+ * A null src marks a tile that was not decoded.  The kernel never dereferences one: the output samples that need that
+ * tile keep the value they had, every other sample of the rectangle is written.
+ * Wide path: a lane owns four consecutive output samples of one row (one plane; with BASIC_IMAGE_HWC and channels 3 or 4,
+ * four pixels of all channels) and reads each source with one 16-byte load where that source's address allows, four
+ * 4-byte loads otherwise.  Taken when the output base is 4-byte (uint8) or 16-byte (float32) aligned, rx0, rw, sx and ox
+ * are multiples of 4 -- the four samples then share their tiles and their band -- and, with BASIC_IMAGE_HWC and more than
+ * one channel, channels is 3 or 4.  Every other call goes sample by sample.  Both paths give the same values;
+ * basic_image_tiles_last_path reports the one taken.
+ * Element offsets are 64-bit; one launch on hip_stream, nothing allocated, nothing synchronised.  BASIC_ERR_INVALID with
+ * a message, before any launch, for a null pointer, an unknown layout or out_kind, a non-positive size, a negative
+ * overlap or one above half a tile, a rectangle that leaves the picture, a float32 output that is not float-aligned, or
+ * more than 2^40 output samples. */
+#define BASIC_PIXEL_U8 0
+#define BASIC_PIXEL_F32 1
+typedef struct basic_tile_source {
+    const float *src; /* [channels][sh][sw] in device memory, or NULL: not decoded */
+    int32_t sh, sw;
+} basic_tile_source;
+int basic_image_tiles_blend_dev(const basic_tile_source *d_table /* [rows * cols], device memory */,
+                                int img_h, int img_w, int th, int tw, int oy, int ox, int channels,
+                                int ry0, int rx0, int rh, int rw, void *d_out, int out_kind, int layout,
+                                void *hip_stream);
 /* The path the calling thread's last tiles call took: 0 scalar, 1 wide; -1 before any (as basic_rans_last_launch: written
  * where the kernel is chosen, read by tests). */
 int basic_image_tiles_last_path(int *path);

@@ -82,6 +82,9 @@ def main(argv=None):
                     help="testing_tile: code every picture as independent TH x TW tiles (TW = TH when omitted) through compress_tiled / "
                          "decompress_tiled; compressed_length is the container's, the distortion the whole picture's (needs "
                          "--batch-size 1, does not combine with --coalesce above 1)")
+    ap.add_argument("--tile-overlap", type=int, nargs="+", default=None, metavar=("OY", "OX"),
+                    help="testing_tile_overlap: neighbouring tiles share OY rows and OX columns (OX = OY when omitted; at most half a tile) and "
+                         "decompress_tiled cross-fades the seams (needs --tile)")
     ap.add_argument("--stream-lanes", type=int, default=1,
                     help="lane streams per image of the y-coder, any codec (a format the reference does not read)")
     ap.add_argument("--stream-rows", action="store_true",
@@ -118,6 +121,16 @@ def main(argv=None):
         if args.coalesce > 1 or args.batch_size != 1:
             ap.error("--tile codes one picture per call: it does not combine with --coalesce above 1 or --batch-size other than 1")
         args.tile = (args.tile[0], args.tile[-1])
+    if args.tile_overlap is not None:
+        if args.tile is None:
+            ap.error("--tile-overlap needs --tile")
+        if len(args.tile_overlap) > 2 or min(args.tile_overlap) < 0:
+            ap.error("--tile-overlap takes OY [OX], not negative")
+        args.tile_overlap = (args.tile_overlap[0], args.tile_overlap[-1])
+        if 2 * args.tile_overlap[0] > args.tile[0] or 2 * args.tile_overlap[1] > args.tile[1]:
+            ap.error("--tile-overlap is at most half a tile")
+    else:
+        args.tile_overlap = (0, 0)
     if args.workers > 1:   # before HIP initialises: one hardware queue per worker stream
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         os.environ.setdefault("BASIC_RANS_WPB", "8")
@@ -149,7 +162,7 @@ def main(argv=None):
 
     def warm(c):   # one item through the route the pass takes
         if args.tile is not None:
-            c.decompress_tiled(c.compress_tiled(batches[0].to("cuda"), tile=args.tile))
+            c.decompress_tiled(c.compress_tiled(batches[0].to("cuda"), tile=args.tile, overlap=args.tile_overlap))
         else:
             c.decompress(c.compress(batches[0].to("cuda")))
     warm_chunks = []
@@ -174,7 +187,7 @@ def main(argv=None):
                                               nn_codec_use_forward_pass=args.forward_pass,
                                               testing_complexity_levels=args.complexity_levels,
                                               testing_variable_rate_levels=args.rate_levels, output_dir=args.out,
-                                              num_testing_workers=args.workers, testing_coalesce_items=args.coalesce, testing_tile=args.tile,
+                                              num_testing_workers=args.workers, testing_coalesce_items=args.coalesce, testing_tile=args.tile, testing_tile_overlap=args.tile_overlap,
                                               codec_builder=(lambda: presets.seed_synthetic_weights(builders[args.codec](), seed=0)) if args.workers > 1 else None)
     if args.workers > 1 and args.warmup:   # the replicas' one-time costs too, one replica at a time (HIP-graph capture)
         pool = bench._worker_pool(batches[0], batch=max((len(c) for c in warm_chunks), default=None))
