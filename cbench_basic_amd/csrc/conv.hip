@@ -61,8 +61,10 @@ constexpr int stage_channels(int ntaps, int waves)
     return (ntaps > kFewTaps ? 2 : (ntaps > kVeryFewTaps ? 4 : 8)) * (waves == 8 ? 2 : 1);
 }
 // 8-wave workgroups pay off for the 25-tap, 128-channel convolutions (measured: +3..5 %); the few-tap phases of
-// the transposed convolutions run faster as two 4-wave workgroups per CU.
-constexpr int plan_waves(int mt, int ntaps) { return (mt == 4 && ntaps > kFewTaps) ? 8 : 4; }
+// the transposed convolutions run faster as two 4-wave workgroups per CU.  GDN layers only: a plain-activation layer also
+// has a 32-channel-slice launch list (mt 1, 4 waves), and the channels per stage are the K order of every output
+// ("K order of the fp32 tap kernel"): both lists of a layer must stage alike, or its bits depend on the batch.
+constexpr int plan_waves(int mt, int ntaps, bool gdn) { return (gdn && mt == 4 && ntaps > kFewTaps) ? 8 : 4; }
 constexpr int kMaxTaps = 25;  // 5x5
 constexpr int kTilePos = 128;  // output positions per workgroup
 constexpr int kPSlots = 12;             // patch elements per thread and stage (patch <= 3072 floats) ...
@@ -1524,6 +1526,14 @@ int build_chunks(basic_conv_plan *p, const float *weight, const float *bias, int
     const int nph = transposed ? stride : 1;
     const int n_chunks = slice ? 1 : (co_n + kMaxCoutPerLaunch - 1) / kMaxCoutPerLaunch;
     const int per_chunk = slice ? co_n : ((co_n + n_chunks - 1) / n_chunks + 31) / 32 * 32;  // balanced, whole M-tiles
+    const bool gdn = p->act == BASIC_ACT_GDN || p->act == BASIC_ACT_IGDN;
+    // column phases (py, 0) = a and (py, 1) = b that one launch can compute from one patch: the second grid inside the first
+    // (same rows, columns shifted right by kw - kwb) -- true for the codec's k5 s2 p2 transposed convolutions
+    auto fusable = [](const Phase &a, const Phase &b) {
+        return a.ntaps > 0 && b.ntaps > 0 && a.kh == b.kh && a.dymin == b.dymin && b.kw <= a.kw &&
+               b.dxmin - a.dxmin == a.kw - b.kw && a.ox0 == 0 && b.ox0 == 1 &&
+               ((a.kh == 3 && a.kw == 3 && b.kw == 2) || (a.kh == 2 && a.kw == 3 && b.kw == 2));
+    };
     for (int co0 = 0; co0 < co_n; co0 += per_chunk) {
         Chunk ch;
         ch.co0 = co0;
@@ -1531,6 +1541,8 @@ int build_chunks(basic_conv_plan *p, const float *weight, const float *bias, int
         ch.mt = slice ? slice / 32 : (ch.cout + 31) / 32;
         ch.coutp = ch.mt * 32;
         ch.nsplit = slice ? (ch.cout + slice - 1) / slice : 1;
+        // ---- geometry of every phase first: the channels per stage of a phase depend on its siblings (below)
+        std::vector<std::vector<std::pair<int, int>>> phase_taps;  // (ky, kx) of tap t of phase i, (-1, -1) for a hole
         for (int py = 0; py < nph; ++py)
             for (int px = 0; px < nph; ++px) {
                 Phase ph;
@@ -1546,9 +1558,10 @@ int build_chunks(basic_conv_plan *p, const float *weight, const float *bias, int
                 }
                 if (kys.empty() || kxs.empty()) {  // phase receives only the bias
                     ph.ntaps = 0;
-                    ph.waves = plan_waves(ch.mt, 0);
+                    ph.waves = plan_waves(ch.mt, 0, gdn);
                     ph.ck = stage_channels(0, ph.waves);  // must match the instantiation launch_mt picks (LDS layout)
                     ch.phases.push_back(ph);
+                    phase_taps.emplace_back();
                     continue;
                 }
                 int dymin = dys[0], dymax = dys[0], dxmin = dxs[0], dxmax = dxs[0];
@@ -1568,9 +1581,22 @@ int build_chunks(basic_conv_plan *p, const float *weight, const float *bias, int
                     ph.dy[t] = static_cast<signed char>(t / ph.kw);
                     ph.dx[t] = static_cast<signed char>(t % ph.kw);
                 }
+                ph.waves = plan_waves(ch.mt, ph.ntaps, gdn);
+                ch.phases.push_back(ph);
+                phase_taps.push_back(taps);
+            }
+        // A plain-activation layer of more than 4 M-tiles runs its phases one by one here, while its 32-channel slices
+        // fuse the column phases at kFusedCK channels per stage: the phases take that staging too, so that an output
+        // sums in the same order in both launch lists.  (Four-phase launches of <= 4 M-tiles, the fallback for output
+        // rows that are not 8-byte aligned, keep their staging in both lists.)
+        const bool fused_order = !gdn && !slice && ch.mt > 4 && transposed && stride == 2 && ch.phases.size() == 4 &&
+                                 fusable(ch.phases[0], ch.phases[1]) && fusable(ch.phases[2], ch.phases[3]);
+        for (size_t pi = 0; pi < ch.phases.size(); ++pi) {
+            Phase &ph = ch.phases[pi];
+            const std::vector<std::pair<int, int>> &taps = phase_taps[pi];
+            if (ph.ntaps > 0) {  // (a bias-only phase has no pack)
                 // ---- pack weights: [slice][cin_pad/CK][ntaps][CK][32][MTP]
-                ph.waves = plan_waves(ch.mt, ph.ntaps);
-                const int kCK = stage_channels(ph.ntaps, ph.waves);
+                const int kCK = fused_order ? kFusedCK : stage_channels(ph.ntaps, ph.waves);
                 const int mtp = mtile_pitch(ch.mt);
                 ph.ck = kCK;
                 ph.cin_pad = (ci_n + kCK - 1) / kCK * kCK;
@@ -1605,20 +1631,17 @@ int build_chunks(basic_conv_plan *p, const float *weight, const float *bias, int
                         }
                     rc = upload(wr, &ph.d_wrow);
                 }
-                ch.phases.push_back(ph);
                 if (rc) { out->push_back(ch); return rc; }
             }
+        }
         // Fused column phases (see conv_tap_mfma_kernel, KWB): for every row phase py, the launch (py, px = 0) takes the
-        // taps of (py, px = 1) after its own.  Needs the second grid inside the first (same rows, columns shifted right
-        // by kw - kwb) -- true for the codec's k5 s2 p2 transposed convolutions -- and at most 4 accumulator tiles.
+        // taps of (py, px = 1) after its own.  Needs a fusable pair (above) and at most 4 accumulator tiles.
         if (transposed && stride == 2 && ch.mt <= 4 && ch.phases.size() == 4) {
             bool ok = true;
             std::vector<Phase> fused;
             for (int py = 0; py < 2 && ok; ++py) {
                 const Phase &a = ch.phases[py * 2], &b = ch.phases[py * 2 + 1];
-                ok = a.ntaps > 0 && b.ntaps > 0 && a.kh == b.kh && a.dymin == b.dymin && b.kw <= a.kw &&
-                     b.dxmin - a.dxmin == a.kw - b.kw && a.ox0 == 0 && b.ox0 == 1 && a.cin_pad % kFusedCK == 0 &&
-                     ((a.kh == 3 && a.kw == 3 && b.kw == 2) || (a.kh == 2 && a.kw == 3 && b.kw == 2));
+                ok = fusable(a, b) && a.cin_pad % kFusedCK == 0;
                 if (!ok) break;
                 Phase f = a;
                 f.kwb = b.kw;
@@ -1806,13 +1829,29 @@ template <int MT>
 int launch_mt(const TapLaunch &g, int kh, int kw, int plan_ck, int plan_waves_, int blocks, int nsplit, size_t lds_bytes,
               hipStream_t st)
 {
-    constexpr int WM = plan_waves(MT, kMaxTaps), WF = plan_waves(MT, kFewTaps), WV = plan_waves(MT, kVeryFewTaps);
+    // the 8-wave shape of the GDN layers' 128-channel, many-tap launches (plan_waves)
+    if constexpr (plan_waves(MT, kMaxTaps, true) == 8) {
+        if (plan_waves_ == 8) {
+            constexpr int kMany8 = stage_channels(kMaxTaps, 8);
+            BASIC_REQUIRE(g.ntaps > kFewTaps && plan_ck == kMany8, "conv_forward: plan / kernel instantiation mismatch");
+            if (kh == 5 && kw == 5) return launch_one<MT, kMany8, 5, 5, 8>(g, blocks, nsplit, lds_bytes, st);
+            return launch_one<MT, kMany8, 0, 0, 8>(g, blocks, nsplit, lds_bytes, st);
+        }
+    }
+    // the phases of a plain-activation layer of more than 4 M-tiles, staged like the fused launches of its slices (build_chunks)
+    if constexpr (MT > 4) {
+        if (plan_ck == kFusedCK && plan_waves_ == 4 && g.ntaps > 0 && g.ntaps <= kVeryFewTaps) {
+            if (kh == 3 && kw == 2) return launch_one<MT, kFusedCK, 3, 2, 4>(g, blocks, nsplit, lds_bytes, st);
+            if (kh == 2 && kw == 3) return launch_one<MT, kFusedCK, 2, 3, 4>(g, blocks, nsplit, lds_bytes, st);
+            if (kh == 2 && kw == 2) return launch_one<MT, kFusedCK, 2, 2, 4>(g, blocks, nsplit, lds_bytes, st);
+        }
+    }
+    constexpr int WM = 4, WF = 4, WV = 4;
     constexpr int kMany = stage_channels(kMaxTaps, WM), kFew = stage_channels(kFewTaps, WF), kVeryFew = stage_channels(kVeryFewTaps, WV);
     // the packing (channels per stage) and the LDS size were derived from the plan's values: they must be the
     // instantiation's, or the kernel would walk off its LDS allocation
     const int inst_ck = g.ntaps > kFewTaps ? kMany : (g.ntaps > kVeryFewTaps ? kFew : kVeryFew);
-    const int inst_waves = g.ntaps > kFewTaps ? WM : (g.ntaps > kVeryFewTaps ? WF : WV);
-    BASIC_REQUIRE(inst_ck == plan_ck && inst_waves == plan_waves_, "conv_forward: plan / kernel instantiation mismatch");
+    BASIC_REQUIRE(inst_ck == plan_ck && plan_waves_ == 4, "conv_forward: plan / kernel instantiation mismatch");
     if (g.ntaps > kFewTaps) {
         if (kh == 5 && kw == 5) return launch_one<MT, kMany, 5, 5, WM>(g, blocks, nsplit, lds_bytes, st);
         return launch_one<MT, kMany, 0, 0, WM>(g, blocks, nsplit, lds_bytes, st);

@@ -5,7 +5,7 @@ Launch paths (basic_conv_forward_dev / choose_launches) and the PATHS cases belo
   path                                          selected by                                               cases
   conv_tap_mfma_kernel MT 1..6, 4 waves         ceil(cout / 32) accumulator tiles per launch              mt1_k3, mt2_k5, mt3_k4, mt5_k2, mt6_k5,
                                                                                                            mt4_k3_igdn
-  conv_tap_mfma_kernel MT 4, 8 waves            plan_waves: MT 4 and more than 9 taps                     mt4_k5_gdn_8w, chunk cases
+  conv_tap_mfma_kernel MT 4, 8 waves            plan_waves: GDN, MT 4 and more than 9 taps                mt4_k5_gdn_8w, table16_mt4
   runtime tap table (KH = 0)                    a tap grid other than 5x5 / 3x3 / 3x2 / 2x3 / 2x2         table16_mt1..6 (4x4), table1_mt1..6 (1x1),
                                                 (the 7..9-tap table variant is unreachable: only 3x3       mt3_k4, tr_k3s2 phases (1x1, 1x2, 2x1)
                                                 grids have 7..9 taps at k <= 5, stride <= 2)
