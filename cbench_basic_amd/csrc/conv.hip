@@ -1,7 +1,8 @@
 // Analysis / synthesis transforms: tap-list implicit-GEMM convolution on the fp32 matrix core
 // (v_mfma_f32_32x32x2_f32) with LDS-staged activation patches and a fused
 // bias + {ReLU, LeakyReLU, GDN, IGDN} epilogue.  The 128-channel launches of the synthesis transform (IGDN layers) run on
-// the bf16 matrix core instead, with fp32 operands split exactly into three bf16 pieces (conv_split_bf16_kernel).
+// the fp16 matrix core instead, with fp32 operands scaled by a power of two and split into two fp16 pieces (conv_split_f16_kernel,
+// DESIGN.md §12).
 //
 // Replaces the ATen calls behind nn/models/google.py:25-101 (compressai conv/deconv/GDN) and
 // nn/layers/slimmable_layers.py:157-183,258-282 (weight slicing = plan of the active slice).
@@ -28,6 +29,8 @@
 //     reads per MT MFMAs, nothing else); the remaining losses are stage barriers and DMA issue.
 #include "common.h"
 
+#include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -472,14 +475,20 @@ __global__ __launch_bounds__(64 * WAVES, (MT <= 4 && WAVES == 4 ? 2 : 1)) void c
 }
 
 // ---------------------------------------------------------------------------------------------
-// Split-bf16 path of the 128-channel synthesis layers.  gfx950 has no TF32, and its bf16 MFMA runs at 16x the
-// fp32 MFMA rate.  Every fp32 operand is split exactly into three bf16 pieces x = x0 + x1 + x2 (8 + 8 + 8 significant bits,
-// each the truncation of what is left), and the six products with i + j <= 2 are accumulated smallest first:
-//     a2b0, a1b1, a0b2, a1b0, a0b1, a0b0      (the three left out are below 2^-24 |a b|)
-// = 6 v_mfma_f32_32x32x16_bf16 (32 cycles each) per 16 K-values instead of 8 v_mfma_f32_32x32x2_f32 (64 cycles each).
+// Split-fp16 path of the 128-channel synthesis layers.  gfx950 has no TF32, and its fp16 MFMA runs at 16x the
+// fp32 MFMA rate.  Every fp32 operand is scaled by a power of two and split into two fp16 pieces by round-to-nearest,
+// x0 = RN16(x), x1 = RN16(x - x0) (the subtraction is exact; x0 + x1 = x to 2^-24 relative while x1 stays above fp16's
+// subnormal spacing, which the scaling sees to), and three products are accumulated smallest first:
+//     a1b0, a0b1, a0b0      (a1b1 is below 2^-24 |a b|; every fp16 x fp16 product is exact in fp32)
+// = 3 v_mfma_f32_32x32x16_f16 (32 cycles each) per 16 K-values instead of 8 v_mfma_f32_32x32x2_f32 (64 cycles each).
+//   * Scaling, exact and undone exactly by one ldexp per accumulator value in the epilogue:
+//       weights      per output channel o by 2^kw[o], so that max |w| 2^kw[o] lies in [2^13, 2^14) (plan time, pack_split);
+//       activations  per IMAGE b by 2^kx[b], so that max |x| 2^kx[b] lies in [2^14, 2^15): image_absmax_kernel writes the
+//                    maxima once per forward call, every staging item and lane derives the kx of its own image from them.
+//                    Per image, not per tensor or tile: an image's bits do not depend on its neighbours or the tile geometry.
 //   * A = weights, split once at plan time (basic_conv_plan_create) in A-fragment order
 //     [cin/16][tap][m-tile][piece][lane][8]: one ds_read_b128 per (m-tile, piece).  They are staged through LDS
-//     (5 taps x 16 channels = 60 KB per stage, two stages) by register staging: plain global loads, so that the
+//     (5 taps x 16 channels = 40 KB per stage, two stages) by register staging: plain global loads, so that the
 //     compiler's counted vmcnt waits keep the activation loads below in flight.
 //   * B = activations, read from the fp32 NCHW input by buffer loads (positions outside the image come back as zeros
 //     from an out-of-range offset).  Two sources, the template parameter PATCH:
@@ -491,7 +500,8 @@ __global__ __launch_bounds__(64 * WAVES, (MT <= 4 && WAVES == 4 ? 2 : 1)) void c
 //         split in registers right before their MFMAs, i.e. once per tap that reads them.
 //     Both feed the MFMAs the same pieces in the same order: the results are identical bit for bit.  Nothing else
 //     changes: the input and output stay fp32 NCHW.
-//   * One fixed K order per output element (channel block, then tap): results do not depend on tile, batch or launch.
+//   * One fixed K order per output element (channel block, then tap, then the three products): results do not depend on
+//     tile, batch or launch.
 // Workgroup = 8 waves x 32 positions, each wave owns all 128 output channels of its positions (MT = 4), so the
 // bias / GDN / IGDN epilogue of conv_tap_mfma_kernel applies unchanged (its second GEMM stays fp32).
 // The launch is the fused column phases (KWB > 0) of a stride-2 transposed convolution, as in conv_tap_mfma_kernel.
@@ -499,53 +509,86 @@ __global__ __launch_bounds__(64 * WAVES, (MT <= 4 && WAVES == 4 ? 2 : 1)) void c
 // quantised and coded, and a different rounding moves a few latents across a rounding boundary: the bitstream would no
 // longer be the fp32 path's byte for byte.
 // ---------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSplitWaves = 8;
 constexpr int kSplitThreads = 64 * kSplitWaves;
-constexpr int kSplitCK = 16;                           // input channels per K block (the K of one bf16 MFMA)
+constexpr int kSplitCK = 16;                           // input channels per K block (the K of one fp16 MFMA)
 constexpr int kSplitStageTaps = 5;                     // taps per weight stage (15 and 10 taps per channel block)
-constexpr int kSplitBlockU4 = 4 * 3 * 64;              // 16-byte A fragments of one (channel block, tap): m-tile x piece x lane
-constexpr int kSplitStageU4 = kSplitStageTaps * kSplitBlockU4;                     // 3840 = 60 KB
-constexpr int kSplitWSlots = (kSplitStageU4 + kSplitThreads - 1) / kSplitThreads;  // 8 staged pieces per thread
-static_assert(kSplitWSlots % 2 == 0, "weight stage in two halves");
-constexpr size_t kSplitLdsBytes = 2 * kSplitStageU4 * 16 + 2 * 128 * sizeof(float);  // two stages + bias, beta
+constexpr int kSplitBlockU4 = 4 * 2 * 64;              // 16-byte A fragments of one (channel block, tap): m-tile x piece x lane
+constexpr int kSplitStageU4 = kSplitStageTaps * kSplitBlockU4;                     // 2560 = 40 KB
+constexpr int kSplitWSlots = (kSplitStageU4 + kSplitThreads - 1) / kSplitThreads;  // 5 staged pieces per thread
+constexpr size_t kSplitLdsBytes = 2 * kSplitStageU4 * 16 + 3 * 128 * sizeof(float);  // two stages + bias, beta, kw
+constexpr int kSplitWTop = 13, kSplitXTop = 14;  // scaled maxima: |w| in [2^13, 2^14) per output channel, |x| in [2^14, 2^15) per image
 
-// x = x0 + x1 + x2 exactly (normal range): each piece is the bf16 truncation of what the previous ones leave.
-// Returns the three pieces of 8 values as bf16x8 (element j = x[j]).
-__device__ __forceinline__ void split_bf16x3(const float (&x)[8], u32x4 &p0, u32x4 &p1, u32x4 &p2)
+// The power of two that takes an image's max |x| (its float bits, from image_absmax_kernel) into [2^14, 2^15); 0 for an
+// all-zero image and for one that holds an infinity or a NaN (bits above infinity's).
+__device__ __forceinline__ int split_act_exp(unsigned amax_bits)
+{
+    const int e = static_cast<int>(amax_bits >> 23);
+    return (amax_bits == 0 || e >= 255) ? 0 : kSplitXTop + 127 - e;
+}
+
+// x 2^k = x0 + x1 to 2^-24 relative: x0 the fp16 nearest to the scaled value, x1 the fp16 nearest to what x0 leaves.
+// Returns the two pieces of 8 values as f16x8 (element j = x[j]).
+__device__ __forceinline__ void split_f16x2(const float (&x)[8], int k, u32x4 &p0, u32x4 &p1)
 {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const unsigned a = __float_as_uint(x[2 * i]), b = __float_as_uint(x[2 * i + 1]);
-        const unsigned a0 = a & 0xFFFF0000u, b0 = b & 0xFFFF0000u;
-        p0[i] = (a >> 16) | b0;
-        const unsigned ra = __float_as_uint(x[2 * i] - __uint_as_float(a0)), rb = __float_as_uint(x[2 * i + 1] - __uint_as_float(b0));
-        const unsigned a1 = ra & 0xFFFF0000u, b1 = rb & 0xFFFF0000u;
-        p1[i] = (ra >> 16) | b1;
-        const unsigned sa = __float_as_uint(__uint_as_float(ra) - __uint_as_float(a1)), sb = __float_as_uint(__uint_as_float(rb) - __uint_as_float(b1));
-        p2[i] = (sa >> 16) | (sb & 0xFFFF0000u);
+        f32x2 v;
+        v[0] = __builtin_ldexpf(x[2 * i], k);
+        v[1] = __builtin_ldexpf(x[2 * i + 1], k);
+        const f16x2 h0 = __builtin_convertvector(v, f16x2);
+        const f16x2 h1 = __builtin_convertvector(v - __builtin_convertvector(h0, f32x2), f16x2);
+        p0[i] = __builtin_bit_cast(unsigned, h0);
+        p1[i] = __builtin_bit_cast(unsigned, h1);
     }
 }
 
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4 &a, const u32x4 &b, const f32x16 &c)
+__device__ __forceinline__ f32x16 mfma_f16(const u32x4 &a, const u32x4 &b, const f32x16 &c)
 {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
-// Split activation patch of the PATCH source, after the stages: 3 pieces x kSplitPatchPos positions x 16 channels x 2 B.
-// kSplitPatchPos takes the rest of the 160 KB: a 16 x 16 tile's patch is 18 x 18 (KH = 3) or 17 x 18 (KH = 2) positions.
+// max |x| of every image of a [batch][n] fp32 tensor as the float's bits in amax[batch] (zeroed before the launch): non-negative
+// floats order like their bits, and a NaN reads as larger than infinity -- the "non-finite" signal of split_act_exp.
+// gridDim.x = batch x per_img workgroups; wave reductions, then one atomicMax per wave.
+__global__ __launch_bounds__(256) void image_absmax_kernel(const float *x, int64_t n, int per_img, unsigned *amax)
+{
+    const int img = blockIdx.x / per_img, part = blockIdx.x - img * per_img;
+    const float *src = x + img * n;
+    unsigned m = 0;
+    if (((reinterpret_cast<uintptr_t>(src) | static_cast<uintptr_t>(n * 4)) & 15) == 0) {
+        const u32x4 *s4 = reinterpret_cast<const u32x4 *>(src);
+        for (int64_t i = part * 256 + threadIdx.x; i < n / 4; i += per_img * 256) {
+            const u32x4 v = s4[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m = max(m, v[e] & 0x7FFFFFFFu);
+        }
+    } else {
+        for (int64_t i = part * 256 + threadIdx.x; i < n; i += per_img * 256) m = max(m, __float_as_uint(src[i]) & 0x7FFFFFFFu);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = max(m, static_cast<unsigned>(__shfl_xor(static_cast<int>(m), off)));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(amax + img, m);
+}
+
+// Split activation patch of the PATCH source, after the stages: 2 pieces x kSplitPatchPos positions x 16 channels x 2 B.
+// A 16 x 16 tile's patch is 18 x 18 (KH = 3) or 17 x 18 (KH = 2) positions, four 8 x 8 images' are 4 x 10 x 10.
 constexpr int kSplitPatchPos = 416;
 constexpr int kSplitPieceBytes = kSplitPatchPos * 32;
-constexpr size_t kSplitLdsPatchBytes = kSplitLdsBytes + 3 * kSplitPieceBytes;
+constexpr size_t kSplitLdsPatchBytes = kSplitLdsBytes + 2 * kSplitPieceBytes;
 static_assert(kSplitLdsPatchBytes <= 160 * 1024, "patch beside the weight stages");
 static_assert(kSplitLdsBytes % 16 == 0, "16-byte aligned patch");
-// patch staging items = (position, 8-channel half): 8 buffer loads, one split and three ds_write_b128 each
+// patch staging items = (position, 8-channel half): 8 buffer loads, one split and two ds_write_b128 each
 constexpr int kSplitPatchRounds = (2 * kSplitPatchPos + kSplitThreads - 1) / kSplitThreads;
 
 template <int KH, int KW, int KWB, bool PATCH>
-__global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const TapLaunch g, const u32x4 *wsplit)
+__global__ __launch_bounds__(kSplitThreads, 1) void conv_split_f16_kernel(const TapLaunch g, const u32x4 *wsplit, const int *kw,
+                                                                          const unsigned *amax)
 {
     constexpr int MT = 4;
     constexpr int kTapsA = KH * KW, kTapsAll = KH * (KW + KWB);
@@ -553,7 +596,7 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
     static_assert(kTapsAll % kSplitStageTaps == 0, "taps per channel block must be whole stages");
     static_assert(KWB > 0 && KWB <= KW, "fused phases: second grid inside the first");
     extern __shared__ u32x4 lds_u4[];
-    float *chan_const = reinterpret_cast<float *>(lds_u4 + 2 * kSplitStageU4);  // [128] bias, [128] beta
+    float *chan_const = reinterpret_cast<float *>(lds_u4 + 2 * kSplitStageU4);  // [128] bias, [128] beta, [128] kw (int)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -578,6 +621,7 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
     if (tid < 128) {
         chan_const[tid] = g.bias ? g.bias[tid] : 0.f;
         chan_const[128 + tid] = g.beta ? g.beta[tid] : 1.f;
+        reinterpret_cast<int *>(chan_const)[256 + tid] = kw[tid];
     }
 
     // Activations of this tile's images through one buffer resource: a lane whose tap falls outside the image (or whose
@@ -614,31 +658,36 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
             d[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff + j * plane_bytes, 0));
     };
 
-    // weight stages: register-staged one stage ahead, in two halves of 4 pieces per thread (fewer staging registers)
+    // power-of-two scale of this lane's image (direct source; the epilogue reads it again rather than keep it alive)
+    int kx_l = 0;
+    if constexpr (!PATCH) kx_l = b < g.batch ? split_act_exp(amax[b]) : 0;
+
+    // weight stages: register-staged one stage ahead, in two halves of 3 and 2 pieces per thread (fewer staging registers)
     const int ncb = g.cin / kSplitCK;
-    constexpr int kHalf = kSplitWSlots / 2;
+    constexpr int kHalf = (kSplitWSlots + 1) / 2;
     u32x4 wst[kHalf];
     auto fetch_w = [&](int s, int h) __attribute__((always_inline)) {
         const u32x4 *src = wsplit + static_cast<int64_t>(s) * kSplitStageU4 + tid;
 #pragma unroll
-        for (int sl = h * kHalf; sl < (h + 1) * kHalf; ++sl)
+        for (int sl = h * kHalf; sl < (h + 1) * kHalf && sl < kSplitWSlots; ++sl)
             if (sl * kSplitThreads + tid < kSplitStageU4) wst[sl - h * kHalf] = src[sl * kSplitThreads];
     };
     auto store_w = [&](int buf, int h) __attribute__((always_inline)) {
         u32x4 *dst = lds_u4 + buf * kSplitStageU4 + tid;
 #pragma unroll
-        for (int sl = h * kHalf; sl < (h + 1) * kHalf; ++sl)
+        for (int sl = h * kHalf; sl < (h + 1) * kHalf && sl < kSplitWSlots; ++sl)
             if (sl * kSplitThreads + tid < kSplitStageU4) dst[sl * kSplitThreads] = wst[sl - h * kHalf];
     };
 
     // PATCH source.  Patch position p = (image, row, column) of the TB x PH x PW patch whose origin is the tile's first tap
     // (s_in = 1, npos <= kSplitPatchPos: host-checked); [piece][p][16 channels] in LDS, 32 bytes per position and piece.
     //   staging item i = r * 512 + tid: position i / 2, channel half i % 2, 16 bytes at i * 16 of each piece; pvoff: its
-    //   global byte offset (past the resource's end outside the image or the batch: loads zero);
+    //   global byte offset (past the resource's end outside the image or the batch: loads zero); pkx: the power-of-two scale
+    //   of the item's own image;
     //   brow: per tap row dy the LDS byte offset of this lane's tap (dy, 0).
     char *const patch = reinterpret_cast<char *>(lds_u4) + kSplitLdsBytes;
     const int PW = TW + KW - 1, PH = TH + KH - 1, npos = TB * PH * PW;
-    int pvoff[kSplitPatchRounds], brow[KH];
+    int pvoff[kSplitPatchRounds], pkx[kSplitPatchRounds], brow[KH];
     if constexpr (PATCH) {
 #pragma unroll
         for (int r = 0; r < kSplitPatchRounds; ++r) {
@@ -648,6 +697,7 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
             const bool inside = i < 2 * npos && img < nimg && gy >= 0 && gy < g.in_h && gx >= 0 && gx < g.in_w;
             pvoff[r] = inside ? static_cast<int>((((static_cast<int64_t>(img) * g.cin + 8 * h) * g.in_h + gy) * g.in_w + gx) * 4)
                               : 0x7FFFFFF0;
+            pkx[r] = inside ? split_act_exp(amax[b0 + img]) : 0;
         }
 #pragma unroll
         for (int dy = 0; dy < KH; ++dy) brow[dy] = ((tb * PH + (lp.my - my0) + dy) * PW + (lp.mx - mx0)) * 32 + 16 * khalf;
@@ -665,18 +715,18 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
 #pragma unroll
         for (int r = 0; r < kSplitPatchRounds; ++r)
             if (r * kSplitThreads + tid < 2 * npos) {
-                u32x4 q[3];
-                split_bf16x3(pf[r], q[0], q[1], q[2]);
+                u32x4 q[2];
+                split_f16x2(pf[r], pkx[r], q[0], q[1]);
 #pragma unroll
-                for (int pc = 0; pc < 3; ++pc)
+                for (int pc = 0; pc < 2; ++pc)
                     *reinterpret_cast<u32x4 *>(patch + (r * kSplitThreads + tid) * 16 + pc * kSplitPieceBytes) = q[pc];
             }
     };
-    // the three pieces of this lane's 8 channels of tap T: one ds_read_b128 each, at immediate offsets from the tap row's base
-    auto read_b = [&](int T, u32x4 (&d)[3]) __attribute__((always_inline)) {
+    // the two pieces of this lane's 8 channels of tap T: one ds_read_b128 each, at immediate offsets from the tap row's base
+    auto read_b = [&](int T, u32x4 (&d)[2]) __attribute__((always_inline)) {
         const char *src = patch + brow[tap_row(T)] + 32 * tap_col(T);
 #pragma unroll
-        for (int pc = 0; pc < 3; ++pc) d[pc] = *reinterpret_cast<const u32x4 *>(src + pc * kSplitPieceBytes);
+        for (int pc = 0; pc < 2; ++pc) d[pc] = *reinterpret_cast<const u32x4 *>(src + pc * kSplitPieceBytes);
     };
 
     f32x16 acc[MT], acc2[MT];  // output columns 2 mx and 2 mx + 1
@@ -689,7 +739,7 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
         }
 
     float xb[8];     // direct source: this tap's activations
-    u32x4 bq[2][3];  // PATCH source: the B pieces of this tap and (read one tap ahead) of the next
+    u32x4 bq[2][2];  // PATCH source: the B pieces of this tap and (read one tap ahead) of the next
     if constexpr (PATCH) fetch_patch(0);
     else load_b(0, 0, xb);
     fetch_w(0, 0);
@@ -710,7 +760,7 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
             for (int tl = 0; tl < kSplitStageTaps; ++tl) {
                 const int T = gi * kSplitStageTaps + tl;
                 float xn[8];
-                u32x4 bd[3];
+                u32x4 bd[2];
                 if constexpr (PATCH) {
                     if (T == 0) read_b(0, bq[0]);  // else read during the previous tap
                 } else {
@@ -720,31 +770,32 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
                     if (T + 1 < kTapsAll) load_b(cb, T + 1, xn);
                     else load_b(cb + 1 < ncb ? cb + 1 : cb, 0, xn);
                     __builtin_amdgcn_sched_barrier(0);
-                    split_bf16x3(xb, bd[0], bd[1], bd[2]);
+                    split_f16x2(xb, kx_l, bd[0], bd[1]);
                 }
-                const u32x4 (&bp)[3] = PATCH ? bq[T & 1] : bd;
+                const u32x4 (&bp)[2] = PATCH ? bq[T & 1] : bd;
                 f32x16 (&dst)[MT] = T < kTapsA ? acc : acc2;  // (compile-time after unrolling)
-                // per M-tile its three A pieces (one ds_read_b128 each, read one tile ahead) and six MFMAs, smallest products
-                // first: (i, j) = (2,0) (1,1) (0,2) (1,0) (0,1) (0,0) -- one dependent chain per tile needs no interleaving
-                u32x4 ap[2][3];
+                // per M-tile its two A pieces (one ds_read_b128 each, read two tiles ahead: three MFMAs alone do not cover an
+                // LDS read) and three MFMAs, smallest products first: a1b0, a0b1, a0b0 -- one dependent chain per tile needs no
+                // interleaving
+                u32x4 ap[3][2];
 #pragma unroll
-                for (int pc = 0; pc < 3; ++pc) ap[0][pc] = wl[(tl * MT * 3 + pc) * 64];
+                for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+                    for (int pc = 0; pc < 2; ++pc) ap[mm][pc] = wl[((tl * MT + mm) * 2 + pc) * 64];
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
-                    const int cur = m & 1;
-                    if (m + 1 < MT) {
+                    const int cur = m % 3;
+                    if (m + 2 < MT) {
 #pragma unroll
-                        for (int pc = 0; pc < 3; ++pc) ap[cur ^ 1][pc] = wl[((tl * MT + m + 1) * 3 + pc) * 64];
-                    } else if constexpr (PATCH) {
-                        if (T + 1 < kTapsAll) read_b(T + 1, bq[(T + 1) & 1]);  // the next tap's B pieces
+                        for (int pc = 0; pc < 2; ++pc) ap[(m + 2) % 3][pc] = wl[((tl * MT + m + 2) * 2 + pc) * 64];
+                    }
+                    if constexpr (PATCH) {
+                        if (m == MT - 3 && T + 1 < kTapsAll) read_b(T + 1, bq[(T + 1) & 1]);  // the next tap's B pieces
                     }
                     __builtin_amdgcn_sched_barrier(0);
-                    dst[m] = mfma_bf16(ap[cur][2], bp[0], dst[m]);
-                    dst[m] = mfma_bf16(ap[cur][1], bp[1], dst[m]);
-                    dst[m] = mfma_bf16(ap[cur][0], bp[2], dst[m]);
-                    dst[m] = mfma_bf16(ap[cur][1], bp[0], dst[m]);
-                    dst[m] = mfma_bf16(ap[cur][0], bp[1], dst[m]);
-                    dst[m] = mfma_bf16(ap[cur][0], bp[0], dst[m]);
+                    dst[m] = mfma_f16(ap[cur][1], bp[0], dst[m]);
+                    dst[m] = mfma_f16(ap[cur][0], bp[1], dst[m]);
+                    dst[m] = mfma_f16(ap[cur][0], bp[0], dst[m]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if constexpr (!PATCH) {
@@ -783,7 +834,19 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
     const int khalf_e = (tid_e >> 5) & 1, col_e = tid_e & 31;
     float *gl = reinterpret_cast<float *>(lds_u4);
     const bool gdn = g.act == BASIC_ACT_GDN || g.act == BASIC_ACT_IGDN;
+    // the power-of-two scale of this lane's image, read again (see kx_l)
+    const int be_s = b0 + pos_of(tid_e).tb;
+    const int kx_e = be_s < g.batch ? split_act_exp(amax[be_s]) : 0;
     auto finish = [&](f32x16 (&acc)[MT]) __attribute__((always_inline)) {
+        // undo the operands' scaling, exactly: by the exponent, not by a float 2^-(kw + kx) that could overflow
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                const i32x4 k4 = *reinterpret_cast<const i32x4 *>(chan_const + 256 + 32 * m + 8 * rq + 4 * khalf_e);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[m][4 * rq + e] = __builtin_ldexpf(acc[m][4 * rq + e], -(k4[e] + kx_e));
+            }
         if (g.bias) {
 #pragma unroll
             for (int m = 0; m < MT; ++m)
@@ -858,14 +921,14 @@ __global__ __launch_bounds__(kSplitThreads, 1) void conv_split_bf16_kernel(const
     }
 }
 
-// One split-bf16 launch: the PATCH source takes all 160 KB of LDS, the direct source the stages and constants only.
+// One split-fp16 launch: the PATCH source takes the patch beside the stages in LDS, the direct source the stages and constants only.
 template <int KH, bool PATCH>
-hipError_t launch_split(const TapLaunch &g, const u32x4 *ws, int blocks, hipStream_t st)
+hipError_t launch_split(const TapLaunch &g, const u32x4 *ws, const int *kw, const unsigned *amax, int blocks, hipStream_t st)
 {
-    const hipError_t e = ensure_max_lds(reinterpret_cast<const void *>(conv_split_bf16_kernel<KH, 3, 2, PATCH>));
+    const hipError_t e = ensure_max_lds(reinterpret_cast<const void *>(conv_split_f16_kernel<KH, 3, 2, PATCH>));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((conv_split_bf16_kernel<KH, 3, 2, PATCH>), dim3(blocks), dim3(kSplitThreads),
-                       PATCH ? kSplitLdsPatchBytes : kSplitLdsBytes, st, g, ws);
+    hipLaunchKernelGGL((conv_split_f16_kernel<KH, 3, 2, PATCH>), dim3(blocks), dim3(kSplitThreads),
+                       PATCH ? kSplitLdsPatchBytes : kSplitLdsBytes, st, g, ws, kw, amax);
     return hipGetLastError();
 }
 
@@ -1428,7 +1491,8 @@ struct Phase {
     float *d_wpack = nullptr;
     float *d_wrow = nullptr;    // see TapLaunch::wrow
     int64_t split_wstride = 0;  // floats per output-channel slice of d_wpack
-    void *d_wsplit = nullptr;   // split-bf16 weights of conv_split_bf16_kernel (see pack_split), or nullptr: fp32 only
+    void *d_wsplit = nullptr;   // split-fp16 weights of conv_split_f16_kernel (see pack_split), or nullptr: fp32 only
+    int *d_wsplit_k = nullptr;  // their power-of-two exponent per output channel [128]
 };
 
 struct Chunk {  // <= 192 output channels handled by one launch family
@@ -1449,6 +1513,8 @@ struct basic_conv_plan {
     float *d_gammaT = nullptr, *d_beta = nullptr;
     float *d_wsm = nullptr, *d_bias4 = nullptr;  // VALU path of the Cout <= 4 synthesis output layer
     int *d_sched = nullptr;                      // tile counter of the persistent first-layer kernel (allocated on first use)
+    unsigned *d_amax = nullptr;                  // split-fp16 path: max |x| per image of the call's input (grown on demand)
+    int amax_cap = 0;
 };
 
 extern "C" void basic_conv_plan_destroy(basic_conv_plan *p)
@@ -1460,14 +1526,17 @@ extern "C" void basic_conv_plan_destroy(basic_conv_plan *p)
                 if (ph.d_wpack) (void)hipFree(ph.d_wpack);
                 if (ph.d_wrow) (void)hipFree(ph.d_wrow);
                 if (ph.d_wsplit) (void)hipFree(ph.d_wsplit);
+                if (ph.d_wsplit_k) (void)hipFree(ph.d_wsplit_k);
             }
             for (auto &ph : ch.fused) {
                 if (ph.d_wpack) (void)hipFree(ph.d_wpack);
                 if (ph.d_wsplit) (void)hipFree(ph.d_wsplit);
+                if (ph.d_wsplit_k) (void)hipFree(ph.d_wsplit_k);
             }
             if (ch.d_bias) (void)hipFree(ch.d_bias);
         }
     if (p->d_sched) (void)hipFree(p->d_sched);
+    if (p->d_amax) (void)hipFree(p->d_amax);
     if (p->d_wsm) (void)hipFree(p->d_wsm);
     if (p->d_bias4) (void)hipFree(p->d_bias4);
     if (p->d_gammaT) (void)hipFree(p->d_gammaT);
@@ -1484,34 +1553,43 @@ int upload(const std::vector<float> &h, float **d)
     return BASIC_OK;
 }
 
-// Split-bf16 weights of conv_split_bf16_kernel from the fp32 pack wp = [cin_pad / ck][ntaps][ck][32][4] of a 4-tile launch:
-// [cin / 16][tap][m-tile][piece][lane][8] bf16, lane = 32 khalf + col holding input channels 16 cb + 8 khalf + j of output
-// channel 32 m + col.  The pieces are the kernel's split_bf16x3 of the weight: w = w0 + w1 + w2, each a bf16 truncation.
-int pack_split(const std::vector<float> &wp, int ck, int ntaps, int cin, void **d)
+// Split-fp16 weights of conv_split_f16_kernel from the fp32 pack wp = [cin_pad / ck][ntaps][ck][32][4] of a 4-tile launch:
+// [cin / 16][tap][m-tile][piece][lane][8] fp16, lane = 32 khalf + col holding input channels 16 cb + 8 khalf + j of output
+// channel 32 m + col, and *d_kw = kw[128]: output channel o is scaled by 2^kw[o] so that its largest |w| 2^kw[o] lies in
+// [2^13, 2^14) (kw = 0 for an all-zero channel).  The pieces are the kernel's split_f16x2 of the scaled weight:
+// w0 = RN16(w 2^kw), w1 = RN16(w 2^kw - w0).
+int pack_split(const std::vector<float> &wp, int ck, int ntaps, int cin, void **d, int **d_kw)
 {
     const int ncb = cin / kSplitCK;
-    std::vector<uint16_t> ws(static_cast<size_t>(ncb) * ntaps * kSplitBlockU4 * 8);
+    auto w_at = [&](int c, int t, int o) { return wp[((static_cast<size_t>(c / ck) * ntaps + t) * ck + c % ck) * 32 * 4 + (o % 32) * 4 + o / 32]; };
+    std::vector<int> kw(128, 0);
+    for (int o = 0; o < 128; ++o) {
+        float m = 0.f;
+        for (int c = 0; c < cin; ++c)
+            for (int t = 0; t < ntaps; ++t) m = std::fmax(m, std::fabs(w_at(c, t, o)));
+        int e = 0;
+        if (m > 0.f && std::isfinite(m)) {
+            (void)std::frexp(m, &e);  // m in [2^(e - 1), 2^e)
+            kw[o] = kSplitWTop - (e - 1);
+        }
+    }
+    std::vector<_Float16> ws(static_cast<size_t>(ncb) * ntaps * kSplitBlockU4 * 8);
     size_t i = 0;
     for (int cb = 0; cb < ncb; ++cb)
         for (int t = 0; t < ntaps; ++t)
             for (int m = 0; m < 4; ++m)
-                for (int pc = 0; pc < 3; ++pc)
+                for (int pc = 0; pc < 2; ++pc)
                     for (int lane = 0; lane < 64; ++lane)
                         for (int j = 0; j < 8; ++j) {
                             const int c = cb * kSplitCK + 8 * (lane >> 5) + j, o = 32 * m + (lane & 31);
-                            float rem = wp[((static_cast<size_t>(c / ck) * ntaps + t) * ck + c % ck) * 32 * 4 + (o % 32) * 4 + o / 32];
-                            uint32_t u = 0;
-                            for (int k = 0; k <= pc; ++k) {
-                                std::memcpy(&u, &rem, 4);
-                                const uint32_t hi = u & 0xFFFF0000u;
-                                float h;
-                                std::memcpy(&h, &hi, 4);
-                                if (k < pc) rem -= h;  // exact
-                            }
-                            ws[i++] = static_cast<uint16_t>(u >> 16);
+                            const float w = std::ldexp(w_at(c, t, o), kw[o]);
+                            const _Float16 w0 = static_cast<_Float16>(w);
+                            ws[i++] = pc ? static_cast<_Float16>(w - static_cast<float>(w0)) : w0;  // the subtraction is exact
                         }
-    BASIC_HIP_TRY(hipMalloc(d, ws.size() * sizeof(uint16_t)));
-    BASIC_HIP_TRY(hipMemcpy(*d, ws.data(), ws.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    BASIC_HIP_TRY(hipMalloc(d, ws.size() * sizeof(_Float16)));
+    BASIC_HIP_TRY(hipMemcpy(*d, ws.data(), ws.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    BASIC_HIP_TRY(hipMalloc(d_kw, kw.size() * sizeof(int)));
+    BASIC_HIP_TRY(hipMemcpy(*d_kw, kw.data(), kw.size() * sizeof(int), hipMemcpyHostToDevice));
     return BASIC_OK;
 }
 
@@ -1671,10 +1749,10 @@ int build_chunks(basic_conv_plan *p, const float *weight, const float *bias, int
                         }
                 wp.resize(wp.size() + kPackTail, 0.f);
                 int rcf = upload(wp, &f.d_wpack);
-                // split-bf16 path: IGDN layers only, i.e. the synthesis transform, whose output is never coded
+                // split-fp16 path: IGDN layers only, i.e. the synthesis transform, whose output is never coded
                 // (the hyper-synthesis layers, whose output sets the coding scales, stay fp32)
                 if (!rcf && !slice && p->act == BASIC_ACT_IGDN && ch.mt == 4 && ch.nsplit == 1 && ci_n % kSplitCK == 0)
-                    rcf = pack_split(wp, kFusedCK, f.ntaps, ci_n, &f.d_wsplit);
+                    rcf = pack_split(wp, kFusedCK, f.ntaps, ci_n, &f.d_wsplit, &f.d_wsplit_k);
                 fused.push_back(f);
                 if (rcf) { ok = false; }
             }
@@ -1682,6 +1760,7 @@ int build_chunks(basic_conv_plan *p, const float *weight, const float *bias, int
             else for (auto &f : fused) {
                 if (f.d_wpack) (void)hipFree(f.d_wpack);
                 if (f.d_wsplit) (void)hipFree(f.d_wsplit);
+                if (f.d_wsplit_k) (void)hipFree(f.d_wsplit_k);
             }
         }
         std::vector<float> hb(static_cast<size_t>(ch.coutp) * ch.nsplit, 0.f);
@@ -1874,20 +1953,20 @@ int pow2_ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 namespace {
 // which launch list forward() walks for this input: 32-channel slices for small position grids, fused column phases when
 // the output rows allow 8-byte pair stores
-struct LaunchChoice { bool use_split, fuse_ok, bf16x3, split_patch; };
+struct LaunchChoice { bool use_split, fuse_ok, split_f16, split_patch; };
 LaunchChoice choose_launches(const basic_conv_plan *p, int batch, int oh, int ow, const void *d_out)
 {
     const int64_t pos_blocks = (static_cast<int64_t>(batch) * ((oh + p->s_out - 1) / p->s_out) * ((ow + p->s_out - 1) / p->s_out) + kTilePos - 1) / kTilePos;
-    // BASIC_CONV_DEBUG path bits (tests): 4 force slices, 8 forbid slices, 512 no fused column phases, 1024 split-bf16
+    // BASIC_CONV_DEBUG path bits (tests): 4 force slices, 8 forbid slices, 512 no fused column phases, 1024 split-fp16
     // activations by direct loads only (no LDS patch)
     const char *dbg_env = getenv("BASIC_CONV_DEBUG");
     const int dbg = dbg_env ? atoi(dbg_env) : 0;
     LaunchChoice c;
     c.use_split = !p->split.empty() && !(dbg & 8) && (pos_blocks < kSplitBelowBlocks || (dbg & 4));
     c.fuse_ok = ow % 2 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0 && !(dbg & 512);
-    // BASIC_CONV_F32=1: the launches that have a split-bf16 variant run the fp32 kernel instead (A/B runs, tests)
+    // BASIC_CONV_F32=1: the launches that have a split-fp16 variant run the fp32 kernel instead (A/B runs, tests)
     const char *f32_env = getenv("BASIC_CONV_F32");
-    c.bf16x3 = !(f32_env && atoi(f32_env) != 0);
+    c.split_f16 =!(f32_env && atoi(f32_env) != 0);
     c.split_patch = !(dbg & 1024);
     return c;
 }
@@ -1960,6 +2039,7 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
     // small position grids: spread the output channels over gridDim.y instead of looping them inside a block;
     // fused column phases: even output width (both phases have the same m-grid) and 8-byte aligned rows for the pair stores
     const LaunchChoice choice = choose_launches(p, batch, oh, ow, d_out);
+    bool amax_done = false;  // split-fp16 path: the per-image maxima of d_in have been queued
     return for_each_launch(p, choice, oh, ow, [&](const Chunk &ch, const Phase &ph, int mh, int mw) -> int {
         TapLaunch g{};
         g.in = d_in; g.out = d_out; g.wpack = ph.d_wpack; g.wrow = ph.d_wrow; g.split_wstride = ph.split_wstride; g.bias = ch.d_bias; g.gammaT = p->d_gammaT; g.beta = p->d_beta;
@@ -1972,8 +2052,8 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
         std::memcpy(g.dx, ph.dx, sizeof(g.dx));
         g.act = p->act;
         const int kCK = ph.ck;
-        if (choice.bf16x3 && ph.d_wsplit) {
-            // split-bf16 path: 256 positions per workgroup, weights through LDS, activations by buffer loads
+        if (choice.split_f16 && ph.d_wsplit) {
+            // split-fp16 path: 256 positions per workgroup, weights through LDS, activations by buffer loads
             const TileShape ts = tile_shape(g.mh, g.mw, kSplitWaves * 32);
             const int tw = ts.tw, th = ts.th, tb = ts.tb;
             if (static_cast<int64_t>(tb) * p->cin * in_h * in_w * 4 < (1ll << 31)) {  // one buffer resource per tile's images
@@ -1983,11 +2063,28 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
                 const int blocks = ((batch + tb - 1) / tb) * g.tiles_y * g.tiles_x;
                 hipStream_t st = as_stream(hip_stream);
                 const u32x4 *ws = static_cast<const u32x4 *>(ph.d_wsplit);
-                BASIC_REQUIRE(ph.kw == 3 && ph.kwb == 2 && (ph.kh == 3 || ph.kh == 2), "conv_forward: split-bf16 plan / kernel instantiation mismatch");
+                BASIC_REQUIRE(ph.kw == 3 && ph.kwb == 2 && (ph.kh == 3 || ph.kh == 2), "conv_forward: split-fp16 plan / kernel instantiation mismatch");
+                // max |x| per image of this call's input, once, before the first row phase that scales by it
+                if (!amax_done) {
+                    auto *pm = const_cast<basic_conv_plan *>(p);  // scratch of the call, not plan state
+                    if (pm->amax_cap < batch) {
+                        if (pm->d_amax) BASIC_HIP_TRY(hipFree(pm->d_amax));
+                        pm->d_amax = nullptr; pm->amax_cap = 0;
+                        BASIC_HIP_TRY(hipMalloc(&pm->d_amax, sizeof(unsigned) * batch));
+                        pm->amax_cap = batch;
+                    }
+                    BASIC_HIP_TRY(hipMemsetAsync(pm->d_amax, 0, sizeof(unsigned) * batch, st));
+                    const int64_t n = static_cast<int64_t>(p->cin) * in_h * in_w;
+                    const int per_img = static_cast<int>(std::min<int64_t>(64, std::max<int64_t>(1, n / 4096)));  // ~16 values per thread, <= 64 workgroups
+                    hipLaunchKernelGGL(image_absmax_kernel, dim3(batch * per_img), dim3(256), 0, st, d_in, n, per_img, pm->d_amax);
+                    BASIC_HIP_TRY(hipGetLastError());
+                    amax_done = true;
+                }
                 // activations from the tile's split patch in LDS where it fits beside the weight stages, else by direct loads
                 const bool patch = choice.split_patch && g.s_in == 1 && tb * (th + ph.kh - 1) * (tw + ph.kw - 1) <= kSplitPatchPos;
-                const hipError_t e = ph.kh == 3 ? (patch ? launch_split<3, true>(g, ws, blocks, st) : launch_split<3, false>(g, ws, blocks, st))
-                                                : (patch ? launch_split<2, true>(g, ws, blocks, st) : launch_split<2, false>(g, ws, blocks, st));
+                const unsigned *am = p->d_amax;
+                const hipError_t e = ph.kh == 3 ? (patch ? launch_split<3, true>(g, ws, ph.d_wsplit_k, am, blocks, st) : launch_split<3, false>(g, ws, ph.d_wsplit_k, am, blocks, st))
+                                                : (patch ? launch_split<2, true>(g, ws, ph.d_wsplit_k, am, blocks, st) : launch_split<2, false>(g, ws, ph.d_wsplit_k, am, blocks, st));
                 BASIC_HIP_TRY(e);
                 return BASIC_OK;
             }

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Stand-alone times of the synthesis transform's split-bf16 layers: g_s layers 1-3 of the hyperprior codec at batch 256
+"""Stand-alone times of the synthesis transform's split-fp16 layers: g_s layers 1-3 of the hyperprior codec at batch 256
 (both fused row-phase launches of each), HIP events around warmed-up repetitions.
 
-Each mode sets the library's switches for the whole layer: `default`, `direct` (BASIC_CONV_DEBUG=1024: split-bf16
+Each mode sets the library's switches for the whole layer: `default`, `direct` (BASIC_CONV_DEBUG=1024: split-fp16
 activations by direct loads, no LDS patch) and `f32` (BASIC_CONV_F32=1: the fp32 kernel).  When `default` and `direct` both
 run, the script prints whether their outputs are equal bit for bit.
 
