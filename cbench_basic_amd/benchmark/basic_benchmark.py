@@ -28,6 +28,11 @@ hands out -- ``codec.decompress(compressed, output_dtype=torch.uint8)``, convert
 independent tiles (``codec.compress_tiled`` / ``decompress_tiled``); ``compressed_length`` is the length of the container and the
 distortion that of the whole pasted picture.  It does not combine with ``testing_coalesce_items``.  ``testing_tile_overlap`` (an int
 or ``(oy, ox)``, at most half a tile; needs ``testing_tile``): the tiles overlap and ``decompress_tiled`` cross-fades the seams.
+
+``testing_tile_pool=N`` (needs ``testing_tile``; INTEGRATION.md, "Tiled pictures"): up to N consecutive batch-1 pictures, of any sizes,
+are coded per call (``codec.compress_tiled_items`` / ``decompress_tiled_items``), the tiles of all of them pooled into shared coding
+calls.  Every item is logged as the unpooled tiled pass logs it -- its own container's length, its own pasted picture's distortion --
+and a call's time is shared equally among its pictures.  It runs on the calling thread: no ``testing_coalesce_items``, no workers.
 """
 import copy
 import csv
@@ -48,7 +53,8 @@ class BasicLosslessCompressionBenchmark:
                  testing_variable_rate_levels=None, testing_variable_rate_bj_delta_metric=None,
                  testing_complexity_levels=None, force_testing_device="cuda", output_dir=None, num_repeats=1,
                  num_testing_workers=0, codec_builder=None, worker_transform_token=None, testing_coalesce_items=0,
-                 metrics_on_uint8=False, on_reconstruction=None, testing_tile=None, testing_tile_overlap=0, **kwargs):
+                 metrics_on_uint8=False, on_reconstruction=None, testing_tile=None, testing_tile_overlap=0, testing_tile_pool=0,
+                 **kwargs):
         self.codec = codec
         self.dataloader = dataloader
         self.distortion_metric = distortion_metric
@@ -102,6 +108,15 @@ class BasicLosslessCompressionBenchmark:
             if 2 * testing_tile_overlap[0] > testing_tile[0] or 2 * testing_tile_overlap[1] > testing_tile[1]:
                 raise ValueError(f"testing_tile_overlap {testing_tile_overlap} is more than half a {testing_tile} tile")
         self.testing_tile_overlap = testing_tile_overlap
+        # pooled tiles: up to this many consecutive pictures per compress_tiled_items / decompress_tiled_items call; 0 / 1 = one each
+        self.testing_tile_pool = int(testing_tile_pool or 0)
+        if self.testing_tile_pool < 0:
+            raise ValueError("testing_tile_pool must be >= 0")
+        if self.testing_tile_pool:
+            if testing_tile is None:
+                raise ValueError("testing_tile_pool needs testing_tile")   # which refuses testing_coalesce_items above 1
+            if self.num_testing_workers > 1:
+                raise ValueError("testing_tile_pool runs on the calling thread: it does not combine with num_testing_workers")
         self._level_prefix = ""
         self._pictures = {}
         self._pool = None
@@ -321,31 +336,76 @@ class BasicLosslessCompressionBenchmark:
                 return
         self._sync()
         t0 = time.time()
-        compressed = codec.compress_items(data, max_batch=n)
+        compressed = self._compress_many(codec, data)
         self._sync()
         time_compress = (time.time() - t0) / n
         if len(compressed) != n:
-            raise ValueError(f"compress_items returned {len(compressed)} strings for {n} items")
+            raise ValueError(f"{len(compressed)} strings were returned for {n} items")
         for i, c, L in zip(chunk, compressed, lengths):
             compressed_length = self._estimate_byte_length(c)
             records[i][0].update(compression_ratio=compressed_length / L, compressed_length=compressed_length,
                                  time_compress=time_compress * 1000, speed_compress=L / time_compress / 1024 / 1024)
         if not self.skip_decompress:
             t0 = time.time()
-            decompressed = codec.decompress_items(compressed, max_batch=n, output_dtype=torch.uint8) if self.metrics_on_uint8 \
-                else codec.decompress_items(compressed, max_batch=n)
+            decompressed = self._decompress_many(codec, compressed)
             self._sync()
             time_decompress = (time.time() - t0) / n
             for i, L in zip(chunk, lengths):
                 records[i][0].update(time_decompress=time_decompress * 1000, speed_decompress=L / time_decompress / 1024 / 1024,
                                      time_total=(time_compress + time_decompress) * 1000,
                                      speed_total=L / (time_compress + time_decompress) / 1024 / 1024)
-            if dm is not None:
+            if dm is not None and self.testing_tile_pool:   # pictures of any sizes: each measured as the tiled pass measures it
+                for i, d, t in zip(chunk, decompressed, targets):
+                    records[i][1].append(dm(d, t, cache_metrics=False))
+            elif dm is not None:
                 for i, r in zip(chunk, dm.per_item(list(decompressed), targets, cache_metrics=False)):
                     records[i][1].append(r)
             if self.on_reconstruction is not None:
                 for i, picture in zip(chunk, decompressed):
                     self._pictures[i] = picture
+
+    def _compress_many(self, codec, data):
+        """The items of a chunk in one call: coalesced items of one shape, or pooled tiles of pictures of any sizes."""
+        if self.testing_tile_pool:
+            return codec.compress_tiled_items(data, tile=self.testing_tile, overlap=self.testing_tile_overlap)
+        return codec.compress_items(data, max_batch=len(data))
+
+    def _decompress_many(self, codec, compressed):
+        if self.testing_tile_pool:
+            return codec.decompress_tiled_items(compressed, output_dtype=torch.uint8 if self.metrics_on_uint8 else None)
+        if self.metrics_on_uint8:
+            return codec.decompress_items(compressed, max_batch=len(compressed), output_dtype=torch.uint8)
+        return codec.decompress_items(compressed, max_batch=len(compressed))
+
+    def _run_dataset_tile_pool(self):
+        """The tiled pass with up to ``testing_tile_pool`` consecutive pictures per call, logged per item in dataset order."""
+        logger = MetricLogger()
+        self._sync()
+        t0 = time.time()
+        items = list(self.dataloader)
+        for d in items:
+            if not isinstance(d, torch.Tensor) or d.dim() != 4 or d.shape[0] != 1:
+                raise ValueError("testing_tile_pool codes a dataset of batch-1 pictures ([1, C, H, W]); got "
+                                 f"{tuple(d.shape) if isinstance(d, torch.Tensor) else type(d).__name__}")
+        if not (hasattr(self.codec, "compress_tiled_items") and hasattr(self.codec, "decompress_tiled_items")):
+            raise ValueError("testing_tile_pool needs a codec with compress_tiled_items / decompress_tiled_items")
+        records = [None] * len(items)
+        for first in range(0, len(items), self.testing_tile_pool):
+            self._run_chunk(list(range(first, min(first + self.testing_tile_pool, len(items)))), items, records)
+        self._sync()
+        wall = time.time() - t0
+        n_bytes = 0
+        for d, (updates, distortions) in zip(items, records):
+            logger.update(**updates)
+            for r in distortions:
+                self.distortion_metric.metric_logger.update(**r)
+            n_bytes += self._estimate_byte_length(d)
+        out = logger.get_global_average()
+        if items:
+            out["time_wall_dataset"] = wall * 1000
+            out["speed_wall_dataset"] = n_bytes / wall / 1024 / 1024
+        self._deliver_pictures()
+        return out
 
     def _run_dataset_coalesced(self):
         from ..utils.item_framing import coalesce_chunks
@@ -399,6 +459,8 @@ class BasicLosslessCompressionBenchmark:
     def _run_dataset(self):
         if self.testing_coalesce_items > 1:
             return self._run_dataset_coalesced()
+        if self.testing_tile_pool > 1:
+            return self._run_dataset_tile_pool()
         logger = MetricLogger()
         n_items, n_bytes = 0, 0
         self._sync()

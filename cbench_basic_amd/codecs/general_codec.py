@@ -53,6 +53,18 @@ class GeneralCodec(HotPathModule, CodecInterface, VariableRateCodecInterface, Va
         with self.profiler.start_time_profile("time_decompress_entropy_coder"):
             return self.entropy_coder.decode_tiled(data, *args, **kwargs)
 
+    def compress_tiled_items(self, pictures, *args, tile=(512, 512), overlap=0, max_batch=None, **kwargs):
+        """N pictures ``[1, C, H, W]`` of any sizes -> their N containers, exactly ``[self.compress_tiled(p, tile=, overlap=) for p in
+        pictures]``, the tiles of all pictures pooled into shared coding calls (entropy coder's ``encode_tiled_items``)."""
+        with self.profiler.start_time_profile("time_compress_entropy_coder"):
+            return self.entropy_coder.encode_tiled_items(pictures, *args, tile=tile, overlap=overlap, max_batch=max_batch, **kwargs)
+
+    def decompress_tiled_items(self, containers, *args, **kwargs):
+        """N containers -> their N pictures, each equal to ``self.decompress_tiled(container)`` (entropy coder's
+        ``decode_tiled_items``)."""
+        with self.profiler.start_time_profile("time_decompress_entropy_coder"):
+            return self.entropy_coder.decode_tiled_items(containers, *args, **kwargs)
+
     @property
     def last_items_calls(self):
         return self.entropy_coder.last_items_calls

@@ -99,6 +99,12 @@ class GroupedVariableRateCodec(HotPathModule, CodecInterface, VariableRateCodecI
     def decompress_tiled(self, data, *args, **kwargs):
         return self.active_codec.decompress_tiled(data, *args, **kwargs)
 
+    def compress_tiled_items(self, pictures, *args, **kwargs):
+        return self.active_codec.compress_tiled_items(pictures, *args, **kwargs)
+
+    def decompress_tiled_items(self, containers, *args, **kwargs):
+        return self.active_codec.decompress_tiled_items(containers, *args, **kwargs)
+
     @property
     def last_items_calls(self):
         return self.active_codec.last_items_calls

@@ -14,7 +14,8 @@
 // one multiply / v_rndne; nothing is contracted into it.
 // The third entry measures such pictures: the exact per-channel sum of squared differences of two uint8 batches (further down).
 // The last entries cut float tiles out of one uint8 picture, paste reconstructed tiles back into one and, for overlapped tiles, write
-// the picture from all their reconstructions with the seams cross-faded (section 8c, at the end).
+// the picture from all their reconstructions with the seams cross-faded (section 8c); the cut and the paste again for tiles of MANY
+// pictures, a table row per tile (section 8d, at the end).
 #include <utility>
 
 #include "common.h"
@@ -441,37 +442,49 @@ __device__ __forceinline__ void locate_run(const TileGroup &g, int64_t r, int64_
     *f32 = ((tile * g.channels + c) * g.fh + row) * g.fw + 4 * q;
 }
 
+// run r of a group, cut and pasted.  Shared by the kernels of one picture here and those of a table of tiles (section 8d).
+template <int C>
+__device__ __forceinline__ void cut_run(const uint32_t *__restrict__ img, float4 *__restrict__ dst, const TileGroup &g, int64_t r,
+                                        const float *lut)
+{
+    const int64_t plane4 = g.fh * g.fw / 4;
+    int64_t u, f;
+    locate_run<C>(g, r, &u, &f);
+    const Words<C> in = *reinterpret_cast<const Words<C> *>(img + u / 4);
+#pragma unroll
+    for (int c = 0; c < C; ++c) dst[f / 4 + c * plane4] = run_to_f32<C>(in, c, lut);
+}
+
+template <int C>
+__device__ __forceinline__ void paste_run(const float4 *__restrict__ src, uint32_t *__restrict__ img, const TileGroup &g, int64_t r)
+{
+    const int64_t plane4 = g.fh * g.fw / 4;
+    int64_t u, f;
+    locate_run<C>(g, r, &u, &f);
+    Words<C> out;
+#pragma unroll
+    for (int k = 0; k < C; ++k) out.w[k] = 0u;
+#pragma unroll
+    for (int c = 0; c < C; ++c) run_from_f32<C>(out, c, src[f / 4 + c * plane4]);
+    *reinterpret_cast<Words<C> *>(img + u / 4) = out;
+}
+
 template <int C>
 __global__ __launch_bounds__(kBlock) void tiles_u8_to_f32_wide_kernel(const uint32_t *__restrict__ img, float4 *__restrict__ dst,
                                                                        TileGroup g, int64_t runs)
 {
     __shared__ float lut[256];
     load_table(lut);
-    const int64_t plane4 = g.fh * g.fw / 4;
-    for (int64_t r = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; r < runs; r += static_cast<int64_t>(gridDim.x) * kBlock) {
-        int64_t u, f;
-        locate_run<C>(g, r, &u, &f);
-        const Words<C> in = *reinterpret_cast<const Words<C> *>(img + u / 4);
-#pragma unroll
-        for (int c = 0; c < C; ++c) dst[f / 4 + c * plane4] = run_to_f32<C>(in, c, lut);
-    }
+    for (int64_t r = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; r < runs; r += static_cast<int64_t>(gridDim.x) * kBlock)
+        cut_run<C>(img, dst, g, r, lut);
 }
 
 template <int C>
 __global__ __launch_bounds__(kBlock) void tiles_f32_to_u8_wide_kernel(const float4 *__restrict__ src, uint32_t *__restrict__ img,
                                                                        TileGroup g, int64_t runs)
 {
-    const int64_t plane4 = g.fh * g.fw / 4;
-    for (int64_t r = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; r < runs; r += static_cast<int64_t>(gridDim.x) * kBlock) {
-        int64_t u, f;
-        locate_run<C>(g, r, &u, &f);
-        Words<C> out;
-#pragma unroll
-        for (int k = 0; k < C; ++k) out.w[k] = 0u;
-#pragma unroll
-        for (int c = 0; c < C; ++c) run_from_f32<C>(out, c, src[f / 4 + c * plane4]);
-        *reinterpret_cast<Words<C> *>(img + u / 4) = out;
-    }
+    for (int64_t r = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; r < runs; r += static_cast<int64_t>(gridDim.x) * kBlock)
+        paste_run<C>(src, img, g, r);
 }
 
 // sample (tile, c, row, col) of a group -> its offsets on the two sides
@@ -483,44 +496,55 @@ __device__ __forceinline__ void locate_sample(const TileGroup &g, int hwc, int64
     *f32 = ((tile * g.channels + c) * g.fh + row) * g.fw + col;
 }
 
-// walks the float side, [tile][c][row][col] (fh x fw = th x tw here)
+// sample i of the float side, [tile][c][row][col] (fh x fw = th x tw here), cut
+__device__ __forceinline__ void cut_sample(const uint8_t *__restrict__ img, float *__restrict__ dst, int hwc, const TileGroup &g, int64_t i,
+                                           const float *lut)
+{
+    const int64_t col = i % g.tw, job = i / g.tw;
+    const int64_t row = job % g.th, t = job / g.th;
+    int64_t u, f;
+    locate_sample(g, hwc, t / g.channels, t % g.channels, row, col, &u, &f);
+    dst[f] = lut[img[u]];
+}
+
+// sample j of the uint8 side of the tiles ([tile][c][row][col], hwc: [tile][row][col][c]), pasted
+__device__ __forceinline__ void paste_sample(const float *__restrict__ src, uint8_t *__restrict__ img, int hwc, const TileGroup &g, int64_t j)
+{
+    int64_t tile, c, row, col;
+    if (hwc) {
+        c = j % g.channels;
+        const int64_t t = j / g.channels;
+        col = t % g.tw;
+        row = t / g.tw % g.th;
+        tile = t / g.tw / g.th;
+    } else {
+        col = j % g.tw;
+        const int64_t job = j / g.tw, t = job / g.th;
+        row = job % g.th;
+        c = t % g.channels;
+        tile = t / g.channels;
+    }
+    int64_t u, f;
+    locate_sample(g, hwc, tile, c, row, col, &u, &f);
+    img[u] = static_cast<uint8_t>(quantise(src[f]));
+}
+
+// walks the float side
 __global__ __launch_bounds__(kBlock) void tiles_u8_to_f32_scalar_kernel(const uint8_t *__restrict__ img, float *__restrict__ dst, int hwc,
                                                                          TileGroup g, int64_t total)
 {
     __shared__ float lut[256];
     load_table(lut);
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * kBlock) {
-        const int64_t col = i % g.tw, job = i / g.tw;
-        const int64_t row = job % g.th, t = job / g.th;
-        int64_t u, f;
-        locate_sample(g, hwc, t / g.channels, t % g.channels, row, col, &u, &f);
-        dst[f] = lut[img[u]];
-    }
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * kBlock)
+        cut_sample(img, dst, hwc, g, i, lut);
 }
 
-// walks the uint8 side of the tiles ([tile][c][row][col], hwc: [tile][row][col][c]), so that a wavefront's byte stores are consecutive
+// walks the uint8 side of the tiles, so that a wavefront's byte stores are consecutive
 __global__ __launch_bounds__(kBlock) void tiles_f32_to_u8_scalar_kernel(const float *__restrict__ src, uint8_t *__restrict__ img, int hwc,
                                                                          TileGroup g, int64_t total)
 {
-    for (int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; j < total; j += static_cast<int64_t>(gridDim.x) * kBlock) {
-        int64_t tile, c, row, col;
-        if (hwc) {
-            c = j % g.channels;
-            const int64_t t = j / g.channels;
-            col = t % g.tw;
-            row = t / g.tw % g.th;
-            tile = t / g.tw / g.th;
-        } else {
-            col = j % g.tw;
-            const int64_t job = j / g.tw, t = job / g.th;
-            row = job % g.th;
-            c = t % g.channels;
-            tile = t / g.channels;
-        }
-        int64_t u, f;
-        locate_sample(g, hwc, tile, c, row, col, &u, &f);
-        img[u] = static_cast<uint8_t>(quantise(src[f]));
-    }
+    for (int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; j < total; j += static_cast<int64_t>(gridDim.x) * kBlock)
+        paste_sample(src, img, hwc, g, j);
 }
 
 struct TilePlan {
@@ -849,6 +873,197 @@ extern "C" int basic_image_tiles_blend_dev(const basic_tile_source *d_table, int
     if (u8) launch_blend<true>(wide_c, d_table, d_out, hwc, g, total, st);
     else launch_blend<false>(wide_c, d_table, d_out, hwc, g, total, st);
     g_tiles_last_path = wide_c ? 1 : 0;
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+// ---- tiles of many pictures (include/basic_hip.h section 8d) ---------------------------------------------------------------
+// The cut and the paste above with a table row per tile in place of the grid arithmetic: tile t of the float batch belongs to the
+// picture, origin and layout of row t.  blockIdx.y strides the tiles, the workgroups of one blockIdx.y share a tile; a workgroup
+// reads its tile's row ONCE, into LDS, and turns it into a TileGroup of one tile, which the run and sample helpers above then
+// walk: the values and the access shapes are theirs.  The layout is per row, so a wide launch of C = 3, 4 takes, tile by tile
+// (uniformly in a workgroup), the interleaved runs or the planar ones.
+namespace {
+
+struct PoolShape {
+    int64_t channels, th, tw, fh, fw;   // a tile, and its plane on the float side
+};
+
+__device__ __forceinline__ TileGroup pool_group(const basic_tile_ref *__restrict__ table, int64_t t, basic_tile_ref *slot, const PoolShape &s)
+{
+    __syncthreads();   // the readers of the previous row
+    if (threadIdx.x == 0) *slot = table[t];
+    __syncthreads();
+    TileGroup g;
+    g.img_h = slot->img_h, g.img_w = slot->img_w;
+    g.y0 = slot->y0, g.x0 = slot->x0, g.step_y = s.th, g.step_x = s.tw, g.nx = 1;
+    g.th = s.th, g.tw = s.tw, g.fh = s.fh, g.fw = s.fw;
+    g.channels = s.channels;
+    return g;
+}
+
+// HC: the channels of the rows whose picture is interleaved (3, 4), or 1: every row is planar
+template <int HC>
+__global__ __launch_bounds__(kBlock) void pool_u8_to_f32_wide_kernel(const basic_tile_ref *__restrict__ table, float4 *__restrict__ dst,
+                                                                      PoolShape s, int64_t n)
+{
+    __shared__ float lut[256];
+    __shared__ basic_tile_ref slot;
+    load_table(lut);
+    const int64_t lane = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x, lanes = static_cast<int64_t>(gridDim.x) * kBlock;
+    const int64_t tile4 = s.channels * s.fh * s.fw / 4;
+    for (int64_t t = blockIdx.y; t < n; t += gridDim.y) {
+        const TileGroup g = pool_group(table, t, &slot, s);
+        const uint32_t *img = static_cast<const uint32_t *>(slot.img);
+        if (HC > 1 && slot.layout == BASIC_IMAGE_HWC) {
+            for (int64_t r = lane; r < s.th * s.tw / 4; r += lanes) cut_run<HC>(img, dst + t * tile4, g, r, lut);
+        } else {
+            for (int64_t r = lane; r < s.channels * s.th * s.tw / 4; r += lanes) cut_run<1>(img, dst + t * tile4, g, r, lut);
+        }
+    }
+}
+
+template <int HC>
+__global__ __launch_bounds__(kBlock) void pool_f32_to_u8_wide_kernel(const float4 *__restrict__ src, const basic_tile_ref *__restrict__ table,
+                                                                      PoolShape s, int64_t n)
+{
+    __shared__ basic_tile_ref slot;
+    const int64_t lane = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x, lanes = static_cast<int64_t>(gridDim.x) * kBlock;
+    const int64_t tile4 = s.channels * s.fh * s.fw / 4;
+    for (int64_t t = blockIdx.y; t < n; t += gridDim.y) {
+        const TileGroup g = pool_group(table, t, &slot, s);
+        uint32_t *img = static_cast<uint32_t *>(slot.img);
+        if (HC > 1 && slot.layout == BASIC_IMAGE_HWC) {
+            for (int64_t r = lane; r < s.th * s.tw / 4; r += lanes) paste_run<HC>(src + t * tile4, img, g, r);
+        } else {
+            for (int64_t r = lane; r < s.channels * s.th * s.tw / 4; r += lanes) paste_run<1>(src + t * tile4, img, g, r);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void pool_u8_to_f32_scalar_kernel(const basic_tile_ref *__restrict__ table, float *__restrict__ dst,
+                                                                        PoolShape s, int64_t n)
+{
+    __shared__ float lut[256];
+    __shared__ basic_tile_ref slot;
+    load_table(lut);
+    const int64_t lane = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x, lanes = static_cast<int64_t>(gridDim.x) * kBlock;
+    const int64_t tile = s.channels * s.fh * s.fw;
+    for (int64_t t = blockIdx.y; t < n; t += gridDim.y) {
+        const TileGroup g = pool_group(table, t, &slot, s);
+        const int hwc = slot.layout == BASIC_IMAGE_HWC && s.channels > 1;
+        for (int64_t i = lane; i < s.channels * s.th * s.tw; i += lanes)
+            cut_sample(static_cast<const uint8_t *>(slot.img), dst + t * tile, hwc, g, i, lut);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void pool_f32_to_u8_scalar_kernel(const float *__restrict__ src, const basic_tile_ref *__restrict__ table,
+                                                                        PoolShape s, int64_t n)
+{
+    __shared__ basic_tile_ref slot;
+    const int64_t lane = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x, lanes = static_cast<int64_t>(gridDim.x) * kBlock;
+    const int64_t tile = s.channels * s.fh * s.fw;
+    for (int64_t t = blockIdx.y; t < n; t += gridDim.y) {
+        const TileGroup g = pool_group(table, t, &slot, s);
+        const int hwc = slot.layout == BASIC_IMAGE_HWC && s.channels > 1;
+        for (int64_t j = lane; j < s.channels * s.th * s.tw; j += lanes)
+            paste_sample(src + t * tile, static_cast<uint8_t *>(slot.img), hwc, g, j);
+    }
+}
+
+struct PoolPlan {
+    PoolShape s;
+    int wide_c;   // 0: sample by sample; 1: wide, every row planar; 3, 4: wide, interleaved rows of that many channels among them
+    dim3 grid;
+};
+
+// every check of both entries, on the HOST table: nothing has been copied or launched when this fails.  fh x fw is the float
+// side's plane (th x tw for the gather).
+int plan_pool(const basic_tile_ref *table, int n, int channels, int th, int tw, int fh, int fw, const void *d_table_ws, const void *d_f32,
+              const char *what, PoolPlan *p)
+{
+    const std::string who(what);
+    BASIC_REQUIRE(table && d_table_ws && d_f32, who + ": null pointer");
+    BASIC_REQUIRE(n >= 1, who + ": n must be positive");
+    BASIC_REQUIRE(channels >= 1 && th >= 1 && tw >= 1 && fh >= 1 && fw >= 1, who + ": channels and the tile sizes must be positive");
+    BASIC_REQUIRE(fh >= th && fw >= tw, who + ": the source tiles are smaller than th x tw");
+    BASIC_REQUIRE(reinterpret_cast<uintptr_t>(d_f32) % sizeof(float) == 0, who + ": the float32 pointer is not float-aligned");
+    BASIC_REQUIRE(reinterpret_cast<uintptr_t>(d_table_ws) % alignof(basic_tile_ref) == 0, who + ": the table workspace is not 8-byte aligned");
+    const int64_t plane = static_cast<int64_t>(fh) * fw;
+    BASIC_REQUIRE(static_cast<int64_t>(n) * channels <= kMaxSamples / plane, who + ": more than 2^40 samples");
+    bool aligned = reinterpret_cast<uintptr_t>(d_f32) % 16 == 0 && tw % 4 == 0 && fw % 4 == 0;
+    bool any_hwc = false;
+    for (int t = 0; t < n; ++t) {
+        const basic_tile_ref &e = table[t];
+        const std::string row = who + ": row " + std::to_string(t);
+        BASIC_REQUIRE(e.img, row + ": null picture");
+        BASIC_REQUIRE(e.layout == BASIC_IMAGE_CHW || e.layout == BASIC_IMAGE_HWC, row + ": layout is BASIC_IMAGE_CHW or BASIC_IMAGE_HWC");
+        BASIC_REQUIRE(e.img_h >= 1 && e.img_w >= 1, row + ": the picture's size must be positive");
+        BASIC_REQUIRE(e.y0 >= 0 && e.x0 >= 0, row + ": y0 and x0 must not be negative");
+        BASIC_REQUIRE(static_cast<int64_t>(e.y0) + th <= e.img_h && static_cast<int64_t>(e.x0) + tw <= e.img_w, row + ": the tile leaves the picture");
+        BASIC_REQUIRE(static_cast<int64_t>(e.img_h) * e.img_w <= (int64_t(1) << 60) / channels, row + ": the picture is too large");
+        const bool hwc = e.layout == BASIC_IMAGE_HWC && channels > 1;   // one channel: the two layouts coincide
+        any_hwc = any_hwc || hwc;
+        aligned = aligned && reinterpret_cast<uintptr_t>(e.img) % 4 == 0 && e.img_w % 4 == 0 && e.x0 % 4 == 0 &&
+                  (!hwc || channels == 3 || channels == 4);
+    }
+    p->s.channels = channels, p->s.th = th, p->s.tw = tw, p->s.fh = fh, p->s.fw = fw;
+    p->wide_c = !aligned ? 0 : any_hwc ? channels : 1;
+    const int64_t tile = static_cast<int64_t>(channels) * th * tw;   // a planar row's lanes: no fewer than an interleaved row's
+    p->grid = sse_grid(p->wide_c ? tile / 4 : tile, n);              // (workgroups that share a tile, tiles side by side)
+    return BASIC_OK;
+}
+
+// the table to the caller's workspace, on the stream; returns when the host table may be written again
+int stage_pool_table(const basic_tile_ref *table, int n, basic_tile_ref *d_table_ws, hipStream_t st)
+{
+    BASIC_HIP_TRY(hipMemcpyAsync(d_table_ws, table, static_cast<size_t>(n) * sizeof(basic_tile_ref), hipMemcpyHostToDevice, st));
+    BASIC_HIP_TRY(hipStreamSynchronize(st));   // pageable memory: the copy has read it
+    return BASIC_OK;
+}
+
+}  // namespace
+
+extern "C" int basic_image_tiles_gather_u8_to_f32_dev(const basic_tile_ref *table, int n, int channels, int th, int tw,
+                                                      basic_tile_ref *d_table_ws, float *d_dst, void *hip_stream)
+{
+    PoolPlan p;
+    int rc = plan_pool(table, n, channels, th, tw, th, tw, d_table_ws, d_dst, "image_tiles_gather_u8_to_f32", &p);
+    if (rc) return rc;
+    rc = require_device();
+    if (rc) return rc;
+    hipStream_t st = as_stream(hip_stream);
+    rc = stage_pool_table(table, n, d_table_ws, st);
+    if (rc) return rc;
+    float4 *dst4 = reinterpret_cast<float4 *>(d_dst);
+    const int64_t n64 = n;
+    if (p.wide_c == 1) hipLaunchKernelGGL(pool_u8_to_f32_wide_kernel<1>, p.grid, dim3(kBlock), 0, st, d_table_ws, dst4, p.s, n64);
+    else if (p.wide_c == 3) hipLaunchKernelGGL(pool_u8_to_f32_wide_kernel<3>, p.grid, dim3(kBlock), 0, st, d_table_ws, dst4, p.s, n64);
+    else if (p.wide_c == 4) hipLaunchKernelGGL(pool_u8_to_f32_wide_kernel<4>, p.grid, dim3(kBlock), 0, st, d_table_ws, dst4, p.s, n64);
+    else hipLaunchKernelGGL(pool_u8_to_f32_scalar_kernel, p.grid, dim3(kBlock), 0, st, d_table_ws, d_dst, p.s, n64);
+    g_tiles_last_path = p.wide_c ? 1 : 0;
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_image_tiles_scatter_f32_to_u8_dev(const float *d_src, int sh, int sw, int channels, int th, int tw,
+                                                       const basic_tile_ref *table, int n, basic_tile_ref *d_table_ws, void *hip_stream)
+{
+    PoolPlan p;
+    int rc = plan_pool(table, n, channels, th, tw, sh, sw, d_table_ws, d_src, "image_tiles_scatter_f32_to_u8", &p);
+    if (rc) return rc;
+    rc = require_device();
+    if (rc) return rc;
+    hipStream_t st = as_stream(hip_stream);
+    rc = stage_pool_table(table, n, d_table_ws, st);
+    if (rc) return rc;
+    const float4 *src4 = reinterpret_cast<const float4 *>(d_src);
+    const int64_t n64 = n;
+    if (p.wide_c == 1) hipLaunchKernelGGL(pool_f32_to_u8_wide_kernel<1>, p.grid, dim3(kBlock), 0, st, src4, d_table_ws, p.s, n64);
+    else if (p.wide_c == 3) hipLaunchKernelGGL(pool_f32_to_u8_wide_kernel<3>, p.grid, dim3(kBlock), 0, st, src4, d_table_ws, p.s, n64);
+    else if (p.wide_c == 4) hipLaunchKernelGGL(pool_f32_to_u8_wide_kernel<4>, p.grid, dim3(kBlock), 0, st, src4, d_table_ws, p.s, n64);
+    else hipLaunchKernelGGL(pool_f32_to_u8_scalar_kernel, p.grid, dim3(kBlock), 0, st, d_src, d_table_ws, p.s, n64);
+    g_tiles_last_path = p.wide_c ? 1 : 0;
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
 }

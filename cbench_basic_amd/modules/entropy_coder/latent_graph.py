@@ -731,6 +731,146 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             return canvas
         return canvas[:, :, ry0 - cy0:ry1 - cy0, rx0 - cx0:rx1 - cx0]
 
+    # ---- pooled tiles: the tiles of MANY pictures, of any sizes, share coding calls; every container keeps its own bytes
+    def encode_tiled_items(self, pictures, *args, tile=(512, 512), overlap=0, max_batch=None, **kwargs) -> List[bytes]:
+        """N pictures ``[1, C, H, W]`` of ANY sizes with one C (uint8 in chw or hwc memory, or float32; host or device; mixed within a
+        call) -> their N containers, container k byte for byte ``self.encode_tiled(pictures[k], tile=tile, overlap=overlap)``.  The
+        tiles of all pictures are pooled by size (utils.tiling.pool_tiles: the full tiles of every picture share one shape, the edge
+        tiles a few more), a chunk of at most ``max_batch`` tiles is cut out of its uint8 pictures by ONE launch
+        (nn.kernels.image_tiles_gather; float32 pictures: one copy per tile, and chunks of their own) and coded by one encode() call,
+        whose string is split as in encode_items.  ``last_items_calls`` counts the encode() calls.  One encode_tiled per picture when
+        a coder cannot split, in training mode, or when the call brings arguments."""
+        from ...nn import kernels as K
+        from ...utils import tiling
+        pictures = list(pictures)
+        for x in pictures:
+            self._check_item(x)
+            if x.dtype not in (torch.uint8, torch.float32):
+                raise TypeError(f"a picture is torch.uint8 or torch.float32, not {x.dtype}")
+        if len({x.shape[1] for x in pictures}) > 1:
+            raise ValueError("the pictures of one call share their channel count")
+        th, tw = self._tile_size(tile)
+        grids = [tiling.TileGrid(x.shape[2], x.shape[3], th, tw, overlap=overlap) for x in pictures]
+        framing = self._items_framing() if not (args or kwargs or self.training) else None
+        if framing is None:
+            out, calls = [], 0
+            for x in pictures:
+                out.append(self.encode_tiled(x, *args, tile=tile, max_batch=max_batch, overlap=overlap, **kwargs))
+                calls += self.last_items_calls
+            self.last_items_calls = calls
+            return out
+        self.last_items_calls = 0
+        pictures = [x if x.device == self.device else x.to(device=self.device) for x in pictures]   # each once, as it lies
+        strings = [[None] * len(g) for g in grids]
+        with torch.no_grad(), torch.cuda.device(self.device):
+            for dtype in (torch.uint8, torch.float32):
+                own = [p for p, x in enumerate(pictures) if x.dtype == dtype]
+                for chunk in tiling.pool_tiles([grids[p] for p in own], max_batch):
+                    refs = [t._replace(picture=own[t.picture]) for t in chunk.tiles]
+                    self.last_items_calls += 1
+                    if len(refs) == 1:
+                        p, k, y, x = refs[0]
+                        strings[p][k] = self.encode(pictures[p][:, :, y:y + chunk.h, x:x + chunk.w])
+                        continue
+                    if dtype == torch.uint8:
+                        batch = K.image_tiles_gather(pictures, refs, chunk.h, chunk.w)
+                    else:
+                        batch = torch.empty((len(refs), pictures[own[0]].shape[1], chunk.h, chunk.w), dtype=dtype, device=self.device)
+                        for j, (p, _, y, x) in enumerate(refs):
+                            batch[j].copy_(pictures[p][0, :, y:y + chunk.h, x:x + chunk.w])
+                    for (p, k, _, _), one in zip(refs, self._split_string(self.encode(batch), len(refs), framing)):
+                        strings[p][k] = one
+        return [tiling.pack_tiled(x.shape[1], g.H, g.W, g.th, g.tw, s, overlap=g.overlap) for x, g, s in zip(pictures, grids, strings)]
+
+    def decode_tiled_items(self, containers, *args, output_dtype=torch.uint8, layout="chw", max_batch=None, **kwargs) -> List[torch.Tensor]:
+        """N containers of encode_tiled / encode_tiled_items, of any picture and tile sizes and overlaps (read from each) -> their N
+        pictures, picture k equal to ``self.decode_tiled(containers[k], output_dtype=output_dtype, layout=layout)``.  Tiles of one size
+        whose strings' own headers agree (as decode_items keys them) share a decode() call of at most ``max_batch`` tiles, in the
+        order of utils.tiling.pool_tiles; ``last_items_calls`` counts the calls.  uint8 results are converted, cropped and pasted by
+        ONE launch per call whatever pictures its tiles belong to (nn.kernels.image_tiles_scatter); float32 results by one copy per
+        tile.  Overlapped containers: a picture is written by the blend launch of decode_tiled (nn.kernels.image_tiles_blend, one per
+        picture) as soon as the last of its tiles is decoded, from views of the pooled batches.  Until then the batches that hold
+        its tiles stay resident, and a batch is freed only when every overlapped picture with a tile in it is written: at worst
+        4 * C * sh * sw bytes per tile of ALL overlapped pictures of the call, on top of the results.  One decode_tiled per
+        container when a coder cannot split, in training mode, or when the call brings arguments.  No ``region=``: decoding a part
+        of a picture stays decode_tiled's."""
+        from ...nn import kernels as K
+        from ...utils import tiling
+        if "region" in kwargs:
+            raise TypeError("decode_tiled_items takes no region: decode a part of a picture with decode_tiled")
+        if output_dtype not in (None, torch.float32, torch.uint8):
+            raise TypeError(f"output_dtype is torch.float32 or torch.uint8, not {output_dtype}")
+        if layout not in K.IMAGE_LAYOUTS:
+            raise ValueError(f"layout is 'chw' or 'hwc', not {layout!r}")
+        containers = list(containers)
+        framing = self._items_framing() if not (args or kwargs or self.training) else None
+        if framing is None:
+            out, calls = [], 0
+            for data in containers:
+                out.append(self.decode_tiled(data, *args, output_dtype=output_dtype, layout=layout, max_batch=max_batch, **kwargs))
+                calls += self.last_items_calls
+            self.last_items_calls = calls
+            return out
+        heads = [tiling.unpack_tiled_any(data) for data in containers]
+        grids = [tiling.TileGrid(H, W, th, tw, overlap) for _, H, W, th, tw, overlap, _ in heads]
+        strings = [head[6] for head in heads]
+        blend = [g.overlap != (0, 0) for g in grids]
+        # the planner's chunks of one size each, refined by what the strings say about themselves, then cut at max_batch
+        chunks = []
+        for size in tiling.pool_tiles(grids, None):
+            by_key = {}
+            for t in size.tiles:
+                segs = split_merged_bytes(strings[t.picture][t.index], num_segments=len(framing))
+                key = (heads[t.picture][0],) + tuple(c.item_shape(seg, **ctx) if hasattr(c, "item_shape") else None
+                                                     for (c, ctx), seg in zip(framing, segs))
+                by_key.setdefault(key, []).append(t)
+            for tiles in by_key.values():
+                step = max_batch or len(tiles)
+                chunks.extend((size.h, size.w, tiles[i:i + step]) for i in range(0, len(tiles), step))
+        as_u8 = output_dtype == torch.uint8
+        dtype = torch.uint8 if as_u8 else torch.float32
+        self.last_items_calls = self.last_tiles_decoded = 0
+        with torch.no_grad(), torch.cuda.device(self.device):
+            canvases = []
+            for (C, H, W, *_rest) in heads:
+                if layout == "hwc":
+                    canvases.append(torch.empty((1, H, W, C), dtype=dtype, device=self.device).permute(0, 3, 1, 2))
+                else:
+                    canvases.append(torch.empty((1, C, H, W), dtype=dtype, device=self.device))
+            waiting = [len(g) if b else 0 for g, b in zip(grids, blend)]   # tiles an overlapped picture still lacks
+            held = [[] for _ in grids]                                    # its (batch view, tile indices) so far
+            for h, w, tiles in chunks:
+                self.last_items_calls += 1
+                self.last_tiles_decoded += len(tiles)
+                if len(tiles) == 1:
+                    rec = self.decode(strings[tiles[0].picture][tiles[0].index])
+                else:
+                    rec = self.decode(self._merge_strings([strings[t.picture][t.index] for t in tiles], framing))
+                C = heads[tiles[0].picture][0]
+                if rec.dim() != 4 or rec.shape[0] != len(tiles) or rec.shape[1] != C or rec.shape[2] < h or rec.shape[3] < w:
+                    raise ValueError(f"tiles of [{len(tiles)}, {C}, {h}, {w}] decoded to {tuple(rec.shape)}")
+                plain = [j for j, t in enumerate(tiles) if not blend[t.picture]]
+                if plain and as_u8:
+                    part = rec if len(plain) == len(tiles) else rec[torch.tensor(plain, device=rec.device)]
+                    K.image_tiles_scatter(part, canvases, [tiles[j] for j in plain], h, w)
+                elif plain:
+                    for j in plain:
+                        p, _, y, x = tiles[j]
+                        canvases[p][0, :, y:y + h, x:x + w].copy_(rec[j, :, :h, :w])
+                j = 0
+                while j < len(tiles):   # picture-major: an overlapped picture's tiles of this chunk are one slice of the batch
+                    p, e = tiles[j].picture, j + 1
+                    while e < len(tiles) and tiles[e].picture == p:
+                        e += 1
+                    if blend[p]:
+                        held[p].append((rec[j:e], [t.index for t in tiles[j:e]]))
+                        waiting[p] -= e - j
+                        if waiting[p] == 0:
+                            K.image_tiles_blend(held[p], grids[p], canvases[p])
+                            held[p] = []
+                    j = e
+        return canvases
+
     def forward(self, data, *args, **kwargs):
         """Eval-mode forward: quantised reconstruction without entropy coding (latent_graph.py:870-1230
         minus the training losses)."""

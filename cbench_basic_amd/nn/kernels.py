@@ -695,6 +695,77 @@ def image_tiles_blend(sources, grid, out, region=None):
     return out
 
 
+_TILE_REF = np.dtype([("img", "<u8"), ("img_h", "<i4"), ("img_w", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("layout", "<i4"), ("pad", "<i4")])   # basic_tile_ref
+
+
+def _tile_ref_table(pictures, refs, device):
+    """The host table of ``refs`` -- ``(picture, tile index, y0, x0)`` rows, utils.tiling.PooledTile -- over ``pictures``, ``{index: (tensor as the
+    library reads it, layout name)}``, and its device workspace."""
+    rows = {p: (img.data_ptr(), img.shape[2], img.shape[3], IMAGE_LAYOUTS[layout]) for p, (img, layout) in pictures.items()}
+    table = np.zeros(len(refs), dtype=_TILE_REF)
+    for k, field in enumerate(("img", "img_h", "img_w", "layout")):   # column by column: a row per tile, a picture's values repeated
+        table[field] = [rows[int(ref[0])][k] for ref in refs]
+    table["y0"], table["x0"] = [int(ref[2]) for ref in refs], [int(ref[3]) for ref in refs]
+    return table, torch.empty(len(refs) * _TILE_REF.itemsize, dtype=torch.uint8, device=device)
+
+
+def image_tiles_gather(pictures, refs, h, w):
+    """Tiles of MANY pictures in one launch (basic_image_tiles_gather_u8_to_f32_dev, include/basic_hip.h section 8d).  ``pictures``: uint8
+    ``[1, C, H, W]`` tensors on one GPU, of any sizes with one C, each read as it lies when it is contiguous or its memory is [H][W][C]
+    (image_layout_of) and made contiguous otherwise; ``refs``: one ``(picture, tile index, y0, x0)`` per tile (utils.tiling.pool_tiles),
+    ``picture`` an index into ``pictures``.  Returns float32 ``[len(refs), C, h, w]``, tile t equal to
+    ``pictures[p][..., y0:y0 + h, x0:x0 + w].float().div(255)``: what image_tiles_to_f32 gives for that picture and origin."""
+    refs = list(refs)
+    if not refs:
+        raise ValueError("image_tiles_gather: no tiles")
+    used = sorted({int(r[0]) for r in refs})
+    lie = {}
+    for p in used:
+        _tiles_picture(pictures[p])
+        lie[p] = _image_u8(pictures[p])
+    first = lie[used[0]][0]
+    C = first.shape[1]
+    if any(t.shape[1] != C or t.device != first.device for t, _ in lie.values()):
+        raise ValueError("image_tiles_gather: the pictures share one channel count and one device")
+    with torch.cuda.device(first.device):
+        table, ws = _tile_ref_table(lie, refs, first.device)
+        out = torch.empty((len(refs), C, int(h), int(w)), device=first.device, dtype=torch.float32)
+        _lib.check(_lib.lib().basic_image_tiles_gather_u8_to_f32_dev(table.ctypes.data, len(refs), C, int(h), int(w), ws.data_ptr(),
+                                                                     out.data_ptr(), _stream()))
+    del lie, ws   # enqueued: the allocator is stream-ordered
+    return out
+
+
+def image_tiles_scatter(batch, canvases, refs, h, w):
+    """The way back (basic_image_tiles_scatter_f32_to_u8_dev): the top-left h x w of reconstruction t of ``batch`` (float32
+    ``[len(refs), C, sh, sw]`` on the GPU) as bytes (image_f32_to_u8's values) at ``(y0, x0)`` of ``canvases[picture]`` of ``refs[t]``; the
+    canvases are uint8 ``[1, C, H, W]`` on the same GPU, contiguous or with [H][W][C] memory, and are written in place, bytes outside
+    the tiles keeping their value.  Tiles of one call must not intersect in a canvas.  One launch."""
+    refs = list(refs)
+    if not refs:
+        raise ValueError("image_tiles_scatter: no tiles")
+    batch = _dev(batch, torch.float32)
+    if batch.dim() != 4 or batch.shape[0] != len(refs):
+        raise ValueError(f"{len(refs)} tiles need a [{len(refs)}, C, sh, sw] batch, not {tuple(batch.shape)}")
+    C = batch.shape[1]
+    lie = {}
+    for p in sorted({int(r[0]) for r in refs}):
+        canvas = canvases[p]
+        _tiles_picture(canvas)
+        layout = image_layout_of(canvas)
+        if layout is None:
+            raise ValueError("a canvas must be contiguous or have [H][W][C] memory: the tiles are written into it in place")
+        if canvas.shape[1] != C or canvas.device != batch.device:
+            raise ValueError(f"image_tiles_scatter: canvas {p} is not a {C}-channel picture on the batch's device")
+        lie[p] = (canvas, layout)
+    with torch.cuda.device(batch.device):
+        table, ws = _tile_ref_table(lie, refs, batch.device)
+        _lib.check(_lib.lib().basic_image_tiles_scatter_f32_to_u8_dev(batch.data_ptr(), batch.shape[2], batch.shape[3], C, int(h), int(w),
+                                                                      table.ctypes.data, len(refs), ws.data_ptr(), _stream()))
+    del ws
+    return canvases
+
+
 def image_sse_u8(a, b):
     """The exact sum of squared differences of two uint8 [B, C, H, W] batches on one GPU, per image and channel: int64 [B, C]
     on that device (basic_image_sse_u8_dev; integer arithmetic, the same value at any batch, layout and alignment).  Each batch is

@@ -138,6 +138,41 @@ def split_group(group: TileGroup, max_batch=None) -> List[TileGroup]:
     return out
 
 
+class PooledTile(NamedTuple):
+    """Tile ``index`` (row-major) of picture ``picture``, whose origin is (y0, x0)."""
+    picture: int
+    index: int
+    y0: int
+    x0: int
+
+
+class TileChunk(NamedTuple):
+    """Tiles of one size (h, w), of any pictures: what one pooled coding call takes."""
+    h: int
+    w: int
+    tiles: Tuple[PooledTile, ...]
+
+
+def pool_tiles(grids: Sequence[TileGrid], max_batch=None) -> List[TileChunk]:
+    """The tiles of many pictures -- ``grids[p]`` is picture p's TileGrid -- as chunks of equally sized tiles: the full tiles of every
+    picture are th x tw whatever the picture's size, and the edge tiles fall into a few more sizes.  The order is fixed: sizes in the
+    order of their first appearance (pictures in order, a picture's tiles row-major), within a size picture-major and tile-major,
+    cut into chunks of at most ``max_batch`` tiles (None / 0: one chunk per size).  So every tile of every picture is in exactly
+    one chunk, and there are ``sum over the sizes of ceil(count / max_batch)`` chunks."""
+    if max_batch is not None and (isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 0):
+        raise ValueError(f"max_batch must be a positive integer or None, not {max_batch!r}")
+    by_size = {}   # insertion-ordered: a size's first appearance
+    for p, grid in enumerate(grids):
+        for k in range(len(grid)):
+            y, x, h, w = grid.tile_rect(k)
+            by_size.setdefault((h, w), []).append(PooledTile(p, k, y, x))
+    out = []
+    for (h, w), tiles in by_size.items():
+        step = max_batch or len(tiles)
+        out.extend(TileChunk(h, w, tuple(tiles[i:i + step])) for i in range(0, len(tiles), step))
+    return out
+
+
 def pack_tiled(channels, H, W, th, tw, strings: Sequence[bytes], overlap=(0, 0)) -> bytes:
     """The container of a picture's tile strings (row-major order): BTL1, or BTL2 when the tiles overlap."""
     grid = TileGrid(H, W, th, tw, overlap)

@@ -560,6 +560,50 @@ int basic_image_tiles_blend_dev(const basic_tile_source *d_table /* [rows * cols
 int basic_image_tiles_last_path(int *path);
 
 /* ======================================================================================
+ * 8d. Tiles of MANY 8-bit pictures (csrc/image.hip): the cut and the paste of section 8c driven by a table with one row per
+ *    tile, so that one launch reads or writes tiles of any number of pictures.  Pictures of different sizes share no batch
+ *    shape, but their tiles do: a caller pools the th x tw tiles of a whole set of pictures into one float batch and codes
+ *    that (cbench_basic_amd/utils/tiling.py: pool_tiles).
+ *    Row t of the table says where tile t of the float batch lies: the picture (device memory, uint8, [channels][img_h][img_w]
+ *    for BASIC_IMAGE_CHW or [img_h][img_w][channels] for BASIC_IMAGE_HWC), its size, and the tile's origin (y0, x0) in it.
+ *    Rows of one table may differ in picture, size and layout; rows may name the same picture again, and rows of a gather may
+ *    overlap (overlapped tiles need no entry of their own here).  Rectangles of ONE SCATTER that intersect in one picture are
+ *    the caller's duty: which tile's bytes such a sample ends up with is not defined.  The scatter writes only bytes inside
+ *    its tiles.
+ *    The table is passed in HOST memory, so that every row is checked before anything runs on the GPU; the entry then copies
+ *    it to the caller's device workspace d_table_ws (n rows, 8-byte aligned) on hip_stream and waits for that copy -- and,
+ *    with it, for what hip_stream held before -- so the host table may be reused when the call returns.  The launch itself
+ *    is enqueued, not awaited: d_table_ws, the pictures and the batch stay untouched until it has run.  One launch per call,
+ *    nothing allocated, 64-bit element offsets.
+ *    Values: exactly those of sections 8b / 8c, from the same device code.  A gathered tile equals, bit for bit, what
+ *    basic_image_tiles_u8_to_f32_dev gives for that picture and origin; a scattered tile what
+ *    basic_image_tiles_f32_to_u8_dev writes.
+ *    Wide path (the rule of 8c, decided on the host): a lane owns four consecutive samples of a tile row -- with
+ *    BASIC_IMAGE_HWC and 3 or 4 channels four pixels -- when the float base is 16-byte aligned, tw (and sw for the scatter)
+ *    is a multiple of 4 and EVERY row has a 4-byte aligned picture, img_w and x0 multiples of 4 and, where its layout is
+ *    BASIC_IMAGE_HWC with more than one channel, 3 or 4 channels.  Otherwise the whole launch goes sample by sample.
+ *    basic_image_tiles_last_path reports the path.  A workgroup reads a tile's row once.
+ *    BASIC_ERR_INVALID with a message, before any copy or launch, for a null pointer (table, workspace, batch, or a row's
+ *    picture), n < 1, a non-positive size, an unknown layout, a negative origin, y0 + th > img_h or x0 + tw > img_w in any
+ *    row, sh < th or sw < tw, a misaligned float pointer or workspace, or more than 2^40 float samples.
+ * ==================================================================================== */
+typedef struct basic_tile_ref {
+    void   *img;            /* uint8 picture in device memory */
+    int32_t img_h, img_w;   /* its size */
+    int32_t y0, x0;         /* the tile's origin in it */
+    int32_t layout;         /* BASIC_IMAGE_CHW / BASIC_IMAGE_HWC, per entry */
+} basic_tile_ref;
+/* Cut + ingest: tile t of d_dst, float32 [n][channels][th][tw], is the th x tw rectangle at (y0, x0) of table[t].img. */
+int basic_image_tiles_gather_u8_to_f32_dev(const basic_tile_ref *table /* HOST, n entries */, int n, int channels,
+                                           int th, int tw, basic_tile_ref *d_table_ws /* device, n entries */,
+                                           float *d_dst, void *hip_stream);
+/* Convert + crop + paste: the top-left th x tw of tile t of d_src, float32 [n][channels][sh][sw], goes to (y0, x0) of
+ * table[t].img. */
+int basic_image_tiles_scatter_f32_to_u8_dev(const float *d_src, int sh, int sw, int channels, int th, int tw,
+                                            const basic_tile_ref *table /* HOST */, int n, basic_tile_ref *d_table_ws,
+                                            void *hip_stream);
+
+/* ======================================================================================
  * 9. Persistent scan-line AR coding loop (csrc/scanline.hip): ONE launch walks all H*W coding steps of
  *    TopoGroupPGMPriorCoder._encode_with_pgm / _pgm_generate (pgm_coder.py:912-981) for the "scanline" topo groups
  *    (one position per group, raster order) with one channel group: masked k x k context convolution at the coded

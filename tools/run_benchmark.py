@@ -85,6 +85,10 @@ def main(argv=None):
     ap.add_argument("--tile-overlap", type=int, nargs="+", default=None, metavar=("OY", "OX"),
                     help="testing_tile_overlap: neighbouring tiles share OY rows and OX columns (OX = OY when omitted; at most half a tile) and "
                          "decompress_tiled cross-fades the seams (needs --tile)")
+    ap.add_argument("--tile-pool", type=int, default=0, metavar="N",
+                    help="testing_tile_pool: code up to N consecutive pictures, of any sizes, per call, the tiles of all of them pooled "
+                         "into shared coding calls (compress_tiled_items / decompress_tiled_items); every picture keeps its own container "
+                         "(needs --tile, does not combine with --workers above 1)")
     ap.add_argument("--stream-lanes", type=int, default=1,
                     help="lane streams per image of the y-coder, any codec (a format the reference does not read)")
     ap.add_argument("--stream-rows", action="store_true",
@@ -131,6 +135,13 @@ def main(argv=None):
             ap.error("--tile-overlap is at most half a tile")
     else:
         args.tile_overlap = (0, 0)
+    if args.tile_pool < 0:
+        ap.error("--tile-pool must be >= 0")
+    if args.tile_pool:
+        if args.tile is None:
+            ap.error("--tile-pool needs --tile")
+        if args.workers > 1:
+            ap.error("--tile-pool runs on the calling thread: it does not combine with --workers above 1")
     if args.workers > 1:   # before HIP initialises: one hardware queue per worker stream
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         os.environ.setdefault("BASIC_RANS_WPB", "8")
@@ -161,7 +172,9 @@ def main(argv=None):
     codec = codec.eval().to("cuda")
 
     def warm(c):   # one item through the route the pass takes
-        if args.tile is not None:
+        if args.tile_pool > 1:   # the first pooled call: the batch shapes the pass will meet
+            c.decompress_tiled_items(c.compress_tiled_items(batches[:args.tile_pool], tile=args.tile, overlap=args.tile_overlap))
+        elif args.tile is not None:
             c.decompress_tiled(c.compress_tiled(batches[0].to("cuda"), tile=args.tile, overlap=args.tile_overlap))
         else:
             c.decompress(c.compress(batches[0].to("cuda")))
@@ -188,6 +201,7 @@ def main(argv=None):
                                               testing_complexity_levels=args.complexity_levels,
                                               testing_variable_rate_levels=args.rate_levels, output_dir=args.out,
                                               num_testing_workers=args.workers, testing_coalesce_items=args.coalesce, testing_tile=args.tile, testing_tile_overlap=args.tile_overlap,
+                                              testing_tile_pool=args.tile_pool,
                                               codec_builder=(lambda: presets.seed_synthetic_weights(builders[args.codec](), seed=0)) if args.workers > 1 else None)
     if args.workers > 1 and args.warmup:   # the replicas' one-time costs too, one replica at a time (HIP-graph capture)
         pool = bench._worker_pool(batches[0], batch=max((len(c) for c in warm_chunks), default=None))
