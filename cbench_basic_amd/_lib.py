@@ -91,6 +91,8 @@ _SIGNATURES = {
     "basic_image_tiles_last_path": (_I, [_P]),
     "basic_image_tiles_gather_u8_to_f32_dev": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "basic_image_tiles_scatter_f32_to_u8_dev": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "basic_image_tiles_gather_pad_u8_to_f32_dev": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "basic_image_tiles_scatter_clip_f32_to_u8_dev": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "basic_hp_encode_images_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
     "basic_hp_decode_images_u8": (_I, [_P, _P, _L, _I, _P, _I, _L, _P]),
     "basic_hp_session_set_rans_waves": (_I, [_P, _I]),

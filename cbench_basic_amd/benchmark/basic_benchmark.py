@@ -33,6 +33,10 @@ or ``(oy, ox)``, at most half a tile; needs ``testing_tile``): the tiles overlap
 are coded per call (``codec.compress_tiled_items`` / ``decompress_tiled_items``), the tiles of all of them pooled into shared coding
 calls.  Every item is logged as the unpooled tiled pass logs it -- its own container's length, its own pasted picture's distortion --
 and a call's time is shared equally among its pictures.  It runs on the calling thread: no ``testing_coalesce_items``, no workers.
+
+``testing_tile_pad`` (an int or ``(py, px)`` that divides the tile; needs ``testing_tile``; INTEGRATION.md, "Tiled pictures"): the edge
+tiles are coded at their size rounded up to multiples of py x px (``compress_tiled(..., pad_to=)``), so ``compressed_length`` is the
+BTL3 container's length.  It composes with ``testing_tile_overlap`` and ``testing_tile_pool``.
 """
 import copy
 import csv
@@ -54,7 +58,7 @@ class BasicLosslessCompressionBenchmark:
                  testing_complexity_levels=None, force_testing_device="cuda", output_dir=None, num_repeats=1,
                  num_testing_workers=0, codec_builder=None, worker_transform_token=None, testing_coalesce_items=0,
                  metrics_on_uint8=False, on_reconstruction=None, testing_tile=None, testing_tile_overlap=0, testing_tile_pool=0,
-                 **kwargs):
+                 testing_tile_pad=None, **kwargs):
         self.codec = codec
         self.dataloader = dataloader
         self.distortion_metric = distortion_metric
@@ -117,6 +121,17 @@ class BasicLosslessCompressionBenchmark:
                 raise ValueError("testing_tile_pool needs testing_tile")   # which refuses testing_coalesce_items above 1
             if self.num_testing_workers > 1:
                 raise ValueError("testing_tile_pool runs on the calling thread: it does not combine with num_testing_workers")
+        # edge-padded tiles: an int or (py, px) that divides the tile; None: no padding, and no pad_to reaches the codec
+        if testing_tile_pad is not None:
+            testing_tile_pad = (testing_tile_pad,) * 2 if isinstance(testing_tile_pad, int) else tuple(int(v) for v in testing_tile_pad)
+            if len(testing_tile_pad) != 2 or min(testing_tile_pad) < 1:
+                raise ValueError(f"testing_tile_pad is (py, px), positive, not {testing_tile_pad!r}")
+            if testing_tile is None:
+                raise ValueError("testing_tile_pad needs testing_tile")
+            if testing_tile[0] % testing_tile_pad[0] or testing_tile[1] % testing_tile_pad[1]:
+                raise ValueError(f"testing_tile_pad {testing_tile_pad} does not divide a {testing_tile} tile")
+        self.testing_tile_pad = testing_tile_pad
+        self._tile_pad = {} if testing_tile_pad is None else dict(pad_to=testing_tile_pad)
         self._level_prefix = ""
         self._pictures = {}
         self._pool = None
@@ -191,7 +206,7 @@ class BasicLosslessCompressionBenchmark:
         if not isinstance(data, torch.Tensor) or data.dim() != 4 or data.shape[0] != 1:
             raise ValueError("testing_tile codes a dataset of batch-1 pictures ([1, C, H, W]); got "
                              f"{tuple(data.shape) if isinstance(data, torch.Tensor) else type(data).__name__}")
-        return codec.compress_tiled(data, tile=self.testing_tile, overlap=self.testing_tile_overlap)
+        return codec.compress_tiled(data, tile=self.testing_tile, overlap=self.testing_tile_overlap, **self._tile_pad)
 
     def _decompress(self, codec, compressed):
         if self.testing_tile is not None:
@@ -367,7 +382,7 @@ class BasicLosslessCompressionBenchmark:
     def _compress_many(self, codec, data):
         """The items of a chunk in one call: coalesced items of one shape, or pooled tiles of pictures of any sizes."""
         if self.testing_tile_pool:
-            return codec.compress_tiled_items(data, tile=self.testing_tile, overlap=self.testing_tile_overlap)
+            return codec.compress_tiled_items(data, tile=self.testing_tile, overlap=self.testing_tile_overlap, **self._tile_pad)
         return codec.compress_items(data, max_batch=len(data))
 
     def _decompress_many(self, codec, compressed):

@@ -40,24 +40,28 @@ class GeneralCodec(HotPathModule, CodecInterface, VariableRateCodecInterface, Va
         with self.profiler.start_time_profile("time_decompress_entropy_coder"):
             return self.entropy_coder.decode_items(strings, *args, max_batch=max_batch, **kwargs)
 
-    def compress_tiled(self, image, *args, tile=(512, 512), max_batch=None, overlap=0, **kwargs):
+    def compress_tiled(self, image, *args, tile=(512, 512), max_batch=None, overlap=0, pad_to=1, **kwargs):
         """One picture ``[1, C, H, W]`` -> the container of its independently coded tiles (utils/tiling.py), tile k's string exactly
         ``self.compress(image[:, :, y:y + h, x:x + w])`` (entropy coder's ``encode_tiled``).  ``overlap`` (int or ``(oy, ox)``, at most
-        half a tile): neighbouring tiles share that many rows / columns, and decompress_tiled cross-fades the seams."""
+        half a tile): neighbouring tiles share that many rows / columns, and decompress_tiled cross-fades the seams.  ``pad_to`` (int or
+        ``(py, px)``, dividing the tile): an edge tile is coded at its size rounded up to multiples of py x px, the picture's last row
+        and column replicated, and decompress_tiled crops it; 1, the default, pads nothing."""
         with self.profiler.start_time_profile("time_compress_entropy_coder"):
-            return self.entropy_coder.encode_tiled(image, *args, tile=tile, max_batch=max_batch, overlap=overlap, **kwargs)
+            return self.entropy_coder.encode_tiled(image, *args, tile=tile, max_batch=max_batch, overlap=overlap, pad_to=pad_to, **kwargs)
 
     def decompress_tiled(self, data, *args, **kwargs):
         """A container of compress_tiled -> the picture at its own size, or the ``region`` of it (entropy coder's ``decode_tiled``);
-        the overlap of the tiles, if any, is read from the container."""
+        the overlap and the padding of the tiles, if any, are read from the container."""
         with self.profiler.start_time_profile("time_decompress_entropy_coder"):
             return self.entropy_coder.decode_tiled(data, *args, **kwargs)
 
-    def compress_tiled_items(self, pictures, *args, tile=(512, 512), overlap=0, max_batch=None, **kwargs):
-        """N pictures ``[1, C, H, W]`` of any sizes -> their N containers, exactly ``[self.compress_tiled(p, tile=, overlap=) for p in
-        pictures]``, the tiles of all pictures pooled into shared coding calls (entropy coder's ``encode_tiled_items``)."""
+    def compress_tiled_items(self, pictures, *args, tile=(512, 512), overlap=0, max_batch=None, pad_to=1, **kwargs):
+        """N pictures ``[1, C, H, W]`` of any sizes -> their N containers, exactly ``[self.compress_tiled(p, tile=, overlap=, pad_to=)
+        for p in pictures]``, the tiles of all pictures pooled into shared coding calls (entropy coder's ``encode_tiled_items``); with
+        ``pad_to=tile`` every tile of every picture has one size."""
         with self.profiler.start_time_profile("time_compress_entropy_coder"):
-            return self.entropy_coder.encode_tiled_items(pictures, *args, tile=tile, overlap=overlap, max_batch=max_batch, **kwargs)
+            return self.entropy_coder.encode_tiled_items(pictures, *args, tile=tile, overlap=overlap, max_batch=max_batch, pad_to=pad_to,
+                                                         **kwargs)
 
     def decompress_tiled_items(self, containers, *args, **kwargs):
         """N containers -> their N pictures, each equal to ``self.decompress_tiled(container)`` (entropy coder's

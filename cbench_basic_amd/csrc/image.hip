@@ -15,7 +15,8 @@
 // The third entry measures such pictures: the exact per-channel sum of squared differences of two uint8 batches (further down).
 // The last entries cut float tiles out of one uint8 picture, paste reconstructed tiles back into one and, for overlapped tiles, write
 // the picture from all their reconstructions with the seams cross-faded (section 8c); the cut and the paste again for tiles of MANY
-// pictures, a table row per tile (section 8d, at the end).
+// pictures, a table row per tile (section 8d, at the end), there also for tiles that leave their picture at the bottom and right: the cut
+// replicates the last row and column into them, the paste clips them (the EDGE instantiations).
 #include <utility>
 
 #include "common.h"
@@ -430,37 +431,64 @@ thread_local int g_tiles_last_path = -1;   // basic_image_tiles_last_path: 0 sca
 
 // run r of a wide launch -> first sample: offset on the uint8 side (channel 0 when C > 1) and on the float side (plane stride
 // fh * fw when C > 1).  Both in samples; both multiples of 4.
-template <int C>
-__device__ __forceinline__ void locate_run(const TileGroup &g, int64_t r, int64_t *u8, int64_t *f32)
+// EDGE (section 8d, tiles that leave their picture at the bottom and right): a run is wholly inside or wholly outside a picture row;
+// the uint8 offset of an outside run is clamped -- rows at or beyond img_h to row img_h - 1, runs at or beyond img_w to the row's last
+// run -- and the result says where the run lay: kRunRight | kRunBelow, 0 inside.  Without EDGE the result is 0.
+constexpr int kRunRight = 1, kRunBelow = 2;
+
+template <int C, bool EDGE = false>
+__device__ __forceinline__ int locate_run(const TileGroup &g, int64_t r, int64_t *u8, int64_t *f32)
 {
     const int64_t qn = g.tw / 4;
     const int64_t q = r % qn, job = r / qn;
     const int64_t row = job % g.th, t = job / g.th;
     const int64_t c = C == 1 ? t % g.channels : 0, tile = C == 1 ? t / g.channels : t;
-    const int64_t y = g.y0 + (tile / g.nx) * g.step_y + row, x = g.x0 + (tile % g.nx) * g.step_x + 4 * q;
+    int64_t y = g.y0 + (tile / g.nx) * g.step_y + row, x = g.x0 + (tile % g.nx) * g.step_x + 4 * q;
+    int where = 0;
+    if (EDGE) {
+        if (x >= g.img_w) where |= kRunRight, x = g.img_w - 4;
+        if (y >= g.img_h) where |= kRunBelow, y = g.img_h - 1;
+    }
     *u8 = C == 1 ? (c * g.img_h + y) * g.img_w + x : (y * g.img_w + x) * C;
     *f32 = ((tile * g.channels + c) * g.fh + row) * g.fw + 4 * q;
+    return where;
+}
+
+// the last pixel of a run in all four places: byte 3 of a planar dword, pixel 3 of an interleaved Words<C>
+template <int C>
+__device__ __forceinline__ Words<C> broadcast_last(const Words<C> &in)
+{
+    Words<C> out;
+#pragma unroll
+    for (int k = 0; k < C; ++k) out.w[k] = 0u;
+#pragma unroll
+    for (int byte = 0; byte < 4 * C; ++byte) {
+        const int from = 3 * C + byte % C;
+        out.w[byte / 4] |= ((in.w[from / 4] >> (8 * (from % 4))) & 0xffu) << (8 * (byte % 4));
+    }
+    return out;
 }
 
 // run r of a group, cut and pasted.  Shared by the kernels of one picture here and those of a table of tiles (section 8d).
-template <int C>
+template <int C, bool EDGE = false>
 __device__ __forceinline__ void cut_run(const uint32_t *__restrict__ img, float4 *__restrict__ dst, const TileGroup &g, int64_t r,
                                         const float *lut)
 {
     const int64_t plane4 = g.fh * g.fw / 4;
     int64_t u, f;
-    locate_run<C>(g, r, &u, &f);
-    const Words<C> in = *reinterpret_cast<const Words<C> *>(img + u / 4);
+    const int where = locate_run<C, EDGE>(g, r, &u, &f);
+    Words<C> in = *reinterpret_cast<const Words<C> *>(img + u / 4);
+    if (EDGE && (where & kRunRight)) in = broadcast_last<C>(in);   // right of the picture: the row's last pixel
 #pragma unroll
     for (int c = 0; c < C; ++c) dst[f / 4 + c * plane4] = run_to_f32<C>(in, c, lut);
 }
 
-template <int C>
+template <int C, bool EDGE = false>
 __device__ __forceinline__ void paste_run(const float4 *__restrict__ src, uint32_t *__restrict__ img, const TileGroup &g, int64_t r)
 {
     const int64_t plane4 = g.fh * g.fw / 4;
     int64_t u, f;
-    locate_run<C>(g, r, &u, &f);
+    if (locate_run<C, EDGE>(g, r, &u, &f)) return;   // outside the picture: nothing is written
     Words<C> out;
 #pragma unroll
     for (int k = 0; k < C; ++k) out.w[k] = 0u;
@@ -488,26 +516,37 @@ __global__ __launch_bounds__(kBlock) void tiles_f32_to_u8_wide_kernel(const floa
 }
 
 // sample (tile, c, row, col) of a group -> its offsets on the two sides
-__device__ __forceinline__ void locate_sample(const TileGroup &g, int hwc, int64_t tile, int64_t c, int64_t row, int64_t col, int64_t *u8,
+// EDGE: the sample's place in the picture clamped to its last row and column; true when it lay outside (false without EDGE)
+template <bool EDGE = false>
+__device__ __forceinline__ bool locate_sample(const TileGroup &g, int hwc, int64_t tile, int64_t c, int64_t row, int64_t col, int64_t *u8,
                                               int64_t *f32)
 {
-    const int64_t y = g.y0 + (tile / g.nx) * g.step_y + row, x = g.x0 + (tile % g.nx) * g.step_x + col;
+    int64_t y = g.y0 + (tile / g.nx) * g.step_y + row, x = g.x0 + (tile % g.nx) * g.step_x + col;
+    bool outside = false;
+    if (EDGE) {
+        outside = y >= g.img_h || x >= g.img_w;
+        if (y >= g.img_h) y = g.img_h - 1;
+        if (x >= g.img_w) x = g.img_w - 1;
+    }
     *u8 = hwc ? (y * g.img_w + x) * g.channels + c : (c * g.img_h + y) * g.img_w + x;
     *f32 = ((tile * g.channels + c) * g.fh + row) * g.fw + col;
+    return outside;
 }
 
 // sample i of the float side, [tile][c][row][col] (fh x fw = th x tw here), cut
+template <bool EDGE = false>
 __device__ __forceinline__ void cut_sample(const uint8_t *__restrict__ img, float *__restrict__ dst, int hwc, const TileGroup &g, int64_t i,
                                            const float *lut)
 {
     const int64_t col = i % g.tw, job = i / g.tw;
     const int64_t row = job % g.th, t = job / g.th;
     int64_t u, f;
-    locate_sample(g, hwc, t / g.channels, t % g.channels, row, col, &u, &f);
+    locate_sample<EDGE>(g, hwc, t / g.channels, t % g.channels, row, col, &u, &f);
     dst[f] = lut[img[u]];
 }
 
 // sample j of the uint8 side of the tiles ([tile][c][row][col], hwc: [tile][row][col][c]), pasted
+template <bool EDGE = false>
 __device__ __forceinline__ void paste_sample(const float *__restrict__ src, uint8_t *__restrict__ img, int hwc, const TileGroup &g, int64_t j)
 {
     int64_t tile, c, row, col;
@@ -525,7 +564,7 @@ __device__ __forceinline__ void paste_sample(const float *__restrict__ src, uint
         tile = t / g.channels;
     }
     int64_t u, f;
-    locate_sample(g, hwc, tile, c, row, col, &u, &f);
+    if (locate_sample<EDGE>(g, hwc, tile, c, row, col, &u, &f)) return;   // outside the picture: nothing is written
     img[u] = static_cast<uint8_t>(quantise(src[f]));
 }
 
@@ -903,7 +942,7 @@ __device__ __forceinline__ TileGroup pool_group(const basic_tile_ref *__restrict
 }
 
 // HC: the channels of the rows whose picture is interleaved (3, 4), or 1: every row is planar
-template <int HC>
+template <int HC, bool EDGE = false>
 __global__ __launch_bounds__(kBlock) void pool_u8_to_f32_wide_kernel(const basic_tile_ref *__restrict__ table, float4 *__restrict__ dst,
                                                                       PoolShape s, int64_t n)
 {
@@ -916,14 +955,14 @@ __global__ __launch_bounds__(kBlock) void pool_u8_to_f32_wide_kernel(const basic
         const TileGroup g = pool_group(table, t, &slot, s);
         const uint32_t *img = static_cast<const uint32_t *>(slot.img);
         if (HC > 1 && slot.layout == BASIC_IMAGE_HWC) {
-            for (int64_t r = lane; r < s.th * s.tw / 4; r += lanes) cut_run<HC>(img, dst + t * tile4, g, r, lut);
+            for (int64_t r = lane; r < s.th * s.tw / 4; r += lanes) cut_run<HC, EDGE>(img, dst + t * tile4, g, r, lut);
         } else {
-            for (int64_t r = lane; r < s.channels * s.th * s.tw / 4; r += lanes) cut_run<1>(img, dst + t * tile4, g, r, lut);
+            for (int64_t r = lane; r < s.channels * s.th * s.tw / 4; r += lanes) cut_run<1, EDGE>(img, dst + t * tile4, g, r, lut);
         }
     }
 }
 
-template <int HC>
+template <int HC, bool EDGE = false>
 __global__ __launch_bounds__(kBlock) void pool_f32_to_u8_wide_kernel(const float4 *__restrict__ src, const basic_tile_ref *__restrict__ table,
                                                                       PoolShape s, int64_t n)
 {
@@ -934,13 +973,14 @@ __global__ __launch_bounds__(kBlock) void pool_f32_to_u8_wide_kernel(const float
         const TileGroup g = pool_group(table, t, &slot, s);
         uint32_t *img = static_cast<uint32_t *>(slot.img);
         if (HC > 1 && slot.layout == BASIC_IMAGE_HWC) {
-            for (int64_t r = lane; r < s.th * s.tw / 4; r += lanes) paste_run<HC>(src + t * tile4, img, g, r);
+            for (int64_t r = lane; r < s.th * s.tw / 4; r += lanes) paste_run<HC, EDGE>(src + t * tile4, img, g, r);
         } else {
-            for (int64_t r = lane; r < s.channels * s.th * s.tw / 4; r += lanes) paste_run<1>(src + t * tile4, img, g, r);
+            for (int64_t r = lane; r < s.channels * s.th * s.tw / 4; r += lanes) paste_run<1, EDGE>(src + t * tile4, img, g, r);
         }
     }
 }
 
+template <bool EDGE = false>
 __global__ __launch_bounds__(kBlock) void pool_u8_to_f32_scalar_kernel(const basic_tile_ref *__restrict__ table, float *__restrict__ dst,
                                                                         PoolShape s, int64_t n)
 {
@@ -953,10 +993,11 @@ __global__ __launch_bounds__(kBlock) void pool_u8_to_f32_scalar_kernel(const bas
         const TileGroup g = pool_group(table, t, &slot, s);
         const int hwc = slot.layout == BASIC_IMAGE_HWC && s.channels > 1;
         for (int64_t i = lane; i < s.channels * s.th * s.tw; i += lanes)
-            cut_sample(static_cast<const uint8_t *>(slot.img), dst + t * tile, hwc, g, i, lut);
+            cut_sample<EDGE>(static_cast<const uint8_t *>(slot.img), dst + t * tile, hwc, g, i, lut);
     }
 }
 
+template <bool EDGE = false>
 __global__ __launch_bounds__(kBlock) void pool_f32_to_u8_scalar_kernel(const float *__restrict__ src, const basic_tile_ref *__restrict__ table,
                                                                         PoolShape s, int64_t n)
 {
@@ -967,7 +1008,7 @@ __global__ __launch_bounds__(kBlock) void pool_f32_to_u8_scalar_kernel(const flo
         const TileGroup g = pool_group(table, t, &slot, s);
         const int hwc = slot.layout == BASIC_IMAGE_HWC && s.channels > 1;
         for (int64_t j = lane; j < s.channels * s.th * s.tw; j += lanes)
-            paste_sample(src + t * tile, static_cast<uint8_t *>(slot.img), hwc, g, j);
+            paste_sample<EDGE>(src + t * tile, static_cast<uint8_t *>(slot.img), hwc, g, j);
     }
 }
 
@@ -977,10 +1018,10 @@ struct PoolPlan {
     dim3 grid;
 };
 
-// every check of both entries, on the HOST table: nothing has been copied or launched when this fails.  fh x fw is the float
-// side's plane (th x tw for the gather).
+// every check of the entries, on the HOST table: nothing has been copied or launched when this fails.  fh x fw is the float
+// side's plane (th x tw for the gather).  edge: tiles may leave their picture at the bottom and right, their origins may not.
 int plan_pool(const basic_tile_ref *table, int n, int channels, int th, int tw, int fh, int fw, const void *d_table_ws, const void *d_f32,
-              const char *what, PoolPlan *p)
+              const char *what, PoolPlan *p, bool edge = false)
 {
     const std::string who(what);
     BASIC_REQUIRE(table && d_table_ws && d_f32, who + ": null pointer");
@@ -1000,7 +1041,8 @@ int plan_pool(const basic_tile_ref *table, int n, int channels, int th, int tw, 
         BASIC_REQUIRE(e.layout == BASIC_IMAGE_CHW || e.layout == BASIC_IMAGE_HWC, row + ": layout is BASIC_IMAGE_CHW or BASIC_IMAGE_HWC");
         BASIC_REQUIRE(e.img_h >= 1 && e.img_w >= 1, row + ": the picture's size must be positive");
         BASIC_REQUIRE(e.y0 >= 0 && e.x0 >= 0, row + ": y0 and x0 must not be negative");
-        BASIC_REQUIRE(static_cast<int64_t>(e.y0) + th <= e.img_h && static_cast<int64_t>(e.x0) + tw <= e.img_w, row + ": the tile leaves the picture");
+        if (edge) BASIC_REQUIRE(e.y0 < e.img_h && e.x0 < e.img_w, row + ": the tile's origin leaves the picture");
+        else BASIC_REQUIRE(static_cast<int64_t>(e.y0) + th <= e.img_h && static_cast<int64_t>(e.x0) + tw <= e.img_w, row + ": the tile leaves the picture");
         BASIC_REQUIRE(static_cast<int64_t>(e.img_h) * e.img_w <= (int64_t(1) << 60) / channels, row + ": the picture is too large");
         const bool hwc = e.layout == BASIC_IMAGE_HWC && channels > 1;   // one channel: the two layouts coincide
         any_hwc = any_hwc || hwc;
@@ -1040,7 +1082,7 @@ extern "C" int basic_image_tiles_gather_u8_to_f32_dev(const basic_tile_ref *tabl
     if (p.wide_c == 1) hipLaunchKernelGGL(pool_u8_to_f32_wide_kernel<1>, p.grid, dim3(kBlock), 0, st, d_table_ws, dst4, p.s, n64);
     else if (p.wide_c == 3) hipLaunchKernelGGL(pool_u8_to_f32_wide_kernel<3>, p.grid, dim3(kBlock), 0, st, d_table_ws, dst4, p.s, n64);
     else if (p.wide_c == 4) hipLaunchKernelGGL(pool_u8_to_f32_wide_kernel<4>, p.grid, dim3(kBlock), 0, st, d_table_ws, dst4, p.s, n64);
-    else hipLaunchKernelGGL(pool_u8_to_f32_scalar_kernel, p.grid, dim3(kBlock), 0, st, d_table_ws, d_dst, p.s, n64);
+    else hipLaunchKernelGGL(pool_u8_to_f32_scalar_kernel<>, p.grid, dim3(kBlock), 0, st, d_table_ws, d_dst, p.s, n64);
     g_tiles_last_path = p.wide_c ? 1 : 0;
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
@@ -1062,7 +1104,54 @@ extern "C" int basic_image_tiles_scatter_f32_to_u8_dev(const float *d_src, int s
     if (p.wide_c == 1) hipLaunchKernelGGL(pool_f32_to_u8_wide_kernel<1>, p.grid, dim3(kBlock), 0, st, src4, d_table_ws, p.s, n64);
     else if (p.wide_c == 3) hipLaunchKernelGGL(pool_f32_to_u8_wide_kernel<3>, p.grid, dim3(kBlock), 0, st, src4, d_table_ws, p.s, n64);
     else if (p.wide_c == 4) hipLaunchKernelGGL(pool_f32_to_u8_wide_kernel<4>, p.grid, dim3(kBlock), 0, st, src4, d_table_ws, p.s, n64);
-    else hipLaunchKernelGGL(pool_f32_to_u8_scalar_kernel, p.grid, dim3(kBlock), 0, st, d_src, d_table_ws, p.s, n64);
+    else hipLaunchKernelGGL(pool_f32_to_u8_scalar_kernel<>, p.grid, dim3(kBlock), 0, st, d_src, d_table_ws, p.s, n64);
+    g_tiles_last_path = p.wide_c ? 1 : 0;
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+// Edge-padded tiles: the same two launches over tiles of ph x pw that may leave their picture at the bottom and right.  The gather
+// replicates the picture's last row and column into the part outside (the clamped address of every sample), the scatter writes the
+// part inside and nothing else.  The EDGE instantiations of the kernels above; a table without an edge tile gives the same bits.
+extern "C" int basic_image_tiles_gather_pad_u8_to_f32_dev(const basic_tile_ref *table, int n, int channels, int ph, int pw,
+                                                          basic_tile_ref *d_table_ws, float *d_dst, void *hip_stream)
+{
+    PoolPlan p;
+    int rc = plan_pool(table, n, channels, ph, pw, ph, pw, d_table_ws, d_dst, "image_tiles_gather_pad_u8_to_f32", &p, true);
+    if (rc) return rc;
+    rc = require_device();
+    if (rc) return rc;
+    hipStream_t st = as_stream(hip_stream);
+    rc = stage_pool_table(table, n, d_table_ws, st);
+    if (rc) return rc;
+    float4 *dst4 = reinterpret_cast<float4 *>(d_dst);
+    const int64_t n64 = n;
+    if (p.wide_c == 1) hipLaunchKernelGGL((pool_u8_to_f32_wide_kernel<1, true>), p.grid, dim3(kBlock), 0, st, d_table_ws, dst4, p.s, n64);
+    else if (p.wide_c == 3) hipLaunchKernelGGL((pool_u8_to_f32_wide_kernel<3, true>), p.grid, dim3(kBlock), 0, st, d_table_ws, dst4, p.s, n64);
+    else if (p.wide_c == 4) hipLaunchKernelGGL((pool_u8_to_f32_wide_kernel<4, true>), p.grid, dim3(kBlock), 0, st, d_table_ws, dst4, p.s, n64);
+    else hipLaunchKernelGGL(pool_u8_to_f32_scalar_kernel<true>, p.grid, dim3(kBlock), 0, st, d_table_ws, d_dst, p.s, n64);
+    g_tiles_last_path = p.wide_c ? 1 : 0;
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_image_tiles_scatter_clip_f32_to_u8_dev(const float *d_src, int sh, int sw, int channels, int ph, int pw,
+                                                            const basic_tile_ref *table, int n, basic_tile_ref *d_table_ws, void *hip_stream)
+{
+    PoolPlan p;
+    int rc = plan_pool(table, n, channels, ph, pw, sh, sw, d_table_ws, d_src, "image_tiles_scatter_clip_f32_to_u8", &p, true);
+    if (rc) return rc;
+    rc = require_device();
+    if (rc) return rc;
+    hipStream_t st = as_stream(hip_stream);
+    rc = stage_pool_table(table, n, d_table_ws, st);
+    if (rc) return rc;
+    const float4 *src4 = reinterpret_cast<const float4 *>(d_src);
+    const int64_t n64 = n;
+    if (p.wide_c == 1) hipLaunchKernelGGL((pool_f32_to_u8_wide_kernel<1, true>), p.grid, dim3(kBlock), 0, st, src4, d_table_ws, p.s, n64);
+    else if (p.wide_c == 3) hipLaunchKernelGGL((pool_f32_to_u8_wide_kernel<3, true>), p.grid, dim3(kBlock), 0, st, src4, d_table_ws, p.s, n64);
+    else if (p.wide_c == 4) hipLaunchKernelGGL((pool_f32_to_u8_wide_kernel<4, true>), p.grid, dim3(kBlock), 0, st, src4, d_table_ws, p.s, n64);
+    else hipLaunchKernelGGL(pool_f32_to_u8_scalar_kernel<true>, p.grid, dim3(kBlock), 0, st, d_src, d_table_ws, p.s, n64);
     g_tiles_last_path = p.wide_c ? 1 : 0;
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;

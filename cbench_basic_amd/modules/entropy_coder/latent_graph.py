@@ -627,25 +627,79 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
         return int(th), int(tw)
 
-    def encode_tiled(self, image, *args, tile=(512, 512), max_batch=None, overlap=0, **kwargs) -> bytes:
+    @staticmethod
+    def _padded_tile(picture, y, x, h, w):
+        """``picture[:, :, y:y + h, x:x + w]`` of a ``[1, C, H, W]`` picture; where the rectangle leaves the picture at the bottom or right,
+        the last row and column replicated: sample (r, q) is ``picture[..., min(y + r, H - 1), min(x + q, W - 1)]`` (index tensors)."""
+        H, W = picture.shape[2], picture.shape[3]
+        if y + h <= H and x + w <= W:
+            return picture[:, :, y:y + h, x:x + w]
+        iy = torch.arange(y, y + h, device=picture.device).clamp_(max=H - 1)
+        ix = torch.arange(x, x + w, device=picture.device).clamp_(max=W - 1)
+        return picture[:, :, iy[:, None], ix[None, :]]
+
+    def _encode_pooled(self, pictures, grids, framing, max_batch, args=(), kwargs=None):
+        """The tile strings of ``pictures`` (on the device) over ``grids``, ``[picture][tile]``: the pooled plan (utils.tiling.pool_tiles)
+        when ``framing`` splits a batch's string, one encode() per tile otherwise.  Counts into ``last_items_calls``."""
+        from ...nn import kernels as K
+        from ...utils import tiling
+        kwargs = kwargs or {}
+        strings = [[None] * len(g) for g in grids]
+        with torch.no_grad(), torch.cuda.device(self.device):
+            if framing is None:
+                for p, g in enumerate(grids):
+                    for k in range(len(g)):
+                        y, x, _, _ = g.tile_rect(k)
+                        self.last_items_calls += 1
+                        strings[p][k] = self.encode(self._padded_tile(pictures[p], y, x, *g.coded_size(k)), *args, **kwargs)
+                return strings
+            for dtype in (torch.uint8, torch.float32):
+                own = [p for p, x in enumerate(pictures) if x.dtype == dtype]
+                padded = any(grids[p].pad_to != (1, 1) for p in own)
+                for chunk in tiling.pool_tiles([grids[p] for p in own], max_batch):
+                    refs = [t._replace(picture=own[t.picture]) for t in chunk.tiles]
+                    self.last_items_calls += 1
+                    if len(refs) == 1:
+                        p, k, y, x = refs[0]
+                        strings[p][k] = self.encode(self._padded_tile(pictures[p], y, x, chunk.h, chunk.w))
+                        continue
+                    if dtype == torch.uint8:
+                        batch = K.image_tiles_gather(pictures, refs, chunk.h, chunk.w, pad=padded)
+                    else:
+                        batch = torch.empty((len(refs), pictures[own[0]].shape[1], chunk.h, chunk.w), dtype=dtype, device=self.device)
+                        for j, (p, _, y, x) in enumerate(refs):
+                            batch[j].copy_(self._padded_tile(pictures[p], y, x, chunk.h, chunk.w)[0])
+                    for (p, k, _, _), one in zip(refs, self._split_string(self.encode(batch), len(refs), framing)):
+                        strings[p][k] = one
+        return strings
+
+    def encode_tiled(self, image, *args, tile=(512, 512), max_batch=None, overlap=0, pad_to=1, **kwargs) -> bytes:
         """One picture ``[1, C, H, W]`` (uint8 in chw or hwc memory, or float32; host or device) -> the container of its tiles'
         strings (utils/tiling.py), tile k's string EXACTLY ``self.encode(image[:, :, y:y + h, x:x + w])``.  Tiles of one size are cut
         out of the uint8 picture by one kernel launch per chunk of at most ``max_batch`` and coded in one encode() call, whose string
         is split as in encode_items; one call per tile when a coder cannot split, a chunk holds one tile, or the call brings
         arguments.  Tiles are coded independently.  ``overlap`` (an int, or ``(oy, ox)``, at most half a tile): neighbouring tiles
         share that many rows and columns (utils/tiling.py), the container is BTL2, and decode_tiled cross-fades the seams; with 0,
-        the default, the tiles abut and every byte of the container is what it was before overlaps existed."""
+        the default, the tiles abut and every byte of the container is what it was before overlaps existed.
+        ``pad_to`` (an int, or ``(py, px)``, dividing the tile): an edge tile is coded at its size rounded up to multiples of py x px, the
+        picture's last row and column replicated (utils/tiling.py): tile k's string is EXACTLY ``self.encode(P_k)`` of that padded tile,
+        the container is BTL3, and decode_tiled crops.  The tiles then take the pooled plan over this one picture (tiles of one coded
+        size share calls of at most ``max_batch``, cut by nn.kernels.image_tiles_gather), so ``pad_to=tile`` codes a picture as one
+        group.  With 1, the default, nothing is padded and nothing changes."""
         from ...nn import kernels as K
         from ...utils import tiling
         self._check_item(image)
         if image.dtype not in (torch.uint8, torch.float32):
             raise TypeError(f"a picture is torch.uint8 or torch.float32, not {image.dtype}")
         _, C, H, W = image.shape
-        grid = tiling.TileGrid(H, W, *self._tile_size(tile), overlap=overlap)
+        grid = tiling.TileGrid(H, W, *self._tile_size(tile), overlap=overlap, pad_to=pad_to)
         self.last_items_calls = 0
         framing = self._items_framing() if not (args or kwargs or self.training) else None
         if image.device != self.device:
             image = image.to(device=self.device)   # once, as it lies: a dense picture keeps its strides
+        if grid.pad_to != (1, 1):
+            out, = self._encode_pooled([image], [grid], framing, max_batch, args, kwargs)
+            return tiling.pack_tiled(C, H, W, grid.th, grid.tw, out, overlap=grid.overlap, pad_to=grid.pad_to)
         out = [None] * len(grid)
         with torch.no_grad():
             for group in grid.groups():
@@ -675,15 +729,20 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         Overlapped tiles (a BTL2 container; the overlap is read from it): the tiles that cover a sample of the picture or region are
         decoded as above, and ONE blend launch (nn.kernels.image_tiles_blend) writes the result from their reconstructions, the
         seams cross-faded as include/basic_hip.h section 8c defines.  The reconstructions of ALL decoded tiles are resident until
-        that launch: 4 * C * sh * sw bytes per tile on top of the result, where the abutting path holds one chunk at a time."""
+        that launch: 4 * C * sh * sw bytes per tile on top of the result, where the abutting path holds one chunk at a time.
+        Edge-padded tiles (a BTL3 container; ``pad_to`` is read from it): every tile's reconstruction is cropped to the tile's valid
+        rectangle, its top-left.  The tiles of the picture or region take the pooled plan of decode_tiled_items over this one picture
+        (one decode() call per coded size and ``max_batch``; uint8 results pasted by nn.kernels.image_tiles_scatter with ``clip=True``);
+        overlapped ones are written by the same blend launch, which reads those top-left samples."""
         from ...nn import kernels as K
         from ...utils import tiling
         if output_dtype not in (None, torch.float32, torch.uint8):
             raise TypeError(f"output_dtype is torch.float32 or torch.uint8, not {output_dtype}")
         if layout not in K.IMAGE_LAYOUTS:
             raise ValueError(f"layout is 'chw' or 'hwc', not {layout!r}")
-        C, H, W, th, tw, overlap, strings = tiling.unpack_tiled_any(data)
-        grid = tiling.TileGrid(H, W, th, tw, overlap)
+        head = tiling.unpack_tiled_full(data)
+        C, H, W, th, tw, overlap, pad_to, strings = head
+        grid = tiling.TileGrid(H, W, th, tw, overlap, pad_to)
         if region is None:
             groups, (ry0, rx0, ry1, rx1) = grid.groups(), (0, 0, H, W)
         else:
@@ -705,6 +764,10 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                 canvas = torch.empty((1, ch, cw, C), dtype=dtype, device=self.device).permute(0, 3, 1, 2)
             else:
                 canvas = torch.empty((1, C, ch, cw), dtype=dtype, device=self.device)
+            if grid.pad_to != (1, 1):
+                self._decode_pooled([head], [grid], [canvas], framing, max_batch, as_u8, picks=[{k for g in groups for k in g.indices}],
+                                    origins=[(cy0, cx0)], regions=[(ry0, rx0, ry1, rx1)], args=args, kwargs=kwargs)
+                groups = []
             for group in groups:
                 for sub in tiling.split_group(group, 1 if framing is None else max_batch):
                     self.last_items_calls += 1
@@ -725,22 +788,92 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                         for j in range(len(sub.indices)):
                             y, x = sub.y0 + j // sub.nx * sub.step_y, sub.x0 + j % sub.nx * sub.step_x
                             canvas[0, :, y:y + sub.h, x:x + sub.w].copy_(rec[j, :, :sub.h, :sub.w])
-            if blend:
+            if blend and grid.pad_to == (1, 1):
                 K.image_tiles_blend(recs, grid, canvas, (ry0, rx0, ry1, rx1))
         if region is None:
             return canvas
         return canvas[:, :, ry0 - cy0:ry1 - cy0, rx0 - cx0:rx1 - cx0]
 
+    def _decode_pooled(self, heads, grids, canvases, framing, max_batch, as_u8, picks=None, origins=None, regions=None, args=(), kwargs=None):
+        """The pooled decode: the tiles of the containers ``heads`` (utils.tiling.TiledPicture; ``grids`` their TileGrids) decoded in calls
+        shared by tiles of one coded size whose strings' own headers agree, each reconstruction cropped to its tile's valid rectangle
+        and written into ``canvases[p]``.  ``picks[p]``: the tile numbers of picture p to decode (default: all); ``origins[p]``: where
+        canvas p's first sample lies in picture p (default: (0, 0)); ``regions[p]``: the rectangle an overlapped picture's blend launch
+        writes (default: the picture; the canvas is then that rectangle).  ``framing`` None: one decode() per tile, with the call's
+        arguments.  Counts into ``last_items_calls`` and ``last_tiles_decoded``."""
+        from ...nn import kernels as K
+        from ...utils import tiling
+        kwargs = kwargs or {}
+        strings = [t.strings for t in heads]
+        blend = [g.overlap != (0, 0) for g in grids]
+        # the planner's chunks of one size each, refined by what the strings say about themselves, then cut at max_batch
+        chunks = []
+        for size in tiling.pool_tiles(grids, None):
+            tiles = [t for t in size.tiles if picks is None or t.index in picks[t.picture]]
+            if framing is None:
+                chunks.extend((size.h, size.w, [t]) for t in tiles)
+                continue
+            by_key = {}
+            for t in tiles:
+                segs = split_merged_bytes(strings[t.picture][t.index], num_segments=len(framing))
+                key = (heads[t.picture][0],) + tuple(c.item_shape(seg, **ctx) if hasattr(c, "item_shape") else None
+                                                     for (c, ctx), seg in zip(framing, segs))
+                by_key.setdefault(key, []).append(t)
+            for tiles in by_key.values():
+                step = max_batch or len(tiles)
+                chunks.extend((size.h, size.w, tiles[i:i + step]) for i in range(0, len(tiles), step))
+        waiting = [0] * len(grids)   # tiles an overlapped picture still lacks
+        for h, w, tiles in chunks:
+            for t in tiles:
+                waiting[t.picture] += blend[t.picture]
+        held = [[] for _ in grids]       # its (batch view, tile indices) so far
+        for h, w, tiles in chunks:
+            self.last_items_calls += 1
+            self.last_tiles_decoded += len(tiles)
+            if len(tiles) == 1:
+                rec = self.decode(strings[tiles[0].picture][tiles[0].index], *args, **kwargs)
+            else:
+                rec = self.decode(self._merge_strings([strings[t.picture][t.index] for t in tiles], framing))
+            C = heads[tiles[0].picture][0]
+            if rec.dim() != 4 or rec.shape[0] != len(tiles) or rec.shape[1] != C or rec.shape[2] < h or rec.shape[3] < w:
+                raise ValueError(f"tiles of [{len(tiles)}, {C}, {h}, {w}] decoded to {tuple(rec.shape)}")
+            plain = [j for j, t in enumerate(tiles) if not blend[t.picture]]
+            if origins is None:
+                placed = [tiles[j] for j in plain]
+            else:   # the canvas is a window of the picture
+                placed = [tiles[j]._replace(y0=tiles[j].y0 - origins[tiles[j].picture][0], x0=tiles[j].x0 - origins[tiles[j].picture][1])
+                          for j in plain]
+            if plain and as_u8:
+                part = rec if len(plain) == len(tiles) else rec[torch.tensor(plain, device=rec.device)]
+                # a padded tile leaves its canvas where it leaves its picture: only the valid rectangle is written
+                K.image_tiles_scatter(part, canvases, placed, h, w, clip=any(grids[t.picture].pad_to != (1, 1) for t in placed))
+            elif plain:
+                for j, (p, k, y, x) in zip(plain, placed):
+                    _, _, vh, vw = grids[p].tile_rect(k)
+                    canvases[p][0, :, y:y + vh, x:x + vw].copy_(rec[j, :, :vh, :vw])
+            j = 0
+            while j < len(tiles):   # picture-major: an overlapped picture's tiles of this chunk are one slice of the batch
+                p, e = tiles[j].picture, j + 1
+                while e < len(tiles) and tiles[e].picture == p:
+                    e += 1
+                if blend[p]:
+                    held[p].append((rec[j:e], [t.index for t in tiles[j:e]]))
+                    waiting[p] -= e - j
+                    if waiting[p] == 0:
+                        K.image_tiles_blend(held[p], grids[p], canvases[p], None if regions is None else regions[p])
+                        held[p] = []
+                j = e
+
     # ---- pooled tiles: the tiles of MANY pictures, of any sizes, share coding calls; every container keeps its own bytes
-    def encode_tiled_items(self, pictures, *args, tile=(512, 512), overlap=0, max_batch=None, **kwargs) -> List[bytes]:
+    def encode_tiled_items(self, pictures, *args, tile=(512, 512), overlap=0, max_batch=None, pad_to=1, **kwargs) -> List[bytes]:
         """N pictures ``[1, C, H, W]`` of ANY sizes with one C (uint8 in chw or hwc memory, or float32; host or device; mixed within a
-        call) -> their N containers, container k byte for byte ``self.encode_tiled(pictures[k], tile=tile, overlap=overlap)``.  The
+        call) -> their N containers, container k byte for byte ``self.encode_tiled(pictures[k], tile=tile, overlap=overlap, pad_to=pad_to)``.  The
         tiles of all pictures are pooled by size (utils.tiling.pool_tiles: the full tiles of every picture share one shape, the edge
         tiles a few more), a chunk of at most ``max_batch`` tiles is cut out of its uint8 pictures by ONE launch
         (nn.kernels.image_tiles_gather; float32 pictures: one copy per tile, and chunks of their own) and coded by one encode() call,
         whose string is split as in encode_items.  ``last_items_calls`` counts the encode() calls.  One encode_tiled per picture when
-        a coder cannot split, in training mode, or when the call brings arguments."""
-        from ...nn import kernels as K
+        a coder cannot split, in training mode, or when the call brings arguments.  With ``pad_to`` the tiles are pooled by their coded
+        size and cut with the edges replicated (``pad=True``); ``pad_to=tile`` makes the pool one size."""
         from ...utils import tiling
         pictures = list(pictures)
         for x in pictures:
@@ -750,37 +883,20 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         if len({x.shape[1] for x in pictures}) > 1:
             raise ValueError("the pictures of one call share their channel count")
         th, tw = self._tile_size(tile)
-        grids = [tiling.TileGrid(x.shape[2], x.shape[3], th, tw, overlap=overlap) for x in pictures]
+        grids = [tiling.TileGrid(x.shape[2], x.shape[3], th, tw, overlap=overlap, pad_to=pad_to) for x in pictures]
         framing = self._items_framing() if not (args or kwargs or self.training) else None
         if framing is None:
             out, calls = [], 0
             for x in pictures:
-                out.append(self.encode_tiled(x, *args, tile=tile, max_batch=max_batch, overlap=overlap, **kwargs))
+                out.append(self.encode_tiled(x, *args, tile=tile, max_batch=max_batch, overlap=overlap, pad_to=pad_to, **kwargs))
                 calls += self.last_items_calls
             self.last_items_calls = calls
             return out
         self.last_items_calls = 0
         pictures = [x if x.device == self.device else x.to(device=self.device) for x in pictures]   # each once, as it lies
-        strings = [[None] * len(g) for g in grids]
-        with torch.no_grad(), torch.cuda.device(self.device):
-            for dtype in (torch.uint8, torch.float32):
-                own = [p for p, x in enumerate(pictures) if x.dtype == dtype]
-                for chunk in tiling.pool_tiles([grids[p] for p in own], max_batch):
-                    refs = [t._replace(picture=own[t.picture]) for t in chunk.tiles]
-                    self.last_items_calls += 1
-                    if len(refs) == 1:
-                        p, k, y, x = refs[0]
-                        strings[p][k] = self.encode(pictures[p][:, :, y:y + chunk.h, x:x + chunk.w])
-                        continue
-                    if dtype == torch.uint8:
-                        batch = K.image_tiles_gather(pictures, refs, chunk.h, chunk.w)
-                    else:
-                        batch = torch.empty((len(refs), pictures[own[0]].shape[1], chunk.h, chunk.w), dtype=dtype, device=self.device)
-                        for j, (p, _, y, x) in enumerate(refs):
-                            batch[j].copy_(pictures[p][0, :, y:y + chunk.h, x:x + chunk.w])
-                    for (p, k, _, _), one in zip(refs, self._split_string(self.encode(batch), len(refs), framing)):
-                        strings[p][k] = one
-        return [tiling.pack_tiled(x.shape[1], g.H, g.W, g.th, g.tw, s, overlap=g.overlap) for x, g, s in zip(pictures, grids, strings)]
+        strings = self._encode_pooled(pictures, grids, framing, max_batch)
+        return [tiling.pack_tiled(x.shape[1], g.H, g.W, g.th, g.tw, s, overlap=g.overlap, pad_to=g.pad_to)
+                for x, g, s in zip(pictures, grids, strings)]
 
     def decode_tiled_items(self, containers, *args, output_dtype=torch.uint8, layout="chw", max_batch=None, **kwargs) -> List[torch.Tensor]:
         """N containers of encode_tiled / encode_tiled_items, of any picture and tile sizes and overlaps (read from each) -> their N
@@ -793,7 +909,8 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         its tiles stay resident, and a batch is freed only when every overlapped picture with a tile in it is written: at worst
         4 * C * sh * sw bytes per tile of ALL overlapped pictures of the call, on top of the results.  One decode_tiled per
         container when a coder cannot split, in training mode, or when the call brings arguments.  No ``region=``: decoding a part
-        of a picture stays decode_tiled's."""
+        of a picture stays decode_tiled's.  Edge-padded containers (BTL3; ``pad_to`` read from each, and free to differ within a call):
+        their tiles are pooled by coded size and cropped to their valid rectangles (the scatter with ``clip=True``)."""
         from ...nn import kernels as K
         from ...utils import tiling
         if "region" in kwargs:
@@ -811,64 +928,19 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                 calls += self.last_items_calls
             self.last_items_calls = calls
             return out
-        heads = [tiling.unpack_tiled_any(data) for data in containers]
-        grids = [tiling.TileGrid(H, W, th, tw, overlap) for _, H, W, th, tw, overlap, _ in heads]
-        strings = [head[6] for head in heads]
-        blend = [g.overlap != (0, 0) for g in grids]
-        # the planner's chunks of one size each, refined by what the strings say about themselves, then cut at max_batch
-        chunks = []
-        for size in tiling.pool_tiles(grids, None):
-            by_key = {}
-            for t in size.tiles:
-                segs = split_merged_bytes(strings[t.picture][t.index], num_segments=len(framing))
-                key = (heads[t.picture][0],) + tuple(c.item_shape(seg, **ctx) if hasattr(c, "item_shape") else None
-                                                     for (c, ctx), seg in zip(framing, segs))
-                by_key.setdefault(key, []).append(t)
-            for tiles in by_key.values():
-                step = max_batch or len(tiles)
-                chunks.extend((size.h, size.w, tiles[i:i + step]) for i in range(0, len(tiles), step))
+        heads = [tiling.unpack_tiled_full(data) for data in containers]
+        grids = [tiling.TileGrid(t.H, t.W, t.th, t.tw, t.overlap, t.pad_to) for t in heads]
         as_u8 = output_dtype == torch.uint8
         dtype = torch.uint8 if as_u8 else torch.float32
         self.last_items_calls = self.last_tiles_decoded = 0
         with torch.no_grad(), torch.cuda.device(self.device):
             canvases = []
-            for (C, H, W, *_rest) in heads:
+            for t in heads:
                 if layout == "hwc":
-                    canvases.append(torch.empty((1, H, W, C), dtype=dtype, device=self.device).permute(0, 3, 1, 2))
+                    canvases.append(torch.empty((1, t.H, t.W, t.channels), dtype=dtype, device=self.device).permute(0, 3, 1, 2))
                 else:
-                    canvases.append(torch.empty((1, C, H, W), dtype=dtype, device=self.device))
-            waiting = [len(g) if b else 0 for g, b in zip(grids, blend)]   # tiles an overlapped picture still lacks
-            held = [[] for _ in grids]                                    # its (batch view, tile indices) so far
-            for h, w, tiles in chunks:
-                self.last_items_calls += 1
-                self.last_tiles_decoded += len(tiles)
-                if len(tiles) == 1:
-                    rec = self.decode(strings[tiles[0].picture][tiles[0].index])
-                else:
-                    rec = self.decode(self._merge_strings([strings[t.picture][t.index] for t in tiles], framing))
-                C = heads[tiles[0].picture][0]
-                if rec.dim() != 4 or rec.shape[0] != len(tiles) or rec.shape[1] != C or rec.shape[2] < h or rec.shape[3] < w:
-                    raise ValueError(f"tiles of [{len(tiles)}, {C}, {h}, {w}] decoded to {tuple(rec.shape)}")
-                plain = [j for j, t in enumerate(tiles) if not blend[t.picture]]
-                if plain and as_u8:
-                    part = rec if len(plain) == len(tiles) else rec[torch.tensor(plain, device=rec.device)]
-                    K.image_tiles_scatter(part, canvases, [tiles[j] for j in plain], h, w)
-                elif plain:
-                    for j in plain:
-                        p, _, y, x = tiles[j]
-                        canvases[p][0, :, y:y + h, x:x + w].copy_(rec[j, :, :h, :w])
-                j = 0
-                while j < len(tiles):   # picture-major: an overlapped picture's tiles of this chunk are one slice of the batch
-                    p, e = tiles[j].picture, j + 1
-                    while e < len(tiles) and tiles[e].picture == p:
-                        e += 1
-                    if blend[p]:
-                        held[p].append((rec[j:e], [t.index for t in tiles[j:e]]))
-                        waiting[p] -= e - j
-                        if waiting[p] == 0:
-                            K.image_tiles_blend(held[p], grids[p], canvases[p])
-                            held[p] = []
-                    j = e
+                    canvases.append(torch.empty((1, t.channels, t.H, t.W), dtype=dtype, device=self.device))
+            self._decode_pooled(heads, grids, canvases, framing, max_batch, as_u8)
         return canvases
 
     def forward(self, data, *args, **kwargs):

@@ -709,12 +709,14 @@ def _tile_ref_table(pictures, refs, device):
     return table, torch.empty(len(refs) * _TILE_REF.itemsize, dtype=torch.uint8, device=device)
 
 
-def image_tiles_gather(pictures, refs, h, w):
+def image_tiles_gather(pictures, refs, h, w, pad=False):
     """Tiles of MANY pictures in one launch (basic_image_tiles_gather_u8_to_f32_dev, include/basic_hip.h section 8d).  ``pictures``: uint8
     ``[1, C, H, W]`` tensors on one GPU, of any sizes with one C, each read as it lies when it is contiguous or its memory is [H][W][C]
     (image_layout_of) and made contiguous otherwise; ``refs``: one ``(picture, tile index, y0, x0)`` per tile (utils.tiling.pool_tiles),
     ``picture`` an index into ``pictures``.  Returns float32 ``[len(refs), C, h, w]``, tile t equal to
-    ``pictures[p][..., y0:y0 + h, x0:x0 + w].float().div(255)``: what image_tiles_to_f32 gives for that picture and origin."""
+    ``pictures[p][..., y0:y0 + h, x0:x0 + w].float().div(255)``: what image_tiles_to_f32 gives for that picture and origin.
+    ``pad=True`` (basic_image_tiles_gather_pad_u8_to_f32_dev): a tile may leave its picture at the bottom and right -- its origin may
+    not -- and sample (r, q) of it is the picture's ``[min(y0 + r, H - 1), min(x0 + q, W - 1)]``: the last row and column replicated."""
     refs = list(refs)
     if not refs:
         raise ValueError("image_tiles_gather: no tiles")
@@ -730,17 +732,20 @@ def image_tiles_gather(pictures, refs, h, w):
     with torch.cuda.device(first.device):
         table, ws = _tile_ref_table(lie, refs, first.device)
         out = torch.empty((len(refs), C, int(h), int(w)), device=first.device, dtype=torch.float32)
-        _lib.check(_lib.lib().basic_image_tiles_gather_u8_to_f32_dev(table.ctypes.data, len(refs), C, int(h), int(w), ws.data_ptr(),
-                                                                     out.data_ptr(), _stream()))
+        L = _lib.lib()
+        gather = L.basic_image_tiles_gather_pad_u8_to_f32_dev if pad else L.basic_image_tiles_gather_u8_to_f32_dev
+        _lib.check(gather(table.ctypes.data, len(refs), C, int(h), int(w), ws.data_ptr(), out.data_ptr(), _stream()))
     del lie, ws   # enqueued: the allocator is stream-ordered
     return out
 
 
-def image_tiles_scatter(batch, canvases, refs, h, w):
+def image_tiles_scatter(batch, canvases, refs, h, w, clip=False):
     """The way back (basic_image_tiles_scatter_f32_to_u8_dev): the top-left h x w of reconstruction t of ``batch`` (float32
     ``[len(refs), C, sh, sw]`` on the GPU) as bytes (image_f32_to_u8's values) at ``(y0, x0)`` of ``canvases[picture]`` of ``refs[t]``; the
     canvases are uint8 ``[1, C, H, W]`` on the same GPU, contiguous or with [H][W][C] memory, and are written in place, bytes outside
-    the tiles keeping their value.  Tiles of one call must not intersect in a canvas.  One launch."""
+    the tiles keeping their value.  Tiles of one call must not intersect in a canvas.  One launch.  ``clip=True``
+    (basic_image_tiles_scatter_clip_f32_to_u8_dev): a tile may leave its canvas at the bottom and right -- its origin may not -- and only
+    the part of its h x w inside the canvas is written."""
     refs = list(refs)
     if not refs:
         raise ValueError("image_tiles_scatter: no tiles")
@@ -760,8 +765,10 @@ def image_tiles_scatter(batch, canvases, refs, h, w):
         lie[p] = (canvas, layout)
     with torch.cuda.device(batch.device):
         table, ws = _tile_ref_table(lie, refs, batch.device)
-        _lib.check(_lib.lib().basic_image_tiles_scatter_f32_to_u8_dev(batch.data_ptr(), batch.shape[2], batch.shape[3], C, int(h), int(w),
-                                                                      table.ctypes.data, len(refs), ws.data_ptr(), _stream()))
+        L = _lib.lib()
+        scatter = L.basic_image_tiles_scatter_clip_f32_to_u8_dev if clip else L.basic_image_tiles_scatter_f32_to_u8_dev
+        _lib.check(scatter(batch.data_ptr(), batch.shape[2], batch.shape[3], C, int(h), int(w), table.ctypes.data, len(refs), ws.data_ptr(),
+                           _stream()))
     del ws
     return canvases
 

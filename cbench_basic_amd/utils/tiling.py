@@ -17,6 +17,14 @@ the picture's edge.  A sample is covered by at most two tiles per axis; the doub
 tile is always longer than the overlap.  Such a picture's container is  b"BTL2"  <B channels> <I H> <I W> <I th> <I tw> <I oy> <I ox>
 <I n>,  then lengths and strings as above; with overlap (0, 0) the container is BTL1, byte for byte.
 
+Edge-padded tiles (``pad_to=(py, px)``, th % py == 0 and tw % px == 0; default (1, 1), none): the grid is the same -- no tile is added
+or moved, ``tile_rect`` stays the valid rectangle -- but an edge tile is CODED at ``coded_size(k)``, its valid h x w rounded up to
+multiples of py x px (never more than th x tw), the extra rows and columns replicating the picture's last row and column:
+``P_k[c, r, q] = image[c, min(y + r, H - 1), min(x + q, W - 1)]``.  A decoder crops every tile to its valid rectangle.  With
+``pad_to=(th, tw)`` every tile of every picture is th x tw.  Such a picture's container is  b"BTL3"  <B channels> <I H> <I W> <I th>
+<I tw> <I oy> <I ox> <I py> <I px> <I n>  (41 bytes), then lengths and strings as above; with pad_to (1, 1) the container is BTL1 / BTL2,
+byte for byte.
+
 Pure host code: no torch, no device.
 """
 import struct
@@ -26,6 +34,8 @@ MAGIC = b"BTL1"
 _HEAD = struct.Struct("<4sBIIIII")
 MAGIC2 = b"BTL2"
 _HEAD2 = struct.Struct("<4sBIIIIIII")
+MAGIC3 = b"BTL3"
+_HEAD3 = struct.Struct("<4sBIIIIIIIII")
 
 
 class TileGroup(NamedTuple):
@@ -59,16 +69,31 @@ def _overlap_pair(overlap):
     return pair
 
 
+def _pad_pair(pad_to):
+    """``pad_to`` -- an int or (py, px) -- as a pair of positive ints."""
+    try:
+        pair = (pad_to, pad_to) if isinstance(pad_to, int) else tuple(pad_to)
+    except TypeError:
+        pair = ()
+    if len(pair) != 2 or any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in pair):
+        raise ValueError(f"pad_to is a positive integer or (py, px), not {pad_to!r}")
+    return pair
+
+
 class TileGrid:
     """The tiles of an H x W picture cut into th x tw tiles (the edge tiles smaller) whose neighbours share ``overlap = (oy, ox)``
-    rows and columns (none by default)."""
+    rows and columns (none by default); ``pad_to = (py, px)``: the edge tiles are coded at their size rounded up to multiples of
+    py x px (``coded_size``), which changes no tile's place or valid rectangle."""
 
-    def __init__(self, H, W, th, tw, overlap=(0, 0)):
+    def __init__(self, H, W, th, tw, overlap=(0, 0), pad_to=(1, 1)):
         self.H, self.W = _positive_int("H", H), _positive_int("W", W)
         self.th, self.tw = _positive_int("th", th), _positive_int("tw", tw)
         self.oy, self.ox = self.overlap = _overlap_pair(overlap)
         if 2 * self.oy > self.th or 2 * self.ox > self.tw:
             raise ValueError(f"an overlap of {self.overlap} is more than half a {self.th} x {self.tw} tile")
+        self.py, self.px = self.pad_to = _pad_pair(pad_to)
+        if self.th % self.py or self.tw % self.px:
+            raise ValueError(f"pad_to {self.pad_to} does not divide a {self.th} x {self.tw} tile")
         self.sy, self.sx = self.th - self.oy, self.tw - self.ox   # the steps between the tiles' origins
         self.rows, self.cols = max(1, -(-(self.H - self.oy) // self.sy)), max(1, -(-(self.W - self.ox) // self.sx))
 
@@ -82,6 +107,11 @@ class TileGrid:
         i, j = divmod(k, self.cols)
         y, x = i * self.sy, j * self.sx
         return y, x, min(self.th, self.H - y), min(self.tw, self.W - x)
+
+    def coded_size(self, k):
+        """(ph, pw) at which tile k is coded: its valid h x w rounded up to multiples of ``pad_to``; at most th x tw."""
+        _, _, h, w = self.tile_rect(k)
+        return -(-h // self.py) * self.py, -(-w // self.px) * self.px
 
     def _bands(self, n, size, step, total, lo=0, hi=None):
         """Index ranges [a, b) of one axis within [lo, hi) that hold tiles of one size: the full ones, then the smaller last one."""
@@ -147,7 +177,7 @@ class PooledTile(NamedTuple):
 
 
 class TileChunk(NamedTuple):
-    """Tiles of one size (h, w), of any pictures: what one pooled coding call takes."""
+    """Tiles of one coded size (h, w), of any pictures: what one pooled coding call takes."""
     h: int
     w: int
     tiles: Tuple[PooledTile, ...]
@@ -158,14 +188,16 @@ def pool_tiles(grids: Sequence[TileGrid], max_batch=None) -> List[TileChunk]:
     picture are th x tw whatever the picture's size, and the edge tiles fall into a few more sizes.  The order is fixed: sizes in the
     order of their first appearance (pictures in order, a picture's tiles row-major), within a size picture-major and tile-major,
     cut into chunks of at most ``max_batch`` tiles (None / 0: one chunk per size).  So every tile of every picture is in exactly
-    one chunk, and there are ``sum over the sizes of ceil(count / max_batch)`` chunks."""
+    one chunk, and there are ``sum over the sizes of ceil(count / max_batch)`` chunks.  A tile's size is its ``coded_size``: the
+    valid size for a grid without padding, and with ``pad_to`` the rounded one, so that the edge tiles of padded grids fall into fewer
+    sizes -- with ``pad_to=(th, tw)`` into the one of the full tiles."""
     if max_batch is not None and (isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 0):
         raise ValueError(f"max_batch must be a positive integer or None, not {max_batch!r}")
     by_size = {}   # insertion-ordered: a size's first appearance
     for p, grid in enumerate(grids):
         for k in range(len(grid)):
-            y, x, h, w = grid.tile_rect(k)
-            by_size.setdefault((h, w), []).append(PooledTile(p, k, y, x))
+            y, x, _, _ = grid.tile_rect(k)
+            by_size.setdefault(grid.coded_size(k), []).append(PooledTile(p, k, y, x))
     out = []
     for (h, w), tiles in by_size.items():
         step = max_batch or len(tiles)
@@ -173,9 +205,10 @@ def pool_tiles(grids: Sequence[TileGrid], max_batch=None) -> List[TileChunk]:
     return out
 
 
-def pack_tiled(channels, H, W, th, tw, strings: Sequence[bytes], overlap=(0, 0)) -> bytes:
-    """The container of a picture's tile strings (row-major order): BTL1, or BTL2 when the tiles overlap."""
-    grid = TileGrid(H, W, th, tw, overlap)
+def pack_tiled(channels, H, W, th, tw, strings: Sequence[bytes], overlap=(0, 0), pad_to=(1, 1)) -> bytes:
+    """The container of a picture's tile strings (row-major order): BTL1, BTL2 when the tiles overlap, BTL3 when the edge tiles are
+    padded (``pad_to`` other than (1, 1))."""
+    grid = TileGrid(H, W, th, tw, overlap, pad_to)
     strings = [bytes(s) for s in strings]
     if len(strings) != len(grid):
         raise ValueError(f"{len(strings)} strings for {grid.rows} x {grid.cols} tiles")
@@ -183,32 +216,60 @@ def pack_tiled(channels, H, W, th, tw, strings: Sequence[bytes], overlap=(0, 0))
         raise ValueError(f"channels must be in 1..255, not {channels!r}")
     if max(H, W, th, tw, len(strings), *[len(s) for s in strings]) >= 1 << 32:
         raise ValueError("a field of the container does not fit 32 bits")
-    head = _HEAD.pack(MAGIC, channels, H, W, th, tw, len(strings)) if grid.overlap == (0, 0) else \
-        _HEAD2.pack(MAGIC2, channels, H, W, th, tw, grid.oy, grid.ox, len(strings))
+    if grid.pad_to != (1, 1):
+        head = _HEAD3.pack(MAGIC3, channels, H, W, th, tw, grid.oy, grid.ox, grid.py, grid.px, len(strings))
+    elif grid.overlap == (0, 0):
+        head = _HEAD.pack(MAGIC, channels, H, W, th, tw, len(strings))
+    else:
+        head = _HEAD2.pack(MAGIC2, channels, H, W, th, tw, grid.oy, grid.ox, len(strings))
     return b"".join([head,
                      struct.pack("<%dI" % len(strings), *[len(s) for s in strings])] + strings)
 
 
+class TiledPicture(NamedTuple):
+    """What a container states, and its tile strings in row-major order."""
+    channels: int
+    H: int
+    W: int
+    th: int
+    tw: int
+    overlap: Tuple[int, int]
+    pad_to: Tuple[int, int]
+    strings: List[bytes]
+
+
+def unpack_tiled_full(data) -> TiledPicture:
+    """A BTL1, BTL2 or BTL3 container as a TiledPicture; ValueError for anything that is not exactly one."""
+    return _unpack(data, (MAGIC, MAGIC2, MAGIC3))
+
+
 def unpack_tiled_any(data):
     """(channels, H, W, th, tw, (oy, ox), [tile strings]) of a BTL1 or BTL2 container; ValueError for anything that is not exactly one."""
+    t = _unpack(data, (MAGIC, MAGIC2))
+    return t.channels, t.H, t.W, t.th, t.tw, t.overlap, t.strings
+
+
+def _unpack(data, magics) -> TiledPicture:
     data = bytes(data)
-    if data[:4] == MAGIC:
-        head, overlapped = _HEAD, False
-    elif data[:4] == MAGIC2:
-        head, overlapped = _HEAD2, True
-    else:
+    if data[:4] not in magics:
         raise ValueError("not a tiled picture: wrong magic")
+    head = {MAGIC: _HEAD, MAGIC2: _HEAD2, MAGIC3: _HEAD3}[data[:4]]
     if len(data) < head.size:
         raise ValueError("truncated tiled picture: head cut short")
     fields = head.unpack_from(data)
     channels, H, W, th, tw = fields[1:6]
-    oy, ox = fields[6:8] if overlapped else (0, 0)
+    oy, ox = fields[6:8] if head is not _HEAD else (0, 0)
+    py, px = fields[8:10] if head is _HEAD3 else (1, 1)
     n = fields[-1]
     if min(channels, H, W, th, tw) < 1:
         raise ValueError("tiled picture: a dimension is zero")
     if 2 * oy > th or 2 * ox > tw:
         raise ValueError(f"tiled picture: an overlap of {(oy, ox)} is more than half a {th} x {tw} tile")
-    grid = TileGrid(H, W, th, tw, (oy, ox))
+    if min(py, px) < 1:
+        raise ValueError("tiled picture: pad_to is zero")
+    if th % py or tw % px:
+        raise ValueError(f"tiled picture: pad_to {(py, px)} does not divide a {th} x {tw} tile")
+    grid = TileGrid(H, W, th, tw, (oy, ox), (py, px))
     if n != len(grid):
         raise ValueError(f"tiled picture: {n} tiles stated, {grid.rows} x {grid.cols} expected")
     cur = head.size
@@ -224,7 +285,7 @@ def unpack_tiled_any(data):
         cur += L
     if cur != len(data):
         raise ValueError(f"tiled picture: {len(data) - cur} bytes after the last tile")
-    return channels, H, W, th, tw, (oy, ox), strings
+    return TiledPicture(channels, H, W, th, tw, (oy, ox), (py, px), strings)
 
 
 def unpack_tiled(data):

@@ -602,6 +602,28 @@ int basic_image_tiles_gather_u8_to_f32_dev(const basic_tile_ref *table /* HOST, 
 int basic_image_tiles_scatter_f32_to_u8_dev(const float *d_src, int sh, int sw, int channels, int th, int tw,
                                             const basic_tile_ref *table /* HOST */, int n, basic_tile_ref *d_table_ws,
                                             void *hip_stream);
+/* Edge-padded tiles: the two entries above for tiles of ph x pw that may leave their picture at the bottom and right (a tile
+ * coded at its size rounded up: cbench_basic_amd/utils/tiling.py, pad_to).  Same signatures, same host-checked table, same
+ * staging, one launch each, nothing allocated.  The origin of every row lies inside its picture: 0 <= y0 < img_h,
+ * 0 <= x0 < img_w.
+ *   gather_pad : d_dst[t][c][r][q] = picture[c][min(y0 + r, img_h - 1)][min(x0 + q, img_w - 1)] / 255 for r < ph, q < pw: the
+ *                picture's last row and column replicated into the part of the tile outside it.  A table in which no tile
+ *                leaves its picture gives, bit for bit, basic_image_tiles_gather_u8_to_f32_dev's output.
+ *   scatter_clip: writes the part of each tile's top-left ph x pw that lies inside its picture, and no other byte.
+ * Wide path: today's rule (float base 16-byte aligned, pw -- and sw -- multiples of 4, every row a 4-byte aligned picture with
+ * img_w and x0 multiples of 4, interleaved rows only with 3 or 4 channels).  Under it a run of four samples is wholly inside
+ * or wholly outside a picture row: an outside run of the gather is the row's last pixel in all four places (byte 3 of the
+ * row's last dword; pixel 3 of its last four interleaved pixels), rows at or beyond img_h read row img_h - 1, and the scatter
+ * skips outside runs and rows.  Otherwise the launch goes sample by sample and clamps, or tests, each sample.
+ * basic_image_tiles_last_path reports the path.
+ * BASIC_ERR_INVALID with a message, before any copy or launch: the refusals of the two entries above, with "the tile leaves
+ * the picture" replaced by "the tile's origin leaves the picture" (y0 >= img_h or x0 >= img_w in any row). */
+int basic_image_tiles_gather_pad_u8_to_f32_dev(const basic_tile_ref *table /* HOST, n entries */, int n, int channels,
+                                               int ph, int pw, basic_tile_ref *d_table_ws /* device, n entries */,
+                                               float *d_dst, void *hip_stream);
+int basic_image_tiles_scatter_clip_f32_to_u8_dev(const float *d_src, int sh, int sw, int channels, int ph, int pw,
+                                                 const basic_tile_ref *table /* HOST */, int n, basic_tile_ref *d_table_ws,
+                                                 void *hip_stream);
 
 /* ======================================================================================
  * 9. Persistent scan-line AR coding loop (csrc/scanline.hip): ONE launch walks all H*W coding steps of

@@ -1,0 +1,283 @@
+"""Edge-padded tiles through the codecs (``pad_to=``): every tile's string is EXACTLY the codec's own string of the padded tile, built
+here with torch index clamps; ``decompress_tiled`` is the crop-and-paste (or, with an overlap, the numpy blend of
+tests/tile_blend_exact.py) of the per-tile ``decompress``; the AR codecs, which refuse tiles whose sides are no multiples of 64, take a
+70 x 100 picture with ``pad_to=64``; pooled calls return the per-picture containers from the planner's number of calls.  The
+yardsticks -- the padded tiles, their strings and their reconstructions -- are computed once per case and left unchanged."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from cbench_basic_amd.utils.tiling import TileGrid, pool_tiles, unpack_tiled_full
+
+import tile_blend_exact as B
+
+pytestmark = pytest.mark.gpu
+
+H, W, T = 70, 100, 64
+KINDS = ["hyperprior-fused", "hyperprior-modules", "checkerboard", "basic-l0"]
+POOL = ((70, 100), (64, 64), (130, 50))
+
+
+@functools.lru_cache(maxsize=None)
+def _codec(kind):
+    from cbench_basic_amd.presets import basic_codec, hyperprior_codec, seed_synthetic_weights, topogroup_ar_codec
+    if kind.startswith("hyperprior"):
+        codec = hyperprior_codec()
+    elif kind == "checkerboard":
+        codec = topogroup_ar_codec("checkerboard")
+    else:
+        codec = basic_codec()
+    codec = seed_synthetic_weights(codec, seed=0).eval().cuda()
+    codec.update_state()
+    if kind == "hyperprior-modules":
+        codec.entropy_coder.use_fused_session = False
+    if kind == "basic-l0":
+        codec.set_complex_level(0)
+    return codec
+
+
+@functools.lru_cache(maxsize=None)
+def _picture(h=H, w=W):
+    """A smooth picture with some noise, uint8 [1, 3, h, w] on the host."""
+    g = torch.Generator().manual_seed(h * 1000 + w)
+    yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+    base = torch.stack([(yy / h + xx / w) / 2, (torch.sin(yy / 9) * torch.cos(xx / 13) + 1) / 2, (xx * yy) / (h * w)])
+    return (base + 0.1 * torch.rand(3, h, w, generator=g)).clamp(0, 1).mul(255).round().to(torch.uint8)[None]
+
+
+def _hwc(x):
+    return x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+
+
+def _padded(picture, grid, k):
+    """P_k: uint8 [1, C, ph, pw], P_k[c, r, q] = picture[0, c, min(y + r, H - 1), min(x + q, W - 1)]."""
+    y, x, _, _ = grid.tile_rect(k)
+    ph, pw = grid.coded_size(k)
+    iy = torch.arange(y, y + ph).clamp(max=grid.H - 1)
+    ix = torch.arange(x, x + pw).clamp(max=grid.W - 1)
+    return picture[:, :, iy[:, None], ix[None, :]].contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(kind, size=(H, W), pad=(T, T), overlap=0):
+    """Computed once per case and left unchanged: the picture, its grid, every tile's own string -- ``compress`` of the padded tile as
+    floats -- and every tile's own reconstruction, float32 [C, sh, sw] on the host."""
+    codec = _codec(kind)
+    picture = _picture(*size)
+    grid = TileGrid(size[0], size[1], T, T, overlap=overlap, pad_to=pad)
+    strings = [codec.compress(_padded(picture, grid, k).float().div(255)) for k in range(len(grid))]
+    recs = [codec.decompress(s).cpu()[0] for s in strings]
+    return picture, grid, strings, recs
+
+
+def _pasted(grid, recs):
+    """The crop-and-paste of abutting tiles, float32 [1, C, H, W]."""
+    out = torch.empty(1, recs[0].shape[0], grid.H, grid.W)
+    for k in range(len(grid)):
+        y, x, h, w = grid.tile_rect(k)
+        out[0, :, y:y + h, x:x + w] = recs[k][:, :h, :w]
+    return out
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_every_tile_string_is_the_codecs_own_string_of_the_padded_tile(kind):
+    from cbench_basic_amd.nn import kernels as K
+    codec = _codec(kind)
+    picture, grid, strings, recs = _reference(kind)
+    assert len(grid) == 4 and {grid.coded_size(k) for k in range(4)} == {(T, T)} and grid.tile_rect(3) == (64, 64, 6, 36)
+    data = codec.compress_tiled(picture.cuda(), tile=T, pad_to=T)
+    assert codec.last_items_calls == 1
+    full = unpack_tiled_full(data)
+    assert data[:4] == b"BTL3" and full.pad_to == (T, T) and full.overlap == (0, 0) and (full.channels, full.H, full.W, full.th, full.tw) == (3, H, W, T, T)
+    assert full.strings == strings
+    assert strings[1] == codec.compress(_padded(picture, grid, 1))            # the 8-bit padded tile: the same bytes
+    # any tile decodes alone; the picture is the crop-and-paste of the tiles' own reconstructions
+    want = _pasted(grid, recs)
+    got = codec.decompress_tiled(data, output_dtype=torch.float32)
+    assert codec.last_items_calls == 1 and codec.last_tiles_decoded == 4
+    assert got.dtype == torch.float32 and torch.equal(got.cpu(), want)
+    want_u8 = K.image_f32_to_u8(want.cuda())
+    for layout in ("chw", "hwc"):
+        got = codec.decompress_tiled(data, layout=layout)
+        assert got.dtype == torch.uint8 and K.image_layout_of(got) == layout and torch.equal(got, want_u8), (kind, layout)
+    if kind in ("checkerboard", "basic-l0"):          # as today: a 64 x 36 tile is refused by the coder itself
+        with pytest.raises(AssertionError, match="not aligned"):
+            codec.compress_tiled(picture, tile=T)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_bytes_do_not_depend_on_memory_order_device_dtype_or_max_batch(kind):
+    codec = _codec(kind)
+    picture, grid, strings, _ = _reference(kind)
+    want = codec.compress_tiled(picture, tile=T, pad_to=T)
+    assert unpack_tiled_full(want).strings == strings
+    floats = picture.float().div(255)
+    for form in (picture.cuda(), _hwc(picture), _hwc(picture).cuda(), floats, floats.cuda(), _hwc(floats).cuda()):
+        assert codec.compress_tiled(form, tile=T, pad_to=(T, T)) == want, (kind, form.dtype, form.device)
+        assert codec.last_items_calls == 1
+    for max_batch, calls in ((1, 4), (3, 2), (None, 1)):
+        for form in (picture.cuda(), floats.cuda()):
+            assert codec.compress_tiled(form, tile=T, pad_to=T, max_batch=max_batch) == want, (kind, max_batch)
+            assert codec.last_items_calls == calls, (kind, max_batch, codec.last_items_calls)
+        ref = codec.decompress_tiled(want)
+        assert torch.equal(codec.decompress_tiled(want, max_batch=max_batch), ref) and codec.last_items_calls == calls
+
+
+def test_pad_to_32_codes_the_edge_tiles_at_32_by_64():
+    codec = _codec("hyperprior-fused")
+    picture, grid, strings, recs = _reference("hyperprior-fused", pad=(32, 32))
+    assert [grid.coded_size(k) for k in range(4)] == [(64, 64), (64, 64), (32, 64), (32, 64)]
+    data = codec.compress_tiled(picture.cuda(), tile=T, pad_to=32)
+    assert codec.last_items_calls == 2
+    full = unpack_tiled_full(data)
+    assert full.pad_to == (32, 32) and full.strings == strings
+    assert strings[2] != _reference("hyperprior-fused")[2][2]                  # not the 64 x 64 tile's string
+    assert torch.equal(codec.decompress_tiled(data, output_dtype=torch.float32).cpu(), _pasted(grid, recs))
+    assert codec.last_items_calls == 2
+    assert codec.compress_tiled(picture.float().div(255), tile=T, pad_to=(32, 32)) == data
+    assert codec.compress_tiled(_hwc(picture), tile=T, pad_to=(32, 32), max_batch=1) == data and codec.last_items_calls == 4
+
+
+@pytest.mark.parametrize("kind", ["hyperprior-fused", "hyperprior-modules", "checkerboard"])
+def test_overlapped_padded_tiles_are_blended_from_their_top_left(kind):
+    from cbench_basic_amd.nn import kernels as K
+    codec = _codec(kind)
+    picture, grid, strings, recs = _reference(kind, overlap=16)
+    assert (grid.rows, grid.cols) == (2, 2) and grid.tile_rect(3) == (48, 48, 22, 52)
+    data = codec.compress_tiled(_hwc(picture).cuda(), tile=T, overlap=16, pad_to=T)
+    assert codec.last_items_calls == 1
+    full = unpack_tiled_full(data)
+    assert full.overlap == (16, 16) and full.pad_to == (T, T) and full.strings == strings
+    want = B.blend(grid, [r.numpy() for r in recs])
+    got = codec.decompress_tiled(data, output_dtype=torch.float32)
+    assert codec.last_items_calls == 1
+    assert np.array_equal(got.cpu().numpy()[0], want)
+    for layout in ("chw", "hwc"):
+        got = codec.decompress_tiled(data, layout=layout, max_batch=3)
+        assert K.image_layout_of(got) == layout and np.array_equal(got.cpu().numpy()[0], B.quantise(want))
+    part = codec.decompress_tiled(data, region=(64, 70, 70, 100), output_dtype=torch.float32)       # inside the corner tile, in no band
+    assert codec.last_tiles_decoded == 1 and np.array_equal(part.cpu().numpy()[0], want[:, 64:70, 70:100])
+    part = codec.decompress_tiled(data, region=(50, 70, 70, 100), output_dtype=torch.float32)       # a band: both its tiles
+    assert codec.last_tiles_decoded == 2 and np.array_equal(part.cpu().numpy()[0], want[:, 50:70, 70:100])
+    part = codec.decompress_tiled(data, region=(40, 3, 66, 51))
+    assert codec.last_tiles_decoded == 4 and np.array_equal(part.cpu().numpy()[0], B.quantise(want)[:, 40:66, 3:51])
+
+
+def test_a_region_equals_the_slice_and_decodes_only_its_tiles():
+    codec = _codec("hyperprior-fused")
+    picture, grid, strings, recs = _reference("hyperprior-fused")
+    data = codec.compress_tiled(picture, tile=T, pad_to=T)
+    whole_u8, whole = codec.decompress_tiled(data), codec.decompress_tiled(data, output_dtype=torch.float32)
+    for region, tiles in (((66, 70, 70, 100), 1), ((0, 0, 10, 10), 1), ((60, 10, 70, 20), 2), ((3, 60, 9, 99), 2), ((63, 63, 65, 65), 4), ((0, 0, H, W), 4)):
+        y0, x0, y1, x1 = region
+        for layout in ("chw", "hwc"):
+            part = codec.decompress_tiled(data, region=region, layout=layout)
+            assert codec.last_tiles_decoded == tiles and torch.equal(part, whole_u8[:, :, y0:y1, x0:x1]), (region, layout)
+        part = codec.decompress_tiled(data, region=region, output_dtype=torch.float32, max_batch=1)
+        assert codec.last_items_calls == tiles and torch.equal(part, whole[:, :, y0:y1, x0:x1]), region
+    for region in ((0, 0, H + 1, W), (5, 5, 5, 9), (H, 0, H + 1, 5)):
+        with pytest.raises(ValueError):
+            codec.decompress_tiled(data, region=region)
+
+
+def test_calls_with_arguments_take_one_call_per_padded_tile():
+    codec = _codec("hyperprior-modules")
+    picture, grid, strings, recs = _reference("hyperprior-modules")
+    data = codec.compress_tiled(picture, tile=T, pad_to=T, unused_argument=None)
+    assert codec.last_items_calls == 4 and unpack_tiled_full(data).strings == strings
+    got = codec.decompress_tiled(data, output_dtype=torch.float32, unused_argument=None)
+    assert codec.last_items_calls == 4 and torch.equal(got.cpu(), _pasted(grid, recs))
+    for pad in (0, 48, (64, 3), (128, 64)):
+        with pytest.raises(ValueError):
+            codec.compress_tiled(picture, tile=T, pad_to=pad)
+    with pytest.raises(ValueError):
+        codec.decompress_tiled(data[:29] + bytes([48]) + data[30:])                # py = 48 does not divide the tile
+    with pytest.raises(ValueError):
+        codec.decompress_tiled(data[:-1])
+
+
+@functools.lru_cache(maxsize=None)
+def _pool_reference(kind, pad):
+    codec = _codec(kind)
+    pictures = [_picture(h, w) for h, w in POOL]
+    containers = [codec.compress_tiled(p, tile=T, pad_to=pad) for p in pictures]
+    return pictures, containers, [codec.decompress_tiled(c) for c in containers], [codec.decompress_tiled(c, output_dtype=torch.float32) for c in containers]
+
+
+@pytest.mark.parametrize("kind,pad,calls", [("hyperprior-fused", 64, 1), ("hyperprior-modules", 64, 1), ("hyperprior-fused", 32, 2), ("checkerboard", 64, 1),
+                                            ("basic-l0", 64, 1)])
+def test_pooled_containers_and_pictures_equal_the_per_picture_padded_path(kind, pad, calls):
+    codec = _codec(kind)
+    pictures, want, want_u8, want_f32 = _pool_reference(kind, pad)
+    grids = [TileGrid(h, w, T, T, pad_to=pad) for h, w in POOL]
+    assert len(pool_tiles(grids)) == calls and len(pool_tiles([TileGrid(h, w, T, T) for h, w in POOL])) == 6
+    for k, (c, g) in enumerate(zip(want, grids)):         # the per-picture containers hold every tile's own string
+        full = unpack_tiled_full(c)
+        assert full.pad_to == g.pad_to and full.strings == [codec.compress(_padded(pictures[k], g, t)) for t in range(len(g))], (kind, k)
+    mixed = [pictures[0].cuda(), _hwc(pictures[1]), _hwc(pictures[2]).cuda()]
+    for max_batch in (None, 3):
+        n = len(pool_tiles(grids, max_batch))
+        assert codec.compress_tiled_items(mixed, tile=T, pad_to=pad, max_batch=max_batch) == want and codec.last_items_calls == n, (kind, max_batch)
+        back = codec.decompress_tiled_items(want, max_batch=max_batch)
+        assert codec.last_items_calls == n and codec.last_tiles_decoded == 8
+        assert all(torch.equal(a, b) for a, b in zip(back, want_u8)), (kind, max_batch)
+    back = codec.decompress_tiled_items(want, output_dtype=torch.float32, layout="hwc")
+    assert all(torch.equal(a, b) for a, b in zip(back, want_f32))
+    floats = [p.float().div(255) for p in pictures]
+    assert codec.compress_tiled_items([floats[0], mixed[1], floats[2].cuda()], tile=T, pad_to=pad) == want
+
+
+def test_a_pooled_decode_of_btl1_btl2_and_btl3_containers():
+    from cbench_basic_amd.codecs.grouped import GroupedVariableRateCodec
+    codec = _codec("hyperprior-fused")
+    a, b = _picture(70, 100), _picture(130, 50)
+    mix = [codec.compress_tiled(a, tile=T), codec.compress_tiled(a, tile=T, pad_to=T), codec.compress_tiled(b, tile=T, overlap=16),
+           codec.compress_tiled(b, tile=T, overlap=16, pad_to=(32, 64)), codec.compress_tiled(b, tile=T, pad_to=32)]
+    assert [c[:4] for c in mix] == [b"BTL1", b"BTL3", b"BTL2", b"BTL3", b"BTL3"]
+    for kw in (dict(), dict(output_dtype=torch.float32), dict(layout="hwc", max_batch=2)):
+        single = {k: v for k, v in kw.items() if k != "max_batch"}
+        want = [codec.decompress_tiled(c, **single) for c in mix]
+        back = codec.decompress_tiled_items(mix, **kw)
+        assert all(torch.equal(x, y) for x, y in zip(back, want)), kw
+    group = GroupedVariableRateCodec([codec])
+    assert group.compress_tiled(a, tile=T, pad_to=T) == mix[1]
+    assert group.compress_tiled_items([a], tile=T, pad_to=T) == mix[1:2]
+
+
+@pytest.mark.parametrize("pool,overlap", [(0, 0), (3, 0), (2, 16)])
+def test_harness_logs_per_item_what_compress_tiled_with_pad_to_gives(pool, overlap, tmp_path, monkeypatch):
+    from cbench_basic_amd.benchmark import BasicLosslessCompressionBenchmark, PytorchBatchedDistortion
+    from cbench_basic_amd.benchmark.metrics import MetricLogger
+    codec = _codec("hyperprior-fused")
+    pictures = [_picture(h, w) for h, w in POOL]
+    want = [len(codec.compress_tiled(p, tile=T, overlap=overlap, pad_to=T)) for p in pictures]
+    assert want != [len(codec.compress_tiled(p, tile=T, overlap=overlap)) for p in pictures]
+    log = []
+    update = MetricLogger.update
+
+    def spy(self, **kwargs):
+        log.append(kwargs)
+        return update(self, **kwargs)
+    monkeypatch.setattr(MetricLogger, "update", spy)
+    bench = BasicLosslessCompressionBenchmark(codec, pictures, distortion_metric=PytorchBatchedDistortion(metrics="psnr"), output_dir=str(tmp_path),
+                                              testing_tile=T, testing_tile_overlap=overlap, testing_tile_pool=pool, testing_tile_pad=T,
+                                              metrics_on_uint8=True)
+    assert bench.testing_tile_pad == (T, T)
+    bench.run_benchmark(ignore_exist_metrics=True)
+    bench.close()
+    assert [u["compressed_length"] for u in log if "compressed_length" in u] == want
+    assert len([u["psnr"] for u in log if "psnr" in u]) == 3
+
+
+def test_harness_refusals():
+    from cbench_basic_amd.benchmark import BasicLosslessCompressionBenchmark
+    codec = _codec("hyperprior-fused")
+    for kw in (dict(testing_tile_pad=64), dict(testing_tile=64, testing_tile_pad=48), dict(testing_tile=(64, 32), testing_tile_pad=(32, 64)),
+               dict(testing_tile=64, testing_tile_pad=0), dict(testing_tile=64, testing_tile_pad=(32, 32, 32))):
+        with pytest.raises(ValueError):
+            BasicLosslessCompressionBenchmark(codec, [_picture()], **kw)
+    ok = BasicLosslessCompressionBenchmark(codec, [_picture()], testing_tile=(64, 32), testing_tile_pad=(32, 16))
+    assert ok.testing_tile_pad == (32, 16)
+    assert BasicLosslessCompressionBenchmark(codec, [_picture()], testing_tile=64).testing_tile_pad is None

@@ -85,6 +85,9 @@ def main(argv=None):
     ap.add_argument("--tile-overlap", type=int, nargs="+", default=None, metavar=("OY", "OX"),
                     help="testing_tile_overlap: neighbouring tiles share OY rows and OX columns (OX = OY when omitted; at most half a tile) and "
                          "decompress_tiled cross-fades the seams (needs --tile)")
+    ap.add_argument("--tile-pad", type=int, nargs="+", default=None, metavar=("PY", "PX"),
+                    help="testing_tile_pad: code the edge tiles at their size rounded up to multiples of PY x PX (PX = PY when omitted; must "
+                         "divide the tile), the picture's last row and column replicated; decompress_tiled crops (needs --tile)")
     ap.add_argument("--tile-pool", type=int, default=0, metavar="N",
                     help="testing_tile_pool: code up to N consecutive pictures, of any sizes, per call, the tiles of all of them pooled "
                          "into shared coding calls (compress_tiled_items / decompress_tiled_items); every picture keeps its own container "
@@ -135,6 +138,15 @@ def main(argv=None):
             ap.error("--tile-overlap is at most half a tile")
     else:
         args.tile_overlap = (0, 0)
+    if args.tile_pad is not None:
+        if args.tile is None:
+            ap.error("--tile-pad needs --tile")
+        if len(args.tile_pad) > 2 or min(args.tile_pad) < 1:
+            ap.error("--tile-pad takes PY [PX], positive")
+        args.tile_pad = (args.tile_pad[0], args.tile_pad[-1])
+        if args.tile[0] % args.tile_pad[0] or args.tile[1] % args.tile_pad[1]:
+            ap.error("--tile-pad must divide the tile")
+    pad = {} if args.tile_pad is None else dict(pad_to=args.tile_pad)
     if args.tile_pool < 0:
         ap.error("--tile-pool must be >= 0")
     if args.tile_pool:
@@ -173,9 +185,9 @@ def main(argv=None):
 
     def warm(c):   # one item through the route the pass takes
         if args.tile_pool > 1:   # the first pooled call: the batch shapes the pass will meet
-            c.decompress_tiled_items(c.compress_tiled_items(batches[:args.tile_pool], tile=args.tile, overlap=args.tile_overlap))
+            c.decompress_tiled_items(c.compress_tiled_items(batches[:args.tile_pool], tile=args.tile, overlap=args.tile_overlap, **pad))
         elif args.tile is not None:
-            c.decompress_tiled(c.compress_tiled(batches[0].to("cuda"), tile=args.tile, overlap=args.tile_overlap))
+            c.decompress_tiled(c.compress_tiled(batches[0].to("cuda"), tile=args.tile, overlap=args.tile_overlap, **pad))
         else:
             c.decompress(c.compress(batches[0].to("cuda")))
     warm_chunks = []
@@ -201,7 +213,7 @@ def main(argv=None):
                                               testing_complexity_levels=args.complexity_levels,
                                               testing_variable_rate_levels=args.rate_levels, output_dir=args.out,
                                               num_testing_workers=args.workers, testing_coalesce_items=args.coalesce, testing_tile=args.tile, testing_tile_overlap=args.tile_overlap,
-                                              testing_tile_pool=args.tile_pool,
+                                              testing_tile_pool=args.tile_pool, testing_tile_pad=args.tile_pad,
                                               codec_builder=(lambda: presets.seed_synthetic_weights(builders[args.codec](), seed=0)) if args.workers > 1 else None)
     if args.workers > 1 and args.warmup:   # the replicas' one-time costs too, one replica at a time (HIP-graph capture)
         pool = bench._worker_pool(batches[0], batch=max((len(c) for c in warm_chunks), default=None))
