@@ -2091,8 +2091,8 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
         }
         const int threads = 64 * ph.waves, tile_pos = 32 * ph.waves;  // one position per half-wave lane
         const TileShape ts = tile_shape(g.mh, g.mw, tile_pos);
-        const int tw = ts.tw, th = ts.th;
-        int tb = ts.tb;
+        const int tw = ts.tw;
+        int th = ts.th, tb = ts.tb;
         const bool first_layer_path = ch.mt == 4 && ch.nsplit == 1 && ph.waves == 8 && ph.kh == 5 && ph.kw == 5 &&
                                       ph.cin_pad == kCK && kCK == 4 && ch.cout == 128 && p->d_gammaT;
         g.ph = (th - 1) * g.s_in + ph.span_y;
@@ -2102,7 +2102,7 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
         // (measured: pays for the 8-wave 25-tap convolutions, +1..1.5 %; the wider rows cost the few-tap launches more than they save)
         g.patch4 = (ph.waves == 8 && !first_layer_path && in_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0) ? 1 : 0;
         g.pwp = g.patch4 ? (g.pw + 3 + 3) / 4 * 4 : (g.pw | 1);
-        const int punit = g.patch4 ? 4 : 1;
+        int punit = g.patch4 ? 4 : 1;
         const int mtp = mtile_pitch(ch.mt);
         const int wl_floats = g.ntaps * kCK * 32 * mtp, gam_floats = 32 * 32 * mtp;
         const int wl_pad = ((wl_floats > gam_floats ? wl_floats : gam_floats) + 4 * threads - 1) / (4 * threads) * (4 * threads);
@@ -2113,7 +2113,22 @@ extern "C" int basic_conv_forward_dev(const basic_conv_plan *p, const float *d_i
         };
         // the patch must fit the gather descriptors and both stage buffers the LDS
         const int slots_avail = ph.kwb ? kPSlotsFused : patch_slots(ch.mt);
-        while (tb > 1 && (patch_slots_needed(tb) > slots_avail || lds_need(tb) > 160 * 1024)) tb >>= 1;
+        auto too_large = [&](int tbv) { return patch_slots_needed(tbv) > slots_avail || lds_need(tbv) > 160 * 1024; };
+        while (tb > 1 && too_large(tb)) tb >>= 1;
+        // A narrow m-grid makes tile_shape() a column (2 x 128, 8 x 32, ...), whose patch has (th - 1) * s_in + span_y rows and
+        // can exceed both limits even with one image per tile.  Only there -- tb == 1 and still too large, where this
+        // function used to return an error, so every launch that fitted keeps its tile -- first give up the 16-byte patch
+        // rows (3 to 6 columns of padding per row), then halve the tile height: the lanes past tw * th positions are dead
+        // (lane_live in the kernels: they recompute a live lane's position and store nothing).
+        if (tb == 1 && too_large(1) && g.patch4) {
+            g.patch4 = 0;
+            punit = 1;
+            g.pwp = g.pw | 1;
+        }
+        while (tb == 1 && th > 1 && too_large(1)) {
+            th >>= 1;
+            g.ph = (th - 1) * g.s_in + ph.span_y;
+        }
         g.tw_log = ilog2(tw); g.th_log = ilog2(th); g.tb_log = ilog2(tb);
         g.tiles_y = (g.mh + th - 1) / th;
         g.tiles_x = (g.mw + tw - 1) / tw;

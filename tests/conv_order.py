@@ -176,7 +176,7 @@ def sensitive(shape, generator_seed):
 
 def case_data(name):
     """(Layer, x [BATCH, cin, H, W]) of a case: order-sensitive activations, weights scaled as a trained layer's
-    (test_gpu_conv_paths._layer(integer=False))."""
+    (conv_ref._layer(integer=False))."""
     c = CASES[name]
     rng = np.random.default_rng(seed(name, "order"))
     wshape = (c.cin, c.cout, c.k, c.k) if c.tr else (c.cout, c.cin, c.k, c.k)

@@ -70,7 +70,7 @@ def test_fma32_is_exactly_rounded():
 
 
 def _int_layer(name):
-    """The integer data of test_gpu_conv_paths._layer(integer=True) at the case's shape: |x| <= 15, |w| <= 7, |b| <= 64."""
+    """The integer data of conv_ref._layer(integer=True) at the case's shape: |x| <= 15, |w| <= 7, |b| <= 64."""
     c = co.CASES[name]
     g = torch.Generator().manual_seed(co.seed(name, "int"))
     wshape = (c.cin, c.cout, c.k, c.k) if c.tr else (c.cout, c.cin, c.k, c.k)

@@ -40,7 +40,8 @@ def test_tables_match_oracle(setup):
     assert oracle.gc[0].shape[0] == 64 and oracle.gc[2][0] == -1 and oracle.gc[1][0] == 5
 
 
-@pytest.mark.parametrize("shape", [(1, 3, 64, 64), (2, 3, 128, 96), (1, 3, 256, 256)])
+@pytest.mark.parametrize("shape", [(1, 3, 64, 64), (2, 3, 128, 96), (1, 3, 256, 256),
+                                   (1, 3, 256, 64), (2, 3, 192, 64)])   # the last two: tall pictures (g_a layer 3 at 64 x 16 and 48 x 16)
 def test_transforms_and_symbols(setup, shape):
     codec, oracle = setup
     ec = codec.entropy_coder
@@ -86,7 +87,8 @@ def test_transforms_and_symbols(setup, shape):
 
 
 @pytest.mark.parametrize("shape", [(1, 3, 64, 64), (3, 3, 64, 96), (2, 3, 192, 128), (5, 3, 64, 64), (1, 3, 128, 256), (4, 3, 128, 64),
-                                   (1, 3, 70, 93), (2, 3, 129, 67)])   # the last two: sizes no layer divides evenly
+                                   (1, 3, 70, 93), (2, 3, 129, 67),    # these two: sizes no layer divides evenly
+                                   (1, 3, 256, 64), (2, 3, 192, 64)])  # tall pictures: column-shaped conv tiles
 def test_compress_decompress_vs_oracle(setup, shape):
     from oracle.codec_oracle import psnr
     codec, oracle = setup

@@ -107,6 +107,52 @@ def test_every_tile_string_is_the_codecs_own_string_of_the_padded_tile(kind):
             codec.compress_tiled(picture, tile=T)
 
 
+TALL = ((256, 296), 256)   # picture and tile: the edge tile, 256 x 40, is coded at 256 x 64 -- a tall, narrow picture for every conv layer
+
+
+@functools.lru_cache(maxsize=None)
+def _tall_reference(size=TALL[0]):
+    """As _reference, with tiles of 256 padded to multiples of 64."""
+    codec = _codec("hyperprior-fused")
+    picture = _picture(*size)
+    grid = TileGrid(size[0], size[1], TALL[1], TALL[1], pad_to=(T, T))
+    strings = [codec.compress(_padded(picture, grid, k).float().div(255)) for k in range(len(grid))]
+    return picture, grid, strings, [codec.decompress(s).cpu()[0] for s in strings]
+
+
+def test_a_tile_coded_at_256_by_64_has_the_codecs_own_string_of_the_padded_tile():
+    codec = _codec("hyperprior-fused")
+    picture, grid, strings, recs = _tall_reference()
+    assert len(grid) == 2 and [grid.coded_size(k) for k in range(2)] == [(256, 256), (256, 64)] and grid.tile_rect(1) == (0, 256, 256, 40)
+    data = codec.compress_tiled(picture.cuda(), tile=TALL[1], pad_to=T)
+    assert codec.last_items_calls == 2
+    full = unpack_tiled_full(data)
+    assert data[:4] == b"BTL3" and full.pad_to == (T, T) and (full.H, full.W, full.th, full.tw) == TALL[0] + (TALL[1], TALL[1])
+    assert full.strings == strings
+    assert strings[1] == codec.compress(_padded(picture, grid, 1))            # the 8-bit padded tile: the same bytes
+    got = codec.decompress_tiled(data, output_dtype=torch.float32)
+    assert codec.last_items_calls == 2 and codec.last_tiles_decoded == 2
+    assert torch.equal(got.cpu(), _pasted(grid, recs))
+
+
+def test_pooled_pictures_whose_grids_share_the_256_by_64_tile():
+    codec = _codec("hyperprior-fused")
+    sizes = (TALL[0], (250, 50))
+    pictures = [_picture(h, w) for h, w in sizes]
+    grids = [TileGrid(h, w, TALL[1], TALL[1], pad_to=(T, T)) for h, w in sizes]
+    assert [[g.coded_size(k) for k in range(len(g))] for g in grids] == [[(256, 256), (256, 64)], [(256, 64)]]
+    assert len(pool_tiles(grids)) == 2                        # one call of the 256 x 256 tile, one of both 256 x 64 tiles
+    want = [codec.compress_tiled(p, tile=TALL[1], pad_to=T) for p in pictures]
+    assert unpack_tiled_full(want[0]).strings == _tall_reference()[2]
+    assert unpack_tiled_full(want[1]).strings == _tall_reference(sizes[1])[2]
+    assert codec.compress_tiled_items([pictures[0].cuda(), _hwc(pictures[1])], tile=TALL[1], pad_to=T) == want
+    assert codec.last_items_calls == 2
+    back = codec.decompress_tiled_items(want, output_dtype=torch.float32)
+    assert codec.last_items_calls == 2 and codec.last_tiles_decoded == 3
+    for k, (g, b) in enumerate(zip(grids, back)):
+        assert torch.equal(b.cpu(), _pasted(g, _tall_reference(sizes[k])[3])), k
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_bytes_do_not_depend_on_memory_order_device_dtype_or_max_batch(kind):
     codec = _codec(kind)
