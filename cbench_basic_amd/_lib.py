@@ -63,6 +63,8 @@ _SIGNATURES = {
     "basic_lanes_pack_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "basic_group_lanes_pack_dev": (_I, [_P, _P, _I, _L, _P, _I, _I, _P, _P, _P]),
     "basic_gc_quantize_index_dev": (_I, [_P, _P, _L, _P, _I, _F, _P, _P, _P, _P]),
+    "basic_gc_quantize_index_q_dev": (_I, [_P, _P, _L, _L, _P, _I, _P, _I, _F, _P, _P, _P, _P]),
+    "basic_gc_dequantize_q_dev": (_I, [_P, _L, _L, _P, _I, _P, _P]),
     "basic_eb_quantize_index_dev": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "basic_eb_dequantize_dev": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "basic_i32_to_f32_dev": (_I, [_P, _L, _P, _P]),
@@ -70,6 +72,7 @@ _SIGNATURES = {
     "basic_pgm_gauss_index_group_dev": (_I, [_P, _I, _I, _I, _P, _L, _P, _I, _P, _L, _L, _P]),
     "basic_pgm_gauss_scatter_group_dev": (_I, [_P, _P, _I, _I, _I, _P, _L, _L, _L, _P, _P]),
     "basic_gauss_nll_per_image_dev": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P]),
+    "basic_gauss_nll_per_image_q_dev": (_I, [_P, _P, _I, _I, _I, _P, _I, _F, _F, _P, _P]),
     "basic_eb_nll_per_image_dev": (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),
     "basic_conv_plan_create": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P]),
     "basic_conv_plan_out_hw": (_I, [_P, _I, _I, _P, _P]),
@@ -97,6 +100,7 @@ _SIGNATURES = {
     "basic_hp_decode_images_u8": (_I, [_P, _P, _L, _I, _P, _I, _L, _P]),
     "basic_hp_session_set_rans_waves": (_I, [_P, _I]),
     "basic_hp_session_set_stream_lanes": (_I, [_P, _I]),
+    "basic_hp_session_set_qsteps": (_I, [_P, _P, _I]),
     "basic_hp_session_set_transform_token": (_I, [_P, _I]),
     "basic_hp_session_destroy": (None, [_P]),
     "basic_conv_plan_destroy": (None, [_P]),

@@ -58,7 +58,7 @@ class BasicLosslessCompressionBenchmark:
                  testing_complexity_levels=None, force_testing_device="cuda", output_dir=None, num_repeats=1,
                  num_testing_workers=0, codec_builder=None, worker_transform_token=None, testing_coalesce_items=0,
                  metrics_on_uint8=False, on_reconstruction=None, testing_tile=None, testing_tile_overlap=0, testing_tile_pool=0,
-                 testing_tile_pad=None, **kwargs):
+                 testing_tile_pad=None, testing_qsteps=None, **kwargs):
         self.codec = codec
         self.dataloader = dataloader
         self.distortion_metric = distortion_metric
@@ -132,6 +132,20 @@ class BasicLosslessCompressionBenchmark:
                 raise ValueError(f"testing_tile_pad {testing_tile_pad} does not divide a {testing_tile} tile")
         self.testing_tile_pad = testing_tile_pad
         self._tile_pad = {} if testing_tile_pad is None else dict(pad_to=testing_tile_pad)
+        # quantiser steps ("Quantiser step"): one pass over the dataset per step through compress_q / decompress_q,
+        # level prefix q<step>; the steps are the rate axis, as the variable-rate levels are for a codec that has them
+        from ..utils.qstep import check_qsteps
+        self.testing_qsteps = [float(q) for q in (testing_qsteps or [])]
+        for q in self.testing_qsteps:
+            check_qsteps(q)
+        if self.testing_qsteps:
+            for name, on in (("testing_variable_rate_levels", bool(self.testing_variable_rate_levels)),
+                             ("testing_complexity_levels", bool(self.testing_complexity_levels)),
+                             ("testing_coalesce_items", self.testing_coalesce_items > 1), ("testing_tile", testing_tile is not None),
+                             ("nn_codec_use_forward_pass", bool(nn_codec_use_forward_pass))):
+                if on:
+                    raise ValueError(f"testing_qsteps does not combine with {name}: the step is a knob of compress_q / decompress_q alone")
+        self._qstep = None
         self._level_prefix = ""
         self._pictures = {}
         self._pool = None
@@ -201,6 +215,8 @@ class BasicLosslessCompressionBenchmark:
         return self._to_f32(data_target) if self.metrics_on_uint8 else data_target
 
     def _compress(self, codec, data):
+        if self._qstep is not None:
+            return codec.compress_q(data, self._qstep)
         if self.testing_tile is None:
             return codec.compress(data)
         if not isinstance(data, torch.Tensor) or data.dim() != 4 or data.shape[0] != 1:
@@ -209,6 +225,8 @@ class BasicLosslessCompressionBenchmark:
         return codec.compress_tiled(data, tile=self.testing_tile, overlap=self.testing_tile_overlap, **self._tile_pad)
 
     def _decompress(self, codec, compressed):
+        if self._qstep is not None:
+            return codec.decompress_q(compressed, output_dtype=torch.uint8 if self.metrics_on_uint8 else None)
         if self.testing_tile is not None:
             return codec.decompress_tiled(compressed, output_dtype=torch.uint8 if self.metrics_on_uint8 else None)
         return codec.decompress(compressed, output_dtype=torch.uint8) if self.metrics_on_uint8 else codec.decompress(compressed)
@@ -528,6 +546,8 @@ class BasicLosslessCompressionBenchmark:
     def run_testing(self, *args, **kwargs):
         metrics, metrics_2d = OrderedDict(), OrderedDict()
         vr, vc = self.testing_variable_rate_levels, self.testing_complexity_levels
+        # the rate axis: (rate level, quantiser step) pairs -- the codec's own levels, or the steps (never both: __init__)
+        axis = [(r, None) for r in vr] or [(None, q) for q in self.testing_qsteps]
         if hasattr(self.codec, "eval"):
             self.codec.eval()
         if self.force_testing_device and hasattr(self.codec, "to"):
@@ -535,7 +555,8 @@ class BasicLosslessCompressionBenchmark:
         for _ in range(self.num_repeats):
             for ci, clevel in enumerate(vc if vc else [None]):
                 rate_pts, distortion_pts = [], []
-                for ri, rlevel in enumerate(vr if vr else [None]):
+                for ri, (rlevel, qstep) in enumerate(axis if axis else [(None, None)]):
+                    self._qstep = qstep
                     if clevel is not None:
                         self.codec.set_complex_level(clevel)
                     if rlevel is not None:
@@ -545,15 +566,16 @@ class BasicLosslessCompressionBenchmark:
                     self.codec.update_state()
                     if self.distortion_metric is not None:
                         self.distortion_metric.reset()
-                    self._level_prefix = "_".join(([f"sclevel{clevel}"] if clevel is not None else []) + ([f"vrlevel{rlevel}"] if rlevel is not None else []))
+                    rate_prefix = [f"vrlevel{rlevel}"] if rlevel is not None else [f"q{qstep:g}"] if qstep is not None else []
+                    self._level_prefix = "_".join(([f"sclevel{clevel}"] if clevel is not None else []) + rate_prefix)
                     current = self._run_dataset()
                     if self.distortion_metric is not None:
                         current.update(**self.distortion_metric.collect_metrics())
                     prefixes = []
                     if clevel is not None:
                         prefixes.append(f"sclevel{clevel}")
-                    if rlevel is not None:
-                        prefixes.append(f"vrlevel{rlevel}")
+                    if rate_prefix:
+                        prefixes.extend(rate_prefix)
                         bj = self.testing_variable_rate_bj_delta_metric
                         if bj is not None:
                             rn, dn = bj.collect_metric_names
@@ -574,11 +596,12 @@ class BasicLosslessCompressionBenchmark:
                                 metrics_2d[prefix][key] = value
                 # BD metric over this complexity level's rate points (needs at least 4 points, :979-992)
                 bj = self.testing_variable_rate_bj_delta_metric
-                if bj is not None and len(vr) > 3 and len(rate_pts) == len(vr):
+                if bj is not None and len(axis) > 3 and len(rate_pts) == len(axis):
                     bj_prefix = f"sclevel{ci}_" if vc else ""
                     value = bj((rate_pts, distortion_pts))[bj.name]
                     metrics[bj_prefix + bj.name] = value
                     metrics_2d[prefix][bj.name] = value
+        self._qstep = None
         if metrics_2d and self.output_dir:
             self.save_metrics(metric_file=os.path.join(self.output_dir, "metrics_2d.csv"),
                               metric_data=list(metrics_2d.values()), names=list(metrics_2d.keys()), raw=False)

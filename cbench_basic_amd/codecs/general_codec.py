@@ -29,6 +29,23 @@ class GeneralCodec(HotPathModule, CodecInterface, VariableRateCodecInterface, Va
         with self.profiler.start_time_profile("time_decompress_entropy_coder"):
             return self.entropy_coder.decode(data, *args, prior=None, **kwargs)
 
+    def compress_q(self, data, qstep, *args, **kwargs):
+        """``compress`` under a quantiser step of the y latent (INTEGRATION.md "Quantiser step"; the hyperprior codec's rate knob,
+        not part of the reference's codec interface): ``qstep`` is one step for the batch or one per image, finite and in
+        [2^-4, 2^6].  -> the container of utils/qstep.py: b"BQS1", uint32 LE n, n float32 LE steps, then exactly what
+        ``entropy_coder.encode(data, qstep=qstep)`` returned -- at step 1 that is ``compress(data)`` byte for byte."""
+        from ..utils.qstep import check_qsteps, pack_qsteps
+        steps = check_qsteps(qstep, data.shape[0])
+        return pack_qsteps(steps, self.compress(data, *args, qstep=steps, **kwargs))
+
+    def decompress_q(self, data, *args, output_dtype=None, **kwargs):
+        """A container of compress_q -> the reconstruction, as ``decompress`` gives it (``output_dtype`` as there).  The steps are
+        read from the container; a wrong magic, a short buffer or a step count that is neither 1 nor the batch of the inner
+        stream is a ValueError raised before anything is launched."""
+        from ..utils.qstep import unpack_qsteps
+        steps, inner = unpack_qsteps(data)
+        return self.decompress(inner, *args, output_dtype=output_dtype, qstep=steps, **kwargs)
+
     def compress_items(self, items, *args, max_batch=None, **kwargs):
         """N batch-1 items -> exactly ``[self.compress(x) for x in items]``, items of one shape coded in shared batches
         (entropy coder's ``encode_items``; not part of the reference's codec interface)."""

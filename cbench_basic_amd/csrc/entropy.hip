@@ -67,6 +67,81 @@ __global__ void gc_quantize_index_kernel(const float *__restrict__ y, const floa
     }
 }
 
+// ---- quantiser step (include/basic_hip.h, "Quantiser step"): the division and the multiply of the format, each one correctly
+// rounded fp32 operation -- no reciprocal, nothing contracted into a neighbour.  The build states
+// -fhip-fp32-correctly-rounded-divide-sqrt itself, so the division does not rest on the compiler's default either.
+__device__ __forceinline__ float step_div(float a, float step)
+{
+#pragma clang fp contract(off)
+    return __fdiv_rn(a, step);
+}
+__device__ __forceinline__ float step_mul(float q, float step)
+{
+#pragma clang fp contract(off)
+    return __fmul_rn(q, step);
+}
+
+// gc_quantize_index_kernel with a quantiser step per image: element i of image b = i / per_image is coded as rint(y / step[b])
+// under the table entry of max(scale, bound) / step[b].  Same streaming shape as the step-less kernel: flat grid-stride over
+// B * per_image, full-width coalesced loads and stores.  The image of an element comes from ONE 64-bit division per
+// grid-stride chunk, uniform over the workgroup (its chunk's first element), and a walk over the image boundaries that fall
+// inside the chunk (none or one unless per_image < 256).
+__global__ void gc_quantize_index_q_kernel(const float *__restrict__ y, const float *__restrict__ scales, int64_t n, int64_t per_image,
+                                           const float *__restrict__ steps, int n_steps, const float *__restrict__ table,
+                                           int table_len, float bound, int32_t *__restrict__ symbols,
+                                           int32_t *__restrict__ indexes, float *__restrict__ yhat)
+{
+    extern __shared__ float s_table[];
+    __shared__ int s_unsorted;
+    if (threadIdx.x == 0) s_unsorted = 0;
+    for (int i = threadIdx.x; i < table_len; i += blockDim.x) s_table[i] = table[i];
+    __syncthreads();
+    for (int i = threadIdx.x; i + 1 < table_len; i += blockDim.x)
+        if (!(s_table[i] <= s_table[i + 1])) s_unsorted = 1;
+    __syncthreads();
+    const bool sorted = s_unsorted == 0;
+    for (int64_t base = static_cast<int64_t>(blockIdx.x) * blockDim.x; base < n; base += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        if (i >= n) break;
+        int64_t b = base / per_image;                         // uniform: once per chunk
+        int64_t r = (base - b * per_image) + threadIdx.x;
+        while (r >= per_image) { r -= per_image; ++b; }        // i < n = B * per_image keeps b < B
+        const float step = steps[n_steps == 1 ? 0 : b];
+        const float s = step_div(fmaxf(scales[i], bound), step);  // LowerBound first, then the step
+        int idx;
+        if (sorted && s == s) {
+            int lo = 0, hi = table_len - 1;   // first j in [0, len - 1) with table[j] >= s, len - 1 if none
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (s_table[mid] < s) lo = mid + 1; else hi = mid;
+            }
+            idx = lo;
+        } else {
+            idx = table_len - 1;
+            for (int j = 0; j < table_len - 1; ++j) idx -= (s <= s_table[j]) ? 1 : 0;
+        }
+        const float q = round_even(step_div(y[i], step));
+        symbols[i] = static_cast<int32_t>(q);
+        indexes[i] = idx;
+        if (yhat) yhat[i] = step_mul(q, step);
+    }
+}
+
+// i32_to_f32_kernel with the step: yhat = float(sym) * step[image], the encoder's q * step (its bits for every sym != 0; a
+// symbol 0 gives +0.0 where the encoder's rint may have left -0.0, as i32_to_f32_kernel does against gc_quantize_index_kernel)
+__global__ void gc_dequantize_q_kernel(const int32_t *__restrict__ in, int64_t n, int64_t per_image, const float *__restrict__ steps,
+                                       int n_steps, float *__restrict__ out)
+{
+    for (int64_t base = static_cast<int64_t>(blockIdx.x) * blockDim.x; base < n; base += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        if (i >= n) break;
+        int64_t b = base / per_image;
+        int64_t r = (base - b * per_image) + threadIdx.x;
+        while (r >= per_image) { r -= per_image; ++b; }
+        out[i] = step_mul(static_cast<float>(in[i]), steps[n_steps == 1 ? 0 : b]);
+    }
+}
+
 __global__ void eb_quantize_index_kernel(const float *__restrict__ z, const float *__restrict__ medians, int64_t total,
                                          int channels, int hw, int32_t *__restrict__ symbols,
                                          int32_t *__restrict__ indexes, float *__restrict__ zhat)
@@ -275,6 +350,33 @@ __global__ void gauss_nll_per_image_kernel(const float *__restrict__ q, const fl
     if (threadIdx.x == 0) nll[img] = red[0];
 }
 
+// MODE 0 of the kernel above under a quantiser step: q = the coded symbol rint(y / step) as float, its likelihood taken
+// under s' = max(scale, bound_s) / step[image] -- what the step coder's tables see.  One workgroup per image: the step is uniform.
+__global__ void gauss_nll_per_image_q_kernel(const float *__restrict__ q, const float *__restrict__ scales, int64_t elems,
+                                             const float *__restrict__ steps, int n_steps, float bound_s, float bound_p,
+                                             float *__restrict__ nll)
+{
+    __shared__ float red[kBlock];
+    const int img = blockIdx.x;
+    const float *pq = q + static_cast<int64_t>(img) * elems, *ps = scales + static_cast<int64_t>(img) * elems;
+    const float step = steps[n_steps == 1 ? 0 : img];
+    float acc = 0.f;
+    for (int64_t i = threadIdx.x; i < elems; i += blockDim.x) {
+        const float s = step_div(fmaxf(ps[i], bound_s), step);
+        const float v = fabsf(pq[i]);
+        const float c = -0.70710678118654752440f;
+        const float p = 0.5f * erfcf(c * ((0.5f - v) / s)) - 0.5f * erfcf(c * ((-0.5f - v) / s));
+        acc += -logf(fmaxf(p, bound_p));
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int st = kBlock / 2; st > 0; st >>= 1) {
+        if (static_cast<int>(threadIdx.x) < st) red[threadIdx.x] += red[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) nll[img] = red[0];
+}
+
 // EntropyBottleneck likelihood (upstream _logits_cumulative; call site compressai_coder.py:203-228): per channel a
 // 1-3-3-3-3-1 network with pre-activated parameters coef[c][58] = softplus(M0[3]) b0[3] tanh(f0)[3] | softplus(M1[9]) b1[3]
 // tanh(f1)[3] | M2.. | M3.. | softplus(M4[3]) b4[1].
@@ -330,6 +432,35 @@ extern "C" int basic_gc_quantize_index_dev(const float *d_y, const float *d_scal
     if (n == 0) return BASIC_OK;
     hipLaunchKernelGGL(gc_quantize_index_kernel, dim3(grid_for(n)), dim3(kBlock), table_len * sizeof(float),
                        as_stream(hip_stream), d_y, d_scales, n, d_table, table_len, scale_bound, d_symbols, d_indexes, d_yhat);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_gc_quantize_index_q_dev(const float *d_y, const float *d_scales, int64_t n, int64_t per_image,
+                                             const float *d_steps, int n_steps, const float *d_table, int table_len,
+                                             float scale_bound, int32_t *d_symbols, int32_t *d_indexes, float *d_yhat,
+                                             void *hip_stream)
+{
+    BASIC_REQUIRE(d_y && d_scales && d_steps && d_table && d_symbols && d_indexes && n >= 0 && table_len >= 1 && table_len <= 4096,
+                  "gc_quantize_index_q: bad argument");
+    BASIC_REQUIRE(per_image >= 1 && n % per_image == 0 && (n_steps == 1 || n_steps == n / per_image),
+                  "gc_quantize_index_q: n is a whole number of images of per_image elements, with one step for all or one each");
+    if (n == 0) return BASIC_OK;
+    hipLaunchKernelGGL(gc_quantize_index_q_kernel, dim3(grid_for(n)), dim3(kBlock), table_len * sizeof(float), as_stream(hip_stream),
+                       d_y, d_scales, n, per_image, d_steps, n_steps, d_table, table_len, scale_bound, d_symbols, d_indexes, d_yhat);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_gc_dequantize_q_dev(const int32_t *d_sym, int64_t n, int64_t per_image, const float *d_steps, int n_steps,
+                                         float *d_yhat, void *hip_stream)
+{
+    BASIC_REQUIRE(d_sym && d_steps && d_yhat && n >= 0, "gc_dequantize_q: bad argument");
+    BASIC_REQUIRE(per_image >= 1 && n % per_image == 0 && (n_steps == 1 || n_steps == n / per_image),
+                  "gc_dequantize_q: n is a whole number of images of per_image elements, with one step for all or one each");
+    if (n == 0) return BASIC_OK;
+    hipLaunchKernelGGL(gc_dequantize_q_kernel, dim3(grid_for(n)), dim3(kBlock), 0, as_stream(hip_stream), d_sym, n, per_image, d_steps,
+                       n_steps, d_yhat);
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
 }
@@ -463,6 +594,18 @@ extern "C" int basic_gauss_nll_per_image_dev(const float *d_q, const float *d_sc
     else
         hipLaunchKernelGGL(gauss_nll_per_image_kernel<0>, dim3(batch), dim3(kBlock), 0, as_stream(hip_stream), d_q, d_scales_or_params,
                            elems, hw, scale_bound, likelihood_bound, d_nll);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_gauss_nll_per_image_q_dev(const float *d_q, const float *d_scales, int batch, int channels, int hw,
+                                               const float *d_steps, int n_steps, float scale_bound, float likelihood_bound,
+                                               float *d_nll, void *hip_stream)
+{
+    BASIC_REQUIRE(d_q && d_scales && d_steps && d_nll && batch >= 1 && channels >= 1 && hw >= 1, "gauss_nll_per_image_q: bad argument");
+    BASIC_REQUIRE(n_steps == 1 || n_steps == batch, "gauss_nll_per_image_q: one step for all images or one each");
+    hipLaunchKernelGGL(gauss_nll_per_image_q_kernel, dim3(batch), dim3(kBlock), 0, as_stream(hip_stream), d_q, d_scales,
+                       static_cast<int64_t>(channels) * hw, d_steps, n_steps, scale_bound, likelihood_bound, d_nll);
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
 }

@@ -115,6 +115,12 @@ struct basic_hp_session {
     int rans_waves = 0;
     int lanes = 1;       // y streams per image (basic_hp_session_set_stream_lanes)
     int res_lanes = 1;   // of the encoded batch held in h_words
+    // quantiser step of the y latent (basic_hp_session_set_qsteps): empty = none, the step-less kernels.  Every call uploads
+    // them on its own stream through h_steps; steps_done closes the last upload, the only reader of h_steps.
+    std::vector<float> qsteps;
+    HBuf h_steps;
+    DBuf d_steps;
+    hipEvent_t steps_done = nullptr;
     DBuf d_medians, d_table;
     DBuf act[2], d_x, d_y, d_z, d_zhat, d_prior, d_scales;
     DBuf z_sym, z_idx, y_sym, y_idx, seg_z, seg_y, slots_z, slots_y, nw, off, packed, words, woff, state, pos;
@@ -362,7 +368,7 @@ basic_hp_session::~basic_hp_session()
                     e = nullptr;
                 }
     }
-    for (hipEvent_t e : {in_done, enc_phase, dec_phase, fork, join, x_free, x_ready, u8_free, xhat_free})
+    for (hipEvent_t e : {in_done, enc_phase, dec_phase, fork, join, x_free, x_ready, u8_free, xhat_free, steps_done})
         if (e) (void)hipEventDestroy(e);
     if (side) (void)hipStreamDestroy(side);
     if (copy) (void)hipStreamDestroy(copy);
@@ -387,6 +393,17 @@ extern "C" int basic_hp_session_set_stream_lanes(basic_hp_session *s, int lanes)
     return BASIC_OK;
 }
 
+extern "C" int basic_hp_session_set_qsteps(basic_hp_session *s, const float *host_steps, int n)
+{
+    BASIC_REQUIRE(s && n >= 0 && (n == 0 || host_steps), "hp_session_set_qsteps: bad argument");
+    for (int i = 0; i < n; ++i)   // NaN fails both comparisons' conjunction, infinities the upper one
+        BASIC_REQUIRE(host_steps[i] >= BASIC_QSTEP_MIN && host_steps[i] <= BASIC_QSTEP_MAX,
+                      "hp_session_set_qsteps: every step must be finite and in [2^-4, 2^6]");
+    s->qsteps.assign(host_steps, host_steps + n);
+    s->res_batch = 0;   // a held batch was coded with the previous steps
+    return BASIC_OK;
+}
+
 extern "C" int64_t basic_hp_encode_bound(const basic_hp_session *s, int batch, int h, int w)
 {
     if (!s || batch < 1 || h < 1 || w < 1) return -1;
@@ -399,6 +416,27 @@ extern "C" int64_t basic_hp_encode_bound(const basic_hp_session *s, int batch, i
 }
 
 namespace {
+
+// the session's steps serve a call of `batch` images: one each, or one for all
+bool qsteps_fit(const basic_hp_session *s, int batch)
+{
+    return s->qsteps.empty() || s->qsteps.size() == 1 || s->qsteps.size() == static_cast<size_t>(batch);
+}
+
+// the steps to the device, on the stream whose kernels read them
+int upload_qsteps(basic_hp_session *s, hipStream_t st)
+{
+    const size_t bytes = sizeof(float) * s->qsteps.size();
+    if (s->steps_done) BASIC_HIP_TRY(hipEventSynchronize(s->steps_done));   // the previous upload has left h_steps
+    else BASIC_HIP_TRY(hipEventCreateWithFlags(&s->steps_done, hipEventDisableTiming));
+    int rc = s->h_steps.ensure(bytes);
+    if (!rc) rc = s->d_steps.ensure(bytes);
+    if (rc) return rc;
+    std::memcpy(s->h_steps.p, s->qsteps.data(), bytes);
+    BASIC_HIP_TRY(hipMemcpyAsync(s->d_steps.p, s->h_steps.p, bytes, hipMemcpyHostToDevice, st));
+    BASIC_HIP_TRY(hipEventRecord(s->steps_done, st));
+    return BASIC_OK;
+}
 
 // enqueues the encoder of `streams` equal-length streams (n symbols each) into right-aligned slots of `slot` words
 int encode_latent(basic_hp_session *s, const basic_rans_tables *t, const int32_t *d_sym, const int32_t *d_idx, int streams,
@@ -485,8 +523,16 @@ int encode_body(basic_hp_session *s, const float *d_x, bool x_in_session, int ba
     rc = s->y_sym.ensure(sizeof(int32_t) * batch * ny);
     if (!rc) rc = s->y_idx.ensure(sizeof(int32_t) * batch * ny);
     if (rc) return rc;
-    rc = basic_gc_quantize_index_dev(s->d_y.as<float>(), d_scales, batch * ny, s->d_table.as<float>(), s->n_scales, s->scale_bound,
-                                     s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
+    if (s->qsteps.empty()) {
+        rc = basic_gc_quantize_index_dev(s->d_y.as<float>(), d_scales, batch * ny, s->d_table.as<float>(), s->n_scales, s->scale_bound,
+                                         s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
+    } else {
+        rc = upload_qsteps(s, st);
+        if (!rc)
+            rc = basic_gc_quantize_index_q_dev(s->d_y.as<float>(), d_scales, batch * ny, ny, s->d_steps.as<float>(),
+                                               static_cast<int>(s->qsteps.size()), s->d_table.as<float>(), s->n_scales, s->scale_bound,
+                                               s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
+    }
     if (rc) return rc;
     rc = encode_latent(s, s->y_tables, s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), sy, nyl, &s->seg_y, &s->slots_y, d_nw_y,
                        slot_y, st);
@@ -554,6 +600,7 @@ extern "C" int basic_hp_encode_images(basic_hp_session *s, const float *x, int x
                                       int64_t out_capacity, int64_t *out_len, void *hip_stream)
 {
     BASIC_REQUIRE(s && x && out_len && batch >= 1 && h >= 1 && w >= 1, "hp_encode_images: bad argument");
+    BASIC_REQUIRE(qsteps_fit(s, batch), "hp_encode_images: the session's quantiser steps are neither one nor one per image of this batch");
     s->res_batch = 0;
     hipStream_t st = as_stream(hip_stream);
     WavesGuard guard(s->rans_waves, s->use_token);
@@ -581,6 +628,7 @@ extern "C" int basic_hp_encode_images_u8(basic_hp_session *s, const uint8_t *x, 
 {
     BASIC_REQUIRE(s && x && out_len && batch >= 1 && h >= 1 && w >= 1, "hp_encode_images_u8: bad argument");
     BASIC_REQUIRE(layout == BASIC_IMAGE_CHW || layout == BASIC_IMAGE_HWC, "hp_encode_images_u8: layout is BASIC_IMAGE_CHW or BASIC_IMAGE_HWC");
+    BASIC_REQUIRE(qsteps_fit(s, batch), "hp_encode_images_u8: the session's quantiser steps are neither one nor one per image of this batch");
     s->res_batch = 0;
     hipStream_t st = as_stream(hip_stream);
     WavesGuard guard(s->rans_waves, s->use_token);
@@ -686,6 +734,7 @@ int decode_body(basic_hp_session *s, const uint8_t *data, int64_t len, float *d_
     rc = entropy_stream(s, caller_st, &st);   // everything before g_s goes to the entropy stream
     if (rc) return rc;
     const int batch = z.n, sy = y.n, K = s->lanes, zh = z.h, zw = z.w, yh = y.h, yw = y.w;
+    BASIC_REQUIRE(qsteps_fit(s, batch), "hp_decode_images: the session's quantiser steps are neither one nor one per image of this stream");
     int oh, ow;
     rc = chain_out_hw(s->g_s, yh, yw, &oh, &ow);
     if (rc) return rc;
@@ -756,13 +805,22 @@ int decode_body(basic_hp_session *s, const uint8_t *data, int64_t len, float *d_
     if (!rc) rc = s->d_y.ensure(sizeof(float) * batch * ny);
     if (rc) return rc;
     // indexes only: the symbol output of this launch is scratch (the module path does the same, compressai_coder.py:387-393)
-    rc = basic_gc_quantize_index_dev(d_scales, d_scales, batch * ny, s->d_table.as<float>(), s->n_scales, s->scale_bound,
-                                     s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
+    const int n_steps = static_cast<int>(s->qsteps.size());
+    if (!n_steps) {
+        rc = basic_gc_quantize_index_dev(d_scales, d_scales, batch * ny, s->d_table.as<float>(), s->n_scales, s->scale_bound,
+                                         s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
+    } else {
+        rc = upload_qsteps(s, st);
+        if (!rc)
+            rc = basic_gc_quantize_index_q_dev(d_scales, d_scales, batch * ny, ny, s->d_steps.as<float>(), n_steps, s->d_table.as<float>(),
+                                               s->n_scales, s->scale_bound, s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
+    }
     if (rc) return rc;
     rc = basic_rans_decode_batch_dev(s->y_tables, d_wy, d_oy, s->y_idx.as<int32_t>(), s->seg_y.as<int64_t>(), sy, s->y_sym.as<int32_t>(),
                                      s->state.as<uint64_t>() + batch, s->pos.as<int64_t>() + batch, st);
     if (rc) return rc;
-    rc = basic_i32_to_f32_dev(s->y_sym.as<int32_t>(), batch * ny, s->d_y.as<float>(), st);
+    if (!n_steps) rc = basic_i32_to_f32_dev(s->y_sym.as<int32_t>(), batch * ny, s->d_y.as<float>(), st);
+    else rc = basic_gc_dequantize_q_dev(s->y_sym.as<int32_t>(), batch * ny, ny, s->d_steps.as<float>(), n_steps, s->d_y.as<float>(), st);
     if (rc) return rc;
     // ---- edge y -> x: g_s straight into the caller's buffer
     rc = rejoin(s, caller_st, st);

@@ -17,6 +17,7 @@ selection logic in complexity_search.py, evaluation = this codec's own forward o
 from typing import Any, Dict, Iterable, List, Optional
 
 import math
+import struct
 import time
 import torch
 import torch.nn as nn
@@ -26,6 +27,7 @@ from ...codecs.base import (VariableComplexityCodecInterface, VariableRateCodecI
                             VariableTaskCodecInterface)
 from ...utils.bytes_ops import merge_bodies, merge_bytes, split_merged_bytes, split_merged_views
 from ...utils import item_framing
+from ...utils.qstep import check_qsteps
 from .complexity_search import search_complexity_levels
 
 
@@ -335,7 +337,10 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         return out
 
     # ---- generative pass (latent_graph.py:760-868)
-    def _generative_process(self, input_dict, prior_dict=None, do_encode=False, **kwargs):
+    def _generative_process(self, input_dict, prior_dict=None, do_encode=False, coder_kwargs=None, **kwargs):
+        """``coder_kwargs``: {node: keywords} handed to that node's entropy coder alone (the quantiser step of the y coder) --
+        not an input of the graph: no mapping, module or node generator sees them."""
+        coder_kwargs = coder_kwargs or {}
         data = dict(**input_dict)
         kw_all = dict(**input_dict, **kwargs)
         prior_dict = dict(prior_dict or {})
@@ -372,6 +377,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                     assert len(priors) <= 1
                     if len(priors) == 1:
                         pk.update(prior=list(priors.values())[0])
+                pk.update(coder_kwargs.get(node, {}))
                 with self.profiler.start_time_profile(f"latent_node_entropy_coders_{node}"):
                     if isinstance(node_data, (bytes, memoryview)):
                         node_data = coder.decode(node_data, **pk)
@@ -460,14 +466,53 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             sess._token = self.fused_transform_token
         return sess
 
-    def encode(self, data, *args, prior=None, **kwargs):
+    QSTEP_NODE = "y"   # the node whose coder takes the quantiser step
+
+    def _qstep_coder_kwargs(self, qstep, batch):
+        """``qstep`` of encode / decode -> (validated float32 steps, the keywords of the y coder), or (None, None) without one.
+        TypeError when the graph's y coder is not the GaussianConditional coder; ValueError for invalid steps (utils/qstep.py)."""
+        if qstep is None:
+            return None, None
+        from ..prior_model.prior_coder.compressai_coder import CompressAIGaussianConditionalCoder
+        coder = self.latent_node_entropy_coders[self.QSTEP_NODE] if self.QSTEP_NODE in self.latent_node_entropy_coders else None
+        if type(coder) is not CompressAIGaussianConditionalCoder:
+            raise TypeError(f"qstep= is the quantiser step of a CompressAIGaussianConditionalCoder at node '{self.QSTEP_NODE}'; this "
+                            f"graph codes it with {type(coder).__name__}.  The PGM coders' own knob is "
+                            "quantizer_type='uniform_scale' with quantizer_params=[step]")
+        steps = check_qsteps(qstep, batch)
+        return steps, {self.QSTEP_NODE: dict(qstep=steps)}
+
+    def _qstep_stream_batch(self, data):
+        """Images in a coded string, from the y body's header (host code: nothing is launched)."""
+        nodes = self._coded_nodes()
+        body = split_merged_views(data, num_segments=len(nodes))[nodes.index(self.QSTEP_NODE)]
+        if len(body) < 12:
+            raise ValueError("truncated stream: the y body has no header")
+        ns = struct.unpack(">3I", body[:12])[2]
+        lanes = self.latent_node_entropy_coders[self.QSTEP_NODE].stream_lanes
+        if ns < lanes or ns % lanes:
+            raise ValueError(f"the y body holds {ns} streams, no multiple of this coder's {lanes} stream lanes")
+        return ns // lanes
+
+    def encode(self, data, *args, prior=None, qstep=None, **kwargs):
+        """``qstep``: None -- today's codec; a number or one number per image -- the quantiser step of the y coder (INTEGRATION.md
+        "Quantiser step").  Like ``output_dtype`` of decode() it is not one of ``kwargs``: it neither changes the path a call takes
+        nor reaches a node generator, and both paths write the same bytes.  The string does not hold the steps: decode() needs them."""
+        steps, coder_kwargs = self._qstep_coder_kwargs(qstep, data.shape[0])
         with torch.no_grad():
             sess = self._fused_session(kwargs, prior) if not args else None
             if sess is not None:   # one C call: upload (when the batch is on the host), transforms, entropy stage, framing
                 if data.is_cuda and data.device != self.device:
                     data = data.to(device=self.device)
                 with self.profiler.start_time_profile("encode_fused"):
-                    out = sess.encode(data)
+                    if steps is None:
+                        out = sess.encode(data)
+                    else:
+                        sess.set_qsteps(steps)
+                        try:
+                            out = sess.encode(data)
+                        finally:
+                            sess.set_qsteps(None)
                 if self.after_inference_hook is not None:
                     self.after_inference_hook()
                 return out
@@ -484,7 +529,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             if self.after_inference_hook is not None:   # the analysis transforms are enqueued (see stream_workers.py)
                 self.after_inference_hook()
             with self.profiler.start_time_profile("encode_generative"):
-                data_dict, _ = self._generative_process(latent_dict, prior_dict=prior_dict, do_encode=True)
+                data_dict, _ = self._generative_process(latent_dict, prior_dict=prior_dict, do_encode=True, coder_kwargs=coder_kwargs)
             nodes = self._coded_nodes()
             bodies = [data_dict[n] for n in nodes]
             if any(hasattr(b, "write_into") for b in bodies):
@@ -492,17 +537,27 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             bodies = [b.result() if hasattr(b, "result") else b for b in bodies]
             return merge_bytes(bodies, num_segments=len(nodes))
 
-    def decode(self, data, *args, prior=None, output_dtype=None, **kwargs):
+    def decode(self, data, *args, prior=None, output_dtype=None, qstep=None, **kwargs):
         """``output_dtype``: None / torch.float32 -- the reconstruction as the graph gives it; torch.uint8 -- the picture,
         ``nan_to_num(x, nan=0).clamp(0, 1).mul(255).round()`` as bytes, converted on the device.  The keyword is the caller's
-        wish about the RESULT: it is not one of ``kwargs``, so it neither changes the path a call takes nor reaches a node generator."""
+        wish about the RESULT: it is not one of ``kwargs``, so it neither changes the path a call takes nor reaches a node generator.
+        ``qstep``: the steps encode() was given (one, or one per image of the string), an explicit keyword in the same way."""
         if output_dtype not in (None, torch.float32, torch.uint8):
             raise TypeError(f"output_dtype is torch.float32 or torch.uint8, not {output_dtype}")
+        steps, coder_kwargs = self._qstep_coder_kwargs(qstep, None)
+        if steps is not None:   # one step or one per image, checked against the string's own header before anything is launched
+            check_qsteps(steps, self._qstep_stream_batch(data))
         with torch.no_grad():
             sess = self._fused_session(kwargs, prior) if not args else None
             if sess is not None:
                 with self.profiler.start_time_profile("decode_fused"):
-                    return sess.decode(data, device=self.device, output_dtype=output_dtype or torch.float32)
+                    if steps is None:
+                        return sess.decode(data, device=self.device, output_dtype=output_dtype or torch.float32)
+                    sess.set_qsteps(steps)
+                    try:
+                        return sess.decode(data, device=self.device, output_dtype=output_dtype or torch.float32)
+                    finally:
+                        sess.set_qsteps(None)
             node_dict = self._node_generate_process(**self._get_default_node_dict(force_add_default_dynamic_nodes=True, **kwargs))
             nodes = self._coded_nodes()
             # coders that read their stream through the buffer protocol get it in place; others get bytes
@@ -513,7 +568,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             if self.use_lossy_compression:
                 input_dict[self.DEFAULT_INPUT_NODE_NAME] = b""
             with self.profiler.start_time_profile("decode_generative"):
-                data_dict, _ = self._generative_process(input_dict, prior_dict=prior_dict, **node_dict)
+                data_dict, _ = self._generative_process(input_dict, prior_dict=prior_dict, coder_kwargs=coder_kwargs, **node_dict)
             out = data_dict[self.DEFAULT_INPUT_NODE_NAME]
             if output_dtype == torch.uint8:
                 from ...nn import kernels as K

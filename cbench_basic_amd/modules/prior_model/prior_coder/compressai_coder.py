@@ -468,8 +468,44 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
             raise ValueError(f"stream_lanes={self.stream_lanes} does not divide the {n} symbols (C * H * W) of an image")
         return n // self.stream_lanes
 
-    def forward(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, **kwargs):
+    # ---- quantiser step (INTEGRATION.md "Quantiser step"; no reference counterpart): ``qstep`` = one step, or one per image
+    def _forward_q(self, y, prior, qstep):
+        scales = self._crop(prior, *y.shape[-2:])
+        steps = K.qsteps_tensor(qstep, y.shape[0], y.device)
+        sym, _, yhat = K.gc_quantize_index_q(y, scales, steps, self._scale_table_dev, self.scale_bound)
+        # the rate of what is coded: the symbols under scale / step
+        nll = K.gauss_nll_per_image(K.i32_to_f32(sym), scales, False, self.scale_bound, 1e-9, steps=steps)
+        self.update_cache("metric_dict", prior_entropy=nll.mean())
+        return yhat
+
+    def _encode_q(self, y, prior, qstep, lazy):
+        sym, idx, _ = K.gc_quantize_index_q(y, self._crop(prior, *y.shape[-2:]), qstep, self._scale_table_dev, self.scale_bound,
+                                            want_yhat=False)
+        per = self._lane_length(y[0].numel())
+        body = PendingBody(self._tables, self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), per), y.shape[-2:])
+        return body if lazy else body.result()
+
+    def _decode_q(self, byte_string, prior, qstep):
+        h, w, ns = K.frame_header(byte_string)
+        scales = self._crop(prior, h, w)
+        per = self._lane_length(scales[0].numel())
+        if self.stream_lanes > 1 and ns != scales.shape[0] * self.stream_lanes:
+            raise ValueError(f"stream body holds {ns} streams, this coder's configuration needs {scales.shape[0] * self.stream_lanes}")
+        steps = K.qsteps_tensor(qstep, scales.shape[0], scales.device)
+        _, idx, _ = K.gc_quantize_index_q(scales, scales, steps, self._scale_table_dev, self.scale_bound, want_yhat=False)
+        sym = self._tables.decode_batch_from_frame(byte_string, idx.reshape(-1), per)
+        return K.gc_dequantize_q(sym.reshape(idx.shape), steps)
+
+    @staticmethod
+    def _qstep_alone(qstep, channel_gains, channel_gains_inv):
+        if qstep is not None and (channel_gains is not None or channel_gains_inv is not None):
+            raise ValueError("qstep= and channel_gains are two rate knobs: give one of them")
+        return qstep is not None
+
+    def forward(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, **kwargs):
         self._ready()
+        if self._qstep_alone(qstep, channel_gains, channel_gains_inv):
+            return self._forward_q(y, prior, qstep)
         if channel_gains is not None:
             y = y * channel_gains.reshape(1, -1, 1, 1)
         scales = self._crop(prior, *y.shape[-2:])
@@ -485,8 +521,10 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
     supports_lazy_encode = True
     accepts_buffer = True  # decode() reads the stream through the buffer protocol (bytes or memoryview)
 
-    def encode(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, lazy=False, **kwargs):  # :377-385
+    def encode(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, lazy=False, qstep=None, **kwargs):  # :377-385
         self._ready()
+        if self._qstep_alone(qstep, channel_gains, channel_gains_inv):
+            return self._encode_q(y, prior, qstep, lazy)
         if channel_gains is not None:
             y = y * channel_gains.reshape(1, -1, 1, 1)
         sym, idx, _ = K.gc_quantize_index(y, self._crop(prior, *y.shape[-2:]), self._scale_table_dev, self.scale_bound,
@@ -496,8 +534,10 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
         body = PendingBody(self._tables, self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), per), y.shape[-2:])
         return body if lazy else body.result()
 
-    def decode(self, byte_string, *args, prior=None, channel_gains=None, channel_gains_inv=None, **kwargs):  # :387-393
+    def decode(self, byte_string, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, **kwargs):  # :387-393
         self._ready()
+        if self._qstep_alone(qstep, channel_gains, channel_gains_inv):
+            return self._decode_q(byte_string, prior, qstep)
         h, w, ns = K.frame_header(byte_string)
         shape = (h, w)
         scales = self._crop(prior, *shape)

@@ -360,6 +360,45 @@ def gc_quantize_index(y, scales, table, bound=0.11, want_yhat=True):
     return sym, idx, yhat
 
 
+def qsteps_tensor(steps, batch, device):
+    """Quantiser steps (a number, a sequence, an array or a tensor) as a float32 device tensor of 1 or ``batch`` elements,
+    validated on the host first (utils/qstep.py: finite, in [2^-4, 2^6], one or one per image) -- ValueError otherwise, nothing launched."""
+    from ..utils.qstep import check_qsteps
+    return torch.from_numpy(check_qsteps(steps, batch)).to(device)
+
+
+def _per_image(t):
+    if t.dim() < 1 or t.shape[0] < 1:
+        raise ValueError("the step kernels take [B, ...] tensors with B >= 1")
+    return t.shape[0], t.numel() // t.shape[0]
+
+
+def gc_quantize_index_q(y, scales, steps, table, bound=0.11, want_yhat=True):
+    """gc_quantize_index under a quantiser step per image of the [B, ...] latent (basic_gc_quantize_index_q_dev):
+    sym = rint(y / step), idx from max(scale, bound) / step, yhat = sym * step.  ``steps``: see qsteps_tensor."""
+    y, scales, table = _dev(y, torch.float32), _dev(scales, torch.float32), _dev(table, torch.float32)
+    B, per = _per_image(y)
+    steps = qsteps_tensor(steps, B, y.device)
+    sym = torch.empty(y.shape, device=y.device, dtype=torch.int32)
+    idx = torch.empty(y.shape, device=y.device, dtype=torch.int32)
+    yhat = torch.empty_like(y) if want_yhat else None
+    _lib.check(_lib.lib().basic_gc_quantize_index_q_dev(y.data_ptr(), scales.data_ptr(), y.numel(), per, steps.data_ptr(), steps.numel(),
+                                                        table.data_ptr(), table.numel(), float(bound), sym.data_ptr(), idx.data_ptr(),
+                                                        yhat.data_ptr() if yhat is not None else None, _stream()))
+    return sym, idx, yhat
+
+
+def gc_dequantize_q(sym, steps):
+    """float(sym) * step of the image, for a [B, ...] int32 tensor (basic_gc_dequantize_q_dev): the encoder's yhat bit for bit."""
+    sym = _dev(sym, torch.int32)
+    B, per = _per_image(sym)
+    steps = qsteps_tensor(steps, B, sym.device)
+    out = torch.empty(sym.shape, device=sym.device, dtype=torch.float32)
+    _lib.check(_lib.lib().basic_gc_dequantize_q_dev(sym.data_ptr(), sym.numel(), per, steps.data_ptr(), steps.numel(), out.data_ptr(),
+                                                    _stream()))
+    return out
+
+
 def lanes_pack(sym, idx, batch, positions, channels, lanes):
     """Lane streams of the scan-line coder: both int32 arrays from coding order [B][P][K][L] to [B * K][P * L] (a row per lane
     stream; basic_lanes_pack_dev)."""
@@ -450,12 +489,21 @@ def ms_ssim_per_image(x, y, data_range=1.0, return_terms=False, workspace=None):
     return (out, terms) if return_terms else out
 
 
-def gauss_nll_per_image(q, scales_or_params, interleaved, scale_bound=0.11, likelihood_bound=1e-9):
-    """Rate estimate (nats per image) of a Gaussian-coded latent; see basic_gauss_nll_per_image_dev."""
+def gauss_nll_per_image(q, scales_or_params, interleaved, scale_bound=0.11, likelihood_bound=1e-9, steps=None):
+    """Rate estimate (nats per image) of a Gaussian-coded latent; see basic_gauss_nll_per_image_dev.  ``steps`` (zero-mean mode
+    only; see qsteps_tensor): q holds the symbols rint(y / step), rated under max(scale, bound) / step
+    (basic_gauss_nll_per_image_q_dev)."""
     q, sp = _dev(q, torch.float32), _dev(scales_or_params, torch.float32)
     B, C = q.shape[0], q.shape[1]
     hw = q.numel() // (B * C)
     out = torch.empty((B,), device=q.device, dtype=torch.float32)
+    if steps is not None:
+        if interleaved:
+            raise ValueError("gauss_nll_per_image: steps= goes with the zero-mean mode (interleaved=False) only")
+        steps = qsteps_tensor(steps, B, q.device)
+        _lib.check(_lib.lib().basic_gauss_nll_per_image_q_dev(q.data_ptr(), sp.data_ptr(), B, C, hw, steps.data_ptr(), steps.numel(),
+                                                              float(scale_bound), float(likelihood_bound), out.data_ptr(), _stream()))
+        return out
     mode = 2 if interleaved == "round_residual" else int(bool(interleaved))
     _lib.check(_lib.lib().basic_gauss_nll_per_image_dev(q.data_ptr(), sp.data_ptr(), B, C, hw, mode, float(scale_bound),
                                                         float(likelihood_bound), out.data_ptr(), _stream()))
@@ -838,6 +886,16 @@ class HyperpriorSession:
     def set_stream_lanes(self, lanes):
         """y streams per image (basic_hp_session_set_stream_lanes): 1 is the reference's format."""
         _lib.check(_lib.lib().basic_hp_session_set_stream_lanes(self._h, int(lanes)))
+
+    def set_qsteps(self, steps):
+        """Quantiser steps of the y latent for the calls that follow (basic_hp_session_set_qsteps): a number or a sequence of
+        one step per image, validated on the host (ValueError); None clears them -- the session then launches what it always did."""
+        if steps is None:
+            _lib.check(_lib.lib().basic_hp_session_set_qsteps(self._h, None, 0))
+            return
+        from ..utils.qstep import check_qsteps
+        steps = check_qsteps(steps)
+        _lib.check(_lib.lib().basic_hp_session_set_qsteps(self._h, steps.ctypes.data, int(steps.size)))
 
     def set_transform_token(self, enable):
         """False / 0: no ordering; True / 1: the transform phases of all sessions one at a time; 2: two at a time."""

@@ -183,6 +183,27 @@ int basic_rans_set_waves(int waves_per_block, int *previous);
 int basic_gc_quantize_index_dev(const float *d_y, const float *d_scales, int64_t n, const float *d_table,
                                 int table_len, float scale_bound, int32_t *d_symbols, int32_t *d_indexes,
                                 float *d_yhat, void *hip_stream);
+/* Quantiser step (no reference counterpart; an opt-in format, INTEGRATION.md "Quantiser step").  Element i belongs to image
+ * b = i / per_image and takes step = d_steps[n_steps == 1 ? 0 : b], float32 on the device.  Every line is one fp32 operation:
+ *     s   = max(scale, bound)                 LowerBound first, as basic_gc_quantize_index_dev
+ *     s'  = s / step                          IEEE division, correctly rounded (no reciprocal)
+ *     idx = the index rule above on s'        (same search, same NaN / unsorted-table fallback)
+ *     q   = round_half_even(y / step)         the same division
+ *     sym = (int32) q,   yhat = q * step      one multiply; the decoder's (float) sym * step is the same bits for sym != 0
+ *                                             (sym == 0: +0.0, where rint may have left the encoder -0.0, as without a step)
+ * With every step 1 the outputs are those of basic_gc_quantize_index_dev / basic_i32_to_f32_dev bit for bit.  n must be a
+ * whole number of images and n_steps 1 or n / per_image, else BASIC_ERR_INVALID.  The step VALUES live on the device and are
+ * not inspected here: the caller validates them on the host (finite, in [BASIC_QSTEP_MIN, BASIC_QSTEP_MAX]) before it uploads
+ * them, as basic_hp_session_set_qsteps does.  A decoder obtains its indexes from the same entry point with d_y = d_scales and
+ * d_yhat = NULL (the symbols are scratch), the way the step-less decoder uses basic_gc_quantize_index_dev. */
+#define BASIC_QSTEP_MIN 0.0625f /* 2^-4 */
+#define BASIC_QSTEP_MAX 64.0f   /* 2^6  */
+int basic_gc_quantize_index_q_dev(const float *d_y, const float *d_scales, int64_t n, int64_t per_image, const float *d_steps,
+                                  int n_steps, const float *d_table, int table_len, float scale_bound, int32_t *d_symbols,
+                                  int32_t *d_indexes, float *d_yhat, void *hip_stream);
+/* d_yhat[i] = (float) d_sym[i] * step of image i / per_image: the encoder's yhat (bit for bit where d_sym[i] != 0). */
+int basic_gc_dequantize_q_dev(const int32_t *d_sym, int64_t n, int64_t per_image, const float *d_steps, int n_steps,
+                              float *d_yhat, void *hip_stream);
 /* Lane streams of the scan-line coder: repacks d_sym / d_idx, int32 [B][positions][channels] in coding order, to
  * [B][lanes][positions][channels / lanes] (lane k = channels [k L, (k + 1) L), L = channels / lanes), so that
  * basic_rans_encode_batch_dev codes B * lanes contiguous streams of positions * L symbols.  Out of place; lanes == 1 copies. */
@@ -237,6 +258,11 @@ int basic_pgm_gauss_scatter_group_dev(const int32_t *d_symbols, const float *d_p
 int basic_gauss_nll_per_image_dev(const float *d_q, const float *d_scales_or_params, int batch, int channels, int hw,
                                   int interleaved_mean_scale, float scale_bound, float likelihood_bound, float *d_nll,
                                   void *hip_stream);
+/* The interleaved_mean_scale == 0 mode under a quantiser step: d_q = the coded symbols round(y / step) as float32 [B][C][HW],
+ * likelihood under s' = max(scale, scale_bound) / step[b] (the division of basic_gc_quantize_index_q_dev); d_steps float32
+ * [n_steps] on the device, n_steps 1 or batch. */
+int basic_gauss_nll_per_image_q_dev(const float *d_q, const float *d_scales, int batch, int channels, int hw, const float *d_steps,
+                                    int n_steps, float scale_bound, float likelihood_bound, float *d_nll, void *hip_stream);
 /* EntropyBottleneck likelihood (call site compressai_coder.py:203-228); d_coef float32 [C][58]: the pre-activated
  * 1-3-3-3-3-1 cumulative-logit network of every channel (softplus(matrix), bias, tanh(factor) per layer). */
 int basic_eb_nll_per_image_dev(const float *d_zq, const float *d_coef, int batch, int channels, int hw,
@@ -404,6 +430,15 @@ int basic_hp_decode_images(basic_hp_session *s, const uint8_t *data, int64_t len
  * A call whose ny is no multiple of lanes, or a stream whose y body does not hold lanes streams per z stream, fails with
  * BASIC_ERR_INVALID.  Configuration of the session like its tables: not written into the stream. */
 int basic_hp_session_set_stream_lanes(basic_hp_session *s, int lanes);
+/* Quantiser step of the y latent (section 4; INTEGRATION.md "Quantiser step"): host_steps = n float32 in host memory, one for
+ * every image of the calls that follow (n == their batch) or one for all (n == 1); n == 0 clears it, and the session launches
+ * exactly what it launched before.  Every step must be finite and in [BASIC_QSTEP_MIN, BASIC_QSTEP_MAX], else
+ * BASIC_ERR_INVALID and the session keeps what it had.  With steps set, basic_hp_encode_images[_u8] and
+ * basic_hp_decode_images[_u8] copy them to the device on the call's stream and take basic_gc_quantize_index_q_dev /
+ * basic_gc_dequantize_q_dev on the y path; z stays at step 1, lane streams keep their meaning, and the two bodies keep their
+ * format.  A call whose batch is neither n nor broadcast from n == 1 fails with BASIC_ERR_INVALID before anything is launched.
+ * The steps are NOT written into the stream: the container that carries them is the caller's (codecs/qstep.py). */
+int basic_hp_session_set_qsteps(basic_hp_session *s, const float *host_steps, int n);
 /* Wavefronts (image streams) per workgroup of this session's rANS launches: 1, 2, 4, 8 or 16 (0 = library default). */
 int basic_hp_session_set_rans_waves(basic_hp_session *s, int waves_per_block);
 /* Opt this session into the process-wide "transform token": the MFMA-heavy phases (compress: everything up to the y

@@ -110,8 +110,27 @@ def main(argv=None):
     ap.add_argument("--metrics-on-uint8", action="store_true",
                     help="measure the 8-bit picture: decompress(output_dtype=torch.uint8) inside the timed region, the distortion from "
                          "exact integers against the 8-bit item (a float item: quantised once)")
+    ap.add_argument("--qsteps", type=float, nargs="+", default=[], metavar="Q",
+                    help="testing_qsteps, --codec hyperprior: one pass per quantiser step of the y coder through compress_q / decompress_q "
+                         "(level prefix q<step>; 1 is the codec as trained, above 1 fewer bits); every step in [0.0625, 64].  Composes with "
+                         "--uint8, --metrics-on-uint8, --workers and --stream-lanes; not with --coalesce, --tile* or --complexity-levels")
     ap.add_argument("--out", required=True)
     args = ap.parse_args(argv)
+    if args.qsteps:
+        from cbench_basic_amd.utils.qstep import check_qsteps
+        if args.codec != "hyperprior":
+            ap.error("--qsteps is the hyperprior y coder's quantiser step: it needs --codec hyperprior (the PGM coders' knob is quantizer_params)")
+        for name, on in (("--coalesce", args.coalesce > 1), ("--tile", args.tile is not None), ("--tile-overlap", args.tile_overlap is not None),
+                         ("--tile-pad", args.tile_pad is not None), ("--tile-pool", args.tile_pool > 0),
+                         ("--complexity-levels", bool(args.complexity_levels)), ("--rate-levels", bool(args.rate_levels)),
+                         ("--forward-pass", args.forward_pass)):
+            if on:
+                ap.error(f"--qsteps does not combine with {name}: the step is a knob of compress_q / decompress_q alone")
+        try:
+            for q in args.qsteps:
+                check_qsteps(q)
+        except ValueError as e:
+            ap.error(f"--qsteps: {e}")
     if args.stream_rows and args.codec != "basic":
         ap.error("--stream-rows needs --codec basic")
     if args.scanline_decode_schedule != "auto" and not args.stream_rows:
@@ -188,6 +207,8 @@ def main(argv=None):
             c.decompress_tiled_items(c.compress_tiled_items(batches[:args.tile_pool], tile=args.tile, overlap=args.tile_overlap, **pad))
         elif args.tile is not None:
             c.decompress_tiled(c.compress_tiled(batches[0].to("cuda"), tile=args.tile, overlap=args.tile_overlap, **pad))
+        elif args.qsteps:   # the step kernels' route, and the session's step buffers
+            c.decompress_q(c.compress_q(batches[0].to("cuda"), args.qsteps[0]))
         else:
             c.decompress(c.compress(batches[0].to("cuda")))
     warm_chunks = []
@@ -213,7 +234,7 @@ def main(argv=None):
                                               testing_complexity_levels=args.complexity_levels,
                                               testing_variable_rate_levels=args.rate_levels, output_dir=args.out,
                                               num_testing_workers=args.workers, testing_coalesce_items=args.coalesce, testing_tile=args.tile, testing_tile_overlap=args.tile_overlap,
-                                              testing_tile_pool=args.tile_pool, testing_tile_pad=args.tile_pad,
+                                              testing_tile_pool=args.tile_pool, testing_tile_pad=args.tile_pad, testing_qsteps=args.qsteps,
                                               codec_builder=(lambda: presets.seed_synthetic_weights(builders[args.codec](), seed=0)) if args.workers > 1 else None)
     if args.workers > 1 and args.warmup:   # the replicas' one-time costs too, one replica at a time (HIP-graph capture)
         pool = bench._worker_pool(batches[0], batch=max((len(c) for c in warm_chunks), default=None))
