@@ -58,7 +58,7 @@ class BasicLosslessCompressionBenchmark:
                  testing_complexity_levels=None, force_testing_device="cuda", output_dir=None, num_repeats=1,
                  num_testing_workers=0, codec_builder=None, worker_transform_token=None, testing_coalesce_items=0,
                  metrics_on_uint8=False, on_reconstruction=None, testing_tile=None, testing_tile_overlap=0, testing_tile_pool=0,
-                 testing_tile_pad=None, testing_qsteps=None, **kwargs):
+                 testing_tile_pad=None, testing_qsteps=None, testing_target_bpps=None, **kwargs):
         self.codec = codec
         self.dataloader = dataloader
         self.distortion_metric = distortion_metric
@@ -145,7 +145,24 @@ class BasicLosslessCompressionBenchmark:
                              ("nn_codec_use_forward_pass", bool(nn_codec_use_forward_pass))):
                 if on:
                     raise ValueError(f"testing_qsteps does not combine with {name}: the step is a knob of compress_q / decompress_q alone")
+        # rate targets ("Rate control"): one pass per target through compress_to_rate / decompress_q, level prefix
+        # bpp<target>; refused with what refuses the steps, and with the steps themselves
+        from ..utils.rate import budgets_from
+        self.testing_target_bpps = [float(r) for r in (testing_target_bpps or [])]
+        for r in self.testing_target_bpps:
+            if not r > 0 or r == float("inf"):
+                raise ValueError(f"testing_target_bpps must be positive and finite, got {r}")
+            budgets_from(None, r, 1, 1 << 12, 1 << 12)
+        if self.testing_target_bpps:
+            for name, on in (("testing_qsteps", bool(self.testing_qsteps)),
+                             ("testing_variable_rate_levels", bool(self.testing_variable_rate_levels)),
+                             ("testing_complexity_levels", bool(self.testing_complexity_levels)),
+                             ("testing_coalesce_items", self.testing_coalesce_items > 1), ("testing_tile", testing_tile is not None),
+                             ("nn_codec_use_forward_pass", bool(nn_codec_use_forward_pass))):
+                if on:
+                    raise ValueError(f"testing_target_bpps does not combine with {name}: the target is a knob of compress_to_rate alone")
         self._qstep = None
+        self._target_bpp = None
         self._level_prefix = ""
         self._pictures = {}
         self._pool = None
@@ -215,6 +232,8 @@ class BasicLosslessCompressionBenchmark:
         return self._to_f32(data_target) if self.metrics_on_uint8 else data_target
 
     def _compress(self, codec, data):
+        if self._target_bpp is not None:
+            return codec.compress_to_rate(data, target_bpp=self._target_bpp)
         if self._qstep is not None:
             return codec.compress_q(data, self._qstep)
         if self.testing_tile is None:
@@ -225,7 +244,7 @@ class BasicLosslessCompressionBenchmark:
         return codec.compress_tiled(data, tile=self.testing_tile, overlap=self.testing_tile_overlap, **self._tile_pad)
 
     def _decompress(self, codec, compressed):
-        if self._qstep is not None:
+        if self._qstep is not None or self._target_bpp is not None:
             return codec.decompress_q(compressed, output_dtype=torch.uint8 if self.metrics_on_uint8 else None)
         if self.testing_tile is not None:
             return codec.decompress_tiled(compressed, output_dtype=torch.uint8 if self.metrics_on_uint8 else None)
@@ -547,7 +566,7 @@ class BasicLosslessCompressionBenchmark:
         metrics, metrics_2d = OrderedDict(), OrderedDict()
         vr, vc = self.testing_variable_rate_levels, self.testing_complexity_levels
         # the rate axis: (rate level, quantiser step) pairs -- the codec's own levels, or the steps (never both: __init__)
-        axis = [(r, None) for r in vr] or [(None, q) for q in self.testing_qsteps]
+        axis = [(r, None, None) for r in vr] or [(None, q, None) for q in self.testing_qsteps] or [(None, None, r) for r in self.testing_target_bpps]
         if hasattr(self.codec, "eval"):
             self.codec.eval()
         if self.force_testing_device and hasattr(self.codec, "to"):
@@ -555,8 +574,8 @@ class BasicLosslessCompressionBenchmark:
         for _ in range(self.num_repeats):
             for ci, clevel in enumerate(vc if vc else [None]):
                 rate_pts, distortion_pts = [], []
-                for ri, (rlevel, qstep) in enumerate(axis if axis else [(None, None)]):
-                    self._qstep = qstep
+                for ri, (rlevel, qstep, bpp) in enumerate(axis if axis else [(None, None, None)]):
+                    self._qstep, self._target_bpp = qstep, bpp
                     if clevel is not None:
                         self.codec.set_complex_level(clevel)
                     if rlevel is not None:
@@ -566,7 +585,8 @@ class BasicLosslessCompressionBenchmark:
                     self.codec.update_state()
                     if self.distortion_metric is not None:
                         self.distortion_metric.reset()
-                    rate_prefix = [f"vrlevel{rlevel}"] if rlevel is not None else [f"q{qstep:g}"] if qstep is not None else []
+                    rate_prefix = [f"vrlevel{rlevel}"] if rlevel is not None else [f"q{qstep:g}"] if qstep is not None else \
+                        [f"bpp{bpp:g}"] if bpp is not None else []
                     self._level_prefix = "_".join(([f"sclevel{clevel}"] if clevel is not None else []) + rate_prefix)
                     current = self._run_dataset()
                     if self.distortion_metric is not None:
@@ -601,7 +621,7 @@ class BasicLosslessCompressionBenchmark:
                     value = bj((rate_pts, distortion_pts))[bj.name]
                     metrics[bj_prefix + bj.name] = value
                     metrics_2d[prefix][bj.name] = value
-        self._qstep = None
+        self._qstep = self._target_bpp = None
         if metrics_2d and self.output_dir:
             self.save_metrics(metric_file=os.path.join(self.output_dir, "metrics_2d.csv"),
                               metric_data=list(metrics_2d.values()), names=list(metrics_2d.keys()), raw=False)

@@ -46,6 +46,33 @@ class GeneralCodec(HotPathModule, CodecInterface, VariableRateCodecInterface, Va
         steps, inner = unpack_qsteps(data)
         return self.decompress(inner, *args, output_dtype=output_dtype, qstep=steps, **kwargs)
 
+    def compress_to_rate(self, data, target_bytes=None, target_bpp=None, candidates=16, passes=2, step_range=(2 ** -4, 2 ** 6),
+                         return_report=False, **kwargs):
+        """``compress_q`` with the step of every image chosen on the GPU so that the image's payload -- its z stream plus its y
+        stream(s); not the fixed framing -- fits a byte budget (INTEGRATION.md "Rate control").  Give exactly one target, a number or one
+        per image: ``target_bytes``, or ``target_bpp`` (budget = floor(bpp * H * W / 8)).  ``candidates`` steps, log-spaced over
+        ``step_range``, are rated in one pass over the latent and the smallest that fits is refined ``passes - 1`` times between
+        itself and its lower neighbour.  -> the BQS1 container of compress_q with one step per image (``decompress_q`` reads it),
+        byte for byte ``compress_q(data, those steps)``; with ``return_report`` also a dict of per-image ``steps``,
+        ``predicted_bytes``, ``payload_bytes``, ``budget`` and ``met`` (payload <= budget).  An image no candidate fits takes the
+        largest step and reports ``met`` False.  ValueError for an invalid request, before anything is launched."""
+        import numpy as np
+        from ..utils.qstep import pack_qsteps
+        from ..utils.rate import RateTarget, budgets_from, first_grid
+        if data.dim() != 4:
+            raise ValueError(f"compress_to_rate takes a [B, C, H, W] batch, got shape {tuple(data.shape)}")
+        B, _, H, W = data.shape
+        budgets = budgets_from(target_bytes, target_bpp, B, H, W)
+        rt = RateTarget(budgets, first_grid(candidates, step_range), passes, batch=B)
+        inner = self.compress(data, rate_target=rt, **kwargs)
+        out = pack_qsteps(rt.steps, inner)
+        if not return_report:
+            return out
+        payload = np.asarray(self.entropy_coder.payload_bytes(inner, B), dtype=np.int64)
+        want = rt.budgets_for(B)
+        return out, dict(steps=rt.steps, predicted_bytes=rt.predicted_bytes, payload_bytes=payload, budget=want, met=payload <= want,
+                         fits=rt.fits)
+
     def compress_items(self, items, *args, max_batch=None, **kwargs):
         """N batch-1 items -> exactly ``[self.compress(x) for x in items]``, items of one shape coded in shared batches
         (entropy coder's ``encode_items``; not part of the reference's codec interface)."""

@@ -55,4 +55,13 @@ struct RansFastView {
 };
 int rans_fast_view(const basic_rans_tables *t, RansFastView *out);   // BASIC_ERR_INVALID when the set has no fast image
 
+// Device view of a table set's cost table (basic_rans_cost_table_host) for the rate kernels of entropy.hip: built and uploaded
+// on the first call.  BASIC_ERR_INVALID when a row holds a frequency that is not positive.
+struct RansRateView {
+    const uint32_t *cost = nullptr;                      // [rows][stride], 2^-16 bit
+    const int32_t *sizes = nullptr, *offsets = nullptr;  // per row
+    int rows = 0, stride = 0, precision = 16, bypass = 1, bypass_precision = 4;
+};
+int rans_rate_view(const basic_rans_tables *t, RansRateView *out);
+
 }  // namespace basic

@@ -8,7 +8,7 @@
 //   EntropyBottleneck.compress/decompress         (call site compressai_coder.py:230-245)
 //   GaussianPGMPriorCoderImpl._select_best_indexes pgm_coder.py:802-821
 //   TopoGroupPGMPriorCoder group step              pgm_coder.py:921-941, 962-978
-#include "common.h"
+#include "ans_common.h"   // clampi, bypass_split, escape_digits: the coder's own split of a value
 
 using namespace basic;
 
@@ -140,6 +140,155 @@ __global__ void gc_dequantize_q_kernel(const int32_t *__restrict__ in, int64_t n
         while (r >= per_image) { r -= per_image; ++b; }
         out[i] = step_mul(static_cast<float>(in[i]), steps[n_steps == 1 ? 0 : b]);
     }
+}
+
+// ---- rate control (include/basic_hip.h, "Rate control"): the exact table cost of every stream at each candidate step.
+// One read of y and sigma serves all candidates: an element sits in two registers while the candidate loop -- unrolled over the
+// template's kNC accumulators, n_cand <= kNC of them live -- repeats gc_quantize_index_q_kernel's arithmetic for the step and
+// looks the symbol's cost up (a 4-byte gather from the [rows][stride] table in HBM / L2: the entries around a row's centre are
+// the hot ones, see profiles/rate_control.txt).  A workgroup belongs to one segment: workgroup g = (segment g / bps, part g % bps).
+// Integer partial sums per lane, then wave (shuffles), workgroup (LDS), and one 64-bit atomic per (workgroup, segment,
+// candidate): nothing here rounds, so the sums depend on neither the grid nor the order of arrival.
+struct RateTables {
+    const uint32_t *cost;
+    const int32_t *sizes, *offsets;
+    int rows, stride;
+    uint32_t bprec;
+};
+constexpr int kRateMaxRows = 1024;
+constexpr int kRateMaxCand = 32;
+
+__device__ __forceinline__ uint32_t symbol_cost(const RateTables &T, const int2 *rowinfo, int32_t row, int32_t sym)
+{
+    row = clampi(row, 0, T.rows - 1);
+    const int2 ri = rowinfo[row];   // (offset, max_value), as the encoder's enc_prepare reads them
+    const int32_t max_value = ri.y;
+    int32_t value = static_cast<int32_t>(static_cast<uint32_t>(sym) - static_cast<uint32_t>(ri.x));
+    uint32_t raw = 0;
+    bypass_split(value, max_value, raw);
+    const bool escaped = value == max_value;
+    value = clampi(value, 0, max_value);
+    uint32_t c = T.cost[static_cast<int64_t>(row) * T.stride + value];
+    if (escaped) {   // the escape code: nb digits, the count nibble, one more per maxbv digits (encode_escape)
+        const uint32_t nb = static_cast<uint32_t>(escape_digits(raw, T.bprec)), maxbv = (1u << T.bprec) - 1u;
+        c += (T.bprec * (nb + 1u + nb / maxbv)) << 16;
+    }
+    return c;
+}
+
+template <int kNC>
+__global__ __launch_bounds__(kBlock) void gc_rate_curve_kernel(const float *__restrict__ y, const float *__restrict__ scales, int64_t per_seg,
+                                                               int segs_per_image, int bps, const float *__restrict__ cand, int n_cand,
+                                                               int cand_per_image, const float *__restrict__ table, int table_len,
+                                                               float bound, RateTables T, unsigned long long *__restrict__ bits)
+{
+    extern __shared__ float s_table[];
+    __shared__ int s_unsorted;
+    __shared__ int2 s_rowinfo[kRateMaxRows];
+    __shared__ float s_cand[kRateMaxCand];
+    __shared__ unsigned long long s_red[kBlock / kWave][kRateMaxCand];
+    const int seg = blockIdx.x / bps, part = blockIdx.x - seg * bps;
+    if (threadIdx.x == 0) s_unsorted = 0;
+    for (int i = threadIdx.x; i < table_len; i += blockDim.x) s_table[i] = table[i];
+    for (int r = threadIdx.x; r < T.rows; r += blockDim.x) s_rowinfo[r] = make_int2(T.offsets[r], T.sizes[r] - 2);
+    if (static_cast<int>(threadIdx.x) < n_cand)
+        s_cand[threadIdx.x] = cand[(cand_per_image ? static_cast<int64_t>(seg / segs_per_image) * n_cand : 0) + threadIdx.x];
+    __syncthreads();
+    for (int i = threadIdx.x; i + 1 < table_len; i += blockDim.x)
+        if (!(s_table[i] <= s_table[i + 1])) s_unsorted = 1;
+    __syncthreads();
+    const bool sorted = s_unsorted == 0;
+    const float *py = y + static_cast<int64_t>(seg) * per_seg, *ps = scales + static_cast<int64_t>(seg) * per_seg;
+    unsigned long long acc[kNC];
+#pragma unroll
+    for (int k = 0; k < kNC; ++k) acc[k] = 0ull;
+    for (int64_t i = static_cast<int64_t>(part) * kBlock + threadIdx.x; i < per_seg; i += static_cast<int64_t>(bps) * kBlock) {
+        const float yv = py[i];
+        const float sb = fmaxf(ps[i], bound);   // LowerBound first, then the step
+#pragma unroll
+        for (int k = 0; k < kNC; ++k) {
+            if (k < n_cand) {
+                const float step = s_cand[k];
+                const float s = step_div(sb, step);
+                int idx;
+                if (sorted && s == s) {
+                    int lo = 0, hi = table_len - 1;   // first j in [0, len - 1) with table[j] >= s, len - 1 if none
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (s_table[mid] < s) lo = mid + 1; else hi = mid;
+                    }
+                    idx = lo;
+                } else {
+                    idx = table_len - 1;
+                    for (int j = 0; j < table_len - 1; ++j) idx -= (s <= s_table[j]) ? 1 : 0;
+                }
+                const float q = round_even(step_div(yv, step));
+                acc[k] += symbol_cost(T, s_rowinfo, idx, static_cast<int32_t>(q));
+            }
+        }
+    }
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+#pragma unroll
+    for (int k = 0; k < kNC; ++k) {
+        if (k < n_cand) {
+            unsigned long long v = acc[k];
+            for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d, kWave);
+            if (lane == 0) s_red[wave][k] = v;
+        }
+    }
+    __syncthreads();
+    if (static_cast<int>(threadIdx.x) < n_cand) {
+        unsigned long long v = 0ull;
+        for (int w = 0; w < kBlock / kWave; ++w) v += s_red[w][threadIdx.x];
+        atomicAdd(&bits[static_cast<int64_t>(seg) * n_cand + threadIdx.x], v);
+    }
+}
+
+// pred_bytes(b, k) of the byte bound; one thread per image walks its candidates in order and keeps the first that fits
+__global__ void rate_select_kernel(const unsigned long long *__restrict__ bits, int n_images, int segs_per_image, int64_t per_seg,
+                                   const float *__restrict__ cand, int n_cand, int cand_per_image, const int32_t *__restrict__ extra_words,
+                                   const int64_t *__restrict__ budget, float *__restrict__ steps_out, int32_t *__restrict__ choice,
+                                   int64_t *__restrict__ pred_bytes)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_images) return;
+    const int64_t extra = extra_words ? 4 * static_cast<int64_t>(extra_words[b]) : 0, want = budget[b];
+    int pick = -1;
+    int64_t pred = 0;
+    for (int k = 0; k < n_cand && pick < 0; ++k) {
+        pred = extra;
+        for (int l = 0; l < segs_per_image; ++l) {
+            const unsigned long long q = bits[(static_cast<int64_t>(b) * segs_per_image + l) * n_cand + k];
+            pred += 4 * (2 + static_cast<int64_t>((q + 4ull * static_cast<unsigned long long>(per_seg)) >> 21));
+        }
+        if (pred <= want) pick = k;
+    }
+    const int k = pick < 0 ? n_cand - 1 : pick;   // nothing fits: the largest step, whose prediction `pred` holds
+    choice[b] = pick < 0 ? (k | BASIC_RATE_NO_FIT) : k;
+    steps_out[b] = cand[(cand_per_image ? static_cast<int64_t>(b) * n_cand : 0) + k];
+    pred_bytes[b] = pred;
+}
+
+__global__ void rate_refine_kernel(const float *__restrict__ cand_in, int cand_per_image, int n_cand, const int32_t *__restrict__ choice,
+                                   int n_images, const float *__restrict__ t, float *__restrict__ cand_out)
+{
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_images * n_cand) return;
+    const int b = i / n_cand, j = i - b * n_cand;
+    const float *c = cand_in + (cand_per_image ? static_cast<int64_t>(b) * n_cand : 0);
+    const int32_t ch = choice[b];
+    const int k = clampi(ch & ~BASIC_RATE_NO_FIT, 0, n_cand - 1);
+    float v = c[k];
+    if (k > 0 && !(ch & BASIC_RATE_NO_FIT) && j < n_cand - 1) {
+        // plain operators under the pragma above: three roundings (the *_rn intrinsics are inline functions compiled under the
+        // build's own contraction mode, and their multiply and add would fuse here)
+        const float lo = c[k - 1], hi = v;
+        const float d = hi - lo;
+        const float p = d * t[j];
+        v = fminf(lo + p, hi);
+    }
+    cand_out[i] = v;
 }
 
 __global__ void eb_quantize_index_kernel(const float *__restrict__ z, const float *__restrict__ medians, int64_t total,
@@ -461,6 +610,72 @@ extern "C" int basic_gc_dequantize_q_dev(const int32_t *d_sym, int64_t n, int64_
     if (n == 0) return BASIC_OK;
     hipLaunchKernelGGL(gc_dequantize_q_kernel, dim3(grid_for(n)), dim3(kBlock), 0, as_stream(hip_stream), d_sym, n, per_image, d_steps,
                        n_steps, d_yhat);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_gc_rate_curve_dev(const float *d_y, const float *d_scales, int n_seg, int64_t per_seg, int segs_per_image,
+                                       const float *d_cand, int n_cand, int cand_per_image, const float *d_table, int table_len,
+                                       float scale_bound, const basic_rans_tables *t, uint64_t *d_bits, void *hip_stream)
+{
+    BASIC_REQUIRE(d_y && d_scales && d_cand && d_table && t && d_bits && table_len >= 1 && table_len <= 4096, "gc_rate_curve: bad argument");
+    BASIC_REQUIRE(n_seg >= 1 && per_seg >= 1 && segs_per_image >= 1 && n_seg % segs_per_image == 0,
+                  "gc_rate_curve: n_seg is a whole number of images of segs_per_image segments, per_seg >= 1");
+    BASIC_REQUIRE(n_cand >= 1 && n_cand <= kRateMaxCand && (cand_per_image == 0 || cand_per_image == 1),
+                  "gc_rate_curve: 1 to 32 candidates, shared (0) or one set per image (1)");
+    BASIC_REQUIRE(per_seg <= (INT64_MAX >> 22), "gc_rate_curve: per_seg * 2^22 does not fit 63 bits");
+    RansRateView v;
+    int rc = rans_rate_view(t, &v);
+    if (rc) return rc;
+    BASIC_REQUIRE(v.bypass && v.precision == 16 && v.rows <= kRateMaxRows,
+                  "gc_rate_curve: the table set must code with bypass, at precision 16, in at most 1024 rows");
+    const hipStream_t st = as_stream(hip_stream);
+    BASIC_HIP_TRY(hipMemsetAsync(d_bits, 0, sizeof(uint64_t) * static_cast<size_t>(n_seg) * n_cand, st));
+    // workgroups per segment: four elements a thread when the segment is long enough, and a grid of about 16 K workgroups at most
+    int64_t bps = (per_seg + 4 * kBlock - 1) / (4 * kBlock);
+    const int64_t cap = n_seg >= 16384 ? 1 : 16384 / n_seg;
+    if (bps > cap) bps = cap;
+    const RateTables T{v.cost, v.sizes, v.offsets, v.rows, v.stride, static_cast<uint32_t>(v.bypass_precision)};
+    const dim3 grid(static_cast<unsigned>(n_seg * bps)), block(kBlock);
+    const size_t lds = table_len * sizeof(float);
+    auto *bits = reinterpret_cast<unsigned long long *>(d_bits);
+#define BASIC_RATE_LAUNCH(NC)                                                                                                        \
+    hipLaunchKernelGGL(gc_rate_curve_kernel<NC>, grid, block, lds, st, d_y, d_scales, per_seg, segs_per_image, static_cast<int>(bps), \
+                       d_cand, n_cand, cand_per_image, d_table, table_len, scale_bound, T, bits)
+    if (n_cand <= 2) BASIC_RATE_LAUNCH(2);
+    else if (n_cand <= 8) BASIC_RATE_LAUNCH(8);
+    else if (n_cand <= 16) BASIC_RATE_LAUNCH(16);
+    else BASIC_RATE_LAUNCH(32);
+#undef BASIC_RATE_LAUNCH
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_rate_select_dev(const uint64_t *d_bits, int n_images, int segs_per_image, int64_t per_seg, const float *d_cand,
+                                     int n_cand, int cand_per_image, const int32_t *d_extra_words, const int64_t *d_budget,
+                                     float *d_steps_out, int32_t *d_choice, int64_t *d_pred_bytes, void *hip_stream)
+{
+    BASIC_REQUIRE(d_bits && d_cand && d_budget && d_steps_out && d_choice && d_pred_bytes && n_images >= 1 && segs_per_image >= 1 &&
+                      per_seg >= 1 && per_seg <= (INT64_MAX >> 22),
+                  "rate_select: bad argument");
+    BASIC_REQUIRE(n_cand >= 1 && n_cand <= kRateMaxCand && (cand_per_image == 0 || cand_per_image == 1),
+                  "rate_select: 1 to 32 candidates, shared (0) or one set per image (1)");
+    hipLaunchKernelGGL(rate_select_kernel, dim3((n_images + kWave - 1) / kWave), dim3(kWave), 0, as_stream(hip_stream),
+                       reinterpret_cast<const unsigned long long *>(d_bits), n_images, segs_per_image, per_seg, d_cand, n_cand,
+                       cand_per_image, d_extra_words, d_budget, d_steps_out, d_choice, d_pred_bytes);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_rate_refine_dev(const float *d_cand_in, int cand_per_image, int n_cand, const int32_t *d_choice, int n_images,
+                                     const float *d_t, float *d_cand_out, void *hip_stream)
+{
+    BASIC_REQUIRE(d_cand_in && d_choice && d_t && d_cand_out && n_images >= 1 && d_cand_out != d_cand_in, "rate_refine: bad argument (out of place)");
+    BASIC_REQUIRE(n_cand >= 1 && n_cand <= kRateMaxCand && (cand_per_image == 0 || cand_per_image == 1),
+                  "rate_refine: 1 to 32 candidates, shared (0) or one set per image (1)");
+    const int total = n_images * n_cand;
+    hipLaunchKernelGGL(rate_refine_kernel, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, as_stream(hip_stream), d_cand_in,
+                       cand_per_image, n_cand, d_choice, n_images, d_t, d_cand_out);
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
 }

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <mutex>
 #include <new>
 #include <type_traits>
 #include <vector>
@@ -62,6 +63,12 @@ struct basic_rans_tables {
     uint32_t *d_enc = nullptr;
     int32_t *d_rowinfo = nullptr;
     bool fast_enc_ok = false;
+    // Cost table of the rate kernels (basic_rans_cost_table_host), [rows][stride]: built on the first rate call or read-back,
+    // uploaded on the first rate call -- a set that is never rated holds neither.  cost_state: 0 = not built, 1 = built, -1 = refused.
+    mutable std::mutex cost_mu;
+    mutable std::vector<uint32_t> cost;
+    mutable uint32_t *d_cost = nullptr;
+    mutable int cost_state = 0;
 };
 
 namespace {
@@ -351,9 +358,76 @@ extern "C" int basic_rans_tables_get_cdfs(const basic_rans_tables *t, int32_t *o
     return BASIC_OK;
 }
 
+extern "C" int basic_rans_cost_table_host(const int32_t *cdfs, int rows, int stride, const int32_t *cdf_sizes, int precision, uint32_t *out)
+{
+    BASIC_REQUIRE(cdfs && cdf_sizes && out && rows >= 1 && stride >= 2 && precision >= 1 && precision <= 30, "rans_cost_table: bad argument");
+    for (int r = 0; r < rows; ++r) {
+        BASIC_REQUIRE(cdf_sizes[r] >= 2 && cdf_sizes[r] <= stride, "rans_cost_table: a row's cdf size is outside [2, stride]");
+        const int32_t *row = cdfs + static_cast<size_t>(r) * stride;
+        uint32_t *dst = out + static_cast<size_t>(r) * stride;
+        for (int v = 0; v < stride; ++v) {
+            dst[v] = 0u;
+            if (v > cdf_sizes[r] - 2) continue;
+            const int64_t freq = static_cast<int64_t>(row[v + 1]) - row[v];
+            BASIC_REQUIRE(freq > 0, "rans_cost_table: a frequency inside a row is not positive");
+            const double bits = static_cast<double>(precision) - std::log2(static_cast<double>(freq));
+            const long long q = std::llrint(bits * 65536.0);
+            dst[v] = q < 0 ? 0u : static_cast<uint32_t>(q);   // freq <= 2^precision for a valid cdf: a wider bin costs nothing
+        }
+    }
+    return BASIC_OK;
+}
+
+namespace {
+
+// the host copy of a set's cost table, built once (cost_mu held)
+int build_costs(const basic_rans_tables *t)
+{
+    if (t->cost_state == 0) {
+        t->cost.assign(static_cast<size_t>(t->rows) * t->stride, 0u);
+        const int rc = basic_rans_cost_table_host(t->cdfs.data(), t->rows, t->stride, t->sizes.data(), t->precision, t->cost.data());
+        t->cost_state = rc ? -1 : 1;
+        if (rc) { t->cost.clear(); t->cost.shrink_to_fit(); }
+    }
+    if (t->cost_state < 0) { set_error("rans cost table: a frequency inside a row of this table set is not positive"); return BASIC_ERR_INVALID; }
+    return BASIC_OK;
+}
+
+}  // namespace
+
+extern "C" int basic_rans_tables_costs(const basic_rans_tables *t, uint32_t *host_out)
+{
+    BASIC_REQUIRE(t && host_out, "ANS not initialized!");
+    std::lock_guard<std::mutex> lock(t->cost_mu);
+    const int rc = build_costs(t);
+    if (rc) return rc;
+    std::memcpy(host_out, t->cost.data(), t->cost.size() * sizeof(uint32_t));
+    return BASIC_OK;
+}
+
+int basic::rans_rate_view(const basic_rans_tables *t, RansRateView *out)
+{
+    BASIC_REQUIRE(t && out, "ANS not initialized!");
+    std::lock_guard<std::mutex> lock(t->cost_mu);
+    int rc = build_costs(t);
+    if (rc) return rc;
+    if (!t->d_cost) {
+        uint32_t *d = nullptr;
+        BASIC_HIP_TRY(hipMalloc(&d, t->cost.size() * sizeof(uint32_t)));
+        const hipError_t e = hipMemcpy(d, t->cost.data(), t->cost.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d); return hip_fail(e, "rans cost table upload", __FILE__, __LINE__); }
+        t->d_cost = d;
+    }
+    out->cost = t->d_cost; out->sizes = t->d_sizes; out->offsets = t->d_offsets;
+    out->rows = t->rows; out->stride = t->stride; out->precision = t->precision;
+    out->bypass = t->bypass ? 1 : 0; out->bypass_precision = t->bypass_precision;
+    return BASIC_OK;
+}
+
 extern "C" void basic_rans_tables_destroy(basic_rans_tables *t)
 {
     if (!t) return;
+    if (t->d_cost) (void)hipFree(t->d_cost);
     if (t->d_cdfs) (void)hipFree(t->d_cdfs);
     if (t->d_sizes) (void)hipFree(t->d_sizes);
     if (t->d_offsets) (void)hipFree(t->d_offsets);

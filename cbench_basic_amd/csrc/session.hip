@@ -121,6 +121,15 @@ struct basic_hp_session {
     HBuf h_steps;
     DBuf d_steps;
     hipEvent_t steps_done = nullptr;
+    // rate targets (basic_hp_session_set_rate_targets): empty = none.  A call uploads budgets, first grid and the refinement's t
+    // through h_rate (rate_up closes the upload), chooses the steps on the device into d_steps, and brings steps, predictions and
+    // choice words back into h_rate_out beside the stream lengths (no synchronisation of its own).
+    std::vector<int64_t> rate_budget;
+    std::vector<float> rate_cand;
+    int rate_passes = 0, rate_res_batch = 0;
+    HBuf h_rate, h_rate_out;
+    DBuf d_rate_in, d_rate_bits, d_rate_cand[2], d_rate_out;
+    hipEvent_t rate_up = nullptr;
     DBuf d_medians, d_table;
     DBuf act[2], d_x, d_y, d_z, d_zhat, d_prior, d_scales;
     DBuf z_sym, z_idx, y_sym, y_idx, seg_z, seg_y, slots_z, slots_y, nw, off, packed, words, woff, state, pos;
@@ -368,7 +377,7 @@ basic_hp_session::~basic_hp_session()
                     e = nullptr;
                 }
     }
-    for (hipEvent_t e : {in_done, enc_phase, dec_phase, fork, join, x_free, x_ready, u8_free, xhat_free, steps_done})
+    for (hipEvent_t e : {in_done, enc_phase, dec_phase, fork, join, x_free, x_ready, u8_free, xhat_free, steps_done, rate_up})
         if (e) (void)hipEventDestroy(e);
     if (side) (void)hipStreamDestroy(side);
     if (copy) (void)hipStreamDestroy(copy);
@@ -396,11 +405,48 @@ extern "C" int basic_hp_session_set_stream_lanes(basic_hp_session *s, int lanes)
 extern "C" int basic_hp_session_set_qsteps(basic_hp_session *s, const float *host_steps, int n)
 {
     BASIC_REQUIRE(s && n >= 0 && (n == 0 || host_steps), "hp_session_set_qsteps: bad argument");
+    BASIC_REQUIRE(n == 0 || s->rate_budget.empty(), "hp_session_set_qsteps: rate targets are set -- clear them first (one way to state the step at a time)");
     for (int i = 0; i < n; ++i)   // NaN fails both comparisons' conjunction, infinities the upper one
         BASIC_REQUIRE(host_steps[i] >= BASIC_QSTEP_MIN && host_steps[i] <= BASIC_QSTEP_MAX,
                       "hp_session_set_qsteps: every step must be finite and in [2^-4, 2^6]");
     s->qsteps.assign(host_steps, host_steps + n);
     s->res_batch = 0;   // a held batch was coded with the previous steps
+    return BASIC_OK;
+}
+
+extern "C" int basic_hp_session_set_rate_targets(basic_hp_session *s, const int64_t *host_budget_bytes, int n, const float *host_cand,
+                                                 int n_cand, int passes)
+{
+    BASIC_REQUIRE(s && n >= 0, "hp_session_set_rate_targets: bad argument");
+    if (n == 0) {
+        s->rate_budget.clear();
+        s->rate_cand.clear();
+        s->rate_passes = 0;
+        s->res_batch = 0;
+        return BASIC_OK;
+    }
+    BASIC_REQUIRE(host_budget_bytes && host_cand, "hp_session_set_rate_targets: bad argument");
+    BASIC_REQUIRE(s->qsteps.empty(), "hp_session_set_rate_targets: quantiser steps are set -- clear them first (one way to state the step at a time)");
+    BASIC_REQUIRE(n_cand >= 2 && n_cand <= 32 && passes >= 1 && passes <= 3, "hp_session_set_rate_targets: 2 to 32 candidates, 1 to 3 passes");
+    for (int i = 0; i < n; ++i) BASIC_REQUIRE(host_budget_bytes[i] >= 1, "hp_session_set_rate_targets: every budget must be at least one byte");
+    for (int k = 0; k < n_cand; ++k)   // NaN fails the conjunction
+        BASIC_REQUIRE(host_cand[k] >= BASIC_QSTEP_MIN && host_cand[k] <= BASIC_QSTEP_MAX && (k == 0 || host_cand[k] > host_cand[k - 1]),
+                      "hp_session_set_rate_targets: candidates must be strictly ascending and in [2^-4, 2^6]");
+    s->rate_budget.assign(host_budget_bytes, host_budget_bytes + n);
+    s->rate_cand.assign(host_cand, host_cand + n_cand);
+    s->rate_passes = passes;
+    s->res_batch = 0;   // a held batch was coded under the previous targets
+    return BASIC_OK;
+}
+
+extern "C" int basic_hp_session_rate_result(const basic_hp_session *s, float *steps, int64_t *pred_bytes, int32_t *flags, int n)
+{
+    BASIC_REQUIRE(s && n >= 1, "hp_session_rate_result: bad argument");
+    BASIC_REQUIRE(s->rate_res_batch == n, "hp_session_rate_result: the session's last call coded no rate-controlled batch of n images");
+    const char *p = static_cast<const char *>(s->h_rate_out.p);   // int64 pred [n] | float steps [n] | int32 choice [n]
+    if (pred_bytes) std::memcpy(pred_bytes, p, sizeof(int64_t) * n);
+    if (steps) std::memcpy(steps, p + sizeof(int64_t) * n, sizeof(float) * n);
+    if (flags) std::memcpy(flags, p + (sizeof(int64_t) + sizeof(float)) * n, sizeof(int32_t) * n);
     return BASIC_OK;
 }
 
@@ -421,6 +467,69 @@ namespace {
 bool qsteps_fit(const basic_hp_session *s, int batch)
 {
     return s->qsteps.empty() || s->qsteps.size() == 1 || s->qsteps.size() == static_cast<size_t>(batch);
+}
+
+// the same for the session's byte budgets
+bool budgets_fit(const basic_hp_session *s, int batch)
+{
+    return s->rate_budget.empty() || s->rate_budget.size() == 1 || s->rate_budget.size() == static_cast<size_t>(batch);
+}
+
+// Rate control of a call: the steps of its `batch` images into d_steps, chosen on the device from the curves of the y latent
+// (sy = batch * lanes streams of nyl symbols) under the budgets, the z streams' word counts (d_nw_z, written earlier on `st`)
+// counted in.  Enqueues only; the results travel to h_rate_out for the caller's next synchronisation of `st`.
+int choose_steps(basic_hp_session *s, const float *d_y, const float *d_scales, int batch, int lanes, int64_t nyl, const int32_t *d_nw_z,
+                 hipStream_t st)
+{
+    const int K = static_cast<int>(s->rate_cand.size());
+    const int sy = batch * lanes;
+    // upload: int64 budget [batch] | float cand [K] | float t [K]
+    const size_t in_bytes = sizeof(int64_t) * batch + 2 * sizeof(float) * K;
+    if (s->rate_up) BASIC_HIP_TRY(hipEventSynchronize(s->rate_up));   // the previous upload has left h_rate
+    else BASIC_HIP_TRY(hipEventCreateWithFlags(&s->rate_up, hipEventDisableTiming));
+    const size_t out_bytes = (sizeof(int64_t) + sizeof(float) + sizeof(int32_t)) * batch;
+    int rc = s->h_rate.ensure(in_bytes);
+    if (!rc) rc = s->d_rate_in.ensure(in_bytes);
+    if (!rc) rc = s->d_rate_bits.ensure(sizeof(uint64_t) * static_cast<size_t>(sy) * K);
+    if (!rc) rc = s->d_rate_cand[0].ensure(sizeof(float) * static_cast<size_t>(batch) * K);
+    if (!rc) rc = s->d_rate_cand[1].ensure(sizeof(float) * static_cast<size_t>(batch) * K);
+    if (!rc) rc = s->d_rate_out.ensure(out_bytes);
+    if (!rc) rc = s->h_rate_out.ensure(out_bytes);
+    if (!rc) rc = s->d_steps.ensure(sizeof(float) * batch);
+    if (rc) return rc;
+    int64_t *h_budget = s->h_rate.as<int64_t>();
+    for (int b = 0; b < batch; ++b) h_budget[b] = s->rate_budget[s->rate_budget.size() == 1 ? 0 : b];
+    float *h_cand = reinterpret_cast<float *>(h_budget + batch), *h_t = h_cand + K;
+    for (int k = 0; k < K; ++k) {
+        h_cand[k] = s->rate_cand[k];
+        h_t[k] = static_cast<float>(k + 1) / static_cast<float>(K);
+    }
+    BASIC_HIP_TRY(hipMemcpyAsync(s->d_rate_in.p, s->h_rate.p, in_bytes, hipMemcpyHostToDevice, st));
+    BASIC_HIP_TRY(hipEventRecord(s->rate_up, st));
+    const int64_t *d_budget = s->d_rate_in.as<int64_t>();
+    const float *d_cand = reinterpret_cast<const float *>(d_budget + batch), *d_t = d_cand + K;
+    int64_t *d_pred = s->d_rate_out.as<int64_t>();
+    float *d_steps_res = reinterpret_cast<float *>(d_pred + batch);
+    int32_t *d_choice = reinterpret_cast<int32_t *>(d_steps_res + batch);
+    int per_image = 0;
+    for (int pass = 0; pass < s->rate_passes; ++pass) {
+        if (pass > 0) {
+            float *next = s->d_rate_cand[pass & 1].as<float>();
+            rc = basic_rate_refine_dev(d_cand, per_image, K, d_choice, batch, d_t, next, st);
+            if (rc) return rc;
+            d_cand = next;
+            per_image = 1;
+        }
+        rc = basic_gc_rate_curve_dev(d_y, d_scales, sy, nyl, lanes, d_cand, K, per_image, s->d_table.as<float>(), s->n_scales,
+                                     s->scale_bound, s->y_tables, s->d_rate_bits.as<uint64_t>(), st);
+        if (!rc)
+            rc = basic_rate_select_dev(s->d_rate_bits.as<uint64_t>(), batch, lanes, nyl, d_cand, K, per_image, d_nw_z, d_budget,
+                                       d_steps_res, d_choice, d_pred, st);
+        if (rc) return rc;
+    }
+    BASIC_HIP_TRY(hipMemcpyAsync(s->d_steps.p, d_steps_res, sizeof(float) * batch, hipMemcpyDeviceToDevice, st));
+    BASIC_HIP_TRY(hipMemcpyAsync(s->h_rate_out.p, s->d_rate_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    return BASIC_OK;
 }
 
 // the steps to the device, on the stream whose kernels read them
@@ -523,7 +632,14 @@ int encode_body(basic_hp_session *s, const float *d_x, bool x_in_session, int ba
     rc = s->y_sym.ensure(sizeof(int32_t) * batch * ny);
     if (!rc) rc = s->y_idx.ensure(sizeof(int32_t) * batch * ny);
     if (rc) return rc;
-    if (s->qsteps.empty()) {
+    s->rate_res_batch = 0;
+    if (!s->rate_budget.empty()) {
+        rc = choose_steps(s, s->d_y.as<float>(), d_scales, batch, K, nyl, d_nw_z, st);
+        if (!rc)
+            rc = basic_gc_quantize_index_q_dev(s->d_y.as<float>(), d_scales, batch * ny, ny, s->d_steps.as<float>(), batch,
+                                               s->d_table.as<float>(), s->n_scales, s->scale_bound, s->y_sym.as<int32_t>(),
+                                               s->y_idx.as<int32_t>(), nullptr, st);
+    } else if (s->qsteps.empty()) {
         rc = basic_gc_quantize_index_dev(s->d_y.as<float>(), d_scales, batch * ny, s->d_table.as<float>(), s->n_scales, s->scale_bound,
                                          s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
     } else {
@@ -588,6 +704,7 @@ int encode_body(basic_hp_session *s, const float *d_x, bool x_in_session, int ba
     BASIC_HIP_TRY(hipStreamSynchronize(st));
     rc = rejoin(s, caller_st, st);
     if (rc) return rc;
+    if (!s->rate_budget.empty()) s->rate_res_batch = batch;
     s->res_batch = batch; s->res_lanes = K; s->res_zh = zh; s->res_zw = zw; s->res_yh = yh; s->res_yw = yw;
     *out_len = 4 + (12 + 4ll * batch + 4 * wz) + (12 + 4ll * sy + 4 * wy);
     if (!out) return BASIC_OK;   // the caller fetches the bytes with basic_hp_encode_result() once it knows their size
@@ -601,6 +718,7 @@ extern "C" int basic_hp_encode_images(basic_hp_session *s, const float *x, int x
 {
     BASIC_REQUIRE(s && x && out_len && batch >= 1 && h >= 1 && w >= 1, "hp_encode_images: bad argument");
     BASIC_REQUIRE(qsteps_fit(s, batch), "hp_encode_images: the session's quantiser steps are neither one nor one per image of this batch");
+    BASIC_REQUIRE(budgets_fit(s, batch), "hp_encode_images: the session's byte budgets are neither one nor one per image of this batch");
     s->res_batch = 0;
     hipStream_t st = as_stream(hip_stream);
     WavesGuard guard(s->rans_waves, s->use_token);
@@ -629,6 +747,7 @@ extern "C" int basic_hp_encode_images_u8(basic_hp_session *s, const uint8_t *x, 
     BASIC_REQUIRE(s && x && out_len && batch >= 1 && h >= 1 && w >= 1, "hp_encode_images_u8: bad argument");
     BASIC_REQUIRE(layout == BASIC_IMAGE_CHW || layout == BASIC_IMAGE_HWC, "hp_encode_images_u8: layout is BASIC_IMAGE_CHW or BASIC_IMAGE_HWC");
     BASIC_REQUIRE(qsteps_fit(s, batch), "hp_encode_images_u8: the session's quantiser steps are neither one nor one per image of this batch");
+    BASIC_REQUIRE(budgets_fit(s, batch), "hp_encode_images_u8: the session's byte budgets are neither one nor one per image of this batch");
     s->res_batch = 0;
     hipStream_t st = as_stream(hip_stream);
     WavesGuard guard(s->rans_waves, s->use_token);

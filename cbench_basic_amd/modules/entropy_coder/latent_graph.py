@@ -19,6 +19,7 @@ from typing import Any, Dict, Iterable, List, Optional
 import math
 import struct
 import time
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -378,6 +379,8 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                     if len(priors) == 1:
                         pk.update(prior=list(priors.values())[0])
                 pk.update(coder_kwargs.get(node, {}))
+                if do_encode and pk.get("rate_target") is not None:   # the budget covers what the image's earlier streams spent
+                    pk["rate_target"].extra_words = self._words_coded(data, nodes[:nodes.index(node)], node_data.shape[0])
                 with self.profiler.start_time_profile(f"latent_node_entropy_coders_{node}"):
                     if isinstance(node_data, (bytes, memoryview)):
                         node_data = coder.decode(node_data, **pk)
@@ -468,6 +471,45 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
 
     QSTEP_NODE = "y"   # the node whose coder takes the quantiser step
 
+    def _words_coded(self, data, nodes, batch):
+        """32-bit words per image in the bodies of ``nodes`` coded so far (host code; a pending body is synchronised for its lengths)."""
+        from ...nn import kernels as K
+        total = np.zeros(batch, dtype=np.int64)
+        for n in nodes:
+            body = data.get(n)
+            if hasattr(body, "_end"):
+                off = body._end()[1]
+            elif isinstance(body, (bytes, memoryview)) and len(body) >= 12:
+                off = K.unframe_streams(bytes(body))[1]
+            else:
+                continue
+            words = np.diff(np.asarray(off, dtype=np.int64))
+            if words.size % batch:
+                raise ValueError(f"node {n} holds {words.size} streams, no multiple of the batch of {batch}")
+            total += words.reshape(batch, -1).sum(1)
+        return total.astype(np.int32)
+
+    def payload_bytes(self, data, batch):
+        """Bytes of rANS payload per image in a coded string of ``batch`` images: the streams of every coded node, without the
+        framing (headers, one uint32 length per stream).  Host code, for coders that write stream bodies (write_body)."""
+        nodes = self._coded_nodes()
+        bodies = dict(zip(nodes, (bytes(v) for v in split_merged_views(data, num_segments=len(nodes)))))
+        return 4 * self._words_coded(bodies, nodes, batch).astype(np.int64)
+
+    def _rate_coder_kwargs(self, rate_target, batch):
+        """``rate_target`` of encode -> (RateTarget, the keywords of the y coder), or (None, None) without one; TypeError when the
+        graph's y coder is not the GaussianConditional coder, ValueError for an invalid request (utils/rate.py)."""
+        if rate_target is None:
+            return None, None
+        from ..prior_model.prior_coder.compressai_coder import CompressAIGaussianConditionalCoder
+        from ...utils.rate import as_rate_target
+        coder = self.latent_node_entropy_coders[self.QSTEP_NODE] if self.QSTEP_NODE in self.latent_node_entropy_coders else None
+        if type(coder) is not CompressAIGaussianConditionalCoder:
+            raise TypeError(f"rate_target= chooses the quantiser step of a CompressAIGaussianConditionalCoder at node '{self.QSTEP_NODE}'; "
+                            f"this graph codes it with {type(coder).__name__}")
+        rt = as_rate_target(rate_target, batch)
+        return rt, {self.QSTEP_NODE: dict(rate_target=rt)}
+
     def _qstep_coder_kwargs(self, qstep, batch):
         """``qstep`` of encode / decode -> (validated float32 steps, the keywords of the y coder), or (None, None) without one.
         TypeError when the graph's y coder is not the GaussianConditional coder; ValueError for invalid steps (utils/qstep.py)."""
@@ -494,18 +536,30 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             raise ValueError(f"the y body holds {ns} streams, no multiple of this coder's {lanes} stream lanes")
         return ns // lanes
 
-    def encode(self, data, *args, prior=None, qstep=None, **kwargs):
+    def encode(self, data, *args, prior=None, qstep=None, rate_target=None, **kwargs):
         """``qstep``: None -- today's codec; a number or one number per image -- the quantiser step of the y coder (INTEGRATION.md
         "Quantiser step").  Like ``output_dtype`` of decode() it is not one of ``kwargs``: it neither changes the path a call takes
         nor reaches a node generator, and both paths write the same bytes.  The string does not hold the steps: decode() needs them."""
         steps, coder_kwargs = self._qstep_coder_kwargs(qstep, data.shape[0])
+        rt, rate_kwargs = self._rate_coder_kwargs(rate_target, data.shape[0])
+        if rt is not None:
+            if steps is not None:
+                raise ValueError("rate_target= and qstep= are two ways to state the step: give one of them")
+            coder_kwargs = rate_kwargs
         with torch.no_grad():
             sess = self._fused_session(kwargs, prior) if not args else None
             if sess is not None:   # one C call: upload (when the batch is on the host), transforms, entropy stage, framing
                 if data.is_cuda and data.device != self.device:
                     data = data.to(device=self.device)
                 with self.profiler.start_time_profile("encode_fused"):
-                    if steps is None:
+                    if rt is not None:   # the steps are chosen inside the call; the choices come back with the stream lengths
+                        sess.set_rate_targets(rt.budgets, rt.candidates, rt.passes)
+                        try:
+                            out = sess.encode(data)
+                            rt.set_result(*sess.rate_result(data.shape[0]))
+                        finally:
+                            sess.set_rate_targets(None)
+                    elif steps is None:
                         out = sess.encode(data)
                     else:
                         sess.set_qsteps(steps)
@@ -533,9 +587,13 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             nodes = self._coded_nodes()
             bodies = [data_dict[n] for n in nodes]
             if any(hasattr(b, "write_into") for b in bodies):
-                return merge_bodies(bodies)  # = merge_bytes(..., num_segments=len(nodes)), bodies framed in place
-            bodies = [b.result() if hasattr(b, "result") else b for b in bodies]
-            return merge_bytes(bodies, num_segments=len(nodes))
+                out = merge_bodies(bodies)  # = merge_bytes(..., num_segments=len(nodes)), bodies framed in place
+            else:
+                bodies = [b.result() if hasattr(b, "result") else b for b in bodies]
+                out = merge_bytes(bodies, num_segments=len(nodes))
+            if rt is not None:
+                rt.resolve()
+            return out
 
     def decode(self, data, *args, prior=None, output_dtype=None, qstep=None, **kwargs):
         """``output_dtype``: None / torch.float32 -- the reconstruction as the graph gives it; torch.uint8 -- the picture,

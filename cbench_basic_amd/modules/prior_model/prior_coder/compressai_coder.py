@@ -485,6 +485,29 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
         body = PendingBody(self._tables, self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), per), y.shape[-2:])
         return body if lazy else body.result()
 
+    # ---- rate control (INTEGRATION.md "Rate control"): the steps are chosen on the device from the coder's own cost table, then
+    # it is _encode_q with them -- the bytes of encode(qstep=the chosen steps)
+    def _encode_rate(self, y, prior, rate_target, lazy):
+        from ....utils.rate import as_rate_target
+        rt = as_rate_target(rate_target, y.shape[0])
+        B = y.shape[0]
+        per = self._lane_length(y[0].numel())
+        scales = self._crop(prior, *y.shape[-2:])
+        budgets = torch.from_numpy(rt.budgets_for(B)).to(y.device)
+        extra = None
+        if rt.extra_words is not None:
+            extra = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(rt.extra_words, dtype=np.int32), (B,)))).to(y.device)
+        steps, choice, pred = K.rate_steps(y, scales, budgets, extra, rt.candidates, rt.passes, self._scale_table_dev, self._tables,
+                                           self.scale_bound, self.stream_lanes)
+        rt.set_device_result(steps, pred, choice)
+        sym, idx, _ = K.gc_quantize_index_q(y, scales, steps, self._scale_table_dev, self.scale_bound, want_yhat=False, steps_on_device=True)
+        body = PendingBody(self._tables, self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), per), y.shape[-2:])
+        if lazy:
+            return body
+        out = body.result()
+        rt.resolve()
+        return out
+
     def _decode_q(self, byte_string, prior, qstep):
         h, w, ns = K.frame_header(byte_string)
         scales = self._crop(prior, h, w)
@@ -521,8 +544,13 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
     supports_lazy_encode = True
     accepts_buffer = True  # decode() reads the stream through the buffer protocol (bytes or memoryview)
 
-    def encode(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, lazy=False, qstep=None, **kwargs):  # :377-385
+    def encode(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, lazy=False, qstep=None, rate_target=None,
+               **kwargs):  # :377-385
         self._ready()
+        if rate_target is not None:
+            if qstep is not None or channel_gains is not None or channel_gains_inv is not None:
+                raise ValueError("rate_target=, qstep= and channel_gains are three rate knobs: give one of them")
+            return self._encode_rate(y, prior, rate_target, lazy)
         if self._qstep_alone(qstep, channel_gains, channel_gains_inv):
             return self._encode_q(y, prior, qstep, lazy)
         if channel_gains is not None:

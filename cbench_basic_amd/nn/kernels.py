@@ -373,12 +373,19 @@ def _per_image(t):
     return t.shape[0], t.numel() // t.shape[0]
 
 
-def gc_quantize_index_q(y, scales, steps, table, bound=0.11, want_yhat=True):
+def gc_quantize_index_q(y, scales, steps, table, bound=0.11, want_yhat=True, steps_on_device=False):
     """gc_quantize_index under a quantiser step per image of the [B, ...] latent (basic_gc_quantize_index_q_dev):
-    sym = rint(y / step), idx from max(scale, bound) / step, yhat = sym * step.  ``steps``: see qsteps_tensor."""
+    sym = rint(y / step), idx from max(scale, bound) / step, yhat = sym * step.  ``steps``: see qsteps_tensor; with
+    ``steps_on_device`` a float32 device tensor of 1 or B steps that a kernel chose among validated candidates (rate_select), read
+    where it lies -- nothing comes back to the host."""
     y, scales, table = _dev(y, torch.float32), _dev(scales, torch.float32), _dev(table, torch.float32)
     B, per = _per_image(y)
-    steps = qsteps_tensor(steps, B, y.device)
+    if steps_on_device:
+        steps = _dev(steps, torch.float32)
+        if steps.numel() not in (1, B):
+            raise ValueError(f"{steps.numel()} quantiser steps for a batch of {B}: give one, or one per image")
+    else:
+        steps = qsteps_tensor(steps, B, y.device)
     sym = torch.empty(y.shape, device=y.device, dtype=torch.int32)
     idx = torch.empty(y.shape, device=y.device, dtype=torch.int32)
     yhat = torch.empty_like(y) if want_yhat else None
@@ -397,6 +404,112 @@ def gc_dequantize_q(sym, steps):
     _lib.check(_lib.lib().basic_gc_dequantize_q_dev(sym.data_ptr(), sym.numel(), per, steps.data_ptr(), steps.numel(), out.data_ptr(),
                                                     _stream()))
     return out
+
+
+# ---- rate control (INTEGRATION.md "Rate control"): the coder's exact table cost at K candidate steps from one read of y and sigma
+def rans_cost_table(cdfs, cdf_sizes, precision=16):
+    """basic_rans_cost_table_host: uint32 [rows][stride] bit costs (2^-16 bit) of the symbols of int32 [rows][stride] cdfs.  Host
+    code: it runs without a GPU."""
+    c = np.ascontiguousarray(cdfs, dtype=np.int32)
+    s = np.ascontiguousarray(cdf_sizes, dtype=np.int32).reshape(-1)
+    if c.ndim != 2 or s.size != c.shape[0]:
+        raise ValueError("rans_cost_table: cdfs is [rows][stride], cdf_sizes [rows]")
+    out = np.zeros(c.shape, dtype=np.uint32)
+    _lib.check(_lib.lib().basic_rans_cost_table_host(c.ctypes.data, c.shape[0], c.shape[1], s.ctypes.data, int(precision), out.ctypes.data))
+    return out
+
+
+def rans_tables_costs(tables):
+    """The cost table of a RansTables set as its rate kernels read it: uint32 [rows][max cdf length]."""
+    rows, mx = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib().basic_rans_tables_info(tables._h, ctypes.byref(rows), ctypes.byref(mx)))
+    out = np.zeros((rows.value, mx.value), dtype=np.uint32)
+    _lib.check(_lib.lib().basic_rans_tables_costs(tables._h, out.ctypes.data))
+    return out
+
+
+def _rate_cand(cand, images):
+    """-> (float32 device tensor, n_cand, cand_per_image) of a [K] (shared) or [B][K] (one grid per image) candidate tensor."""
+    cand = _dev(cand, torch.float32)
+    if cand.dim() == 1:
+        return cand, cand.shape[0], 0
+    if cand.dim() != 2 or cand.shape[0] != images:
+        raise ValueError(f"candidates are [K] or [{images}][K], got {tuple(cand.shape)}")
+    return cand, cand.shape[1], 1
+
+
+def rate_curve(y, scales, cand, table, tables, bound=0.11, lanes=1):
+    """basic_gc_rate_curve_dev on a [B, ...] latent: int64 [B * lanes][K], entry (b * lanes + l, k) = the summed table cost (2^-16 bit)
+    of lane stream l of image b at step ``cand[k]`` (``cand``: float32 device tensor [K], or [B][K] with a grid per image; the values
+    are the caller's to validate).  ``tables``: the RansTables that will code the symbols."""
+    y, scales, table = _dev(y, torch.float32), _dev(scales, torch.float32), _dev(table, torch.float32)
+    B, per = _per_image(y)
+    if scales.numel() != y.numel():
+        raise ValueError("rate_curve: y and scales must hold the same number of elements")
+    if lanes < 1 or per % lanes:
+        raise ValueError(f"rate_curve: {lanes} lanes do not divide the {per} symbols of an image")
+    cand, K, cpi = _rate_cand(cand, B)
+    bits = torch.empty((B * lanes, K), device=y.device, dtype=torch.int64)
+    _lib.check(_lib.lib().basic_gc_rate_curve_dev(y.data_ptr(), scales.data_ptr(), B * lanes, per // lanes, int(lanes), cand.data_ptr(), K, cpi,
+                                                  table.data_ptr(), table.numel(), float(bound), tables._h, bits.data_ptr(), _stream()))
+    return bits
+
+
+def rate_select(bits, per_seg, cand, budgets, extra_words=None, lanes=1):
+    """basic_rate_select_dev: (steps float32 [B], choice int32 [B], pred_bytes int64 [B]) from the curves ``bits`` int64 [B * lanes][K],
+    the candidates ([K] or [B][K]), byte budgets int64 [B] and, when given, int32 [B] words already spent per image."""
+    bits = _dev(bits, torch.int64)
+    B = bits.shape[0] // lanes
+    cand, K, cpi = _rate_cand(cand, B)
+    budgets = _dev(budgets, torch.int64)
+    if bits.dim() != 2 or bits.shape[0] != B * lanes or bits.shape[1] != K or budgets.numel() != B:
+        raise ValueError("rate_select: bits is [B * lanes][K] and budgets [B]")
+    if extra_words is not None:
+        extra_words = _dev(extra_words, torch.int32)
+        if extra_words.numel() != B:
+            raise ValueError("rate_select: extra_words is [B]")
+    steps = torch.empty((B,), device=bits.device, dtype=torch.float32)
+    choice = torch.empty((B,), device=bits.device, dtype=torch.int32)
+    pred = torch.empty((B,), device=bits.device, dtype=torch.int64)
+    _lib.check(_lib.lib().basic_rate_select_dev(bits.data_ptr(), B, int(lanes), int(per_seg), cand.data_ptr(), K, cpi,
+                                                extra_words.data_ptr() if extra_words is not None else None, budgets.data_ptr(),
+                                                steps.data_ptr(), choice.data_ptr(), pred.data_ptr(), _stream()))
+    return steps, choice, pred
+
+
+def rate_refine(cand, choice, t=None):
+    """basic_rate_refine_dev: the next grids float32 [B][K] between every image's chosen candidate and the one below it."""
+    choice = _dev(choice, torch.int32)
+    B = choice.numel()
+    cand, K, cpi = _rate_cand(cand, B)
+    if t is None:
+        from ..utils.rate import refine_t
+        t = torch.from_numpy(refine_t(K)).to(cand.device)
+    t = _dev(t, torch.float32)
+    if t.numel() != K:
+        raise ValueError("rate_refine: t is [K]")
+    out = torch.empty((B, K), device=cand.device, dtype=torch.float32)
+    _lib.check(_lib.lib().basic_rate_refine_dev(cand.data_ptr(), cpi, K, choice.data_ptr(), B, t.data_ptr(), out.data_ptr(), _stream()))
+    return out
+
+
+def rate_steps(y, scales, budgets, extra_words, candidates, passes, table, tables, bound=0.11, lanes=1, return_trace=False):
+    """curve -> select -> (refine -> curve -> select) x (passes - 1) on the device, nothing synchronised: (steps float32 [B], choice
+    int32 [B], pred_bytes int64 [B]) of the last pass.  ``candidates``: the first grid, validated on the host (utils/rate.py);
+    ``budgets``: int64 [B] device tensor.  ``return_trace``: also the list of every pass's (candidates, bits, choice)."""
+    from ..utils.rate import check_candidates, check_passes, refine_t
+    passes = check_passes(passes)
+    B, per = _per_image(y)
+    cand = torch.from_numpy(check_candidates(candidates)).to(y.device)
+    t = torch.from_numpy(refine_t(cand.numel())).to(y.device)
+    trace = []
+    for p in range(passes):
+        if p:
+            cand = rate_refine(cand, choice, t)
+        bits = rate_curve(y, scales, cand, table, tables, bound, lanes)
+        steps, choice, pred = rate_select(bits, per // lanes, cand, budgets, extra_words, lanes)
+        trace.append((cand, bits, choice))
+    return (steps, choice, pred, trace) if return_trace else (steps, choice, pred)
 
 
 def lanes_pack(sym, idx, batch, positions, channels, lanes):
@@ -896,6 +1009,25 @@ class HyperpriorSession:
         from ..utils.qstep import check_qsteps
         steps = check_qsteps(steps)
         _lib.check(_lib.lib().basic_hp_session_set_qsteps(self._h, steps.ctypes.data, int(steps.size)))
+
+    def set_rate_targets(self, budgets, candidates=None, passes=2):
+        """Byte budgets of the payloads of the calls that follow (basic_hp_session_set_rate_targets): a number or one per image;
+        ``candidates``: the first grid (utils/rate.py first_grid() by default), ``passes`` in [1, 3].  Validated on the host
+        (ValueError).  None clears them -- the session then launches what it always did."""
+        if budgets is None:
+            _lib.check(_lib.lib().basic_hp_session_set_rate_targets(self._h, None, 0, None, 0, 0))
+            return
+        from ..utils.rate import check_budgets, check_candidates, check_passes, first_grid
+        b = check_budgets(budgets)
+        c = first_grid() if candidates is None else check_candidates(candidates)
+        _lib.check(_lib.lib().basic_hp_session_set_rate_targets(self._h, b.ctypes.data, int(b.size), c.ctypes.data, int(c.size),
+                                                                check_passes(passes)))
+
+    def rate_result(self, batch):
+        """The last rate-controlled encode's (steps float32 [B], predicted payload bytes int64 [B], choice words int32 [B])."""
+        steps, pred, flags = np.zeros(batch, np.float32), np.zeros(batch, np.int64), np.zeros(batch, np.int32)
+        _lib.check(_lib.lib().basic_hp_session_rate_result(self._h, steps.ctypes.data, pred.ctypes.data, flags.ctypes.data, int(batch)))
+        return steps, pred, flags
 
     def set_transform_token(self, enable):
         """False / 0: no ordering; True / 1: the transform phases of all sessions one at a time; 2: two at a time."""

@@ -59,6 +59,13 @@ int basic_rans_tables_set_ar_ops(basic_rans_tables *t, const float *ops, int k);
 int basic_rans_tables_info(const basic_rans_tables *t, int *rows, int *max_cdf_len);
 /* get_cdfs(): out int32 [rows][out_stride], padding written as 0. */
 int basic_rans_tables_get_cdfs(const basic_rans_tables *t, int32_t *out, int out_stride);
+/* Bit cost of every table symbol in units of 2^-16 bit (rate control, section 4): pure host code, no device.
+ *     out[r][v] = llrint((precision - log2(cdf[r][v + 1] - cdf[r][v])) * 65536)   in double, v <= cdf_sizes[r] - 2; 0 beyond
+ * cdfs int32 [rows][stride], out uint32 [rows][stride].  A frequency that is not positive: BASIC_ERR_INVALID. */
+int basic_rans_cost_table_host(const int32_t *cdfs, int rows, int stride, const int32_t *cdf_sizes, int precision, uint32_t *out);
+/* The cost table of a table set, uint32 [rows][max_cdf_len] (basic_rans_tables_info), as the rate kernels read it.  A set builds
+ * and uploads it on the first rate call (or here): sets that are never rated hold nothing for it. */
+int basic_rans_tables_costs(const basic_rans_tables *t, uint32_t *host_out);
 void basic_rans_tables_destroy(basic_rans_tables *t);
 
 /* ======================================================================================
@@ -204,6 +211,38 @@ int basic_gc_quantize_index_q_dev(const float *d_y, const float *d_scales, int64
 /* d_yhat[i] = (float) d_sym[i] * step of image i / per_image: the encoder's yhat (bit for bit where d_sym[i] != 0). */
 int basic_gc_dequantize_q_dev(const int32_t *d_sym, int64_t n, int64_t per_image, const float *d_steps, int n_steps,
                               float *d_yhat, void *hip_stream);
+/* Rate control (no reference counterpart; INTEGRATION.md "Rate control"): what the rANS coder of table set t would spend on every
+ * stream at each of n_cand candidate steps, from ONE read of y and the scales.  Segment s = image b, lane l -> b * segs_per_image + l
+ * holds the per_seg contiguous elements from s * per_seg on, the streams of the batched encoder.  d_cand: float32 on the device,
+ * [n_cand] shared by all images (cand_per_image == 0) or [n_seg / segs_per_image][n_cand] (cand_per_image == 1); the values are not
+ * inspected here (the caller validates them on the host, as for d_steps above).  d_bits uint64 [n_seg][n_cand], cleared by the call:
+ *     d_bits[s][k] = sum over the segment of cost(sym, idx),  (sym, idx) = what basic_gc_quantize_index_q_dev writes at step cand[k]
+ *     value = sym - offset[idx], max = cdf_size[idx] - 2
+ *     value < 0: raw = -2 value - 1;  value >= max: raw = 2 (value - max);  either way the symbol is escaped
+ *     cost = table[idx][escaped ? max : value] + (escaped ? bypass_precision (nb + 1 + nb / maxbv) 65536 : 0)
+ *     nb = digits of bypass_precision bits in raw, maxbv = 2^bypass_precision - 1;  table = basic_rans_cost_table_host's
+ * in units of 2^-16 bit.  Integer sums: the result depends on neither the launch shape nor the order of arrival.
+ * BASIC_ERR_INVALID: n_cand outside [1, 32], n_seg no multiple of segs_per_image, tables without bypass coding, with a precision
+ * other than 16 or more than 1024 rows, per_seg * 2^22 past 63 bits. */
+int basic_gc_rate_curve_dev(const float *d_y, const float *d_scales, int n_seg, int64_t per_seg, int segs_per_image, const float *d_cand,
+                            int n_cand, int cand_per_image, const float *d_table, int table_len, float scale_bound,
+                            const basic_rans_tables *t, uint64_t *d_bits, void *hip_stream);
+/* The step of every image from its curve.  A stream of n symbols whose costs sum to bits (2^-16 bit) takes at most
+ * 2 + ((bits + 4 n) >> 21) 32-bit words (INTEGRATION.md "Rate control": the byte bound), so
+ *     pred_bytes(b, k) = 4 extra_words[b] + sum over the lanes of 4 (2 + ((bits[s][k] + 4 per_seg) >> 21))
+ * and d_choice[b] = the FIRST k in candidate order with pred_bytes(b, k) <= d_budget[b] (the curve need not be monotone); when none
+ * fits, (n_cand - 1) | BASIC_RATE_NO_FIT.  d_steps_out[b] = the chosen candidate, d_pred_bytes[b] its prediction.  d_extra_words:
+ * int32 [n_images] (e.g. the z streams' word counts) or NULL; d_budget int64 [n_images]. */
+#define BASIC_RATE_NO_FIT 0x40000000
+int basic_rate_select_dev(const uint64_t *d_bits, int n_images, int segs_per_image, int64_t per_seg, const float *d_cand, int n_cand,
+                          int cand_per_image, const int32_t *d_extra_words, const int64_t *d_budget, float *d_steps_out,
+                          int32_t *d_choice, int64_t *d_pred_bytes, void *hip_stream);
+/* The next grid, d_cand_out float32 [n_images][n_cand], between the chosen candidate k and the one below it.  k == 0 or no fit:
+ * every entry is the chosen step (the image is settled).  Otherwise lo = cand[k - 1], hi = cand[k] and
+ *     cand_out[j] = fminf(lo + (hi - lo) * t[j], hi)  for j < n_cand - 1,   cand_out[n_cand - 1] = hi
+ * subtract, multiply and add each one fp32 operation.  d_t float32 [n_cand] (the caller's (j + 1) / n_cand). */
+int basic_rate_refine_dev(const float *d_cand_in, int cand_per_image, int n_cand, const int32_t *d_choice, int n_images,
+                          const float *d_t, float *d_cand_out, void *hip_stream);
 /* Lane streams of the scan-line coder: repacks d_sym / d_idx, int32 [B][positions][channels] in coding order, to
  * [B][lanes][positions][channels / lanes] (lane k = channels [k L, (k + 1) L), L = channels / lanes), so that
  * basic_rans_encode_batch_dev codes B * lanes contiguous streams of positions * L symbols.  Out of place; lanes == 1 copies. */
@@ -439,6 +478,18 @@ int basic_hp_session_set_stream_lanes(basic_hp_session *s, int lanes);
  * format.  A call whose batch is neither n nor broadcast from n == 1 fails with BASIC_ERR_INVALID before anything is launched.
  * The steps are NOT written into the stream: the container that carries them is the caller's (codecs/qstep.py). */
 int basic_hp_session_set_qsteps(basic_hp_session *s, const float *host_steps, int n);
+/* Rate targets (section 4, "Rate control"): host_budget_bytes = n int64 byte budgets, one per image of the calls that follow or one
+ * for all (n == 1); n == 0 clears them.  A budget covers an image's payload: its z stream plus its y stream(s).  host_cand: n_cand
+ * in [2, 32] float32 candidate steps, strictly ascending, inside [BASIC_QSTEP_MIN, BASIC_QSTEP_MAX]; passes in [1, 3].  With targets
+ * set, basic_hp_encode_images[_u8] runs curve -> select -> (refine -> curve -> select) x (passes - 1) in front of the y quantiser, on
+ * the call's stream, the z streams' word counts as extra_words, and the y path reads the steps the select kernel wrote: the bytes
+ * are those of the same call under basic_hp_session_set_qsteps with these steps.  No host synchronisation is added.  Refused while
+ * quantiser steps are set, as basic_hp_session_set_qsteps is while targets are: one way to state the step at a time. */
+int basic_hp_session_set_rate_targets(basic_hp_session *s, const int64_t *host_budget_bytes, int n, const float *host_cand, int n_cand,
+                                      int passes);
+/* The last rate-controlled encode call's choices, n = its batch: the steps, the predicted payload bytes and the select kernel's
+ * d_choice word (BASIC_RATE_NO_FIT set: nothing fitted, the largest step was taken).  Any of the three may be NULL. */
+int basic_hp_session_rate_result(const basic_hp_session *s, float *steps, int64_t *pred_bytes, int32_t *flags, int n);
 /* Wavefronts (image streams) per workgroup of this session's rANS launches: 1, 2, 4, 8 or 16 (0 = library default). */
 int basic_hp_session_set_rans_waves(basic_hp_session *s, int waves_per_block);
 /* Opt this session into the process-wide "transform token": the MFMA-heavy phases (compress: everything up to the y

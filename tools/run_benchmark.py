@@ -114,8 +114,25 @@ def main(argv=None):
                     help="testing_qsteps, --codec hyperprior: one pass per quantiser step of the y coder through compress_q / decompress_q "
                          "(level prefix q<step>; 1 is the codec as trained, above 1 fewer bits); every step in [0.0625, 64].  Composes with "
                          "--uint8, --metrics-on-uint8, --workers and --stream-lanes; not with --coalesce, --tile* or --complexity-levels")
+    ap.add_argument("--target-bpp", type=float, nargs="+", default=[], metavar="R",
+                    help="testing_target_bpps, --codec hyperprior: one pass per rate target through compress_to_rate / decompress_q (level "
+                         "prefix bpp<target>): every item's step is chosen on the GPU so that its payload fits floor(R * H * W / 8) bytes.  "
+                         "Composes and refuses as --qsteps does, and does not combine with it")
     ap.add_argument("--out", required=True)
     args = ap.parse_args(argv)
+    if args.target_bpp:
+        import math
+        if args.codec != "hyperprior":
+            ap.error("--target-bpp chooses the hyperprior y coder's quantiser step: it needs --codec hyperprior")
+        for name, on in (("--qsteps", bool(args.qsteps)), ("--coalesce", args.coalesce > 1), ("--tile", args.tile is not None),
+                         ("--tile-overlap", args.tile_overlap is not None), ("--tile-pad", args.tile_pad is not None),
+                         ("--tile-pool", args.tile_pool > 0), ("--complexity-levels", bool(args.complexity_levels)),
+                         ("--rate-levels", bool(args.rate_levels)), ("--forward-pass", args.forward_pass)):
+            if on:
+                ap.error(f"--target-bpp does not combine with {name}: the target is a knob of compress_to_rate alone")
+        for r in args.target_bpp:
+            if not (math.isfinite(r) and r > 0):
+                ap.error(f"--target-bpp: every target must be positive and finite, got {r}")
     if args.qsteps:
         from cbench_basic_amd.utils.qstep import check_qsteps
         if args.codec != "hyperprior":
@@ -207,6 +224,8 @@ def main(argv=None):
             c.decompress_tiled_items(c.compress_tiled_items(batches[:args.tile_pool], tile=args.tile, overlap=args.tile_overlap, **pad))
         elif args.tile is not None:
             c.decompress_tiled(c.compress_tiled(batches[0].to("cuda"), tile=args.tile, overlap=args.tile_overlap, **pad))
+        elif args.target_bpp:   # the rate kernels' route: the cost table's upload, the session's rate buffers
+            c.decompress_q(c.compress_to_rate(batches[0].to("cuda"), target_bpp=args.target_bpp[0]))
         elif args.qsteps:   # the step kernels' route, and the session's step buffers
             c.decompress_q(c.compress_q(batches[0].to("cuda"), args.qsteps[0]))
         else:
@@ -235,6 +254,7 @@ def main(argv=None):
                                               testing_variable_rate_levels=args.rate_levels, output_dir=args.out,
                                               num_testing_workers=args.workers, testing_coalesce_items=args.coalesce, testing_tile=args.tile, testing_tile_overlap=args.tile_overlap,
                                               testing_tile_pool=args.tile_pool, testing_tile_pad=args.tile_pad, testing_qsteps=args.qsteps,
+                                              testing_target_bpps=args.target_bpp,
                                               codec_builder=(lambda: presets.seed_synthetic_weights(builders[args.codec](), seed=0)) if args.workers > 1 else None)
     if args.workers > 1 and args.warmup:   # the replicas' one-time costs too, one replica at a time (HIP-graph capture)
         pool = bench._worker_pool(batches[0], batch=max((len(c) for c in warm_chunks), default=None))
