@@ -70,6 +70,7 @@ _SIGNATURES = {
     "basic_gc_rate_curve_dev": (_I, [_P, _P, _I, _L, _I, _P, _I, _I, _P, _I, _F, _P, _P, _P]),
     "basic_rate_select_dev": (_I, [_P, _I, _I, _L, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "basic_rate_refine_dev": (_I, [_P, _I, _I, _P, _I, _P, _P, _P]),
+    "basic_rate_select_groups_dev": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "basic_hp_session_set_rate_targets": (_I, [_P, _P, _I, _P, _I, _I]),
     "basic_hp_session_rate_result": (_I, [_P, _P, _P, _P, _I]),
     "basic_eb_quantize_index_dev": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),

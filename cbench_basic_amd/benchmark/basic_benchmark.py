@@ -37,6 +37,13 @@ and a call's time is shared equally among its pictures.  It runs on the calling 
 ``testing_tile_pad`` (an int or ``(py, px)`` that divides the tile; needs ``testing_tile``; INTEGRATION.md, "Tiled pictures"): the edge
 tiles are coded at their size rounded up to multiples of py x px (``compress_tiled(..., pad_to=)``), so ``compressed_length`` is the
 BTL3 container's length.  It composes with ``testing_tile_overlap`` and ``testing_tile_pool``.
+
+``testing_tile_qsteps`` / ``testing_tile_target_bpps`` (need ``testing_tile``; INTEGRATION.md, "Tiled pictures: step and byte budget"):
+one pass per step through ``compress_tiled_q``, or per target through ``compress_tiled_to_rate`` (with ``testing_tile_pool`` their
+``_items`` forms), under the level prefixes ``tq<step>`` / ``tbpp<target>``; ``compressed_length`` is the BTQ1 container's length and
+``decompress_tiled`` reads the steps from it.  They compose with the overlap, the padding, the pool and ``metrics_on_uint8``, and are
+refused with each other, with ``testing_qsteps`` / ``testing_target_bpps`` (which stay refused with ``testing_tile``) and with what
+refuses those.
 """
 import copy
 import csv
@@ -58,7 +65,8 @@ class BasicLosslessCompressionBenchmark:
                  testing_complexity_levels=None, force_testing_device="cuda", output_dir=None, num_repeats=1,
                  num_testing_workers=0, codec_builder=None, worker_transform_token=None, testing_coalesce_items=0,
                  metrics_on_uint8=False, on_reconstruction=None, testing_tile=None, testing_tile_overlap=0, testing_tile_pool=0,
-                 testing_tile_pad=None, testing_qsteps=None, testing_target_bpps=None, **kwargs):
+                 testing_tile_pad=None, testing_qsteps=None, testing_target_bpps=None, testing_tile_qsteps=None,
+                 testing_tile_target_bpps=None, **kwargs):
         self.codec = codec
         self.dataloader = dataloader
         self.distortion_metric = distortion_metric
@@ -161,8 +169,35 @@ class BasicLosslessCompressionBenchmark:
                              ("nn_codec_use_forward_pass", bool(nn_codec_use_forward_pass))):
                 if on:
                     raise ValueError(f"testing_target_bpps does not combine with {name}: the target is a knob of compress_to_rate alone")
+        # tiled pictures under a step or a byte budget ("Tiled pictures: step and byte budget"): one pass per value
+        # through compress_tiled_q / compress_tiled_to_rate (with testing_tile_pool their _items forms), level prefixes tq<step> and
+        # tbpp<target>; decompress_tiled reads the step from the container.  They need testing_tile, and are refused with each other,
+        # with the untiled knobs above and with what refuses those
+        self.testing_tile_qsteps = [float(q) for q in (testing_tile_qsteps or [])]
+        for q in self.testing_tile_qsteps:
+            check_qsteps(q)
+        self.testing_tile_target_bpps = [float(r) for r in (testing_tile_target_bpps or [])]
+        for r in self.testing_tile_target_bpps:
+            if not r > 0 or r == float("inf"):
+                raise ValueError(f"testing_tile_target_bpps must be positive and finite, got {r}")
+            budgets_from(None, r, 1, 1 << 12, 1 << 12)
+        for mine, other in (("testing_tile_qsteps", "testing_tile_target_bpps"), ("testing_tile_target_bpps", "testing_tile_qsteps")):
+            if not getattr(self, mine):
+                continue
+            if testing_tile is None:
+                raise ValueError(f"{mine} needs testing_tile: the untiled knobs are testing_qsteps / testing_target_bpps")
+            for name, on in ((other, bool(getattr(self, other))), ("testing_qsteps", bool(self.testing_qsteps)),
+                             ("testing_target_bpps", bool(self.testing_target_bpps)),
+                             ("testing_variable_rate_levels", bool(self.testing_variable_rate_levels)),
+                             ("testing_complexity_levels", bool(self.testing_complexity_levels)),
+                             ("testing_coalesce_items", self.testing_coalesce_items > 1),
+                             ("nn_codec_use_forward_pass", bool(nn_codec_use_forward_pass))):
+                if on:
+                    raise ValueError(f"{mine} does not combine with {name}: it is a knob of the tiled calls alone")
         self._qstep = None
         self._target_bpp = None
+        self._tile_qstep = None
+        self._tile_bpp = None
         self._level_prefix = ""
         self._pictures = {}
         self._pool = None
@@ -241,6 +276,11 @@ class BasicLosslessCompressionBenchmark:
         if not isinstance(data, torch.Tensor) or data.dim() != 4 or data.shape[0] != 1:
             raise ValueError("testing_tile codes a dataset of batch-1 pictures ([1, C, H, W]); got "
                              f"{tuple(data.shape) if isinstance(data, torch.Tensor) else type(data).__name__}")
+        if self._tile_bpp is not None:
+            return codec.compress_tiled_to_rate(data, target_bpp=self._tile_bpp, tile=self.testing_tile, overlap=self.testing_tile_overlap,
+                                                **self._tile_pad)
+        if self._tile_qstep is not None:
+            return codec.compress_tiled_q(data, self._tile_qstep, tile=self.testing_tile, overlap=self.testing_tile_overlap, **self._tile_pad)
         return codec.compress_tiled(data, tile=self.testing_tile, overlap=self.testing_tile_overlap, **self._tile_pad)
 
     def _decompress(self, codec, compressed):
@@ -418,6 +458,12 @@ class BasicLosslessCompressionBenchmark:
 
     def _compress_many(self, codec, data):
         """The items of a chunk in one call: coalesced items of one shape, or pooled tiles of pictures of any sizes."""
+        if self.testing_tile_pool and self._tile_bpp is not None:
+            return codec.compress_tiled_items_to_rate(data, target_bpp=self._tile_bpp, tile=self.testing_tile,
+                                                      overlap=self.testing_tile_overlap, **self._tile_pad)
+        if self.testing_tile_pool and self._tile_qstep is not None:
+            return codec.compress_tiled_items_q(data, self._tile_qstep, tile=self.testing_tile, overlap=self.testing_tile_overlap,
+                                                **self._tile_pad)
         if self.testing_tile_pool:
             return codec.compress_tiled_items(data, tile=self.testing_tile, overlap=self.testing_tile_overlap, **self._tile_pad)
         return codec.compress_items(data, max_batch=len(data))
@@ -567,6 +613,9 @@ class BasicLosslessCompressionBenchmark:
         vr, vc = self.testing_variable_rate_levels, self.testing_complexity_levels
         # the rate axis: (rate level, quantiser step) pairs -- the codec's own levels, or the steps (never both: __init__)
         axis = [(r, None, None) for r in vr] or [(None, q, None) for q in self.testing_qsteps] or [(None, None, r) for r in self.testing_target_bpps]
+        # the tiled knobs take the same place: (None, step, target) with the tiled calls behind them
+        tiled_axis = [(None, q, None) for q in self.testing_tile_qsteps] or [(None, None, r) for r in self.testing_tile_target_bpps]
+        axis = axis or tiled_axis
         if hasattr(self.codec, "eval"):
             self.codec.eval()
         if self.force_testing_device and hasattr(self.codec, "to"):
@@ -575,7 +624,10 @@ class BasicLosslessCompressionBenchmark:
             for ci, clevel in enumerate(vc if vc else [None]):
                 rate_pts, distortion_pts = [], []
                 for ri, (rlevel, qstep, bpp) in enumerate(axis if axis else [(None, None, None)]):
-                    self._qstep, self._target_bpp = qstep, bpp
+                    if tiled_axis:
+                        self._tile_qstep, self._tile_bpp = qstep, bpp
+                    else:
+                        self._qstep, self._target_bpp = qstep, bpp
                     if clevel is not None:
                         self.codec.set_complex_level(clevel)
                     if rlevel is not None:
@@ -587,6 +639,8 @@ class BasicLosslessCompressionBenchmark:
                         self.distortion_metric.reset()
                     rate_prefix = [f"vrlevel{rlevel}"] if rlevel is not None else [f"q{qstep:g}"] if qstep is not None else \
                         [f"bpp{bpp:g}"] if bpp is not None else []
+                    if tiled_axis:
+                        rate_prefix = ["t" + rate_prefix[0]]
                     self._level_prefix = "_".join(([f"sclevel{clevel}"] if clevel is not None else []) + rate_prefix)
                     current = self._run_dataset()
                     if self.distortion_metric is not None:
@@ -621,7 +675,7 @@ class BasicLosslessCompressionBenchmark:
                     value = bj((rate_pts, distortion_pts))[bj.name]
                     metrics[bj_prefix + bj.name] = value
                     metrics_2d[prefix][bj.name] = value
-        self._qstep = self._target_bpp = None
+        self._qstep = self._target_bpp = self._tile_qstep = self._tile_bpp = None
         if metrics_2d and self.output_dir:
             self.save_metrics(metric_file=os.path.join(self.output_dir, "metrics_2d.csv"),
                               metric_data=list(metrics_2d.values()), names=list(metrics_2d.keys()), raw=False)

@@ -113,6 +113,45 @@ class GeneralCodec(HotPathModule, CodecInterface, VariableRateCodecInterface, Va
         with self.profiler.start_time_profile("time_decompress_entropy_coder"):
             return self.entropy_coder.decode_tiled_items(containers, *args, **kwargs)
 
+    # ---- tiled pictures under a quantiser step, stated or chosen for a byte budget (INTEGRATION.md "Tiled pictures: step and byte
+    # budget"; the hyperprior codec).  decompress_tiled / decompress_tiled_items read the BTQ1 containers these return.
+    def compress_tiled_q(self, image, qstep, tile=(512, 512), overlap=0, pad_to=1, max_batch=None):
+        """``compress_tiled`` under a quantiser step: ``qstep`` is one step, or one per tile in grid order.  -> a BTQ1 container
+        (utils/tiling.py), tile k's string exactly ``compress_q(P_k, step_k)[12:]`` of the tile compress_tiled cuts."""
+        with self.profiler.start_time_profile("time_compress_entropy_coder"):
+            return self.entropy_coder.encode_tiled_q(image, qstep, tile=tile, max_batch=max_batch, overlap=overlap, pad_to=pad_to)
+
+    def compress_tiled_items_q(self, pictures, qsteps, tile=(512, 512), overlap=0, pad_to=1, max_batch=None):
+        """``compress_tiled_items`` under quantiser steps, one for all or one per picture: N BTQ1 containers, each byte for byte
+        ``compress_tiled_q`` of its picture, from the same pooled calls as the step-less method."""
+        with self.profiler.start_time_profile("time_compress_entropy_coder"):
+            return self.entropy_coder.encode_tiled_items_q(pictures, qsteps, tile=tile, overlap=overlap, max_batch=max_batch, pad_to=pad_to)
+
+    def compress_tiled_to_rate(self, image, target_bytes=None, target_bpp=None, tile=(512, 512), overlap=0, pad_to=1, max_batch=None,
+                               candidates=16, passes=2, step_range=(2 ** -4, 2 ** 6), return_report=False, workspace_limit=2 << 30):
+        """``compress_tiled_q`` with the picture's ONE step chosen on the GPU so that the whole container, framing included, fits a byte
+        budget: ``target_bytes``, or ``target_bpp`` (budget = floor(bpp * H * W / 8)).  -> the container, byte for byte
+        ``compress_tiled_q(image, that step)``; with ``return_report`` also a dict of ``step``, ``predicted_bytes``,
+        ``container_bytes``, ``budget``, ``met``, ``fits``, ``n_tiles`` and per-tile ``predicted_payload`` / ``payload``.  When nothing
+        fits the picture takes the largest step and ``met`` is False.  ValueError, before anything is launched, for an invalid request,
+        a budget not above the framing, or latents past ``workspace_limit`` bytes."""
+        with self.profiler.start_time_profile("time_compress_entropy_coder"):
+            return self.entropy_coder.encode_tiled_to_rate(image, target_bytes=target_bytes, target_bpp=target_bpp, tile=tile, overlap=overlap,
+                                                           pad_to=pad_to, max_batch=max_batch, candidates=candidates, passes=passes,
+                                                           step_range=step_range, return_report=return_report,
+                                                           workspace_limit=workspace_limit)
+
+    def compress_tiled_items_to_rate(self, pictures, target_bytes=None, target_bpp=None, tile=(512, 512), overlap=0, pad_to=1,
+                                     max_batch=None, candidates=16, passes=2, step_range=(2 ** -4, 2 ** 6), return_report=False,
+                                     workspace_limit=2 << 30):
+        """``compress_tiled_to_rate`` of N pictures, one target for all or one each, the tiles pooled as in ``compress_tiled_items``:
+        N containers, each byte for byte ``compress_tiled_to_rate`` of its picture alone; the reports come as a list."""
+        with self.profiler.start_time_profile("time_compress_entropy_coder"):
+            return self.entropy_coder.encode_tiled_items_to_rate(pictures, target_bytes=target_bytes, target_bpp=target_bpp, tile=tile,
+                                                                 overlap=overlap, pad_to=pad_to, max_batch=max_batch, candidates=candidates,
+                                                                 passes=passes, step_range=step_range, return_report=return_report,
+                                                                 workspace_limit=workspace_limit)
+
     @property
     def last_items_calls(self):
         return self.entropy_coder.last_items_calls

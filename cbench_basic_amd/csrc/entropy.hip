@@ -269,6 +269,86 @@ __global__ void rate_select_kernel(const unsigned long long *__restrict__ bits, 
     pred_bytes[b] = pred;
 }
 
+// rate_select_kernel for groups of tiles (a tiled picture's budget is one number over all its tiles): workgroup g owns group g, its
+// threads stride over the group's tiles with one 64-bit sum per candidate each, the sums meet in the wave (shuffles) and in the
+// workgroup (LDS), thread 0 walks the candidates, and every thread writes its tiles' step and prediction at the chosen one.
+// Integer sums only: the result depends on neither the block width nor the order.  The plan arrays are the entry point's own
+// validated upload.
+constexpr int kGroupMaxBlock = 1024;
+
+__device__ __forceinline__ int64_t tile_pred_bytes(const unsigned long long *__restrict__ bits, int first_seg, int lanes, int64_t per_seg,
+                                                   int32_t extra_words, int n_cand, int k)
+{
+    int64_t pred = 4 * static_cast<int64_t>(extra_words);
+    for (int l = 0; l < lanes; ++l) {
+        const unsigned long long q = bits[static_cast<int64_t>(first_seg + l) * n_cand + k];
+        pred += 4 * (2 + static_cast<int64_t>((q + 4ull * static_cast<unsigned long long>(per_seg)) >> 21));
+    }
+    return pred;
+}
+
+template <int kNC>
+__global__ __launch_bounds__(kGroupMaxBlock) void rate_select_groups_kernel(
+    const unsigned long long *__restrict__ bits, int lanes, const int32_t *__restrict__ tile_first_seg,
+    const int64_t *__restrict__ tile_per_seg, const int32_t *__restrict__ tile_extra_words, const int32_t *__restrict__ group_first,
+    const int32_t *__restrict__ group_tiles, const float *__restrict__ cand, int n_cand, int cand_per_group,
+    const int64_t *__restrict__ budget, float *__restrict__ steps_out, int32_t *__restrict__ choice, int64_t *__restrict__ pred_bytes,
+    float *__restrict__ tile_steps, int64_t *__restrict__ tile_pred)
+{
+    __shared__ long long s_red[kGroupMaxBlock / kWave][kRateMaxCand];
+    __shared__ long long s_pred[kRateMaxCand];
+    __shared__ int s_pick;
+    const int g = blockIdx.x;
+    const int t0 = group_first[g], t1 = group_first[g + 1];
+    long long acc[kNC];
+#pragma unroll
+    for (int k = 0; k < kNC; ++k) acc[k] = 0;
+    for (int i = t0 + static_cast<int>(threadIdx.x); i < t1; i += static_cast<int>(blockDim.x)) {
+        const int t = group_tiles[i];
+        const int first = tile_first_seg[t];
+        const int64_t per = tile_per_seg[t];
+        const int32_t extra = tile_extra_words ? tile_extra_words[t] : 0;
+#pragma unroll
+        for (int k = 0; k < kNC; ++k)
+            if (k < n_cand) acc[k] += tile_pred_bytes(bits, first, lanes, per, extra, n_cand, k);
+    }
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, n_waves = (blockDim.x + kWave - 1) / kWave;
+#pragma unroll
+    for (int k = 0; k < kNC; ++k) {
+        if (k < n_cand) {
+            long long v = acc[k];
+            for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d, kWave);
+            if (lane == 0) s_red[wave][k] = v;
+        }
+    }
+    __syncthreads();
+    if (static_cast<int>(threadIdx.x) < n_cand) {
+        long long v = 0;
+        for (int w = 0; w < n_waves; ++w) v += s_red[w][threadIdx.x];
+        s_pred[threadIdx.x] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int64_t want = budget[g];
+        int pick = -1;
+        for (int k = 0; k < n_cand && pick < 0; ++k)
+            if (s_pred[k] <= want) pick = k;
+        const int k = pick < 0 ? n_cand - 1 : pick;   // nothing fits: the largest step and its prediction
+        choice[g] = pick < 0 ? (k | BASIC_RATE_NO_FIT) : k;
+        pred_bytes[g] = s_pred[k];
+        s_pick = k;
+    }
+    __syncthreads();
+    const int k = s_pick;
+    const float step = cand[(cand_per_group ? static_cast<int64_t>(g) * n_cand : 0) + k];
+    if (threadIdx.x == 0) steps_out[g] = step;
+    for (int i = t0 + static_cast<int>(threadIdx.x); i < t1; i += static_cast<int>(blockDim.x)) {
+        const int t = group_tiles[i];
+        tile_steps[t] = step;
+        tile_pred[t] = tile_pred_bytes(bits, tile_first_seg[t], lanes, tile_per_seg[t], tile_extra_words ? tile_extra_words[t] : 0, n_cand, k);
+    }
+}
+
 __global__ void rate_refine_kernel(const float *__restrict__ cand_in, int cand_per_image, int n_cand, const int32_t *__restrict__ choice,
                                    int n_images, const float *__restrict__ t, float *__restrict__ cand_out)
 {
@@ -663,6 +743,63 @@ extern "C" int basic_rate_select_dev(const uint64_t *d_bits, int n_images, int s
     hipLaunchKernelGGL(rate_select_kernel, dim3((n_images + kWave - 1) / kWave), dim3(kWave), 0, as_stream(hip_stream),
                        reinterpret_cast<const unsigned long long *>(d_bits), n_images, segs_per_image, per_seg, d_cand, n_cand,
                        cand_per_image, d_extra_words, d_budget, d_steps_out, d_choice, d_pred_bytes);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_rate_select_groups_dev(const uint64_t *d_bits, int n_seg, int lanes, int n_tiles, const int32_t *host_tile_first_seg,
+                                            const int64_t *host_tile_per_seg, const int32_t *d_tile_extra_words, int n_groups,
+                                            const int32_t *host_group_first, const int32_t *host_group_tiles, void *d_plan,
+                                            const float *d_cand, int n_cand, int cand_per_group, const int64_t *d_budget,
+                                            float *d_steps_out, int32_t *d_choice, int64_t *d_pred_bytes, float *d_tile_steps,
+                                            int64_t *d_tile_pred, int block_threads, void *hip_stream)
+{
+    BASIC_REQUIRE(d_bits && host_tile_first_seg && host_tile_per_seg && host_group_first && host_group_tiles && d_plan && d_cand &&
+                      d_budget && d_steps_out && d_choice && d_pred_bytes && d_tile_steps && d_tile_pred,
+                  "rate_select_groups: a null pointer");
+    BASIC_REQUIRE(reinterpret_cast<uintptr_t>(d_plan) % sizeof(int64_t) == 0, "rate_select_groups: d_plan must be 8-byte aligned");
+    BASIC_REQUIRE(n_seg >= 1 && lanes >= 1 && n_tiles >= 1 && n_groups >= 1, "rate_select_groups: n_seg, lanes, n_tiles and n_groups are >= 1");
+    BASIC_REQUIRE(n_cand >= 1 && n_cand <= kRateMaxCand && (cand_per_group == 0 || cand_per_group == 1),
+                  "rate_select_groups: 1 to 32 candidates, shared (0) or one set per group (1)");
+    if (block_threads == 0) block_threads = kBlock;
+    BASIC_REQUIRE(block_threads >= kWave && block_threads <= kGroupMaxBlock && block_threads % kWave == 0,
+                  "rate_select_groups: block_threads is 0 (the default) or a multiple of 64 in [64, 1024]");
+    for (int t = 0; t < n_tiles; ++t) {
+        BASIC_REQUIRE(host_tile_first_seg[t] >= 0 && static_cast<int64_t>(host_tile_first_seg[t]) + lanes <= n_seg,
+                      "rate_select_groups: a tile's segments leave the curve tensor");
+        BASIC_REQUIRE(host_tile_per_seg[t] >= 1 && host_tile_per_seg[t] <= (INT64_MAX >> 22), "rate_select_groups: a tile's per_seg is out of range");
+    }
+    BASIC_REQUIRE(host_group_first[0] == 0 && host_group_first[n_groups] <= n_tiles, "rate_select_groups: group_first starts at 0 and lists at most n_tiles");
+    for (int g = 0; g < n_groups; ++g)
+        BASIC_REQUIRE(host_group_first[g + 1] > host_group_first[g], "rate_select_groups: an empty group");
+    const int listed = host_group_first[n_groups];
+    std::string seen(static_cast<size_t>(n_tiles), '\0');
+    for (int i = 0; i < listed; ++i) {
+        const int t = host_group_tiles[i];
+        BASIC_REQUIRE(t >= 0 && t < n_tiles, "rate_select_groups: a tile index out of range");
+        BASIC_REQUIRE(!seen[t], "rate_select_groups: a tile listed twice");
+        seen[t] = 1;
+    }
+    // the plan as the kernel reads it: int64 per_seg [T] | int32 first_seg [T] | int32 group_first [G + 1] | int32 group_tiles [listed]
+    const hipStream_t st = as_stream(hip_stream);
+    char *plan = static_cast<char *>(d_plan);
+    const size_t o_first = sizeof(int64_t) * n_tiles, o_gfirst = o_first + sizeof(int32_t) * n_tiles,
+                 o_gtiles = o_gfirst + sizeof(int32_t) * (n_groups + 1);
+    BASIC_HIP_TRY(hipMemcpyAsync(plan, host_tile_per_seg, sizeof(int64_t) * n_tiles, hipMemcpyHostToDevice, st));
+    BASIC_HIP_TRY(hipMemcpyAsync(plan + o_first, host_tile_first_seg, sizeof(int32_t) * n_tiles, hipMemcpyHostToDevice, st));
+    BASIC_HIP_TRY(hipMemcpyAsync(plan + o_gfirst, host_group_first, sizeof(int32_t) * (n_groups + 1), hipMemcpyHostToDevice, st));
+    BASIC_HIP_TRY(hipMemcpyAsync(plan + o_gtiles, host_group_tiles, sizeof(int32_t) * listed, hipMemcpyHostToDevice, st));
+    const dim3 grid(static_cast<unsigned>(n_groups)), block(static_cast<unsigned>(block_threads));
+#define BASIC_GROUPS_LAUNCH(NC)                                                                                                          \
+    hipLaunchKernelGGL(rate_select_groups_kernel<NC>, grid, block, 0, st, reinterpret_cast<const unsigned long long *>(d_bits), lanes,     \
+                       reinterpret_cast<const int32_t *>(plan + o_first), reinterpret_cast<const int64_t *>(plan), d_tile_extra_words,    \
+                       reinterpret_cast<const int32_t *>(plan + o_gfirst), reinterpret_cast<const int32_t *>(plan + o_gtiles), d_cand,    \
+                       n_cand, cand_per_group, d_budget, d_steps_out, d_choice, d_pred_bytes, d_tile_steps, d_tile_pred)
+    if (n_cand <= 2) BASIC_GROUPS_LAUNCH(2);
+    else if (n_cand <= 8) BASIC_GROUPS_LAUNCH(8);
+    else if (n_cand <= 16) BASIC_GROUPS_LAUNCH(16);
+    else BASIC_GROUPS_LAUNCH(32);
+#undef BASIC_GROUPS_LAUNCH
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
 }

@@ -751,11 +751,33 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         ix = torch.arange(x, x + w, device=picture.device).clamp_(max=W - 1)
         return picture[:, :, iy[:, None], ix[None, :]]
 
-    def _encode_pooled(self, pictures, grids, framing, max_batch, args=(), kwargs=None):
-        """The tile strings of ``pictures`` (on the device) over ``grids``, ``[picture][tile]``: the pooled plan (utils.tiling.pool_tiles)
-        when ``framing`` splits a batch's string, one encode() per tile otherwise.  Counts into ``last_items_calls``."""
+    def _pooled_batches(self, pictures, grids, max_batch):
+        """The pooled plan over ``pictures`` (on the device): yields (refs, batch) per chunk of utils.tiling.pool_tiles, uint8 pictures
+        first -- ``refs`` the chunk's PooledTiles with ``picture`` an index into ``pictures``, ``batch`` the one tile as it is cut out of
+        its picture (a chunk of one) or the chunk's float32 batch (uint8 tiles cut by one image_tiles_gather launch)."""
         from ...nn import kernels as K
         from ...utils import tiling
+        for dtype in (torch.uint8, torch.float32):
+            own = [p for p, x in enumerate(pictures) if x.dtype == dtype]
+            padded = any(grids[p].pad_to != (1, 1) for p in own)
+            for chunk in tiling.pool_tiles([grids[p] for p in own], max_batch):
+                refs = [t._replace(picture=own[t.picture]) for t in chunk.tiles]
+                if len(refs) == 1:
+                    p, k, y, x = refs[0]
+                    batch = self._padded_tile(pictures[p], y, x, chunk.h, chunk.w)
+                elif dtype == torch.uint8:
+                    batch = K.image_tiles_gather(pictures, refs, chunk.h, chunk.w, pad=padded)
+                else:
+                    batch = torch.empty((len(refs), pictures[own[0]].shape[1], chunk.h, chunk.w), dtype=dtype, device=self.device)
+                    for j, (p, _, y, x) in enumerate(refs):
+                        batch[j].copy_(self._padded_tile(pictures[p], y, x, chunk.h, chunk.w)[0])
+                yield refs, batch
+
+    def _encode_pooled(self, pictures, grids, framing, max_batch, args=(), kwargs=None, steps=None):
+        """The tile strings of ``pictures`` (on the device) over ``grids``, ``[picture][tile]``: the pooled plan (utils.tiling.pool_tiles)
+        when ``framing`` splits a batch's string, one encode() per tile otherwise.  Counts into ``last_items_calls``.
+        ``steps[p]``: float32, the quantiser step of every tile of picture p; a chunk's steps reach its encode() as ``qstep=``, an
+        explicit keyword, so they change neither the plan nor the number of calls."""
         kwargs = kwargs or {}
         strings = [[None] * len(g) for g in grids]
         with torch.no_grad(), torch.cuda.device(self.device):
@@ -766,24 +788,14 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                         self.last_items_calls += 1
                         strings[p][k] = self.encode(self._padded_tile(pictures[p], y, x, *g.coded_size(k)), *args, **kwargs)
                 return strings
-            for dtype in (torch.uint8, torch.float32):
-                own = [p for p, x in enumerate(pictures) if x.dtype == dtype]
-                padded = any(grids[p].pad_to != (1, 1) for p in own)
-                for chunk in tiling.pool_tiles([grids[p] for p in own], max_batch):
-                    refs = [t._replace(picture=own[t.picture]) for t in chunk.tiles]
-                    self.last_items_calls += 1
-                    if len(refs) == 1:
-                        p, k, y, x = refs[0]
-                        strings[p][k] = self.encode(self._padded_tile(pictures[p], y, x, chunk.h, chunk.w))
-                        continue
-                    if dtype == torch.uint8:
-                        batch = K.image_tiles_gather(pictures, refs, chunk.h, chunk.w, pad=padded)
-                    else:
-                        batch = torch.empty((len(refs), pictures[own[0]].shape[1], chunk.h, chunk.w), dtype=dtype, device=self.device)
-                        for j, (p, _, y, x) in enumerate(refs):
-                            batch[j].copy_(self._padded_tile(pictures[p], y, x, chunk.h, chunk.w)[0])
-                    for (p, k, _, _), one in zip(refs, self._split_string(self.encode(batch), len(refs), framing)):
-                        strings[p][k] = one
+            for refs, batch in self._pooled_batches(pictures, grids, max_batch):
+                self.last_items_calls += 1
+                stated = {} if steps is None else dict(qstep=np.array([steps[p][k] for p, k, _, _ in refs], dtype=np.float32))
+                if len(refs) == 1:
+                    strings[refs[0].picture][refs[0].index] = self.encode(batch, **stated)
+                    continue
+                for (p, k, _, _), one in zip(refs, self._split_string(self.encode(batch, **stated), len(refs), framing)):
+                    strings[p][k] = one
         return strings
 
     def encode_tiled(self, image, *args, tile=(512, 512), max_batch=None, overlap=0, pad_to=1, **kwargs) -> bytes:
@@ -799,28 +811,43 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         the container is BTL3, and decode_tiled crops.  The tiles then take the pooled plan over this one picture (tiles of one coded
         size share calls of at most ``max_batch``, cut by nn.kernels.image_tiles_gather), so ``pad_to=tile`` codes a picture as one
         group.  With 1, the default, nothing is padded and nothing changes."""
-        from ...nn import kernels as K
         from ...utils import tiling
-        self._check_item(image)
-        if image.dtype not in (torch.uint8, torch.float32):
-            raise TypeError(f"a picture is torch.uint8 or torch.float32, not {image.dtype}")
+        self._check_picture(image)
         _, C, H, W = image.shape
         grid = tiling.TileGrid(H, W, *self._tile_size(tile), overlap=overlap, pad_to=pad_to)
-        self.last_items_calls = 0
         framing = self._items_framing() if not (args or kwargs or self.training) else None
+        out = self._encode_tiles(image, grid, framing, max_batch, args, kwargs)
+        return tiling.pack_tiled(C, H, W, grid.th, grid.tw, out, overlap=grid.overlap, pad_to=grid.pad_to)
+
+    @classmethod
+    def _check_picture(cls, image):
+        cls._check_item(image)
+        if image.dtype not in (torch.uint8, torch.float32):
+            raise TypeError(f"a picture is torch.uint8 or torch.float32, not {image.dtype}")
+
+    def _encode_tiles(self, image, grid, framing, max_batch, args=(), kwargs=None, steps=None):
+        """The tile strings of one picture over ``grid``, by encode_tiled's plan.  ``steps``: float32, one quantiser step per tile --
+        ``qstep=`` of the encode() call that codes the tile, an explicit keyword: the plan and ``last_items_calls`` are the step-less
+        call's."""
+        from ...nn import kernels as K
+        from ...utils import tiling
+        kwargs = kwargs or {}
+        C = image.shape[1]
+        self.last_items_calls = 0
         if image.device != self.device:
             image = image.to(device=self.device)   # once, as it lies: a dense picture keeps its strides
         if grid.pad_to != (1, 1):
-            out, = self._encode_pooled([image], [grid], framing, max_batch, args, kwargs)
-            return tiling.pack_tiled(C, H, W, grid.th, grid.tw, out, overlap=grid.overlap, pad_to=grid.pad_to)
+            out, = self._encode_pooled([image], [grid], framing, max_batch, args, kwargs, steps=None if steps is None else [steps])
+            return out
         out = [None] * len(grid)
         with torch.no_grad():
             for group in grid.groups():
                 for sub in tiling.split_group(group, 1 if framing is None else max_batch):
                     self.last_items_calls += 1
+                    stated = {} if steps is None else dict(qstep=np.ascontiguousarray(steps[list(sub.indices)], dtype=np.float32))
                     if len(sub.indices) == 1:
                         y, x = sub.y0, sub.x0
-                        out[sub.indices[0]] = self.encode(image[:, :, y:y + sub.h, x:x + sub.w], *args, **kwargs)
+                        out[sub.indices[0]] = self.encode(image[:, :, y:y + sub.h, x:x + sub.w], *args, **stated, **kwargs)
                         continue
                     if image.dtype == torch.uint8:
                         batch = K.image_tiles_to_f32(image, sub)
@@ -829,9 +856,9 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                         for j in range(len(sub.indices)):
                             y, x = sub.y0 + j // sub.nx * sub.step_y, sub.x0 + j % sub.nx * sub.step_x
                             batch[j].copy_(image[0, :, y:y + sub.h, x:x + sub.w])
-                    for k, one in zip(sub.indices, self._split_string(self.encode(batch), len(sub.indices), framing)):
+                    for k, one in zip(sub.indices, self._split_string(self.encode(batch, **stated), len(sub.indices), framing)):
                         out[k] = one
-        return tiling.pack_tiled(C, H, W, grid.th, grid.tw, out, overlap=grid.overlap)
+        return out
 
     def decode_tiled(self, data, *args, output_dtype=torch.uint8, layout="chw", region=None, max_batch=None, **kwargs):
         """A container of encode_tiled -> the picture ``[1, C, H, W]`` at its own size: every tile's ``self.decode(string)``, cropped
@@ -853,7 +880,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             raise TypeError(f"output_dtype is torch.float32 or torch.uint8, not {output_dtype}")
         if layout not in K.IMAGE_LAYOUTS:
             raise ValueError(f"layout is 'chw' or 'hwc', not {layout!r}")
-        head = tiling.unpack_tiled_full(data)
+        head, steps = self._unpack_tiled(data)
         C, H, W, th, tw, overlap, pad_to, strings = head
         grid = tiling.TileGrid(H, W, th, tw, overlap, pad_to)
         if region is None:
@@ -879,16 +906,17 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                 canvas = torch.empty((1, C, ch, cw), dtype=dtype, device=self.device)
             if grid.pad_to != (1, 1):
                 self._decode_pooled([head], [grid], [canvas], framing, max_batch, as_u8, picks=[{k for g in groups for k in g.indices}],
-                                    origins=[(cy0, cx0)], regions=[(ry0, rx0, ry1, rx1)], args=args, kwargs=kwargs)
+                                    origins=[(cy0, cx0)], regions=[(ry0, rx0, ry1, rx1)], args=args, kwargs=kwargs, steps=[steps])
                 groups = []
             for group in groups:
                 for sub in tiling.split_group(group, 1 if framing is None else max_batch):
                     self.last_items_calls += 1
                     self.last_tiles_decoded += len(sub.indices)
+                    stated = {} if steps is None else dict(qstep=np.ascontiguousarray(steps[list(sub.indices)], dtype=np.float32))
                     if len(sub.indices) == 1:
-                        rec = self.decode(strings[sub.indices[0]], *args, **kwargs)
+                        rec = self.decode(strings[sub.indices[0]], *args, **stated, **kwargs)
                     else:
-                        rec = self.decode(self._merge_strings([strings[k] for k in sub.indices], framing))
+                        rec = self.decode(self._merge_strings([strings[k] for k in sub.indices], framing), **stated)
                     if rec.dim() != 4 or rec.shape[0] != len(sub.indices) or rec.shape[1] != C or rec.shape[2] < sub.h or rec.shape[3] < sub.w:
                         raise ValueError(f"tiles of [{len(sub.indices)}, {C}, {sub.h}, {sub.w}] decoded to {tuple(rec.shape)}")
                     if blend:
@@ -907,16 +935,29 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             return canvas
         return canvas[:, :, ry0 - cy0:ry1 - cy0, rx0 - cx0:rx1 - cx0]
 
-    def _decode_pooled(self, heads, grids, canvases, framing, max_batch, as_u8, picks=None, origins=None, regions=None, args=(), kwargs=None):
+    @staticmethod
+    def _unpack_tiled(data):
+        """(TiledPicture, steps) of a container, by its magic: BTL1 - BTL3 state no steps (None); BTQ1 states one per tile (float32 [n]),
+        validated with the rest of the container before anything is launched (utils/tiling.py)."""
+        from ...utils import tiling
+        if bytes(data[:4]) == tiling.MAGIC_Q:
+            t = tiling.unpack_tiled_q(data)
+            return tiling.TiledPicture(*t[:8]), t.steps
+        return tiling.unpack_tiled_full(data), None
+
+    def _decode_pooled(self, heads, grids, canvases, framing, max_batch, as_u8, picks=None, origins=None, regions=None, args=(), kwargs=None,
+                       steps=None):
         """The pooled decode: the tiles of the containers ``heads`` (utils.tiling.TiledPicture; ``grids`` their TileGrids) decoded in calls
         shared by tiles of one coded size whose strings' own headers agree, each reconstruction cropped to its tile's valid rectangle
         and written into ``canvases[p]``.  ``picks[p]``: the tile numbers of picture p to decode (default: all); ``origins[p]``: where
         canvas p's first sample lies in picture p (default: (0, 0)); ``regions[p]``: the rectangle an overlapped picture's blend launch
         writes (default: the picture; the canvas is then that rectangle).  ``framing`` None: one decode() per tile, with the call's
-        arguments.  Counts into ``last_items_calls`` and ``last_tiles_decoded``."""
+        arguments.  Counts into ``last_items_calls`` and ``last_tiles_decoded``.  ``steps[p]``: None, or the quantiser steps of picture
+        p's tiles (a BTQ1 container); such tiles share calls among themselves only, and a call's steps reach decode() as ``qstep=``."""
         from ...nn import kernels as K
         from ...utils import tiling
         kwargs = kwargs or {}
+        steps = steps or [None] * len(heads)
         strings = [t.strings for t in heads]
         blend = [g.overlap != (0, 0) for g in grids]
         # the planner's chunks of one size each, refined by what the strings say about themselves, then cut at max_batch
@@ -929,7 +970,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             by_key = {}
             for t in tiles:
                 segs = split_merged_bytes(strings[t.picture][t.index], num_segments=len(framing))
-                key = (heads[t.picture][0],) + tuple(c.item_shape(seg, **ctx) if hasattr(c, "item_shape") else None
+                key = (heads[t.picture][0], steps[t.picture] is not None) + tuple(c.item_shape(seg, **ctx) if hasattr(c, "item_shape") else None
                                                      for (c, ctx), seg in zip(framing, segs))
                 by_key.setdefault(key, []).append(t)
             for tiles in by_key.values():
@@ -943,10 +984,11 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         for h, w, tiles in chunks:
             self.last_items_calls += 1
             self.last_tiles_decoded += len(tiles)
+            stated = {} if steps[tiles[0].picture] is None else dict(qstep=np.array([steps[t.picture][t.index] for t in tiles], dtype=np.float32))
             if len(tiles) == 1:
-                rec = self.decode(strings[tiles[0].picture][tiles[0].index], *args, **kwargs)
+                rec = self.decode(strings[tiles[0].picture][tiles[0].index], *args, **stated, **kwargs)
             else:
-                rec = self.decode(self._merge_strings([strings[t.picture][t.index] for t in tiles], framing))
+                rec = self.decode(self._merge_strings([strings[t.picture][t.index] for t in tiles], framing), **stated)
             C = heads[tiles[0].picture][0]
             if rec.dim() != 4 or rec.shape[0] != len(tiles) or rec.shape[1] != C or rec.shape[2] < h or rec.shape[3] < w:
                 raise ValueError(f"tiles of [{len(tiles)}, {C}, {h}, {w}] decoded to {tuple(rec.shape)}")
@@ -1041,7 +1083,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                 calls += self.last_items_calls
             self.last_items_calls = calls
             return out
-        heads = [tiling.unpack_tiled_full(data) for data in containers]
+        heads, steps = zip(*(self._unpack_tiled(data) for data in containers)) if containers else ((), ())
         grids = [tiling.TileGrid(t.H, t.W, t.th, t.tw, t.overlap, t.pad_to) for t in heads]
         as_u8 = output_dtype == torch.uint8
         dtype = torch.uint8 if as_u8 else torch.float32
@@ -1053,8 +1095,196 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                     canvases.append(torch.empty((1, t.H, t.W, t.channels), dtype=dtype, device=self.device).permute(0, 3, 1, 2))
                 else:
                     canvases.append(torch.empty((1, t.channels, t.H, t.W), dtype=dtype, device=self.device))
-            self._decode_pooled(heads, grids, canvases, framing, max_batch, as_u8)
+            self._decode_pooled(heads, grids, canvases, framing, max_batch, as_u8, steps=list(steps))
         return canvases
+
+    # ---- tiled pictures under a quantiser step, stated or chosen per picture for a byte budget (INTEGRATION.md "Tiled pictures: step
+    # and byte budget").  New entry points: encode_tiled / encode_tiled_items and their containers do not change.
+    def _tiled_q_framing(self):
+        """The item framing of a stepped tiled call, refusals first: ValueError in training mode and when a coder cannot give every
+        image its own body, TypeError when the y coder takes no step."""
+        if self.training:
+            raise ValueError("tiled coding under a quantiser step is an inference call: the codec is in training mode")
+        self._qstep_coder_kwargs(1.0, 1)   # TypeError: not a GaussianConditional y coder
+        framing = self._items_framing()
+        if framing is None:
+            raise ValueError("tiled coding under a quantiser step needs coders that split a batch's string into its images' (split_items)")
+        return framing
+
+    def encode_tiled_q(self, image, qstep, tile=(512, 512), max_batch=None, overlap=0, pad_to=1) -> bytes:
+        """encode_tiled under a quantiser step of the y latent: ``qstep`` is one step for the picture, or one per tile in grid
+        (row-major) order.  -> the BTQ1 container (utils/tiling.py), tile k's string EXACTLY ``self.encode(P_k, qstep=step_k)`` of the
+        tile encode_tiled cuts, by encode_tiled's plan: ``last_items_calls`` is the step-less call's."""
+        from ...utils import tiling
+        self._check_picture(image)
+        framing = self._tiled_q_framing()
+        _, C, H, W = image.shape
+        grid = tiling.TileGrid(H, W, *self._tile_size(tile), overlap=overlap, pad_to=pad_to)
+        steps = np.array(np.broadcast_to(check_qsteps(qstep, len(grid)), (len(grid),)), dtype=np.float32)
+        out = self._encode_tiles(image, grid, framing, max_batch, steps=steps)
+        return tiling.pack_tiled_q(C, H, W, grid.th, grid.tw, out, steps, overlap=grid.overlap, pad_to=grid.pad_to)
+
+    def _check_pictures(self, pictures):
+        pictures = list(pictures)
+        for x in pictures:
+            self._check_picture(x)
+        if not pictures:
+            raise ValueError("no pictures")
+        if len({x.shape[1] for x in pictures}) > 1:
+            raise ValueError("the pictures of one call share their channel count")
+        return pictures
+
+    def encode_tiled_items_q(self, pictures, qsteps, tile=(512, 512), overlap=0, max_batch=None, pad_to=1) -> List[bytes]:
+        """encode_tiled_items under quantiser steps: ``qsteps`` is one step, or one per picture.  -> N BTQ1 containers, container k byte
+        for byte ``self.encode_tiled_q(pictures[k], step_k, tile=, overlap=, pad_to=)``, by the pooled plan of encode_tiled_items."""
+        from ...utils import tiling
+        pictures = self._check_pictures(pictures)
+        framing = self._tiled_q_framing()
+        th, tw = self._tile_size(tile)
+        grids = [tiling.TileGrid(x.shape[2], x.shape[3], th, tw, overlap=overlap, pad_to=pad_to) for x in pictures]
+        per_picture = np.broadcast_to(check_qsteps(qsteps, len(pictures)), (len(pictures),))
+        steps = [np.full(len(g), s, dtype=np.float32) for g, s in zip(grids, per_picture)]
+        self.last_items_calls = 0
+        pictures = [x if x.device == self.device else x.to(device=self.device) for x in pictures]
+        strings = self._encode_pooled(pictures, grids, framing, max_batch, steps=steps)
+        return [tiling.pack_tiled_q(x.shape[1], g.H, g.W, g.th, g.tw, s, q, overlap=g.overlap, pad_to=g.pad_to)
+                for x, g, s, q in zip(pictures, grids, strings, steps)]
+
+    def _measure_latents(self, batch):
+        """The analysis side of encode()'s module path on one batch: g_a, h_a, the coding of every node before the y node (enqueued,
+        not synchronised) and h_s.  -> (the pending bodies of those nodes, y, sigma): what the y coder's encode() was handed, kept on
+        the device.  The transforms run here once; the step is chosen and y coded from these tensors."""
+        from ...nn import kernels as K
+        if batch.dtype == torch.uint8:
+            batch = K.image_u8_to_f32(batch)
+        node_dict = self._node_generate_process(**self._get_default_node_dict(force_add_default_dynamic_nodes=True))
+        latent = self._inference_process({self.DEFAULT_INPUT_NODE_NAME: batch, **node_dict})
+        held = {}
+        data_dict, _ = self._generative_process(latent, do_encode=True, coder_kwargs={self.QSTEP_NODE: dict(rate_measure=held)})
+        nodes = self._coded_nodes()
+        return [data_dict[n] for n in nodes if n != self.QSTEP_NODE], held["y"], held["scales"]
+
+    def encode_tiled_items_to_rate(self, pictures, target_bytes=None, target_bpp=None, tile=(512, 512), overlap=0, pad_to=1, max_batch=None,
+                                   candidates=16, passes=2, step_range=(2 ** -4, 2 ** 6), return_report=False, workspace_limit=2 << 30):
+        """encode_tiled_items_q with ONE step per picture chosen on the GPU so that the picture's whole BTQ1 container -- framing included
+        -- fits a byte budget.  Give exactly one target, a number or one per picture: ``target_bytes``, or ``target_bpp`` (budget =
+        floor(bpp * H * W / 8), the picture's own H and W).  The host takes utils.tiling.tiled_q_framing_bytes off the budget; the
+        rest is the budget of the picture's payload over all its tiles.  Every pooled chunk runs the analysis side once
+        (_measure_latents); y and sigma of all chunks stay on the device (``workspace_limit`` bytes at most, else ValueError before
+        anything is launched), the candidate steps are rated chunk by chunk into one curve tensor, nn.kernels.rate_steps_groups picks
+        the first candidate whose predicted payload fits each picture and refines it ``passes - 1`` times, and every chunk's y is
+        coded from the retained tensors under its tiles' steps, read on the device.  -> N containers, container k byte for byte
+        ``self.encode_tiled_q(pictures[k], its step)``; with ``return_report`` also a list of per-picture dicts: ``step``,
+        ``predicted_bytes``, ``container_bytes``, ``budget``, ``met`` (container <= budget), ``fits``, ``n_tiles`` and per tile
+        ``predicted_payload`` and ``payload``.  A picture no candidate fits takes the largest step and reports ``met`` False."""
+        from ...nn import kernels as K
+        from ...utils import tiling
+        from ...utils.rate import NO_FIT, budgets_from, check_passes, first_grid
+        pictures = self._check_pictures(pictures)
+        framing = self._tiled_q_framing()
+        N = len(pictures)
+        th, tw = self._tile_size(tile)
+        grids = [tiling.TileGrid(x.shape[2], x.shape[3], th, tw, overlap=overlap, pad_to=pad_to) for x in pictures]
+        nodes = self._coded_nodes()
+        if nodes[-1] != self.QSTEP_NODE:
+            raise ValueError(f"a byte budget chooses the step of node '{self.QSTEP_NODE}', which must be the last node coded, not {nodes}")
+        ycoder = self.latent_node_entropy_coders[self.QSTEP_NODE]
+        lanes = ycoder.stream_lanes
+        streams = [getattr(c, "stream_lanes", 1) for c, _ in framing]
+        if (target_bytes is None) == (target_bpp is None):
+            raise ValueError("give exactly one of target_bytes and target_bpp")
+        target = np.asarray(target_bytes if target_bytes is not None else target_bpp, dtype=object).reshape(-1)
+        if target.size not in (1, N):
+            raise ValueError(f"give one target, or one per picture of the {N} (got {target.size})")
+        budgets, framings = np.zeros(N, np.int64), np.zeros(N, np.int64)
+        for p, g in enumerate(grids):
+            one = target[p if target.size == N else 0]
+            budgets[p] = budgets_from(one if target_bytes is not None else None, one if target_bpp is not None else None, 1, g.H, g.W)[0]
+            framings[p] = tiling.tiled_q_framing_bytes(g, streams_per_body=streams)
+            if budgets[p] <= framings[p]:
+                raise ValueError(f"picture {p}: a budget of {budgets[p]} bytes is not above the {framings[p]} bytes of framing its "
+                                 f"{len(g)} tiles take (utils.tiling.tiled_q_framing_bytes); nothing is left for the payload")
+        grid0 = first_grid(candidates, step_range)
+        passes = check_passes(passes)
+        # y and sigma of every tile stay resident: 2 * 4 bytes per latent sample, M / 256 samples per coded pixel (6 bytes a pixel at M = 192)
+        gen = self.latent_inference_modules
+        M = next((int(m.M) for name, m in gen.items() if name.split(self.DEFAULT_EDGE_SPLIT_SYMBOL)[1] == self.QSTEP_NODE and hasattr(m, "M")), 192)
+        pixels = sum(g.coded_size(k)[0] * g.coded_size(k)[1] for g in grids for k in range(len(g)))
+        need = 8 * M * pixels // 256
+        if need > workspace_limit:
+            raise ValueError(f"the latents of {sum(len(g) for g in grids)} tiles ({pixels} coded pixels) take {need} bytes on the device, "
+                             f"more than workspace_limit={workspace_limit}: code the pictures in several calls")
+        self.last_items_calls = 0
+        pictures = [x if x.device == self.device else x.to(device=self.device) for x in pictures]
+        with torch.no_grad(), torch.cuda.device(self.device):
+            chunks, latents, extras, tile_of = [], [], [], {}
+            for refs, batch in self._pooled_batches(pictures, grids, max_batch):
+                self.last_items_calls += 1
+                before, y, scales = self._measure_latents(batch)
+                words = torch.zeros((len(refs),), device=y.device, dtype=torch.int32)
+                for body in before:   # the words an image has spent on its earlier streams: on the device, as the coder counted them
+                    if not hasattr(body, "_handle") or body._handle is None:
+                        raise ValueError("a byte budget needs the earlier nodes' coders to enqueue their streams (encode(lazy=True))")
+                    words += body._handle["nwords"].clamp(min=0).reshape(len(refs), -1).sum(1, dtype=torch.int32)
+                for ref in refs:
+                    tile_of[(ref.picture, ref.index)] = len(tile_of)
+                chunks.append((refs, before))
+                latents.append((y, scales))
+                extras.append(words)
+            groups = [[tile_of[(p, k)] for k in range(len(g))] for p, g in enumerate(grids)]
+            payload_budgets = torch.from_numpy(budgets - framings).to(self.device)
+            steps, choice, pred, tile_steps, tile_pred = K.rate_steps_groups(
+                latents, groups, payload_budgets, torch.cat(extras), grid0, passes, ycoder._scale_table_dev, ycoder._tables,
+                ycoder.scale_bound, lanes)
+            strings = [[None] * len(g) for g in grids]
+            spent = [[0] * len(g) for g in grids]
+
+            def finish(refs, before, ybody):   # the one synchronisation of a chunk: its bytes, framed and split per tile
+                merged = merge_bodies(before + [ybody])
+                spent_words = self._words_coded(dict(zip(nodes, before)), nodes[:-1], len(refs))
+                for j, ((p, k, _, _), one) in enumerate(zip(refs, self._split_string(merged, len(refs), framing))):
+                    strings[p][k], spent[p][k] = one, int(spent_words[j])
+
+            row, waiting = 0, None
+            for c, (refs, before) in enumerate(chunks):
+                y, scales = latents[c]
+                latents[c] = None   # coded from here on: the chunk's latents go when its symbols are written
+                ybody = ycoder._encode_q(y, scales, tile_steps[row:row + len(refs)], lazy=True, steps_on_device=True)
+                row += len(refs)
+                if waiting is not None:   # the chunk before is framed on the host while this one is coded
+                    finish(*waiting)
+                waiting = (refs, before, ybody)
+            host = [t.cpu().numpy() for t in (steps, choice, pred, tile_pred, torch.cat(extras))]   # after the last chunk's coding is enqueued
+            finish(*waiting)
+        steps, choice, pred, tile_pred, extra = host
+        for p, g in enumerate(grids):
+            for k in range(len(g)):
+                if spent[p][k] != int(extra[tile_of[(p, k)]]):
+                    raise RuntimeError(f"picture {p}, tile {k}: an earlier stream was re-coded with a larger buffer after the step was chosen; "
+                                       "its length is not the one the budget was charged")
+        out = [tiling.pack_tiled_q(x.shape[1], g.H, g.W, g.th, g.tw, s, float(q), overlap=g.overlap, pad_to=g.pad_to)
+               for x, g, s, q in zip(pictures, grids, strings, steps)]
+        if not return_report:
+            return out
+        report = []
+        for p, g in enumerate(grids):
+            mine = [tile_of[(p, k)] for k in range(len(g))]
+            report.append(dict(step=float(steps[p]), predicted_bytes=int(pred[p] + framings[p]), container_bytes=len(out[p]),
+                               budget=int(budgets[p]), met=len(out[p]) <= int(budgets[p]), fits=not (int(choice[p]) & NO_FIT), n_tiles=len(g),
+                               predicted_payload=tile_pred[mine].astype(np.int64),
+                               payload=np.array([int(self.payload_bytes(s, 1)[0]) for s in strings[p]], dtype=np.int64)))
+        return out, report
+
+    def encode_tiled_to_rate(self, image, target_bytes=None, target_bpp=None, tile=(512, 512), overlap=0, pad_to=1, max_batch=None,
+                             candidates=16, passes=2, step_range=(2 ** -4, 2 ** 6), return_report=False, workspace_limit=2 << 30):
+        """One picture coded as tiles into a byte budget that covers its whole BTQ1 container: encode_tiled_items_to_rate of the one
+        picture.  -> the container, byte for byte ``self.encode_tiled_q(image, the chosen step)``; with ``return_report`` also its
+        report (a dict)."""
+        self._check_picture(image)
+        out = self.encode_tiled_items_to_rate([image], target_bytes=target_bytes, target_bpp=target_bpp, tile=tile, overlap=overlap,
+                                              pad_to=pad_to, max_batch=max_batch, candidates=candidates, passes=passes,
+                                              step_range=step_range, return_report=return_report, workspace_limit=workspace_limit)
+        return (out[0][0], out[1][0]) if return_report else out[0]
 
     def forward(self, data, *args, **kwargs):
         """Eval-mode forward: quantised reconstruction without entropy coding (latent_graph.py:870-1230

@@ -478,9 +478,11 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
         self.update_cache("metric_dict", prior_entropy=nll.mean())
         return yhat
 
-    def _encode_q(self, y, prior, qstep, lazy):
+    def _encode_q(self, y, prior, qstep, lazy, steps_on_device=False):
+        """``steps_on_device``: ``qstep`` is a float32 device tensor of one step per image that a kernel chose among validated
+        candidates (nn.kernels.rate_select_groups), read where it lies."""
         sym, idx, _ = K.gc_quantize_index_q(y, self._crop(prior, *y.shape[-2:]), qstep, self._scale_table_dev, self.scale_bound,
-                                            want_yhat=False)
+                                            want_yhat=False, steps_on_device=steps_on_device)
         per = self._lane_length(y[0].numel())
         body = PendingBody(self._tables, self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), per), y.shape[-2:])
         return body if lazy else body.result()
@@ -545,8 +547,15 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
     accepts_buffer = True  # decode() reads the stream through the buffer protocol (bytes or memoryview)
 
     def encode(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, lazy=False, qstep=None, rate_target=None,
-               **kwargs):  # :377-385
+               rate_measure=None, **kwargs):  # :377-385
         self._ready()
+        if rate_measure is not None:
+            # a caller that chooses the step over several calls (tiled pictures): nothing is coded here -- the call's y and sigma are
+            # handed back in the dict, and the caller codes them with _encode_q once the steps are chosen
+            if qstep is not None or rate_target is not None or channel_gains is not None or channel_gains_inv is not None:
+                raise ValueError("rate_measure= retains the latent for a step chosen later: no qstep=, rate_target= or channel_gains with it")
+            rate_measure.update(y=y, scales=self._crop(prior, *y.shape[-2:]))
+            return None
         if rate_target is not None:
             if qstep is not None or channel_gains is not None or channel_gains_inv is not None:
                 raise ValueError("rate_target=, qstep= and channel_gains are three rate knobs: give one of them")

@@ -438,10 +438,11 @@ def _rate_cand(cand, images):
     return cand, cand.shape[1], 1
 
 
-def rate_curve(y, scales, cand, table, tables, bound=0.11, lanes=1):
+def rate_curve(y, scales, cand, table, tables, bound=0.11, lanes=1, out=None):
     """basic_gc_rate_curve_dev on a [B, ...] latent: int64 [B * lanes][K], entry (b * lanes + l, k) = the summed table cost (2^-16 bit)
     of lane stream l of image b at step ``cand[k]`` (``cand``: float32 device tensor [K], or [B][K] with a grid per image; the values
-    are the caller's to validate).  ``tables``: the RansTables that will code the symbols."""
+    are the caller's to validate).  ``tables``: the RansTables that will code the symbols.  ``out``: a contiguous int64 [B * lanes][K]
+    device tensor to write instead of a new one (the rows of a larger curve tensor)."""
     y, scales, table = _dev(y, torch.float32), _dev(scales, torch.float32), _dev(table, torch.float32)
     B, per = _per_image(y)
     if scales.numel() != y.numel():
@@ -449,7 +450,12 @@ def rate_curve(y, scales, cand, table, tables, bound=0.11, lanes=1):
     if lanes < 1 or per % lanes:
         raise ValueError(f"rate_curve: {lanes} lanes do not divide the {per} symbols of an image")
     cand, K, cpi = _rate_cand(cand, B)
-    bits = torch.empty((B * lanes, K), device=y.device, dtype=torch.int64)
+    if out is None:
+        bits = torch.empty((B * lanes, K), device=y.device, dtype=torch.int64)
+    else:
+        bits = out
+        if bits.dtype != torch.int64 or bits.device != y.device or tuple(bits.shape) != (B * lanes, K) or not bits.is_contiguous():
+            raise ValueError(f"rate_curve: out is a contiguous int64 [{B * lanes}][{K}] tensor on the latent's device")
     _lib.check(_lib.lib().basic_gc_rate_curve_dev(y.data_ptr(), scales.data_ptr(), B * lanes, per // lanes, int(lanes), cand.data_ptr(), K, cpi,
                                                   table.data_ptr(), table.numel(), float(bound), tables._h, bits.data_ptr(), _stream()))
     return bits
@@ -510,6 +516,111 @@ def rate_steps(y, scales, budgets, extra_words, candidates, passes, table, table
         steps, choice, pred = rate_select(bits, per // lanes, cand, budgets, extra_words, lanes)
         trace.append((cand, bits, choice))
     return (steps, choice, pred, trace) if return_trace else (steps, choice, pred)
+
+
+def _group_csr(groups, n_tiles):
+    """Groups (a sequence of sequences of tile numbers) as the host CSR arrays (group_first int32 [G + 1], group_tiles int32 [listed])
+    and tile_group int64 [n_tiles], the group of every tile (-1: in none)."""
+    first, tiles = [0], []
+    tile_group = np.full(int(n_tiles), -1, dtype=np.int64)
+    for g, members in enumerate(groups):
+        members = [int(t) for t in members]
+        tiles.extend(members)
+        first.append(len(tiles))
+        for t in members:
+            if 0 <= t < n_tiles:
+                tile_group[t] = g
+    return np.asarray(first, dtype=np.int32), np.asarray(tiles, dtype=np.int32).reshape(-1), tile_group
+
+
+def rate_select_groups(bits, tile_first_seg, tile_per_seg, groups, cand, budgets, tile_extra_words=None, lanes=1, block_threads=0):
+    """basic_rate_select_groups_dev: rate_select with GROUPS of tiles in the place of images -- a group (a tiled picture) has one budget
+    over all its tiles.  ``bits`` int64 [S][K]; tile t owns rows ``tile_first_seg[t]`` .. + lanes - 1, streams of ``tile_per_seg[t]``
+    symbols; ``groups``: a sequence of sequences of tile numbers (or the CSR pair ``(group_first, group_tiles)``); ``cand`` [K] or
+    [G][K]; ``budgets`` int64 [G]; ``tile_extra_words`` int32 [T] on the device or None.  The plan arrays are host data, checked by the
+    entry point before it enqueues anything.  -> (steps float32 [G], choice int32 [G], pred_bytes int64 [G], tile_steps float32 [T],
+    tile_pred int64 [T]); a tile in no group keeps step 1 and prediction 0."""
+    bits = _dev(bits, torch.int64)
+    first_seg = np.ascontiguousarray(tile_first_seg, dtype=np.int32).reshape(-1)
+    per_seg = np.ascontiguousarray(tile_per_seg, dtype=np.int64).reshape(-1)
+    T = first_seg.size
+    if isinstance(groups, tuple) and len(groups) == 2 and isinstance(groups[0], np.ndarray):
+        gfirst, gtiles = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in groups)
+    else:
+        gfirst, gtiles, _ = _group_csr(groups, T)
+    G = gfirst.size - 1
+    if bits.dim() != 2 or per_seg.size != T or T < 1 or G < 1 or gtiles.size != int(gfirst[-1]):
+        raise ValueError("rate_select_groups: bits is [S][K], tile_first_seg and tile_per_seg are [T], the groups list tiles")
+    cand, K, cpg = _rate_cand(cand, G)
+    budgets = _dev(budgets, torch.int64)
+    if bits.shape[1] != K or budgets.numel() != G:
+        raise ValueError("rate_select_groups: bits is [S][K] and budgets [G]")
+    if tile_extra_words is not None:
+        tile_extra_words = _dev(tile_extra_words, torch.int32)
+        if tile_extra_words.numel() != T:
+            raise ValueError("rate_select_groups: tile_extra_words is [T]")
+    dev = bits.device
+    plan = torch.empty(((16 * T + 4 * (G + 1) + 7) // 8,), device=dev, dtype=torch.int64)
+    steps = torch.empty((G,), device=dev, dtype=torch.float32)
+    choice = torch.empty((G,), device=dev, dtype=torch.int32)
+    pred = torch.empty((G,), device=dev, dtype=torch.int64)
+    tile_steps = torch.ones((T,), device=dev, dtype=torch.float32)
+    tile_pred = torch.zeros((T,), device=dev, dtype=torch.int64)
+    _lib.check(_lib.lib().basic_rate_select_groups_dev(
+        bits.data_ptr(), int(bits.shape[0]), int(lanes), T, first_seg.ctypes.data, per_seg.ctypes.data,
+        tile_extra_words.data_ptr() if tile_extra_words is not None else None, G, gfirst.ctypes.data, gtiles.ctypes.data, plan.data_ptr(),
+        cand.data_ptr(), K, cpg, budgets.data_ptr(), steps.data_ptr(), choice.data_ptr(), pred.data_ptr(), tile_steps.data_ptr(),
+        tile_pred.data_ptr(), int(block_threads), _stream()))
+    return steps, choice, pred, tile_steps, tile_pred
+
+
+def rate_steps_groups(chunks, groups, budgets, tile_extra_words, candidates, passes, table, tables, bound=0.11, lanes=1,
+                      return_trace=False):
+    """rate_steps over the tiles of many pictures: ``chunks`` is a list of (y, scales) pairs of [B_c, ...] latents (one per pooled coding
+    call; the tiles are numbered through the chunks in order), ``groups`` the tile numbers of every picture.  Per pass: one
+    rate_curve per chunk into that chunk's rows of ONE curve tensor (every tile under its own picture's candidate grid), one
+    rate_select_groups, and between passes one rate_refine with groups in the place of images.  Nothing is synchronised.
+    -> (steps [G], choice [G], pred_bytes [G], tile_steps [T], tile_pred [T]) of the last pass; ``return_trace``: also the list of
+    every pass's (candidates, bits, choice)."""
+    from ..utils.rate import check_candidates, check_passes, refine_t
+    passes = check_passes(passes)
+    grid0 = check_candidates(candidates)
+    first_seg, per_seg, sizes = [], [], []
+    for y, scales in chunks:
+        B, per = _per_image(y)
+        if scales.numel() != y.numel():
+            raise ValueError("rate_steps_groups: y and scales must hold the same number of elements")
+        if lanes < 1 or per % lanes:
+            raise ValueError(f"rate_steps_groups: {lanes} lanes do not divide the {per} symbols of a tile")
+        first_seg.extend((len(per_seg) + j) * lanes for j in range(B))
+        per_seg.extend([per // lanes] * B)
+        sizes.append(B)
+    T = len(per_seg)
+    if T < 1:
+        raise ValueError("rate_steps_groups: no tiles")
+    gfirst, gtiles, tile_group = _group_csr(groups, T)
+    if (tile_group < 0).any():
+        raise ValueError("rate_steps_groups: every tile belongs to a group")
+    dev = chunks[0][0].device
+    K = grid0.size
+    cand = torch.from_numpy(grid0).to(dev)
+    t = torch.from_numpy(refine_t(K)).to(dev)
+    tile_group_dev = torch.from_numpy(tile_group).to(dev)
+    bits = torch.empty((T * lanes, K), device=dev, dtype=torch.int64)
+    trace = []
+    for p in range(passes):
+        if p:
+            cand = rate_refine(cand, choice, t)
+        row = 0
+        for (y, scales), B in zip(chunks, sizes):
+            mine = cand if cand.dim() == 1 else cand.index_select(0, tile_group_dev[row:row + B])
+            rate_curve(y, scales, mine, table, tables, bound, lanes, out=bits[row * lanes:(row + B) * lanes])
+            row += B
+        steps, choice, pred, tile_steps, tile_pred = rate_select_groups(bits, first_seg, per_seg, (gfirst, gtiles), cand, budgets,
+                                                                        tile_extra_words, lanes)
+        trace.append((cand, bits.clone() if return_trace else None, choice))
+    out = (steps, choice, pred, tile_steps, tile_pred)
+    return out + (trace,) if return_trace else out
 
 
 def lanes_pack(sym, idx, batch, positions, channels, lanes):

@@ -108,6 +108,21 @@ def merge_compressai_bodies(bodies, streams_per_item=1) -> bytes:
     return _write_compressai(shape[0], shape[1], streams)
 
 
+def compressai_body_framing(n_streams) -> int:
+    """Bytes of a CompressAI-style body of ``n_streams`` streams that are not payload: the ">III" header and a ">I" length per stream
+    (what ``_write_compressai`` writes around the streams)."""
+    return struct.calcsize(">3I") + struct.calcsize(">I") * _check_streams_per_item(n_streams)
+
+
+def compressai_string_framing(streams_per_body: Sequence[int], num_bytes_length=4) -> int:
+    """Bytes that are not payload in a whole-codec string of CompressAI-style bodies, body k of ``streams_per_body[k]`` streams:
+    merge_bytes(bodies, num_segments=len(bodies)) writes a length in front of every body but the last."""
+    streams_per_body = list(streams_per_body)
+    if not streams_per_body:
+        raise ValueError("a codec string holds at least one body")
+    return num_bytes_length * (len(streams_per_body) - 1) + sum(compressai_body_framing(s) for s in streams_per_body)
+
+
 # ---------------------------------------------------------------- PGM bodies
 def _pgm_head(body, has_head):
     """(batch, dims, offset of what follows) of the optional shape head."""

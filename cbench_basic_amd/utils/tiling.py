@@ -294,3 +294,102 @@ def unpack_tiled(data):
         raise ValueError("not a tiled picture: wrong magic")
     channels, H, W, th, tw, _, strings = unpack_tiled_any(data)
     return channels, H, W, th, tw, strings
+
+
+# ---------------------------------------------------------------- BTQ1: tiles coded under a quantiser step (utils/qstep.py)
+# b"BTQ1", the BTL3 head fields (channels, H, W, th, tw, oy, ox, py, px, n), n float32 LE steps (one per tile, row-major), n uint32
+# lengths, the n tile strings.  Tile k's string is the inner stream of compress_q(P_k, step_k) -- encode(P_k, qstep=step_k) -- which
+# does not hold its step: the container does.  A step per tile, so that a per-tile allocation needs no new format; a picture coded
+# under one step carries it n times.
+MAGIC_Q = b"BTQ1"
+_HEAD_Q = _HEAD3
+_STEP, _LEN = struct.Struct("<f"), struct.Struct("<I")
+
+
+class TiledPictureQ(NamedTuple):
+    """What a BTQ1 container states: the TiledPicture fields, and ``steps``, float32 [n], the quantiser step of every tile."""
+    channels: int
+    H: int
+    W: int
+    th: int
+    tw: int
+    overlap: Tuple[int, int]
+    pad_to: Tuple[int, int]
+    strings: List[bytes]
+    steps: "object"
+
+
+def pack_tiled_q(channels, H, W, th, tw, strings: Sequence[bytes], steps, overlap=(0, 0), pad_to=(1, 1)) -> bytes:
+    """The BTQ1 container of a picture's tile strings (row-major order) coded under ``steps``: one step, or one per tile."""
+    import numpy as np
+    from .qstep import check_qsteps
+    grid = TileGrid(H, W, th, tw, overlap, pad_to)
+    strings = [bytes(s) for s in strings]
+    if len(strings) != len(grid):
+        raise ValueError(f"{len(strings)} strings for {grid.rows} x {grid.cols} tiles")
+    steps = np.broadcast_to(check_qsteps(steps, len(grid)), (len(grid),))
+    if not 1 <= channels <= 255:
+        raise ValueError(f"channels must be in 1..255, not {channels!r}")
+    if max(H, W, th, tw, len(strings), *[len(s) for s in strings]) >= 1 << 32:
+        raise ValueError("a field of the container does not fit 32 bits")
+    head = _HEAD_Q.pack(MAGIC_Q, channels, H, W, th, tw, grid.oy, grid.ox, grid.py, grid.px, len(strings))
+    return b"".join([head, steps.astype("<f4").tobytes(),
+                     struct.pack("<%dI" % len(strings), *[len(s) for s in strings])] + strings)
+
+
+def unpack_tiled_q(data) -> TiledPictureQ:
+    """A BTQ1 container as a TiledPictureQ; ValueError for anything that is not exactly one: a wrong magic, a short buffer, a tile
+    count that is not the grid's, lengths that do not add up to the buffer, a step that is not finite or lies outside [2^-4, 2^6]."""
+    import numpy as np
+    from .qstep import check_qsteps
+    data = bytes(data)
+    if data[:4] != MAGIC_Q:
+        raise ValueError("not a tiled picture with quantiser steps: wrong magic")
+    if len(data) < _HEAD_Q.size:
+        raise ValueError("truncated tiled picture: head cut short")
+    _, channels, H, W, th, tw, oy, ox, py, px, n = _HEAD_Q.unpack_from(data)
+    if min(channels, H, W, th, tw) < 1:
+        raise ValueError("tiled picture: a dimension is zero")
+    if 2 * oy > th or 2 * ox > tw:
+        raise ValueError(f"tiled picture: an overlap of {(oy, ox)} is more than half a {th} x {tw} tile")
+    if min(py, px) < 1:
+        raise ValueError("tiled picture: pad_to is zero")
+    if th % py or tw % px:
+        raise ValueError(f"tiled picture: pad_to {(py, px)} does not divide a {th} x {tw} tile")
+    grid = TileGrid(H, W, th, tw, (oy, ox), (py, px))
+    if n != len(grid):
+        raise ValueError(f"tiled picture: {n} tiles stated, {grid.rows} x {grid.cols} expected")
+    cur = _HEAD_Q.size
+    if cur + _STEP.size * n > len(data):
+        raise ValueError("truncated tiled picture: step table cut short")
+    steps = check_qsteps(np.frombuffer(data, dtype="<f4", count=n, offset=cur), n)
+    cur += _STEP.size * n
+    if cur + _LEN.size * n > len(data):
+        raise ValueError("truncated tiled picture: length table cut short")
+    lens = struct.unpack_from("<%dI" % n, data, cur)
+    cur += _LEN.size * n
+    if cur + sum(lens) > len(data):
+        raise ValueError("truncated tiled picture: payload cut short")
+    strings = []
+    for L in lens:
+        strings.append(data[cur:cur + L])
+        cur += L
+    if cur != len(data):
+        raise ValueError(f"tiled picture: {len(data) - cur} bytes after the last tile")
+    return TiledPictureQ(channels, H, W, th, tw, (oy, ox), (py, px), strings, np.broadcast_to(steps, (n,)).copy())
+
+
+def tiled_q_framing_bytes(grid, stream_lanes=1, n_bodies=2, streams_per_body=None) -> int:
+    """The exact number of bytes of a BTQ1 container that are not rANS payload: the head, a step and a length per tile, and per
+    tile string the bodies' framing (utils/item_framing.py: a length in front of every body but the last, per body the header and
+    one length per stream).  ``grid``: a TileGrid, or the number of tiles.  A tile string holds ``n_bodies`` CompressAI-style bodies,
+    the last of ``stream_lanes`` streams (the y coder's) and the others of one; ``streams_per_body`` states every body's count."""
+    from .item_framing import compressai_string_framing
+    n = grid if isinstance(grid, int) and not isinstance(grid, bool) else len(grid)
+    if n < 1:
+        raise ValueError(f"a picture has at least one tile, not {n!r}")
+    if streams_per_body is None:
+        if isinstance(n_bodies, bool) or not isinstance(n_bodies, int) or n_bodies < 1:
+            raise ValueError(f"n_bodies must be a positive integer, not {n_bodies!r}")
+        streams_per_body = [1] * (n_bodies - 1) + [stream_lanes]
+    return _HEAD_Q.size + n * (_STEP.size + _LEN.size + compressai_string_framing(streams_per_body))

@@ -237,6 +237,27 @@ int basic_gc_rate_curve_dev(const float *d_y, const float *d_scales, int n_seg, 
 int basic_rate_select_dev(const uint64_t *d_bits, int n_images, int segs_per_image, int64_t per_seg, const float *d_cand, int n_cand,
                           int cand_per_image, const int32_t *d_extra_words, const int64_t *d_budget, float *d_steps_out,
                           int32_t *d_choice, int64_t *d_pred_bytes, void *hip_stream);
+/* basic_rate_select_dev for GROUPS of tiles: a tiled picture (group g) has one budget over all its tiles, which lie in several
+ * curve calls and need not share per_seg (INTEGRATION.md "Tiled pictures: step and byte budget").  Tile t owns the `lanes` rows
+ * tile_first_seg[t] .. + lanes - 1 of d_bits uint64 [n_seg][n_cand], streams of tile_per_seg[t] symbols each; group g lists the tiles
+ * group_tiles[group_first[g] .. group_first[g + 1]) (CSR; a tile belongs to at most one group, any order).
+ *     pred(g, k) = sum over t in g of (4 extra_words[t] + sum over the lanes of 4 (2 + ((bits[s][k] + 4 per_seg[t]) >> 21)))
+ * d_choice[g] = the FIRST k in candidate order with pred(g, k) <= d_budget[g]; none: (n_cand - 1) | BASIC_RATE_NO_FIT.
+ * d_steps_out[g] = the chosen candidate (d_cand float32 [n_cand], or [n_groups][n_cand] with cand_per_group == 1), d_pred_bytes[g] =
+ * its prediction; d_tile_steps[t] / d_tile_pred[t] = the group's step and the tile's own term of the sum at the chosen k, for every
+ * listed tile (the others are not written).  d_tile_steps is what basic_gc_quantize_index_q_dev reads as one step per image.
+ * The four plan arrays are HOST arrays: they are checked here and uploaded (stream-ordered) into d_plan, device memory of at least
+ * BASIC_RATE_GROUPS_PLAN_BYTES(n_tiles, n_groups) bytes, 8-byte aligned, which the kernel reads -- it never sees an unchecked index.
+ * d_tile_extra_words: int32 [n_tiles] on the device, or NULL.  One workgroup of block_threads (0: 256; else a multiple of 64 up to
+ * 1024) per group; integer sums, so the result depends on neither.  BASIC_ERR_INVALID, before anything is enqueued: a null pointer,
+ * n_cand outside [1, 32], lanes / n_seg / n_tiles / n_groups < 1, a tile whose rows leave d_bits or whose per_seg * 2^22 passes 63
+ * bits, an empty group, a tile index out of range or listed twice, a bad block_threads. */
+#define BASIC_RATE_GROUPS_PLAN_BYTES(n_tiles, n_groups) (16 * (size_t)(n_tiles) + 4 * ((size_t)(n_groups) + 1))
+int basic_rate_select_groups_dev(const uint64_t *d_bits, int n_seg, int lanes, int n_tiles, const int32_t *host_tile_first_seg,
+                                 const int64_t *host_tile_per_seg, const int32_t *d_tile_extra_words, int n_groups,
+                                 const int32_t *host_group_first, const int32_t *host_group_tiles, void *d_plan, const float *d_cand,
+                                 int n_cand, int cand_per_group, const int64_t *d_budget, float *d_steps_out, int32_t *d_choice,
+                                 int64_t *d_pred_bytes, float *d_tile_steps, int64_t *d_tile_pred, int block_threads, void *hip_stream);
 /* The next grid, d_cand_out float32 [n_images][n_cand], between the chosen candidate k and the one below it.  k == 0 or no fit:
  * every entry is the chosen step (the image is settled).  Otherwise lo = cand[k - 1], hi = cand[k] and
  *     cand_out[j] = fminf(lo + (hi - lo) * t[j], hi)  for j < n_cand - 1,   cand_out[n_cand - 1] = hi
