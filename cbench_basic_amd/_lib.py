@@ -68,6 +68,9 @@ _SIGNATURES = {
     "basic_rans_cost_table_host": (_I, [_P, _I, _I, _P, _I, _P]),
     "basic_rans_tables_costs": (_I, [_P, _P]),
     "basic_gc_rate_curve_dev": (_I, [_P, _P, _I, _L, _I, _P, _I, _I, _P, _I, _F, _P, _P, _P]),
+    "basic_gc_quantize_index_ms_dev": (_I, [_P, _P, _P, _L, _L, _L, _P, _I, _P, _I, _F, _P, _P, _P, _P]),
+    "basic_gc_dequantize_ms_dev": (_I, [_P, _P, _L, _L, _L, _P, _I, _P, _P]),
+    "basic_gc_rate_curve_ms_dev": (_I, [_P, _P, _P, _L, _I, _L, _I, _P, _I, _I, _P, _I, _F, _P, _P, _P]),
     "basic_rate_select_dev": (_I, [_P, _I, _I, _L, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "basic_rate_refine_dev": (_I, [_P, _I, _I, _P, _I, _P, _P, _P]),
     "basic_rate_select_groups_dev": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),

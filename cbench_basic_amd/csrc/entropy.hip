@@ -142,6 +142,102 @@ __global__ void gc_dequantize_q_kernel(const int32_t *__restrict__ in, int64_t n
     }
 }
 
+// ---- mean-scale hyperprior (include/basic_hip.h, "Mean-scale"): y is coded as rint(y - mu) under the scale's table entry and
+// rebuilt as q + mu.  Each helper is one correctly rounded fp32 operation.  They are plain operators under the pragma, as in
+// rate_refine_kernel: the *_rn intrinsics are inline functions compiled under the build's own contraction mode, and a multiply
+// and an add of theirs that meet after inlining would fuse -- (q * step) + mu is two roundings in the format, never an FMA.
+__device__ __forceinline__ float mean_sub(float y, float mu)
+{
+#pragma clang fp contract(off)
+    return y - mu;
+}
+__device__ __forceinline__ float mean_add(float q, float mu)
+{
+#pragma clang fp contract(off)
+    return q + mu;
+}
+__device__ __forceinline__ float step_mul_mean_add(float q, float step, float mu)
+{
+#pragma clang fp contract(off)
+    const float p = q * step;
+    return p + mu;
+}
+
+// gc_quantize_index_q_kernel with a mean per element; kStep == false is the step-less format and carries no division.  Same
+// streaming shape: flat grid-stride over B * per_image, the image of a chunk from one 64-bit division.  The parameters of element
+// (b, r) lie at b * param_stride + r of `scales` and `means`, so the two halves of a chunked prior [B][2 M][h][w] are read in
+// place (means = scales + per_image, param_stride = 2 per_image) and consecutive lanes still read consecutive addresses.
+// y == nullptr: indexes only (the decoder), nothing but the scales is read.
+template <bool kStep>
+__global__ void gc_quantize_index_ms_kernel(const float *__restrict__ y, const float *__restrict__ scales, const float *__restrict__ means,
+                                            int64_t n, int64_t per_image, int64_t param_stride, const float *__restrict__ steps,
+                                            int n_steps, const float *__restrict__ table, int table_len, float bound,
+                                            int32_t *__restrict__ symbols, int32_t *__restrict__ indexes, float *__restrict__ yhat)
+{
+    extern __shared__ float s_table[];
+    __shared__ int s_unsorted;
+    if (threadIdx.x == 0) s_unsorted = 0;
+    for (int i = threadIdx.x; i < table_len; i += blockDim.x) s_table[i] = table[i];
+    __syncthreads();
+    for (int i = threadIdx.x; i + 1 < table_len; i += blockDim.x)
+        if (!(s_table[i] <= s_table[i + 1])) s_unsorted = 1;
+    __syncthreads();
+    const bool sorted = s_unsorted == 0;
+    for (int64_t base = static_cast<int64_t>(blockIdx.x) * blockDim.x; base < n; base += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        if (i >= n) break;
+        int64_t b = base / per_image;                         // uniform: once per chunk
+        int64_t r = (base - b * per_image) + threadIdx.x;
+        while (r >= per_image) { r -= per_image; ++b; }        // i < n = B * per_image keeps b < B
+        const int64_t p = b * param_stride + r;
+        float step = 1.f;
+        if constexpr (kStep) step = steps[n_steps == 1 ? 0 : b];
+        float s = fmaxf(scales[p], bound);  // LowerBound first, then the step
+        if constexpr (kStep) s = step_div(s, step);
+        int idx;
+        if (sorted && s == s) {
+            int lo = 0, hi = table_len - 1;   // first j in [0, len - 1) with table[j] >= s, len - 1 if none
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (s_table[mid] < s) lo = mid + 1; else hi = mid;
+            }
+            idx = lo;
+        } else {
+            idx = table_len - 1;
+            for (int j = 0; j < table_len - 1; ++j) idx -= (s <= s_table[j]) ? 1 : 0;
+        }
+        indexes[i] = idx;
+        if (y) {
+            const float mu = means[p];
+            float res = mean_sub(y[i], mu);
+            if constexpr (kStep) res = step_div(res, step);
+            const float q = round_even(res);
+            symbols[i] = static_cast<int32_t>(q);
+            if (yhat) {
+                if constexpr (kStep) yhat[i] = step_mul_mean_add(q, step, mu);
+                else yhat[i] = mean_add(q, mu);
+            }
+        }
+    }
+}
+
+// the decoder's yhat = float(sym) + mu, or (float(sym) * step) + mu: the encoder's bits wherever sym != 0 or mu != 0
+template <bool kStep>
+__global__ void gc_dequantize_ms_kernel(const int32_t *__restrict__ in, const float *__restrict__ means, int64_t n, int64_t per_image,
+                                        int64_t param_stride, const float *__restrict__ steps, int n_steps, float *__restrict__ out)
+{
+    for (int64_t base = static_cast<int64_t>(blockIdx.x) * blockDim.x; base < n; base += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        if (i >= n) break;
+        int64_t b = base / per_image;
+        int64_t r = (base - b * per_image) + threadIdx.x;
+        while (r >= per_image) { r -= per_image; ++b; }
+        const float mu = means[b * param_stride + r], q = static_cast<float>(in[i]);
+        if constexpr (kStep) out[i] = step_mul_mean_add(q, steps[n_steps == 1 ? 0 : b], mu);
+        else out[i] = mean_add(q, mu);
+    }
+}
+
 // ---- rate control (include/basic_hip.h, "Rate control"): the exact table cost of every stream at each candidate step.
 // One read of y and sigma serves all candidates: an element sits in two registers while the candidate loop -- unrolled over the
 // template's kNC accumulators, n_cand <= kNC of them live -- repeats gc_quantize_index_q_kernel's arithmetic for the step and
@@ -176,8 +272,13 @@ __device__ __forceinline__ uint32_t symbol_cost(const RateTables &T, const int2 
     return c;
 }
 
-template <int kNC>
-__global__ __launch_bounds__(kBlock) void gc_rate_curve_kernel(const float *__restrict__ y, const float *__restrict__ scales, int64_t per_seg,
+//
+// kMean (the mean-scale coder): the element's mean is read beside y and the candidate loop works on y - mu, subtracted once; the
+// parameters of segment s, image b = s / segs_per_image, start at b * param_stride + (s % segs_per_image) * per_seg of `scales` and
+// `means` (gc_quantize_index_ms_kernel's addressing).  Without it neither argument is read.
+template <int kNC, bool kMean>
+__global__ __launch_bounds__(kBlock) void gc_rate_curve_kernel(const float *__restrict__ y, const float *__restrict__ scales,
+                                                               const float *__restrict__ means, int64_t param_stride, int64_t per_seg,
                                                                int segs_per_image, int bps, const float *__restrict__ cand, int n_cand,
                                                                int cand_per_image, const float *__restrict__ table, int table_len,
                                                                float bound, RateTables T, unsigned long long *__restrict__ bits)
@@ -199,11 +300,18 @@ __global__ __launch_bounds__(kBlock) void gc_rate_curve_kernel(const float *__re
     __syncthreads();
     const bool sorted = s_unsorted == 0;
     const float *py = y + static_cast<int64_t>(seg) * per_seg, *ps = scales + static_cast<int64_t>(seg) * per_seg;
+    const float *pm = nullptr;
+    if constexpr (kMean) {
+        const int64_t at = static_cast<int64_t>(seg / segs_per_image) * param_stride + static_cast<int64_t>(seg % segs_per_image) * per_seg;
+        ps = scales + at;
+        pm = means + at;
+    }
     unsigned long long acc[kNC];
 #pragma unroll
     for (int k = 0; k < kNC; ++k) acc[k] = 0ull;
     for (int64_t i = static_cast<int64_t>(part) * kBlock + threadIdx.x; i < per_seg; i += static_cast<int64_t>(bps) * kBlock) {
-        const float yv = py[i];
+        float yv = py[i];
+        if constexpr (kMean) yv = mean_sub(yv, pm[i]);
         const float sb = fmaxf(ps[i], bound);   // LowerBound first, then the step
 #pragma unroll
         for (int k = 0; k < kNC; ++k) {
@@ -694,9 +802,56 @@ extern "C" int basic_gc_dequantize_q_dev(const int32_t *d_sym, int64_t n, int64_
     return BASIC_OK;
 }
 
-extern "C" int basic_gc_rate_curve_dev(const float *d_y, const float *d_scales, int n_seg, int64_t per_seg, int segs_per_image,
-                                       const float *d_cand, int n_cand, int cand_per_image, const float *d_table, int table_len,
-                                       float scale_bound, const basic_rans_tables *t, uint64_t *d_bits, void *hip_stream)
+extern "C" int basic_gc_quantize_index_ms_dev(const float *d_y, const float *d_scales, const float *d_means, int64_t n, int64_t per_image,
+                                              int64_t param_stride, const float *d_steps, int n_steps, const float *d_table,
+                                              int table_len, float scale_bound, int32_t *d_symbols, int32_t *d_indexes, float *d_yhat,
+                                              void *hip_stream)
+{
+    BASIC_REQUIRE(d_scales && d_table && d_indexes && n >= 0 && table_len >= 1 && table_len <= 4096, "gc_quantize_index_ms: bad argument");
+    BASIC_REQUIRE(d_y ? (d_symbols && d_means) : (!d_symbols && !d_yhat),
+                  "gc_quantize_index_ms: d_y needs d_means and d_symbols; without d_y (indexes only) there is neither d_symbols nor d_yhat");
+    if (!d_steps) n_steps = 0;
+    BASIC_REQUIRE(per_image >= 1 && n % per_image == 0 && (n_steps == 0 || n_steps == 1 || n_steps == n / per_image),
+                  "gc_quantize_index_ms: n is a whole number of images of per_image elements, with no step, one for all or one each");
+    BASIC_REQUIRE(param_stride >= per_image, "gc_quantize_index_ms: param_stride is at least per_image");
+    if (n == 0) return BASIC_OK;
+    const dim3 grid(grid_for(n)), block(kBlock);
+    const size_t lds = table_len * sizeof(float);
+    if (n_steps)
+        hipLaunchKernelGGL(gc_quantize_index_ms_kernel<true>, grid, block, lds, as_stream(hip_stream), d_y, d_scales, d_means, n, per_image,
+                           param_stride, d_steps, n_steps, d_table, table_len, scale_bound, d_symbols, d_indexes, d_yhat);
+    else
+        hipLaunchKernelGGL(gc_quantize_index_ms_kernel<false>, grid, block, lds, as_stream(hip_stream), d_y, d_scales, d_means, n, per_image,
+                           param_stride, d_steps, n_steps, d_table, table_len, scale_bound, d_symbols, d_indexes, d_yhat);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_gc_dequantize_ms_dev(const int32_t *d_sym, const float *d_means, int64_t n, int64_t per_image, int64_t param_stride,
+                                          const float *d_steps, int n_steps, float *d_yhat, void *hip_stream)
+{
+    BASIC_REQUIRE(d_sym && d_means && d_yhat && n >= 0, "gc_dequantize_ms: bad argument");
+    if (!d_steps) n_steps = 0;
+    BASIC_REQUIRE(per_image >= 1 && n % per_image == 0 && (n_steps == 0 || n_steps == 1 || n_steps == n / per_image),
+                  "gc_dequantize_ms: n is a whole number of images of per_image elements, with no step, one for all or one each");
+    BASIC_REQUIRE(param_stride >= per_image, "gc_dequantize_ms: param_stride is at least per_image");
+    if (n == 0) return BASIC_OK;
+    if (n_steps)
+        hipLaunchKernelGGL(gc_dequantize_ms_kernel<true>, dim3(grid_for(n)), dim3(kBlock), 0, as_stream(hip_stream), d_sym, d_means, n,
+                           per_image, param_stride, d_steps, n_steps, d_yhat);
+    else
+        hipLaunchKernelGGL(gc_dequantize_ms_kernel<false>, dim3(grid_for(n)), dim3(kBlock), 0, as_stream(hip_stream), d_sym, d_means, n,
+                           per_image, param_stride, d_steps, n_steps, d_yhat);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+namespace {
+
+// both rate-curve entry points: d_means == nullptr is the zero-mean coder (param_stride unused)
+int rate_curve_launch(const float *d_y, const float *d_scales, const float *d_means, int64_t param_stride, int n_seg, int64_t per_seg,
+                      int segs_per_image, const float *d_cand, int n_cand, int cand_per_image, const float *d_table, int table_len,
+                      float scale_bound, const basic_rans_tables *t, uint64_t *d_bits, void *hip_stream)
 {
     BASIC_REQUIRE(d_y && d_scales && d_cand && d_table && t && d_bits && table_len >= 1 && table_len <= 4096, "gc_rate_curve: bad argument");
     BASIC_REQUIRE(n_seg >= 1 && per_seg >= 1 && segs_per_image >= 1 && n_seg % segs_per_image == 0,
@@ -719,16 +874,45 @@ extern "C" int basic_gc_rate_curve_dev(const float *d_y, const float *d_scales, 
     const dim3 grid(static_cast<unsigned>(n_seg * bps)), block(kBlock);
     const size_t lds = table_len * sizeof(float);
     auto *bits = reinterpret_cast<unsigned long long *>(d_bits);
-#define BASIC_RATE_LAUNCH(NC)                                                                                                        \
-    hipLaunchKernelGGL(gc_rate_curve_kernel<NC>, grid, block, lds, st, d_y, d_scales, per_seg, segs_per_image, static_cast<int>(bps), \
-                       d_cand, n_cand, cand_per_image, d_table, table_len, scale_bound, T, bits)
-    if (n_cand <= 2) BASIC_RATE_LAUNCH(2);
-    else if (n_cand <= 8) BASIC_RATE_LAUNCH(8);
-    else if (n_cand <= 16) BASIC_RATE_LAUNCH(16);
-    else BASIC_RATE_LAUNCH(32);
+#define BASIC_RATE_LAUNCH(NC, MEAN)                                                                                                   \
+    hipLaunchKernelGGL((gc_rate_curve_kernel<NC, MEAN>), grid, block, lds, st, d_y, d_scales, d_means, param_stride, per_seg,         \
+                       segs_per_image, static_cast<int>(bps), d_cand, n_cand, cand_per_image, d_table, table_len, scale_bound, T, bits)
+    if (d_means) {
+        if (n_cand <= 2) BASIC_RATE_LAUNCH(2, true);
+        else if (n_cand <= 8) BASIC_RATE_LAUNCH(8, true);
+        else if (n_cand <= 16) BASIC_RATE_LAUNCH(16, true);
+        else BASIC_RATE_LAUNCH(32, true);
+    } else {
+        if (n_cand <= 2) BASIC_RATE_LAUNCH(2, false);
+        else if (n_cand <= 8) BASIC_RATE_LAUNCH(8, false);
+        else if (n_cand <= 16) BASIC_RATE_LAUNCH(16, false);
+        else BASIC_RATE_LAUNCH(32, false);
+    }
 #undef BASIC_RATE_LAUNCH
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
+}
+
+}  // namespace
+
+extern "C" int basic_gc_rate_curve_dev(const float *d_y, const float *d_scales, int n_seg, int64_t per_seg, int segs_per_image,
+                                       const float *d_cand, int n_cand, int cand_per_image, const float *d_table, int table_len,
+                                       float scale_bound, const basic_rans_tables *t, uint64_t *d_bits, void *hip_stream)
+{
+    return rate_curve_launch(d_y, d_scales, nullptr, 0, n_seg, per_seg, segs_per_image, d_cand, n_cand, cand_per_image, d_table, table_len,
+                             scale_bound, t, d_bits, hip_stream);
+}
+
+extern "C" int basic_gc_rate_curve_ms_dev(const float *d_y, const float *d_scales, const float *d_means, int64_t param_stride, int n_seg,
+                                          int64_t per_seg, int segs_per_image, const float *d_cand, int n_cand, int cand_per_image,
+                                          const float *d_table, int table_len, float scale_bound, const basic_rans_tables *t,
+                                          uint64_t *d_bits, void *hip_stream)
+{
+    BASIC_REQUIRE(d_means, "gc_rate_curve_ms: d_means is null");
+    BASIC_REQUIRE(per_seg >= 1 && per_seg <= (INT64_MAX >> 32) && segs_per_image >= 1 && param_stride >= per_seg * segs_per_image,
+                  "gc_rate_curve_ms: param_stride is at least the per_seg * segs_per_image elements of an image");
+    return rate_curve_launch(d_y, d_scales, d_means, param_stride, n_seg, per_seg, segs_per_image, d_cand, n_cand, cand_per_image, d_table,
+                             table_len, scale_bound, t, d_bits, hip_stream);
 }
 
 extern "C" int basic_rate_select_dev(const uint64_t *d_bits, int n_images, int segs_per_image, int64_t per_seg, const float *d_cand,

@@ -1,4 +1,5 @@
-// Fused image entry points of the plain hyperprior latent graph (include/basic_hip.h section 8).
+// Fused image entry points of the two hyperprior latent graphs (include/basic_hip.h section 8): the scale hyperprior, whose h_s
+// gives a scale per latent, and the mean-scale hyperprior, whose h_s gives (scale, mean) and whose y is coded as round(y - mean).
 //
 // One C call = what GeneralCodec.compress / decompress (cbench/codecs/general_codec.py:44-130) run for the graph of
 // configs/lossy_graph_scalable_exp_hp.py:182-215 through LatentGraphicalANSEntropyCoder.encode / decode
@@ -112,6 +113,9 @@ struct basic_hp_session {
     const basic_rans_tables *z_tables = nullptr, *y_tables = nullptr;
     int z_channels = 0, y_channels = 0, x_channels = 0, out_channels = 0, n_scales = 0;
     float scale_bound = 0.11f;
+    // mean-scale graph: h_s ends in 2 * y_channels planes per image, scales [0, M) and means [M, 2 M) (upstream's chunk(2, 1)), and
+    // y is coded as round(y - mean).  Both halves are read where h_s (or the crop) left them.
+    bool mean_scale = false;
     int rans_waves = 0;
     int lanes = 1;       // y streams per image (basic_hp_session_set_stream_lanes)
     int res_lanes = 1;   // of the encoded batch held in h_words
@@ -346,11 +350,17 @@ extern "C" int basic_hp_session_create(const basic_conv_plan *const *g_a, int n_
     bool ok = ci == s->y_channels && co == z_channels;
     basic_conv_plan_channels(s->h_s.front(), &ci, nullptr);
     basic_conv_plan_channels(s->h_s.back(), nullptr, &co);
-    ok = ok && ci == z_channels && co == s->y_channels;   // scales only: the GaussianConditional graph
+    // y_channels outputs: scales only, the GaussianConditional graph; 2 * y_channels: (scales, means), the mean-scale graph
+    s->mean_scale = co == 2 * s->y_channels;
+    ok = ok && ci == z_channels && (co == s->y_channels || s->mean_scale);
     basic_conv_plan_channels(s->g_s.front(), &ci, nullptr);
     basic_conv_plan_channels(s->g_s.back(), nullptr, &s->out_channels);
     ok = ok && ci == s->y_channels;
-    if (!ok) { delete s; set_error("hp_session_create: channel counts of the transforms do not chain (x->y->z->scales(y)->x)"); return BASIC_ERR_INVALID; }
+    if (!ok) {
+        delete s;
+        set_error("hp_session_create: channel counts of the transforms do not chain (x->y->z->scales(y) or (scales, means)(y)->x)");
+        return BASIC_ERR_INVALID;
+    }
     s->z_channels = z_channels;
     s->z_tables = z_tables;
     s->y_tables = y_tables;
@@ -478,8 +488,8 @@ bool budgets_fit(const basic_hp_session *s, int batch)
 // Rate control of a call: the steps of its `batch` images into d_steps, chosen on the device from the curves of the y latent
 // (sy = batch * lanes streams of nyl symbols) under the budgets, the z streams' word counts (d_nw_z, written earlier on `st`)
 // counted in.  Enqueues only; the results travel to h_rate_out for the caller's next synchronisation of `st`.
-int choose_steps(basic_hp_session *s, const float *d_y, const float *d_scales, int batch, int lanes, int64_t nyl, const int32_t *d_nw_z,
-                 hipStream_t st)
+int choose_steps(basic_hp_session *s, const float *d_y, const float *d_scales, const float *d_means, int64_t param_stride, int batch,
+                 int lanes, int64_t nyl, const int32_t *d_nw_z, hipStream_t st)
 {
     const int K = static_cast<int>(s->rate_cand.size());
     const int sy = batch * lanes;
@@ -520,8 +530,13 @@ int choose_steps(basic_hp_session *s, const float *d_y, const float *d_scales, i
             d_cand = next;
             per_image = 1;
         }
-        rc = basic_gc_rate_curve_dev(d_y, d_scales, sy, nyl, lanes, d_cand, K, per_image, s->d_table.as<float>(), s->n_scales,
-                                     s->scale_bound, s->y_tables, s->d_rate_bits.as<uint64_t>(), st);
+        if (d_means)   // the mean-scale graph: the curve of round((y - mean) / step)
+            rc = basic_gc_rate_curve_ms_dev(d_y, d_scales, d_means, param_stride, sy, nyl, lanes, d_cand, K, per_image,
+                                            s->d_table.as<float>(), s->n_scales, s->scale_bound, s->y_tables,
+                                            s->d_rate_bits.as<uint64_t>(), st);
+        else
+            rc = basic_gc_rate_curve_dev(d_y, d_scales, sy, nyl, lanes, d_cand, K, per_image, s->d_table.as<float>(), s->n_scales,
+                                         s->scale_bound, s->y_tables, s->d_rate_bits.as<uint64_t>(), st);
         if (!rc)
             rc = basic_rate_select_dev(s->d_rate_bits.as<uint64_t>(), batch, lanes, nyl, d_cand, K, per_image, d_nw_z, d_budget,
                                        d_steps_res, d_choice, d_pred, st);
@@ -596,6 +611,7 @@ int encode_body(basic_hp_session *s, const float *d_x, bool x_in_session, int ba
     rc = run_chain(s, s->h_a, s->d_y.as<float>(), batch, yh, yw, &s->d_z, nullptr, &zh, &zw, st);
     if (rc) return rc;
     const int64_t nz = static_cast<int64_t>(s->z_channels) * zh * zw, ny = static_cast<int64_t>(s->y_channels) * yh * yw;
+    const int64_t np = s->mean_scale ? 2 * ny : ny;   // prior elements per image: scales, or scales then means
     // lane streams: the y latent of image b is K contiguous runs of ny / K symbols, stream b * K + k (the z path keeps one stream)
     const int K = s->lanes;
     BASIC_REQUIRE(ny % K == 0, "hp_encode_images: stream_lanes does not divide the y latent (channels * h * w) of this call");
@@ -622,10 +638,10 @@ int encode_body(basic_hp_session *s, const float *d_x, bool x_in_session, int ba
     BASIC_REQUIRE(ph >= yh && pw >= yw, "hp_encode_images: the hyper-synthesis output is smaller than the latent");
     const float *d_scales = s->d_prior.as<float>();
     if (ph != yh || pw != yw) {
-        rc = s->d_scales.ensure(sizeof(float) * batch * ny);
+        rc = s->d_scales.ensure(sizeof(float) * batch * np);
         if (rc) return rc;
-        hipLaunchKernelGGL(crop_planes_kernel, dim3(grid_for(batch * ny)), dim3(256), 0, st, s->d_prior.as<float>(), ph, pw,
-                           s->d_scales.as<float>(), yh, yw, static_cast<int64_t>(batch) * s->y_channels);
+        hipLaunchKernelGGL(crop_planes_kernel, dim3(grid_for(batch * np)), dim3(256), 0, st, s->d_prior.as<float>(), ph, pw,
+                           s->d_scales.as<float>(), yh, yw, static_cast<int64_t>(batch) * (np / (static_cast<int64_t>(yh) * yw)));
         BASIC_HIP_TRY(hipGetLastError());
         d_scales = s->d_scales.as<float>();
     }
@@ -633,8 +649,24 @@ int encode_body(basic_hp_session *s, const float *d_x, bool x_in_session, int ba
     if (!rc) rc = s->y_idx.ensure(sizeof(int32_t) * batch * ny);
     if (rc) return rc;
     s->rate_res_batch = 0;
-    if (!s->rate_budget.empty()) {
-        rc = choose_steps(s, s->d_y.as<float>(), d_scales, batch, K, nyl, d_nw_z, st);
+    if (s->mean_scale) {
+        // the means half of every image's prior follows its scales half: read in place, nothing is copied
+        const float *d_means = d_scales + ny, *d_steps = nullptr;
+        int n_steps = 0;
+        if (!s->rate_budget.empty()) {
+            rc = choose_steps(s, s->d_y.as<float>(), d_scales, d_means, np, batch, K, nyl, d_nw_z, st);
+            n_steps = batch;
+        } else if (!s->qsteps.empty()) {
+            rc = upload_qsteps(s, st);
+            n_steps = static_cast<int>(s->qsteps.size());
+        }
+        if (n_steps) d_steps = s->d_steps.as<float>();
+        if (!rc)
+            rc = basic_gc_quantize_index_ms_dev(s->d_y.as<float>(), d_scales, d_means, batch * ny, ny, np, d_steps, n_steps,
+                                                s->d_table.as<float>(), s->n_scales, s->scale_bound, s->y_sym.as<int32_t>(),
+                                                s->y_idx.as<int32_t>(), nullptr, st);
+    } else if (!s->rate_budget.empty()) {
+        rc = choose_steps(s, s->d_y.as<float>(), d_scales, nullptr, 0, batch, K, nyl, d_nw_z, st);
         if (!rc)
             rc = basic_gc_quantize_index_q_dev(s->d_y.as<float>(), d_scales, batch * ny, ny, s->d_steps.as<float>(), batch,
                                                s->d_table.as<float>(), s->n_scales, s->scale_bound, s->y_sym.as<int32_t>(),
@@ -859,6 +891,7 @@ int decode_body(basic_hp_session *s, const uint8_t *data, int64_t len, float *d_
     if (rc) return rc;
     BASIC_REQUIRE(static_cast<int64_t>(batch) * s->out_channels * oh * ow <= xhat_capacity_floats, "hp_decode_images: output buffer too small");
     const int64_t nz = static_cast<int64_t>(s->z_channels) * zh * zw, ny = static_cast<int64_t>(s->y_channels) * yh * yw;
+    const int64_t np = s->mean_scale ? 2 * ny : ny;   // prior elements per image: scales, or scales then means
     BASIC_REQUIRE(ny % K == 0, "hp_decode_images: stream_lanes does not divide the y latent (channels * h * w) of this stream");
     const int64_t nyl = ny / K;   // y: stream b * K + k continues image b at symbol k * nyl -- contiguous runs of [B][ny]
     // ---- unframe both bodies into ONE pinned staging area [z words | y words | z offsets | y offsets] and upload it
@@ -912,10 +945,10 @@ int decode_body(basic_hp_session *s, const uint8_t *data, int64_t len, float *d_
     BASIC_REQUIRE(ph >= yh && pw >= yw, "hp_decode_images: the hyper-synthesis output is smaller than the latent");
     const float *d_scales = s->d_prior.as<float>();
     if (ph != yh || pw != yw) {
-        rc = s->d_scales.ensure(sizeof(float) * batch * ny);
+        rc = s->d_scales.ensure(sizeof(float) * batch * np);
         if (rc) return rc;
-        hipLaunchKernelGGL(crop_planes_kernel, dim3(grid_for(batch * ny)), dim3(256), 0, st, s->d_prior.as<float>(), ph, pw,
-                           s->d_scales.as<float>(), yh, yw, static_cast<int64_t>(batch) * s->y_channels);
+        hipLaunchKernelGGL(crop_planes_kernel, dim3(grid_for(batch * np)), dim3(256), 0, st, s->d_prior.as<float>(), ph, pw,
+                           s->d_scales.as<float>(), yh, yw, static_cast<int64_t>(batch) * (np / (static_cast<int64_t>(yh) * yw)));
         BASIC_HIP_TRY(hipGetLastError());
         d_scales = s->d_scales.as<float>();
     }
@@ -925,7 +958,13 @@ int decode_body(basic_hp_session *s, const uint8_t *data, int64_t len, float *d_
     if (rc) return rc;
     // indexes only: the symbol output of this launch is scratch (the module path does the same, compressai_coder.py:387-393)
     const int n_steps = static_cast<int>(s->qsteps.size());
-    if (!n_steps) {
+    if (s->mean_scale) {
+        if (n_steps) rc = upload_qsteps(s, st);
+        if (!rc)
+            rc = basic_gc_quantize_index_ms_dev(nullptr, d_scales, nullptr, batch * ny, ny, np, n_steps ? s->d_steps.as<float>() : nullptr,
+                                                n_steps, s->d_table.as<float>(), s->n_scales, s->scale_bound, nullptr,
+                                                s->y_idx.as<int32_t>(), nullptr, st);
+    } else if (!n_steps) {
         rc = basic_gc_quantize_index_dev(d_scales, d_scales, batch * ny, s->d_table.as<float>(), s->n_scales, s->scale_bound,
                                          s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
     } else {
@@ -938,7 +977,10 @@ int decode_body(basic_hp_session *s, const uint8_t *data, int64_t len, float *d_
     rc = basic_rans_decode_batch_dev(s->y_tables, d_wy, d_oy, s->y_idx.as<int32_t>(), s->seg_y.as<int64_t>(), sy, s->y_sym.as<int32_t>(),
                                      s->state.as<uint64_t>() + batch, s->pos.as<int64_t>() + batch, st);
     if (rc) return rc;
-    if (!n_steps) rc = basic_i32_to_f32_dev(s->y_sym.as<int32_t>(), batch * ny, s->d_y.as<float>(), st);
+    if (s->mean_scale)
+        rc = basic_gc_dequantize_ms_dev(s->y_sym.as<int32_t>(), d_scales + ny, batch * ny, ny, np, n_steps ? s->d_steps.as<float>() : nullptr,
+                                        n_steps, s->d_y.as<float>(), st);
+    else if (!n_steps) rc = basic_i32_to_f32_dev(s->y_sym.as<int32_t>(), batch * ny, s->d_y.as<float>(), st);
     else rc = basic_gc_dequantize_q_dev(s->y_sym.as<int32_t>(), batch * ny, ny, s->d_steps.as<float>(), n_steps, s->d_y.as<float>(), st);
     if (rc) return rc;
     // ---- edge y -> x: g_s straight into the caller's buffer

@@ -426,14 +426,16 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
 
     def _fused_session(self, kwargs, prior):
         """The HyperpriorSession serving this graph, or None when the graph is anything but
-        x -g_a-> y -h_a-> z, z: EntropyBottleneck coder, y: GaussianConditional coder on h_s(z), x: dummy
-        (configs/lossy_graph_scalable_exp_hp.py:182-215) with no dynamic nodes / gains / caller-supplied inputs."""
+        x -g_a-> y -h_a-> z, z: EntropyBottleneck coder, y: GaussianConditional coder (or its mean-scale form) on h_s(z), x: dummy
+        (configs/lossy_graph_scalable_exp_hp.py:182-215) with no dynamic nodes / gains / caller-supplied inputs.  The session tells
+        the two y coders apart by the channels h_s ends in."""
         if not self.use_fused_session or self.training or prior is not None or kwargs:
             return None
         elig = getattr(self, "_fused_eligible", None)
         if elig is None:
             from ..prior_model.prior_coder.compressai_coder import (CompressAIEntropyBottleneckPriorCoder,
-                                                                    CompressAIGaussianConditionalCoder)
+                                                                    CompressAIGaussianConditionalCoder,
+                                                                    CompressAIMeanScaleGaussianConditionalCoder)
             from ...nn.models.google import BasicHyperpriorModule
             c, inf, gen = self.latent_node_entropy_coders, self.latent_inference_modules, self.latent_generative_modules
             elig = (list(self.latent_node_inference_topo_order) == ["x", "y", "z"]
@@ -441,7 +443,8 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                     and len(self.node_generators) == 0 and self._num_rate_levels <= 0 and self._num_complex_levels <= 0
                     and self._num_tasks <= 0 and set(inf.keys()) == {"x_y", "y_z"} and set(gen.keys()) == {"z_y", "y_x"}
                     and all(type(m).forward is BasicHyperpriorModule.forward for m in list(inf.values()) + list(gen.values()))
-                    and type(c["y"]) is CompressAIGaussianConditionalCoder and type(c["z"]) is CompressAIEntropyBottleneckPriorCoder
+                    and type(c["y"]) in (CompressAIGaussianConditionalCoder, CompressAIMeanScaleGaussianConditionalCoder)
+                    and type(c["z"]) is CompressAIEntropyBottleneckPriorCoder
                     and not self.latent_inference_input_mapping and not self.latent_generative_input_mapping
                     and (self.use_lossy_compression or isinstance(c["x"] if "x" in c else None, LossyDummyEntropyCoder)))
             self._fused_eligible = bool(elig)
@@ -501,11 +504,12 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         graph's y coder is not the GaussianConditional coder, ValueError for an invalid request (utils/rate.py)."""
         if rate_target is None:
             return None, None
-        from ..prior_model.prior_coder.compressai_coder import CompressAIGaussianConditionalCoder
+        from ..prior_model.prior_coder.compressai_coder import (CompressAIGaussianConditionalCoder,
+                                                                CompressAIMeanScaleGaussianConditionalCoder)
         from ...utils.rate import as_rate_target
         coder = self.latent_node_entropy_coders[self.QSTEP_NODE] if self.QSTEP_NODE in self.latent_node_entropy_coders else None
-        if type(coder) is not CompressAIGaussianConditionalCoder:
-            raise TypeError(f"rate_target= chooses the quantiser step of a CompressAIGaussianConditionalCoder at node '{self.QSTEP_NODE}'; "
+        if type(coder) not in (CompressAIGaussianConditionalCoder, CompressAIMeanScaleGaussianConditionalCoder):
+            raise TypeError(f"rate_target= chooses the quantiser step of a CompressAIGaussianConditionalCoder (scale-only or mean-scale) at node '{self.QSTEP_NODE}'; "
                             f"this graph codes it with {type(coder).__name__}")
         rt = as_rate_target(rate_target, batch)
         return rt, {self.QSTEP_NODE: dict(rate_target=rt)}
@@ -515,10 +519,11 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         TypeError when the graph's y coder is not the GaussianConditional coder; ValueError for invalid steps (utils/qstep.py)."""
         if qstep is None:
             return None, None
-        from ..prior_model.prior_coder.compressai_coder import CompressAIGaussianConditionalCoder
+        from ..prior_model.prior_coder.compressai_coder import (CompressAIGaussianConditionalCoder,
+                                                                CompressAIMeanScaleGaussianConditionalCoder)
         coder = self.latent_node_entropy_coders[self.QSTEP_NODE] if self.QSTEP_NODE in self.latent_node_entropy_coders else None
-        if type(coder) is not CompressAIGaussianConditionalCoder:
-            raise TypeError(f"qstep= is the quantiser step of a CompressAIGaussianConditionalCoder at node '{self.QSTEP_NODE}'; this "
+        if type(coder) not in (CompressAIGaussianConditionalCoder, CompressAIMeanScaleGaussianConditionalCoder):
+            raise TypeError(f"qstep= is the quantiser step of a CompressAIGaussianConditionalCoder (scale-only or mean-scale) at node '{self.QSTEP_NODE}'; this "
                             f"graph codes it with {type(coder).__name__}.  The PGM coders' own knob is "
                             "quantizer_type='uniform_scale' with quantizer_params=[step]")
         steps = check_qsteps(qstep, batch)
@@ -1210,7 +1215,8 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         gen = self.latent_inference_modules
         M = next((int(m.M) for name, m in gen.items() if name.split(self.DEFAULT_EDGE_SPLIT_SYMBOL)[1] == self.QSTEP_NODE and hasattr(m, "M")), 192)
         pixels = sum(g.coded_size(k)[0] * g.coded_size(k)[1] for g in grids for k in range(len(g)))
-        need = 8 * M * pixels // 256
+        curve_means = getattr(ycoder, "rate_curve_means", None)   # the mean-scale coder: the retained sigma is its chunked prior
+        need = (12 if curve_means is not None else 8) * M * pixels // 256
         if need > workspace_limit:
             raise ValueError(f"the latents of {sum(len(g) for g in grids)} tiles ({pixels} coded pixels) take {need} bytes on the device, "
                              f"more than workspace_limit={workspace_limit}: code the pictures in several calls")
@@ -1235,7 +1241,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             payload_budgets = torch.from_numpy(budgets - framings).to(self.device)
             steps, choice, pred, tile_steps, tile_pred = K.rate_steps_groups(
                 latents, groups, payload_budgets, torch.cat(extras), grid0, passes, ycoder._scale_table_dev, ycoder._tables,
-                ycoder.scale_bound, lanes)
+                ycoder.scale_bound, lanes, means=curve_means)
             strings = [[None] * len(g) for g in grids]
             spent = [[0] * len(g) for g in grids]
 

@@ -1,6 +1,7 @@
 """z / y latent coders of the plain hyperprior graph -- API of
 cbench/modules/prior_model/prior_coder/compressai_coder.py:87-397 (CompressAIEntropyBottleneckPriorCoder,
-CompressAISlimmableEntropyBottleneckPriorCoder, CompressAIGaussianConditionalCoder).
+CompressAISlimmableEntropyBottleneckPriorCoder, CompressAIGaussianConditionalCoder) and, for the mean-scale hyperprior graph
+(:556-619), CompressAIMeanScaleGaussianConditionalCoder.
 
 The reference delegates the arithmetic to CompressAI 1.2.3 (``EntropyBottleneck``,
 ``GaussianConditional``, ``compressai.ans``), which is NOT vendored in the reference tree
@@ -587,3 +588,116 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
         if channel_gains_inv is not None:
             yhat = yhat * channel_gains_inv.reshape(1, -1, 1, 1)
         return yhat
+
+
+class CompressAIMeanScaleGaussianConditionalCoder(CompressAIGaussianConditionalCoder):
+    """compressai_coder.py:556-619 (upstream MeanScaleHyperprior): a Gaussian whose hyperprior gives (scale, mean) for every latent.
+
+    ``prior`` is [B][2 C][h'][w'] -- scales in channels [0, C), means in [C, 2 C), upstream's ``gaussian_params.chunk(2, 1)`` -- and y
+    is coded as ``round(y - mean)`` under the scale's table entry, rebuilt as ``symbol + mean`` (INTEGRATION.md "Mean-scale
+    hyperprior").  Constructor, tables, ``state_dict`` keys (``gaussian_conditional.*``), ``stream_lanes``, ``qstep=``,
+    ``rate_target=``, ``rate_measure=`` and ``lazy=`` are the base coder's; the cropped prior is read in place by the ``_ms`` kernels,
+    its halves are never copied apart.  ``channel_gains`` are refused: upstream defines no order of gain and mean."""
+
+    rate_curve_means = K.CHUNKED   # what the rate kernels are told about the "scales" this coder retains (rate_measure=)
+
+    def _split(self, y_shape, prior):
+        """The cropped, contiguous prior of a latent of ``y_shape`` = (B, C, h, w); ValueError unless it has exactly 2 C channels."""
+        B, C, h, w = y_shape
+        if prior is None or prior.dim() != 4 or prior.shape[1] != 2 * C:
+            got = None if prior is None else tuple(prior.shape)
+            raise ValueError(f"the mean-scale coder takes a prior of 2 * {C} channels (scales, then means) for a latent of {C}, got {got}")
+        if prior.shape[0] != B or prior.shape[2] < h or prior.shape[3] < w:
+            raise ValueError(f"the prior {tuple(prior.shape)} does not cover the latent {tuple(y_shape)}")
+        return self._crop(prior, h, w)
+
+    @staticmethod
+    def _no_gains(channel_gains, channel_gains_inv):
+        if channel_gains is not None or channel_gains_inv is not None:
+            raise ValueError("the mean-scale coder takes no channel_gains: upstream defines no order of gain and mean (use qstep=)")
+
+    def _begin(self, y, sym, idx, lazy):
+        per = self._lane_length(y[0].numel())
+        body = PendingBody(self._tables, self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), per), y.shape[-2:])
+        return body if lazy else body.result()
+
+    def _encode_q(self, y, prior, qstep, lazy, steps_on_device=False):
+        """The base coder's, on the chunked prior (``qstep`` None: the step-less format)."""
+        sym, idx, _ = K.gc_quantize_index_ms(y, self._split(y.shape, prior), self._scale_table_dev, self.scale_bound, steps=qstep,
+                                             want_yhat=False, steps_on_device=steps_on_device)
+        return self._begin(y, sym, idx, lazy)
+
+    def _encode_rate(self, y, prior, rate_target, lazy):
+        from ....utils.rate import as_rate_target
+        rt = as_rate_target(rate_target, y.shape[0])
+        B = y.shape[0]
+        self._lane_length(y[0].numel())
+        prior = self._split(y.shape, prior)
+        budgets = torch.from_numpy(rt.budgets_for(B)).to(y.device)
+        extra = None
+        if rt.extra_words is not None:
+            extra = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(rt.extra_words, dtype=np.int32), (B,)))).to(y.device)
+        steps, choice, pred = K.rate_steps(y, prior, budgets, extra, rt.candidates, rt.passes, self._scale_table_dev, self._tables,
+                                           self.scale_bound, self.stream_lanes, means=K.CHUNKED)
+        rt.set_device_result(steps, pred, choice)
+        sym, idx, _ = K.gc_quantize_index_ms(y, prior, self._scale_table_dev, self.scale_bound, steps=steps, want_yhat=False,
+                                             steps_on_device=True)
+        body = self._begin(y, sym, idx, True)
+        if lazy:
+            return body
+        out = body.result()
+        rt.resolve()
+        return out
+
+    def forward(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, **kwargs):
+        self._ready()
+        self._no_gains(channel_gains, channel_gains_inv)
+        prior = self._split(y.shape, prior)
+        C = y.shape[1]
+        scales = prior[:, :C].contiguous()   # the likelihood kernel's [B][C][h][w] layout (not on the coding path)
+        if qstep is None and getattr(self, "rate_proxy", "round") == "noise":   # upstream quantize(..., "noise"): the train-mode proxy
+            yhat = y + (torch.rand_like(y) - 0.5)
+            res = yhat - prior[:, C:]
+            self.update_cache("metric_dict", prior_entropy=K.gauss_nll_per_image(res.contiguous(), scales, False, self.scale_bound, 1e-9).mean())
+            return yhat
+        steps = None if qstep is None else K.qsteps_tensor(qstep, y.shape[0], y.device)
+        sym, _, yhat = K.gc_quantize_index_ms(y, prior, self._scale_table_dev, self.scale_bound, steps=steps, steps_on_device=steps is not None)
+        # the rate of what is coded: the symbols under the scales (scale / step with a step), as the base coder's _forward_q has it
+        self.update_cache("metric_dict", prior_entropy=K.gauss_nll_per_image(K.i32_to_f32(sym), scales, False, self.scale_bound, 1e-9,
+                                                                              steps=steps).mean())
+        return yhat
+
+    def encode(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, lazy=False, qstep=None, rate_target=None,
+               rate_measure=None, **kwargs):
+        self._ready()
+        self._no_gains(channel_gains, channel_gains_inv)
+        if rate_measure is not None:
+            if qstep is not None or rate_target is not None:
+                raise ValueError("rate_measure= retains the latent for a step chosen later: no qstep= or rate_target= with it")
+            prior = self._split(y.shape, prior)
+            # the one cropped prior holds both halves where they lie: "scales" is what rate_steps_groups(means=CHUNKED) and
+            # _encode_q read in place, "means" the view of its second half
+            rate_measure.update(y=y, scales=prior, means=prior[:, y.shape[1]:])
+            return None
+        if rate_target is not None:
+            if qstep is not None:
+                raise ValueError("rate_target= and qstep= are two rate knobs: give one of them")
+            return self._encode_rate(y, prior, rate_target, lazy)
+        return self._encode_q(y, prior, qstep, lazy)
+
+    def decode(self, byte_string, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, **kwargs):
+        self._ready()
+        self._no_gains(channel_gains, channel_gains_inv)
+        h, w, ns = K.frame_header(byte_string)
+        if prior is None or prior.dim() != 4 or prior.shape[1] % 2:
+            got = None if prior is None else tuple(prior.shape)
+            raise ValueError(f"the mean-scale coder takes a prior of 2 * C channels (scales, then means), got {got}")
+        prior = self._crop(prior, h, w)
+        B, C = prior.shape[0], prior.shape[1] // 2
+        per = self._lane_length(C * h * w)
+        if self.stream_lanes > 1 and ns != B * self.stream_lanes:
+            raise ValueError(f"stream body holds {ns} streams, this coder's configuration needs {B * self.stream_lanes}")
+        steps = None if qstep is None else K.qsteps_tensor(qstep, B, prior.device)
+        _, idx, _ = K.gc_quantize_index_ms(None, prior, self._scale_table_dev, self.scale_bound, steps=steps, steps_on_device=steps is not None)
+        sym = self._tables.decode_batch_from_frame(byte_string, idx.reshape(-1), per)
+        return K.gc_dequantize_ms(sym.reshape(idx.shape), prior, steps=qstep)

@@ -406,6 +406,87 @@ def gc_dequantize_q(sym, steps):
     return out
 
 
+# ---- mean-scale y coder (INTEGRATION.md "Mean-scale hyperprior"): sym = rint(y - mu), yhat = sym + mu
+def _ms_params(prior, means, B, per, what):
+    """-> (scales address, means address, param_stride, tensors to keep alive) of the parameters of a [B, ...] latent with ``per``
+    elements an image.  ``means`` None: ``prior`` is the chunked prior [B][2 M][...], scales then means along dim 1 (upstream's
+    chunk(2, 1)), read in place -- it may be a view of a larger tensor as long as every image's 2 * per elements are contiguous.
+    Else ``prior`` holds the scales and ``means`` the means, two contiguous tensors of B * per elements."""
+    if means is not None:
+        scales, means = _dev(prior, torch.float32), _dev(means, torch.float32)
+        if scales.numel() != B * per or means.numel() != B * per:
+            raise ValueError(f"{what}: scales and means hold one element per latent element ({B * per})")
+        return scales.data_ptr(), means.data_ptr(), per, (scales, means)
+    if not isinstance(prior, torch.Tensor) or not prior.is_cuda:
+        raise _lib.BasicHipError("cbench_basic_amd kernels need tensors on the MI355X (got a CPU tensor); there is no CPU fallback")
+    if prior.dtype != torch.float32:
+        raise TypeError(f"expected {torch.float32}, got {prior.dtype}")
+    if prior.dim() < 2 or prior.shape[0] != B or prior[0].numel() != 2 * per:
+        raise ValueError(f"{what}: the chunked prior is [B][2 M][...] with twice the latent's {per} elements an image, got {tuple(prior.shape)}")
+    if not prior[0].is_contiguous() or (B > 1 and prior.stride(0) < 2 * per):
+        raise ValueError(f"{what}: the prior of an image must be contiguous (scales then means); call .contiguous() on it")
+    stride = prior.stride(0) if B > 1 else 2 * per
+    return prior.data_ptr(), prior.data_ptr() + 4 * per, stride, (prior,)
+
+
+def _ms_steps(steps, B, device, steps_on_device):
+    if steps is None:
+        return None
+    if steps_on_device:
+        steps = _dev(steps, torch.float32)
+        if steps.numel() not in (1, B):
+            raise ValueError(f"{steps.numel()} quantiser steps for a batch of {B}: give one, or one per image")
+        return steps
+    return qsteps_tensor(steps, B, device)
+
+
+def gc_quantize_index_ms(y, prior, table, bound=0.11, steps=None, means=None, want_yhat=True, steps_on_device=False):
+    """basic_gc_quantize_index_ms_dev on a [B, ...] latent: sym = rint(y - mu) (rint((y - mu) / step) with ``steps``), idx from
+    max(scale, bound) (/ step), yhat = sym + mu ((sym * step) + mu).  ``prior`` / ``means``: see _ms_params.  ``y`` None: indexes
+    only (the decoder) -- the latent's shape is then the scales half of ``prior`` (or ``prior`` itself with ``means``), and
+    (None, idx, None) comes back."""
+    table = _dev(table, torch.float32)
+    if y is None:
+        if means is None:
+            if prior.dim() < 2 or prior.shape[1] % 2:
+                raise ValueError("gc_quantize_index_ms: the chunked prior is [B][2 M][...]")
+            shape = (prior.shape[0], prior.shape[1] // 2) + tuple(prior.shape[2:])
+        else:
+            shape = tuple(prior.shape)
+        B, per = shape[0], int(np.prod(shape[1:]))
+        device = prior.device
+    else:
+        y = _dev(y, torch.float32)
+        B, per = _per_image(y)
+        shape, device = tuple(y.shape), y.device
+    ps, pm, stride, keep = _ms_params(prior, means, B, per, "gc_quantize_index_ms")
+    steps = _ms_steps(steps, B, device, steps_on_device)
+    idx = torch.empty(shape, device=device, dtype=torch.int32)
+    sym = torch.empty(shape, device=device, dtype=torch.int32) if y is not None else None
+    yhat = torch.empty(shape, device=device, dtype=torch.float32) if (y is not None and want_yhat) else None
+    _lib.check(_lib.lib().basic_gc_quantize_index_ms_dev(
+        y.data_ptr() if y is not None else None, ps, pm if y is not None else None, B * per, per, stride,
+        steps.data_ptr() if steps is not None else None, steps.numel() if steps is not None else 0, table.data_ptr(), table.numel(),
+        float(bound), sym.data_ptr() if sym is not None else None, idx.data_ptr(), yhat.data_ptr() if yhat is not None else None, _stream()))
+    del keep
+    return sym, idx, yhat
+
+
+def gc_dequantize_ms(sym, prior, steps=None, means=None):
+    """float(sym) + mu, or (float(sym) * step) + mu, for a [B, ...] int32 tensor (basic_gc_dequantize_ms_dev).  ``prior`` / ``means``:
+    see _ms_params (of a chunked prior only the means half is read)."""
+    sym = _dev(sym, torch.int32)
+    B, per = _per_image(sym)
+    _, pm, stride, keep = _ms_params(prior, means, B, per, "gc_dequantize_ms")
+    steps = _ms_steps(steps, B, sym.device, False)
+    out = torch.empty(sym.shape, device=sym.device, dtype=torch.float32)
+    _lib.check(_lib.lib().basic_gc_dequantize_ms_dev(sym.data_ptr(), pm, sym.numel(), per, stride,
+                                                     steps.data_ptr() if steps is not None else None,
+                                                     steps.numel() if steps is not None else 0, out.data_ptr(), _stream()))
+    del keep
+    return out
+
+
 # ---- rate control (INTEGRATION.md "Rate control"): the coder's exact table cost at K candidate steps from one read of y and sigma
 def rans_cost_table(cdfs, cdf_sizes, precision=16):
     """basic_rans_cost_table_host: uint32 [rows][stride] bit costs (2^-16 bit) of the symbols of int32 [rows][stride] cdfs.  Host
@@ -438,15 +519,25 @@ def _rate_cand(cand, images):
     return cand, cand.shape[1], 1
 
 
-def rate_curve(y, scales, cand, table, tables, bound=0.11, lanes=1, out=None):
+CHUNKED = "chunked"   # means=CHUNKED: the ``scales`` argument is the chunked prior [B][2 M][...], scales then means, read in place
+
+
+def rate_curve(y, scales, cand, table, tables, bound=0.11, lanes=1, out=None, means=None):
     """basic_gc_rate_curve_dev on a [B, ...] latent: int64 [B * lanes][K], entry (b * lanes + l, k) = the summed table cost (2^-16 bit)
     of lane stream l of image b at step ``cand[k]`` (``cand``: float32 device tensor [K], or [B][K] with a grid per image; the values
     are the caller's to validate).  ``tables``: the RansTables that will code the symbols.  ``out``: a contiguous int64 [B * lanes][K]
-    device tensor to write instead of a new one (the rows of a larger curve tensor)."""
-    y, scales, table = _dev(y, torch.float32), _dev(scales, torch.float32), _dev(table, torch.float32)
+    device tensor to write instead of a new one (the rows of a larger curve tensor).  ``means``: the mean-scale coder's curve
+    (basic_gc_rate_curve_ms_dev), the costs of rint((y - mu) / step) -- a tensor of means beside ``scales``, or CHUNKED when
+    ``scales`` is the chunked prior (_ms_params)."""
+    y, table = _dev(y, torch.float32), _dev(table, torch.float32)
     B, per = _per_image(y)
-    if scales.numel() != y.numel():
-        raise ValueError("rate_curve: y and scales must hold the same number of elements")
+    ms = None
+    if means is not None:
+        ms = _ms_params(scales, None if isinstance(means, str) and means == CHUNKED else means, B, per, "rate_curve")
+    else:
+        scales = _dev(scales, torch.float32)
+        if scales.numel() != y.numel():
+            raise ValueError("rate_curve: y and scales must hold the same number of elements")
     if lanes < 1 or per % lanes:
         raise ValueError(f"rate_curve: {lanes} lanes do not divide the {per} symbols of an image")
     cand, K, cpi = _rate_cand(cand, B)
@@ -456,6 +547,11 @@ def rate_curve(y, scales, cand, table, tables, bound=0.11, lanes=1, out=None):
         bits = out
         if bits.dtype != torch.int64 or bits.device != y.device or tuple(bits.shape) != (B * lanes, K) or not bits.is_contiguous():
             raise ValueError(f"rate_curve: out is a contiguous int64 [{B * lanes}][{K}] tensor on the latent's device")
+    if ms is not None:
+        _lib.check(_lib.lib().basic_gc_rate_curve_ms_dev(y.data_ptr(), ms[0], ms[1], ms[2], B * lanes, per // lanes, int(lanes),
+                                                         cand.data_ptr(), K, cpi, table.data_ptr(), table.numel(), float(bound),
+                                                         tables._h, bits.data_ptr(), _stream()))
+        return bits
     _lib.check(_lib.lib().basic_gc_rate_curve_dev(y.data_ptr(), scales.data_ptr(), B * lanes, per // lanes, int(lanes), cand.data_ptr(), K, cpi,
                                                   table.data_ptr(), table.numel(), float(bound), tables._h, bits.data_ptr(), _stream()))
     return bits
@@ -499,10 +595,11 @@ def rate_refine(cand, choice, t=None):
     return out
 
 
-def rate_steps(y, scales, budgets, extra_words, candidates, passes, table, tables, bound=0.11, lanes=1, return_trace=False):
+def rate_steps(y, scales, budgets, extra_words, candidates, passes, table, tables, bound=0.11, lanes=1, return_trace=False, means=None):
     """curve -> select -> (refine -> curve -> select) x (passes - 1) on the device, nothing synchronised: (steps float32 [B], choice
     int32 [B], pred_bytes int64 [B]) of the last pass.  ``candidates``: the first grid, validated on the host (utils/rate.py);
-    ``budgets``: int64 [B] device tensor.  ``return_trace``: also the list of every pass's (candidates, bits, choice)."""
+    ``budgets``: int64 [B] device tensor.  ``return_trace``: also the list of every pass's (candidates, bits, choice).  ``means``: as
+    rate_curve's."""
     from ..utils.rate import check_candidates, check_passes, refine_t
     passes = check_passes(passes)
     B, per = _per_image(y)
@@ -512,7 +609,7 @@ def rate_steps(y, scales, budgets, extra_words, candidates, passes, table, table
     for p in range(passes):
         if p:
             cand = rate_refine(cand, choice, t)
-        bits = rate_curve(y, scales, cand, table, tables, bound, lanes)
+        bits = rate_curve(y, scales, cand, table, tables, bound, lanes, means=means)
         steps, choice, pred = rate_select(bits, per // lanes, cand, budgets, extra_words, lanes)
         trace.append((cand, bits, choice))
     return (steps, choice, pred, trace) if return_trace else (steps, choice, pred)
@@ -575,20 +672,28 @@ def rate_select_groups(bits, tile_first_seg, tile_per_seg, groups, cand, budgets
 
 
 def rate_steps_groups(chunks, groups, budgets, tile_extra_words, candidates, passes, table, tables, bound=0.11, lanes=1,
-                      return_trace=False):
+                      return_trace=False, means=None):
     """rate_steps over the tiles of many pictures: ``chunks`` is a list of (y, scales) pairs of [B_c, ...] latents (one per pooled coding
     call; the tiles are numbered through the chunks in order), ``groups`` the tile numbers of every picture.  Per pass: one
     rate_curve per chunk into that chunk's rows of ONE curve tensor (every tile under its own picture's candidate grid), one
     rate_select_groups, and between passes one rate_refine with groups in the place of images.  Nothing is synchronised.
     -> (steps [G], choice [G], pred_bytes [G], tile_steps [T], tile_pred [T]) of the last pass; ``return_trace``: also the list of
-    every pass's (candidates, bits, choice)."""
+    every pass's (candidates, bits, choice).  ``means``: the mean-scale coder -- CHUNKED when every chunk's ``scales`` is its chunked
+    prior, or a list of one tensor of means per chunk (rate_curve)."""
     from ..utils.rate import check_candidates, check_passes, refine_t
     passes = check_passes(passes)
     grid0 = check_candidates(candidates)
+    chunks = list(chunks)
+    if means is None or isinstance(means, str):
+        chunk_means = [means] * len(chunks)
+    else:
+        chunk_means = list(means)
+        if len(chunk_means) != len(chunks):
+            raise ValueError("rate_steps_groups: means is CHUNKED or one tensor per chunk")
     first_seg, per_seg, sizes = [], [], []
     for y, scales in chunks:
         B, per = _per_image(y)
-        if scales.numel() != y.numel():
+        if means is None and scales.numel() != y.numel():
             raise ValueError("rate_steps_groups: y and scales must hold the same number of elements")
         if lanes < 1 or per % lanes:
             raise ValueError(f"rate_steps_groups: {lanes} lanes do not divide the {per} symbols of a tile")
@@ -612,9 +717,9 @@ def rate_steps_groups(chunks, groups, budgets, tile_extra_words, candidates, pas
         if p:
             cand = rate_refine(cand, choice, t)
         row = 0
-        for (y, scales), B in zip(chunks, sizes):
+        for (y, scales), B, mu in zip(chunks, sizes, chunk_means):
             mine = cand if cand.dim() == 1 else cand.index_select(0, tile_group_dev[row:row + B])
-            rate_curve(y, scales, mine, table, tables, bound, lanes, out=bits[row * lanes:(row + B) * lanes])
+            rate_curve(y, scales, mine, table, tables, bound, lanes, out=bits[row * lanes:(row + B) * lanes], means=mu)
             row += B
         steps, choice, pred, tile_steps, tile_pred = rate_select_groups(bits, first_seg, per_seg, (gfirst, gtiles), cand, budgets,
                                                                         tile_extra_words, lanes)
@@ -1077,9 +1182,10 @@ def ms_ssim_per_image_u8(a, b, return_terms=False):
 
 
 class HyperpriorSession:
-    """basic_hp_session_*: the fused compress / decompress entry points of the plain hyperprior latent graph (one C call
-    per batch instead of a Python walk over the graph).  Borrows the layer plans and table sets it is given (kept alive
-    here); one session serves one call at a time."""
+    """basic_hp_session_*: the fused compress / decompress entry points of the two hyperprior latent graphs (one C call
+    per batch instead of a Python walk over the graph): an ``h_s`` that ends in the latent's channels is the scale hyperprior, one
+    that ends in twice as many (scales, then means) the mean-scale hyperprior.  Borrows the layer plans and table sets it is
+    given (kept alive here); one session serves one call at a time."""
 
     def __init__(self, g_a, h_a, h_s, g_s, eb_medians, z_tables, scale_table, scale_bound, y_tables):
         self._keep = (list(g_a), list(h_a), list(h_s), list(g_s), z_tables, y_tables)

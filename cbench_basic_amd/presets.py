@@ -2,15 +2,19 @@
 instantiate through ClassBuilder; here as plain functions).
 
   hyperprior_codec(N, M)  <- configs/lossy_graph_scalable_exp_hp.py:182-215
+  mean_scale_hyperprior_codec(N, M)  <- the same graph with nn/models/google.py's MeanScale hyper transforms and the mean-scale y
+                                        coder (compressai_coder.py:556-619); CompressAI's mbt2018-mean
 """
 import torch
 
 from .codecs.general_codec import GeneralCodec
 from .modules.entropy_coder.latent_graph import LatentGraphicalANSEntropyCoder, LossyDummyEntropyCoder
 from .modules.prior_model.prior_coder.compressai_coder import (CompressAIEntropyBottleneckPriorCoder,
-                                                               CompressAIGaussianConditionalCoder)
+                                                               CompressAIGaussianConditionalCoder,
+                                                               CompressAIMeanScaleGaussianConditionalCoder)
 from .nn.models.google import (HyperpriorAnalysisModel, HyperpriorHyperAnalysisModel,
-                               HyperpriorHyperSynthesisModel, HyperpriorSynthesisModel)
+                               HyperpriorHyperSynthesisModel, HyperpriorSynthesisModel,
+                               MeanScaleHyperpriorHyperAnalysisModel, MeanScaleHyperpriorHyperSynthesisModel)
 
 
 def hyperprior_codec(N=128, M=192, stream_lanes=1):
@@ -26,6 +30,24 @@ def hyperprior_codec(N=128, M=192, stream_lanes=1):
         ),
         latent_inference_dict=dict(x_y=HyperpriorAnalysisModel(N=N, M=M), y_z=HyperpriorHyperAnalysisModel(N=N, M=M)),
         latent_generative_dict=dict(z_y=HyperpriorHyperSynthesisModel(N=N, M=M), y_x=HyperpriorSynthesisModel(N=N, M=M)),
+    )
+    return GeneralCodec(entropy_coder=ec)
+
+
+def mean_scale_hyperprior_codec(N=128, M=192, stream_lanes=1):
+    """hyperprior_codec with the mean-scale hyper transforms (h_s ends in 2 M channels: scales [0, M), means [M, 2 M)) and the y coder
+    that codes ``round(y - mean)`` (INTEGRATION.md "Mean-scale hyperprior").  With N = M = 192 it is the graph of CompressAI's
+    ``mbt2018-mean`` at qualities 1-4.  ``stream_lanes``: as hyperprior_codec's."""
+    ec = LatentGraphicalANSEntropyCoder(
+        latent_node_inference_topo_order=["x", "y", "z"],
+        latent_node_generative_topo_order=["z", "y", "x"],
+        latent_node_entropy_coder_dict=dict(
+            x=LossyDummyEntropyCoder(lambda_rd=145.2225),
+            y=CompressAIMeanScaleGaussianConditionalCoder(stream_lanes=stream_lanes),
+            z=CompressAIEntropyBottleneckPriorCoder(entropy_bottleneck_channels=N, use_inner_aux_opt=True),
+        ),
+        latent_inference_dict=dict(x_y=HyperpriorAnalysisModel(N=N, M=M), y_z=MeanScaleHyperpriorHyperAnalysisModel(N=N, M=M)),
+        latent_generative_dict=dict(z_y=MeanScaleHyperpriorHyperSynthesisModel(N=N, M=M), y_x=HyperpriorSynthesisModel(N=N, M=M)),
     )
     return GeneralCodec(entropy_coder=ec)
 
@@ -238,4 +260,10 @@ def seed_synthetic_weights(codec, seed=0, y_std=0.5):
         last_gs = conv_of(g_s[len(g_s) - 1])
         last_gs.weight.mul_(0.05)
         last_gs.bias.fill_(0.5)
+        # mean-scale y coder: the second half of the last h_s conv predicts means, which the branch above gave the scales' positive
+        # bias.  Redrawn signed, uniform in [-1.5, 1.5) -- the LAST draw from the generator, so every other codec's weights keep their bits
+        y_coder = ec.latent_node_entropy_coders["y"] if "y" in ec.latent_node_entropy_coders else None
+        if isinstance(y_coder, CompressAIMeanScaleGaussianConditionalCoder):
+            half = last_hs.bias.numel() // 2
+            last_hs.bias[half:].copy_(torch.rand((half,), generator=g) * 3.0 - 1.5)
     return codec

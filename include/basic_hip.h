@@ -227,6 +227,35 @@ int basic_gc_dequantize_q_dev(const int32_t *d_sym, int64_t n, int64_t per_image
 int basic_gc_rate_curve_dev(const float *d_y, const float *d_scales, int n_seg, int64_t per_seg, int segs_per_image, const float *d_cand,
                             int n_cand, int cand_per_image, const float *d_table, int table_len, float scale_bound,
                             const basic_rans_tables *t, uint64_t *d_bits, void *hip_stream);
+/* Mean-scale (the y coder of the mean-scale hyperprior, upstream's MeanScaleHyperprior; INTEGRATION.md "Mean-scale hyperprior").
+ * The parameters of element i, image b = i / per_image, r = i % per_image, lie at d_scales[b * param_stride + r] and
+ * d_means[b * param_stride + r]: the halves of a chunked prior [B][2 M][h][w] are read in place with d_means = d_scales + per_image
+ * and param_stride = 2 * per_image; two separate contiguous arrays have param_stride = per_image.  Every line one fp32 operation:
+ *     s    = max(scale, bound)                    s' = s / step            (only with a step)
+ *     idx  = the index rule above on s (or s')
+ *     r    = y - mu
+ *     q    = round_half_even(r)                   or round_half_even(r / step)
+ *     sym  = (int32) q
+ *     yhat = q + mu                               or (q * step) + mu: two roundings, never an FMA
+ *     decoder (basic_gc_dequantize_ms_dev): yhat = (float) sym + mu   or ((float) sym * step) + mu
+ * The decoder's yhat has the encoder's bits wherever sym != 0 or mu != 0 (at sym == 0 and mu == +-0 both are a zero).  With every
+ * step 1 the outputs are the step-less ones bit for bit; with mu = +0.0 everywhere sym, idx and the value of yhat are those of
+ * basic_gc_quantize_index_q_dev / basic_gc_quantize_index_dev.  n_steps == 0 or d_steps == NULL: the step-less lines (a kernel
+ * without a division); else d_steps as above.  d_y == NULL with d_symbols == NULL and d_yhat == NULL: indexes only (the decoder;
+ * d_means is not read).  BASIC_ERR_INVALID, before any launch: n no whole number of images, n_steps not in {0, 1, n / per_image},
+ * param_stride < per_image, d_y without d_symbols or d_means, d_symbols or d_yhat without d_y. */
+int basic_gc_quantize_index_ms_dev(const float *d_y, const float *d_scales, const float *d_means, int64_t n, int64_t per_image,
+                                   int64_t param_stride, const float *d_steps, int n_steps, const float *d_table, int table_len,
+                                   float scale_bound, int32_t *d_symbols, int32_t *d_indexes, float *d_yhat, void *hip_stream);
+int basic_gc_dequantize_ms_dev(const int32_t *d_sym, const float *d_means, int64_t n, int64_t per_image, int64_t param_stride,
+                               const float *d_steps, int n_steps, float *d_yhat, void *hip_stream);
+/* basic_gc_rate_curve_dev for the mean-scale coder: (sym, idx) = what basic_gc_quantize_index_ms_dev writes at step cand[k].  The
+ * parameters of segment s, image b = s / segs_per_image, start at b * param_stride + (s % segs_per_image) * per_seg of d_scales
+ * and d_means; param_stride >= per_seg * segs_per_image, else BASIC_ERR_INVALID.  Everything else as above. */
+int basic_gc_rate_curve_ms_dev(const float *d_y, const float *d_scales, const float *d_means, int64_t param_stride, int n_seg,
+                               int64_t per_seg, int segs_per_image, const float *d_cand, int n_cand, int cand_per_image,
+                               const float *d_table, int table_len, float scale_bound, const basic_rans_tables *t, uint64_t *d_bits,
+                               void *hip_stream);
 /* The step of every image from its curve.  A stream of n symbols whose costs sum to bits (2^-16 bit) takes at most
  * 2 + ((bits + 4 n) >> 21) 32-bit words (INTEGRATION.md "Rate control": the byte bound), so
  *     pred_bytes(b, k) = 4 extra_words[b] + sum over the lanes of 4 (2 + ((bits[s][k] + 4 per_seg) >> 21))
@@ -446,7 +475,11 @@ int basic_msssim_per_image_dev(const float *d_x, const float *d_y, int batch, in
                                void *d_workspace, int64_t workspace_bytes, float *d_msssim, float *d_terms, void *hip_stream);
 
 /* ======================================================================================
- * 8. Fused image entry points of the plain hyperprior latent graph (SURVEY 8b "basic_encode_image / decode_image"):
+ * 8. Fused image entry points of the two hyperprior latent graphs (SURVEY 8b "basic_encode_image / decode_image"): the scale
+ *    hyperprior (h_s ends in y_channels planes, the scales; y coded as round(y)) and the mean-scale hyperprior (h_s ends in
+ *    2 * y_channels planes, scales [0, M) then means [M, 2 M); y coded as round(y - mean) with the basic_gc_*_ms_dev entry points of
+ *    section 4, both halves read where h_s left them).  basic_hp_session_create tells them apart by h_s's last plan; every setter,
+ *    the z path, lane streams and the wire format are the same for both.
  *    ONE call runs what GeneralCodec.compress / decompress run for that graph
  *      compress   general_codec.py:44-89 -> LatentGraphicalANSEntropyCoder.encode latent_graph.py:1232-1264
  *                 x -> g_a -> y -> h_a -> z ; EntropyBottleneck coder (compressai_coder.py:230-236) ; h_s ;

@@ -3,6 +3,7 @@
 tools/run_benchmark.py for the testing half of a benchmark config).
 
   python tools/run_benchmark.py --codec hyperprior --images /data/kodak --out runs/hp_kodak
+  python tools/run_benchmark.py --codec meanscale --synthetic 8 --qsteps 1 2 4 --out runs/ms_q
   python tools/run_benchmark.py --codec basic --synthetic 8 --size 256 --complexity-levels 0 1 2 3 4 5 6 7 --out runs/basic
   python tools/run_benchmark.py --codec topogroup --method checkerboard --synthetic 4 --out runs/ckbd
 
@@ -52,9 +53,15 @@ class ReconstructionWriter:
             Image.fromarray(a[..., 0] if a.shape[-1] == 1 else a).save(self.files[-1])
 
 
-def main(argv=None):
+STEP_CODECS = ("hyperprior", "meanscale")   # the codecs whose y coder takes a quantiser step (--qsteps, --target-bpp, --tile-*)
+
+
+def parse_args(argv=None):
+    """The command line, parsed and checked (argparse's error exit, status 2, for a refused combination).  Host code: nothing here
+    touches the GPU."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--codec", choices=["hyperprior", "topogroup", "basic"], default="hyperprior")
+    ap.add_argument("--codec", choices=["hyperprior", "meanscale", "topogroup", "basic"], default="hyperprior",
+                    help="hyperprior: the scale hyperprior; meanscale: the mean-scale hyperprior (presets.mean_scale_hyperprior_codec)")
     ap.add_argument("--method", default="checkerboard", help="topo-group pattern of --codec topogroup")
     ap.add_argument("--checkpoint", default=None, help="state_dict (.pt) of the entropy coder or of the whole codec")
     ap.add_argument("--images", default=None, help="folder of PNG/JPEG images")
@@ -111,20 +118,20 @@ def main(argv=None):
                     help="measure the 8-bit picture: decompress(output_dtype=torch.uint8) inside the timed region, the distortion from "
                          "exact integers against the 8-bit item (a float item: quantised once)")
     ap.add_argument("--qsteps", type=float, nargs="+", default=[], metavar="Q",
-                    help="testing_qsteps, --codec hyperprior: one pass per quantiser step of the y coder through compress_q / decompress_q "
+                    help="testing_qsteps, --codec hyperprior or meanscale: one pass per quantiser step of the y coder through compress_q / decompress_q "
                          "(level prefix q<step>; 1 is the codec as trained, above 1 fewer bits); every step in [0.0625, 64].  Composes with "
                          "--uint8, --metrics-on-uint8, --workers and --stream-lanes; not with --coalesce, --tile* or --complexity-levels")
     ap.add_argument("--target-bpp", type=float, nargs="+", default=[], metavar="R",
-                    help="testing_target_bpps, --codec hyperprior: one pass per rate target through compress_to_rate / decompress_q (level "
+                    help="testing_target_bpps, --codec hyperprior or meanscale: one pass per rate target through compress_to_rate / decompress_q (level "
                          "prefix bpp<target>): every item's step is chosen on the GPU so that its payload fits floor(R * H * W / 8) bytes.  "
                          "Composes and refuses as --qsteps does, and does not combine with it")
     ap.add_argument("--tile-qsteps", type=float, nargs="+", default=[], metavar="Q",
-                    help="testing_tile_qsteps, --codec hyperprior with --tile: one pass per quantiser step through compress_tiled_q / "
+                    help="testing_tile_qsteps, --codec hyperprior or meanscale with --tile: one pass per quantiser step through compress_tiled_q / "
                          "decompress_tiled (level prefix tq<step>; the BTQ1 container carries the step); every step in [0.0625, 64].  "
                          "Composes with --tile-overlap, --tile-pad, --tile-pool, --uint8 and --metrics-on-uint8; not with --qsteps, "
                          "--target-bpp, --coalesce, --complexity-levels, --rate-levels or --forward-pass")
     ap.add_argument("--tile-target-bpp", type=float, nargs="+", default=[], metavar="R",
-                    help="testing_tile_target_bpps, --codec hyperprior with --tile: one pass per rate target through compress_tiled_to_rate "
+                    help="testing_tile_target_bpps, --codec hyperprior or meanscale with --tile: one pass per rate target through compress_tiled_to_rate "
                          "(level prefix tbpp<target>): ONE step per picture is chosen on the GPU so that the whole container, framing "
                          "included, fits floor(R * H * W / 8) bytes.  Composes and refuses as --tile-qsteps does, and does not combine with it")
     ap.add_argument("--out", required=True)
@@ -134,8 +141,8 @@ def main(argv=None):
         if not values:
             continue
         import math
-        if args.codec != "hyperprior":
-            ap.error(f"{flag} is a knob of the hyperprior y coder's quantiser step: it needs --codec hyperprior")
+        if args.codec not in STEP_CODECS:
+            ap.error(f"{flag} is a knob of the hyperprior y coder's quantiser step: it needs --codec hyperprior or --codec meanscale")
         if args.tile is None:
             ap.error(f"{flag} needs --tile: the untiled knobs are --qsteps and --target-bpp")
         for name, on in (other, ("--qsteps", bool(args.qsteps)), ("--target-bpp", bool(args.target_bpp)), ("--coalesce", args.coalesce > 1),
@@ -156,8 +163,8 @@ def main(argv=None):
                     ap.error(f"--tile-target-bpp: every target must be positive and finite, got {r}")
     if args.target_bpp:
         import math
-        if args.codec != "hyperprior":
-            ap.error("--target-bpp chooses the hyperprior y coder's quantiser step: it needs --codec hyperprior")
+        if args.codec not in STEP_CODECS:
+            ap.error("--target-bpp chooses the hyperprior y coder's quantiser step: it needs --codec hyperprior or --codec meanscale")
         for name, on in (("--qsteps", bool(args.qsteps)), ("--coalesce", args.coalesce > 1), ("--tile", args.tile is not None),
                          ("--tile-overlap", args.tile_overlap is not None), ("--tile-pad", args.tile_pad is not None),
                          ("--tile-pool", args.tile_pool > 0), ("--complexity-levels", bool(args.complexity_levels)),
@@ -169,8 +176,9 @@ def main(argv=None):
                 ap.error(f"--target-bpp: every target must be positive and finite, got {r}")
     if args.qsteps:
         from cbench_basic_amd.utils.qstep import check_qsteps
-        if args.codec != "hyperprior":
-            ap.error("--qsteps is the hyperprior y coder's quantiser step: it needs --codec hyperprior (the PGM coders' knob is quantizer_params)")
+        if args.codec not in STEP_CODECS:
+            ap.error("--qsteps is the hyperprior y coder's quantiser step: it needs --codec hyperprior or --codec meanscale (the PGM coders' "
+                     "knob is quantizer_params)")
         for name, on in (("--coalesce", args.coalesce > 1), ("--tile", args.tile is not None), ("--tile-overlap", args.tile_overlap is not None),
                          ("--tile-pad", args.tile_pad is not None), ("--tile-pool", args.tile_pool > 0),
                          ("--complexity-levels", bool(args.complexity_levels)), ("--rate-levels", bool(args.rate_levels)),
@@ -216,7 +224,6 @@ def main(argv=None):
         args.tile_pad = (args.tile_pad[0], args.tile_pad[-1])
         if args.tile[0] % args.tile_pad[0] or args.tile[1] % args.tile_pad[1]:
             ap.error("--tile-pad must divide the tile")
-    pad = {} if args.tile_pad is None else dict(pad_to=args.tile_pad)
     if args.tile_pool < 0:
         ap.error("--tile-pool must be >= 0")
     if args.tile_pool:
@@ -224,6 +231,12 @@ def main(argv=None):
             ap.error("--tile-pool needs --tile")
         if args.workers > 1:
             ap.error("--tile-pool runs on the calling thread: it does not combine with --workers above 1")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    pad = {} if args.tile_pad is None else dict(pad_to=args.tile_pad)
     if args.workers > 1:   # before HIP initialises: one hardware queue per worker stream
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         os.environ.setdefault("BASIC_RANS_WPB", "8")
@@ -239,7 +252,8 @@ def main(argv=None):
     else:
         ds = RandomImageDataset(num=args.synthetic or 8, size=(3, args.height or args.size, args.width or args.size), dtype=dtype)
     batches = list(batched(ds, args.batch_size))
-    builders = dict(hyperprior=lambda: presets.hyperprior_codec(stream_lanes=args.stream_lanes), basic=lambda **kw: presets.basic_codec(stream_lanes=args.stream_lanes, stream_rows=args.stream_rows,
+    builders = dict(hyperprior=lambda: presets.hyperprior_codec(stream_lanes=args.stream_lanes),
+                    meanscale=lambda: presets.mean_scale_hyperprior_codec(stream_lanes=args.stream_lanes), basic=lambda **kw: presets.basic_codec(stream_lanes=args.stream_lanes, stream_rows=args.stream_rows,
                                                               scanline_decode_schedule=args.scanline_decode_schedule, **kw),
                     topogroup=lambda: presets.topogroup_ar_codec(method=args.method, stream_lanes=args.stream_lanes))
     codec = builders["basic"](search_dataset=batches) if (args.codec == "basic" and args.complexity_search) else builders[args.codec]()
