@@ -62,6 +62,8 @@ _SIGNATURES = {
     "basic_rans_set_waves": (_I, [_I, _P]),
     "basic_lanes_pack_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "basic_group_lanes_pack_dev": (_I, [_P, _P, _I, _L, _P, _I, _I, _P, _P, _P]),
+    "basic_skip_compact_dev": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _P, _P]),
+    "basic_skip_expand_dev": (_I, [_P, _P, _I, _L, _I, _P, _P, _P]),
     "basic_gc_quantize_index_dev": (_I, [_P, _P, _L, _P, _I, _F, _P, _P, _P, _P]),
     "basic_gc_quantize_index_q_dev": (_I, [_P, _P, _L, _L, _P, _I, _P, _I, _F, _P, _P, _P, _P]),
     "basic_gc_dequantize_q_dev": (_I, [_P, _L, _L, _P, _I, _P, _P]),
@@ -112,6 +114,7 @@ _SIGNATURES = {
     "basic_hp_session_set_rans_waves": (_I, [_P, _I]),
     "basic_hp_session_set_stream_lanes": (_I, [_P, _I]),
     "basic_hp_session_set_qsteps": (_I, [_P, _P, _I]),
+    "basic_hp_session_set_skip_rows": (_I, [_P, _I]),
     "basic_hp_session_set_transform_token": (_I, [_P, _I]),
     "basic_hp_session_destroy": (None, [_P]),
     "basic_conv_plan_destroy": (None, [_P]),

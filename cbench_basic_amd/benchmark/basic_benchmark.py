@@ -44,6 +44,10 @@ one pass per step through ``compress_tiled_q``, or per target through ``compress
 ``decompress_tiled`` reads the steps from it.  They compose with the overlap, the padding, the pool and ``metrics_on_uint8``, and are
 refused with each other, with ``testing_qsteps`` / ``testing_target_bpps`` (which stay refused with ``testing_tile``) and with what
 refuses those.
+
+``testing_skip_rows=[r, ...]`` ("Skip coding"): one pass per value through ``compress_skip`` / ``decompress_skip``
+under the level prefix ``skip<r>``; ``compressed_length`` is the BSK1 container's length.  Refused with what refuses
+``testing_qsteps``, and with the steps, the targets and the tiled knobs themselves.
 """
 import copy
 import csv
@@ -66,7 +70,7 @@ class BasicLosslessCompressionBenchmark:
                  num_testing_workers=0, codec_builder=None, worker_transform_token=None, testing_coalesce_items=0,
                  metrics_on_uint8=False, on_reconstruction=None, testing_tile=None, testing_tile_overlap=0, testing_tile_pool=0,
                  testing_tile_pad=None, testing_qsteps=None, testing_target_bpps=None, testing_tile_qsteps=None,
-                 testing_tile_target_bpps=None, **kwargs):
+                 testing_tile_target_bpps=None, testing_skip_rows=None, **kwargs):
         self.codec = codec
         self.dataloader = dataloader
         self.distortion_metric = distortion_metric
@@ -194,6 +198,21 @@ class BasicLosslessCompressionBenchmark:
                              ("nn_codec_use_forward_pass", bool(nn_codec_use_forward_pass))):
                 if on:
                     raise ValueError(f"{mine} does not combine with {name}: it is a knob of the tiled calls alone")
+        # skip coding ("Skip coding"): one pass per row count through compress_skip / decompress_skip, level prefix
+        # skip<r>; refused with what refuses the steps, and with every other rate knob
+        from ..utils.skip import check_skip_rows
+        self.testing_skip_rows = [check_skip_rows(r) for r in (testing_skip_rows or [])]
+        if self.testing_skip_rows:
+            for name, on in (("testing_qsteps", bool(self.testing_qsteps)), ("testing_target_bpps", bool(self.testing_target_bpps)),
+                             ("testing_tile_qsteps", bool(self.testing_tile_qsteps)),
+                             ("testing_tile_target_bpps", bool(self.testing_tile_target_bpps)),
+                             ("testing_variable_rate_levels", bool(self.testing_variable_rate_levels)),
+                             ("testing_complexity_levels", bool(self.testing_complexity_levels)),
+                             ("testing_coalesce_items", self.testing_coalesce_items > 1), ("testing_tile", testing_tile is not None),
+                             ("nn_codec_use_forward_pass", bool(nn_codec_use_forward_pass))):
+                if on:
+                    raise ValueError(f"testing_skip_rows does not combine with {name}: the rows are a knob of compress_skip / decompress_skip alone")
+        self._skip_rows = None
         self._qstep = None
         self._target_bpp = None
         self._tile_qstep = None
@@ -267,6 +286,8 @@ class BasicLosslessCompressionBenchmark:
         return self._to_f32(data_target) if self.metrics_on_uint8 else data_target
 
     def _compress(self, codec, data):
+        if self._skip_rows is not None:
+            return codec.compress_skip(data, self._skip_rows)
         if self._target_bpp is not None:
             return codec.compress_to_rate(data, target_bpp=self._target_bpp)
         if self._qstep is not None:
@@ -284,6 +305,8 @@ class BasicLosslessCompressionBenchmark:
         return codec.compress_tiled(data, tile=self.testing_tile, overlap=self.testing_tile_overlap, **self._tile_pad)
 
     def _decompress(self, codec, compressed):
+        if self._skip_rows is not None:
+            return codec.decompress_skip(compressed, output_dtype=torch.uint8 if self.metrics_on_uint8 else None)
         if self._qstep is not None or self._target_bpp is not None:
             return codec.decompress_q(compressed, output_dtype=torch.uint8 if self.metrics_on_uint8 else None)
         if self.testing_tile is not None:
@@ -613,6 +636,8 @@ class BasicLosslessCompressionBenchmark:
         vr, vc = self.testing_variable_rate_levels, self.testing_complexity_levels
         # the rate axis: (rate level, quantiser step) pairs -- the codec's own levels, or the steps (never both: __init__)
         axis = [(r, None, None) for r in vr] or [(None, q, None) for q in self.testing_qsteps] or [(None, None, r) for r in self.testing_target_bpps]
+        skip_axis = list(self.testing_skip_rows)   # the skip rows take the axis alone (__init__): one (None, None, None) entry each
+        axis = axis or [(None, None, None)] * len(skip_axis)
         # the tiled knobs take the same place: (None, step, target) with the tiled calls behind them
         tiled_axis = [(None, q, None) for q in self.testing_tile_qsteps] or [(None, None, r) for r in self.testing_tile_target_bpps]
         axis = axis or tiled_axis
@@ -624,7 +649,9 @@ class BasicLosslessCompressionBenchmark:
             for ci, clevel in enumerate(vc if vc else [None]):
                 rate_pts, distortion_pts = [], []
                 for ri, (rlevel, qstep, bpp) in enumerate(axis if axis else [(None, None, None)]):
-                    if tiled_axis:
+                    if skip_axis:
+                        self._skip_rows = skip_axis[ri]
+                    elif tiled_axis:
                         self._tile_qstep, self._tile_bpp = qstep, bpp
                     else:
                         self._qstep, self._target_bpp = qstep, bpp
@@ -641,6 +668,8 @@ class BasicLosslessCompressionBenchmark:
                         [f"bpp{bpp:g}"] if bpp is not None else []
                     if tiled_axis:
                         rate_prefix = ["t" + rate_prefix[0]]
+                    if skip_axis:
+                        rate_prefix = [f"skip{skip_axis[ri]}"]
                     self._level_prefix = "_".join(([f"sclevel{clevel}"] if clevel is not None else []) + rate_prefix)
                     current = self._run_dataset()
                     if self.distortion_metric is not None:
@@ -675,7 +704,7 @@ class BasicLosslessCompressionBenchmark:
                     value = bj((rate_pts, distortion_pts))[bj.name]
                     metrics[bj_prefix + bj.name] = value
                     metrics_2d[prefix][bj.name] = value
-        self._qstep = self._target_bpp = self._tile_qstep = self._tile_bpp = None
+        self._qstep = self._target_bpp = self._tile_qstep = self._tile_bpp = self._skip_rows = None
         if metrics_2d and self.output_dir:
             self.save_metrics(metric_file=os.path.join(self.output_dir, "metrics_2d.csv"),
                               metric_data=list(metrics_2d.values()), names=list(metrics_2d.keys()), raw=False)

@@ -46,6 +46,30 @@ class GeneralCodec(HotPathModule, CodecInterface, VariableRateCodecInterface, Va
         steps, inner = unpack_qsteps(data)
         return self.decompress(inner, *args, output_dtype=output_dtype, qstep=steps, **kwargs)
 
+    def compress_skip(self, data, skip_rows, qstep=None, *args, **kwargs):
+        """``compress`` with skip coding of the y latent (INTEGRATION.md "Skip coding"; the hyperprior codecs, not part of the
+        reference's codec interface): an element whose table row is below ``skip_rows`` -- an integer in [0, rows of the scale table];
+        utils.skip.skip_rows_for_sigma states it as a scale -- is not coded, and decodes as 0 (the mean, for the mean-scale codec).
+        ``qstep``: None, or the quantiser step(s) of compress_q; the rows are then those of sigma / step.  -> the container of
+        utils/skip.py: b"BSK1", uint32 LE skip_rows, uint32 LE n (0 without a step), n float32 LE steps, then exactly what
+        ``entropy_coder.encode(data, skip_rows=, qstep=)`` returned -- at skip_rows 0 that is ``compress(data)``, or the inner stream
+        of ``compress_q(data, qstep)``, byte for byte.  No rate target, tiles or autoregressive codec with it (ValueError / TypeError)."""
+        from ..utils.qstep import check_qsteps
+        from ..utils.skip import check_skip_rows, pack_skip
+        r = check_skip_rows(skip_rows)
+        steps = None if qstep is None else check_qsteps(qstep, data.shape[0])
+        extra = {} if steps is None else dict(qstep=steps)
+        return pack_skip(r, steps, self.compress(data, *args, skip_rows=r, **extra, **kwargs))
+
+    def decompress_skip(self, data, *args, output_dtype=None, **kwargs):
+        """A container of compress_skip -> the reconstruction, as ``decompress`` gives it (``output_dtype`` as there).  The skip rows
+        and the steps are read from the container; a wrong magic, a short buffer, rows past the table or invalid steps are a ValueError
+        raised before anything is launched."""
+        from ..utils.skip import unpack_skip
+        r, steps, inner = unpack_skip(data)
+        extra = {} if steps is None else dict(qstep=steps)
+        return self.decompress(inner, *args, output_dtype=output_dtype, skip_rows=r, **extra, **kwargs)
+
     def compress_to_rate(self, data, target_bytes=None, target_bpp=None, candidates=16, passes=2, step_range=(2 ** -4, 2 ** 6),
                          return_report=False, **kwargs):
         """``compress_q`` with the step of every image chosen on the GPU so that the image's payload -- its z stream plus its y

@@ -1155,3 +1155,212 @@ extern "C" int basic_eb_nll_per_image_dev(const float *d_zq, const float *d_coef
     BASIC_HIP_TRY(hipGetLastError());
     return BASIC_OK;
 }
+
+// ---- skip coding (include/basic_hip.h, "Skip coding"): order-preserving compaction of the elements whose table row is at least
+// skip_rows, per stream, and its inverse.  A workgroup owns one chunk of BASIC_SKIP_CHUNK elements of one stream, a lane four
+// consecutive ones (one 16-byte load where they are aligned and inside the stream; the same lines serve a tail and an unaligned
+// stream element by element).  Three launches: the chunks' counts, ONE workgroup's exclusive scan of them in int64 (a chunk's
+// base is global: the streams lie back to back in the output, so it already holds the stream's segment start), and the scatter.
+// Inside a chunk a kept element's rank is: the kept elements of lower lanes of its wave (four ballots, popcounts under the lane's
+// mask) + its own lane's earlier ones + the totals of the lower waves (LDS).  Nothing waits on another workgroup and no atomic
+// decides a position.
+namespace {
+
+constexpr int kSkipBlock = 256, kSkipLane = 4, kSkipWaves = kSkipBlock / kWave, kSkipScanBlock = 1024;
+static_assert(kSkipBlock * kSkipLane == BASIC_SKIP_CHUNK, "a workgroup pass is one chunk");
+
+// the lane's four elements of a stream of `per` elements from `off` on; past the stream's end: 0 (never kept, see skip_keep)
+__device__ __forceinline__ void skip_load4(const int32_t *__restrict__ p, int64_t off, int64_t per, int32_t v[kSkipLane])
+{
+    if (off + kSkipLane <= per && (reinterpret_cast<uintptr_t>(p + off) & 15u) == 0) {
+        const int4 q = *reinterpret_cast<const int4 *>(p + off);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kSkipLane; ++j) v[j] = off + j < per ? p[off + j] : 0;
+    }
+}
+
+__device__ __forceinline__ void skip_keep(const int32_t v[kSkipLane], int64_t off, int64_t per, int skip_rows, bool keep[kSkipLane])
+{
+#pragma unroll
+    for (int j = 0; j < kSkipLane; ++j) keep[j] = off + j < per && v[j] >= skip_rows;
+}
+
+// -> the number of kept elements before the lane's first one inside its chunk; *chunk_total (optional) = the chunk's count.
+// s_w: kSkipWaves ints of LDS.  Every thread of the workgroup calls it.
+__device__ __forceinline__ int skip_rank(const bool keep[kSkipLane], int *s_w, int *chunk_total)
+{
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int before = 0, total = 0;
+#pragma unroll
+    for (int j = 0; j < kSkipLane; ++j) {
+        const unsigned long long m = __ballot(keep[j]);
+        before += __popcll(m & below);
+        total += __popcll(m);
+    }
+    if (lane == 0) s_w[wave] = total;
+    __syncthreads();
+    int sum = 0;
+#pragma unroll
+    for (int w = 0; w < kSkipWaves; ++w) {
+        if (w < wave) before += s_w[w];
+        sum += s_w[w];
+    }
+    if (chunk_total) *chunk_total = sum;
+    return before;
+}
+
+__global__ __launch_bounds__(kSkipBlock) void skip_count_kernel(const int32_t *__restrict__ idx, int64_t per, int cps, int skip_rows,
+                                                                int64_t *__restrict__ counts)
+{
+    __shared__ int s_w[kSkipWaves];
+    const int64_t s = blockIdx.x / cps;
+    const int64_t off = static_cast<int64_t>(blockIdx.x - s * cps) * BASIC_SKIP_CHUNK + threadIdx.x * kSkipLane;
+    int32_t v[kSkipLane];
+    bool keep[kSkipLane];
+    skip_load4(idx + s * per, off, per, v);
+    skip_keep(v, off, per, skip_rows, keep);
+    int total;
+    skip_rank(keep, s_w, &total);
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// counts[0 .. n) -> their exclusive prefix sums, in place; seg (optional) [nstreams + 1]: the base of every stream's first chunk and
+// the grand total.  One workgroup, kSkipScanBlock entries a round with the carry in a register of every thread.
+__global__ __launch_bounds__(kSkipScanBlock) void skip_scan_kernel(int64_t *__restrict__ counts, int64_t n, int cps, int64_t *__restrict__ seg,
+                                                                   int nstreams)
+{
+    __shared__ long long s_w[kSkipScanBlock / kWave];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    long long carry = 0;
+    for (int64_t base = 0; base < n; base += kSkipScanBlock) {
+        const int64_t i = base + threadIdx.x;
+        const long long v = i < n ? counts[i] : 0;
+        long long inc = v;
+        for (int d = 1; d < kWave; d <<= 1) {
+            const long long up = __shfl_up(inc, d, kWave);
+            if (lane >= d) inc += up;
+        }
+        if (lane == kWave - 1) s_w[wave] = inc;
+        __syncthreads();
+        long long wbase = 0, round = 0;
+        for (int w = 0; w < kSkipScanBlock / kWave; ++w) {
+            if (w < wave) wbase += s_w[w];
+            round += s_w[w];
+        }
+        const long long excl = carry + wbase + inc - v;
+        if (i < n) {
+            counts[i] = excl;
+            if (seg && i % cps == 0) seg[i / cps] = excl;
+        }
+        carry += round;
+        __syncthreads();   // s_w is rewritten by the next round
+    }
+    if (seg && threadIdx.x == 0) seg[nstreams] = carry;
+}
+
+template <bool kSym>
+__global__ __launch_bounds__(kSkipBlock) void skip_scatter_kernel(const int32_t *__restrict__ sym, const int32_t *__restrict__ idx, int64_t per,
+                                                                  int cps, int skip_rows, const int64_t *__restrict__ bases,
+                                                                  int32_t *__restrict__ sym_out, int32_t *__restrict__ idx_out)
+{
+    __shared__ int s_w[kSkipWaves];
+    const int64_t s = blockIdx.x / cps;
+    const int64_t off = static_cast<int64_t>(blockIdx.x - s * cps) * BASIC_SKIP_CHUNK + threadIdx.x * kSkipLane;
+    int32_t v[kSkipLane], u[kSkipLane];
+    bool keep[kSkipLane];
+    skip_load4(idx + s * per, off, per, v);
+    if constexpr (kSym) skip_load4(sym + s * per, off, per, u);
+    skip_keep(v, off, per, skip_rows, keep);
+    int64_t o = bases[blockIdx.x] + skip_rank(keep, s_w, nullptr);   // < the total kept <= nstreams * per
+#pragma unroll
+    for (int j = 0; j < kSkipLane; ++j) {
+        if (keep[j]) {
+            idx_out[o] = v[j];
+            if constexpr (kSym) sym_out[o] = u[j];
+            ++o;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kSkipBlock) void skip_expand_kernel(const int32_t *__restrict__ compact, const int32_t *__restrict__ idx, int64_t per,
+                                                                 int cps, int skip_rows, const int64_t *__restrict__ bases,
+                                                                 int32_t *__restrict__ dense)
+{
+    __shared__ int s_w[kSkipWaves];
+    const int64_t s = blockIdx.x / cps;
+    const int64_t off = static_cast<int64_t>(blockIdx.x - s * cps) * BASIC_SKIP_CHUNK + threadIdx.x * kSkipLane;
+    int32_t v[kSkipLane], u[kSkipLane];
+    bool keep[kSkipLane];
+    skip_load4(idx + s * per, off, per, v);
+    skip_keep(v, off, per, skip_rows, keep);
+    int64_t o = bases[blockIdx.x] + skip_rank(keep, s_w, nullptr);
+#pragma unroll
+    for (int j = 0; j < kSkipLane; ++j) u[j] = keep[j] ? compact[o++] : 0;   // keep[j] holds only inside the stream
+    int32_t *q = dense + s * per;
+    if (off + kSkipLane <= per && (reinterpret_cast<uintptr_t>(q + off) & 15u) == 0) {
+        *reinterpret_cast<int4 *>(q + off) = make_int4(u[0], u[1], u[2], u[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < kSkipLane; ++j)
+            if (off + j < per) q[off + j] = u[j];
+    }
+}
+
+// the arguments both entry points share; *cps = chunks per stream, *nchunks = the grid
+int skip_plan(const void *d_idx, int nstreams, int64_t per, int skip_rows, const void *d_scratch, int *cps, int *nchunks)
+{
+    BASIC_REQUIRE(d_idx && d_scratch && nstreams >= 1 && per >= 1 && skip_rows >= 0, "skip: bad argument");
+    BASIC_REQUIRE(reinterpret_cast<uintptr_t>(d_scratch) % sizeof(int64_t) == 0, "skip: d_scratch must be 8-byte aligned");
+    const int64_t c = (per + BASIC_SKIP_CHUNK - 1) / BASIC_SKIP_CHUNK;
+    BASIC_REQUIRE(c <= (1ll << 30) && c * nstreams <= (1ll << 30), "skip: more than 2^30 chunks");
+    *cps = static_cast<int>(c);
+    *nchunks = static_cast<int>(c * nstreams);
+    return BASIC_OK;
+}
+
+}  // namespace
+
+extern "C" int basic_skip_compact_dev(const int32_t *d_sym, const int32_t *d_idx, int nstreams, int64_t per, int skip_rows, void *d_scratch,
+                                      int32_t *d_sym_out, int32_t *d_idx_out, int64_t *d_seg, void *hip_stream)
+{
+    BASIC_REQUIRE(d_idx_out && d_seg && (d_sym != nullptr) == (d_sym_out != nullptr),
+                  "skip_compact: d_idx_out and d_seg are required, d_sym and d_sym_out come together or not at all");
+    BASIC_REQUIRE(d_idx_out != d_idx && (!d_sym || d_sym_out != d_sym), "skip_compact: out of place");
+    int cps = 0, nchunks = 0;
+    const int rc = skip_plan(d_idx, nstreams, per, skip_rows, d_scratch, &cps, &nchunks);
+    if (rc) return rc;
+    const hipStream_t st = as_stream(hip_stream);
+    int64_t *bases = static_cast<int64_t *>(d_scratch);
+    hipLaunchKernelGGL(skip_count_kernel, dim3(nchunks), dim3(kSkipBlock), 0, st, d_idx, per, cps, skip_rows, bases);
+    hipLaunchKernelGGL(skip_scan_kernel, dim3(1), dim3(kSkipScanBlock), 0, st, bases, static_cast<int64_t>(nchunks), cps, d_seg, nstreams);
+    if (d_sym)
+        hipLaunchKernelGGL(skip_scatter_kernel<true>, dim3(nchunks), dim3(kSkipBlock), 0, st, d_sym, d_idx, per, cps, skip_rows, bases,
+                           d_sym_out, d_idx_out);
+    else
+        hipLaunchKernelGGL(skip_scatter_kernel<false>, dim3(nchunks), dim3(kSkipBlock), 0, st, d_sym, d_idx, per, cps, skip_rows, bases,
+                           d_sym_out, d_idx_out);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}
+
+extern "C" int basic_skip_expand_dev(const int32_t *d_sym_compact, const int32_t *d_idx_dense, int nstreams, int64_t per, int skip_rows,
+                                     void *d_scratch, int32_t *d_sym_dense_out, void *hip_stream)
+{
+    BASIC_REQUIRE(d_sym_compact && d_sym_dense_out && d_sym_dense_out != d_sym_compact && d_sym_dense_out != d_idx_dense,
+                  "skip_expand: bad argument (out of place)");
+    int cps = 0, nchunks = 0;
+    const int rc = skip_plan(d_idx_dense, nstreams, per, skip_rows, d_scratch, &cps, &nchunks);
+    if (rc) return rc;
+    const hipStream_t st = as_stream(hip_stream);
+    int64_t *bases = static_cast<int64_t *>(d_scratch);
+    hipLaunchKernelGGL(skip_count_kernel, dim3(nchunks), dim3(kSkipBlock), 0, st, d_idx_dense, per, cps, skip_rows, bases);
+    hipLaunchKernelGGL(skip_scan_kernel, dim3(1), dim3(kSkipScanBlock), 0, st, bases, static_cast<int64_t>(nchunks), cps,
+                       static_cast<int64_t *>(nullptr), nstreams);
+    hipLaunchKernelGGL(skip_expand_kernel, dim3(nchunks), dim3(kSkipBlock), 0, st, d_sym_compact, d_idx_dense, per, cps, skip_rows, bases,
+                       d_sym_dense_out);
+    BASIC_HIP_TRY(hipGetLastError());
+    return BASIC_OK;
+}

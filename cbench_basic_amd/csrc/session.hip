@@ -134,6 +134,10 @@ struct basic_hp_session {
     HBuf h_rate, h_rate_out;
     DBuf d_rate_in, d_rate_bits, d_rate_cand[2], d_rate_out;
     hipEvent_t rate_up = nullptr;
+    // skip coding of the y latent (basic_hp_session_set_skip_rows): 0 = none, no extra launch.  Else the y streams are the compacted
+    // ones: y_symc / y_idxc hold them back to back, seg_y their bounds as the compaction wrote them.
+    int skip_rows = 0;
+    DBuf skip_scratch, y_symc, y_idxc;
     DBuf d_medians, d_table;
     DBuf act[2], d_x, d_y, d_z, d_zhat, d_prior, d_scales;
     DBuf z_sym, z_idx, y_sym, y_idx, seg_z, seg_y, slots_z, slots_y, nw, off, packed, words, woff, state, pos;
@@ -436,6 +440,7 @@ extern "C" int basic_hp_session_set_rate_targets(basic_hp_session *s, const int6
         return BASIC_OK;
     }
     BASIC_REQUIRE(host_budget_bytes && host_cand, "hp_session_set_rate_targets: bad argument");
+    BASIC_REQUIRE(s->skip_rows == 0, "hp_session_set_rate_targets: skip rows are set -- the rate curve would count symbols that are not coded");
     BASIC_REQUIRE(s->qsteps.empty(), "hp_session_set_rate_targets: quantiser steps are set -- clear them first (one way to state the step at a time)");
     BASIC_REQUIRE(n_cand >= 2 && n_cand <= 32 && passes >= 1 && passes <= 3, "hp_session_set_rate_targets: 2 to 32 candidates, 1 to 3 passes");
     for (int i = 0; i < n; ++i) BASIC_REQUIRE(host_budget_bytes[i] >= 1, "hp_session_set_rate_targets: every budget must be at least one byte");
@@ -446,6 +451,16 @@ extern "C" int basic_hp_session_set_rate_targets(basic_hp_session *s, const int6
     s->rate_cand.assign(host_cand, host_cand + n_cand);
     s->rate_passes = passes;
     s->res_batch = 0;   // a held batch was coded under the previous targets
+    return BASIC_OK;
+}
+
+extern "C" int basic_hp_session_set_skip_rows(basic_hp_session *s, int rows)
+{
+    BASIC_REQUIRE(s && rows >= 0 && rows <= s->n_scales, "hp_session_set_skip_rows: an integer in [0, rows of the scale table]");
+    BASIC_REQUIRE(rows == 0 || s->rate_budget.empty(),
+                  "hp_session_set_skip_rows: rate targets are set -- the rate curve would count symbols that are not coded");
+    s->skip_rows = rows;
+    s->res_batch = 0;   // a held batch was coded under the previous rule
     return BASIC_OK;
 }
 
@@ -575,6 +590,35 @@ int encode_latent(basic_hp_session *s, const basic_rans_tables *t, const int32_t
     return basic_rans_encode_batch_dev(t, d_sym, d_idx, seg->as<int64_t>(), streams, slots->as<uint32_t>(), slot, d_nw, st);
 }
 
+// encode_latent for streams of unequal lengths: d_seg (device, streams + 1 entries) bounds them inside d_sym / d_idx, none longer than
+// the slot allows for
+int encode_latent_seg(const basic_rans_tables *t, const int32_t *d_sym, const int32_t *d_idx, int streams, const int64_t *d_seg, DBuf *slots,
+                      int32_t *d_nw, int64_t slot, hipStream_t st)
+{
+    const int rc = slots->ensure(sizeof(uint32_t) * static_cast<size_t>(streams) * slot);
+    if (rc) return rc;
+    return basic_rans_encode_batch_dev(t, d_sym, d_idx, d_seg, streams, slots->as<uint32_t>(), slot, d_nw, st);
+}
+
+// the y encoder of a call: equal runs of nyl symbols, or with skip rows their compactions (kept <= nyl: both slot bounds hold)
+int encode_y(basic_hp_session *s, int sy, int64_t nyl, int32_t *d_nw_y, int64_t slot_y, hipStream_t st)
+{
+    if (s->skip_rows == 0)
+        return encode_latent(s, s->y_tables, s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), sy, nyl, &s->seg_y, &s->slots_y, d_nw_y, slot_y, st);
+    return encode_latent_seg(s->y_tables, s->y_symc.as<int32_t>(), s->y_idxc.as<int32_t>(), sy, s->seg_y.as<int64_t>(), &s->slots_y, d_nw_y,
+                             slot_y, st);
+}
+
+// the buffers of the compaction of sy streams of nyl elements
+int ensure_skip(basic_hp_session *s, int sy, int64_t nyl)
+{
+    int rc = s->skip_scratch.ensure(BASIC_SKIP_SCRATCH_BYTES(sy, nyl));
+    if (!rc) rc = s->y_symc.ensure(sizeof(int32_t) * static_cast<size_t>(sy) * nyl);
+    if (!rc) rc = s->y_idxc.ensure(sizeof(int32_t) * static_cast<size_t>(sy) * nyl);
+    if (!rc) rc = s->seg_y.ensure(sizeof(int64_t) * (sy + 1));
+    return rc;
+}
+
 // the copy stream and the events that order a session's input buffers between calls
 int ensure_copy_stream(basic_hp_session *s)
 {
@@ -682,8 +726,14 @@ int encode_body(basic_hp_session *s, const float *d_x, bool x_in_session, int ba
                                                s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
     }
     if (rc) return rc;
-    rc = encode_latent(s, s->y_tables, s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), sy, nyl, &s->seg_y, &s->slots_y, d_nw_y,
-                       slot_y, st);
+    if (s->skip_rows) {   // the streams shrink to the elements whose row is at least skip_rows, each run on its own
+        rc = ensure_skip(s, sy, nyl);
+        if (!rc)
+            rc = basic_skip_compact_dev(s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), sy, nyl, s->skip_rows, s->skip_scratch.p,
+                                        s->y_symc.as<int32_t>(), s->y_idxc.as<int32_t>(), s->seg_y.as<int64_t>(), st);
+        if (rc) return rc;
+    }
+    rc = encode_y(s, sy, nyl, d_nw_y, slot_y, st);
     if (rc) return rc;
     // ---- stream lengths to the host; offsets and compaction on the device meanwhile
     rc = s->h_nw.ensure(sizeof(int32_t) * (batch + sy));
@@ -717,8 +767,7 @@ int encode_body(basic_hp_session *s, const float *d_x, bool x_in_session, int ba
         }
         if (over_y) {
             slot_y = 3 * nyl + 4;   // guaranteed per lane stream
-            rc = encode_latent(s, s->y_tables, s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), sy, nyl, &s->seg_y, &s->slots_y, d_nw_y,
-                               slot_y, st);
+            rc = encode_y(s, sy, nyl, d_nw_y, slot_y, st);
             if (rc) return rc;
         }
     }
@@ -974,8 +1023,23 @@ int decode_body(basic_hp_session *s, const uint8_t *data, int64_t len, float *d_
                                                s->n_scales, s->scale_bound, s->y_sym.as<int32_t>(), s->y_idx.as<int32_t>(), nullptr, st);
     }
     if (rc) return rc;
-    rc = basic_rans_decode_batch_dev(s->y_tables, d_wy, d_oy, s->y_idx.as<int32_t>(), s->seg_y.as<int64_t>(), sy, s->y_sym.as<int32_t>(),
-                                     s->state.as<uint64_t>() + batch, s->pos.as<int64_t>() + batch, st);
+    if (s->skip_rows) {
+        // the streams hold the elements whose row is at least skip_rows: compact the indexes (seg_y becomes the streams' bounds),
+        // decode into the compact array, put the symbols back where they belong with 0 in between
+        rc = ensure_skip(s, sy, nyl);
+        if (!rc)
+            rc = basic_skip_compact_dev(nullptr, s->y_idx.as<int32_t>(), sy, nyl, s->skip_rows, s->skip_scratch.p, nullptr,
+                                        s->y_idxc.as<int32_t>(), s->seg_y.as<int64_t>(), st);
+        if (!rc)
+            rc = basic_rans_decode_batch_dev(s->y_tables, d_wy, d_oy, s->y_idxc.as<int32_t>(), s->seg_y.as<int64_t>(), sy,
+                                             s->y_symc.as<int32_t>(), s->state.as<uint64_t>() + batch, s->pos.as<int64_t>() + batch, st);
+        if (!rc)
+            rc = basic_skip_expand_dev(s->y_symc.as<int32_t>(), s->y_idx.as<int32_t>(), sy, nyl, s->skip_rows, s->skip_scratch.p,
+                                       s->y_sym.as<int32_t>(), st);
+    } else {
+        rc = basic_rans_decode_batch_dev(s->y_tables, d_wy, d_oy, s->y_idx.as<int32_t>(), s->seg_y.as<int64_t>(), sy, s->y_sym.as<int32_t>(),
+                                         s->state.as<uint64_t>() + batch, s->pos.as<int64_t>() + batch, st);
+    }
     if (rc) return rc;
     if (s->mean_scale)
         rc = basic_gc_dequantize_ms_dev(s->y_sym.as<int32_t>(), d_scales + ny, batch * ny, ny, np, n_steps ? s->d_steps.as<float>() : nullptr,

@@ -529,6 +529,27 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         steps = check_qsteps(qstep, batch)
         return steps, {self.QSTEP_NODE: dict(qstep=steps)}
 
+    def _skip_coder_kwargs(self, skip_rows):
+        """``skip_rows`` of encode / decode -> the validated row count, or None without one.  TypeError when the graph's y coder is
+        not the GaussianConditional coder; ValueError for an invalid count (utils/skip.py)."""
+        if skip_rows is None:
+            return None
+        from ..prior_model.prior_coder.compressai_coder import (CompressAIGaussianConditionalCoder,
+                                                                CompressAIMeanScaleGaussianConditionalCoder)
+        from ...utils.skip import SKIP_TABLE_ROWS, check_skip_rows
+        coder = self.latent_node_entropy_coders[self.QSTEP_NODE] if self.QSTEP_NODE in self.latent_node_entropy_coders else None
+        if type(coder) not in (CompressAIGaussianConditionalCoder, CompressAIMeanScaleGaussianConditionalCoder):
+            raise TypeError(f"skip_rows= is skip coding of a CompressAIGaussianConditionalCoder (scale-only or mean-scale) at node '{self.QSTEP_NODE}'; "
+                            f"this graph codes it with {type(coder).__name__}, whose context model reads every symbol: skip coding of the "
+                            "autoregressive codecs is not implemented")
+        return check_skip_rows(skip_rows, coder.scale_table.numel() or SKIP_TABLE_ROWS)
+
+    @staticmethod
+    def _no_skip_rows(kwargs, what):
+        if "skip_rows" in kwargs:
+            raise ValueError(f"{what} takes no skip_rows=: skip coding of tiled pictures is not implemented (their containers carry no "
+                             "skip rows); code the picture whole with compress_skip")
+
     def _qstep_stream_batch(self, data):
         """Images in a coded string, from the y body's header (host code: nothing is launched)."""
         nodes = self._coded_nodes()
@@ -541,16 +562,23 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
             raise ValueError(f"the y body holds {ns} streams, no multiple of this coder's {lanes} stream lanes")
         return ns // lanes
 
-    def encode(self, data, *args, prior=None, qstep=None, rate_target=None, **kwargs):
+    def encode(self, data, *args, prior=None, qstep=None, rate_target=None, skip_rows=None, **kwargs):
         """``qstep``: None -- today's codec; a number or one number per image -- the quantiser step of the y coder (INTEGRATION.md
         "Quantiser step").  Like ``output_dtype`` of decode() it is not one of ``kwargs``: it neither changes the path a call takes
-        nor reaches a node generator, and both paths write the same bytes.  The string does not hold the steps: decode() needs them."""
+        nor reaches a node generator, and both paths write the same bytes.  The string does not hold the steps: decode() needs them.
+        ``skip_rows``: None -- today's codec; r -- skip coding of the y coder (INTEGRATION.md "Skip coding"), an explicit keyword in the
+        same way, with ``qstep=`` or alone; decode() needs it too."""
         steps, coder_kwargs = self._qstep_coder_kwargs(qstep, data.shape[0])
         rt, rate_kwargs = self._rate_coder_kwargs(rate_target, data.shape[0])
+        skip = self._skip_coder_kwargs(skip_rows)
         if rt is not None:
             if steps is not None:
                 raise ValueError("rate_target= and qstep= are two ways to state the step: give one of them")
+            if skip is not None:
+                raise ValueError("rate_target= and skip_rows= do not combine: the rate curve would count symbols that are not coded")
             coder_kwargs = rate_kwargs
+        if skip is not None:
+            coder_kwargs = {self.QSTEP_NODE: dict((coder_kwargs or {}).get(self.QSTEP_NODE, {}), skip_rows=skip)}
         with torch.no_grad():
             sess = self._fused_session(kwargs, prior) if not args else None
             if sess is not None:   # one C call: upload (when the batch is on the host), transforms, entropy stage, framing
@@ -564,13 +592,16 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                             rt.set_result(*sess.rate_result(data.shape[0]))
                         finally:
                             sess.set_rate_targets(None)
-                    elif steps is None:
+                    elif steps is None and not skip:
                         out = sess.encode(data)
                     else:
-                        sess.set_qsteps(steps)
+                        if steps is not None:
+                            sess.set_qsteps(steps)
                         try:
+                            sess.set_skip_rows(skip)
                             out = sess.encode(data)
                         finally:
+                            sess.set_skip_rows(0)
                             sess.set_qsteps(None)
                 if self.after_inference_hook is not None:
                     self.after_inference_hook()
@@ -600,26 +631,33 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
                 rt.resolve()
             return out
 
-    def decode(self, data, *args, prior=None, output_dtype=None, qstep=None, **kwargs):
+    def decode(self, data, *args, prior=None, output_dtype=None, qstep=None, skip_rows=None, **kwargs):
         """``output_dtype``: None / torch.float32 -- the reconstruction as the graph gives it; torch.uint8 -- the picture,
         ``nan_to_num(x, nan=0).clamp(0, 1).mul(255).round()`` as bytes, converted on the device.  The keyword is the caller's
         wish about the RESULT: it is not one of ``kwargs``, so it neither changes the path a call takes nor reaches a node generator.
-        ``qstep``: the steps encode() was given (one, or one per image of the string), an explicit keyword in the same way."""
+        ``qstep``: the steps encode() was given (one, or one per image of the string), an explicit keyword in the same way.
+        ``skip_rows``: the rows encode() was given, likewise."""
         if output_dtype not in (None, torch.float32, torch.uint8):
             raise TypeError(f"output_dtype is torch.float32 or torch.uint8, not {output_dtype}")
         steps, coder_kwargs = self._qstep_coder_kwargs(qstep, None)
+        skip = self._skip_coder_kwargs(skip_rows)
+        if skip is not None:
+            coder_kwargs = {self.QSTEP_NODE: dict((coder_kwargs or {}).get(self.QSTEP_NODE, {}), skip_rows=skip)}
         if steps is not None:   # one step or one per image, checked against the string's own header before anything is launched
             check_qsteps(steps, self._qstep_stream_batch(data))
         with torch.no_grad():
             sess = self._fused_session(kwargs, prior) if not args else None
             if sess is not None:
                 with self.profiler.start_time_profile("decode_fused"):
-                    if steps is None:
+                    if steps is None and not skip:
                         return sess.decode(data, device=self.device, output_dtype=output_dtype or torch.float32)
-                    sess.set_qsteps(steps)
+                    if steps is not None:
+                        sess.set_qsteps(steps)
                     try:
+                        sess.set_skip_rows(skip)
                         return sess.decode(data, device=self.device, output_dtype=output_dtype or torch.float32)
                     finally:
+                        sess.set_skip_rows(0)
                         sess.set_qsteps(None)
             node_dict = self._node_generate_process(**self._get_default_node_dict(force_add_default_dynamic_nodes=True, **kwargs))
             nodes = self._coded_nodes()
@@ -817,6 +855,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         size share calls of at most ``max_batch``, cut by nn.kernels.image_tiles_gather), so ``pad_to=tile`` codes a picture as one
         group.  With 1, the default, nothing is padded and nothing changes."""
         from ...utils import tiling
+        self._no_skip_rows(kwargs, "encode_tiled")
         self._check_picture(image)
         _, C, H, W = image.shape
         grid = tiling.TileGrid(H, W, *self._tile_size(tile), overlap=overlap, pad_to=pad_to)
@@ -880,6 +919,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         (one decode() call per coded size and ``max_batch``; uint8 results pasted by nn.kernels.image_tiles_scatter with ``clip=True``);
         overlapped ones are written by the same blend launch, which reads those top-left samples."""
         from ...nn import kernels as K
+        self._no_skip_rows(kwargs, "decode_tiled")
         from ...utils import tiling
         if output_dtype not in (None, torch.float32, torch.uint8):
             raise TypeError(f"output_dtype is torch.float32 or torch.uint8, not {output_dtype}")
@@ -1035,6 +1075,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         a coder cannot split, in training mode, or when the call brings arguments.  With ``pad_to`` the tiles are pooled by their coded
         size and cut with the edges replicated (``pad=True``); ``pad_to=tile`` makes the pool one size."""
         from ...utils import tiling
+        self._no_skip_rows(kwargs, "encode_tiled_items")
         pictures = list(pictures)
         for x in pictures:
             self._check_item(x)
@@ -1072,6 +1113,7 @@ class LatentGraphicalANSEntropyCoder(HotPathModule, VariableRateCodecInterface, 
         of a picture stays decode_tiled's.  Edge-padded containers (BTL3; ``pad_to`` read from each, and free to differ within a call):
         their tiles are pooled by coded size and cropped to their valid rectangles (the scatter with ``clip=True``)."""
         from ...nn import kernels as K
+        self._no_skip_rows(kwargs, "decode_tiled_items")
         from ...utils import tiling
         if "region" in kwargs:
             raise TypeError("decode_tiled_items takes no region: decode a part of a picture with decode_tiled")

@@ -522,14 +522,87 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
         sym = self._tables.decode_batch_from_frame(byte_string, idx.reshape(-1), per)
         return K.gc_dequantize_q(sym.reshape(idx.shape), steps)
 
+    # ---- skip coding (INTEGRATION.md "Skip coding"; no reference counterpart): ``skip_rows`` = r, elements whose table row is
+    # below r are not coded and decode as symbol 0.  The three hooks are what the mean-scale coder replaces.
+    def _skip(self, skip_rows, *other_knobs):
+        """None -> None; else the validated row count.  ValueError beside rate_target=, rate_measure= or channel_gains."""
+        if skip_rows is None:
+            return None
+        from ....utils.skip import SKIP_TABLE_ROWS, check_skip_rows
+        r = check_skip_rows(skip_rows, self.scale_table.numel() or SKIP_TABLE_ROWS)
+        if any(k is not None for k in other_knobs):
+            raise ValueError("skip_rows= leaves the low rows uncoded: rate_target= and rate_measure= would count symbols that are not "
+                             "coded, and channel_gains has no defined order with it -- give skip_rows= with qstep= or alone")
+        return r
+
+    def _skip_quantize(self, y, prior, qstep):
+        """-> (sym, idx, the cropped prior _skip_dequantize and _skip_scales read) of the latent, as encode() obtains them."""
+        scales = self._crop(prior, *y.shape[-2:])
+        if qstep is None:
+            sym, idx, _ = K.gc_quantize_index(y, scales, self._scale_table_dev, self.scale_bound, want_yhat=False)
+        else:
+            sym, idx, _ = K.gc_quantize_index_q(y, scales, qstep, self._scale_table_dev, self.scale_bound, want_yhat=False)
+        return sym, idx, scales
+
+    def _skip_indexes(self, prior, h, w, qstep):
+        """-> (idx [B][C][h][w], the cropped prior _skip_dequantize reads) as decode() obtains them."""
+        scales = self._crop(prior, h, w)
+        if qstep is None:
+            _, idx, _ = K.gc_quantize_index(scales, scales, self._scale_table_dev, self.scale_bound, want_yhat=False)
+        else:
+            _, idx, _ = K.gc_quantize_index_q(scales, scales, qstep, self._scale_table_dev, self.scale_bound, want_yhat=False)
+        return idx, scales
+
+    def _skip_dequantize(self, sym, params, qstep):
+        return K.i32_to_f32(sym) if qstep is None else K.gc_dequantize_q(sym, qstep)
+
+    @staticmethod
+    def _skip_scales(params, channels):
+        """The scales [B][C][h][w] of the likelihood kernel (forward only)."""
+        return params
+
+    def _encode_skip(self, y, prior, skip_rows, qstep, lazy):
+        sym, idx, _ = self._skip_quantize(y, prior, qstep)
+        per = self._lane_length(y[0].numel())
+        # stream (b, k) is the compaction of the k-th of K equal runs of image b: B * K segments of at most `per` symbols
+        sym_c, idx_c, seg = K.skip_compact(sym, idx, y.shape[0] * self.stream_lanes, skip_rows)
+        body = PendingBody(self._tables, self._tables.encode_batch_begin(sym_c, idx_c, per, seg=seg), y.shape[-2:])
+        return body if lazy else body.result()
+
+    def _decode_skip(self, byte_string, prior, skip_rows, qstep):
+        h, w, ns = K.frame_header(byte_string)
+        idx, params = self._skip_indexes(prior, h, w, qstep)
+        per = self._lane_length(idx[0].numel())
+        if ns != idx.shape[0] * self.stream_lanes:
+            raise ValueError(f"stream body holds {ns} streams, this coder's configuration needs {idx.shape[0] * self.stream_lanes}")
+        _, idx_c, seg = K.skip_compact(None, idx, ns, skip_rows)
+        sym_c = self._tables.decode_batch_from_frame(byte_string, idx_c, per, seg=seg)
+        return self._skip_dequantize(K.skip_expand(sym_c, idx, ns, skip_rows), params, qstep)
+
+    def _forward_skip(self, y, prior, skip_rows, qstep):
+        """The decoder's yhat: the coded symbols with 0 at every skipped element, de-quantised by the decoder's kernels."""
+        sym, idx, params = self._skip_quantize(y, prior, qstep)
+        self._lane_length(y[0].numel())
+        ns = y.shape[0] * self.stream_lanes
+        sym_c, _, _ = K.skip_compact(sym, idx, ns, skip_rows)
+        sym = K.skip_expand(sym_c, idx, ns, skip_rows)
+        steps = None if qstep is None else K.qsteps_tensor(qstep, y.shape[0], y.device)
+        # the table cost of a skipped element is about 1e-4 bit: the estimate of the symbols as decoded is the rate's
+        self.update_cache("metric_dict", prior_entropy=K.gauss_nll_per_image(K.i32_to_f32(sym), self._skip_scales(params, y.shape[1]), False,
+                                                                              self.scale_bound, 1e-9, steps=steps).mean())
+        return self._skip_dequantize(sym, params, qstep)
+
     @staticmethod
     def _qstep_alone(qstep, channel_gains, channel_gains_inv):
         if qstep is not None and (channel_gains is not None or channel_gains_inv is not None):
             raise ValueError("qstep= and channel_gains are two rate knobs: give one of them")
         return qstep is not None
 
-    def forward(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, **kwargs):
+    def forward(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, skip_rows=None, **kwargs):
         self._ready()
+        skip_rows = self._skip(skip_rows, channel_gains, channel_gains_inv)
+        if skip_rows is not None:
+            return self._forward_skip(y, prior, skip_rows, qstep)
         if self._qstep_alone(qstep, channel_gains, channel_gains_inv):
             return self._forward_q(y, prior, qstep)
         if channel_gains is not None:
@@ -548,8 +621,11 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
     accepts_buffer = True  # decode() reads the stream through the buffer protocol (bytes or memoryview)
 
     def encode(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, lazy=False, qstep=None, rate_target=None,
-               rate_measure=None, **kwargs):  # :377-385
+               rate_measure=None, skip_rows=None, **kwargs):  # :377-385
         self._ready()
+        skip_rows = self._skip(skip_rows, rate_target, rate_measure, channel_gains, channel_gains_inv)
+        if skip_rows is not None:
+            return self._encode_skip(y, prior, skip_rows, qstep, lazy)
         if rate_measure is not None:
             # a caller that chooses the step over several calls (tiled pictures): nothing is coded here -- the call's y and sigma are
             # handed back in the dict, and the caller codes them with _encode_q once the steps are chosen
@@ -572,8 +648,12 @@ class CompressAIGaussianConditionalCoder(CompressAIItemFraming, HotPathModule):
         body = PendingBody(self._tables, self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), per), y.shape[-2:])
         return body if lazy else body.result()
 
-    def decode(self, byte_string, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, **kwargs):  # :387-393
+    def decode(self, byte_string, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, skip_rows=None,
+               **kwargs):  # :387-393
         self._ready()
+        skip_rows = self._skip(skip_rows, channel_gains, channel_gains_inv)
+        if skip_rows is not None:
+            return self._decode_skip(byte_string, prior, skip_rows, qstep)
         if self._qstep_alone(qstep, channel_gains, channel_gains_inv):
             return self._decode_q(byte_string, prior, qstep)
         h, w, ns = K.frame_header(byte_string)
@@ -616,6 +696,26 @@ class CompressAIMeanScaleGaussianConditionalCoder(CompressAIGaussianConditionalC
         if channel_gains is not None or channel_gains_inv is not None:
             raise ValueError("the mean-scale coder takes no channel_gains: upstream defines no order of gain and mean (use qstep=)")
 
+    def _skip_quantize(self, y, prior, qstep):
+        prior = self._split(y.shape, prior)
+        sym, idx, _ = K.gc_quantize_index_ms(y, prior, self._scale_table_dev, self.scale_bound, steps=qstep, want_yhat=False)
+        return sym, idx, prior
+
+    def _skip_indexes(self, prior, h, w, qstep):
+        if prior is None or prior.dim() != 4 or prior.shape[1] % 2:
+            got = None if prior is None else tuple(prior.shape)
+            raise ValueError(f"the mean-scale coder takes a prior of 2 * C channels (scales, then means), got {got}")
+        prior = self._crop(prior, h, w)
+        _, idx, _ = K.gc_quantize_index_ms(None, prior, self._scale_table_dev, self.scale_bound, steps=qstep)
+        return idx, prior
+
+    def _skip_dequantize(self, sym, params, qstep):
+        return K.gc_dequantize_ms(sym, params, steps=qstep)
+
+    @staticmethod
+    def _skip_scales(params, channels):
+        return params[:, :channels].contiguous()
+
     def _begin(self, y, sym, idx, lazy):
         per = self._lane_length(y[0].numel())
         body = PendingBody(self._tables, self._tables.encode_batch_begin(sym.reshape(-1), idx.reshape(-1), per), y.shape[-2:])
@@ -649,9 +749,12 @@ class CompressAIMeanScaleGaussianConditionalCoder(CompressAIGaussianConditionalC
         rt.resolve()
         return out
 
-    def forward(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, **kwargs):
+    def forward(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, skip_rows=None, **kwargs):
         self._ready()
         self._no_gains(channel_gains, channel_gains_inv)
+        skip_rows = self._skip(skip_rows)
+        if skip_rows is not None:
+            return self._forward_skip(y, prior, skip_rows, qstep)
         prior = self._split(y.shape, prior)
         C = y.shape[1]
         scales = prior[:, :C].contiguous()   # the likelihood kernel's [B][C][h][w] layout (not on the coding path)
@@ -668,9 +771,12 @@ class CompressAIMeanScaleGaussianConditionalCoder(CompressAIGaussianConditionalC
         return yhat
 
     def encode(self, y, *args, prior=None, channel_gains=None, channel_gains_inv=None, lazy=False, qstep=None, rate_target=None,
-               rate_measure=None, **kwargs):
+               rate_measure=None, skip_rows=None, **kwargs):
         self._ready()
         self._no_gains(channel_gains, channel_gains_inv)
+        skip_rows = self._skip(skip_rows, rate_target, rate_measure)
+        if skip_rows is not None:
+            return self._encode_skip(y, prior, skip_rows, qstep, lazy)
         if rate_measure is not None:
             if qstep is not None or rate_target is not None:
                 raise ValueError("rate_measure= retains the latent for a step chosen later: no qstep= or rate_target= with it")
@@ -685,9 +791,12 @@ class CompressAIMeanScaleGaussianConditionalCoder(CompressAIGaussianConditionalC
             return self._encode_rate(y, prior, rate_target, lazy)
         return self._encode_q(y, prior, qstep, lazy)
 
-    def decode(self, byte_string, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, **kwargs):
+    def decode(self, byte_string, *args, prior=None, channel_gains=None, channel_gains_inv=None, qstep=None, skip_rows=None, **kwargs):
         self._ready()
         self._no_gains(channel_gains, channel_gains_inv)
+        skip_rows = self._skip(skip_rows)
+        if skip_rows is not None:
+            return self._decode_skip(byte_string, prior, skip_rows, qstep)
         h, w, ns = K.frame_header(byte_string)
         if prior is None or prior.dim() != 4 or prior.shape[1] % 2:
             got = None if prior is None else tuple(prior.shape)

@@ -233,10 +233,17 @@ class RansTables:
 
     # ---- batched streams <-> host bytes.  begin() only enqueues GPU work (encode, device-side offsets, compaction);
     # end() is the single host synchronisation, so a caller can launch more kernels in between.
-    def encode_batch_begin(self, symbols, indexes, n_per_stream, slot=None):
+    def encode_batch_begin(self, symbols, indexes, n_per_stream, slot=None, seg=None):
+        """``seg`` (skip coding): an int64 device tensor [ns + 1] bounding streams of unequal lengths inside symbols / indexes, as
+        skip_compact writes it; ``n_per_stream`` is then the bound of a stream's length that sizes the slots."""
         symbols, indexes = _dev(symbols, torch.int32), _dev(indexes, torch.int32)
-        ns = symbols.numel() // n_per_stream
-        seg = torch.arange(ns + 1, device=symbols.device, dtype=torch.int64) * n_per_stream
+        given = seg
+        if seg is None:
+            ns = symbols.numel() // n_per_stream
+            seg = torch.arange(ns + 1, device=symbols.device, dtype=torch.int64) * n_per_stream
+        else:
+            seg = _dev(seg, torch.int64)
+            ns = seg.numel() - 1
         slot = slot or n_per_stream + 2  # the reference's own buffer size (rans64.cpp:240)
         words, nwords = self.encode_batch(symbols, indexes, seg, slot)
         d_off = torch.zeros((ns + 1,), device=symbols.device, dtype=torch.int64)
@@ -244,7 +251,8 @@ class RansTables:
         packed = torch.empty((ns * slot,), device=symbols.device, dtype=torch.int32)
         _lib.check(_lib.lib().basic_rans_compact_streams_dev(words.data_ptr(), slot, nwords.data_ptr(), d_off.data_ptr(), ns,
                                                              packed.data_ptr(), _stream()))
-        return dict(symbols=symbols, indexes=indexes, n=n_per_stream, ns=ns, slot=slot, nwords=nwords, packed=packed, keep=words)
+        return dict(symbols=symbols, indexes=indexes, n=n_per_stream, ns=ns, slot=slot, nwords=nwords, packed=packed, keep=words,
+                    seg=given)
 
     def _pinned(self, which, nbytes):
         """Page-locked staging buffer owned by this table set (D2H of encoded words / H2D of words to decode): DMA at
@@ -260,7 +268,7 @@ class RansTables:
         table set's pinned staging buffer: valid until its next encode_batch_end()."""
         nw = h["nwords"].cpu().numpy()
         if (nw < 0).any():  # bypass-heavy data overflowed the reference's bound: redo with the guaranteed one
-            h = self.encode_batch_begin(h["symbols"], h["indexes"], h["n"], slot=3 * h["n"] + 4)
+            h = self.encode_batch_begin(h["symbols"], h["indexes"], h["n"], slot=3 * h["n"] + 4, seg=h.get("seg"))
             nw = h["nwords"].cpu().numpy()
         off = np.zeros(h["ns"] + 1, dtype=np.int64)
         np.cumsum(nw, out=off[1:])
@@ -282,13 +290,16 @@ class RansTables:
             ev.synchronize()
         return self._pinned("in", 4 * max(nwords, 1))[: 4 * nwords].view(torch.int32)
 
-    def decode_batch_from_frame(self, data, indexes, n_per_stream):
+    def decode_batch_from_frame(self, data, indexes, n_per_stream, seg=None):
         """Framed body (frame_streams / write_body) -> int32 symbols like ``indexes``: the payloads are unframed by the C
-        helper straight into the pinned staging buffer and DMA'd from there."""
+        helper straight into the pinned staging buffer and DMA'd from there.  ``seg`` (skip coding): an int64 device tensor, one
+        entry more than the body has streams, bounding the streams' symbols inside ``indexes`` instead of ``n_per_stream``."""
         h, w, n = frame_header(data)
+        if seg is not None and seg.numel() != n + 1:
+            raise ValueError(f"stream body holds {n} streams, the segment tensor bounds {seg.numel() - 1}")
         stage = self._stage_in((len(data) - 12 - 4 * n) // 4)
         words, word_off, _ = unframe_streams(data, out=stage.numpy().view(np.uint32))
-        return self._decode_staged(stage[: words.size], word_off, indexes, n_per_stream)
+        return self._decode_staged(stage[: words.size], word_off, indexes, n_per_stream, seg=seg)
 
     def decode_batch_from_words(self, host_words, word_off, indexes, n_per_stream):
         """Streams given as one uint32 array + word offsets (see unframe_streams): int32 symbols like ``indexes``."""
@@ -296,14 +307,15 @@ class RansTables:
         stage.numpy()[:] = host_words.view(np.int32)
         return self._decode_staged(stage, word_off, indexes, n_per_stream)
 
-    def _decode_staged(self, stage, word_off, indexes, n_per_stream):
+    def _decode_staged(self, stage, word_off, indexes, n_per_stream, seg=None):
         indexes = _dev(indexes, torch.int32)
         ns = len(word_off) - 1
         d_words = stage.to(indexes.device, non_blocking=True)
         self._pin_in_event = torch.cuda.Event()
         self._pin_in_event.record(torch.cuda.current_stream(indexes.device))
         d_woff = torch.from_numpy(np.ascontiguousarray(word_off, dtype=np.int64)).to(indexes.device)
-        seg = torch.arange(ns + 1, device=indexes.device, dtype=torch.int64) * n_per_stream
+        if seg is None:
+            seg = torch.arange(ns + 1, device=indexes.device, dtype=torch.int64) * n_per_stream
         out, _, _ = self.decode_batch(d_words, d_woff, indexes, seg)
         return out
 
@@ -756,6 +768,59 @@ def group_lanes_pack(sym, idx, bases, lanes):
     _lib.check(_lib.lib().basic_group_lanes_pack_dev(sym.data_ptr(), idx.data_ptr(), int(B), int(n), bases.data_ptr(), int(bases.numel() - 1),
                                                      int(lanes), so.data_ptr(), io.data_ptr(), _stream()))
     return so, io
+
+
+# ---- skip coding (INTEGRATION.md "Skip coding"): elements whose table row is below skip_rows are not coded
+SKIP_CHUNK = 1024   # BASIC_SKIP_CHUNK: the elements of one stream a workgroup pass covers
+
+
+def skip_scratch_bytes(nstreams, per):
+    """BASIC_SKIP_SCRATCH_BYTES."""
+    return 8 * int(nstreams) * ((int(per) + SKIP_CHUNK - 1) // SKIP_CHUNK)
+
+
+def _skip_args(idx, nstreams, skip_rows, what):
+    from ..utils.skip import check_skip_rows
+    idx = _dev(idx, torch.int32)
+    nstreams = int(nstreams)
+    if nstreams < 1 or idx.numel() < nstreams or idx.numel() % nstreams:
+        raise ValueError(f"{what}: {idx.numel()} elements are no whole number of {nstreams} non-empty streams")
+    per = idx.numel() // nstreams
+    rows = check_skip_rows(skip_rows, 2 ** 31 - 1)   # the table's length is the coder's to check
+    scratch = torch.empty((max(skip_scratch_bytes(nstreams, per) // 8, 1),), device=idx.device, dtype=torch.int64)
+    return idx, nstreams, per, rows, scratch
+
+
+def skip_compact(sym, idx, nstreams, skip_rows):
+    """basic_skip_compact_dev on int32 arrays of ``nstreams`` equal streams: -> (sym_c, idx_c, seg), the elements with
+    idx >= skip_rows of stream 0, then stream 1, ..., back to back in their order; seg int64 [nstreams + 1] = their bounds
+    (seg[-1] = the total kept).  sym_c / idx_c are flat and as long as the input: what lies past seg[-1] is unwritten.  ``sym`` None:
+    indexes and segments only (None comes back for sym_c)."""
+    idx, nstreams, per, rows, scratch = _skip_args(idx, nstreams, skip_rows, "skip_compact")
+    if sym is not None:
+        sym = _dev(sym, torch.int32)
+        if sym.numel() != idx.numel():
+            raise ValueError("skip_compact: symbols and indexes hold the same number of elements")
+    sym_c = torch.empty((idx.numel(),), device=idx.device, dtype=torch.int32) if sym is not None else None
+    idx_c = torch.empty((idx.numel(),), device=idx.device, dtype=torch.int32)
+    seg = torch.empty((nstreams + 1,), device=idx.device, dtype=torch.int64)
+    _lib.check(_lib.lib().basic_skip_compact_dev(sym.data_ptr() if sym is not None else None, idx.data_ptr(), nstreams, per, rows,
+                                                 scratch.data_ptr(), sym_c.data_ptr() if sym_c is not None else None, idx_c.data_ptr(),
+                                                 seg.data_ptr(), _stream()))
+    return sym_c, idx_c, seg
+
+
+def skip_expand(sym_compact, idx, nstreams, skip_rows):
+    """basic_skip_expand_dev: int32 symbols shaped like the dense ``idx`` -- the j-th element with idx >= skip_rows of stream s
+    receives the j-th of the stream's run in ``sym_compact`` (the runs back to back, as skip_compact writes them), every other 0."""
+    idx, nstreams, per, rows, scratch = _skip_args(idx, nstreams, skip_rows, "skip_expand")
+    sym_compact = _dev(sym_compact, torch.int32)
+    if sym_compact.numel() == 0:   # everything skipped and an empty tensor given: the C ABI still wants a valid pointer
+        sym_compact = torch.zeros((1,), device=idx.device, dtype=torch.int32)
+    out = torch.empty(idx.shape, device=idx.device, dtype=torch.int32)
+    _lib.check(_lib.lib().basic_skip_expand_dev(sym_compact.data_ptr(), idx.data_ptr(), nstreams, per, rows, scratch.data_ptr(),
+                                                out.data_ptr(), _stream()))
+    return out
 
 
 def eb_quantize_index(z, medians):
@@ -1226,6 +1291,11 @@ class HyperpriorSession:
         from ..utils.qstep import check_qsteps
         steps = check_qsteps(steps)
         _lib.check(_lib.lib().basic_hp_session_set_qsteps(self._h, steps.ctypes.data, int(steps.size)))
+
+    def set_skip_rows(self, rows):
+        """Skip coding of the y latent for the calls that follow (basic_hp_session_set_skip_rows): elements whose table row is below
+        ``rows`` are not coded; 0 / None is the format without it.  Refused (BasicHipError) while rate targets are set."""
+        _lib.check(_lib.lib().basic_hp_session_set_skip_rows(self._h, int(rows or 0)))
 
     def set_rate_targets(self, budgets, candidates=None, passes=2):
         """Byte budgets of the payloads of the calls that follow (basic_hp_session_set_rate_targets): a number or one per image;

@@ -305,6 +305,35 @@ int basic_lanes_pack_dev(const int32_t *d_sym, const int32_t *d_idx, int batch, 
  * lengths).  Out of place; lanes == 1 copies.  lanes in [1, 256] and n % lanes == 0, else BASIC_ERR_INVALID. */
 int basic_group_lanes_pack_dev(const int32_t *d_sym, const int32_t *d_idx, int batch, int64_t n, const int64_t *d_bases, int groups,
                                int lanes, int32_t *d_sym_out, int32_t *d_idx_out, void *hip_stream);
+/* Skip coding (no reference counterpart; an opt-in format, INTEGRATION.md "Skip coding"): an element whose table row is below
+ * skip_rows is not coded, and the decoder rebuilds it as symbol 0.  Both sides obtain the rows from the same index kernel on the
+ * same prior, so the rule needs no side information.  keep(i) = d_idx[i] >= skip_rows.
+ *
+ * basic_skip_compact_dev: d_sym / d_idx are dense int32 [nstreams][per].  The outputs hold the kept elements of stream 0, then of
+ * stream 1, and so on, back to back and each in its original order; d_seg int64 [nstreams + 1]: d_seg[s] = elements kept before
+ * stream s, d_seg[nstreams] = the total -- what basic_rans_encode_batch_dev / basic_rans_decode_batch_dev take as they stand.
+ * d_sym == NULL with d_sym_out == NULL: indexes and segments only (the decoder's call).  The outputs must hold nstreams * per
+ * elements (everything may be kept), out of place.  skip_rows == 0 copies, d_seg[s] = s * per.
+ *
+ * basic_skip_expand_dev: the inverse.  The j-th kept element of stream s receives d_sym_compact[d_seg[s] + j], a skipped one 0;
+ * d_idx_dense is the dense index array the compaction read.  The call RECOMPUTES the positions from d_idx_dense (a count and a
+ * scan launch of its own): it needs no d_seg and nothing a compact call left in d_scratch, which may be any scratch of the size.
+ *
+ * Three launches each: per-chunk counts (a workgroup reads BASIC_SKIP_CHUNK elements of one stream, 16 bytes a lane where the
+ * lane's four elements are 16-byte aligned and inside the stream, element by element otherwise), one workgroup's exclusive scan of
+ * the counts in int64, and the scatter (ranks inside a chunk from wave ballots and an LDS sum over the waves).  No workgroup waits on
+ * another and no atomic decides a position: the output is a function of the input alone.  Chunk c of stream s covers elements
+ * [c * BASIC_SKIP_CHUNK, min(per, (c + 1) * BASIC_SKIP_CHUNK)); a stream has ceil(per / BASIC_SKIP_CHUNK) chunks.
+ * d_scratch: BASIC_SKIP_SCRATCH_BYTES(nstreams, per) bytes of device memory, 8-byte aligned, private to the call until the stream
+ * has passed it.  BASIC_ERR_INVALID, before any launch: a null pointer, nstreams < 1, per < 1, skip_rows < 0, d_sym without
+ * d_sym_out or the reverse, a misaligned d_scratch, more than 2^30 chunks. */
+#define BASIC_SKIP_CHUNK 1024
+#define BASIC_SKIP_SCRATCH_BYTES(nstreams, per) \
+    (8 * (size_t)(nstreams) * (((size_t)(per) + BASIC_SKIP_CHUNK - 1) / BASIC_SKIP_CHUNK))
+int basic_skip_compact_dev(const int32_t *d_sym, const int32_t *d_idx, int nstreams, int64_t per, int skip_rows, void *d_scratch,
+                           int32_t *d_sym_out, int32_t *d_idx_out, int64_t *d_seg, void *hip_stream);
+int basic_skip_expand_dev(const int32_t *d_sym_compact, const int32_t *d_idx_dense, int nstreams, int64_t per, int skip_rows,
+                          void *d_scratch, int32_t *d_sym_dense_out, void *hip_stream);
 /* EntropyBottleneck path (compressai_coder.py:230-245): sym = round(z - median[c]),
  * idx = c, zhat = sym + median[c].  Layout [B][C][HW]. */
 int basic_eb_quantize_index_dev(const float *d_z, const float *d_medians, int batch, int channels, int hw,
@@ -544,6 +573,15 @@ int basic_hp_session_set_rate_targets(basic_hp_session *s, const int64_t *host_b
 /* The last rate-controlled encode call's choices, n = its batch: the steps, the predicted payload bytes and the select kernel's
  * d_choice word (BASIC_RATE_NO_FIT set: nothing fitted, the largest step was taken).  Any of the three may be NULL. */
 int basic_hp_session_rate_result(const basic_hp_session *s, float *steps, int64_t *pred_bytes, int32_t *flags, int n);
+/* Skip coding of the y latent (section 4, "Skip coding"): rows in [0, n_scales]; 0 (the default) is the format without it, and the
+ * session launches exactly what it launched before.  With rows > 0 the encoder compacts the y symbols and indexes behind the
+ * quantise launch (basic_skip_compact_dev) and codes the compacted streams; the decoder compacts the indexes, decodes, expands
+ * (basic_skip_expand_dev) and de-quantises with the unchanged kernels, so a skipped element is rebuilt as symbol 0: yhat = 0, or the
+ * mean.  Quantiser steps (the rows are then those of sigma / step), lane streams (every lane's run is shortened on its own), the
+ * mean-scale graph and the uint8 entry points keep their meaning; the body's format is unchanged, its streams are shorter.  Refused
+ * with BASIC_ERR_INVALID while rate targets are set, as basic_hp_session_set_rate_targets is while rows > 0: the rate curve counts
+ * symbols that would not be coded.  Not written into the stream: the container that carries it is the caller's (utils/skip.py). */
+int basic_hp_session_set_skip_rows(basic_hp_session *s, int rows);
 /* Wavefronts (image streams) per workgroup of this session's rANS launches: 1, 2, 4, 8 or 16 (0 = library default). */
 int basic_hp_session_set_rans_waves(basic_hp_session *s, int waves_per_block);
 /* Opt this session into the process-wide "transform token": the MFMA-heavy phases (compress: everything up to the y

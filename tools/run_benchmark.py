@@ -134,8 +134,29 @@ def parse_args(argv=None):
                     help="testing_tile_target_bpps, --codec hyperprior or meanscale with --tile: one pass per rate target through compress_tiled_to_rate "
                          "(level prefix tbpp<target>): ONE step per picture is chosen on the GPU so that the whole container, framing "
                          "included, fits floor(R * H * W / 8) bytes.  Composes and refuses as --tile-qsteps does, and does not combine with it")
+    ap.add_argument("--skip-rows", type=int, nargs="+", default=[], metavar="R",
+                    help="testing_skip_rows, --codec hyperprior or meanscale: one pass per value through compress_skip / decompress_skip (level "
+                         "prefix skip<R>): y elements whose scale-table row is below R are not coded and decode as 0 (the mean); R in "
+                         "[0, 64], 0 skips nothing.  Composes with --uint8, --metrics-on-uint8, --workers and --stream-lanes; not with "
+                         "--qsteps, --target-bpp, --coalesce, --tile*, --complexity-levels, --rate-levels or --forward-pass")
     ap.add_argument("--out", required=True)
     args = ap.parse_args(argv)
+    if args.skip_rows:
+        from cbench_basic_amd.utils.skip import check_skip_rows
+        if args.codec not in STEP_CODECS:
+            ap.error("--skip-rows is skip coding of the hyperprior y coder: it needs --codec hyperprior or --codec meanscale")
+        for name, on in (("--qsteps", bool(args.qsteps)), ("--target-bpp", bool(args.target_bpp)), ("--tile-qsteps", bool(args.tile_qsteps)),
+                         ("--tile-target-bpp", bool(args.tile_target_bpp)), ("--coalesce", args.coalesce > 1), ("--tile", args.tile is not None),
+                         ("--tile-overlap", args.tile_overlap is not None), ("--tile-pad", args.tile_pad is not None),
+                         ("--tile-pool", args.tile_pool > 0), ("--complexity-levels", bool(args.complexity_levels)),
+                         ("--rate-levels", bool(args.rate_levels)), ("--forward-pass", args.forward_pass)):
+            if on:
+                ap.error(f"--skip-rows does not combine with {name}: the rows are a knob of compress_skip / decompress_skip alone")
+        try:
+            for r in args.skip_rows:
+                check_skip_rows(r)
+        except ValueError as e:
+            ap.error(f"--skip-rows: {e}")
     for flag, values, other in (("--tile-qsteps", args.tile_qsteps, ("--tile-target-bpp", bool(args.tile_target_bpp))),
                                 ("--tile-target-bpp", args.tile_target_bpp, ("--tile-qsteps", bool(args.tile_qsteps)))):
         if not values:
@@ -281,6 +302,8 @@ def main(argv=None):
             c.decompress_q(c.compress_to_rate(batches[0].to("cuda"), target_bpp=args.target_bpp[0]))
         elif args.qsteps:   # the step kernels' route, and the session's step buffers
             c.decompress_q(c.compress_q(batches[0].to("cuda"), args.qsteps[0]))
+        elif args.skip_rows:   # the compaction's route, and the session's compact buffers
+            c.decompress_skip(c.compress_skip(batches[0].to("cuda"), args.skip_rows[0]))
         else:
             c.decompress(c.compress(batches[0].to("cuda")))
     warm_chunks = []
@@ -308,7 +331,7 @@ def main(argv=None):
                                               num_testing_workers=args.workers, testing_coalesce_items=args.coalesce, testing_tile=args.tile, testing_tile_overlap=args.tile_overlap,
                                               testing_tile_pool=args.tile_pool, testing_tile_pad=args.tile_pad, testing_qsteps=args.qsteps,
                                               testing_target_bpps=args.target_bpp, testing_tile_qsteps=args.tile_qsteps,
-                                              testing_tile_target_bpps=args.tile_target_bpp,
+                                              testing_tile_target_bpps=args.tile_target_bpp, testing_skip_rows=args.skip_rows,
                                               codec_builder=(lambda: presets.seed_synthetic_weights(builders[args.codec](), seed=0)) if args.workers > 1 else None)
     if args.workers > 1 and args.warmup:   # the replicas' one-time costs too, one replica at a time (HIP-graph capture)
         pool = bench._worker_pool(batches[0], batch=max((len(c) for c in warm_chunks), default=None))
